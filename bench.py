@@ -5,13 +5,24 @@ Metric (BASELINE.json): real-time stereo DAB MP2 streams sustained, as frames/s,
 
 Workload
   N = 1 : BASELINE.json configs[1] -- 4096 streams x 48 kHz stereo x 128 kbps, psy model 1, mode 's', full encode
-          (filterbank + psy + allocation + quantise + pack + CRC/ScF-CRC), PCM resident in HBM.  After the timed region
-          (never inside it) the same process also times mode 'j', configs[2] (16384 streams, psy 3) and the
+          (filterbank + psy + allocation + quantise + pack + CRC/ScF-CRC), PCM resident in HBM.  With --full, after the timed
+          region (never inside it) the same process also times mode 'j', configs[2] (16384 streams, psy 3) and the
           PCIe-inclusive rate (pinned host buffers through tlb_encode_host) and reports them under "also".
   N > 1 : BASELINE.json configs[3] -- 16384 streams PER GPU, psy model 3 (131072 streams on 8 GPUs), weak scaling.
   --config 4 (any N): BASELINE.json configs[4] -- per GPU 16384 streams, even 32 kHz mono 64 kbps / odd 48 kHz stereo 192 kbps in ONE
-          batch, psy model 4 as `value`, psy model 2 (its sibling the reference's setter accepts) as `also.configs4_psy2`; both sharded
-          over the N ranks with the same barriers, per-GPU and aggregate rates, an oracle check on every rank.
+          batch, psy model 4 as `value`; with --full also psy model 2 (its sibling the reference's setter accepts) as `also.configs4_psy2`;
+          both sharded over the N ranks with the same barriers, per-GPU and aggregate rates.
+
+Plain run and --full
+  A plain run sets up, warms up, times --steps launches, writes the last timed launch's output if --dump-outputs is given, and prints
+  the line: `value`, `ms_per_step` and what describes the workload.  --full adds everything else, after the timed region: the oracle
+  check of the last launch's output on every rank (`output_check`), the roofline and per-kernel figures with the shader-clock probe
+  (`roofline`), the secondary workloads (`also`; --no-also drops them) and the CPU baseline (`cpu_baseline`; --no-cpu-baseline).
+
+--dump-outputs DIR
+  DIR/frames.npy (DIR/frames_rank<r>.npy per rank when N > 1): the output buffer of the last timed launch, uint8 [slot][stream][out_stride]
+  as the caller of tlb_encode_device receives it, stored as float32.  Above DUMP_BYTES a fixed sample is taken: streams, then slots, drawn
+  by numpy.random.default_rng(DUMP_SEED) and sorted.  The inputs depend on the arguments only, so two builds compare output for output.
 
 A "step" = one launch of the hot path: every stream encodes --frames-per-step consecutive frames (default: 131072 (stream,
 frame) units per launch, i.e. 32 frames at 4096 streams, 8 at 16384; the kernels' ramp-up and tail are paid once per launch).  One process per GPU; streams shard with no data-path collective; RCCL carries only the
@@ -59,6 +70,10 @@ _K = 4.00 / 4.41
 CLASS_COST = {"add_f64": 4.41 * _K, "mul_f64": 4.41 * _K, "fma_f64": 5.20 * _K, "trans_f64": 16.3 * _K, "cvt": 4.3 * _K, "int32": 3.75 * _K, "int64": 4.4 * _K,
               "other": 4.4 * _K}
 FLAT_COST = 3.9                  # no class split committed for the workload: every instruction at the mean cost of the configs[1] mix
+DUMP_BYTES = 32 << 20            # --dump-outputs: at most this many bytes of float32 over all ranks (the contract allows 64 MB)
+DUMP_STREAMS = 512               # ... and at most this many streams per rank
+DUMP_SEED = 0
+HOST_THREADS = 16                # host threads for the PCM generation (numpy releases the GIL); never more than the CPUs this process may use
 
 
 def parse_args(argv=None):
@@ -71,8 +86,12 @@ def parse_args(argv=None):
     ap.add_argument("--config", type=int, default=None, choices=(1, 2, 3, 4), help="BASELINE.json configs[k] (default: 1 at --gpus 1, 3 above)")
     ap.add_argument("--psy", type=int, default=None)
     ap.add_argument("--mode", default="s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the oracle check, roofline and per-kernel figures, the secondary workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed launch's output to DIR/frames.npy (float32; a fixed seeded sample above %d MB)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary measurements after the headline")
     ap.add_argument("--dry-run", action="store_true", help="CPU emulation over gloo: plumbing check only, not a measurement")
     ap.add_argument("--force-group", action="store_true",
                     help="build the process group even at world size 1, so that init_process_group / barrier / all_reduce / all_gather run through the "
@@ -126,6 +145,26 @@ def stream_configs(M, S, psy, mode, mixed):
 def algo_bytes(c):
     """PCM in + bitstream out per frame of configuration c"""
     return (1 if c.mode == "m" else 2) * 1152 * 2 + 144000 * c.bitrate // c.samplerate
+
+
+def dump_index(F, S, stride, world=1):
+    """--dump-outputs: (slots, streams) of the [F][S][stride] output buffer to store, both sorted; the whole buffer when it fits
+    DUMP_BYTES / world as float32, else a sample drawn by numpy.random.default_rng(DUMP_SEED) -- the same for the same arguments"""
+    import numpy as np
+    budget = DUMP_BYTES // 4 // world
+    rng = np.random.default_rng(DUMP_SEED)
+    ns = int(min(S, DUMP_STREAMS, max(1, budget // (F * stride))))
+    streams = np.arange(S) if ns == S else np.sort(rng.choice(S, ns, replace=False))
+    nf = int(min(F, max(1, budget // (ns * stride))))
+    slots = np.arange(F) if nf == F else np.sort(rng.choice(F, nf, replace=False))
+    return slots, streams
+
+
+def host_threads():
+    try:
+        return max(1, min(HOST_THREADS, len(os.sched_getaffinity(0))))
+    except AttributeError:
+        return 1
 
 
 def workload_label(streams, psy, mode, frames_per_step, world, mixed=False):
@@ -362,14 +401,18 @@ class GpuRun:
     batch, the output buffer.  step(i) = one launch."""
 
     def __init__(self, M, torch, np, gen_pcm, stream_ids, F, mode, psy, local_rank, distinct=None, mixed=False):
+        from concurrent.futures import ThreadPoolExecutor
         S = len(stream_ids)
         host = np.empty((2 * F, S, 2, 1152), dtype=np.int16)
         nd = S if distinct is None else min(S, distinct)
-        for k, sid in enumerate(stream_ids[:nd]):     # stream i uses seed i (SURVEY 8d)
-            host[:, k] = gen_pcm(sid, 0, 0, 2 * F)
+
+        def fill(k):                                  # stream i uses seed i (SURVEY 8d)
+            host[:, k] = gen_pcm(stream_ids[k], 0, 0, 2 * F)
+        with ThreadPoolExecutor(host_threads()) as ex:
+            list(ex.map(fill, range(nd)))
         for k in range(nd, S, nd):                    # secondary workloads only: the signals repeat every `distinct` streams
             host[:, k:k + nd] = host[:, :min(nd, S - k)]
-        self.pcm = [torch.from_numpy(host[:F].copy()).cuda(), torch.from_numpy(host[F:].copy()).cuda()]
+        self.pcm = [torch.from_numpy(host[:F]).cuda(), torch.from_numpy(host[F:]).cuda()]
         self.check_streams = sorted({0, S - 1})
         self.check_pcm = {k: host[:, k].copy() for k in self.check_streams}      # the 2F frames stream k loops over
         self.launches = 0
@@ -381,7 +424,7 @@ class GpuRun:
         self.stream = torch.cuda.current_stream()
         self.F, self.S, self.torch, self.np = F, S, torch, np
         self.cdev = "cuda"
-        self.dev, self.sclk_mhz = local_rank, None
+        self.dev, self.sclk_mhz, self.stage_ms, self.kept = local_rank, None, None, None
         self.pci = device_identity(torch, local_rank).get("pci_bus_id")
 
     def step(self, i):
@@ -389,12 +432,14 @@ class GpuRun:
         self.batch.encode_device(self.pcm[i & 1].data_ptr(), self.F, self.out.data_ptr(), stream=self.stream.cuda_stream)
         self.launches += 1
 
-    def timed(self, dist, shard, warmup, steps):
-        """-> (max-over-ranks seconds, own seconds, mean kernel ms from HIP events on the launch stream)"""
+    def timed(self, dist, shard, warmup, steps, full=True, keep=None):
+        """-> (max-over-ranks seconds, own seconds, mean kernel ms from HIP events on the launch stream; None unless `full`).
+        keep = (slots, streams): self.kept = that part of the last timed launch's output, float32 on the host, taken before
+        anything else is launched"""
         torch = self.torch
         for i in range(warmup):
             self.step(i)
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)] if full else []
 
         def run():
             for i in range(steps):
@@ -402,7 +447,16 @@ class GpuRun:
                 self.step(warmup + i)
                 evs[i][1].record(self.stream)
 
-        elapsed, own = shard.timed_region_detail(dist, run, device_sync=torch.cuda.synchronize, device=self.cdev)
+        def run_plain():
+            for i in range(steps):
+                self.step(warmup + i)
+
+        elapsed, own = shard.timed_region_detail(dist, run if full else run_plain, device_sync=torch.cuda.synchronize, device=self.cdev)
+        if keep is not None:
+            ix = [torch.as_tensor(a, dtype=torch.long, device=self.out.device) for a in keep]
+            self.kept = self.out.index_select(0, ix[0]).index_select(1, ix[1]).cpu().numpy().astype(self.np.float32)
+        if not full:
+            return elapsed, own, None
         kernel_ms = float(self.np.mean([a.elapsed_time(b) for a, b in evs]))
         self.stage_ms = self.batch.last_stage_ms()      # (psy-2 kernel, encode + finish kernels) of the last launch: batches of models 2/4 only
         # the shader clock under this load: an untimed probe of the same launches, AFTER the region (an even number: the buffers keep alternating)
@@ -623,6 +677,8 @@ def main():
     t0 = time.time()
 
     if args.dry_run:
+        if args.dump_outputs is not None:
+            raise SystemExit("bench.py: --dump-outputs writes what the GPU path computed; --dry-run has none")
         return dry_run(args, shard, np, gen_pcm, world, S if args.streams is not None else 2, psy, min(F, 2))
 
     if not torch.cuda.is_available():
@@ -646,22 +702,30 @@ def main():
     devices_seen, n_distinct = observed_devices(shard, dist, device_identity(torch, dev_index), cdev, time.time() - t0)
     num_simds = 4 * torch.cuda.get_device_properties(dev_index).multi_processor_count
 
-    def sharded_run(psy_k):
-        """one workload on every rank: timed region between barriers, the oracle check on EVERY rank (its verdict travels as a flag
-        with the gathered floats: a rank whose check fails still takes part in the collectives), per-rank (frames, seconds)"""
+    def sharded_run(psy_k, dump=False):
+        """one workload on every rank: timed region between barriers, per-rank (frames, seconds); with --full the oracle check on EVERY
+        rank (its verdict travels as a flag with the gathered floats: a rank whose check fails still takes part in the collectives)"""
         r = GpuRun(M, torch, np, gen_pcm, shard.weak_stream_ids(rank, S), F, args.mode, psy_k, local_rank, mixed=mixed)
         r.cdev = cdev
-        el, own_s, k_ms = r.timed(dist, shard, args.warmup, args.steps)
-        l_ms = r.batch.last_kernel_ms()
-        chk = r.check_flag()
+        keep = dump_index(F, S, r.batch.out_stride, world) if dump else None
+        el, own_s, k_ms = r.timed(dist, shard, args.warmup, args.steps, full=args.full, keep=keep)
+        if dump:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            name = "frames.npy" if world == 1 else f"frames_rank{rank}.npy"
+            np.save(os.path.join(args.dump_outputs, name), r.kept)
+            dumped = {"files": [name], "shape": list(r.kept.shape), "dtype": "float32", "stride": r.batch.out_stride,
+                      "sample": "whole buffer" if r.kept.shape[:2] == (F, S) else
+                                f"streams, then slots, drawn by numpy.random.default_rng({DUMP_SEED}) (bench.dump_index), sorted"}
+        l_ms = r.batch.last_kernel_ms() if args.full else None
+        chk = r.check_flag() if args.full else {"checked": False, "why": "plain run: the oracle check runs with --full"}
         pr = shard.gather_floats(dist, [S * F * args.steps, own_s, 0.0 if chk.get("failed") else 1.0], device=cdev)
         out = dict(elapsed=el, kernel_ms=k_ms, last_ms=l_ms, checked=chk, per_rank=pr, stage_ms=r.stage_ms,
-                   algo=r.algo_bytes_per_launch, audio_s=r.audio_s_per_launch, sclk=r.sclk_mhz)
+                   algo=r.algo_bytes_per_launch, audio_s=r.audio_s_per_launch, sclk=r.sclk_mhz, dumped=dumped if dump else None)
         r.close()
         return out
 
-    head = sharded_run(psy)
-    sib = sharded_run(2) if mixed and psy == 4 else None         # configs[4]: psy 2 next to psy 4, on every rank too
+    head = sharded_run(psy, dump=args.dump_outputs is not None)
+    sib = sharded_run(2) if args.full and mixed and psy == 4 else None         # configs[4]: psy 2 next to psy 4, on every rank too
     elapsed, kernel_ms, last_ms, checked, per_rank, run_stage_ms = (head[k] for k in ("elapsed", "kernel_ms", "last_ms", "checked", "per_rank", "stage_ms"))
     if dist is not None:          # nothing below is collective: the ranks part here, rank 0 goes on to its host-side legs alone
         dist.destroy_process_group()
@@ -735,18 +799,7 @@ def main():
     if rank == 0:
         frames = sum(int(p[0]) for p in per_rank)
         value = frames / elapsed
-        pk = "tl_psy2_kernel" if psy in (2, 4) else None
-        kname = (f"{pk} + tl_main_kernel<2> + tl_finish_kernel (the three kernels of one launch of the path)" if pk
-                 else "tl_main_kernel<0> + tl_finish_kernel (model 0 has no psy kernel)" if psy == 0
-                 else f"tl_frame_kernel<{psy}> (psy model, then encoder, per (stream, frame) unit) + tl_finish_kernel")
-        kernels = None
-        if pk and run_stage_ms:
-            kernels = {pk: round(run_stage_ms[0], 4), "tl_main_kernel + tl_finish_kernel": round(run_stage_ms[1], 4),
-                       "source": "hipEvents on the launch stream inside the library (tlb_last_stage_ms), last timed launch"}
         label, cfg_k = workload_label(S, psy, args.mode, F, world, mixed)
-        rf = roofline(head, S, F, psy, args.mode)
-        rf.update({"kernel": kname, "kernels_ms": kernels})
-        checked["per_rank_ok"] = [p[2] == 1.0 for p in per_rank]
         res = {
             "metric": "real-time stereo DAB MP2 streams sustained (frames/s) @128 kbps/48 kHz" if not mixed else
                       "real-time DAB MP2 streams sustained (frames/s), BASELINE configs[4]: 32 kHz mono 64 kbps + 48 kHz stereo 192 kbps interleaved",
@@ -760,10 +813,22 @@ def main():
             "devices_observed": devices_seen, "distinct_devices_observed": n_distinct,
             "world_size_observed": observed_world, "collective_backend": ("rccl (torch.distributed nccl)" if args.backend == "nccl" else "gloo (smoke test: ranks may share GPUs)") if had_group else None,
             "per_gpu_frames_per_s": [round(p[0] / p[1], 1) for p in per_rank],
-            "roofline": rf,
-            "lds_bytes_per_stream": M.lds_bytes_per_stream(),
-            "output_check": checked,
         }
+        if head["dumped"] is not None:
+            res["dump_outputs"] = dict(head["dumped"], dir=args.dump_outputs)
+    if rank == 0 and args.full:
+        pk = "tl_psy2_kernel" if psy in (2, 4) else None
+        kname = (f"{pk} + tl_main_kernel<2> + tl_finish_kernel (the three kernels of one launch of the path)" if pk
+                 else "tl_main_kernel<0> + tl_finish_kernel (model 0 has no psy kernel)" if psy == 0
+                 else f"tl_frame_kernel<{psy}> (psy model, then encoder, per (stream, frame) unit) + tl_finish_kernel")
+        kernels = None
+        if pk and run_stage_ms:
+            kernels = {pk: round(run_stage_ms[0], 4), "tl_main_kernel + tl_finish_kernel": round(run_stage_ms[1], 4),
+                       "source": "hipEvents on the launch stream inside the library (tlb_last_stage_ms), last timed launch"}
+        rf = roofline(head, S, F, psy, args.mode)
+        rf.update({"kernel": kname, "kernels_ms": kernels})
+        checked["per_rank_ok"] = [p[2] == 1.0 for p in per_rank]
+        res.update({"roofline": rf, "lds_bytes_per_stream": M.lds_bytes_per_stream(), "output_check": checked})
         if sib is not None:
             sib["checked"]["per_rank_ok"] = [p[2] == 1.0 for p in sib["per_rank"]]
             res["also"] = {"configs4_psy2": {
@@ -771,8 +836,8 @@ def main():
                 "unit": "frames/s", "per_gpu_frames_per_s": [round(p[0] / p[1], 1) for p in sib["per_rank"]], "ms_per_step": round(sib["elapsed"] / args.steps * 1e3, 4),
                 "realtime_streams": round(sib["audio_s"] * world * args.steps / sib["elapsed"], 1), "roofline": roofline(sib, S, F, 2, args.mode),
                 "output_check": sib["checked"]}}
-    # ---- secondary measurements, after (outside) the headline's timed region; single GPU only ----
-    if world == 1 and not args.no_also and not mixed:
+    # ---- secondary measurements (--full), after (outside) the headline's timed region; single GPU only ----
+    if args.full and world == 1 and not args.no_also and not mixed:
         also = {}
         F2 = max(1, 131072 // CONFIGS[2][0])        # 16384 streams x 8 frames = 604 MB of PCM per buffer
         # encoder_only_psy0: BASELINE configs[1] names "filterbank+quantise kernels only" -- that is the encoder without a psychoacoustic
@@ -886,7 +951,7 @@ def main():
         if had_group:
             res["collectives_executed"] = ["init_process_group(device_id)", "barrier", "all_reduce(MAX)", "all_gather"]
         res["setup_s"] = round(time.time() - t0, 1)
-        if not args.no_cpu_baseline:         # rank 0's host cores, after every rank's timed region (N > 1: the configs[3] model, psy 3)
+        if args.full and not args.no_cpu_baseline:         # rank 0's host cores, after every rank's timed region (N > 1: the configs[3] model, psy 3)
             res["cpu_baseline"] = cpu_baseline(psy, args.mode)
         else:
             res["cpu_baseline"] = None

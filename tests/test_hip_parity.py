@@ -1178,7 +1178,7 @@ def test_bench_two_ranks_on_the_gpu():
     import subprocess
     import sys
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--no-also",
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--full", "--no-also",
                         "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1202,7 +1202,7 @@ def test_bench_configs4_two_ranks_on_the_gpu():
     import sys
     root = Path(__file__).resolve().parent.parent
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--config", "4", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--streams", "4096", "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=900)
+                        "--streams", "4096", "--full", "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["world_size_observed"] == 2 and line["config"]["baseline_config"] == 4 and "configs[4]" in line["config"]["workload"]

@@ -229,7 +229,7 @@ def test_bench_forced_rccl_group_on_one_gpu():
     """the `nccl` branch of the harness -- init_process_group("nccl", device_id=...), barrier, all_reduce(MAX),
     all_gather on DEVICE tensors -- executed through RCCL on the MI355X, as a one-rank group (`--force-group`).  An 8-GPU driver
     run then repeats with more ranks what has already run once."""
-    line = _bench("--gpus", "1", "--backend", "nccl", "--force-group", "--steps", "3", "--warmup", "1", "--no-also", "--no-cpu-baseline")
+    line = _bench("--gpus", "1", "--backend", "nccl", "--force-group", "--steps", "3", "--warmup", "1", "--full", "--no-also", "--no-cpu-baseline")
     assert line["collective_backend"].startswith("rccl") and line["world_size_observed"] == 1 and line["n_gpus"] == 1
     assert line["collectives_executed"] == ["init_process_group(device_id)", "barrier", "all_reduce(MAX)", "all_gather"]
     assert line["value"] > 0 and line["output_check"]["checked"] and line["output_check"]["per_rank_ok"] == [True]
@@ -242,6 +242,36 @@ def test_bench_forced_rccl_group_on_one_gpu():
     print("devices_observed:", dev)
     assert len(dev) == 1 and line["distinct_devices_observed"] == 1 and dev[0]["name"] and (dev[0].get("pci_bus_id") or dev[0].get("uuid")), dev
     assert dev[0]["compute_units"] == 256
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run: the headline alone (no oracle check, roofline, secondary workloads or CPU baseline in the line), `steps`
+    timed launches, and with --dump-outputs the last timed launch's output buffer as float32 -- its sampled slots byte for byte the
+    oracle's frames of the same looped PCM (slot f of launch L holds global frame (L - 1) * F + f - 1)."""
+    import sys
+    from pathlib import Path
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    import bench
+    steps, warmup = 3, 1
+    line = _bench("--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["dtype"] == "f64"
+    assert not any(k in line for k in ("also", "roofline", "output_check")) and line["cpu_baseline"] is None
+    S, F = line["config"]["streams_per_gpu"], line["config"]["frames_per_step"]
+    got = np.load(tmp_path / "frames.npy")
+    stride = line["dump_outputs"]["stride"]
+    slots, streams = bench.dump_index(F, S, stride)
+    assert got.dtype == np.float32 and got.shape == (len(slots), len(streams), stride) and got.nbytes <= 64 << 20
+    assert np.all(got == np.round(got)) and got.min() >= 0 and got.max() <= 255
+    launches = warmup + steps
+    for j in (0, len(streams) - 1):
+        sid = int(streams[j])
+        ref = O.oracle_stream(np.concatenate([gen_pcm(sid, 0, 0, 2 * F)] * (launches // 2 + 1))[:launches * F],
+                              samplerate=48000, mode="s", kbps=128, psy=1)[0]
+        for i, f in enumerate(slots):
+            g = (launches - 1) * F + int(f) - 1
+            assert bytes(got[i, j, :384].astype(np.uint8)) == ref[g * 384:(g + 1) * 384], (sid, int(f))
 
 
 def test_bench_in_process_node_two_shards_on_the_gpu():

@@ -159,6 +159,31 @@ def test_bench_workload_labels():
     assert "mono, two streams per wave" in bench.workload_label(4096, 1, "m", 32, 1)[0]
     a = bench.parse_args(["--gpus", "8"])
     assert a.gpus == 8 and a.streams is None and a.psy is None
+    assert a.full is False and a.dump_outputs is None          # a plain run: the headline only, nothing written
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_bench_dump_index_is_fixed_and_bounded():
+    """--dump-outputs: the sample of the output buffer depends on the arguments only, stays within the contract's 64 MB of float32
+    over all ranks, and is the whole buffer when that fits"""
+    sys.path.insert(0, str(ROOT))
+    import numpy as np
+    import bench
+    for F, S, stride, world in ((32, 4096, 384, 1), (8, 16384, 576, 1), (1, 131072, 384, 1), (8192, 1, 384, 1), (100000, 1, 576, 1),
+                                (8, 16384, 384, 8), (4, 6, 384, 1)):
+        slots, streams = bench.dump_index(F, S, stride, world)
+        again = bench.dump_index(F, S, stride, world)
+        assert np.array_equal(slots, again[0]) and np.array_equal(streams, again[1])
+        assert len(slots) >= 1 and len(streams) >= 1 and len(streams) <= bench.DUMP_STREAMS
+        assert np.all(np.diff(slots) > 0) and np.all(np.diff(streams) > 0) and slots[-1] < F and streams[-1] < S
+        assert len(slots) * len(streams) * stride * 4 * world <= 64 << 20, (F, S, stride, world)
+    slots, streams = bench.dump_index(4, 6, 384)
+    assert list(slots) == list(range(4)) and list(streams) == list(range(6))
+    a = bench.parse_args(["--dry-run", "--dump-outputs", "x"])
+    assert a.dry_run and a.dump_outputs == "x"
+    r = _run_bench(["--dry-run", "--steps", "1", "--dump-outputs", str(ROOT / "never_written")])
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (ROOT / "never_written").exists()
 
 
 def test_forced_one_rank_group_runs_the_collectives():

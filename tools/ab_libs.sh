@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for r in 1 2 3; do
   for L in "$@"; do
     if [ "$L" = default ]; then unset TLB_LIB_PATH; else export TLB_LIB_PATH=$PWD/$L; fi
-    python3 bench.py --no-also --no-cpu-baseline --steps 100 --warmup 10 $ARGS 2>/dev/null | tail -1 | python3 -c "
+    python3 bench.py --full --no-also --no-cpu-baseline --steps 100 --warmup 10 $ARGS 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$L', 'round $r', d['value'], 'frames/s', d['roofline']['kernel_ms'], 'ms', d['output_check'].get('checked'))"
   done
