@@ -420,15 +420,19 @@ TL_FN TlPsy1Ch tl_psy1_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const d
     return r;
 }
 
-// weight sums of the bands (psycho_1.c:364-366), ascending line order; lane b < nbands owns band b.  Only used where the
-// weights cannot ride along with the dB-sum chain (channel 0 of a stereo frame, whose terms leave LDS before its chain runs).
-TL_FN void tl_psy1_weights(TlPsyLds &w, int nbands, PARG(double, wt))
+// weight sums of the bands (psycho_1.c:364-366) of BOTH channels of a stereo frame, ascending line order: lanes 0..31 sum channel 0's
+// terms (put back at TL_PX, ranges in r0/r1), lanes 32..63 channel 1's (at fft[], ranges from bandoff[]).  Result: lane b holds
+// channel 0's weight, lane 32+b channel 1's.  (The weights cannot ride along with the paired dB-sum chains: levels and terms of two
+// channels do not fit the LDS arrays at once.)
+TL_FN void tl_psy1_weights2(TlPsyLds &w, int nbands, PARG(int, r0), PARG(int, r1), PARG(double, wt))
 {
     TL_LANES_BEGIN
     double weight = 0.0;
-    if (lane < nbands) {
-        const double *vt = w.u.fft;
-        const int i0 = w.bandoff[lane], i1 = w.bandoff[lane + 1];
+    const int band = lane & 31;
+    if (band < nbands) {
+        const bool second = lane >= 32;
+        const double *vt = second ? w.u.fft : TL_PX(w);
+        const int i0 = second ? (int)w.bandoff[band] : L(r0), i1 = second ? (int)w.bandoff[band + 1] : L(r1);
         int i = i0;
         for (; i + 16 <= i1; i += 16) {                             // sixteen operands per LDS round trip, summed in order
             double t[16];
@@ -840,10 +844,11 @@ TL_FN void tl_psy1(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double *TL_
     tl_psy1_finish(w, db, C, ch, st, rec, sp);
 }
 
-// Both channels of a stereo frame.  Order: front(0) -> park channel 0's front results in registers -> front(1) -> the dB-sum
-// chains of both channels side by side -> back(1) -> channel 0's results return to the LDS arrays -> back(0).
-// Parked: the compacted levels (<= 466 doubles: 8 per lane), the tone records (conf_c, tlist, tone_x), the spike levels, the
-// band ranges and the weight sums.  ptype[] is not parked: after the tone labelling a line is TONE exactly if it is the line
+// Both channels of a stereo frame.  Order: front(0) -> park channel 0's front results in registers -> front(1) -> the weight
+// sums of both channels side by side -> the dB-sum chains of both channels side by side -> back(1) -> channel 0's results
+// return to the LDS arrays -> back(0).
+// Parked: the compacted levels and weight terms (<= 466 doubles each: 8 per lane), the tone records (conf_c, tlist, tone_x), the
+// band ranges.  ptype[] is not parked: after the tone labelling a line is TONE exactly if it is the line
 // of a confirmed tone that was not erased by its successor, so it is rebuilt from conf_c.  A dead-head channel (see
 // tl_psy1_front) falls back to the plain per-channel order.
 TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double *TL_RESTRICT db,
@@ -858,16 +863,19 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
         return;
     }
     // ---- park channel 0 ----
-    PV(double, wt0); PV(int, r0); PV(int, r1);
-    PA(double, pvp, 8); PV(int, pcc); PV(int, ptl); PV(double, ptx0); PV(double, ptx1);
-    if (TL_EXP_LEVEL < 3) tl_psy1_weights(w, nbands, wt0);
+    PV(int, r0); PV(int, r1);
+    PA(double, pvp, 8); PA(double, pvt, 8); PV(int, pcc); PV(int, ptl); PV(double, ptx0); PV(double, ptx1);
     TL_LANES_BEGIN
     L(r0) = lane < nbands ? (int)w.bandoff[lane] : 0; L(r1) = lane < nbands ? (int)w.bandoff[lane + 1] : 0;
-    const double *vp = TL_PX(w);
+    const double *vp = TL_PX(w), *vt = w.u.fft;
 #ifndef TL_EMULATE
 #pragma unroll
 #endif
     for (int k = 0; k < 8; k++) L(pvp)[k] = lane + 64 * k < 504 ? vp[lane + 64 * k] : 0.0;
+#ifndef TL_EMULATE
+#pragma unroll
+#endif
+    for (int k = 0; k < 8; k++) L(pvt)[k] = lane + 64 * k < 504 ? vt[lane + 64 * k] : 0.0;
     const int hi = 64 + lane < TL_TONE_MAX ? 64 + lane : 0;
     L(pcc) = (int)((uint32_t)(uint16_t)w.conf_c[lane] | ((uint32_t)(uint16_t)w.conf_c[hi] << 16));
     L(ptl) = (int)((uint32_t)(uint16_t)w.tlist[lane] | ((uint32_t)(uint16_t)w.tlist[hi] << 16));
@@ -875,7 +883,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     TL_LANES_END
     // ---- channel 1's front; a dead-head channel 1 is finished in the plain order first ----
     const TlPsy1Ch s1 = tl_psy1_front(w, T, db, C, pv, 1, rec, sp1);
-    PV(double, bsum); PV(double, wt1); PV(int, blo); PV(int, bhi);
+    PV(double, bsum); PV(double, wt); PV(int, blo); PV(int, bhi);
     tl_psy1_limits(C, nbands, blo, bhi);                              // (used after the chains, by both channels' centres)
     if (s1.dead_head) {
         tl_psy1_finish(w, db, C, 1, s1, rec, sp1);
@@ -883,7 +891,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
 #ifndef TL_EMULATE
 #pragma unroll
 #endif
-        for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) TL_PX(w)[lane + 64 * k] = L(pvp)[k];
+        for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) { TL_PX(w)[lane + 64 * k] = L(pvp)[k]; w.u.fft[lane + 64 * k] = L(pvt)[k]; }
         if (lane <= nbands) w.bandoff[lane] = (int16_t)(lane < nbands ? L(r0) : 0);
         TL_LANES_END
         // bandoff[nbands] = end of the last band
@@ -891,30 +899,37 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
             const int last_end = TL_READLANE_I32(r1, nbands - 1);
             TL_LANES_BEGIN if (lane == 0) w.bandoff[nbands] = (int16_t)last_end; TL_LANES_END
         }
-        PV(double, wdummy);
-        // the weight terms are gone; tl_psy1_chain's weight output is ignored (the parked sums are used)
-        TL_LANES_BEGIN
-        for (int i = lane; i < 504; i += 64) { uint64_t z = 0; TL_KEEP(z); w.u.fft[i] = tl_u2d(z); }   // (a zero made here, not a register kept through the frame)
-        TL_LANES_END
-        TL_PRIO(1); tl_psy1_chain(w, db, nbands, bsum, wdummy); TL_PRIO(0);
+        // channel 0's levels and weight terms are back where its front left them: its chain sums both, as for one channel
+        TL_PRIO(1); tl_psy1_chain(w, db, nbands, bsum, wt); TL_PRIO(0);
     } else {
-        // ---- both chains: channel 1's weight sums first (its terms sit where channel 0's levels go) ----
-        if (TL_EXP_LEVEL < 3) tl_psy1_weights(w, nbands, wt1);
+        // ---- both channels' weight sums on the two halves: channel 0's terms go where channel 1's levels are (swapped through the
+        //      registers that held them), then the levels of both channels take the places the chains read them from ----
         TL_LANES_BEGIN
 #ifndef TL_EMULATE
 #pragma unroll
 #endif
-        for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) w.u.fft[lane + 64 * k] = L(pvp)[k];
+        for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) {
+            const double v = TL_PX(w)[lane + 64 * k];
+            TL_PX(w)[lane + 64 * k] = L(pvt)[k]; L(pvt)[k] = v;         // pvt: channel 1's levels from here on
+        }
+        TL_LANES_END
+        if (TL_EXP_LEVEL < 3) tl_psy1_weights2(w, nbands, r0, r1, wt);
+        TL_LANES_BEGIN
+#ifndef TL_EMULATE
+#pragma unroll
+#endif
+        for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) { w.u.fft[lane + 64 * k] = L(pvp)[k]; TL_PX(w)[lane + 64 * k] = L(pvt)[k]; }
         TL_LANES_END
         TL_STAMP(sp1, 4);
         if (TL_EXP_LEVEL < 3) { TL_PRIO(1); tl_psy1_chain2(w, db, nbands, r0, r1, bsum); TL_PRIO(0); }
         TL_STAMP(sp0, 4);                                               // both channels' chains: sp1[4] -> sp0[4]
-        // ---- back(1): its sums move from lanes 32+b to lanes b ----
-        PV(double, bsum1);
+        // ---- back(1): its sums and weights move from lanes 32+b to lanes b ----
+        PV(double, bsum1); PV(double, wt1);
 #ifdef TL_EMULATE
-        for (int lane = 0; lane < 64; ++lane) bsum1[lane] = bsum[(lane + 32) & 63];
+        for (int lane = 0; lane < 64; ++lane) { bsum1[lane] = bsum[(lane + 32) & 63]; wt1[lane] = wt[(lane + 32) & 63]; }
 #else
         bsum1 = __shfl(bsum, (int)((threadIdx.x + 32u) & 63u), 64);
+        wt1 = __shfl(wt, (int)((threadIdx.x + 32u) & 63u), 64);
 #endif
         if (TL_EXP_LEVEL < 3) tl_psy1_centres(w, nbands, bsum1, wt1, blo, bhi);
         tl_psy1_back(w, db, C, 1, s1, rec, sp1, false);
@@ -929,7 +944,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     TL_LANES_BEGIN
     for (int i = lane; i < s0.nconf; i += 64) { const int cc = w.conf_c[i]; if (!((cc >> 13) & 1)) w.ptype[cc & 511] = TL_T_TONE; }
     TL_LANES_END
-    if (TL_EXP_LEVEL < 3) tl_psy1_centres(w, nbands, bsum, wt0, blo, bhi);
+    if (TL_EXP_LEVEL < 3) tl_psy1_centres(w, nbands, bsum, wt, blo, bhi);
     tl_psy1_back(w, db, C, 0, s0, rec, sp0, s1.dead_head);
 }
 
