@@ -10,10 +10,12 @@
 //   two ticks are kept in flight: while tick t's packets are shipped, tick t+1 is on the GPUs and tick t+2's PCM is being filled.
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
-// usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af]
+// usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
 //   in.s16le: interleaved stereo 48 kHz; stream s starts reading at frame s (so the services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
 //   -o: the AF packets of the LAST stream of the node, length-prefixed (uint32 LE) -- the stream farthest from shard 0.
+//   --deadline-ms: the node's tick deadline (include/toolame_batch.h, TICK DEADLINE): a shard that misses it goes off air on its own
+//   while the others tick on, and comes back by itself; each shard's late / missed / dropped counts go to stderr at the end.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -45,8 +47,8 @@ static void fill(void *vctx, int g, int first, int n)
     Ctx &c = *(Ctx *)vctx;
     for (int s = first; s < first + n; s++) {
         int16_t *dst = tlb_node_pcm(c.nd, s);
-        if (!dst) {                                              // a BROKEN shard takes no input (its block is off air until it is restarted); anything else is a bug
-            if (tlb_node_shard_status(c.nd, g, nullptr) == TLB_SHARD_BROKEN) return;
+        if (!dst) {                                              // a BROKEN or LATE shard takes no input (its block is off air until it is back); anything else is a bug
+            if (tlb_node_shard_status(c.nd, g, nullptr) != TLB_SHARD_OK) return;
             die("no input set free", s);
         }
         const size_t f = ((size_t)s + (size_t)c.tick) % c.nframes_in;
@@ -75,10 +77,11 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]\n", argv[0]);
         return 2;
     }
     int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1;
+    double deadline_ms = 0;
     std::string devs, outpath;
     for (int i = 2; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
@@ -90,6 +93,7 @@ int main(int argc, char **argv)
         else if (k == "-b") kbps = std::atoi(v);
         else if (k == "-p") psy = std::atoi(v);
         else if (k == "-o") outpath = v;
+        else if (k == "--deadline-ms") { deadline_ms = std::atof(v); if (!(deadline_ms > 0)) die("--deadline-ms wants a positive number", 0); }
         else die("unknown option", 0);
     }
     const int ndev = tlb_device_count();
@@ -133,6 +137,8 @@ int main(int argc, char **argv)
     int err = 0;
     tlb_node *nd = tlb_node_create(G, devices.data(), nstreams, cfg.data(), &nc, &err);
     if (!nd) die("tlb_node_create", err);
+    if (deadline_ms > 0)
+        if (int rc = tlb_node_set_deadline_ms(nd, deadline_ms)) die("tlb_node_set_deadline_ms", rc);
 
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
@@ -155,15 +161,20 @@ int main(int argc, char **argv)
     // A GPU that fails takes ITS block off air, not the node (include/toolame_batch.h, FAULT ISOLATION): the call in which a shard
     // breaks returns its code, every other shard has completed the call.  The caller's part: find out which shard, log why, restart it
     // when no tick is in flight -- the reference's "restart the failed input, nothing else stops" (src/odr-audioenc.cpp:875-902) one level up.
+    // With --deadline-ms a shard whose tick does not complete in time goes LATE: the call returns TLB_ERR_LATE, the shard is off air
+    // (skipped, NULL accessors) and comes back by itself at a later wait once its tick has returned; a late job that returns an error
+    // leaves the shard broken, handled as above.
     long restarts = 0;
     auto shard_failed = [&](const char *where, int rc) {
         int alive = 0;
         for (int g = 0; g < G; g++) {
             tlb_node_shard_info info;
-            if (tlb_node_shard_status(nd, g, &info) == TLB_SHARD_BROKEN) std::fprintf(stderr, "nodetick: %s: shard %d on %s is down (%s)\n", where, g, info.device_name, info.what);
+            const int st = tlb_node_shard_status(nd, g, &info);
+            if (st == TLB_SHARD_BROKEN) std::fprintf(stderr, "nodetick: %s: shard %d on %s is down (%s)\n", where, g, info.device_name, info.what);
+            else if (st == TLB_SHARD_LATE) { std::fprintf(stderr, "nodetick: %s: shard %d on %s is late (missed the %.1f ms deadline)\n", where, g, info.device_name, deadline_ms); alive++; }
             else alive++;
         }
-        if (!alive) die(where, rc);                                       // nobody left: nothing to carry on with
+        if (!alive) die(where, rc);                                       // nobody left: nothing to carry on with (a late shard may come back)
     };
     const auto t0 = std::chrono::steady_clock::now();
     // fill 0, submit 0; then per tick: fill t+1, submit t+1, wait t, ship t
@@ -202,6 +213,13 @@ int main(int argc, char **argv)
         all ^= hash[(size_t)g] + 0x9e3779b97f4a7c15ull * (uint64_t)(g + 1);
         npk += packets[(size_t)g]; nby += bytes[(size_t)g];
     }
+    if (deadline_ms > 0)
+        for (int g = 0; g < G; g++) {
+            tlb_node_shard_deadline dl;
+            tlb_node_shard_deadline_status(nd, g, &dl);
+            std::fprintf(stderr, "nodetick: shard %d: late_events %ld, missed_steps %ld, dropped_steps %ld (rejoins %ld, worst overrun %.1f ms)\n", g,
+                         dl.late_events, dl.missed_steps, dl.dropped_steps, dl.rejoins, dl.worst_overrun_ms);
+        }
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",
                 nstreams, G, ticks, tot.frames, npk, nby, sec, sec > 0 ? tot.frames / sec : 0.0, sec > 0 ? ticks * 0.024 / sec : 0.0);

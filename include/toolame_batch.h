@@ -56,6 +56,7 @@ enum {
     TLB_ERR_NO_DEVICE = 16,
     TLB_ERR_HIP = 17,
     TLB_ERR_ARG = 18,
+    TLB_ERR_LATE = 19,             /* node level, TICK plane with a deadline set: a shard missed it (tlb_node_set_deadline_ms) */
 };
 
 /* The six knobs odr-audioenc sets (src/odr-audioenc.cpp:687-722), per stream. */
@@ -345,6 +346,35 @@ float tlb_tick_last_ms(tlb_tick *t);           /* first copy-in queued -> last c
  * the streams have NOW and the caller's gains; it joins the lockstep at the next submit (first tick: nothing out, one frame of
  * latency).  Restart is legal between steps (no tick in flight / after tlb_node_sync), also on a healthy shard.
  *
+ * TICK DEADLINE.  The above covers a device call that RETURNS an error; a call that does not return would hold up every shard, because
+ * each node-wide call waits for all of them.  tlb_node_set_deadline_ms(ms > 0) bounds that wait on the TICK plane (the reference puts
+ * its own wall-clock limits at this level of its loop: the underrun abort, src/odr-audioenc.cpp:925-931, and the silence timeout,
+ * :1064-1079).  Off (0) by default; then nothing below applies and every call behaves as without the deadline.
+ *   Deadline points.  tlb_node_wait: the node-level submit time of the step waited for, plus ms (the real-time budget runs from
+ *   submit).  tlb_node_submit / tlb_node_finish: call start plus ms.  tlb_node_run is submit followed by wait.
+ *   Going late.  A shard whose part of the call has not returned by its deadline becomes LATE (TLB_SHARD_LATE): the call returns
+ *   TLB_ERR_LATE -- unless a shard broke in the same call, whose code then wins as above -- and the other shards' results of the call
+ *   are readable.  Its job keeps running on its own thread; nothing is cancelled.
+ *   While LATE.  Every node-wide call skips the shard (submit, wait, finish, set_gain_db(-1), tlb_node_parallel, whose fn is not called
+ *   for it); the accessors of its streams answer NULL / 0 / length 0 -- tlb_node_pcm NULL, so nothing is written into buffers the shard
+ *   may still use; the life-cycle calls of its streams, gain on one of them and tlb_node_shard_restart return TLB_ERR_LATE (a gain set
+ *   meanwhile is remembered and applied when the shard comes back).  Each node step submitted meanwhile counts in missed_steps: its
+ *   streams' input for that step is never encoded.
+ *   Poll point.  Late shards are examined, without blocking, only at the end of tlb_node_wait (and so of tlb_node_run): the caller's
+ *   next fill, which follows the wait in both the run() loop and the submit, submit, wait loop, reaches a shard that came back there
+ *   before the next submit.  When the late job has returned
+ *     - with an error: the shard is BROKEN exactly as above (its in-flight steps counted lost); that wait returns the code;
+ *     - OK, with ticks of its own still in flight (the second tick of the pipelined loop): the node queues the wait for the next one and
+ *       does not wait for it; the results of those ticks, and the late tick's own, are never shown (dropped_steps);
+ *     - OK, with nothing in flight: the shard is OK again (rejoins) and takes part from the next submit on.  Nothing is restarted or
+ *       reset: its encoders are those that have encoded every input the shard accepted.
+ *   After a wait the accessors of a stream show results only if its shard took part in that node step; otherwise NULL / length 0,
+ *   never the results of an older step.  tlb_node_shard_deadline_status() has the record of every shard; tlb_node_shard_status() and
+ *   tlb_node_counters() report a late shard as it stood before the late call.
+ *   Unit of isolation: a DEVICE.  A real hang of a GPU stalls every shard placed on it; the deadline keeps the shards on OTHER devices on
+ *   air.  tlb_node_destroy() still waits for a late shard's job without a limit: a shard that never returns is the caller's cue to exit
+ *   non-zero, or to drive that GPU from a fresh child process (never by re-executing the process that holds the GPU).
+ *
  * Two planes, chosen at creation:
  *   TLB_NODE_TICK   the real-time loop: a tlb_tick per shard, host buffers in, packets out (everything of tlb_tick_* per stream).
  *   TLB_NODE_BATCH  device-resident buffers: a tlb_batch per shard, tlb_node_encode_device() takes one device pointer per shard.
@@ -369,11 +399,12 @@ typedef struct {
 /* health and identity of one shard (tlb_node_shard_status) */
 #define TLB_SHARD_OK 0
 #define TLB_SHARD_BROKEN 1
+#define TLB_SHARD_LATE 2             /* TICK plane with a deadline: its job missed the deadline and has not been seen to return (TICK DEADLINE) */
 #define TLB_NODE_WHAT_LEN 192
 #define TLB_NODE_NAME_LEN 64
 typedef struct {
     int shard, device, first, nstreams;
-    int state;                     /* TLB_SHARD_OK / TLB_SHARD_BROKEN */
+    int state;                     /* TLB_SHARD_OK / TLB_SHARD_BROKEN / TLB_SHARD_LATE */
     int last_err;                  /* TLB_ERR_* of the failure that broke it last (kept after a restart), 0 = never failed */
     long failures, restarts;       /* times it broke / was restarted */
     long lost_steps;               /* steps that were in flight when it broke (not in the counters) */
@@ -402,8 +433,24 @@ int tlb_node_counters(const tlb_node *nd, tlb_node_counter *per_shard, tlb_node_
 /* One line per shard: device ordinal and name, CUs, XCDs, memory, PCI address, UUID, stream block -- what a log of a multi-GPU run
  * should open with (also printed to stderr at creation when TLB_VERBOSE is set in the environment).  Valid until tlb_node_destroy. */
 const char *tlb_node_describe(const tlb_node *nd);
-/* Returns TLB_SHARD_OK / TLB_SHARD_BROKEN (negative: -TLB_ERR_ARG) and fills *info (may be NULL). */
+/* Returns TLB_SHARD_OK / TLB_SHARD_BROKEN / TLB_SHARD_LATE (negative: -TLB_ERR_ARG) and fills *info (may be NULL). */
 int tlb_node_shard_status(const tlb_node *nd, int shard, tlb_node_shard_info *info);
+/* TICK DEADLINE (above): ms > 0 sets it, 0 turns it off (the default).  TICK plane only, between steps only: TLB_ERR_ARG on a BATCH
+ * node, for a negative or non-finite value, or while a step is in flight. */
+int tlb_node_set_deadline_ms(tlb_node *nd, double ms);
+/* the deadline record of one shard (tlb_node_shard_deadline_status; a struct of its own: tlb_node_shard_info keeps its size) */
+typedef struct {
+    int state;                     /* TLB_SHARD_OK / TLB_SHARD_BROKEN / TLB_SHARD_LATE */
+    long late_events;              /* times the shard went late */
+    long rejoins;                  /* times it came back on its own */
+    long dropped_steps;            /* steps it completed after the node had given up on them: their results are never shown */
+    long missed_steps;             /* node steps submitted while it was late: its streams' input for them is never encoded */
+    long last_late_step;           /* node step index (0-based count of node submits) at which it last went late; -1: never */
+    long last_rejoin_step;         /* first node step it took part in after coming back; -1: never */
+    double worst_overrun_ms;       /* longest a late job ran past its deadline, as seen at the node's poll points */
+} tlb_node_shard_deadline;
+/* Returns the state as tlb_node_shard_status does (negative: -TLB_ERR_ARG) and fills *info (may be NULL). */
+int tlb_node_shard_deadline_status(const tlb_node *nd, int shard, tlb_node_shard_deadline *info);
 /* Destroy + re-create one shard's object (see FAULT ISOLATION above).  now_s >= 0: the EDI timestamp origin of the restarted senders
  * (TICK plane; < 0 keeps the creation-time value).  Returns 0, TLB_ERR_ARG while a step is in flight or after finish, or the code
  * the re-creation failed with (the shard then stays broken and may be restarted again). */

@@ -11,6 +11,10 @@ extern "C" {
 int tlb_debug_fail_next(tlb_batch *b, int nth);                    /* the nth launch of this batch from now fails (1 = the next; 0 disarms) */
 int tlb_debug_tick_fail_next(tlb_tick *t, int nth);                /* ... the nth submit of this tick object, in its LAST group: the groups before it have been queued */
 int tlb_debug_node_fail_next(tlb_node *nd, int shard, int nth);    /* ... of one shard of a node */
+/* A stalled shard for the node's tick deadline: the nth wait job of that shard from now (1 = the next; 0 disarms), AFTER its
+ * tlb_tick_wait has returned with the tick complete, sleeps `ms` on the shard's HOST thread and then returns `rc` (0: the tick's results
+ * stand; non-zero: as a failing call would).  The device stays idle and healthy: no kernel spins, no event is left incomplete. */
+int tlb_debug_node_stall_next(tlb_node *nd, int shard, int nth, int ms, int rc);
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,13 @@
 // thread per mailbox (the node's caller), one job in the slot at a time.  Header-only and HIP-free so that a CPU test can drive it
 // with fake jobs under ThreadSanitizer (tests/test_mailbox_tsan.py, tests/emu/mailbox_tsan.cpp); `on_start` runs once on the new
 // thread before the first job (the shard sets its HIP device there).
+// The node's tick deadline (include/toolame_batch.h, TICK DEADLINE) needs three more questions of the slot: join_job_until() waits up
+// to a time point, poll() does not wait, busy() says whether a job is posted and not yet returned.  None of them consumes the job: a
+// job that missed its deadline stays the mailbox's until it returns, and the poster asks again later (tests/emu/mailbox_deadline_tsan.cpp).
+// Posting to a busy mailbox is a programming error (it would overwrite the slot).
 #pragma once
+#include <cassert>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -44,6 +50,7 @@ struct TlbMailbox {
     {
         {
             std::lock_guard<std::mutex> lk(mu);
+            assert(!has_job && done && "TlbMailbox::post on a busy mailbox");
             job = std::move(j); has_job = true; done = false;
         }
         cv.notify_all();
@@ -53,6 +60,27 @@ struct TlbMailbox {
         std::unique_lock<std::mutex> lk(mu);
         cv.wait(lk, [&] { return done; });
         return rc;
+    }
+    // true with the job's code in *r if it has returned by t (or nothing was posted); false if it is still running at t
+    bool join_job_until(std::chrono::steady_clock::time_point t, int *r)
+    {
+        std::unique_lock<std::mutex> lk(mu);
+        if (!cv.wait_until(lk, t, [&] { return done; })) return false;
+        if (r) *r = rc;
+        return true;
+    }
+    // the same without waiting
+    bool poll(int *r)
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!done) return false;
+        if (r) *r = rc;
+        return true;
+    }
+    bool busy()
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        return has_job || !done;
     }
     // no further job: the thread leaves its loop after the one it may be running
     void stop()

@@ -12,9 +12,11 @@
 #include <string.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -30,10 +32,14 @@
 
 namespace {
 
+using Clock = std::chrono::steady_clock;
+
 double now_ns()
 {
-    return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    return (double)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now().time_since_epoch()).count();
 }
+Clock::time_point at_ns(double ns) { return Clock::time_point(std::chrono::nanoseconds((long long)ns)); }      // (now_ns()'s clock)
+Clock::duration ms_dur(double ms) { return std::chrono::duration_cast<Clock::duration>(std::chrono::duration<double, std::milli>(ms)); }
 
 // One block of streams: the object that encodes it, the thread that talks to it (the mailbox: csrc/tlb_mailbox.h).
 struct Shard : TlbMailbox {
@@ -61,6 +67,36 @@ struct Shard : TlbMailbox {
     int num_cu = 0, num_xcd = 0;
     double hbm_gb = 0;
 
+    // TICK DEADLINE (include/toolame_batch.h).  NODE-SIDE records: read and written on the node's caller thread only, never inside a job.
+    // While a shard is late its fields above belong to the job it is still running; the node reads them again only after poll() has
+    // reported that job done (the mailbox mutex orders the two), and meanwhile reports the shard from `kept`.
+    bool late = false;                           // its job missed a deadline and has not been seen to return
+    bool late_wait = false;                      // ... and that job retires a tick (a wait), whose results the node will not show
+    bool stale = false;                          // its tick's read accessors show a step the node did not wait for it in
+    bool rejoined = false;                       // back from LATE: the next submit it takes part in is last_rejoin_step
+    bool gain_missed = false;                    // a gain call skipped it while late: applied again when it comes back
+    bool took = false;                           // the last node-wide call: its part returned in time ...
+    int got = 0;                                 // ... with this code
+    std::deque<long> nsteps;                     // node step index of each of its ticks in flight
+    Clock::time_point due;                       // the deadline its late job missed
+    long late_events = 0, rejoins = 0, dropped_steps = 0, missed_steps = 0, last_late_step = -1, last_rejoin_step = -1;
+    double worst_overrun_ms = 0;
+    struct Kept {
+        long steps, frames, failures, restarts, lost_steps;
+        double busy_ns, device_ms;
+        int last_err;
+        char what[TLB_NODE_WHAT_LEN];
+    } kept = {};
+    void keep()                                  // before a job that may go late is posted (the shard is idle: its fields are readable)
+    {
+        kept.steps = steps; kept.frames = frames; kept.failures = failures; kept.restarts = restarts; kept.lost_steps = lost_steps;
+        kept.busy_ns = busy_ns; kept.device_ms = device_ms; kept.last_err = last_err;
+        memcpy(kept.what, what, sizeof what);
+    }
+#ifdef TLB_FAULT_INJECT
+    int stall_nth = 0, stall_ms = 0, stall_rc = 0;        // tlb_debug_node_stall_next: set between jobs, read inside wait jobs
+#endif
+
     // called on the shard's thread right after the failing call: what HIP last complained about in this thread, then the mark
     int fail(int rc, const char *where)
     {
@@ -76,7 +112,28 @@ struct Shard : TlbMailbox {
         return rc;
     }
     bool live() const { return !broken && (tick || batch); }
+    bool on() const { return !late && live(); }            // (`late` first: a late shard's own fields are not read)
 };
+
+// The wait part of a tick, on the shard's thread: tlb_node_wait's job, and the one the poll point queues for a tick the node has
+// already given up on.  Owns nothing but the shard.
+int tick_wait_job(Shard &s)
+{
+    if (s.t_submit.empty()) return 0;                            // (cannot happen in lockstep; a shard without a tick in flight has nothing to wait for)
+    if (int r = tlb_tick_wait(s.tick)) return r;
+#ifdef TLB_FAULT_INJECT
+    if (s.stall_nth > 0 && --s.stall_nth == 0) {                 // the tick is complete: only this host thread is held up
+        std::this_thread::sleep_for(std::chrono::milliseconds(s.stall_ms));
+        if (s.stall_rc) return s.stall_rc;
+    }
+#endif
+    const double t = now_ns();
+    s.busy_ns += t - s.t_submit.front(); s.frames += s.f_submit.front(); s.t_submit.pop_front(); s.f_submit.pop_front();
+    s.steps++;
+    const float ms = tlb_tick_last_ms(s.tick);
+    if (ms > 0) s.device_ms += ms;
+    return 0;
+}
 
 }  // namespace
 
@@ -92,25 +149,92 @@ struct tlb_node {
     // node-level clock: first submit -> last wait of a step
     std::deque<double> t_submit;
     double wall_ns = 0;
+    long submitted = 0, waited = 0;              // node steps: submits / waits so far (a step's index is its submit's)
+    double deadline_ms = 0;                      // TICK DEADLINE; 0 = none
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
     // first non-zero code of THIS call -- the caller's cue to look at tlb_node_shard_status() -- or TLB_ERR_HIP when no shard is live.
-    int live(const char *where, const std::function<int(Shard &)> &fn)
+    // `due` (TICK DEADLINE): a shard whose part has not returned by then goes LATE at node step `step`; its job keeps running and owns
+    // what it uses (fn is shared with it).  `wait`: only shards whose oldest tick in flight is node step `step` take part.
+    int live(const char *where, std::function<int(Shard &)> fn, const Clock::time_point *due = nullptr, long step = 0, bool wait = false)
     {
+        const auto job = std::make_shared<const std::function<int(Shard &)>>(std::move(fn));
         std::vector<Shard *> on;
-        for (Shard *s : shards)
-            if (s->live()) { on.push_back(s); s->post([s, &fn, where] { const int r = fn(*s); return r ? s->fail(r, where) : 0; }); }
-        int rc = on.empty() ? (int)TLB_ERR_HIP : 0;
-        for (Shard *s : on) { const int r = s->join_job(); if (r && !rc) rc = r; }
+        bool any = false, late = false;
+        for (Shard *s : shards) {
+            s->took = false;
+            if (!s->on()) continue;
+            any = true;
+            if (wait && (s->nsteps.empty() || s->nsteps.front() != step)) { s->stale = true; continue; }     // (back from LATE: not in this step)
+            if (due) s->keep();
+            on.push_back(s);
+            s->post([s, job, where] { const int r = (*job)(*s); return r ? s->fail(r, where) : 0; });
+        }
+        int rc = 0;
+        for (Shard *s : on) {
+            int r = 0;
+            if (!due) r = s->join_job();
+            else if (!s->join_job_until(*due, &r)) {
+                s->late = true; s->late_wait = wait; s->due = *due; s->late_events++; s->last_late_step = step; s->nsteps.clear();
+                late = true;
+                continue;
+            }
+            s->took = true; s->got = r;
+            if (r) s->nsteps.clear();                                // (Shard::fail has emptied its queues)
+            if (r && !rc) rc = r;
+        }
+        if (!rc && late) rc = TLB_ERR_LATE;
+        if (!any) rc = any_late() ? (int)TLB_ERR_LATE : (int)TLB_ERR_HIP;
         return rc;
     }
-    // every shard, broken or not (creation, teardown, the caller's own per-block work); first non-zero code wins, nothing is marked
+    bool any_late() const
+    {
+        for (const Shard *s : shards) if (s->late) return true;
+        return false;
+    }
+    // The poll point (end of tlb_node_wait): late shards are looked at without blocking.  Returns the code of a late job that came
+    // back with an error (its shard is BROKEN now, as any other), else 0.
+    int poll_late()
+    {
+        int rc = 0;
+        Clock::time_point now{};
+        for (Shard *s : shards) {
+            if (!s->late) continue;
+            if (now == Clock::time_point{}) now = Clock::now();
+            const double over = std::chrono::duration<double, std::milli>(now - s->due).count();
+            if (over > s->worst_overrun_ms) s->worst_overrun_ms = over;
+            int r = 0;
+            if (!s->poll(&r)) continue;
+            s->late = false;                                         // the job has returned: the shard's fields are the node's to read again
+            if (r) { if (!rc) rc = r; continue; }
+            if (s->late_wait) { s->steps--; s->frames -= s->n; s->dropped_steps++; }      // a tick retired after the node gave up on it: not shown
+            if (!s->t_submit.empty()) {                              // its next tick is still in flight: queue its wait, do not wait for it
+                s->keep();
+                s->late = true; s->late_wait = true; s->due = now + ms_dur(deadline_ms);
+                s->post([s] { const int q = tick_wait_job(*s); return q ? s->fail(q, "tlb_tick_wait") : 0; });
+                continue;
+            }
+            s->rejoins++; s->rejoined = true; s->stale = true;       // OK again; takes part from the next submit on
+            if (s->gain_missed) {
+                s->gain_missed = false;
+                const int q = one(s->index, [this](Shard &sh) {
+                    for (int k = 0; k < sh.n; k++)
+                        if (int e = tlb_tick_set_gain_db(sh.tick, k, gain_db[(size_t)(sh.first + k)])) return sh.fail(e, "set_gain_db");
+                    return 0;
+                });
+                if (q && !rc) rc = q;
+            }
+        }
+        return rc;
+    }
+    // every shard, broken or not (creation, teardown, the caller's own per-block work) but a late one; first non-zero code wins, nothing is marked
     int all(const std::function<int(Shard &)> &fn)
     {
-        for (Shard *s : shards) s->post([s, &fn] { return fn(*s); });
+        std::vector<Shard *> on;
+        for (Shard *s : shards) if (!s->late) { on.push_back(s); s->post([s, &fn] { return fn(*s); }); }
         int rc = 0;
-        for (Shard *s : shards) { const int r = s->join_job(); if (r && !rc) rc = r; }
+        for (Shard *s : on) { const int r = s->join_job(); if (r && !rc) rc = r; }
         return rc;
     }
     int one(int shard, const std::function<int(Shard &)> &fn)
@@ -126,11 +250,18 @@ struct tlb_node {
         *local = stream - s->first;
         return s;
     }
-    // the owning shard of a stream if its results may be read: NULL for a broken shard (its buffers hold a half-finished step)
+    // the owning shard of a stream if its results may be read: NULL for a broken shard (its buffers hold a half-finished step), a late
+    // one, and one that did not take part in the step last waited for
     Shard *read(int stream, int *local) const
     {
         Shard *s = of(stream, local);
-        return s && s->live() ? s : nullptr;
+        return s && s->on() && !s->stale ? s : nullptr;
+    }
+    // ... if its input set may be written: NULL for a broken or a late shard
+    Shard *input(int stream, int *local) const
+    {
+        Shard *s = of(stream, local);
+        return s && s->on() ? s : nullptr;
     }
 };
 
@@ -229,6 +360,7 @@ void tlb_node_destroy(tlb_node *nd)
     if (!nd) return;
     for (Shard *s : nd->shards) {
         if (s->th.joinable()) {
+            if (s->late) (void)s->join_job();                        // a late shard's job is waited for WITHOUT a limit (TICK DEADLINE)
             s->post([s] { shard_unmake(*s); return 0; });            // objects are torn down on the thread that made them
             (void)s->join_job();
             s->stop();
@@ -286,6 +418,19 @@ int tlb_node_shard_status(const tlb_node *nd, int shard, tlb_node_shard_info *in
 {
     if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return -TLB_ERR_ARG;
     const Shard &s = *nd->shards[(size_t)shard];
+    if (s.late) {                                                    // from the node's own record: its job still owns the shard's fields
+        if (info) {
+            memset(info, 0, sizeof *info);
+            info->shard = s.index; info->device = s.device; info->first = s.first; info->nstreams = s.n;
+            info->state = TLB_SHARD_LATE; info->last_err = s.kept.last_err;
+            info->failures = s.kept.failures; info->restarts = s.kept.restarts; info->lost_steps = s.kept.lost_steps;
+            memcpy(info->what, s.kept.what, sizeof info->what);
+            memcpy(info->device_name, s.device_name, sizeof info->device_name);
+            memcpy(info->pci, s.pci, sizeof info->pci); memcpy(info->uuid, s.uuid, sizeof info->uuid);
+            info->num_cu = s.num_cu; info->num_xcd = s.num_xcd; info->hbm_gb = s.hbm_gb;
+        }
+        return TLB_SHARD_LATE;
+    }
     if (info) {
         memset(info, 0, sizeof *info);
         info->shard = s.index; info->device = s.device; info->first = s.first; info->nstreams = s.n;
@@ -305,7 +450,10 @@ int tlb_node_shard_status(const tlb_node *nd, int shard, tlb_node_shard_info *in
 // submit, and its first tick emits nothing (one frame of latency), exactly like a new node's.  Works on a healthy shard too.
 int tlb_node_shard_restart(tlb_node *nd, int shard, long long now_s)
 {
-    if (!nd || shard < 0 || shard >= (int)nd->shards.size() || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return TLB_ERR_ARG;
+    if (nd->shards[(size_t)shard]->late) return TLB_ERR_LATE;
+    if (nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    nd->shards[(size_t)shard]->nsteps.clear();
     const int rc = nd->one(shard, [&](Shard &s) {
         shard_unmake(s);
         (void)hipGetLastError();                                     // the old failure is on record in `what`; start clean
@@ -327,7 +475,8 @@ int tlb_node_counters(const tlb_node *nd, tlb_node_counter *per_shard, tlb_node_
         tlb_node_counter c;
         memset(&c, 0, sizeof c);
         c.shard = s.index; c.device = s.device; c.first = s.first; c.nstreams = s.n;
-        c.steps = s.steps; c.frames = s.frames; c.busy_ns = s.busy_ns; c.device_ms = s.device_ms;
+        if (s.late) { c.steps = s.kept.steps; c.frames = s.kept.frames; c.busy_ns = s.kept.busy_ns; c.device_ms = s.kept.device_ms; }
+        else { c.steps = s.steps; c.frames = s.frames; c.busy_ns = s.busy_ns; c.device_ms = s.device_ms; }
         if (per_shard) per_shard[g] = c;
         t.frames += c.frames;
         if (g == 0 || c.steps < t.steps) t.steps = c.steps;
@@ -344,22 +493,42 @@ int tlb_node_parallel(tlb_node *nd, void (*fn)(void *ctx, int shard, int first, 
     return nd->all([&](Shard &s) { fn(ctx, s.index, s.first, s.n); return 0; });
 }
 
+int tlb_node_set_deadline_ms(tlb_node *nd, double ms)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || !std::isfinite(ms) || ms < 0 || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    nd->deadline_ms = ms;
+    return TLB_OK;
+}
+int tlb_node_shard_deadline_status(const tlb_node *nd, int shard, tlb_node_shard_deadline *info)
+{
+    if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return -TLB_ERR_ARG;
+    const Shard &s = *nd->shards[(size_t)shard];
+    const int st = s.late ? TLB_SHARD_LATE : s.live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN;
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->state = st;
+        info->late_events = s.late_events; info->rejoins = s.rejoins; info->dropped_steps = s.dropped_steps; info->missed_steps = s.missed_steps;
+        info->last_late_step = s.last_late_step; info->last_rejoin_step = s.last_rejoin_step; info->worst_overrun_ms = s.worst_overrun_ms;
+    }
+    return st;
+}
+
 // ---- TICK plane ----
 int16_t *tlb_node_pcm(tlb_node *nd, int stream)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
     int16_t *p = s && s->tick ? tlb_tick_pcm(s->tick) : nullptr;
     return p ? p + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME : nullptr;
 }
 uint8_t *tlb_node_xpad(tlb_node *nd, int stream)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
     uint8_t *p = s && s->tick ? tlb_tick_xpad(s->tick) : nullptr;
     return p ? p + (size_t)k * TLB_MAX_XPAD : nullptr;
 }
 int32_t *tlb_node_xpad_len(tlb_node *nd, int stream)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
     int32_t *p = s && s->tick ? tlb_tick_xpad_len(s->tick) : nullptr;
     return p ? p + k : nullptr;
 }
@@ -368,30 +537,35 @@ int tlb_node_submit(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->t_submit.size() >= 2) return TLB_ERR_ARG;
     const double t0 = now_ns();
-    const int rc = nd->live("tlb_tick_submit", [&](Shard &s) {
+    const long step = nd->submitted;
+    for (Shard *s : nd->shards) if (s->late) s->missed_steps++;      // its streams' input for this step is never encoded
+    const Clock::time_point due = at_ns(t0) + ms_dur(nd->deadline_ms);
+    const int rc = nd->live("tlb_tick_submit", [](Shard &s) {
         const double t = now_ns();
         if (int r = tlb_tick_submit(s.tick)) return r;
         s.t_submit.push_back(t); s.f_submit.push_back((long)s.n);
         return 0;
-    });
+    }, nd->deadline_ms > 0 ? &due : nullptr, step);
+    for (Shard *s : nd->shards)
+        if (s->took && !s->got) {
+            s->nsteps.push_back(step);
+            if (s->rejoined) { s->last_rejoin_step = step; s->rejoined = false; }
+        }
     nd->t_submit.push_back(t0);                                      // the node's step exists whatever a shard did: wait() retires it
+    nd->submitted++;
     return rc;
 }
 int tlb_node_wait(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->t_submit.empty()) return TLB_ERR_ARG;
-    const int rc = nd->live("tlb_tick_wait", [&](Shard &s) {
-        if (s.t_submit.empty()) return 0;                            // (cannot happen in lockstep; a shard without a tick in flight has nothing to wait for)
-        if (int r = tlb_tick_wait(s.tick)) return r;
-        const double t = now_ns();
-        s.busy_ns += t - s.t_submit.front(); s.frames += s.f_submit.front(); s.t_submit.pop_front(); s.f_submit.pop_front();
-        s.steps++;
-        const float ms = tlb_tick_last_ms(s.tick);
-        if (ms > 0) s.device_ms += ms;
-        return 0;
-    });
+    const Clock::time_point due = at_ns(nd->t_submit.front()) + ms_dur(nd->deadline_ms);     // the real-time budget runs from submit
+    const int rc = nd->live("tlb_tick_wait", tick_wait_job, nd->deadline_ms > 0 ? &due : nullptr, nd->waited, true);
+    for (Shard *s : nd->shards)
+        if (s->took && !s->got) { s->stale = false; s->nsteps.pop_front(); }
     nd->wall_ns += now_ns() - nd->t_submit.front(); nd->t_submit.pop_front();
-    return rc;
+    nd->waited++;
+    const int rp = nd->poll_late();                                  // the one poll point of late shards
+    return rc && rc != TLB_ERR_LATE ? rc : rp ? rp : rc;
 }
 int tlb_node_run(tlb_node *nd)
 {
@@ -404,7 +578,10 @@ int tlb_node_run(tlb_node *nd)
 int tlb_node_finish(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
-    const int rc = nd->live("tlb_tick_finish", [&](Shard &s) { return tlb_tick_finish(s.tick); });
+    const Clock::time_point due = Clock::now() + ms_dur(nd->deadline_ms);
+    const int rc = nd->live("tlb_tick_finish", [](Shard &s) { return tlb_tick_finish(s.tick); }, nd->deadline_ms > 0 ? &due : nullptr, nd->submitted);
+    for (Shard *s : nd->shards)
+        if (s->took && !s->got) s->stale = false;
     nd->finished = true;
     return rc;
 }
@@ -456,17 +633,20 @@ const uint8_t *tlb_node_fragment(const tlb_node *nd, int stream, int unit, int k
 }
 
 // ---- both planes: gain, life cycle of one stream (on the owning shard's thread, like every other call on the shard's object) ----
-// A stream of a BROKEN shard answers TLB_ERR_HIP (the gain is remembered and applied when the shard is restarted).
+// A stream of a BROKEN shard answers TLB_ERR_HIP (the gain is remembered and applied when the shard is restarted), of a LATE one
+// TLB_ERR_LATE (the gain is remembered and applied when the shard comes back).
 int tlb_node_set_gain_db(tlb_node *nd, int stream, double gain_db)
 {
     if (!nd || stream < -1 || stream >= nd->nstreams) return TLB_ERR_ARG;
     auto f = [&](Shard &s, int k) { return s.tick ? tlb_tick_set_gain_db(s.tick, k, gain_db) : tlb_set_gain_db(s.batch, k, gain_db); };
     if (stream < 0) {
         for (double &g : nd->gain_db) g = gain_db;
+        for (Shard *s : nd->shards) if (s->late) s->gain_missed = true;
         return nd->live("set_gain_db", [&](Shard &s) { return f(s, -1); });
     }
     nd->gain_db[(size_t)stream] = gain_db;
     int k; Shard *s = nd->of(stream, &k);
+    if (s->late) { s->gain_missed = true; return TLB_ERR_LATE; }
     if (!s->live()) return TLB_ERR_HIP;
     return nd->one(s->index, [&](Shard &sh) { return f(sh, k); });
 }
@@ -474,6 +654,7 @@ int tlb_node_stream_reset(tlb_node *nd, int stream)
 {
     int k; Shard *s = nd ? nd->of(stream, &k) : nullptr;
     if (!s) return TLB_ERR_ARG;
+    if (s->late) return TLB_ERR_LATE;
     if (!s->live()) return TLB_ERR_HIP;
     return nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reset(sh.tick, k) : tlb_stream_reset(sh.batch, k); });
 }
@@ -481,6 +662,7 @@ int tlb_node_stream_finish(tlb_node *nd, int stream, uint8_t *out, size_t out_si
 {
     int k; Shard *s = nd ? nd->of(stream, &k) : nullptr;
     if (!s) return -TLB_ERR_ARG;
+    if (s->late) return -TLB_ERR_LATE;
     if (!s->live()) return -TLB_ERR_HIP;
     return nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_finish(sh.tick, k, out, out_size) : tlb_stream_finish(sh.batch, k, out, out_size); });
 }
@@ -488,6 +670,7 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
 {
     int k; Shard *s = nd ? nd->of(stream, &k) : nullptr;
     if (!s || !cfg) return TLB_ERR_ARG;
+    if (s->late) return TLB_ERR_LATE;
     if (!s->live()) return TLB_ERR_HIP;
     const int rc = nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reconfigure(sh.tick, k, cfg) : tlb_stream_reconfigure(sh.batch, k, cfg); });
     if (!rc) nd->cfgs[(size_t)stream] = *cfg;                        // a restart of the shard re-creates the stream as it is NOW
@@ -497,7 +680,7 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
 // ---- BATCH plane ----
 tlb_batch *tlb_node_batch(tlb_node *nd, int shard)
 {
-    return nd && shard >= 0 && shard < (int)nd->shards.size() && nd->shards[(size_t)shard]->live() ? nd->shards[(size_t)shard]->batch : nullptr;
+    return nd && shard >= 0 && shard < (int)nd->shards.size() && nd->shards[(size_t)shard]->on() ? nd->shards[(size_t)shard]->batch : nullptr;
 }
 void *tlb_node_device_alloc(tlb_node *nd, int shard, size_t bytes)
 {
@@ -586,7 +769,17 @@ int tlb_debug_node_fail_next(tlb_node *nd, int shard, int nth)
 {
     if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return TLB_ERR_ARG;
     Shard &s = *nd->shards[(size_t)shard];
+    if (s.late) return TLB_ERR_LATE;
     return s.tick ? tlb_debug_tick_fail_next(s.tick, nth) : s.batch ? tlb_debug_fail_next(s.batch, nth) : (int)TLB_ERR_ARG;
+}
+// ... the nth wait job of ONE shard from now holds its host thread `ms` after its tick is complete, then returns rc
+int tlb_debug_node_stall_next(tlb_node *nd, int shard, int nth, int ms, int rc)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || shard < 0 || shard >= (int)nd->shards.size() || nth < 0 || ms < 0) return TLB_ERR_ARG;
+    Shard &s = *nd->shards[(size_t)shard];
+    if (s.late) return TLB_ERR_LATE;                                 // (its fields belong to the job it is running)
+    s.stall_nth = nth; s.stall_ms = ms; s.stall_rc = rc;
+    return TLB_OK;
 }
 #endif
 

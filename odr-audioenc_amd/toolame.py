@@ -22,7 +22,7 @@ SAMPLES = 1152
 
 _ERR = {1: "illegal sample rate (48000/44100/32000/24000/22050/16000 Hz; the egress calls: no 32/44.1/22.05 kHz)", 2: "bad channel mode", 3: "invalid PSY model",
         4: "illegal bitrate for this MPEG version", 5: "invalid XPAD length", 16: "no usable HIP device",
-        17: "HIP runtime error", 18: "bad argument"}
+        17: "HIP runtime error", 18: "bad argument", 19: "a shard missed the node's tick deadline (it is LATE)"}
 
 
 class ToolameError(RuntimeError):
@@ -73,6 +73,7 @@ def load_fault_library():
         L.tlb_debug_fail_next.argtypes = [C.c_void_p, C.c_int]
         L.tlb_debug_tick_fail_next.argtypes = [C.c_void_p, C.c_int]
         L.tlb_debug_node_fail_next.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.tlb_debug_node_stall_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         _fault_lib = L
     return _fault_lib
 
@@ -213,6 +214,9 @@ def _bind(L):
         L.tlb_node_describe.restype = C.c_char_p
         L.tlb_node_shard_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.tlb_node_shard_restart.argtypes = [C.c_void_p, C.c_int, C.c_longlong]
+    if hasattr(L, "tlb_node_set_deadline_ms"):
+        L.tlb_node_set_deadline_ms.argtypes = [C.c_void_p, C.c_double]
+        L.tlb_node_shard_deadline_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return L
 
 
@@ -653,6 +657,11 @@ class _CNodeShardInfo(C.Structure):
                 ("hbm_gb", C.c_double)]
 
 
+class _CNodeShardDeadline(C.Structure):
+    _fields_ = [("state", C.c_int), ("late_events", C.c_long), ("rejoins", C.c_long), ("dropped_steps", C.c_long), ("missed_steps", C.c_long),
+                ("last_late_step", C.c_long), ("last_rejoin_step", C.c_long), ("worst_overrun_ms", C.c_double)]
+
+
 class _CNodeCounter(C.Structure):
     _fields_ = [("shard", C.c_int), ("device", C.c_int), ("first", C.c_int), ("nstreams", C.c_int), ("steps", C.c_long), ("frames", C.c_long),
                 ("busy_ns", C.c_double), ("device_ms", C.c_double), ("wall_ns", C.c_double)]
@@ -692,10 +701,13 @@ def node_plan(configs, nshards):
 class Node:
     """tlb_node_*: N streams over the shards of one host (one tlb_tick or tlb_batch + one host thread per shard; `devices[g]` is the HIP
     device of shard g and may repeat).  plane "tick": fill pcm(s), run() / submit() + wait(), read frame(s) / packets(s) ...;
-    plane "batch": device-resident buffers per shard, encode(pcm) with pcm int16 [nframes][nstreams][2][1152] split by the wrapper."""
+    plane "batch": device-resident buffers per shard, encode(pcm) with pcm int16 [nframes][nstreams][2][1152] split by the wrapper.
+    deadline_ms > 0 (plane "tick"): the node's tick deadline (include/toolame_batch.h, TICK DEADLINE); a call in which a shard goes late
+    raises ToolameError code 19, shard_deadline(g) has its record."""
 
     def __init__(self, configs, devices=(0,), plane="tick", egress="frames", ngroups=0, with_xpad=False, version=b"", now_s=1700000000,
-                 delay_ms=0, tist=False, tai_utc_offset=37, fec=0, chunk_len=207, transport=False, addr_source=0, dest_port=0, lib=None):
+                 delay_ms=0, tist=False, tai_utc_offset=37, fec=0, chunk_len=207, transport=False, addr_source=0, dest_port=0, lib=None,
+                 deadline_ms=0):
         self.L = lib or load_library()
         configs = list(configs)
         self.configs = configs
@@ -717,6 +729,8 @@ class Node:
         self._dev = {}          # BATCH plane: (shard, tag) -> (device pointer, bytes)
         if plane == "tick":
             self.units = [self.L.tlb_node_units(self.h, s) for s in range(self.nstreams)]
+        if deadline_ms:
+            self.set_deadline_ms(deadline_ms)
 
     def close(self):
         if self.h:
@@ -767,6 +781,24 @@ class Node:
         """fault-injection TEST build only (lib=load_fault_library()): the nth launch / tick of shard g from now fails"""
         return self.L.tlb_debug_node_fail_next(self.h, g, nth)
 
+    # ---- tick deadline (include/toolame_batch.h, TICK DEADLINE) ----
+    def set_deadline_ms(self, ms):
+        """ms > 0 sets the TICK plane's deadline, 0 turns it off; between steps only"""
+        self._rc(self.L.tlb_node_set_deadline_ms(self.h, float(ms)), "tlb_node_set_deadline_ms")
+
+    def shard_deadline(self, g):
+        """dict(state, late_events, rejoins, dropped_steps, missed_steps, last_late_step, last_rejoin_step, worst_overrun_ms)"""
+        info = _CNodeShardDeadline()
+        st = self.L.tlb_node_shard_deadline_status(self.h, g, C.byref(info))
+        if st < 0:
+            raise ToolameError(-st, "tlb_node_shard_deadline_status")
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
+    def stall_next(self, g, nth, ms, rc=0):
+        """fault-injection TEST build only: the nth wait job of shard g from now holds its host thread `ms` after the tick is
+        complete, then returns rc (0: the tick's results stand)"""
+        self._rc(self.L.tlb_debug_node_stall_next(self.h, g, nth, int(ms), rc), "tlb_debug_node_stall_next")
+
     def counters(self):
         per = (_CNodeCounter * self.nshards)()
         tot = _CNodeCounter()
@@ -784,7 +816,7 @@ class Node:
             p = self.L.tlb_node_pcm(self.h, f)
             if not p:
                 if not self.shard_ok(g):
-                    continue                # a broken shard takes no input; its streams are off air until it is restarted
+                    continue                # a broken or late shard takes no input; its streams are off air until it is back
                 raise ToolameError(18, "tlb_node_pcm: no input set is free (two ticks in flight)")
             np.ctypeslib.as_array((C.c_int16 * (n * 2 * SAMPLES)).from_address(p)).reshape(n, 2 * SAMPLES)[:] = inter[f:f + n]
 
