@@ -516,6 +516,14 @@ TL_FN void tl_psy1_limits(const TlConfig *TL_RESTRICT C, int nbands, PARG(int, b
     L(blo) = C->p1_cbound[b]; L(bhi) = C->p1_cbound[b + 1];
     TL_LANES_END
 }
+// the same for two channels: lanes b and 32 + b both hold band b's limits (one fetch, mirrored by the address)
+TL_FN void tl_psy1_limits2(const TlConfig *TL_RESTRICT C, int nbands, PARG(int, blo), PARG(int, bhi))
+{
+    TL_LANES_BEGIN
+    const int b = (lane & 31) < nbands ? (lane & 31) : 0;
+    L(blo) = C->p1_cbound[b]; L(bhi) = C->p1_cbound[b + 1];
+    TL_LANES_END
+}
 TL_FN void tl_psy1_centres(TlPsyLds &w, int nbands, PARG(double, bsum), PARG(double, wt), PARG(int, blo), PARG(int, bhi))
 {
     TL_LANES_BEGIN
@@ -532,6 +540,30 @@ TL_FN void tl_psy1_centres(TlPsyLds &w, int nbands, PARG(double, bsum), PARG(dou
         if (w.ptype[centre] == TL_T_TONE) { if (w.ptype[centre + 1] == TL_T_TONE) centre++; else centre--; }
         w.nsum[lane] = sum; w.ncentre[lane] = (int16_t)centre;
     }
+    TL_LANES_END
+}
+// band centres of BOTH channels: lane b does channel 0's band b (its line types at TL_P1B_PTYPE), lane 32 + b channel 1's (w.ptype), from
+// the sums and weights the paired chains left per half.  The centres stay in registers (ncen; lanes without a band: a negative value no
+// line equals); ontone says that the band's centre sits on a tone's line.
+TL_FN void tl_psy1_centres2(TlPsyLds &w, int nbands, PARG(double, bsum), PARG(double, wt), PARG(int, blo), PARG(int, bhi), PARG(int, ncen), PARG(bool, ontone))
+{
+    TL_LANES_BEGIN
+    int centre = -1 - lane;
+    bool ont = false;
+    if ((lane & 31) < nbands) {
+        const uint8_t *pt = lane >= 32 ? w.ptype : TL_P1B_PTYPE(w);
+        const int lo = L(blo), hi = L(bhi);
+        const double sum = L(bsum), weight = L(wt);
+        if (sum <= TL_DBMIN) centre = (hi + lo) / 2;
+        else {
+            double index = weight * tlm_pow10_sl(-0.1 * sum);
+            centre = lo + (int)(index * (double)(hi - lo));
+        }
+        centre = centre < 1 ? 1 : centre > 510 ? 510 : centre;     // out-of-range only on non-finite input (UB in the reference)
+        if (pt[centre] == TL_T_TONE) { TL_DBG_BACK(2); if (pt[centre + 1] == TL_T_TONE) centre++; else centre--; }
+        ont = pt[centre] == TL_T_TONE;
+    }
+    L(ncen) = centre; L(ontone) = ont;
     TL_LANES_END
 }
 
@@ -741,6 +773,140 @@ TL_FN void tl_psy1_back(TlPsyLds &w, const double *TL_RESTRICT db, const TlConfi
     tl_psy1_thresholds(w, db, C, ch, ntone, nnoise, rec, sp);
 }
 
+// Band levels and decimation (psycho_1.c:390-470) of BOTH channels in one pass: channel 0's bands, tones and noise components on lanes
+// 0..31, channel 1's on lanes 32..63 -- the stages of tl_psy1_back up to the thresholds, with every ballot split and every lane read
+// offset per half.  Needs at most TL_P1B_LIST tones in either list.  Channel 0's tone records are read from the second set of arrays
+// (TL_P1B_*; its list entry from the parked register tl0), channel 1's from the wave's own.  Channel 1's masker list is written where
+// tl_psy1_thresholds reads it, channel 0's to TL_P1B_MKX / TL_P1B_MKBARK.
+struct TlPsy1Mk2 { int ntone0, nnoise0, ntone1, nnoise1; };
+TL_FN TlPsy1Mk2 tl_psy1_decimate2(TlPsyLds &w, const TlConfig *TL_RESTRICT C, int nbands, int nl0, int nl1, PARG(int, tl0),
+                                  PARG(double, bsum), PARG(int, ncen), PARG(bool, ontone))
+{
+    PV(double, nlev); PV(int, nsh); PV(int, nsl);
+    TL_LANES_BEGIN
+    const double v = (lane & 31) < nbands ? L(bsum) : 0.0;
+    L(nlev) = v; L(nsh) = (int)(uint32_t)(tl_d2u(v) >> 32); L(nsl) = (int)(uint32_t)tl_d2u(v);
+    TL_LANES_END
+    const bool centre_on_tone = TL_BALLOT(ontone) != 0ull;            // in either channel (rare); a channel without one has no line to match
+    if (centre_on_tone) TL_DBG_BACK(6);
+    // two bands of a channel with the same centre (see tl_psy1_back): each channel marks its own half of the scratch map
+    PV(bool, shared_c);
+    uint8_t *cmark = (uint8_t *)w.cinfo;                              // centres are 1..510: channel 0 at [0, 512), channel 1 at [512, 1024)
+    TL_LANES_BEGIN if ((lane & 31) < nbands) cmark[((lane >> 5) << 9) + L(ncen)] = (uint8_t)(lane & 31); TL_LANES_END
+    TL_LANES_BEGIN L(shared_c) = (lane & 31) < nbands && cmark[((lane >> 5) << 9) + L(ncen)] != (uint8_t)(lane & 31); TL_LANES_END
+    if (TL_BALLOT(shared_c) != 0ull) {
+        TL_DBG_BACK(3);
+        for (int b = 1; b < nbands; b++) {
+            const int cb0 = TL_READLANE_I32(ncen, b), cb1 = TL_READLANE_I32(ncen, 32 + b);
+            const double vb0 = tl_u2d(((uint64_t)(uint32_t)TL_READLANE_I32(nsh, b) << 32) | (uint32_t)TL_READLANE_I32(nsl, b));
+            const double vb1 = tl_u2d(((uint64_t)(uint32_t)TL_READLANE_I32(nsh, 32 + b) << 32) | (uint32_t)TL_READLANE_I32(nsl, 32 + b));
+            TL_LANES_BEGIN if ((lane & 31) < b && L(ncen) == (lane >= 32 ? cb1 : cb0)) L(nlev) = lane >= 32 ? vb1 : vb0; TL_LANES_END
+        }
+    }
+    TlPsy1Mk2 r;
+    // the noise components' table values are requested now and used after the tones (see tl_psy1_back)
+    PV(double, nbk0); PV(double, nhear0);
+    TL_LANES_BEGIN
+    const int c0 = (lane & 31) < nbands ? L(ncen) : 1;
+    L(nbk0) = C->p1_lbark[c0]; L(nhear0) = C->p1_lhear[c0];
+    TL_LANES_END
+    // tones: keep if not erased and not below the threshold in quiet (order preserved); one pass, a list per half
+    {
+        PV(bool, keep); PV(double, kx); PV(double, kb); PV(int, tline); PV(int, tcc); PV(double, tbk); PV(double, thr); PV(bool, inl);
+        TL_LANES_BEGIN
+        const bool second = lane >= 32;
+        const int k = lane & 31;
+        const bool in = k < (second ? nl1 : nl0);
+        double x = 0; int c = -1000 - lane, cc = 0;
+        if (in) {
+            const int ti = second ? (int)w.tlist[k] : (int)(int16_t)(L(tl0) & 0xffff);
+            const int16_t *cf = second ? w.conf_c : TL_P1B_CONF_C(w);
+            const double *tx = second ? w.tone_x : TL_P1B_TONE_X(w);
+            cc = cf[ti]; c = cc & 511; x = tx[ti];
+        }
+        L(kx) = x; L(tline) = c; L(tcc) = cc; L(inl) = in;
+        L(tbk) = C->p1_lbark[c < 0 ? 0 : c]; L(thr) = C->p1_lhear[c < 0 ? 0 : c];
+        TL_LANES_END
+        if (centre_on_tone)
+            for (int b = 0; b < nbands; b++) {                      // a band centre on the tone's line replaces its level
+                const int cb0 = TL_READLANE_I32(ncen, b), cb1 = TL_READLANE_I32(ncen, 32 + b);
+                const double vb0 = tl_u2d(((uint64_t)(uint32_t)TL_READLANE_I32(nsh, b) << 32) | (uint32_t)TL_READLANE_I32(nsl, b));
+                const double vb1 = tl_u2d(((uint64_t)(uint32_t)TL_READLANE_I32(nsh, 32 + b) << 32) | (uint32_t)TL_READLANE_I32(nsl, 32 + b));
+                TL_LANES_BEGIN if (L(tline) == (lane >= 32 ? cb1 : cb0)) L(kx) = lane >= 32 ? vb1 : vb0; TL_LANES_END
+            }
+        TL_LANES_BEGIN
+        bool kp = false; double bk = 0;
+        if (L(inl)) {
+            bk = L(tbk);
+            kp = !((L(tcc) >> 13) & 1) && !(L(kx) < L(thr));
+        }
+        L(keep) = kp; L(kb) = bk;
+        TL_LANES_END
+        const uint64_t m = TL_BALLOT(keep);
+        TL_LANES_BEGIN
+        if ((m >> lane) & 1ull) {
+            const bool second = lane >= 32;
+            const int pos = __builtin_popcountll(m & ((1ull << lane) - 1ull) & (second ? ~0xffffffffull : 0xffffffffull));
+            (second ? TL_MK_X(w) : TL_P1B_MKX(w))[pos] = L(kx); (second ? TL_MK_BARK(w) : TL_P1B_MKBARK(w))[pos] = L(kb);
+        }
+        TL_LANES_END
+        r.ntone0 = __builtin_popcountll(m & 0xffffffffull); r.ntone1 = __builtin_popcountll(m >> 32);
+    }
+    // tones closer than 0.5 bark: keep the stronger (psycho_1.c:443-469; see tl_psy1_back).  A channel whose neighbours are all apart is
+    // left alone; otherwise the two channels' walks are two independent states advanced in the same trips.
+    {
+        PV(bool, closep);
+        TL_LANES_BEGIN
+        const bool second = lane >= 32;
+        const int q = 1 + (lane & 31);
+        const double *bk = second ? TL_MK_BARK(w) : TL_P1B_MKBARK(w);
+        L(closep) = q < (second ? r.ntone1 : r.ntone0) && (bk[q] - bk[q - 1] < 0.5);
+        TL_LANES_END
+        const uint64_t cm = TL_BALLOT(closep);
+        if (cm != 0ull) {
+            const bool do0 = (cm & 0xffffffffull) != 0ull, do1 = (cm >> 32) != 0ull;
+            double *X0 = TL_P1B_MKX(w), *B0 = TL_P1B_MKBARK(w), *X1 = TL_MK_X(w), *B1 = TL_MK_BARK(w);
+            const int t0 = do0 ? r.ntone0 : 0, t1 = do1 ? r.ntone1 : 0;
+            int n0 = 0, n1 = 0;           // compacted in place: entries [0,n) are final, (xi,bi) is the current survivor
+            double xi0 = X0[0], bi0 = B0[0], xi1 = X1[0], bi1 = B1[0];
+            for (int q = 1; q < (t0 > t1 ? t0 : t1); q++) {
+                if (q < t0) {
+                    const double xn = X0[q], bn = B0[q];
+                    if (bn - bi0 < 0.5) {
+                        if (xn > xi0) { xi0 = xn; bi0 = bn; }
+                    } else { X0[n0] = xi0; B0[n0] = bi0; n0++; xi0 = xn; bi0 = bn; }
+                }
+                if (q < t1) {
+                    const double xn = X1[q], bn = B1[q];
+                    if (bn - bi1 < 0.5) {
+                        if (xn > xi1) { xi1 = xn; bi1 = bn; }
+                    } else { X1[n1] = xi1; B1[n1] = bi1; n1++; xi1 = xn; bi1 = bn; }
+                }
+            }
+            if (do0) { X0[n0] = xi0; B0[n0] = bi0; r.ntone0 = n0 + 1; }
+            if (do1) { X1[n1] = xi1; B1[n1] = bi1; r.ntone1 = n1 + 1; }
+            TL_SYNC();
+        }
+    }
+    // noise: band order, keep if not below the threshold in quiet (psycho_1.c:429-442)
+    {
+        PV(bool, keepn);
+        TL_LANES_BEGIN
+        L(keepn) = (lane & 31) < nbands && !(L(nlev) < L(nhear0));
+        TL_LANES_END
+        const uint64_t mn = TL_BALLOT(keepn);
+        TL_LANES_BEGIN
+        if ((mn >> lane) & 1ull) {
+            const bool second = lane >= 32;
+            const int pos = (second ? r.ntone1 : r.ntone0) + __builtin_popcountll(mn & ((1ull << lane) - 1ull) & (second ? ~0xffffffffull : 0xffffffffull));
+            (second ? TL_MK_X(w) : TL_P1B_MKX(w))[pos] = L(nlev); (second ? TL_MK_BARK(w) : TL_P1B_MKBARK(w))[pos] = L(nbk0);
+        }
+        TL_LANES_END
+        r.nnoise0 = __builtin_popcountll(mn & 0xffffffffull); r.nnoise1 = __builtin_popcountll(mn >> 32);
+    }
+    return r;
+}
+
 // the dead-head replay (see tl_psy1_front): works on power[] (px) and the shared links like the reference
 TL_FN void tl_psy1_deadhead(TlPsyLds &w, const double *TL_RESTRICT db, const TlConfig *TL_RESTRICT C, int ch, const TlPsy1Ch &st, PARGA(double, rec, 4), long long *sp)
 {
@@ -845,8 +1011,10 @@ TL_FN void tl_psy1(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double *TL_
 }
 
 // Both channels of a stereo frame.  Order: front(0) -> park channel 0's front results in registers -> front(1) -> the weight
-// sums of both channels side by side -> the dB-sum chains of both channels side by side -> back(1) -> channel 0's results
-// return to the LDS arrays -> back(0).
+// sums of both channels side by side -> the dB-sum chains of both channels side by side -> channel 0's tone records to the top of
+// the (now dead) transform buffer -> band centres and decimation of both channels side by side -> thresholds(1) -> channel 0's
+// masker list moves into place -> thresholds(0).  A frame with more than TL_P1B_LIST tones in either list takes the older order
+// after the chains: back(1) -> channel 0's results return to the LDS arrays -> back(0).
 // Parked: the compacted levels and weight terms (<= 466 doubles each: 8 per lane), the tone records (conf_c, tlist, tone_x), the
 // band ranges.  ptype[] is not parked: after the tone labelling a line is TONE exactly if it is the line
 // of a confirmed tone that was not erased by its successor, so it is rebuilt from conf_c.  A dead-head channel (see
@@ -858,6 +1026,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     long long *sp0 = sp ? sp + 8 : nullptr, *sp1 = sp ? sp + 16 : nullptr;
     const TlPsy1Ch s0 = tl_psy1_front(w, T, db, C, pv, 0, rec, sp0);
     if (s0.dead_head) {                                               // plain order for both channels
+        TL_DBG_BACK(4);
         tl_psy1_finish(w, db, C, 0, s0, rec, sp0);
         tl_psy1(w, T, db, C, pv, 1, rec, sp1);
         return;
@@ -884,8 +1053,9 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     // ---- channel 1's front; a dead-head channel 1 is finished in the plain order first ----
     const TlPsy1Ch s1 = tl_psy1_front(w, T, db, C, pv, 1, rec, sp1);
     PV(double, bsum); PV(double, wt); PV(int, blo); PV(int, bhi);
-    tl_psy1_limits(C, nbands, blo, bhi);                              // (used after the chains, by both channels' centres)
+    tl_psy1_limits2(C, nbands, blo, bhi);                             // (used after the chains, by both channels' centres: band b on lanes b and 32 + b)
     if (s1.dead_head) {
+        TL_DBG_BACK(5);
         tl_psy1_finish(w, db, C, 1, s1, rec, sp1);
         TL_LANES_BEGIN
 #ifndef TL_EMULATE
@@ -923,7 +1093,41 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
         TL_STAMP(sp1, 4);
         if (TL_EXP_LEVEL < 3) { TL_PRIO(1); tl_psy1_chain2(w, db, nbands, r0, r1, bsum); TL_PRIO(0); }
         TL_STAMP(sp0, 4);                                               // both channels' chains: sp1[4] -> sp0[4]
-        // ---- back(1): its sums and weights move from lanes 32+b to lanes b ----
+        if (s0.nlist <= TL_P1B_LIST && s1.nlist <= TL_P1B_LIST) {
+            // ---- centres and decimation of both channels in one pass on the halves, then both thresholds back to back.  The levels and
+            //      terms in the transform buffer are dead: channel 0's tone records leave their registers for its top (TL_P1B_*), with its
+            //      line types rebuilt from conf_c, so that both channels' small records are resident at once ----
+            TL_DBG_BACK(0);
+            PV(int, ncen); PV(bool, ontone);
+            TlPsy1Mk2 mk = {0, 0, 0, 0};
+            if (TL_EXP_LEVEL < 3) {
+                TL_LANES_BEGIN
+                ((double *)TL_P1B_PTYPE(w))[lane] = 0.0;                // 520 bytes of zeros
+                if (lane == 0) ((double *)TL_P1B_PTYPE(w))[64] = 0.0;
+                const int hi = 64 + lane < TL_TONE_MAX ? 64 + lane : 0;
+                TL_P1B_CONF_C(w)[lane] = (int16_t)(L(pcc) & 0xffff); TL_P1B_TONE_X(w)[lane] = L(ptx0);
+                if (64 + lane < TL_TONE_MAX) { TL_P1B_CONF_C(w)[hi] = (int16_t)((uint32_t)L(pcc) >> 16); TL_P1B_TONE_X(w)[hi] = L(ptx1); }
+                TL_LANES_END
+                TL_LANES_BEGIN
+                if (lane < s0.nconf) { const int cc = L(pcc) & 0xffff; if (!((cc >> 13) & 1)) TL_P1B_PTYPE(w)[cc & 511] = TL_T_TONE; }
+                if (64 + lane < s0.nconf) { const int cc = (int)((uint32_t)L(pcc) >> 16); if (!((cc >> 13) & 1)) TL_P1B_PTYPE(w)[cc & 511] = TL_T_TONE; }
+                TL_LANES_END
+                tl_psy1_centres2(w, nbands, bsum, wt, blo, bhi, ncen, ontone);
+                if (TL_EXP_LEVEL < 2) mk = tl_psy1_decimate2(w, C, nbands, s0.nlist, s1.nlist, ptl, bsum, ncen, ontone);
+            }
+            tl_psy1_thresholds(w, db, C, 1, mk.ntone1, mk.nnoise1, rec, sp1);
+            // channel 0's masker list moves to where the thresholds read it (at most TL_P1B_LIST + 27 <= 64 entries)
+            TL_LANES_BEGIN
+            if (lane < mk.ntone0 + mk.nnoise0) {
+                const double x = TL_P1B_MKX(w)[lane], bk = TL_P1B_MKBARK(w)[lane];
+                TL_MK_X(w)[lane] = x; TL_MK_BARK(w)[lane] = bk;
+            }
+            TL_LANES_END
+            tl_psy1_thresholds(w, db, C, 0, mk.ntone0, mk.nnoise0, rec, sp0);
+            return;
+        }
+        TL_DBG_BACK(1);
+        // ---- a tone list too long for a half: the per-channel order.  back(1): its sums and weights move from lanes 32+b to lanes b ----
         PV(double, bsum1); PV(double, wt1);
 #ifdef TL_EMULATE
         for (int lane = 0; lane < 64; ++lane) { bsum1[lane] = bsum[(lane + 32) & 63]; wt1[lane] = wt[(lane + 32) & 63]; }

@@ -295,7 +295,14 @@ static long tl_dbg_rounds = 0, tl_dbg_tones = 0, tl_dbg_deadheads = 0, tl_dbg_fr
 #define TL_DBG_CAND(n) (tl_dbg_cands += (n))
 #define TL_DBG_ROUND() (tl_dbg_rounds++)
 #define TL_DBG_TONES(n, dh) (tl_dbg_tones += (n), tl_dbg_deadheads += (dh) ? 1 : 0, tl_dbg_fronts++)
+// which way stereo psy-1 frames went (tl_psy1_stereo) -- 0: paired centres and decimation, 1: a tone list too long for a half, 2: paired, a
+// band's centre fell on a tone's line and moved off it (per band), 3: paired with two bands sharing a centre, 4 / 5: channel 0's / channel
+// 1's dead head, 6: paired with a centre still on a tone's line after the move (its level then replaces the tone's)
+static long tl_dbg_back[7] = {0, 0, 0, 0, 0, 0, 0};
+#define TL_DBG_BACK(k) (tl_dbg_back[k]++)
+extern "C" __attribute__((weak, visibility("default"))) void emu_back_stats(long *out) { for (int i = 0; i < 7; i++) out[i] = tl_dbg_back[i]; }
 #else
+#define TL_DBG_BACK(k) ((void)0)
 #define TL_DBG_DUMP(tag, ch, nt, nn, x, b) ((void)0)
 #define TL_DBG_WALK(ch, lane, cnt) ((void)0)
 #define TL_DBG_ROUND() ((void)0)
@@ -410,6 +417,18 @@ struct TlPsyLds {
 struct TlMasker { double bark, av, g, c17, n; };
 #define TL_MK4(w) ((TlMasker *)((w).u.fft + 2 * TL_MASKER_MAX + 136))   /* [TL_MASKER_MAX], ends at fft[1032] */
 static_assert(2 * TL_MASKER_MAX + 136 + 5 * TL_MASKER_MAX <= TL_FFT_WORDS, "masker records fit the transform buffer");
+// psy 1, two channels with the paired centres and decimation (tl_psy1_stereo): channel 0's small records and its waiting masker list live
+// in the top of the transform buffer, dead after the dB-sum chains.  That path only runs with at most TL_P1B_LIST tones per channel, so a
+// channel has at most TL_P1B_LIST + 27 maskers and channel 1's thresholds end their masker records below TL_P1B_BASE.
+#define TL_P1B_LIST 32
+#define TL_P1B_BASE 700
+#define TL_P1B_MKX(w) ((w).u.fft + TL_P1B_BASE)                     /* [64] channel 0's masker levels until channel 1's thresholds are done */
+#define TL_P1B_MKBARK(w) ((w).u.fft + TL_P1B_BASE + 64)             /* [64] */
+#define TL_P1B_TONE_X(w) ((w).u.fft + TL_P1B_BASE + 128)            /* [TL_TONE_MAX] */
+#define TL_P1B_PTYPE(w) ((uint8_t *)((w).u.fft + TL_P1B_BASE + 128 + TL_TONE_MAX))                /* [520]: 65 doubles */
+#define TL_P1B_CONF_C(w) ((int16_t *)((w).u.fft + TL_P1B_BASE + 128 + TL_TONE_MAX + 65))         /* [TL_TONE_MAX]: 20 doubles */
+static_assert(TL_P1B_LIST + 27 <= 64 && 2 * TL_MASKER_MAX + 136 + 5 * (TL_P1B_LIST + 27) <= TL_P1B_BASE, "channel 1's masker records end below channel 0's records");
+static_assert(TL_P1B_BASE + 128 + TL_TONE_MAX + 65 + (2 * TL_TONE_MAX + 7) / 8 <= TL_FFT_WORDS, "channel 0's records fit the transform buffer");
 
 
 

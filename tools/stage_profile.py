@@ -64,10 +64,16 @@ if psy in (1, 3) and mode != "m":
            ("dB-sum chains, BOTH channels", c1 + 4, c0 + 4),
            ("ch1 centres + decimation", c0 + 4, c1 + 5), ("ch1 thresholds", c1 + 5, c1 + 6),
            ("ch0 resumed: centres + decimation", c1 + 6, c0 + 5), ("ch0 thresholds", c0 + 5, c0 + 6)]
+    if psy == 1:
+        # psy 1: channel 0's records return right after the chains and ONE pass does both channels' centres and decimation (tl_psy1_centres2,
+        # tl_psy1_decimate2); between the two thresholds only channel 0's masker list moves into place.  (Frames with more than 32 tones in
+        # a list or a dead head take the per-channel order and blur the means slightly.)
+        seq[-4] = ("BOTH channels: ch0 un-park, centres + decimation", c0 + 4, c1 + 5)
+        seq[-2] = ("ch0 masker list into place", c1 + 6, c0 + 5)
     print("  model phase in running order (ticks per unit, share of encode + psy):")
     for n, a, b_ in seq:
         d = (st[..., b_] - st[..., a]).mean()
-        print(f"    {n:36s} {d:10.0f}  {100 * d / tot:5.1f}%")
+        print(f"    {n:48s} {d:10.0f}  {100 * d / tot:5.1f}%")
 else:
     rows_per_channel()
 if st[..., 25].max() > 0:
