@@ -7,7 +7,9 @@
 //        -> whole frames -> file                          (what src/odr-audioenc.cpp:1208-1225 re-frames out of the bursts)
 //
 // build: g++ -O2 -std=c++17 examples/mp2enc.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o mp2enc
-// usage: mp2enc in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams]
+// usage: mp2enc in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [--verify]
+// --verify: every frame is read back on the device right after it was encoded (tlb_decode_host: header, CRC-16, ScF-CRC, bit budget);
+// any TLB_DEC_BAD_MASK flag ends the run with exit status 3.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -27,15 +29,18 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [--verify]\n", argv[0]);
         return 2;
     }
     long rate = 48000;
     int channels = 2, kbps = 128, psy = 1, nstreams = 1;
     char mode = 0;
     double gain_db = 0.0;
-    for (int i = 3; i + 1 < argc; i += 2) {
+    bool verify = false;
+    for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
+        if (k == "--verify") { verify = true; i -= 1; continue; }
+        if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") rate = std::atol(v);
         else if (k == "-c") channels = std::atoi(v);
@@ -78,7 +83,21 @@ int main(int argc, char **argv)
     std::vector<int16_t> inter((size_t)chunk * nstreams * 2304), pcm((size_t)chunk * nstreams * 2304), peaks((size_t)chunk * nstreams * 2);
     std::vector<uint8_t> out((size_t)chunk * nstreams * stride);
     std::vector<int32_t> len((size_t)chunk * nstreams);
-    long written = 0;
+    long written = 0, checked = 0;
+    std::vector<tlb_frame_report> report(verify ? (size_t)chunk * nstreams : 0);
+    // TEST-ONLY hook of this example (tests/test_decode_gpu.py): a byte offset into the first call's frame buffer, flipped before the check
+    const char *corrupt = std::getenv("MP2ENC_TEST_CORRUPT");
+    auto check = [&](const uint8_t *frames, const int32_t *lens, int nf) {
+        if ((err = tlb_decode_host(enc, frames, lens, nf, report.data(), nullptr, nullptr)) != TLB_OK) die("tlb_decode_host", err);
+        for (size_t i = 0; i < (size_t)nf * nstreams; i++) {
+            if (report[i].status & TLB_DEC_BAD_MASK) {
+                std::fprintf(stderr, "mp2enc: verify failed: frame slot %zu, status 0x%x (CRC-16 stored %04x, computed %04x)\n", i, report[i].status,
+                             report[i].crc_stored, report[i].crc_computed);
+                std::exit(3);
+            }
+            checked += !(report[i].status & TLB_DEC_EMPTY);
+        }
+    };
     const auto t0 = std::chrono::steady_clock::now();
     for (int f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = nframes - f0 < chunk ? nframes - f0 : chunk;
@@ -87,6 +106,10 @@ int main(int argc, char **argv)
                 std::memcpy(&inter[((size_t)f * nstreams + s) * 2304], &in[(size_t)(f0 + f) * per_frame], per_frame * sizeof(int16_t));
         if ((err = tlb_ingest_host(enc, inter.data(), nf, pcm.data(), peaks.data())) != TLB_OK) die("tlb_ingest_host", err);
         if ((err = tlb_encode_host_len(enc, pcm.data(), nf, nullptr, nullptr, out.data(), len.data(), nullptr)) != TLB_OK) die("tlb_encode_host_len", err);
+        if (verify) {
+            if (corrupt && f0 == 0 && (size_t)std::atol(corrupt) < out.size()) out[(size_t)std::atol(corrupt)] ^= 0x10;
+            check(out.data(), len.data(), nf);
+        }
         for (int f = 0; f < nf; f++) {                       // stream 0 goes to the file; slot f = the frame before input frame f (length 0: none yet)
             const size_t slot = (size_t)f * nstreams;
             if (len[slot] > 0) { std::fwrite(&out[slot * stride], 1, (size_t)len[slot], fo); written += len[slot]; }
@@ -96,12 +119,14 @@ int main(int argc, char **argv)
         std::vector<uint8_t> last((size_t)nstreams * stride);
         std::vector<int32_t> llen((size_t)nstreams);
         if ((err = tlb_flush_host_len(enc, last.data(), llen.data())) != TLB_OK) die("tlb_flush_host_len", err);
+        if (verify) check(last.data(), llen.data(), 1);
         if (llen[0] > 0) { std::fwrite(last.data(), 1, (size_t)llen[0], fo); written += llen[0]; }
     }
     const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fclose(fo);
     std::fprintf(stderr, "mp2enc: %d frames x %d stream(s) in %.3f s = %.0f frames/s (%.0f x real time per stream); %ld bytes written; %s\n",
                  nframes, nstreams, dt, (double)nframes * nstreams / dt, (double)nframes * 1152.0 / (double)rate / dt, written, tlb_version());
+    if (verify) std::fprintf(stderr, "mp2enc: verify ok: %ld frames read back on the device, %ld bad\n", checked, tlb_decode_bad_frames(enc));
     tlb_destroy(enc);
     return 0;
 }

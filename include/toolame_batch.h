@@ -499,6 +499,57 @@ int tlb_node_encode_device(tlb_node *nd, const int16_t *const *d_pcm, int nframe
 int tlb_node_flush_device(tlb_node *nd, uint8_t *const *d_out, int32_t *const *d_out_len);
 int tlb_node_sync(tlb_node *nd);
 
+/* ---------------------------------------------------------------------------------------------
+ * Frame check and decode: the confidence monitor for the batch's OWN frames.
+ * tlb_decode_*() reads frames as tlb_encode_*_len / tlb_flush_*_len leave them -- slot stride tlb_out_stride(), a length per slot,
+ * 0 = empty slot -- and checks each against the configuration of the stream it belongs to; on request it also hands back the parsed
+ * fields and the decoded audio.  One wavefront per (stream, slot); nothing is shipped to the host unless the host variant is used.
+ *   d_frames uint8  [nframes][nstreams][tlb_out_stride()]
+ *   d_len    int32  [nframes][nstreams] or NULL: every slot holds a frame (of the length its padding bit and configuration say)
+ *   d_report tlb_frame_report [nframes][nstreams]
+ *   d_fields tlb_frame_fields [nframes][nstreams] or NULL: bit_alloc / scfsi / scalar / subband in the layout of the encoder's stage
+ *            taps; cells the frame does not transmit are 0 (a joint-stereo cell above the bound: samples under channel 0 only)
+ *   d_pcm    int16  [nframes][nstreams][2][1152] or NULL: planar like the encoder's input; a mono stream fills channel 0 (channel 1: zeros)
+ * status is a set of independent flags.  A frame "passes" when none of TLB_DEC_BAD_MASK and not EMPTY is set.
+ *   - the header is compared field by field with the stream's configuration; a joint-stereo stream's frames may be stereo or joint
+ *     stereo with any bound (the encoder chooses per frame).  A slot longer than its frame is a HEADER_MISMATCH, a shorter one OVERRUN.
+ *   - CRC-16 over header bits 16..31, bit_alloc and scfsi; stored and computed value are both reported.
+ *   - DAB ScF-CRC: the bytes protecting frame n's scalefactors travel in the tail of frame n-1 (toolame.c:527-542), so frame n is checked
+ *     against the last non-empty slot before it (in this call or, for the call's first frames, the call before).  Where there is none --
+ *     the first frame after creation or a reset -- or that slot was too short to hold its tail, the flag is SCFCRC_UNCHECKED, not an error.
+ *   - bit budget: header + CRC + allocation + scfsi + scalefactors + samples + the smallest PAD (ScF-CRC + F-PAD) must fit the frame.
+ *     No read leaves the slot whatever its bytes say.
+ * PCM: requantisation by ISO/IEC 11172-3 2.4.3.3.4, synthesis filterbank by Annex 3-A.2 in fp64, rounded to nearest, saturated.  A frame
+ * that did not pass, or an empty slot, yields 1152 zero samples per channel and counts as silence for its successor's filter history.
+ * The output does not depend on how a stream's frames are cut into calls: a call leaves the stream's last slot behind for the next.
+ * That state and the decoder's tables are allocated by the first decode call: a batch that never decodes pays nothing.
+ * Asynchronous on `hip_stream` like tlb_encode_device; decode calls of one batch must be ordered on one stream (the very first decode
+ * call of a batch also waits for the device once, while it uploads its tables).  Every buffer must be 4-byte aligned (hipMalloc'ed
+ * memory is): frames and PCM move as 32-bit words.  Argument errors -- a NULL batch, frames or report pointer, nframes <= 0, a
+ * misaligned pointer -- return TLB_ERR_ARG and change nothing.
+ *   tlb_decode_reset(b, stream)  the stream's next frame is "first after a reset" again (stream = -1: all); tlb_reset, tlb_stream_reset,
+ *                                tlb_stream_finish and tlb_stream_reconfigure do the same for the streams they touch
+ *   tlb_decode_bad_frames(b)     frames with any TLB_DEC_BAD_MASK flag since creation (waits for the device; < 0: -TLB_ERR_*)
+ * Note on tlb_stream_finish: it resets the stream BEFORE the caller holds the frame it returns, so that frame, decoded afterwards, is a
+ * "first frame" (SCFCRC_UNCHECKED, silent filter history) -- unlike the same frame obtained through tlb_flush_*, which resets nothing.
+ * A caller that wants the last frame checked against its predecessor flushes (or decodes the pending frame's slot) before finishing.
+ * Where lengths are given, a frame whose slot length and padding bit disagree (cut short, or its padding bit damaged) cannot be trusted
+ * to hold its tail where expected: its successor is SCFCRC_UNCHECKED rather than falsely BAD_SCFCRC.
+ * ------------------------------------------------------------------------------------------ */
+enum {
+    TLB_DEC_EMPTY = 0x01, TLB_DEC_BAD_SYNC = 0x02, TLB_DEC_HEADER_MISMATCH = 0x04, TLB_DEC_BAD_CRC16 = 0x08, TLB_DEC_BAD_SCFCRC = 0x10,
+    TLB_DEC_SCFCRC_UNCHECKED = 0x20, TLB_DEC_BAD_ALLOC = 0x40, TLB_DEC_OVERRUN = 0x80,
+    TLB_DEC_BAD_MASK = 0x02 | 0x04 | 0x08 | 0x10 | 0x40 | 0x80,
+};
+typedef struct { uint32_t status; uint16_t crc_stored, crc_computed; uint8_t mode, mode_ext; uint16_t audio_bits; } tlb_frame_report;
+typedef struct { uint8_t bit_alloc[2][32], scfsi[2][32], scalar[2][3][32]; uint16_t subband[2][3][12][32]; } tlb_frame_fields;
+int tlb_decode_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, tlb_frame_report *d_report,
+                      tlb_frame_fields *d_fields, int16_t *d_pcm, void *hip_stream);
+int tlb_decode_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int nframes, tlb_frame_report *report,
+                    tlb_frame_fields *fields, int16_t *pcm);
+int tlb_decode_reset(tlb_batch *b, int stream);
+long tlb_decode_bad_frames(const tlb_batch *b);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

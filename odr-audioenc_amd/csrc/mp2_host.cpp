@@ -36,6 +36,23 @@ double freq2bark(double freq)                      // ath.c:73-78
 }
 }  // namespace
 
+// Decode path (mp2_synth.h).  N[i][k] = cos((16 + i)(2k + 1) pi / 64) and D[i] = 32 C[i] are Annex 3-A.2's; C and D of the requantisation are
+// table 3-B.4's decimals as printed there, indexed by the quantiser class of TL_STEPS (3, 5, 7, 9, 15 ... 65535 steps).
+void tl_build_synth_tables(TlSynthTables *Y)
+{
+    static const double rq_c[18] = {0, 1.33333333333, 1.60000000000, 1.14285714286, 1.77777777777, 1.06666666666, 1.03225806452, 1.01587301587,
+                                    1.00787401575, 1.00392156863, 1.00195694716, 1.00097751711, 1.00048851979, 1.00024420024, 1.00012208522,
+                                    1.00006103888, 1.00003051851, 1.00001525902};
+    static const double rq_d[18] = {0, 0.50000000000, 0.50000000000, 0.25000000000, 0.50000000000, 0.12500000000, 0.06250000000, 0.03125000000,
+                                    0.01562500000, 0.00781250000, 0.00390625000, 0.00195312500, 0.00097656250, 0.00048828125, 0.00024414063,
+                                    0.00012207031, 0.00006103516, 0.00003051758};
+    memset(Y, 0, sizeof *Y);
+    for (int i = 0; i < 64; i++)
+        for (int k = 0; k < 32; k++) Y->n[k][i] = cos((double)((16 + i) * (2 * k + 1)) * M_PI / 64.0);
+    for (int i = 0; i < 512; i++) Y->d[i] = 32.0 * ((double)TL_ENWINDOW_E9[i] / 1e9);
+    for (int q = 0; q < 18; q++) { Y->rq_c[q] = rq_c[q]; Y->rq_d[q] = rq_d[q]; }
+}
+
 void tl_build_tables(TlTables *T)
 {
     memset(T, 0, sizeof *T);

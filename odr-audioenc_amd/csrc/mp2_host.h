@@ -7,6 +7,7 @@
 // reference computes them -- and uploaded to HBM; the per-frame device path never calls libm.
 #pragma once
 #include "mp2_types.h"
+#include "mp2_dec_types.h"
 
 // error codes of tl_build_config (non-zero like the reference's setters, toolame.h:9-10)
 enum {
@@ -19,6 +20,8 @@ enum {
 };
 
 void tl_build_tables(TlTables *T);
+// decode path: synthesis matrix (host cos, as the analysis matrix), synthesis window D = 32 C, requantisation constants (ISO/IEC 11172-3 table 3-B.4)
+void tl_build_synth_tables(TlSynthTables *Y);
 // psy-2 tables for a sample rate (48000/32000/24000/16000); returns the table slot 0..2 used as TlConfig::psy2_tab
 #define TL_PSY2_SLOTS 6      // sample rates with their own psy-2 / psy-4 tables: 48, 32, 24, 16, 44.1, 22.05 kHz
 int tl_psy2_slot(long samplerate);

@@ -1,5 +1,5 @@
 // tl_kernels.h -- the one door between the host translation units (tlb_batch.cpp, tlb_egress.cpp, tlb_tick.cpp: plain C++, seconds to
-// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
+// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
 // `st` and returns hipGetLastError(); grid shapes that depend on the kernels' wave counts are computed from the constants below.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -8,6 +8,7 @@
 
 #include "mp2_types.h"
 #include "edi_types.h"
+#include "mp2_dec_types.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -33,4 +34,6 @@ hipError_t tlk_edi_af(unsigned bx, unsigned by, hipStream_t st, const TlEdiArgs 
 hipError_t tlk_edi_pft(unsigned bx, unsigned by, hipStream_t st, const TlPftArgs &A, const TlTables *T);
 hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state, const TlConfig *configs, const int32_t *stream_cfg,
                      uint8_t *out, int32_t *out_len, int nstreams, int out_stride);
+// toolame_dec.hip: tl_unpack_kernel over every (stream, slot) of the launch, tl_synth_kernel when A.pcm is set, then tl_dec_carry_kernel per stream
+hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

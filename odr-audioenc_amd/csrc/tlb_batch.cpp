@@ -52,6 +52,10 @@ void tlb_destroy(tlb_batch *b)
     if (b->d_psy2_state) (void)hipFree(b->d_psy2_state);
     if (b->d_chain) (void)hipFree(b->d_chain);
     if (b->d_partner) (void)hipFree(b->d_partner);
+    if (b->d_synth) (void)hipFree(b->d_synth);
+    if (b->d_dec_state) (void)hipFree(b->d_dec_state);
+    if (b->d_dec_prev) (void)hipFree(b->d_dec_prev);
+    if (b->d_dec_bad) (void)hipFree(b->d_dec_bad);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_mid) (void)hipEventDestroy(b->ev_mid);
@@ -188,6 +192,7 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
     if (b->d_newlag) HIPCHK(hipMemset(b->d_newlag + s0, 0, sizeof(double) * (size_t)n));
     if (b->d_edi_state_tmp) HIPCHK(hipMemset(b->d_edi_state_tmp + s0, 0, sizeof(TlEdiState) * (size_t)n));
     if (b->d_pseq_tmp) HIPCHK(hipMemset(b->d_pseq_tmp + s0, 0, sizeof(uint16_t) * (size_t)n));
+    if (b->d_dec_state) HIPCHK(hipMemset(b->d_dec_state + s0, 0, sizeof(TlDecStream) * (size_t)n));      // the decoder's next frame of these streams is a first frame
     return TLB_OK;
 }
 

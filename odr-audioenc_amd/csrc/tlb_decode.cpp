@@ -1,0 +1,106 @@
+// tlb_decode.cpp -- the frame check / decode entry points of include/toolame_batch.h (tlb_decode_*): argument checks, the decoder's tables
+// and per-stream state (allocated by the first call), one launch of the kernels of toolame_dec.hip through tl_kernels.h.  Host C++.
+#include "tlb_internal.h"
+
+static_assert(TLB_DEC_EMPTY == TL_DEC_EMPTY && TLB_DEC_BAD_SYNC == TL_DEC_BAD_SYNC && TLB_DEC_HEADER_MISMATCH == TL_DEC_HEADER_MISMATCH &&
+              TLB_DEC_BAD_CRC16 == TL_DEC_BAD_CRC16 && TLB_DEC_BAD_SCFCRC == TL_DEC_BAD_SCFCRC && TLB_DEC_SCFCRC_UNCHECKED == TL_DEC_SCFCRC_UNCHECKED &&
+              TLB_DEC_BAD_ALLOC == TL_DEC_BAD_ALLOC && TLB_DEC_OVERRUN == TL_DEC_OVERRUN && TLB_DEC_BAD_MASK == TL_DEC_BAD_MASK, "status flags");
+static_assert(sizeof(tlb_frame_report) == sizeof(TlFrameReport) && sizeof(tlb_frame_fields) == sizeof(TlFrameFields), "C-ABI records");
+
+static int dec_prepare(tlb_batch *b)
+{
+    if (b->d_dec_bad) return TLB_OK;
+    const size_t n = (size_t)b->nstreams;
+    if (!b->d_synth) {
+        TlSynthTables *hy = new TlSynthTables;
+        tl_build_synth_tables(hy);
+        hipError_t e = hipMalloc(&b->d_synth, sizeof(TlSynthTables));
+        if (e == hipSuccess) e = hipMemcpy(b->d_synth, hy, sizeof(TlSynthTables), hipMemcpyHostToDevice);
+        delete hy;
+        HIPCHK(e);
+    }
+    if (!b->d_dec_state) {
+        HIPCHK(hipMalloc(&b->d_dec_state, sizeof(TlDecStream) * n));
+        HIPCHK(hipMemset(b->d_dec_state, 0, sizeof(TlDecStream) * n));
+    }
+    if (!b->d_dec_prev) {
+        HIPCHK(hipMalloc(&b->d_dec_prev, n * (size_t)b->out_stride));
+        HIPCHK(hipMemset(b->d_dec_prev, 0, n * (size_t)b->out_stride));
+    }
+    unsigned long long *bad = nullptr;
+    HIPCHK(hipMalloc(&bad, sizeof *bad));
+    if (hipMemset(bad, 0, sizeof *bad) != hipSuccess) { (void)hipFree(bad); return TLB_ERR_HIP; }
+    // the copies and memsets above ran on the null stream; the caller's stream may be a non-blocking one that nothing orders behind
+    // them, so the first call (only) waits for the device here
+    if (hipDeviceSynchronize() != hipSuccess) { (void)hipFree(bad); return TLB_ERR_HIP; }
+    b->d_dec_bad = bad;                          // last: its presence says that everything above is there
+    return TLB_OK;
+}
+
+extern "C" {
+
+int tlb_decode_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, tlb_frame_report *d_report,
+                      tlb_frame_fields *d_fields, int16_t *d_pcm, void *hip_stream)
+{
+    if (!b || !d_frames || !d_report || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
+    // the kernels move frames and PCM as 32-bit words and store 32-bit report fields
+    if (((uintptr_t)d_frames | (uintptr_t)d_report | (uintptr_t)d_len | (uintptr_t)d_fields | (uintptr_t)d_pcm) & 3u) return TLB_ERR_ARG;
+    if (b->broken) return TLB_ERR_HIP;           // the device's stream -> configuration table may disagree with the host's (tlb_reset)
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = dec_prepare(b)) return rc;
+    TlDecLaunch A;
+    memset(&A, 0, sizeof A);
+    A.tables = b->d_tables; A.configs = b->d_configs; A.stream_cfg = b->h_configs.size() == 1 ? nullptr : b->d_stream_cfg;
+    A.synth = b->d_synth; A.frames = d_frames; A.len = d_len;
+    A.report = (TlFrameReport *)d_report; A.fields = (TlFrameFields *)d_fields; A.pcm = d_pcm;
+    A.state = b->d_dec_state; A.prev = b->d_dec_prev; A.bad = b->d_dec_bad;
+    A.nstreams = b->nstreams; A.nframes = nframes; A.out_stride = b->out_stride;
+    HIPCHK(tlk_decode((hipStream_t)hip_stream, A));
+    return TLB_OK;
+}
+
+int tlb_decode_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int nframes, tlb_frame_report *report,
+                    tlb_frame_fields *fields, int16_t *pcm)
+{
+    if (!b || !frames || !report || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t slots = (size_t)nframes * (size_t)b->nstreams;
+    DevFree guard_;
+    uint8_t *d_frames = nullptr; int32_t *d_len = nullptr; tlb_frame_report *d_report = nullptr; tlb_frame_fields *d_fields = nullptr; int16_t *d_pcm = nullptr;
+    DEVALLOC(d_frames, slots * (size_t)b->out_stride);
+    DEVALLOC(d_report, slots * sizeof(tlb_frame_report));
+    if (len) DEVALLOC(d_len, slots * sizeof(int32_t));
+    if (fields) DEVALLOC(d_fields, slots * sizeof(tlb_frame_fields));
+    if (pcm) DEVALLOC(d_pcm, slots * 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t));
+    HIPCHK(hipMemcpy(d_frames, frames, slots * (size_t)b->out_stride, hipMemcpyHostToDevice));
+    if (len) HIPCHK(hipMemcpy(d_len, len, slots * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (int rc = tlb_decode_device(b, d_frames, d_len, nframes, d_report, d_fields, d_pcm, nullptr)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(report, d_report, slots * sizeof(tlb_frame_report), hipMemcpyDeviceToHost));
+    if (fields) HIPCHK(hipMemcpy(fields, d_fields, slots * sizeof(tlb_frame_fields), hipMemcpyDeviceToHost));
+    if (pcm) HIPCHK(hipMemcpy(pcm, d_pcm, slots * 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost));
+    return TLB_OK;
+}
+
+int tlb_decode_reset(tlb_batch *b, int stream)
+{
+    if (!b || stream < -1 || stream >= b->nstreams) return TLB_ERR_ARG;
+    if (!b->d_dec_state) return TLB_OK;          // never decoded: every stream's next frame is a first frame already
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (stream < 0) HIPCHK(hipMemset(b->d_dec_state, 0, sizeof(TlDecStream) * (size_t)b->nstreams));
+    else HIPCHK(hipMemset(b->d_dec_state + stream, 0, sizeof(TlDecStream)));
+    return TLB_OK;
+}
+
+long tlb_decode_bad_frames(const tlb_batch *b)
+{
+    if (!b) return -TLB_ERR_ARG;
+    if (!b->d_dec_bad) return 0;
+    unsigned long long n = 0;
+    if (hipSetDevice(b->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(&n, b->d_dec_bad, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return -TLB_ERR_HIP;
+    return (long)n;
+}
+
+}  // extern "C"

@@ -65,6 +65,11 @@ struct tlb_batch {
     bool broken = false;                         // a launch or a reconfiguration failed half way: stream state, psy-2 state copies and lists may disagree;
                                                  // every further launch is refused (TLB_ERR_HIP) until tlb_reset() has put all streams back to zero
     int num_cu = 256;
+    // frame check / decode (tlb_decode.cpp): tables and per-stream state, allocated by the first decode call
+    TlSynthTables *d_synth = nullptr;
+    TlDecStream *d_dec_state = nullptr;          // [nstreams]
+    uint8_t *d_dec_prev = nullptr;               // [nstreams][out_stride] the last slot of the call before
+    unsigned long long *d_dec_bad = nullptr;     // frames with a TL_DEC_BAD_MASK flag since creation
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
 };
 

@@ -204,6 +204,12 @@ def _bind(L):
     L.tlb_node_copy_out.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     L.tlb_node_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tlb_node_flush_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "tlb_decode_device"):           # frame check / decode (an older build loaded through TLB_LIB_PATH has none of it)
+        L.tlb_decode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_decode_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_decode_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_decode_bad_frames.argtypes = [C.c_void_p]
+        L.tlb_decode_bad_frames.restype = C.c_long
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -252,6 +258,15 @@ TAPS_DTYPE = np.dtype([
     ("adb_left", np.int32), ("mode", np.int32), ("mode_ext", np.int32), ("jsbound", np.int32), ("crc16", np.int32),
     ("scfcrc", np.uint8, (4,)), ("pad_", np.int32, (2,)),
 ])
+
+
+# tlb_frame_report / tlb_frame_fields (include/toolame_batch.h) and the status flags
+FRAME_REPORT_DTYPE = np.dtype([("status", np.uint32), ("crc_stored", np.uint16), ("crc_computed", np.uint16), ("mode", np.uint8),
+                               ("mode_ext", np.uint8), ("audio_bits", np.uint16)])
+FRAME_FIELDS_DTYPE = np.dtype([("bit_alloc", np.uint8, (2, 32)), ("scfsi", np.uint8, (2, 32)), ("scalar", np.uint8, (2, 3, 32)),
+                               ("subband", np.uint16, (2, 3, 12, 32))])
+DEC_EMPTY, DEC_BAD_SYNC, DEC_HEADER_MISMATCH, DEC_BAD_CRC16, DEC_BAD_SCFCRC, DEC_SCFCRC_UNCHECKED, DEC_BAD_ALLOC, DEC_OVERRUN = (1 << i for i in range(8))
+DEC_BAD_MASK = DEC_BAD_SYNC | DEC_HEADER_MISMATCH | DEC_BAD_CRC16 | DEC_BAD_SCFCRC | DEC_BAD_ALLOC | DEC_OVERRUN
 
 
 def _config_array(configs):
@@ -521,6 +536,45 @@ class Batch:
         self.frame_bytes[s] = self.L.tlb_frame_bytes(self.h, s)
         self.unit_bytes[s] = self.L.tlb_egress_unit_bytes(self.h, s)
         self.units_per_frame[s] = self.L.tlb_egress_units_per_frame(self.h, s)
+
+    # -- frame check / decode: the batch's own frames read back (tlb_decode_*) ----------------
+    def decode(self, frames, lens=None, want_fields=False, want_pcm=False):
+        """frames uint8 [nframes, nstreams, out_stride], lens int32 [nframes, nstreams] or None (every slot full) ->
+        (reports FRAME_REPORT_DTYPE [nframes, nstreams], fields FRAME_FIELDS_DTYPE [nframes, nstreams] or None,
+        pcm int16 [nframes, nstreams, 2, 1152] or None)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        nf = frames.shape[0]
+        if frames.shape != (nf, self.nstreams, self.out_stride):
+            raise ToolameError(18, f"frames shape {frames.shape}")
+        ln = None
+        if lens is not None:
+            ln = np.ascontiguousarray(lens, dtype=np.int32)
+            if ln.shape != (nf, self.nstreams):
+                raise ToolameError(18, "lens shape")
+        rep = np.zeros((nf, self.nstreams), dtype=FRAME_REPORT_DTYPE)
+        fl = np.zeros((nf, self.nstreams), dtype=FRAME_FIELDS_DTYPE) if want_fields else None
+        pcm = np.zeros((nf, self.nstreams, 2, SAMPLES), dtype=np.int16) if want_pcm else None
+        rc = self.L.tlb_decode_host(self.h, frames.ctypes.data, ln.ctypes.data if ln is not None else None, nf, rep.ctypes.data,
+                                    fl.ctypes.data if fl is not None else None, pcm.ctypes.data if pcm is not None else None)
+        if rc:
+            raise ToolameError(rc, "tlb_decode_host")
+        return rep, fl, pcm
+
+    def decode_device(self, d_frames_ptr, d_len_ptr, nframes, d_report_ptr, d_fields_ptr=None, d_pcm_ptr=None, stream=None):
+        rc = self.L.tlb_decode_device(self.h, d_frames_ptr, d_len_ptr, nframes, d_report_ptr, d_fields_ptr, d_pcm_ptr, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_decode_device")
+
+    def decode_reset(self, stream=-1):
+        rc = self.L.tlb_decode_reset(self.h, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_decode_reset")
+
+    def decode_bad_frames(self):
+        n = self.L.tlb_decode_bad_frames(self.h)
+        if n < 0:
+            raise ToolameError(-n, "tlb_decode_bad_frames")
+        return int(n)
 
     # -- device-resident path (bench, production) -------------------------------------------
     def encode_device(self, d_pcm_ptr, nframes, d_out_ptr, d_xpad_ptr=None, d_xpad_len_ptr=None, stream=None):

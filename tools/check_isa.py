@@ -32,6 +32,9 @@ LIMITS = [
     (re.compile(r"tl_frame_kernel"), dict(vgpr=168, lds=163840, vgpr_spill=0, pairs2_frac=0.01)),
     (re.compile(r"tl_main_kernel"), dict(vgpr=168, lds=163840, vgpr_spill=0, pairs2_frac=0.0)),
     (re.compile(r"tl_psy2_kernel"), dict(vgpr=168, lds=163840, vgpr_spill=0)),       # keeps the vectorizer (csrc/Makefile): b128 forms expected
+    # frame check / decode (csrc/toolame_dec.hip): the synthesis kernel holds the matrixing row and the V ring in registers and runs three waves per SIMD
+    (re.compile(r"tl_synth_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
+    (re.compile(r"tl_unpack_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
 ]
 
 
