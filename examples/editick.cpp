@@ -7,6 +7,9 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
+//                [--short-every N --short-by M]
+//   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth stream delivers M sample
+//   frames fewer than 1152; the library stretches what came over the frame as the reference does and counts the underruns.
 // out.af: for every packet a little-endian uint32 length, then the packet.
 #include <chrono>
 #include <cstdint>
@@ -27,12 +30,12 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M]\n", argv[0]);
         return 2;
     }
     long rate = 48000;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0;
     char mode = 0;
     double gain_db = 0.0;
     for (int i = 3; i + 1 < argc; i += 2) {
@@ -46,11 +49,14 @@ int main(int argc, char **argv)
         else if (k == "-g") gain_db = std::atof(v);
         else if (k == "-n") nstreams = std::atoi(v);
         else if (k == "-t") now_s = std::atoll(v);
+        else if (k == "--short-every") short_every = std::atoi(v);
+        else if (k == "--short-by") short_by = std::atoi(v);
         else die("unknown option", 0);
     }
     if (!mode) mode = channels == 1 ? 'm' : 'j';             // odr-audioenc's defaults (src/odr-audioenc.cpp:697-709)
     if (channels != 1 && channels != 2) die("1 or 2 channels", channels);
     if (nstreams < 1) die("streams", nstreams);
+    if (short_every < 0 || short_by < 0 || short_by > 1152 || (short_every > 0) != (short_by > 0)) die("--short-every N --short-by M: N >= 1 and 1 <= M <= 1152, both or neither", 0);
 
     std::FILE *fi = std::fopen(argv[1], "rb");
     if (!fi) die("cannot open input", 0);
@@ -68,6 +74,7 @@ int main(int argc, char **argv)
     tlb_tick *t = tlb_tick_create(0, nstreams, cfg.data(), &tc, &err);
     if (!t) die("tlb_tick_create", err);
     if (gain_db != 0.0 && tlb_tick_set_gain_db(t, -1, gain_db)) die("gain", 0);
+    if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
 
     const size_t per_frame = 1152 * (size_t)channels;        // samples of one frame in the file
     std::vector<int16_t> frame(per_frame);
@@ -87,6 +94,10 @@ int main(int argc, char **argv)
     while (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) == per_frame) {
         int16_t *in = tlb_tick_pcm(t);                       // pinned [nstreams][2304]; mono streams use the first 1152 values
         for (int s = 0; s < nstreams; s++) std::memcpy(in + (size_t)s * 2304, frame.data(), per_frame * sizeof(int16_t));
+        if (short_every && frames % short_every == 0) {          // every set comes back all 1152: only the short streams are written
+            int32_t *valid = tlb_tick_valid(t);                  // pinned [nstreams], re-fetched like the PCM
+            for (int s = 0; s < nstreams; s += short_every) valid[s] = 1152 - short_by;
+        }
         if (int rc = tlb_tick_run(t)) die("tlb_tick_run", rc);
         emit();
         frames++;
@@ -94,6 +105,10 @@ int main(int argc, char **argv)
     if (frames > 0) {
         if (int rc = tlb_tick_finish(t)) die("tlb_tick_finish", rc);     // the pending last frame (toolame_finish at stream end)
         emit();
+    }
+    if (short_every) {                                           // what a caller acts on: the reference gives up after 60 s without a full read (:925-931)
+        const uint32_t *ms = tlb_tick_underrun_ms(t), *n = tlb_tick_underruns(t);
+        std::fprintf(stderr, "editick: stream 0: %u short reads, %u ms since its last full read\n", n[0], ms[0]);
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",

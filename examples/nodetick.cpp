@@ -11,11 +11,14 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
+//                 [--short-every N --short-by M]
 //   in.s16le: interleaved stereo 48 kHz; stream s starts reading at frame s (so the services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
 //   -o: the AF packets of the LAST stream of the node, length-prefixed (uint32 LE) -- the stream farthest from shard 0.
 //   --deadline-ms: the node's tick deadline (include/toolame_batch.h, TICK DEADLINE): a shard that misses it goes off air on its own
 //   while the others tick on, and comes back by itself; each shard's late / missed / dropped counts go to stderr at the end.
+//   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth service delivers M
+//   sample frames fewer than 1152; the total of short reads and the longest time without a full read go to stderr at the end.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -39,6 +42,7 @@ struct Ctx {
     long tick;
     std::vector<uint64_t> *hash;                             // per shard: FNV-1a over every packet byte shipped
     std::vector<long> *packets, *bytes;
+    int short_every, short_by;                               // 0: every read is full
 };
 
 // step 1 on shard `g`'s thread: the block's services copy their frame of this tick into the pinned input set
@@ -53,6 +57,8 @@ static void fill(void *vctx, int g, int first, int n)
         }
         const size_t f = ((size_t)s + (size_t)c.tick) % c.nframes_in;
         std::memcpy(dst, c.pcm->data() + f * 2304, 2304 * sizeof(int16_t));
+        if (c.short_every && c.tick % c.short_every == 0 && s % c.short_every == 0)
+            if (int32_t *valid = tlb_node_valid(c.nd, s)) *valid = 1152 - c.short_by;        // untouched, it reads 1152
     }
     (void)g;
 }
@@ -77,10 +83,10 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0;
     double deadline_ms = 0;
     std::string devs, outpath;
     for (int i = 2; i + 1 < argc; i += 2) {
@@ -94,8 +100,11 @@ int main(int argc, char **argv)
         else if (k == "-p") psy = std::atoi(v);
         else if (k == "-o") outpath = v;
         else if (k == "--deadline-ms") { deadline_ms = std::atof(v); if (!(deadline_ms > 0)) die("--deadline-ms wants a positive number", 0); }
+        else if (k == "--short-every") short_every = std::atoi(v);
+        else if (k == "--short-by") short_by = std::atoi(v);
         else die("unknown option", 0);
     }
+    if (short_every < 0 || short_by < 0 || short_by > 1152 || (short_every > 0) != (short_by > 0)) die("--short-every N --short-by M: N >= 1 and 1 <= M <= 1152, both or neither", 0);
     const int ndev = tlb_device_count();
     if (ndev <= 0) die("no GPU", ndev);
     std::vector<int> devices;
@@ -139,10 +148,12 @@ int main(int argc, char **argv)
     if (!nd) die("tlb_node_create", err);
     if (deadline_ms > 0)
         if (int rc = tlb_node_set_deadline_ms(nd, deadline_ms)) die("tlb_node_set_deadline_ms", rc);
+    if (short_every)
+        if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
 
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes};
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     auto tap = [&]() {                                           // -o: the last stream's packets
         if (!fo) return;
@@ -220,6 +231,11 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "nodetick: shard %d: late_events %ld, missed_steps %ld, dropped_steps %ld (rejoins %ld, worst overrun %.1f ms)\n", g,
                          dl.late_events, dl.missed_steps, dl.dropped_steps, dl.rejoins, dl.worst_overrun_ms);
         }
+    if (short_every) {                                                    // the reference aborts a service after 60 s without a full read (:925-931): the caller's decision here
+        unsigned long total = 0; uint32_t worst = 0;
+        for (int s = 0; s < nstreams; s++) { total += tlb_node_underruns(nd, s); const uint32_t ms = tlb_node_underrun_ms(nd, s); if (ms > worst) worst = ms; }
+        std::fprintf(stderr, "nodetick: %lu short reads in all, longest time without a full read %u ms\n", total, worst);
+    }
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",
                 nstreams, G, ticks, tot.frames, npk, nby, sec, sec > 0 ? tot.frames / sec : 0.0, sec > 0 ? ticks * 0.024 / sec : 0.0);

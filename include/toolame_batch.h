@@ -158,6 +158,30 @@ int tlb_flush_device(tlb_batch *b, uint8_t *d_out, void *hip_stream);
 int tlb_set_gain_db(tlb_batch *b, int stream, double gain_db);
 int tlb_ingest_device(tlb_batch *b, const int16_t *d_interleaved, int nframes, int16_t *d_pcm, int16_t *d_peaks, void *hip_stream);
 int tlb_ingest_host(tlb_batch *b, const int16_t *interleaved, int nframes, int16_t *pcm, int16_t *peaks);
+/* Ingest with SHORT READS: the drift compensation of the caller's loop (expand_missing_samples, src/odr-audioenc.cpp:335-373, called at
+ * :910-917) ahead of the steps above, which then see the stretched frame.
+ *   d_valid  int32 [nframes][nstreams]: whole sample frames the slot delivers (a sample frame is one L/R pair, or one sample of a
+ *            one-channel stream).  Above 1152 counts as 1152, below 0 as 0.  NULL: tlb_ingest_device exactly.
+ * ZERO TAIL.  The reference's queue zero-fills what it could not deliver (src/SampleQueue.h:217-276), so whatever the caller's buffer
+ * holds behind `valid` is never read as samples: the frames behind the valid ones are zeros.  With missing = 1152 - valid:
+ *   missing == 0       the frame passes unchanged (the function is not called, :913-915).
+ *   missing >= 116     the valid frames followed by zeros (:351-356; the test is `missing * bytes_per_sample > buf.size() / 10` in
+ *                      integer arithmetic, the same 116 for one and two channels; 115 is still stretched).
+ *   1 .. 115           output frame i is source frame src(i) of the zero-tailed buffer, with q = valid / missing (integer division):
+ *                      src(0) = 0, src(i) = i - (i - 1) / q for i >= 1 -- the closed form of the loop at :361-371, which does not
+ *                      advance its source index after an i that is a positive multiple of q.
+ * Two consequences, both the reference's and both reproduced: with missing == 1 the last output frame is source frame 1151, a zero of
+ * the tail (:361-371 with q = 1151); with larger counts up to 22 valid frames at the end are never used (missing == 105: q = 9). */
+int tlb_ingest_device_valid(tlb_batch *b, const int16_t *d_interleaved, const int32_t *d_valid, int nframes, int16_t *d_pcm, int16_t *d_peaks,
+                            void *hip_stream);
+int tlb_ingest_host_valid(tlb_batch *b, const int16_t *interleaved, const int32_t *valid, int nframes, int16_t *pcm, int16_t *peaks);
+/* The underrun bookkeeping that goes with it (src/odr-audioenc.cpp:919-935), per stream over the frames of the call in order, both arrays
+ * uint32 [nstreams] and read-modify-write like d_silence_ms:
+ *   d_underrun_ms  a short frame (valid < 1152) adds the frame's duration in whole milliseconds (as the silence counter), a full frame
+ *                  sets it to 0.  The reference aborts when it exceeds 60 s (:925-931); that decision stays with the caller.
+ *   d_underruns    short frames so far: what the reference reports through notify_underrun (:920-923). */
+int tlb_underrun_device(tlb_batch *b, const int32_t *d_valid, int nframes, uint32_t *d_underrun_ms, uint32_t *d_underruns, void *hip_stream);
+int tlb_underrun_host(tlb_batch *b, const int32_t *valid, int nframes, uint32_t *underrun_ms, uint32_t *underruns);
 /* The caller's silence accounting (src/odr-audioenc.cpp:1053-1079): per stream, a frame with both peaks 0 adds its duration
  * in whole milliseconds (24 at 48 kHz, 36 at 32 kHz, 48 at 24 kHz) to d_silence_ms[stream], any other frame resets it to 0.
  * The decision itself (`measured_silence_ms > 1000 * silence_timeout` -> stop the stream) stays with the caller. */
@@ -289,6 +313,17 @@ int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config
 int16_t *tlb_tick_pcm(tlb_tick *t);
 uint8_t *tlb_tick_xpad(tlb_tick *t);
 int32_t *tlb_tick_xpad_len(tlb_tick *t);
+/* SHORT READS (tlb_ingest_device_valid, tlb_underrun_device).  tlb_tick_enable_short_reads() before the first submit (TLB_ERR_ARG after
+ * it) makes the object carry an int32 [nstreams] array of delivered sample frames with every input set: tlb_tick_valid() follows the
+ * rules of tlb_tick_pcm() (it alternates; NULL while two ticks are in flight), and every set reads 1152 everywhere when it is handed
+ * back, so a stream the caller does not touch is a full read.  The counters of tlb_underrun_device come back with the silence counter:
+ * tlb_tick_underrun_ms() / tlb_tick_underruns(), uint32 [nstreams], of the tick waited for last.  The stream life-cycle calls leave
+ * them alone, as they leave the silence counter.  An object that was never enabled makes the device calls it made before this existed;
+ * its three accessors return NULL. */
+int tlb_tick_enable_short_reads(tlb_tick *t);
+int32_t *tlb_tick_valid(tlb_tick *t);
+const uint32_t *tlb_tick_underrun_ms(const tlb_tick *t);
+const uint32_t *tlb_tick_underruns(const tlb_tick *t);
 int tlb_tick_run(tlb_tick *t);                 /* = tlb_tick_submit() + tlb_tick_wait() */
 /* Ticks overlapped: the object owns TWO sets of pinned host input buffers (and three of outputs).  tlb_tick_submit() queues a tick on the input set the caller has
  * just filled and returns at once; from then on tlb_tick_pcm() / _xpad() / _xpad_len() point at the OTHER input set, which the caller
@@ -465,6 +500,11 @@ int tlb_node_parallel(tlb_node *nd, void (*fn)(void *ctx, int shard, int first, 
 int16_t *tlb_node_pcm(tlb_node *nd, int stream);
 uint8_t *tlb_node_xpad(tlb_node *nd, int stream);            /* uint8[TLB_MAX_XPAD] */
 int32_t *tlb_node_xpad_len(tlb_node *nd, int stream);
+/* short reads: tlb_tick_enable_short_reads of every shard (before the first submit; a restarted shard is enabled again);
+ * tlb_node_valid(stream) is that stream's int32 in its shard's current input set -- NULL when not enabled, while two ticks are in flight
+ * and for a broken or late shard, whose input is not written */
+int tlb_node_enable_short_reads(tlb_node *nd);
+int32_t *tlb_node_valid(tlb_node *nd, int stream);
 int tlb_node_submit(tlb_node *nd);
 int tlb_node_wait(tlb_node *nd);
 int tlb_node_run(tlb_node *nd);
@@ -472,6 +512,8 @@ int tlb_node_finish(tlb_node *nd);
 int tlb_node_units(const tlb_node *nd, int stream);
 const int16_t *tlb_node_peaks(const tlb_node *nd, int stream);          /* int16[2] */
 uint32_t tlb_node_silence_ms(const tlb_node *nd, int stream);
+uint32_t tlb_node_underrun_ms(const tlb_node *nd, int stream);         /* 0 when not enabled, and for a broken, late or stale shard */
+uint32_t tlb_node_underruns(const tlb_node *nd, int stream);
 const uint8_t *tlb_node_frame(const tlb_node *nd, int stream, int *len);
 const uint8_t *tlb_node_packet(const tlb_node *nd, int stream, int unit, int *len);
 const uint8_t *tlb_node_message(const tlb_node *nd, int stream, int unit, int *len);

@@ -1,5 +1,5 @@
 // tl_kernels.h -- the one door between the host translation units (tlb_batch.cpp, tlb_egress.cpp, tlb_tick.cpp: plain C++, seconds to
-// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
+// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
 // `st` and returns hipGetLastError(); grid shapes that depend on the kernels' wave counts are computed from the constants below.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -36,4 +36,9 @@ hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state
                      uint8_t *out, int32_t *out_len, int nstreams, int out_stride);
 // toolame_dec.hip: tl_unpack_kernel over every (stream, slot) of the launch, tl_synth_kernel when A.pcm is set, then tl_dec_carry_kernel per stream
 hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
+// toolame_ingest.hip: tl_ingest_valid_kernel (one workgroup per slot, valid int32 [nframes][nstreams]) and tl_underrun_kernel (256 threads, one per stream)
+hipError_t tlk_ingest_valid(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid, int16_t *out, int16_t *peaks, const double *gain,
+                            const TlConfig *configs, const int32_t *stream_cfg, int nstreams);
+hipError_t tlk_underrun(unsigned blocks, hipStream_t st, const int32_t *valid, uint32_t *underrun_ms, uint32_t *underruns, const TlConfig *configs,
+                        const int32_t *stream_cfg, int nstreams, int nframes);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

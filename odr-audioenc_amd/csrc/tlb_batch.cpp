@@ -528,6 +528,68 @@ int tlb_ingest_host(tlb_batch *b, const int16_t *interleaved, int nframes, int16
     return rc;
 }
 
+// Ingest with short reads (csrc/mp2_ingest.h): d_valid int32 [nframes][nstreams], the whole sample frames each slot delivers.  Without the
+// array this IS tlb_ingest_device -- the same kernel, the same launch.
+int tlb_ingest_device_valid(tlb_batch *b, const int16_t *d_interleaved, const int32_t *d_valid, int nframes, int16_t *d_pcm, int16_t *d_peaks, void *hip_stream)
+{
+    if (!d_valid) return tlb_ingest_device(b, d_interleaved, nframes, d_pcm, d_peaks, hip_stream);
+    if (!b || !d_interleaved || !d_pcm || !d_peaks || nframes <= 0) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(tlk_ingest_valid((unsigned)((size_t)nframes * (size_t)b->nstreams), (hipStream_t)hip_stream, d_interleaved, d_valid, d_pcm, d_peaks, b->d_gain, b->d_configs, b->d_stream_cfg, b->nstreams));
+    return TLB_OK;
+}
+
+int tlb_ingest_host_valid(tlb_batch *b, const int16_t *interleaved, const int32_t *valid, int nframes, int16_t *pcm, int16_t *peaks)
+{
+    if (!valid) return tlb_ingest_host(b, interleaved, nframes, pcm, peaks);
+    DevFree guard_;
+    if (!b || !interleaved || !pcm || !peaks || nframes <= 0) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t slots = (size_t)nframes * (size_t)b->nstreams;
+    HIPCHK(stage_reserve(b, 9, slots * 2304 * 2));
+    HIPCHK(stage_reserve(b, 10, slots * 2304 * 2));
+    HIPCHK(stage_reserve(b, 11, slots * 2 * 2));
+    int16_t *d_in = (int16_t *)b->stage[9], *d_out = (int16_t *)b->stage[10], *d_pk = (int16_t *)b->stage[11];
+    int32_t *d_valid = nullptr;
+    DEVALLOC(d_valid, slots * sizeof(int32_t));
+    HIPCHK(hipMemcpy(d_in, interleaved, slots * 2304 * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_valid, valid, slots * sizeof(int32_t), hipMemcpyHostToDevice));
+    int rc = tlb_ingest_device_valid(b, d_in, d_valid, nframes, d_out, d_pk, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(pcm, d_out, slots * 2304 * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(peaks, d_pk, slots * 2 * 2, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// Underrun bookkeeping of the caller (src/odr-audioenc.cpp:919-935; tl_underrun_stream): the 60-second decision stays with the caller
+int tlb_underrun_device(tlb_batch *b, const int32_t *d_valid, int nframes, uint32_t *d_underrun_ms, uint32_t *d_underruns, void *hip_stream)
+{
+    if (!b || !d_valid || !d_underrun_ms || !d_underruns || nframes <= 0) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(tlk_underrun((unsigned)((b->nstreams + 255) / 256), (hipStream_t)hip_stream, d_valid, d_underrun_ms, d_underruns, b->d_configs, b->d_stream_cfg, b->nstreams, nframes));
+    return TLB_OK;
+}
+
+int tlb_underrun_host(tlb_batch *b, const int32_t *valid, int nframes, uint32_t *underrun_ms, uint32_t *underruns)
+{
+    DevFree guard_;
+    if (!b || !valid || !underrun_ms || !underruns || nframes <= 0) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t slots = (size_t)nframes * (size_t)b->nstreams, n = (size_t)b->nstreams;
+    int32_t *d_v = nullptr; uint32_t *d_m = nullptr, *d_n = nullptr;
+    DEVALLOC(d_v, slots * sizeof(int32_t));
+    DEVALLOC(d_m, sizeof(uint32_t) * n);
+    DEVALLOC(d_n, sizeof(uint32_t) * n);
+    HIPCHK(hipMemcpy(d_v, valid, slots * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_m, underrun_ms, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_n, underruns, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+    int rc = tlb_underrun_device(b, d_v, nframes, d_m, d_n, nullptr);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(underrun_ms, d_m, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(underruns, d_n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    return rc;
+}
+
 int tlb_silence_device(tlb_batch *b, const int16_t *d_peaks, int nframes, uint32_t *d_silence_ms, void *hip_stream)
 {
     if (!b || !d_peaks || !d_silence_ms || nframes <= 0) return TLB_ERR_ARG;

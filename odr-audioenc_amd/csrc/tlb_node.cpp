@@ -151,6 +151,7 @@ struct tlb_node {
     double wall_ns = 0;
     long submitted = 0, waited = 0;              // node steps: submits / waits so far (a step's index is its submit's)
     double deadline_ms = 0;                      // TICK DEADLINE; 0 = none
+    bool short_reads = false;                    // tlb_node_enable_short_reads(): every shard's tick object carries `valid` and the underrun counters (a restarted shard's too)
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
@@ -278,6 +279,7 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (now_s >= 0) tc.now_s = now_s;
         s.tick = tlb_tick_create(s.device, s.n, nd->cfgs.data() + s.first, &tc, &e);
         if (!s.tick) return e ? e : TLB_ERR_HIP;
+        if (nd->short_reads) if (int rc = tlb_tick_enable_short_reads(s.tick)) return rc;
     } else {
         s.batch = tlb_create(s.device, s.n, nd->cfgs.data() + s.first, &e);
         if (!s.batch) return e ? e : TLB_ERR_HIP;
@@ -532,6 +534,21 @@ int32_t *tlb_node_xpad_len(tlb_node *nd, int stream)
     int32_t *p = s && s->tick ? tlb_tick_xpad_len(s->tick) : nullptr;
     return p ? p + k : nullptr;
 }
+// Short reads (tlb_tick_enable_short_reads of every shard, on the shards' threads): before the first submit, TICK plane only.
+int tlb_node_enable_short_reads(tlb_node *nd)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
+    if (nd->short_reads) return TLB_OK;
+    const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
+    if (!rc) nd->short_reads = true;
+    return rc;
+}
+int32_t *tlb_node_valid(tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
+    int32_t *p = s && s->tick ? tlb_tick_valid(s->tick) : nullptr;
+    return p ? p + k : nullptr;
+}
 
 int tlb_node_submit(tlb_node *nd)
 {
@@ -600,6 +617,18 @@ uint32_t tlb_node_silence_ms(const tlb_node *nd, int stream)
 {
     int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
     const uint32_t *p = s && s->tick ? tlb_tick_silence_ms(s->tick) : nullptr;
+    return p ? p[k] : 0;
+}
+uint32_t tlb_node_underrun_ms(const tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    const uint32_t *p = s && s->tick ? tlb_tick_underrun_ms(s->tick) : nullptr;
+    return p ? p[k] : 0;
+}
+uint32_t tlb_node_underruns(const tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    const uint32_t *p = s && s->tick ? tlb_tick_underruns(s->tick) : nullptr;
     return p ? p[k] : 0;
 }
 const uint8_t *tlb_node_frame(const tlb_node *nd, int stream, int *len)

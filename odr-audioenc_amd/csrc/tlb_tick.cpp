@@ -20,6 +20,8 @@ struct TickGroup {
     uint16_t *d_pseq = nullptr; uint8_t *d_frags = nullptr; int32_t *d_fraglen = nullptr, *d_nfrag = nullptr;
     uint8_t *d_msgs = nullptr; int msg_stride = 0;              // ZeroMQ egress
     uint32_t *d_silence = nullptr;                              // milliseconds of digital silence so far, per stream
+    int32_t *d_valid = nullptr;                                 // short reads (tlb_tick_enable_short_reads): sample frames delivered this tick, per stream
+    uint32_t *d_underrun_ms = nullptr, *d_underruns = nullptr;  // ... milliseconds without a full read / short reads so far, per stream
     // this group's slices of the pinned host outputs, THREE sets: tick n's results land in set n % 3.  With two ticks in flight the
     // caller is still reading tick n (valid until the next wait) while tick n + 1 is on its way and tick n + 2 is being submitted:
     // three sets make "until the next wait" true without a copy (two sets let submit n + 2 overwrite what tick n showed)
@@ -41,6 +43,10 @@ struct tlb_tick {
     // three OUTPUT sets; results are read from `out_set`, the set of the tick waited for last
     int16_t *h_inter[2] = {}, *h_peaks[3] = {}; uint8_t *h_xpad[2] = {}; int32_t *h_xl[2] = {};
     uint32_t *h_silence[3] = {};
+    // short reads (src/odr-audioenc.cpp:335-373,910-935), off until tlb_tick_enable_short_reads(): `valid` travels with the input sets,
+    // the two underrun counters with the output sets.  A set of h_valid is all 1152 whenever the caller can see it untouched.
+    bool short_reads = false;
+    int32_t *h_valid[2] = {}; uint32_t *h_underrun_ms[3] = {}, *h_underruns[3] = {};
     int in_set = 0, out_set = 0;
     long waited = 0;                             // ticks whose results have been waited for (ticks: submitted)
     std::vector<void *> pinned, dev;
@@ -192,6 +198,41 @@ int16_t *tlb_tick_pcm(tlb_tick *t) { return tick_input_free(t) ? t->h_inter[t->i
 uint8_t *tlb_tick_xpad(tlb_tick *t) { return tick_input_free(t) && t->with_xpad ? t->h_xpad[t->in_set] : nullptr; }
 int32_t *tlb_tick_xpad_len(tlb_tick *t) { return tick_input_free(t) && t->with_xpad ? t->h_xl[t->in_set] : nullptr; }
 const int16_t *tlb_tick_peaks(const tlb_tick *t) { return t ? t->h_peaks[t->out_set] : nullptr; }
+int32_t *tlb_tick_valid(tlb_tick *t) { return tick_input_free(t) && t->short_reads ? t->h_valid[t->in_set] : nullptr; }
+const uint32_t *tlb_tick_underrun_ms(const tlb_tick *t) { return t && t->short_reads ? t->h_underrun_ms[t->out_set] : nullptr; }
+const uint32_t *tlb_tick_underruns(const tlb_tick *t) { return t && t->short_reads ? t->h_underruns[t->out_set] : nullptr; }
+// Short reads are opted into by this call, before the first submit: the object then carries `valid` per stream in with the PCM, runs the
+// ingest kernel that stretches (tlb_ingest_device_valid) and the underrun counters (tlb_underrun_device).  An object that never makes the
+// call makes the device calls it always made.
+int tlb_tick_enable_short_reads(tlb_tick *t)
+{
+    if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (t->short_reads) return TLB_OK;
+    HIPCHK(hipSetDevice(t->device));
+    const size_t ns = (size_t)t->nstreams;
+    auto pin = [&](size_t bytes) -> void * { void *p = nullptr; if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr; memset(p, 0, bytes); t->pinned.push_back(p); return p; };
+    for (int k = 0; k < 2; k++) {
+        if (!(t->h_valid[k] = (int32_t *)pin(ns * sizeof(int32_t)))) return TLB_ERR_HIP;
+        for (size_t i = 0; i < ns; i++) t->h_valid[k][i] = TLB_SAMPLES_PER_FRAME;
+    }
+    for (int k = 0; k < 3; k++) {
+        t->h_underrun_ms[k] = (uint32_t *)pin(ns * sizeof(uint32_t)); t->h_underruns[k] = (uint32_t *)pin(ns * sizeof(uint32_t));
+        if (!t->h_underrun_ms[k] || !t->h_underruns[k]) return TLB_ERR_HIP;
+    }
+    for (auto &G : t->groups) {
+        void *p[3] = {};
+        for (int k = 0; k < 3; k++) {
+            HIPCHK(hipMalloc(&p[k], (size_t)G.n * 4));
+            t->dev.push_back(p[k]);
+            HIPCHK(hipMemset(p[k], 0, (size_t)G.n * 4));
+        }
+        G.d_valid = (int32_t *)p[0]; G.d_underrun_ms = (uint32_t *)p[1]; G.d_underruns = (uint32_t *)p[2];
+    }
+    HIPCHK(hipDeviceSynchronize());                                  // the memsets ran on the null stream, the tick's streams do not wait for it
+    t->short_reads = true;
+    return TLB_OK;
+}
 long tlb_tick_count(const tlb_tick *t) { return t ? t->ticks : 0; }
 int tlb_tick_set_gain_db(tlb_tick *t, int stream, double gain_db)
 {
@@ -253,6 +294,10 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
+    if (t->short_reads) {
+        HIPCHK(hipMemcpyAsync(t->h_underrun_ms[set] + G.first, G.d_underrun_ms, n * 4, hipMemcpyDeviceToHost, t->s_out));
+        HIPCHK(hipMemcpyAsync(t->h_underruns[set] + G.first, G.d_underruns, n * 4, hipMemcpyDeviceToHost, t->s_out));
+    }
     if (have_frames) {                                               // (the very first tick: no frame is final yet, lengths stay 0)
         if (t->egress == TLB_TICK_FRAMES) {
             HIPCHK(hipMemcpyAsync(G.h_frames[set], G.d_frames, n * (size_t)G.out_stride, hipMemcpyDeviceToHost, t->s_out));
@@ -306,6 +351,7 @@ int tlb_tick_submit(tlb_tick *t)
         hipError_t e = hipSuccess;
         if (t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_ingested, 0);
         if (e == hipSuccess) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && t->short_reads) e = hipMemcpyAsync(G.d_valid, t->h_valid[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->with_xpad && t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_encoded, 0);
         if (e == hipSuccess && t->with_xpad) e = hipMemcpyAsync(G.d_xpad, t->h_xpad[set] + (size_t)G.first * TL_MAX_XPAD, n * TL_MAX_XPAD, hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->with_xpad) e = hipMemcpyAsync(G.d_xl, t->h_xl[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
@@ -313,7 +359,10 @@ int tlb_tick_submit(tlb_tick *t)
         if (e == hipSuccess) e = hipStreamWaitEvent(t->s_run, G.ev_in, 0);
         if (e == hipSuccess && t->ticks > 0) e = hipStreamWaitEvent(t->s_run, G.ev_out, 0);
         if (e != hipSuccess) rc = TLB_ERR_HIP;
-        if (!rc) rc = tlb_ingest_device(G.b, G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
+        if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
+        if (!rc && t->short_reads) rc = tlb_ingest_device_valid(G.b, G.d_inter, G.d_valid, 1, G.d_pcm, G.d_peaks, t->s_run);
+        // (the counters here and not with the silence counter: the next tick's copy-in may overwrite d_valid once ev_ingested has passed)
+        if (!rc && t->short_reads) rc = tlb_underrun_device(G.b, G.d_valid, 1, G.d_underrun_ms, G.d_underruns, t->s_run);
         if (!rc && hipEventRecord(G.ev_ingested, t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc) rc = tlb_launch(G.b, G.d_pcm, 1, t->with_xpad ? G.d_xpad : nullptr, t->with_xpad ? G.d_xl : nullptr, G.d_frames, nullptr, t->s_run, nullptr, G.d_flen);
         if (!rc && hipEventRecord(G.ev_encoded, t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
@@ -336,6 +385,8 @@ int tlb_tick_wait(tlb_tick *t)
     const int set = (int)(t->waited % 3);
     if (hipEventSynchronize(t->ev1[set]) != hipSuccess) return tick_fail(t, TLB_ERR_HIP);
     t->out_set = set;
+    // the retired tick's input set goes back to the caller (now, or after the next submit): untouched streams are full reads
+    if (t->short_reads) { int32_t *v = t->h_valid[t->waited & 1]; for (int i = 0; i < t->nstreams; i++) v[i] = TLB_SAMPLES_PER_FRAME; }
     t->waited++;
     return TLB_OK;
 }

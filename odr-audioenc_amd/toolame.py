@@ -210,6 +210,21 @@ def _bind(L):
         L.tlb_decode_reset.argtypes = [C.c_void_p, C.c_int]
         L.tlb_decode_bad_frames.argtypes = [C.c_void_p]
         L.tlb_decode_bad_frames.restype = C.c_long
+    if hasattr(L, "tlb_ingest_device_valid"):     # short reads (an older build loaded through TLB_LIB_PATH has none of it)
+        L.tlb_ingest_device_valid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_ingest_host_valid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_underrun_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_underrun_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        for f in ("tlb_tick_valid", "tlb_tick_underrun_ms", "tlb_tick_underruns"):
+            getattr(L, f).restype = C.c_void_p
+            getattr(L, f).argtypes = [C.c_void_p]
+        L.tlb_tick_enable_short_reads.argtypes = [C.c_void_p]
+        L.tlb_node_enable_short_reads.argtypes = [C.c_void_p]
+        L.tlb_node_valid.restype = C.c_void_p
+        L.tlb_node_valid.argtypes = [C.c_void_p, C.c_int]
+        for f in ("tlb_node_underrun_ms", "tlb_node_underruns"):
+            getattr(L, f).restype = C.c_uint32
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -335,6 +350,28 @@ class Tick:
     @property
     def silence_ms(self):
         return self._view("tlb_tick_silence_ms", C.c_uint32, (self.nstreams,))
+
+    # -- short reads (src/odr-audioenc.cpp:335-373,910-935): opt in before the first submit --
+    def enable_short_reads(self):
+        rc = self.L.tlb_tick_enable_short_reads(self.h)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_short_reads")
+
+    @property
+    def valid(self):
+        """int32 [nstreams] of the input set to fill next: sample frames delivered, 1152 (a full read) unless the caller writes less;
+        None when not enabled or while two ticks are in flight"""
+        return self._view("tlb_tick_valid", C.c_int32, (self.nstreams,))
+
+    @property
+    def underrun_ms(self):
+        """uint32 [nstreams]: milliseconds since the stream's last full read (the reference aborts above 60 s); None when not enabled"""
+        return self._view("tlb_tick_underrun_ms", C.c_uint32, (self.nstreams,))
+
+    @property
+    def underruns(self):
+        """uint32 [nstreams]: short reads so far; None when not enabled"""
+        return self._view("tlb_tick_underruns", C.c_uint32, (self.nstreams,))
 
     def submit(self):
         """queue one tick on the input set just filled and return at once; `pcm` then shows the other input set"""
@@ -594,18 +631,38 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_set_gain_db")
 
-    def ingest(self, interleaved):
-        """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2])"""
+    def ingest(self, interleaved, valid=None):
+        """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2]).
+        valid: int32 [nframes, nstreams] sample frames each slot delivers -- a short read is stretched over the frame as the reference
+        does (tlb_ingest_host_valid); None: every read is full"""
         a = np.ascontiguousarray(interleaved, dtype=np.int16)
         nf = a.shape[0]
         if a.shape != (nf, self.nstreams, 2 * SAMPLES):
             raise ToolameError(18, f"interleaved shape {a.shape}")
         pcm = np.zeros((nf, self.nstreams, 2, SAMPLES), dtype=np.int16)
         peaks = np.zeros((nf, self.nstreams, 2), dtype=np.int16)
-        rc = self.L.tlb_ingest_host(self.h, a.ctypes.data, nf, pcm.ctypes.data, peaks.ctypes.data)
+        if valid is None:
+            rc = self.L.tlb_ingest_host(self.h, a.ctypes.data, nf, pcm.ctypes.data, peaks.ctypes.data)
+            if rc:
+                raise ToolameError(rc, "tlb_ingest_host")
+            return pcm, peaks
+        v = np.ascontiguousarray(valid, dtype=np.int32)
+        if v.shape != (nf, self.nstreams):
+            raise ToolameError(18, f"valid shape {v.shape}")
+        rc = self.L.tlb_ingest_host_valid(self.h, a.ctypes.data, v.ctypes.data, nf, pcm.ctypes.data, peaks.ctypes.data)
         if rc:
-            raise ToolameError(rc, "tlb_ingest_host")
+            raise ToolameError(rc, "tlb_ingest_host_valid")
         return pcm, peaks
+
+    def underrun(self, valid, underrun_ms, underruns):
+        """tlb_underrun_host over valid int32 [nframes, nstreams]: the two uint32 [nstreams] counters are advanced in place"""
+        v = np.ascontiguousarray(valid, dtype=np.int32)
+        if v.ndim != 2 or v.shape[1] != self.nstreams or underrun_ms.dtype != np.uint32 or underruns.dtype != np.uint32 or \
+                underrun_ms.shape != (self.nstreams,) or underruns.shape != (self.nstreams,):
+            raise ToolameError(18, "underrun arguments")
+        rc = self.L.tlb_underrun_host(self.h, v.ctypes.data, v.shape[0], underrun_ms.ctypes.data, underruns.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_underrun_host")
 
     def ingest_device(self, d_in_ptr, nframes, d_pcm_ptr, d_peaks_ptr, stream=None):
         rc = self.L.tlb_ingest_device(self.h, d_in_ptr, nframes, d_pcm_ptr, d_peaks_ptr, stream)
@@ -899,6 +956,22 @@ class Node:
 
     def silence_ms(self, s):
         return int(self.L.tlb_node_silence_ms(self.h, s))
+
+    # short reads (Tick.enable_short_reads, per stream with node-wide indices)
+    def enable_short_reads(self):
+        self._rc(self.L.tlb_node_enable_short_reads(self.h), "tlb_node_enable_short_reads")
+
+    def valid(self, s):
+        """the stream's int32 in its shard's current input set as a one-element view (write [0]); None when not enabled, while two ticks
+        are in flight and for a broken or late shard"""
+        p = self.L.tlb_node_valid(self.h, s)
+        return np.ctypeslib.as_array((C.c_int32 * 1).from_address(p)) if p else None
+
+    def underrun_ms(self, s):
+        return int(self.L.tlb_node_underrun_ms(self.h, s))
+
+    def underruns(self, s):
+        return int(self.L.tlb_node_underruns(self.h, s))
 
     def frame(self, s):
         n = C.c_int(0)

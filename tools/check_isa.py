@@ -35,6 +35,8 @@ LIMITS = [
     # frame check / decode (csrc/toolame_dec.hip): the synthesis kernel holds the matrixing row and the V ring in registers and runs three waves per SIMD
     (re.compile(r"tl_synth_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
     (re.compile(r"tl_unpack_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
+    # ingest with short reads (csrc/toolame_ingest.hip): a streaming kernel, nothing may spill and the gather's index arithmetic must not go through scratch
+    (re.compile(r"tl_ingest_valid_kernel"), dict(vgpr_spill=0, sgpr_spill=0, scratch=0)),
 ]
 
 
