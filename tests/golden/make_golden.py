@@ -54,6 +54,11 @@ def cases():
     for psy, fs, mode, kbps in ((1, 16000, "m", 32), (3, 16000, "s", 64), (2, 16000, "j", 48), (1, 24000, "d", 96), (4, 16000, "d", 80)):
         out.append(dict(name=f"p{psy}_{fs // 1000}k_{mode}_{kbps}_k0", samplerate=fs, mode=mode, kbps=kbps, psy=psy, kind=0,
                         seed=600 + psy + kbps, pad_len=0))
+    # allocation table B.2d (32 kHz, 48 kbps per channel or less: sblimit 12, 2-byte ScF-CRC), which no case above selects, and the highest
+    # rate there is (192 kbps per channel: long runs of 16-bit sample codes)
+    for psy, fs, mode, kbps in ((1, 32000, "m", 48), (3, 32000, "j", 96), (2, 32000, "s", 64), (1, 48000, "s", 384)):
+        out.append(dict(name=f"p{psy}_{fs // 1000}k_{mode}_{kbps}_k0", samplerate=fs, mode=mode, kbps=kbps, psy=psy, kind=0,
+                        seed=700 + psy + kbps, pad_len=0))
     out.append(dict(name="p1_48k_j_128_xpad", samplerate=48000, mode="j", kbps=128, psy=1, kind=0, seed=42, pad_len=58))
     out.append(dict(name="p3_48k_s_192_xpad", samplerate=48000, mode="s", kbps=192, psy=3, kind=0, seed=43, pad_len=58))
     # round 5: the DAB maximum (196 bytes), the largest length the caller accepts (255, src/odr-audioenc.cpp:566), and a small frame

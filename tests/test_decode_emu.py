@@ -26,7 +26,7 @@ def emu_so(tmp_path_factory):
 @pytest.fixture(scope="module")
 def goldens():
     names = D.golden_names()
-    assert len(names) == 122                                     # no golden may be left out
+    assert len(names) == 126                                     # no golden may be left out
     gs = [np.load(D.GOLDEN / (n + ".npz")) for n in names]
     cfgs = [D.golden_cfg(g) for g in gs]
     frames = [D.cut_frames(g["data"], c) for g, c in zip(gs, cfgs)]
@@ -36,7 +36,7 @@ def goldens():
 
 @pytest.fixture(scope="module")
 def golden_run(emu_so, goldens):
-    """all 122 goldens as ONE mixed batch: reports, fields, PCM"""
+    """all 126 goldens as ONE mixed batch: reports, fields, PCM"""
     names, gs, cfgs, frames = goldens
     e = D.DecEmu(emu_so, cfgs)
     fr, ln = D.batch_arrays(frames, e.stride)
@@ -204,22 +204,27 @@ def test_damage_is_found_and_contained(emu_so, goldens):
     run_damage(lambda c: D.DecEmu(emu_so, c), fl, cfgs)
 
 
+def run_truncation(dec_factory, fl, cfgs, f=5, s=2):
+    """frame f of stream s loses its last 3 bytes; asserts"""
+    e = dec_factory(cfgs)
+    fr, ln = D.batch_arrays(fl, e.stride)
+    rep0, _, _ = e.decode(fr, ln)
+    e.close()
+    ln[f, s] -= 3
+    e = dec_factory(cfgs)
+    rep, _, _ = e.decode(fr, ln)
+    e.close()
+    assert int(rep[f, s]["status"]) == D.OVERRUN and int(rep[f + 1, s]["status"]) == D.SCFCRC_UNCHECKED
+    keep = np.ones(rep.shape, dtype=bool)
+    keep[f:f + 2, s] = False
+    assert np.array_equal(rep[keep], rep0[keep])
+
+
 def test_truncation_unchecks_the_successor(emu_so, goldens):
     """A frame cut short in the MIDDLE of a stream: OVERRUN on it, SCFCRC_UNCHECKED (not an error) on the next frame, whose ScF-CRC bytes
     went with the lost tail; nothing else changes."""
     fl, cfgs = _damage_set(goldens)
-    e = D.DecEmu(emu_so, cfgs)
-    fr, ln = D.batch_arrays(fl, e.stride)
-    rep0, _, _ = e.decode(fr, ln)
-    e.close()
-    ln[5, 2] -= 3
-    e = D.DecEmu(emu_so, cfgs)
-    rep, _, _ = e.decode(fr, ln)
-    e.close()
-    assert int(rep[5, 2]["status"]) == D.OVERRUN and int(rep[6, 2]["status"]) == D.SCFCRC_UNCHECKED
-    keep = np.ones(rep.shape, dtype=bool)
-    keep[5:7, 2] = False
-    assert np.array_equal(rep[keep], rep0[keep])
+    run_truncation(lambda c: D.DecEmu(emu_so, c), fl, cfgs)
 
 
 def test_padding_bit_damage_unchecks_the_successor(emu_so, goldens):
@@ -247,9 +252,9 @@ def test_padding_bit_damage_unchecks_the_successor(emu_so, goldens):
     assert len({int(x) for x in ln[:, s]}) == 2                  # the stream has frames of both lengths
 
 
-def hostile_cases(goldens, stride):
-    """every input batch of the damage, truncation, padding-bit and noise tests: [(frames, lens or None)]"""
-    fl, cfgs = _damage_set(goldens)
+def hostile_cases_of(fl, cfgs, stride, pad_stream):
+    """every input batch of the damage, truncation, padding-bit and noise tests over the streams `fl` (`pad_stream`: one with padding
+    slots, whose padding bit is flipped): [(frames, lens or None)]"""
     fr0, ln0 = D.batch_arrays(fl, stride)
     cases = [(fr0, ln0)]
     for kind, s, f, fn, _, _ in damage_cases(fl, cfgs):
@@ -262,7 +267,7 @@ def hostile_cases(goldens, stride):
         cases.append((fr, ln))
     ln = ln0.copy(); ln[5, 2] -= 3
     cases.append((fr0, ln))
-    fr = fr0.copy(); fr[4, DAMAGE_STREAMS.index("p1_44k_j_192_k0"), 2] ^= 0x02
+    fr = fr0.copy(); fr[4, pad_stream, 2] ^= 0x02
     cases.append((fr, ln0))
     rng = np.random.default_rng(5)
     fr = rng.integers(0, 256, (6, len(cfgs), stride), dtype=np.uint8)
@@ -271,7 +276,13 @@ def hostile_cases(goldens, stride):
     ln = rng.integers(0, stride + 40, (6, len(cfgs))).astype(np.int32)
     ln[3] = -5
     cases += [(fr, ln), (fr, None)]
-    return cfgs, cases
+    return cases
+
+
+def hostile_cases(goldens, stride):
+    """hostile_cases_of over the damage set of the goldens"""
+    fl, cfgs = _damage_set(goldens)
+    return cfgs, hostile_cases_of(fl, cfgs, stride, DAMAGE_STREAMS.index("p1_44k_j_192_k0"))
 
 
 def test_hostile_bytes_stay_inside_the_slot(emu_so, goldens):

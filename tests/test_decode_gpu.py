@@ -33,7 +33,7 @@ def emu_so(tmp_path_factory):
 @pytest.fixture(scope="module")
 def goldens():
     names = D.golden_names()
-    assert len(names) == 122
+    assert len(names) == 126
     gs = [np.load(D.GOLDEN / (n + ".npz")) for n in names]
     cfgs = [D.golden_cfg(g) for g in gs]
     return names, gs, cfgs, [D.cut_frames(g["data"], c) for g, c in zip(gs, cfgs)]
@@ -64,7 +64,7 @@ class DevDec:
 
 
 def test_device_equals_emulation_on_every_golden(M, emu_so, goldens):
-    """Item 7: reports, fields and PCM of all 122 goldens in ONE mixed batch, in ragged calls on the device against one call of the emulation."""
+    """Item 7: reports, fields and PCM of all 126 goldens in ONE mixed batch, in ragged calls on the device against one call of the emulation."""
     names, gs, cfgs, frames = goldens
     e = D.DecEmu(emu_so, cfgs)
     fr, ln = D.batch_arrays(frames, e.stride)

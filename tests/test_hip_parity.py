@@ -405,8 +405,9 @@ def test_soak_slice_all_models(M, seed):
 
 
 def test_configuration_sweep_vs_oracle(M):
-    """Every legal (sample rate, mode, bitrate) x psy model as ONE mixed batch, a different signal per stream, against the
-    oracle byte for byte (SURVEY 8d cfg5 generalised: mixed configurations share a launch)."""
+    """A hand-picked list of (sample rate, mode, bitrate) triples of all six rates and four modes x psy model as ONE mixed batch, a different
+    signal per stream, against the oracle byte for byte (SURVEY 8d cfg5 generalised: mixed configurations share a launch).  Its 32 kHz
+    entries all use tables B.2a / B.2b; ALL 336 legal triples are swept by tests/test_config_sweep_gpu.py."""
     rates = {48000: [(m, k) for m in "sjdm" for k in ((64, 96, 128, 160, 192, 256, 384) if m != "m" else (32, 48, 64, 96, 128, 192))],
              32000: [("s", 128), ("j", 192), ("m", 64), ("m", 96), ("d", 256)],
              24000: [("s", 64), ("j", 96), ("m", 32), ("m", 64), ("s", 128)],
