@@ -313,6 +313,84 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
             L(q_rsf)[gr] = 1.0 / L(q_sf)[gr];                          // one division per granule instead of twelve
         }
         TL_LANES_END
+        // Few live cells: the triples are dealt over all 64 lanes (mp2_wave.h, TL_Q_REDEAL).  Not with joint-coded subbands (the channel lanes
+        // exchange samples first) and not with taps (they index by the cell's own lane).
+        uint64_t q_mask = 0;
+        int q_n = 64;
+        if (TL_Q_REDEAL && !any_joint && !taps) {
+            PV(bool, q_live);
+            TL_LANES_BEGIN L(q_live) = L(q_ba) != 0; TL_LANES_END
+            q_mask = TL_BALLOT(q_live);
+            q_n = (int)__builtin_popcountll(q_mask);
+        }
+        const bool redeal = q_n <= TL_Q_REDEAL_MAX;
+        TL_DBG_REDEAL(redeal, q_ba);
+        if (redeal) {
+            TlQCell *const qc = TL_QRD_CELLS(w);
+            TlQGran *const qg = TL_QRD_GRANS(w);
+            PV(int, q_rank);
+            TL_LANES_BEGIN
+            L(q_rank) = TL_RANK_BELOW(q_mask);                         // live cells in lane order
+            if (L(q_ba)) {
+                TlQCell *rec = &qc[L(q_rank)];
+                const uint32_t w0 = (uint32_t)L(q_steps) | ((uint32_t)L(o_smp) << 17);
+                const uint32_t w1 = (uint32_t)L(q_s2n) | ((uint32_t)(L(q_grp) * L(q_nb)) << 16) | (L(q_grp) == 3 ? 1u << 22 : 0u);
+                TL_ST2(&rec->a, L(q_a), L(q_b));
+                TL_ST2(&rec->s2nf, L(q_s2nf), tl_u2d(((uint64_t)w1 << 32) | w0));
+            }
+            TL_LANES_END
+            const int rounds = (q_n + 15) >> 4;
+#ifndef TL_EMULATE
+#pragma unroll
+#endif
+            for (int gr = 0; gr < 3; gr++) {
+                TL_LANES_BEGIN
+                if (L(q_ba)) {                                          // the granule's samples and scalefactor to the cell's block: seven 16-byte stores
+                    TlQGran *blk = &qg[L(q_rank)];
+#ifndef TL_EMULATE
+#pragma unroll
+#endif
+                    for (int j = 0; j < 12; j += 2) TL_ST2(&blk->s[j], L(smp)[gr * 12 + j], L(smp)[gr * 12 + j + 1]);
+                    TL_ST2(&blk->sf, L(q_sf)[gr], L(q_rsf)[gr]);
+                }
+                TL_LANES_END
+#ifndef TL_EMULATE
+#pragma nounroll
+#endif
+                for (int k = 0; k < rounds; k++) {
+                    TL_LANES_BEGIN
+                    const int cell = 16 * k + (lane >> 2), j = lane & 3;
+                    if (cell < q_n) {
+                        const TlQCell *rec = &qc[cell];
+                        const TlQGran *blk = &qg[cell];
+                        double c_a, c_b, c_s2nf, c_w, sfv, rsf;
+                        TL_LD2(&rec->a, c_a, c_b);
+                        TL_LD2(&rec->s2nf, c_s2nf, c_w);
+                        TL_LD2(&blk->sf, sfv, rsf);
+                        const uint64_t cw = tl_d2u(c_w);
+                        const uint32_t w0 = (uint32_t)cw, w1 = (uint32_t)(cw >> 32);
+                        const unsigned s2n = w1 & 0xffffu;
+                        unsigned v[3];
+                        for (int x = 0; x < 3; x++) {                   // the lane-per-cell loop's statements, on the triple's own cell
+                            const double s = blk->s[3 * j + x];
+                            double d = tl_div_by(s, sfv, rsf);
+                            d = d * c_a + c_b;
+                            const bool neg = !(d >= 0);
+                            d += TL_SELECT(neg, 1.0, 0.0);
+                            const unsigned qv = (unsigned)(d * c_s2nf);
+                            v[x] = qv | (neg ? 0u : s2n);
+                        }
+                        const int pos = p_smp + (4 * gr + j) * n_smp + (int)(w0 >> 17);
+                        const bool three = (w1 >> 22) != 0;
+                        const unsigned M = w0 & 0x1ffffu;
+                        const unsigned fa = TL_SELECT(three, v[2], v[0]), fc = TL_SELECT(three, v[0], v[2]);
+                        const unsigned inner = v[1] + M * fc;
+                        tl_put_bits48(frame, pos, (uint64_t)fa + (uint64_t)M * (uint64_t)inner, (int)((w1 >> 16) & 63u));
+                    }
+                    TL_LANES_END
+                }
+            }
+        } else {
 #ifndef TL_EMULATE
 #pragma unroll
 #endif
@@ -354,6 +432,7 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
             }
             if (taps) for (int x = 0; x < 3; x++) taps->subband[c][gr][j0 + x][sb] = (c < nch) ? v[x] : 0;
             TL_LANES_END
+        }
         }
     }
 

@@ -77,6 +77,8 @@ TL_FN void tlh_par_sum_i32(int (&d)[64], const int (&v)[64])
 #define TL_PIN(x) ((void)0)
 #define TL_TIE(p, v) ((void)0)
 #define TL_LD2(p, a, b) do { const double *p_ = (p); (a) = p_[0]; (b) = p_[1]; } while (0)
+#define TL_ST2(p, a, b) do { double *p_ = (p); p_[0] = (a); p_[1] = (b); } while (0)
+#define TL_RANK_BELOW(mask) __builtin_popcountll((mask) & ((1ull << lane) - 1ull))     /* set bits of a ballot below this lane */
 #else
 #define TL_FN __device__ __forceinline__
 #define TL_LANES_BEGIN { int lane_ = (int)(threadIdx.x & 63u); asm volatile("" : "+v"(lane_)); __builtin_assume(lane_ >= 0 && lane_ < 64); const int lane = lane_;
@@ -229,6 +231,8 @@ TL_FN int tld_par_sum_i32(int v)
 #define TL_KEEP(x) asm volatile("" : : "v"(x))             /* x is computed (a load: issued) here, not sunk into a later branch */
 typedef double tl_f64x2 __attribute__((ext_vector_type(2)));
 #define TL_LD2(p, a, b) do { const tl_f64x2 v_ = *(const tl_f64x2 *)(p); (a) = v_.x; (b) = v_.y; } while (0)      /* two doubles, 16-byte aligned: one ds_read_b128 */
+#define TL_ST2(p, a, b) do { tl_f64x2 v_; v_.x = (a); v_.y = (b); *(tl_f64x2 *)(p) = v_; } while (0)      /* ... one ds_write_b128 */
+#define TL_RANK_BELOW(mask) ((int)__builtin_amdgcn_mbcnt_hi((uint32_t)((mask) >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)(mask), 0u)))
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) struct TlLaunch *TlKArg;     /* the kernel-argument segment: scalar loads */
 #else
@@ -389,6 +393,31 @@ struct TlMainLds {
     __device__ YpRows yp_rows() { return yp; }
 #endif
 };
+// The quantiser's re-deal (mp2_pack.h K6): a frame whose live cells (bit_alloc != 0) are few leaves the lanes of the others idle through
+// all twelve rounds of three samples.  Such a frame ranks its live cells, passes their samples through LDS a granule at a time and gives
+// every lane ONE triple of a round: lane -> (cell 16 k + (lane >> 2), triple lane & 3), ceil(n / 16) rounds per granule instead of four.
+// What travels is a record per cell (class constants and field geometry, written once) and a block per cell and granule (its twelve
+// samples, the granule's scalefactor and its reciprocal).  Both live in what is dead while K6 runs: the staging area behind frame[0]
+// (u.fbk.pcm; frame[1] belongs to tl_encode_pair, which keeps the lane-per-cell loop) and the filterbank's yp[] right after it.
+// TL_Q_REDEAL=0 builds without it (measurement: the lane-per-cell loop for every frame); TL_Q_REDEAL_MAX is the largest count of live
+// cells that takes it (48: nine rounds instead of twelve; above that the rounds are twelve either way).
+#ifndef TL_Q_REDEAL
+#define TL_Q_REDEAL 1
+#endif
+#ifndef TL_Q_REDEAL_MAX
+#define TL_Q_REDEAL_MAX 48
+#endif
+struct alignas(16) TlQCell { double a, b, s2nf; uint32_t w0, w1; };     // w0: M | o_smp << 17, w1: steps2n | field bits << 16 | grouped << 22
+struct alignas(16) TlQGran { double s[12]; double sf, rsf; };
+#define TL_QRD_OFF ((4 * (TL_MAX_FRAME_WORDS + 2) + 15) & ~15)          /* bytes from the block's start: behind frame[0] */
+#define TL_QRD_CELLS(w) ((TlQCell *)((char *)&(w) + TL_QRD_OFF))                                          /* [TL_Q_REDEAL_MAX] */
+#define TL_QRD_GRANS(w) ((TlQGran *)((char *)&(w) + TL_QRD_OFF + TL_Q_REDEAL_MAX * sizeof(TlQCell)))      /* [TL_Q_REDEAL_MAX] */
+static_assert(sizeof(TlQCell) == 32 && sizeof(TlQGran) == 112, "records are whole 16-byte pieces");
+static_assert(offsetof(TlMainLds, u) == 0 && offsetof(TlMainLds, yp) == sizeof(((TlMainLds *)0)->u) && offsetof(TlMainLds, yp) % 16 == 0,
+              "yp[] follows the staging union without a gap");
+static_assert(TL_QRD_OFF + TL_Q_REDEAL_MAX * (sizeof(TlQCell) + sizeof(TlQGran)) <= offsetof(TlMainLds, yp) + sizeof(((TlMainLds *)0)->yp),
+              "cell records and granule blocks end inside yp[]");
+static_assert(TL_Q_REDEAL_MAX >= 0 && TL_Q_REDEAL_MAX <= 64 && TL_MAX_FRAME_BYTES * 8 / 12 < (1 << 11), "a rank per lane; o_smp fits its 11 bits");
 // Per-wave LDS of the psy kernel of models 2 and 4: the transform / energies (partition sums in its dead upper half) and c[] / fthr[].
 struct alignas(16) TlPsy2Lds {       // (16: the partition sums are read as pairs, tl_psy2_pass)
     struct { double fft[1024]; } u;
@@ -439,6 +468,17 @@ static long tl_emu_near1_full = 0;
 #define TL_DBG_NEAR1_FULL() (tl_emu_near1_full++)
 #else
 #define TL_DBG_NEAR1_FULL() ((void)0)
+#endif
+// Emulation only: which way the quantiser went, frame by frame (mp2_pack.h K6), with the frame's count of live cells -- out[0] / out[1]:
+// frames of tl_encode_frame on the lane-per-cell loop / re-dealt; out[2 + n] / out[67 + n]: the same by live cells n = 0..64.
+#ifdef TL_EMULATE
+static long tl_emu_redeal[2][66];
+#define TL_DBG_REDEAL(took, ba) do { int n_ = 0; for (int l_ = 0; l_ < 64; l_++) n_ += (ba)[l_] != 0; \
+                                     tl_emu_redeal[(took) ? 1 : 0][0]++; tl_emu_redeal[(took) ? 1 : 0][1 + n_]++; } while (0)
+extern "C" __attribute__((weak, visibility("default"))) void emu_redeal_stats(long *out)
+{ out[0] = tl_emu_redeal[0][0]; out[1] = tl_emu_redeal[1][0]; for (int i = 0; i < 65; i++) { out[2 + i] = tl_emu_redeal[0][1 + i]; out[67 + i] = tl_emu_redeal[1][1 + i]; } }
+#else
+#define TL_DBG_REDEAL(took, ba) ((void)0)
 #endif
 
 // ---- the stages, one file each.  They are FRAGMENTS of this header: they rely on the macros and LDS blocks above and on each
