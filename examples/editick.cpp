@@ -7,9 +7,12 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M]
+//                [--short-every N --short-by M] [--monitor check|audio]
 //   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth stream delivers M sample
 //   frames fewer than 1152; the library stretches what came over the frame as the reference does and counts the underruns.
+//   --monitor check|audio: the confidence monitor (tlb_tick_enable_monitor): every frame that leaves is checked on the device (audio: also
+//   decoded).  One summary line at the end -- frames checked, bad frames, longest bad run over all streams, streams whose decoded output
+//   is silent -- and a non-zero exit status when any frame was bad.
 // out.af: for every packet a little-endian uint32 length, then the packet.
 #include <chrono>
 #include <cstdint>
@@ -30,12 +33,12 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio]\n", argv[0]);
         return 2;
     }
     long rate = 48000;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0;
     char mode = 0;
     double gain_db = 0.0;
     for (int i = 3; i + 1 < argc; i += 2) {
@@ -51,6 +54,7 @@ int main(int argc, char **argv)
         else if (k == "-t") now_s = std::atoll(v);
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
+        else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
     if (!mode) mode = channels == 1 ? 'm' : 'j';             // odr-audioenc's defaults (src/odr-audioenc.cpp:697-709)
@@ -75,10 +79,12 @@ int main(int argc, char **argv)
     if (!t) die("tlb_tick_create", err);
     if (gain_db != 0.0 && tlb_tick_set_gain_db(t, -1, gain_db)) die("gain", 0);
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
+    if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
 
     const size_t per_frame = 1152 * (size_t)channels;        // samples of one frame in the file
     std::vector<int16_t> frame(per_frame);
     long frames = 0, packets = 0;
+    uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any stream has shown after a tick
     const auto t0 = std::chrono::steady_clock::now();
     auto emit = [&]() {
         for (int u = 0; u < tlb_tick_units(t, 0); u++) {
@@ -90,6 +96,8 @@ int main(int argc, char **argv)
             if (std::fwrite(le, 1, 4, fo) != 4 || std::fwrite(p, 1, n, fo) != n) die("write", 0);
             packets++;
         }
+        if (const tlb_monitor_record *r = tlb_tick_monitor(t))   // what an operator reads every tick: [nstreams] records of the tick just waited for
+            for (int s = 0; s < nstreams; s++) if (r[s].bad_run > longest_run) longest_run = r[s].bad_run;
     };
     while (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) == per_frame) {
         int16_t *in = tlb_tick_pcm(t);                       // pinned [nstreams][2304]; mono streams use the first 1152 values
@@ -110,11 +118,18 @@ int main(int argc, char **argv)
         const uint32_t *ms = tlb_tick_underrun_ms(t), *n = tlb_tick_underruns(t);
         std::fprintf(stderr, "editick: stream 0: %u short reads, %u ms since its last full read\n", n[0], ms[0]);
     }
+    unsigned long checked = 0, bad = 0;
+    if (monitor) {
+        const tlb_monitor_record *r = tlb_tick_monitor(t);
+        int silent = 0;
+        for (int s = 0; s < nstreams; s++) { checked += r[s].frames; bad += r[s].bad_frames; silent += r[s].out_silence_ms > 0; }
+        std::fprintf(stderr, "editick: monitor: %lu frames checked, %lu bad, longest bad run %u, %d stream(s) silent at the output\n", checked, bad, longest_run, silent);
+    }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",
                  frames, nstreams, packets, sec, sec > 0 ? (double)frames * nstreams / sec : 0.0);
     tlb_tick_destroy(t);
     std::fclose(fi);
     std::fclose(fo);
-    return 0;
+    return bad ? 3 : 0;
 }

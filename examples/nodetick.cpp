@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M]
+//                 [--short-every N --short-by M] [--monitor check|audio]
 //   in.s16le: interleaved stereo 48 kHz; stream s starts reading at frame s (so the services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
 //   -o: the AF packets of the LAST stream of the node, length-prefixed (uint32 LE) -- the stream farthest from shard 0.
@@ -19,6 +19,9 @@
 //   while the others tick on, and comes back by itself; each shard's late / missed / dropped counts go to stderr at the end.
 //   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth service delivers M
 //   sample frames fewer than 1152; the total of short reads and the longest time without a full read go to stderr at the end.
+//   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
+//   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
+//   is silent -- and a non-zero exit status when any frame was bad.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -83,10 +86,10 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0;
     double deadline_ms = 0;
     std::string devs, outpath;
     for (int i = 2; i + 1 < argc; i += 2) {
@@ -102,6 +105,7 @@ int main(int argc, char **argv)
         else if (k == "--deadline-ms") { deadline_ms = std::atof(v); if (!(deadline_ms > 0)) die("--deadline-ms wants a positive number", 0); }
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
+        else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
     if (short_every < 0 || short_by < 0 || short_by > 1152 || (short_every > 0) != (short_by > 0)) die("--short-every N --short-by M: N >= 1 and 1 <= M <= 1152, both or neither", 0);
@@ -150,12 +154,18 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_set_deadline_ms(nd, deadline_ms)) die("tlb_node_set_deadline_ms", rc);
     if (short_every)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
+    if (monitor)
+        if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
 
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
     Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
-    auto tap = [&]() {                                           // -o: the last stream's packets
+    uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick
+    auto tap = [&]() {                                           // the records of the step just waited for; -o: the last stream's packets
+        if (monitor)
+            for (int s = 0; s < nstreams; s++)
+                if (const tlb_monitor_record *r = tlb_node_monitor(nd, s)) if (r->bad_run > longest_run) longest_run = r->bad_run;      // (NULL: its shard is down or late)
         if (!fo) return;
         const int s = nstreams - 1;
         for (int u = 0; u < tlb_node_units(nd, s); u++) {
@@ -236,11 +246,18 @@ int main(int argc, char **argv)
         for (int s = 0; s < nstreams; s++) { total += tlb_node_underruns(nd, s); const uint32_t ms = tlb_node_underrun_ms(nd, s); if (ms > worst) worst = ms; }
         std::fprintf(stderr, "nodetick: %lu short reads in all, longest time without a full read %u ms\n", total, worst);
     }
+    unsigned long checked = 0, bad = 0;
+    if (monitor) {                                                        // (a restarted shard's records count from its restart)
+        int silent = 0;
+        for (int s = 0; s < nstreams; s++)
+            if (const tlb_monitor_record *r = tlb_node_monitor(nd, s)) { checked += r->frames; bad += r->bad_frames; silent += r->out_silence_ms > 0; }
+        std::fprintf(stderr, "nodetick: monitor: %lu frames checked, %lu bad, longest bad run %u, %d service(s) silent at the output\n", checked, bad, longest_run, silent);
+    }
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",
                 nstreams, G, ticks, tot.frames, npk, nby, sec, sec > 0 ? tot.frames / sec : 0.0, sec > 0 ? ticks * 0.024 / sec : 0.0);
     (void)all; (void)restarts;
     if (fo) std::fclose(fo);
     tlb_node_destroy(nd);
-    return 0;
+    return bad ? 3 : 0;
 }

@@ -592,6 +592,70 @@ int tlb_decode_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int
 int tlb_decode_reset(tlb_batch *b, int stream);
 long tlb_decode_bad_frames(const tlb_batch *b);
 
+/* ---------------------------------------------------------------------------------------------
+ * Confidence monitor: the frame check above where the frames are -- inside the real-time loop (tlb_tick_*, tlb_node_*), which keeps them on
+ * the device between encode and egress.  Three questions per stream and tick: did the frame that just left pass its checks, how many
+ * failed and how many in a row, is there audio at the output when there is audio at the input.  Opt-in at every level: an object that
+ * never enables it makes exactly the device calls it made before this existed.
+ *
+ * THE FOLD (batch level).  tlb_monitor_*() folds what tlb_decode_*() reports into ONE 32-byte record per stream (little-endian, no padding):
+ *   d_report tlb_frame_report [nframes][nstreams]     (tlb_decode_device output)
+ *   d_pcm    int16 [nframes][nstreams][2][1152] exactly as tlb_decode_device writes it, or NULL
+ *   d_record tlb_monitor_record [nstreams], read-modify-write like d_silence_ms: the caller zeroes it once
+ * A stream's slots are taken in order; with st the slot's status:
+ *   1. last_status = st, flags_seen |= st.
+ *   2. st & TLB_DEC_EMPTY: out_peak = {0, 0}; nothing else changes.
+ *   3. frames++.  st & TLB_DEC_BAD_MASK: bad_frames++ and bad_run++; otherwise bad_run = 0.
+ *   4. with PCM: out_peak[c] = max(0, max_i pcm[c][i]); out_silence_ms gains the frame's duration -- the one tlb_silence_device adds for the
+ *      stream's configuration -- when both peaks are 0 and goes back to 0 otherwise.  A frame that failed decodes to zeros and so counts
+ *      as silence: that is what a listener hears.
+ *   5. without PCM: out_peak and out_silence_ms stay as they are.
+ * Integer arithmetic throughout: the result does not depend on how a stream's slots are cut into calls.  Asynchronous on `hip_stream` and
+ * ordered like the decode calls; one wavefront per stream.  A NULL batch, report or record pointer, nframes <= 0 or a pointer that is not
+ * 4-byte aligned return TLB_ERR_ARG and change nothing.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    uint32_t frames;               /* non-empty slots looked at */
+    uint32_t bad_frames;           /* of those, with any TLB_DEC_BAD_MASK flag */
+    uint32_t bad_run;              /* bad frames in a row ending at the last non-empty slot; 0 after a frame that passed */
+    uint32_t flags_seen;           /* OR of every status looked at */
+    uint32_t last_status;          /* status of the last slot looked at, EMPTY included */
+    uint32_t out_silence_ms;       /* the silence counter of tlb_silence_device, on the DECODED audio */
+    int16_t out_peak[2];           /* max(0, samples) per channel of the last slot's decoded audio, as tlb_ingest_device's peaks */
+    uint32_t reserved_;            /* 0 */
+} tlb_monitor_record;
+int tlb_monitor_device(tlb_batch *b, const tlb_frame_report *d_report, const int16_t *d_pcm, int nframes, tlb_monitor_record *d_record,
+                       void *hip_stream);
+int tlb_monitor_host(tlb_batch *b, const tlb_frame_report *report, const int16_t *pcm, int nframes, tlb_monitor_record *record);
+/* TICK PLANE.  tlb_tick_enable_monitor(what) before the first submit (TLB_ERR_ARG after it, and for any other `what`; TLB_ERR_HIP on a
+ * broken object; a second call with the same `what` is OK): every tick that has frames -- all but the first, and tlb_tick_finish's flushed
+ * frames -- then queues tlb_decode_device on the group's frames behind its egress kernels, and the fold into the group's device records.
+ * The packets' copy-out does not wait for either; the records travel behind it, in three host sets like the silence counter.
+ *   TLB_MONITOR_CHECK  unpack and verify only: frames, bad_frames, bad_run, flags_seen, last_status
+ *   TLB_MONITOR_AUDIO  also synthesise: out_peak, out_silence_ms, listen (implies CHECK)
+ * tlb_tick_monitor() shows tlb_monitor_record [nstreams] of the tick waited for last -- NULL when the monitor is not enabled; on a broken
+ * object the last good tick, like the other read accessors.  The group's batch owns the decoder state, so the stream life-cycle calls
+ * reset the decoder for the stream they touch (its next frame is SCFCRC_UNCHECKED); they leave the records alone, as they leave the silence
+ * counter.  A record counts the frames that LEFT: after T submits and tlb_tick_finish, frames == T.
+ * LISTEN (AUDIO only; TLB_ERR_ARG otherwise, and for a stream out of range): tlb_tick_monitor_listen(stream) selects ONE stream, or -1 for
+ * none (the default), between any two submits and from the next submit on; that stream's decoded frame, int16 [2][1152], then comes back
+ * with every tick (one 4608-byte copy).  tlb_tick_monitor_pcm() shows it for the tick waited for last, *stream (may be NULL) = the stream
+ * that tick carried; NULL with *stream = -1 when none was selected, on the first tick, or when the monitor is not enabled.
+ * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_monitor goes to every shard before the first submit, and a
+ * restarted shard is enabled again -- its records start from zero, its streams are fresh.  tlb_node_monitor(stream) takes a node-wide index
+ * and answers NULL when not enabled and for a broken, late or stale shard.  tlb_node_monitor_listen routes to the stream's shard and clears
+ * the selection on the others: TLB_ERR_HIP for a stream of a broken shard, TLB_ERR_LATE for one of a late shard. */
+#define TLB_MONITOR_CHECK 1
+#define TLB_MONITOR_AUDIO 2
+int tlb_tick_enable_monitor(tlb_tick *t, int what);
+const tlb_monitor_record *tlb_tick_monitor(const tlb_tick *t);
+int tlb_tick_monitor_listen(tlb_tick *t, int stream);
+const int16_t *tlb_tick_monitor_pcm(const tlb_tick *t, int *stream);
+int tlb_node_enable_monitor(tlb_node *nd, int what);
+const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream);
+int tlb_node_monitor_listen(tlb_node *nd, int stream);
+const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

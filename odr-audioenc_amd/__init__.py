@@ -13,4 +13,5 @@ from .toolame import (  # noqa: F401
     Batch, StreamConfig, ToolameError, LIB_PATH, build, load_library, lds_bytes_per_stream, legacy_api,
     EDI_STATE_DTYPE, edi_state_init, Tick, Node, node_partition, node_plan, load_fault_library, FAULT_LIB_PATH,
     FRAME_REPORT_DTYPE, FRAME_FIELDS_DTYPE, DEC_EMPTY, DEC_BAD_MASK, DEC_SCFCRC_UNCHECKED,
+    MONITOR_DTYPE,
 )

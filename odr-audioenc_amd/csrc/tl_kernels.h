@@ -1,5 +1,5 @@
 // tl_kernels.h -- the one door between the host translation units (tlb_batch.cpp, tlb_egress.cpp, tlb_tick.cpp: plain C++, seconds to
-// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
+// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip, toolame_monitor.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
 // `st` and returns hipGetLastError(); grid shapes that depend on the kernels' wave counts are computed from the constants below.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -41,4 +41,7 @@ hipError_t tlk_ingest_valid(unsigned blocks, hipStream_t st, const int16_t *in, 
                             const TlConfig *configs, const int32_t *stream_cfg, int nstreams);
 hipError_t tlk_underrun(unsigned blocks, hipStream_t st, const int32_t *valid, uint32_t *underrun_ms, uint32_t *underruns, const TlConfig *configs,
                         const int32_t *stream_cfg, int nstreams, int nframes);
+// toolame_monitor.hip: tl_monitor_kernel, one wavefront per stream over the stream's slots in order (csrc/mp2_monitor.h); record uint32 [nstreams][8]
+hipError_t tlk_monitor(hipStream_t st, const TlFrameReport *report, const int16_t *pcm, uint32_t *record, const TlConfig *configs,
+                       const int32_t *stream_cfg, int nstreams, int nframes);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

@@ -10,6 +10,10 @@ extern "C" {
 #endif
 int tlb_debug_fail_next(tlb_batch *b, int nth);                    /* the nth launch of this batch from now fails (1 = the next; 0 disarms) */
 int tlb_debug_tick_fail_next(tlb_tick *t, int nth);                /* ... the nth submit of this tick object, in its LAST group: the groups before it have been queued */
+/* The nth submit from now (1 = the next; 0 disarms) XORs byte `byte` of that stream's slot in the tick's device frame buffer with xor_mask, after the
+ * encode and before the egress and the confidence monitor: the caller receives the damaged frame and the monitor sees the same bytes.  A
+ * host-queued one-byte copy out and back in; it does not fault the device. */
+int tlb_debug_tick_damage_next(tlb_tick *t, int stream, int byte, int xor_mask, int nth);
 int tlb_debug_node_fail_next(tlb_node *nd, int shard, int nth);    /* ... of one shard of a node */
 /* A stalled shard for the node's tick deadline: the nth wait job of that shard from now (1 = the next; 0 disarms), AFTER its
  * tlb_tick_wait has returned with the tick complete, sleeps `ms` on the shard's HOST thread and then returns `rc` (0: the tick's results

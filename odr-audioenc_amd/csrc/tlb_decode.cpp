@@ -7,6 +7,8 @@ static_assert(TLB_DEC_EMPTY == TL_DEC_EMPTY && TLB_DEC_BAD_SYNC == TL_DEC_BAD_SY
               TLB_DEC_BAD_ALLOC == TL_DEC_BAD_ALLOC && TLB_DEC_OVERRUN == TL_DEC_OVERRUN && TLB_DEC_BAD_MASK == TL_DEC_BAD_MASK, "status flags");
 static_assert(sizeof(tlb_frame_report) == sizeof(TlFrameReport) && sizeof(tlb_frame_fields) == sizeof(TlFrameFields), "C-ABI records");
 
+static int dec_prepare(tlb_batch *b);
+int decode_prepare(tlb_batch *b) { return dec_prepare(b); }
 static int dec_prepare(tlb_batch *b)
 {
     if (b->d_dec_bad) return TLB_OK;

@@ -97,4 +97,6 @@ int tlb_launch(tlb_batch *b, const int16_t *d_pcm, int nframes, const uint8_t *d
 int zmq_frame_device(tlb_batch *b, const uint8_t *d_frames, const int16_t *d_peaks, int nframes, uint8_t *d_msgs, void *hip_stream, const int32_t *d_frame_len);
 int edi_af_device(tlb_batch *b, const uint8_t *d_frames, const int16_t *d_levels, int nframes, tlb_edi_state *d_state,
                   const char *version, int version_len, uint8_t *d_pkts, int32_t *d_pkt_len, void *hip_stream, const int32_t *d_frame_len);
+// tlb_decode.cpp: the decoder's tables and per-stream state, as the first decode call makes them (it waits for the device once)
+int decode_prepare(tlb_batch *b);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -152,6 +152,8 @@ struct tlb_node {
     long submitted = 0, waited = 0;              // node steps: submits / waits so far (a step's index is its submit's)
     double deadline_ms = 0;                      // TICK DEADLINE; 0 = none
     bool short_reads = false;                    // tlb_node_enable_short_reads(): every shard's tick object carries `valid` and the underrun counters (a restarted shard's too)
+    int monitor = 0;                             // tlb_node_enable_monitor(): TLB_MONITOR_* of every shard's tick object (a restarted shard's too)
+    int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
@@ -280,6 +282,8 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         s.tick = tlb_tick_create(s.device, s.n, nd->cfgs.data() + s.first, &tc, &e);
         if (!s.tick) return e ? e : TLB_ERR_HIP;
         if (nd->short_reads) if (int rc = tlb_tick_enable_short_reads(s.tick)) return rc;
+        if (nd->monitor) if (int rc = tlb_tick_enable_monitor(s.tick, nd->monitor)) return rc;
+        if (nd->monitor && nd->listen >= s.first && nd->listen < s.first + s.n) if (int rc = tlb_tick_monitor_listen(s.tick, nd->listen - s.first)) return rc;
     } else {
         s.batch = tlb_create(s.device, s.n, nd->cfgs.data() + s.first, &e);
         if (!s.batch) return e ? e : TLB_ERR_HIP;
@@ -542,6 +546,47 @@ int tlb_node_enable_short_reads(tlb_node *nd)
     const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
     if (!rc) nd->short_reads = true;
     return rc;
+}
+// The confidence monitor (tlb_tick_enable_monitor of every shard, on the shards' threads): before the first submit, TICK plane only.
+int tlb_node_enable_monitor(tlb_node *nd, int what)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0 || (what != TLB_MONITOR_CHECK && what != TLB_MONITOR_AUDIO)) return TLB_ERR_ARG;
+    if (nd->monitor) return nd->monitor == what ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    const int rc = nd->all([what](Shard &s) { return s.tick ? tlb_tick_enable_monitor(s.tick, what) : (int)TLB_ERR_HIP; });
+    if (!rc) nd->monitor = what;
+    return rc;
+}
+const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    const tlb_monitor_record *p = s && s->tick ? tlb_tick_monitor(s->tick) : nullptr;
+    return p ? p + k : nullptr;
+}
+// One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'
+// tick objects that their next submit reads; no shard but a late one runs a job between the node's calls, and a late one is left alone
+// (it cannot be the stream's shard: TLB_ERR_LATE).
+int tlb_node_monitor_listen(tlb_node *nd, int stream)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= nd->nstreams) return TLB_ERR_ARG;
+    int k = 0; Shard *own = stream >= 0 ? nd->of(stream, &k) : nullptr;
+    if (own && own->late) return TLB_ERR_LATE;
+    if (own && !own->live()) return TLB_ERR_HIP;
+    for (Shard *s : nd->shards)
+        if (s->on() && s->tick) (void)tlb_tick_monitor_listen(s->tick, s == own ? k : -1);
+    nd->listen = stream;
+    return TLB_OK;
+}
+const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream)
+{
+    if (stream) *stream = -1;
+    if (!nd || nd->monitor != TLB_MONITOR_AUDIO) return nullptr;
+    for (const Shard *s : nd->shards) {
+        if (!s->on() || s->stale || !s->tick) continue;
+        int k = -1;
+        const int16_t *p = tlb_tick_monitor_pcm(s->tick, &k);
+        if (p) { if (stream) *stream = s->first + k; return p; }
+    }
+    return nullptr;
 }
 int32_t *tlb_node_valid(tlb_node *nd, int stream)
 {

@@ -28,6 +28,9 @@ struct TickGroup {
     uint8_t *h_frames[3] = {}; int32_t *h_flen[3] = {}; uint8_t *h_pkts[3] = {}; int32_t *h_plen[3] = {};
     uint8_t *h_frags[3] = {}; int32_t *h_fraglen[3] = {}, *h_nfrag[3] = {};
     uint8_t *h_msgs[3] = {};
+    // confidence monitor (tlb_tick_enable_monitor): the decode call's reports (and PCM under AUDIO) of this tick's frames, the folded records
+    tlb_frame_report *d_report = nullptr; int16_t *d_mpcm = nullptr; tlb_monitor_record *d_record = nullptr;
+    hipEvent_t ev_mon = nullptr;                                // decode + fold done: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
                                                                                 // ingest (d_inter) / encode (X-PAD), its kernels for this tick's copy-out
@@ -47,6 +50,14 @@ struct tlb_tick {
     // the two underrun counters with the output sets.  A set of h_valid is all 1152 whenever the caller can see it untouched.
     bool short_reads = false;
     int32_t *h_valid[2] = {}; uint32_t *h_underrun_ms[3] = {}, *h_underruns[3] = {};
+    // confidence monitor, off (0) until tlb_tick_enable_monitor(): the records and the listened stream's PCM travel with the output sets
+    int monitor = 0;                             // TLB_MONITOR_CHECK / TLB_MONITOR_AUDIO
+    tlb_monitor_record *h_record[3] = {}; int16_t *h_listen[3] = {};
+    int listen = -1;                             // the stream the NEXT submit carries (tlb_tick_monitor_listen); -1: none
+    int listen_of[3] = {-1, -1, -1};             // ... the tick of each output set carried
+#ifdef TLB_FAULT_INJECT
+    int damage_nth = 0, damage_stream = 0, damage_byte = 0; uint8_t damage_xor = 0, damage_val = 0;      // tlb_debug_tick_damage_next
+#endif
     int in_set = 0, out_set = 0;
     long waited = 0;                             // ticks whose results have been waited for (ticks: submitted)
     std::vector<void *> pinned, dev;
@@ -74,6 +85,7 @@ void tlb_tick_destroy(tlb_tick *t)
         if (g.ev_ingested) (void)hipEventDestroy(g.ev_ingested);
         if (g.ev_encoded) (void)hipEventDestroy(g.ev_encoded);
         if (g.ev_out) (void)hipEventDestroy(g.ev_out);
+        if (g.ev_mon) (void)hipEventDestroy(g.ev_mon);
     }
     for (void *p : t->dev) (void)hipFree(p);
     for (void *p : t->pinned) (void)hipHostFree(p);
@@ -233,6 +245,49 @@ int tlb_tick_enable_short_reads(tlb_tick *t)
     t->short_reads = true;
     return TLB_OK;
 }
+// The confidence monitor is opted into the same way: the object then queues tlb_decode_device and the fold (tlb_monitor_device) behind
+// every tick's egress kernels.  The decoder's tables and state are made here, not by the first tick (the first decode call of a batch
+// waits for the device once).  An object that never makes the call makes the device calls it always made.
+int tlb_tick_enable_monitor(tlb_tick *t, int what)
+{
+    if (!t || t->finished || t->ticks > 0 || (what != TLB_MONITOR_CHECK && what != TLB_MONITOR_AUDIO)) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (t->monitor) return t->monitor == what ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(t->device));
+    const size_t ns = (size_t)t->nstreams, pcm_bytes = 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t);
+    auto pin = [&](size_t bytes) -> void * { void *p = nullptr; if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr; memset(p, 0, bytes); t->pinned.push_back(p); return p; };
+    for (int k = 0; k < 3; k++) {
+        t->h_record[k] = (tlb_monitor_record *)pin(ns * sizeof(tlb_monitor_record));
+        t->h_listen[k] = (int16_t *)pin(pcm_bytes);
+        if (!t->h_record[k] || !t->h_listen[k]) return TLB_ERR_HIP;
+    }
+    for (auto &G : t->groups) {
+        const size_t n = (size_t)G.n;
+        auto dev = [&](size_t bytes) -> void * { void *p = nullptr; if (hipMalloc(&p, bytes) != hipSuccess) return nullptr; t->dev.push_back(p); return hipMemset(p, 0, bytes) == hipSuccess ? p : nullptr; };
+        if (int rc = decode_prepare(G.b)) return rc;
+        G.d_report = (tlb_frame_report *)dev(n * sizeof(tlb_frame_report));
+        G.d_record = (tlb_monitor_record *)dev(n * sizeof(tlb_monitor_record));
+        if (what == TLB_MONITOR_AUDIO) G.d_mpcm = (int16_t *)dev(n * pcm_bytes);
+        if (!G.d_report || !G.d_record || (what == TLB_MONITOR_AUDIO && !G.d_mpcm)) return TLB_ERR_HIP;
+        if (!G.ev_mon) HIPCHK(hipEventCreateWithFlags(&G.ev_mon, hipEventDisableTiming));
+    }
+    HIPCHK(hipDeviceSynchronize());                                  // the memsets ran on the null stream, the tick's streams do not wait for it
+    t->monitor = what;
+    return TLB_OK;
+}
+const tlb_monitor_record *tlb_tick_monitor(const tlb_tick *t) { return t && t->monitor ? t->h_record[t->out_set] : nullptr; }
+int tlb_tick_monitor_listen(tlb_tick *t, int stream)
+{
+    if (!t || t->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
+    t->listen = stream;
+    return TLB_OK;
+}
+const int16_t *tlb_tick_monitor_pcm(const tlb_tick *t, int *stream)
+{
+    const int s = t && t->monitor == TLB_MONITOR_AUDIO ? t->listen_of[t->out_set] : -1;
+    if (stream) *stream = s;
+    return s >= 0 ? t->h_listen[t->out_set] : nullptr;
+}
 long tlb_tick_count(const tlb_tick *t) { return t ? t->ticks : 0; }
 int tlb_tick_set_gain_db(tlb_tick *t, int stream, double gain_db)
 {
@@ -291,6 +346,11 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
                                             G.d_frags, G.d_fraglen, G.d_nfrag, G.max_frags, G.frag_stride, t->s_run)) return rc;
     }
     HIPCHK(hipEventRecord(G.ev_run, t->s_run));
+    if (t->monitor && have_frames) {                                 // behind the egress kernels: the packets' copy-out waits for ev_run only
+        if (int rc = tlb_decode_device(G.b, G.d_frames, G.d_flen, 1, G.d_report, nullptr, G.d_mpcm, t->s_run)) return rc;
+        if (int rc = tlb_monitor_device(G.b, G.d_report, G.d_mpcm, 1, G.d_record, t->s_run)) return rc;
+        HIPCHK(hipEventRecord(G.ev_mon, t->s_run));
+    }
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -313,7 +373,14 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
             HIPCHK(hipMemcpyAsync(G.h_nfrag[set], G.d_nfrag, slots * 4, hipMemcpyDeviceToHost, t->s_out));
         }
     }
-    HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed
+    if (t->monitor) {                                                // the records (and the listened stream's frame) behind the packets
+        if (have_frames) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_mon, 0));
+        HIPCHK(hipMemcpyAsync(t->h_record[set] + G.first, G.d_record, n * sizeof(tlb_monitor_record), hipMemcpyDeviceToHost, t->s_out));
+        const int k = t->listen_of[set] - G.first;
+        if (G.d_mpcm && k >= 0 && k < G.n)
+            HIPCHK(hipMemcpyAsync(t->h_listen[set], G.d_mpcm + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME, 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost, t->s_out));
+    }
+    HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed (the monitor's reads of d_frames included)
     return TLB_OK;
 }
 
@@ -329,6 +396,24 @@ int tlb_tick_status(const tlb_tick *t) { return !t ? TLB_ERR_ARG : t->broken ? T
 #ifdef TLB_FAULT_INJECT
 // test builds only (csrc/tlb_debug.h): the nth submit from now fails in its LAST group -- after the groups before it have been queued
 int tlb_debug_tick_fail_next(tlb_tick *t, int nth) { if (!t || nth < 0) return TLB_ERR_ARG; t->groups.back().b->fail_in = nth; return TLB_OK; }
+// ... the nth submit from now XORs one byte of that stream's slot in d_frames, between the encode and the egress: what the caller receives
+// and what the monitor sees are the same damaged bytes.  Host-queued copies on s_run, the stream waited for in between: nothing faults.
+int tlb_debug_tick_damage_next(tlb_tick *t, int stream, int byte, int xor_mask, int nth)
+{
+    if (!t || nth < 0 || stream < 0 || stream >= t->nstreams || byte < 0 || byte >= t->groups[(size_t)t->group_of[(size_t)stream]].out_stride) return TLB_ERR_ARG;
+    t->damage_nth = nth; t->damage_stream = stream; t->damage_byte = byte; t->damage_xor = (uint8_t)xor_mask;
+    return TLB_OK;
+}
+static int tick_damage(tlb_tick *t, TickGroup &G)
+{
+    uint8_t *p = G.d_frames + (size_t)(t->damage_stream - G.first) * (size_t)G.out_stride + (size_t)t->damage_byte;
+    HIPCHK(hipMemcpyAsync(&t->damage_val, p, 1, hipMemcpyDeviceToHost, t->s_run));
+    HIPCHK(hipStreamSynchronize(t->s_run));
+    t->damage_val ^= t->damage_xor;
+    HIPCHK(hipMemcpyAsync(p, &t->damage_val, 1, hipMemcpyHostToDevice, t->s_run));
+    HIPCHK(hipStreamSynchronize(t->s_run));
+    return TLB_OK;
+}
 #endif
 
 // Queue one tick -- copy-in, ingest, encode, egress, copy-out of every group -- on the input set the caller has just filled, and
@@ -345,6 +430,10 @@ int tlb_tick_submit(tlb_tick *t)
     const int set = (int)(t->ticks & 1);                             // == in_set: ticks and input sets alternate together
     const int oset = (int)(t->ticks % 3);                            // output set: the caller may still be reading tick - 2's
     if (hipEventRecord(t->ev0[oset], t->s_in) != hipSuccess) return tick_fail(t, TLB_ERR_HIP);
+    t->listen_of[oset] = t->monitor == TLB_MONITOR_AUDIO && t->ticks > 0 ? t->listen : -1;
+#ifdef TLB_FAULT_INJECT
+    const bool damage = t->damage_nth > 0 && --t->damage_nth == 0;
+#endif
     for (auto &G : t->groups) {
         const size_t n = (size_t)G.n;
         int rc = TLB_OK;
@@ -366,6 +455,9 @@ int tlb_tick_submit(tlb_tick *t)
         if (!rc && hipEventRecord(G.ev_ingested, t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc) rc = tlb_launch(G.b, G.d_pcm, 1, t->with_xpad ? G.d_xpad : nullptr, t->with_xpad ? G.d_xl : nullptr, G.d_frames, nullptr, t->s_run, nullptr, G.d_flen);
         if (!rc && hipEventRecord(G.ev_encoded, t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
+#ifdef TLB_FAULT_INJECT
+        if (!rc && damage && t->damage_stream >= G.first && t->damage_stream < G.first + G.n) rc = tick_damage(t, G);
+#endif
         if (!rc) rc = tick_egress(t, G, t->ticks > 0, oset);
         if (rc) return tick_fail(t, rc);
     }
@@ -406,6 +498,7 @@ int tlb_tick_finish(tlb_tick *t)
     if (t->broken) return TLB_ERR_HIP;
     if (hipSetDevice(t->device) != hipSuccess) return tick_fail(t, TLB_ERR_HIP);
     const int set = (int)(t->ticks % 3);
+    t->listen_of[set] = t->monitor == TLB_MONITOR_AUDIO ? t->listen : -1;
     for (auto &G : t->groups) {
         int rc = hipStreamWaitEvent(t->s_run, G.ev_out, 0) == hipSuccess ? TLB_OK : TLB_ERR_HIP;
         if (!rc) rc = tlb_flush_device_len(G.b, G.d_frames, G.d_flen, t->s_run);

@@ -73,6 +73,7 @@ def load_fault_library():
         L.tlb_debug_fail_next.argtypes = [C.c_void_p, C.c_int]
         L.tlb_debug_tick_fail_next.argtypes = [C.c_void_p, C.c_int]
         L.tlb_debug_node_fail_next.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.tlb_debug_tick_damage_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.tlb_debug_node_stall_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         _fault_lib = L
     return _fault_lib
@@ -225,6 +226,21 @@ def _bind(L):
         for f in ("tlb_node_underrun_ms", "tlb_node_underruns"):
             getattr(L, f).restype = C.c_uint32
             getattr(L, f).argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_monitor_device"):          # confidence monitor (an older build loaded through TLB_LIB_PATH has none of it)
+        L.tlb_monitor_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_monitor_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_tick_enable_monitor.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_tick_monitor.restype = C.c_void_p
+        L.tlb_tick_monitor.argtypes = [C.c_void_p]
+        L.tlb_tick_monitor_listen.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_tick_monitor_pcm.restype = C.c_void_p
+        L.tlb_tick_monitor_pcm.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.tlb_node_enable_monitor.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_monitor.restype = C.c_void_p
+        L.tlb_node_monitor.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_monitor_listen.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_monitor_pcm.restype = C.c_void_p
+        L.tlb_node_monitor_pcm.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -282,6 +298,10 @@ FRAME_FIELDS_DTYPE = np.dtype([("bit_alloc", np.uint8, (2, 32)), ("scfsi", np.ui
                                ("subband", np.uint16, (2, 3, 12, 32))])
 DEC_EMPTY, DEC_BAD_SYNC, DEC_HEADER_MISMATCH, DEC_BAD_CRC16, DEC_BAD_SCFCRC, DEC_SCFCRC_UNCHECKED, DEC_BAD_ALLOC, DEC_OVERRUN = (1 << i for i in range(8))
 DEC_BAD_MASK = DEC_BAD_SYNC | DEC_HEADER_MISMATCH | DEC_BAD_CRC16 | DEC_BAD_SCFCRC | DEC_BAD_ALLOC | DEC_OVERRUN
+# tlb_monitor_record (include/toolame_batch.h): the confidence monitor's fold, one per stream
+MONITOR_DTYPE = np.dtype([("frames", np.uint32), ("bad_frames", np.uint32), ("bad_run", np.uint32), ("flags_seen", np.uint32),
+                          ("last_status", np.uint32), ("out_silence_ms", np.uint32), ("out_peak", np.int16, (2,)), ("reserved_", np.uint32)])
+MONITOR_WHAT = {"check": 1, "audio": 2}         # TLB_MONITOR_CHECK / TLB_MONITOR_AUDIO
 
 
 def _config_array(configs):
@@ -372,6 +392,41 @@ class Tick:
     def underruns(self):
         """uint32 [nstreams]: short reads so far; None when not enabled"""
         return self._view("tlb_tick_underruns", C.c_uint32, (self.nstreams,))
+
+    # -- confidence monitor (tlb_decode_device + tlb_monitor_device behind every tick's egress): opt in before the first submit --
+    def enable_monitor(self, what="audio"):
+        """what: "check" (unpack and verify) or "audio" (also synthesise: out_peak, out_silence_ms, listen)"""
+        rc = self.L.tlb_tick_enable_monitor(self.h, MONITOR_WHAT.get(what, what))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_monitor")
+
+    @property
+    def monitor(self):
+        """MONITOR_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when not enabled"""
+        p = self.L.tlb_tick_monitor(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * MONITOR_DTYPE.itemsize)).from_address(p), dtype=MONITOR_DTYPE)
+
+    def monitor_listen(self, s):
+        """select ONE stream (-1: none) whose decoded frame comes back with every tick from the next submit on ("audio" only)"""
+        rc = self.L.tlb_tick_monitor_listen(self.h, int(s))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_monitor_listen")
+
+    def monitor_pcm(self):
+        """(stream, int16 [2][1152] view) of the tick waited for last, or (-1, None) when that tick carried none"""
+        s = C.c_int(-1)
+        p = self.L.tlb_tick_monitor_pcm(self.h, C.byref(s))
+        if not p:
+            return -1, None
+        return s.value, np.ctypeslib.as_array((C.c_int16 * (2 * SAMPLES)).from_address(p)).reshape(2, SAMPLES)
+
+    def damage_next(self, stream, byte, xor_mask, nth=1):
+        """fault-injection TEST build only: the nth submit from now XORs one byte of that stream's frame on the device, ahead of egress and monitor"""
+        rc = self.L.tlb_debug_tick_damage_next(self.h, stream, byte, xor_mask, nth)
+        if rc:
+            raise ToolameError(rc, "tlb_debug_tick_damage_next")
 
     def submit(self):
         """queue one tick on the input set just filled and return at once; `pcm` then shows the other input set"""
@@ -596,6 +651,27 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_decode_host")
         return rep, fl, pcm
+
+    def monitor(self, report, pcm=None, record=None):
+        """tlb_monitor_host: fold reports FRAME_REPORT_DTYPE [nframes, nstreams] (and the decoded pcm int16 [nframes, nstreams, 2, 1152] or
+        None) into record MONITOR_DTYPE [nstreams] -- advanced in place when given, else a fresh all-zero one -- and return it"""
+        rep = np.ascontiguousarray(report, dtype=FRAME_REPORT_DTYPE)
+        if rep.ndim != 2 or rep.shape[1] != self.nstreams:
+            raise ToolameError(18, f"report shape {rep.shape}")
+        nf = rep.shape[0]
+        pc = None
+        if pcm is not None:
+            pc = np.ascontiguousarray(pcm, dtype=np.int16)
+            if pc.shape != (nf, self.nstreams, 2, SAMPLES):
+                raise ToolameError(18, f"pcm shape {pc.shape}")
+        if record is None:
+            record = np.zeros(self.nstreams, dtype=MONITOR_DTYPE)
+        if record.dtype != MONITOR_DTYPE or record.shape != (self.nstreams,) or not record.flags.c_contiguous:
+            raise ToolameError(18, "record: MONITOR_DTYPE [nstreams]")
+        rc = self.L.tlb_monitor_host(self.h, rep.ctypes.data, pc.ctypes.data if pc is not None else None, nf, record.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_monitor_host")
+        return record
 
     def decode_device(self, d_frames_ptr, d_len_ptr, nframes, d_report_ptr, d_fields_ptr=None, d_pcm_ptr=None, stream=None):
         rc = self.L.tlb_decode_device(self.h, d_frames_ptr, d_len_ptr, nframes, d_report_ptr, d_fields_ptr, d_pcm_ptr, stream)
@@ -972,6 +1048,28 @@ class Node:
 
     def underruns(self, s):
         return int(self.L.tlb_node_underruns(self.h, s))
+
+    # confidence monitor (Tick.enable_monitor, per stream with node-wide indices)
+    def enable_monitor(self, what="audio"):
+        self._rc(self.L.tlb_node_enable_monitor(self.h, MONITOR_WHAT.get(what, what)), "tlb_node_enable_monitor")
+
+    def monitor(self, s):
+        """the stream's record (a MONITOR_DTYPE scalar, copied) of the step waited for last; None when not enabled and for a broken, late or stale shard"""
+        p = self.L.tlb_node_monitor(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * MONITOR_DTYPE.itemsize).from_address(p), dtype=MONITOR_DTYPE)[0].copy()
+
+    def monitor_listen(self, s):
+        self._rc(self.L.tlb_node_monitor_listen(self.h, int(s)), "tlb_node_monitor_listen")
+
+    def monitor_pcm(self):
+        """(node-wide stream, int16 [2][1152] view) of the step waited for last, or (-1, None)"""
+        s = C.c_int(-1)
+        p = self.L.tlb_node_monitor_pcm(self.h, C.byref(s))
+        if not p:
+            return -1, None
+        return s.value, np.ctypeslib.as_array((C.c_int16 * (2 * SAMPLES)).from_address(p)).reshape(2, SAMPLES)
 
     def frame(self, s):
         n = C.c_int(0)
