@@ -7,12 +7,15 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare]
 //   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth stream delivers M sample
 //   frames fewer than 1152; the library stretches what came over the frame as the reference does and counts the underruns.
 //   --monitor check|audio: the confidence monitor (tlb_tick_enable_monitor): every frame that leaves is checked on the device (audio: also
 //   decoded).  One summary line at the end -- frames checked, bad frames, longest bad run over all streams, streams whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
+//   --compare: the compare monitor on top of it (tlb_tick_enable_compare with the header's default params; implies --monitor audio): every
+//   frame that leaves is decoded and set against the audio that went in.  A stream whose mismatch_run reaches 3 is printed when it does;
+//   one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any stream got there.
 // out.af: for every packet a little-endian uint32 length, then the packet.
 #include <chrono>
 #include <cstdint>
@@ -33,16 +36,18 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare]\n", argv[0]);
         return 2;
     }
     long rate = 48000;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     char mode = 0;
     double gain_db = 0.0;
-    for (int i = 3; i + 1 < argc; i += 2) {
+    for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
+        if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
+        if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") rate = std::atol(v);
         else if (k == "-c") channels = std::atoi(v);
@@ -57,6 +62,7 @@ int main(int argc, char **argv)
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
+    if (compare) { if (monitor == TLB_MONITOR_CHECK) die("--compare needs --monitor audio", 0); monitor = TLB_MONITOR_AUDIO; }
     if (!mode) mode = channels == 1 ? 'm' : 'j';             // odr-audioenc's defaults (src/odr-audioenc.cpp:697-709)
     if (channels != 1 && channels != 2) die("1 or 2 channels", channels);
     if (nstreams < 1) die("streams", nstreams);
@@ -80,10 +86,13 @@ int main(int argc, char **argv)
     if (gain_db != 0.0 && tlb_tick_set_gain_db(t, -1, gain_db)) die("gain", 0);
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
+    const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
+    if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
     const size_t per_frame = 1152 * (size_t)channels;        // samples of one frame in the file
     std::vector<int16_t> frame(per_frame);
     long frames = 0, packets = 0;
+    int alarms = 0;                                              // compare monitor: times a stream's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any stream has shown after a tick
     const auto t0 = std::chrono::steady_clock::now();
     auto emit = [&]() {
@@ -98,6 +107,13 @@ int main(int argc, char **argv)
         }
         if (const tlb_monitor_record *r = tlb_tick_monitor(t))   // what an operator reads every tick: [nstreams] records of the tick just waited for
             for (int s = 0; s < nstreams; s++) if (r[s].bad_run > longest_run) longest_run = r[s].bad_run;
+        if (const tlb_compare_record *c = tlb_tick_compare(t))   // likewise; a run passes 3 once: a skipped or unjudged frame leaves it alone, so look at this tick's flags too
+            for (int s = 0; s < nstreams; s++)
+                if (c[s].mismatch_run == 3 && (c[s].last_flags & TLB_COMPARE_MISMATCH)) {
+                    std::fprintf(stderr, "editick: compare: stream %d: 3 frames in a row do not sound like their input%s (tick %ld)\n", s,
+                                 c[s].last_flags & TLB_COMPARE_SWAPPED ? ", channels exchanged" : "", frames);
+                    alarms++;
+                }
     };
     while (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) == per_frame) {
         int16_t *in = tlb_tick_pcm(t);                       // pinned [nstreams][2304]; mono streams use the first 1152 values
@@ -125,11 +141,17 @@ int main(int argc, char **argv)
         for (int s = 0; s < nstreams; s++) { checked += r[s].frames; bad += r[s].bad_frames; silent += r[s].out_silence_ms > 0; }
         std::fprintf(stderr, "editick: monitor: %lu frames checked, %lu bad, longest bad run %u, %d stream(s) silent at the output\n", checked, bad, longest_run, silent);
     }
+    if (compare) {
+        const tlb_compare_record *c = tlb_tick_compare(t);
+        unsigned long compared = 0, judged = 0, mismatched = 0;
+        for (int s = 0; s < nstreams; s++) { compared += c[s].frames_compared; judged += c[s].frames_judged; mismatched += c[s].mismatch_frames; }
+        std::fprintf(stderr, "editick: compare: %lu frames compared, %lu judged, %lu mismatched, %d alarm(s)\n", compared, judged, mismatched, alarms);
+    }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",
                  frames, nstreams, packets, sec, sec > 0 ? (double)frames * nstreams / sec : 0.0);
     tlb_tick_destroy(t);
     std::fclose(fi);
     std::fclose(fo);
-    return bad ? 3 : 0;
+    return bad ? 3 : alarms ? 4 : 0;
 }

@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M] [--monitor check|audio]
+//                 [--short-every N --short-by M] [--monitor check|audio] [--compare]
 //   in.s16le: interleaved stereo 48 kHz; stream s starts reading at frame s (so the services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
 //   -o: the AF packets of the LAST stream of the node, length-prefixed (uint32 LE) -- the stream farthest from shard 0.
@@ -22,6 +22,9 @@
 //   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
 //   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
+//   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
+//   frame that leaves is decoded on its GPU and set against the audio that went in.  A service whose mismatch_run reaches 3 is printed when
+//   it does; one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any service got there.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -86,14 +89,16 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     double deadline_ms = 0;
     std::string devs, outpath;
-    for (int i = 2; i + 1 < argc; i += 2) {
+    for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
+        if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
+        if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-n") nstreams = std::atoi(v);
         else if (k == "-G") G = std::atoi(v);
@@ -108,6 +113,7 @@ int main(int argc, char **argv)
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
+    if (compare) { if (monitor == TLB_MONITOR_CHECK) die("--compare needs --monitor audio", 0); monitor = TLB_MONITOR_AUDIO; }
     if (short_every < 0 || short_by < 0 || short_by > 1152 || (short_every > 0) != (short_by > 0)) die("--short-every N --short-by M: N >= 1 and 1 <= M <= 1152, both or neither", 0);
     const int ndev = tlb_device_count();
     if (ndev <= 0) die("no GPU", ndev);
@@ -156,16 +162,29 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
     if (monitor)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
+    const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
+    if (compare)
+        if (int rc = tlb_node_enable_compare(nd, &cparams)) die("tlb_node_enable_compare", rc);         // after the audio monitor, before the first submit
 
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
     Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
+    int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick
     auto tap = [&]() {                                           // the records of the step just waited for; -o: the last stream's packets
         if (monitor)
             for (int s = 0; s < nstreams; s++)
                 if (const tlb_monitor_record *r = tlb_node_monitor(nd, s)) if (r->bad_run > longest_run) longest_run = r->bad_run;      // (NULL: its shard is down or late)
+        if (compare)                                             // a run passes 3 once: a skipped or unjudged frame leaves it alone, so look at this step's flags too
+            for (int s = 0; s < nstreams; s++)
+                if (const tlb_compare_record *c = tlb_node_compare(nd, s))
+                    if (c->mismatch_run == 3 && (c->last_flags & TLB_COMPARE_MISMATCH)) {
+                        std::fprintf(stderr, "nodetick: compare: service %d (shard %d): 3 frames in a row do not sound like their input%s (step %ld)\n", s,
+                                     tlb_node_shard_of(nd, s), c->last_flags & TLB_COMPARE_SWAPPED ? ", channels exchanged" : "", taps);
+                        alarms++;
+                    }
+        taps++;
         if (!fo) return;
         const int s = nstreams - 1;
         for (int u = 0; u < tlb_node_units(nd, s); u++) {
@@ -253,11 +272,17 @@ int main(int argc, char **argv)
             if (const tlb_monitor_record *r = tlb_node_monitor(nd, s)) { checked += r->frames; bad += r->bad_frames; silent += r->out_silence_ms > 0; }
         std::fprintf(stderr, "nodetick: monitor: %lu frames checked, %lu bad, longest bad run %u, %d service(s) silent at the output\n", checked, bad, longest_run, silent);
     }
+    if (compare) {
+        unsigned long compared = 0, judged = 0, mismatched = 0;
+        for (int s = 0; s < nstreams; s++)
+            if (const tlb_compare_record *c = tlb_node_compare(nd, s)) { compared += c->frames_compared; judged += c->frames_judged; mismatched += c->mismatch_frames; }
+        std::fprintf(stderr, "nodetick: compare: %lu frames compared, %lu judged, %lu mismatched, %d alarm(s)\n", compared, judged, mismatched, alarms);
+    }
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",
                 nstreams, G, ticks, tot.frames, npk, nby, sec, sec > 0 ? tot.frames / sec : 0.0, sec > 0 ? ticks * 0.024 / sec : 0.0);
     (void)all; (void)restarts;
     if (fo) std::fclose(fo);
     tlb_node_destroy(nd);
-    return bad ? 3 : 0;
+    return bad ? 3 : alarms ? 4 : 0;
 }

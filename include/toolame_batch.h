@@ -656,6 +656,83 @@ const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream);
 int tlb_node_monitor_listen(tlb_node *nd, int stream);
 const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Compare: is the decoded audio the audio that went in?  The record above answers "is there audio at the output" with peaks and a silence
+ * counter; it cannot see a perfectly valid frame that carries the WRONG audio -- stream k's slot holding stream j's programme, left and
+ * right exchanged, a mono pair crossed, a shard's block shifted by one stream, a stale frame sent again.  Those are the faults of a
+ * batched encoder's indexing, and every one of them has good CRCs and non-silent audio.  tlb_compare_*() sets the planar PCM the encoder
+ * was given beside the PCM tlb_decode_*() synthesised from the frame that left, at the codec's delay, and correlates them in integers.
+ *   d_in_pcm  int16 [nframes][nstreams][2][1152]  the d_pcm of the tlb_encode_device call, or NULL (see FLUSH)
+ *   d_dec_pcm int16 [nframes][nstreams][2][1152]  the d_pcm tlb_decode_device wrote for that call's d_out
+ *   d_report  tlb_frame_report [nframes][nstreams] of that decode call
+ *   d_record  tlb_compare_record [nstreams], read-modify-write like the monitor's: the caller zeroes it once
+ * One stream, slot f.  Output slot f holds input frame f - 1, so dec[f] is the audio of the previous input frame.  The batch keeps, per
+ * stream, that previous input frame P and the last D = TLB_COMPARE_DELAY samples Q of the one before (allocated by the first compare call,
+ * as the decoder's state is).  With x[c][i] = Q[c][i] for i < D, P[c][i - D] for i >= D, and y[c][i] = dec[f][c][i], over i = 0..1151:
+ *   sxx[c] = sum x^2, syy[c] = sum y^2, sxy[c] = sum x y, sxz[c] = sum x[c] y[1 - c]      (int64, below 2^41 in magnitude)
+ * A one-channel stream uses c = 0 only; the rest is 0.  After the slot the history advances by in[f].
+ *   channel c is JUDGED   when sxx[c] >= min_energy
+ *   channel c MATCHES     when sxy[c] > 0 and corr_den^2 sxy[c]^2 >= corr_num^2 sxx[c] syy[c], compared as 128-bit integers;
+ *   the CROSS test        is the same with sxz[c] and syy[1 - c]
+ *   the frame is a MISMATCH when any judged channel fails to match; it is SWAPPED when the stream has two channels, both are judged, neither
+ *   matches and both cross tests match.
+ * frames_compared++; with a judged channel frames_judged++, and a mismatch adds to mismatch_frames and mismatch_run while a match sets
+ * mismatch_run to 0 -- a frame nobody judged leaves mismatch_run alone.  The sums and last_flags are those of the last compared slot.
+ * SKIPPED: a slot whose report has TLB_DEC_EMPTY or any TLB_DEC_BAD_MASK flag is not compared: last_flags = TLB_COMPARE_SKIPPED, sums and
+ * counters stay; its input still advances the history.  FLUSH: with d_in_pcm == NULL (nframes must be 1) the pending frame -- tlb_flush_*'s,
+ * decoded -- is compared against the history, which does not advance.  Integer arithmetic throughout, no floating point anywhere: the
+ * result does not depend on how a stream's slots are cut into calls.  tlb_reset, tlb_stream_reset, tlb_stream_finish and
+ * tlb_stream_reconfigure clear the history of the streams they touch (zeros: never judged until two frames have gone in) and leave the
+ * records alone; tlb_compare_reset(b, stream) does only that (stream = -1: all).  Asynchronous on `hip_stream`, ordered like the decode
+ * calls; one wavefront per stream.  A NULL batch, decoded PCM, report, params or record pointer, nframes <= 0, a NULL d_in_pcm with
+ * nframes != 1, a PCM pointer that is not 16-byte aligned (report: 4, record: 8; hipMalloc'ed memory is) or params outside
+ * 0 < corr_num <= corr_den <= 1024, min_energy >= 1 return TLB_ERR_ARG and change nothing.
+ * THE DELAY is measured, not assumed (tests/test_compare_emu.py: the lag of the largest sum in dec over 0..1151, white noise, the same for
+ * 48 kHz stereo, 24 kHz mono and joint stereo): 481 = the analysis and the synthesis filterbank.  THE DEFAULTS come from
+ * profiles/compare_margins.txt (tools/compare_margins.py): the smallest correlation of a healthy stream and the largest
+ * of a mispaired one over every (rate, mode, bitrate) of the configuration sweep; the default ratio 3/8 lies between the two.
+ * COMPARE NOT MEANINGFUL WITH DEFAULT PARAMS (a healthy stream's correlation falls below the ratio or within 0.05 of it; two or three subbands
+ * are transmitted): 8 kbps at 24 kHz in 's', 'j' and 'd' (0.05, 0.28, 0.05) and at 22.05 kHz in 's' and 'd' (0.376: on the ratio).
+ * Usable with little room (within 0.1): 8 kbps at 22.05 kHz 'j' (0.46) and at 16 kHz 's', 'j', 'd' (0.46).  Over the other 327
+ * configurations the smallest healthy correlation is 0.56 and the largest mispaired one 0.18 (0.19 with the four just named).
+ * TICK PLANE.  tlb_tick_enable_compare(params) after tlb_tick_enable_monitor(TLB_MONITOR_AUDIO) and before the first submit (TLB_ERR_ARG
+ * otherwise; a second call with identical params is OK): every tick then queues the compare behind the group's decode, with the tick's
+ * planar PCM as input (the group's batch keeps the previous tick's through its history, 6.4 KB per stream); tlb_tick_finish's flushed
+ * frames go through the NULL-input form.  tlb_tick_compare() shows tlb_compare_record [nstreams] of the tick waited for last, NULL when not
+ * enabled; the records travel in three host sets behind the packets' copy-out, like the monitor's.  Nothing is allocated or launched
+ * unless compare is enabled.  NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): every shard is enabled, a restarted shard is enabled
+ * again with zero records, and tlb_node_compare(stream) answers NULL when not enabled and for a broken, late or stale shard.
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_COMPARE_DELAY 481
+#define TLB_COMPARE_JUDGED0 0x01u
+#define TLB_COMPARE_JUDGED1 0x02u
+#define TLB_COMPARE_MISMATCH 0x04u
+#define TLB_COMPARE_SWAPPED 0x08u
+#define TLB_COMPARE_SKIPPED 0x10u
+#define TLB_COMPARE_DEFAULT_MIN_ENERGY 75497472      /* 1152 * 256^2: a frame at - 42 dBFS */
+#define TLB_COMPARE_DEFAULT_CORR_NUM 3               /* 3/8: between the largest mispaired (0.18) and the smallest healthy correlation (0.56) outside the nine 8 kbps two-channel LSF configurations named above */
+#define TLB_COMPARE_DEFAULT_CORR_DEN 8
+typedef struct { int64_t min_energy; int32_t corr_num, corr_den; } tlb_compare_params;
+typedef struct {
+    int64_t sxx[2], syy[2], sxy[2], sxz[2];      /* of the last compared slot */
+    uint32_t frames_compared;      /* slots that were not skipped */
+    uint32_t frames_judged;        /* of those, with at least one judged channel */
+    uint32_t mismatch_frames;      /* of those, with a judged channel that did not match */
+    uint32_t mismatch_run;         /* mismatches in a row ending at the last judged frame; 0 after a judged frame that matched */
+    uint32_t swapped_frames;       /* mismatches whose channels match crosswise */
+    uint32_t last_flags;           /* TLB_COMPARE_* of the last slot */
+    uint32_t reserved_[2];         /* 0 */
+} tlb_compare_record;
+int tlb_compare_device(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_dec_pcm, const tlb_frame_report *d_report, int nframes,
+                       const tlb_compare_params *params, tlb_compare_record *d_record, void *hip_stream);
+int tlb_compare_host(tlb_batch *b, const int16_t *in_pcm, const int16_t *dec_pcm, const tlb_frame_report *report, int nframes,
+                     const tlb_compare_params *params, tlb_compare_record *record);
+int tlb_compare_reset(tlb_batch *b, int stream);
+int tlb_tick_enable_compare(tlb_tick *t, const tlb_compare_params *params);
+const tlb_compare_record *tlb_tick_compare(const tlb_tick *t);
+int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params);
+const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

@@ -13,5 +13,6 @@ from .toolame import (  # noqa: F401
     Batch, StreamConfig, ToolameError, LIB_PATH, build, load_library, lds_bytes_per_stream, legacy_api,
     EDI_STATE_DTYPE, edi_state_init, Tick, Node, node_partition, node_plan, load_fault_library, FAULT_LIB_PATH,
     FRAME_REPORT_DTYPE, FRAME_FIELDS_DTYPE, DEC_EMPTY, DEC_BAD_MASK, DEC_SCFCRC_UNCHECKED,
-    MONITOR_DTYPE,
+    MONITOR_DTYPE, COMPARE_DTYPE, COMPARE_PARAMS_DTYPE, COMPARE_DELAY, COMPARE_DEFAULTS, compare_params,
+    COMPARE_JUDGED0, COMPARE_JUDGED1, COMPARE_MISMATCH, COMPARE_SWAPPED, COMPARE_SKIPPED,
 )

@@ -1,5 +1,5 @@
 // tl_kernels.h -- the one door between the host translation units (tlb_batch.cpp, tlb_egress.cpp, tlb_tick.cpp: plain C++, seconds to
-// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip, toolame_monitor.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
+// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip, toolame_monitor.hip, toolame_compare.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
 // `st` and returns hipGetLastError(); grid shapes that depend on the kernels' wave counts are computed from the constants below.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -9,6 +9,7 @@
 #include "mp2_types.h"
 #include "edi_types.h"
 #include "mp2_dec_types.h"
+#include "mp2_compare.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -44,4 +45,7 @@ hipError_t tlk_underrun(unsigned blocks, hipStream_t st, const int32_t *valid, u
 // toolame_monitor.hip: tl_monitor_kernel, one wavefront per stream over the stream's slots in order (csrc/mp2_monitor.h); record uint32 [nstreams][8]
 hipError_t tlk_monitor(hipStream_t st, const TlFrameReport *report, const int16_t *pcm, uint32_t *record, const TlConfig *configs,
                        const int32_t *stream_cfg, int nstreams, int nframes);
+// toolame_compare.hip: tl_compare_kernel, one wavefront per stream over the stream's slots in order (csrc/mp2_compare.h); in / report may be NULL
+hipError_t tlk_compare(hipStream_t st, const int16_t *in, const int16_t *dec, const TlFrameReport *report, int16_t *hist, TlCompareRecord *record,
+                       const TlCompareParams &P, const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int nframes);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

@@ -56,6 +56,7 @@ void tlb_destroy(tlb_batch *b)
     if (b->d_dec_state) (void)hipFree(b->d_dec_state);
     if (b->d_dec_prev) (void)hipFree(b->d_dec_prev);
     if (b->d_dec_bad) (void)hipFree(b->d_dec_bad);
+    if (b->d_cmp_hist) (void)hipFree(b->d_cmp_hist);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_mid) (void)hipEventDestroy(b->ev_mid);
@@ -193,6 +194,7 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
     if (b->d_edi_state_tmp) HIPCHK(hipMemset(b->d_edi_state_tmp + s0, 0, sizeof(TlEdiState) * (size_t)n));
     if (b->d_pseq_tmp) HIPCHK(hipMemset(b->d_pseq_tmp + s0, 0, sizeof(uint16_t) * (size_t)n));
     if (b->d_dec_state) HIPCHK(hipMemset(b->d_dec_state + s0, 0, sizeof(TlDecStream) * (size_t)n));      // the decoder's next frame of these streams is a first frame
+    if (b->d_cmp_hist) HIPCHK(hipMemset(b->d_cmp_hist + (size_t)s0 * 2 * TL_CMP_HIST, 0, sizeof(int16_t) * 2 * TL_CMP_HIST * (size_t)n));      // ... and the compare monitor has no input to set their next frame against
     return TLB_OK;
 }
 

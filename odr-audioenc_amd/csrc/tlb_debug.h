@@ -14,6 +14,10 @@ int tlb_debug_tick_fail_next(tlb_tick *t, int nth);                /* ... the nt
  * encode and before the egress and the confidence monitor: the caller receives the damaged frame and the monitor sees the same bytes.  A
  * host-queued one-byte copy out and back in; it does not fault the device. */
 int tlb_debug_tick_damage_next(tlb_tick *t, int stream, int byte, int xor_mask, int nth);
+/* From the nth submit from now ON (1 = the next; 0 disarms; tlb_tick_finish included) the slots of streams a and b of one group are exchanged in
+ * the tick's device frame buffer, lengths too, after the encode and before the egress and the monitors, tick after tick: valid frames that
+ * carry the other stream's programme.  The caller receives the exchanged frames.  Device-to-device copies on the tick's own stream. */
+int tlb_debug_tick_cross_from(tlb_tick *t, int a, int b, int nth);
 int tlb_debug_node_fail_next(tlb_node *nd, int shard, int nth);    /* ... of one shard of a node */
 /* A stalled shard for the node's tick deadline: the nth wait job of that shard from now (1 = the next; 0 disarms), AFTER its
  * tlb_tick_wait has returned with the tick complete, sleeps `ms` on the shard's HOST thread and then returns `rc` (0: the tick's results

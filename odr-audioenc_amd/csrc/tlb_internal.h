@@ -70,6 +70,7 @@ struct tlb_batch {
     TlDecStream *d_dec_state = nullptr;          // [nstreams]
     uint8_t *d_dec_prev = nullptr;               // [nstreams][out_stride] the last slot of the call before
     unsigned long long *d_dec_bad = nullptr;     // frames with a TL_DEC_BAD_MASK flag since creation
+    int16_t *d_cmp_hist = nullptr;               // compare monitor (tlb_compare.cpp): [nstreams][2][TL_CMP_HIST] the input the next decoded frame is set against, allocated by the first compare call
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
 };
 
@@ -99,4 +100,9 @@ int edi_af_device(tlb_batch *b, const uint8_t *d_frames, const int16_t *d_levels
                   const char *version, int version_len, uint8_t *d_pkts, int32_t *d_pkt_len, void *hip_stream, const int32_t *d_frame_len);
 // tlb_decode.cpp: the decoder's tables and per-stream state, as the first decode call makes them (it waits for the device once)
 int decode_prepare(tlb_batch *b);
+// tlb_compare.cpp: the history as the first compare call makes it; the launch itself with a report that may be NULL (every slot skipped:
+// a tick that has no frames yet still advances the history)
+int compare_prepare(tlb_batch *b);
+int compare_launch(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_dec_pcm, const tlb_frame_report *d_report, int nframes,
+                   const tlb_compare_params *params, tlb_compare_record *d_record, void *hip_stream);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -153,6 +153,8 @@ struct tlb_node {
     double deadline_ms = 0;                      // TICK DEADLINE; 0 = none
     bool short_reads = false;                    // tlb_node_enable_short_reads(): every shard's tick object carries `valid` and the underrun counters (a restarted shard's too)
     int monitor = 0;                             // tlb_node_enable_monitor(): TLB_MONITOR_* of every shard's tick object (a restarted shard's too)
+    bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
+    tlb_compare_params cparams = {};
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
@@ -283,6 +285,7 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (!s.tick) return e ? e : TLB_ERR_HIP;
         if (nd->short_reads) if (int rc = tlb_tick_enable_short_reads(s.tick)) return rc;
         if (nd->monitor) if (int rc = tlb_tick_enable_monitor(s.tick, nd->monitor)) return rc;
+        if (nd->compare) if (int rc = tlb_tick_enable_compare(s.tick, &nd->cparams)) return rc;
         if (nd->monitor && nd->listen >= s.first && nd->listen < s.first + s.n) if (int rc = tlb_tick_monitor_listen(s.tick, nd->listen - s.first)) return rc;
     } else {
         s.batch = tlb_create(s.device, s.n, nd->cfgs.data() + s.first, &e);
@@ -560,6 +563,23 @@ const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream)
 {
     int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
     const tlb_monitor_record *p = s && s->tick ? tlb_tick_monitor(s->tick) : nullptr;
+    return p ? p + k : nullptr;
+}
+// The compare monitor (tlb_tick_enable_compare of every shard): after tlb_node_enable_monitor(TLB_MONITOR_AUDIO), before the first submit.
+int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params)
+{
+    if (!nd || !params || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0 || nd->monitor != TLB_MONITOR_AUDIO) return TLB_ERR_ARG;
+    if (params->min_energy < 1 || params->corr_num <= 0 || params->corr_num > params->corr_den || params->corr_den > 1024) return TLB_ERR_ARG;
+    if (nd->compare) return params->min_energy == nd->cparams.min_energy && params->corr_num == nd->cparams.corr_num && params->corr_den == nd->cparams.corr_den ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    const tlb_compare_params P = *params;
+    const int rc = nd->all([P](Shard &s) { return s.tick ? tlb_tick_enable_compare(s.tick, &P) : (int)TLB_ERR_HIP; });
+    if (!rc) { nd->cparams = P; nd->compare = true; }
+    return rc;
+}
+const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    const tlb_compare_record *p = s && s->tick ? tlb_tick_compare(s->tick) : nullptr;
     return p ? p + k : nullptr;
 }
 // One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'

@@ -30,7 +30,8 @@ struct TickGroup {
     uint8_t *h_msgs[3] = {};
     // confidence monitor (tlb_tick_enable_monitor): the decode call's reports (and PCM under AUDIO) of this tick's frames, the folded records
     tlb_frame_report *d_report = nullptr; int16_t *d_mpcm = nullptr; tlb_monitor_record *d_record = nullptr;
-    hipEvent_t ev_mon = nullptr;                                // decode + fold done: the records' copy-out waits for it, the packets' does not
+    tlb_compare_record *d_crecord = nullptr;                    // compare monitor (tlb_tick_enable_compare): the group's records
+    hipEvent_t ev_mon = nullptr;                                // decode + fold (+ compare) done: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
                                                                                 // ingest (d_inter) / encode (X-PAD), its kernels for this tick's copy-out
@@ -55,8 +56,13 @@ struct tlb_tick {
     tlb_monitor_record *h_record[3] = {}; int16_t *h_listen[3] = {};
     int listen = -1;                             // the stream the NEXT submit carries (tlb_tick_monitor_listen); -1: none
     int listen_of[3] = {-1, -1, -1};             // ... the tick of each output set carried
+    // compare monitor, off until tlb_tick_enable_compare(): needs the AUDIO monitor's decoded PCM; its records travel with the output sets too
+    bool compare = false;
+    tlb_compare_params cparams = {};
+    tlb_compare_record *h_crecord[3] = {};
 #ifdef TLB_FAULT_INJECT
     int damage_nth = 0, damage_stream = 0, damage_byte = 0; uint8_t damage_xor = 0, damage_val = 0;      // tlb_debug_tick_damage_next
+    int cross_nth = 0, cross_a = -1, cross_b = -1; bool cross_on = false; uint8_t *d_cross_tmp = nullptr;   // tlb_debug_tick_cross_from
 #endif
     int in_set = 0, out_set = 0;
     long waited = 0;                             // ticks whose results have been waited for (ticks: submitted)
@@ -70,6 +76,9 @@ struct tlb_tick {
 };
 // a failing submit / wait / finish: drain what was queued, mark the object, hand the code on
 static int tick_fail(tlb_tick *t, int rc);
+#ifdef TLB_FAULT_INJECT
+static int tick_cross(tlb_tick *t, TickGroup &G);
+#endif
 
 extern "C" {
 
@@ -276,6 +285,37 @@ int tlb_tick_enable_monitor(tlb_tick *t, int what)
     return TLB_OK;
 }
 const tlb_monitor_record *tlb_tick_monitor(const tlb_tick *t) { return t && t->monitor ? t->h_record[t->out_set] : nullptr; }
+// The compare monitor on top of it: the tick's planar PCM (d_pcm, what the encoder is given) against the decoded PCM of the frame that
+// leaves in the same tick (d_mpcm), through the history of the group's batch -- made here, not by the first tick.  Opt-in like the rest.
+int tlb_tick_enable_compare(tlb_tick *t, const tlb_compare_params *params)
+{
+    if (!t || !params || t->finished || t->ticks > 0 || t->monitor != TLB_MONITOR_AUDIO) return TLB_ERR_ARG;
+    if (params->min_energy < 1 || params->corr_num <= 0 || params->corr_num > params->corr_den || params->corr_den > 1024) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (t->compare) return params->min_energy == t->cparams.min_energy && params->corr_num == t->cparams.corr_num && params->corr_den == t->cparams.corr_den ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(t->device));
+    const size_t ns = (size_t)t->nstreams;
+    for (int k = 0; k < 3; k++) {
+        void *p = nullptr;
+        if (hipHostMalloc(&p, ns * sizeof(tlb_compare_record), hipHostMallocDefault) != hipSuccess) return TLB_ERR_HIP;
+        memset(p, 0, ns * sizeof(tlb_compare_record));
+        t->pinned.push_back(p);
+        t->h_crecord[k] = (tlb_compare_record *)p;
+    }
+    for (auto &G : t->groups) {
+        if (int rc = compare_prepare(G.b)) return rc;
+        void *p = nullptr;
+        HIPCHK(hipMalloc(&p, (size_t)G.n * sizeof(tlb_compare_record)));
+        t->dev.push_back(p);
+        HIPCHK(hipMemset(p, 0, (size_t)G.n * sizeof(tlb_compare_record)));
+        G.d_crecord = (tlb_compare_record *)p;
+    }
+    HIPCHK(hipDeviceSynchronize());                                  // the memsets ran on the null stream, the tick's streams do not wait for it
+    t->cparams = *params;
+    t->compare = true;
+    return TLB_OK;
+}
+const tlb_compare_record *tlb_tick_compare(const tlb_tick *t) { return t && t->compare ? t->h_crecord[t->out_set] : nullptr; }
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)
 {
     if (!t || t->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
@@ -336,6 +376,9 @@ int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config
 static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, bool new_input = true)
 {
     const size_t n = (size_t)G.n, slots = n * (size_t)G.max_upf;
+#ifdef TLB_FAULT_INJECT
+    if (have_frames && t->cross_on && t->cross_a >= G.first && t->cross_a < G.first + G.n) if (int rc = tick_cross(t, G)) return rc;
+#endif
     if (new_input) if (int rc = tlb_silence_device(G.b, G.d_peaks, 1, G.d_silence, t->s_run)) return rc;       // odr-audioenc.cpp:1053-1079 (the decision stays with the caller)
     if (have_frames && t->egress == TLB_TICK_ZMQ) {
         if (int rc = zmq_frame_device(G.b, G.d_frames, G.d_peaks, 1, G.d_msgs, t->s_run, G.d_flen)) return rc;
@@ -349,6 +392,11 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
     if (t->monitor && have_frames) {                                 // behind the egress kernels: the packets' copy-out waits for ev_run only
         if (int rc = tlb_decode_device(G.b, G.d_frames, G.d_flen, 1, G.d_report, nullptr, G.d_mpcm, t->s_run)) return rc;
         if (int rc = tlb_monitor_device(G.b, G.d_report, G.d_mpcm, 1, G.d_record, t->s_run)) return rc;
+        if (!t->compare) HIPCHK(hipEventRecord(G.ev_mon, t->s_run));
+    }
+    if (t->compare) {                                                // behind the decode: this tick's input against the frame that leaves with it.  The first
+        // tick has no frame yet (no report: the slot counts as skipped) and only advances the history; the flush has no input and does not advance it
+        if (int rc = compare_launch(G.b, new_input ? G.d_pcm : nullptr, G.d_mpcm, have_frames ? G.d_report : nullptr, 1, &t->cparams, G.d_crecord, t->s_run)) return rc;
         HIPCHK(hipEventRecord(G.ev_mon, t->s_run));
     }
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
@@ -374,8 +422,9 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
         }
     }
     if (t->monitor) {                                                // the records (and the listened stream's frame) behind the packets
-        if (have_frames) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_mon, 0));
+        if (have_frames || t->compare) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_mon, 0));
         HIPCHK(hipMemcpyAsync(t->h_record[set] + G.first, G.d_record, n * sizeof(tlb_monitor_record), hipMemcpyDeviceToHost, t->s_out));
+        if (t->compare) HIPCHK(hipMemcpyAsync(t->h_crecord[set] + G.first, G.d_crecord, n * sizeof(tlb_compare_record), hipMemcpyDeviceToHost, t->s_out));
         const int k = t->listen_of[set] - G.first;
         if (G.d_mpcm && k >= 0 && k < G.n)
             HIPCHK(hipMemcpyAsync(t->h_listen[set], G.d_mpcm + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME, 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost, t->s_out));
@@ -402,6 +451,37 @@ int tlb_debug_tick_damage_next(tlb_tick *t, int stream, int byte, int xor_mask, 
 {
     if (!t || nth < 0 || stream < 0 || stream >= t->nstreams || byte < 0 || byte >= t->groups[(size_t)t->group_of[(size_t)stream]].out_stride) return TLB_ERR_ARG;
     t->damage_nth = nth; t->damage_stream = stream; t->damage_byte = byte; t->damage_xor = (uint8_t)xor_mask;
+    return TLB_OK;
+}
+// ... from the nth submit from now ON (tlb_tick_finish included) the slots of streams a and b in d_frames / d_flen are exchanged between the
+// encode and the egress, tick after tick: the indexing fault of a batched encoder -- stream a's slot holds stream b's programme, in frames
+// that are valid in every respect.  Both streams must lie in one group.  Device-to-device copies queued on s_run; nothing faults.
+int tlb_debug_tick_cross_from(tlb_tick *t, int a, int b, int nth)
+{
+    if (!t || nth < 0 || a < 0 || b < 0 || a >= t->nstreams || b >= t->nstreams || a == b || t->group_of[(size_t)a] != t->group_of[(size_t)b]) return TLB_ERR_ARG;
+    if (!t->d_cross_tmp) {
+        HIPCHK(hipSetDevice(t->device));
+        void *p = nullptr;
+        size_t widest = 0;                                           // one buffer for every later call: any group's slot fits
+        for (auto &G : t->groups) if ((size_t)G.out_stride > widest) widest = (size_t)G.out_stride;
+        HIPCHK(hipMalloc(&p, widest + 16));
+        t->dev.push_back(p);
+        t->d_cross_tmp = (uint8_t *)p;
+    }
+    t->cross_nth = nth; t->cross_a = a; t->cross_b = b; t->cross_on = false;
+    return TLB_OK;
+}
+static int tick_cross(tlb_tick *t, TickGroup &G)
+{
+    const size_t n = (size_t)G.out_stride;
+    uint8_t *fa = G.d_frames + (size_t)(t->cross_a - G.first) * n, *fb = G.d_frames + (size_t)(t->cross_b - G.first) * n;
+    int32_t *la = G.d_flen + (t->cross_a - G.first), *lb = G.d_flen + (t->cross_b - G.first);
+    HIPCHK(hipMemcpyAsync(t->d_cross_tmp, fa, n, hipMemcpyDeviceToDevice, t->s_run));
+    HIPCHK(hipMemcpyAsync(fa, fb, n, hipMemcpyDeviceToDevice, t->s_run));
+    HIPCHK(hipMemcpyAsync(fb, t->d_cross_tmp, n, hipMemcpyDeviceToDevice, t->s_run));
+    HIPCHK(hipMemcpyAsync(t->d_cross_tmp + n, la, 4, hipMemcpyDeviceToDevice, t->s_run));
+    HIPCHK(hipMemcpyAsync(la, lb, 4, hipMemcpyDeviceToDevice, t->s_run));
+    HIPCHK(hipMemcpyAsync(lb, t->d_cross_tmp + n, 4, hipMemcpyDeviceToDevice, t->s_run));
     return TLB_OK;
 }
 static int tick_damage(tlb_tick *t, TickGroup &G)
@@ -433,6 +513,7 @@ int tlb_tick_submit(tlb_tick *t)
     t->listen_of[oset] = t->monitor == TLB_MONITOR_AUDIO && t->ticks > 0 ? t->listen : -1;
 #ifdef TLB_FAULT_INJECT
     const bool damage = t->damage_nth > 0 && --t->damage_nth == 0;
+    if (t->cross_nth > 0 && --t->cross_nth == 0) t->cross_on = true;
 #endif
     for (auto &G : t->groups) {
         const size_t n = (size_t)G.n;

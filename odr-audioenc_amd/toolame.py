@@ -74,6 +74,8 @@ def load_fault_library():
         L.tlb_debug_tick_fail_next.argtypes = [C.c_void_p, C.c_int]
         L.tlb_debug_node_fail_next.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.tlb_debug_tick_damage_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "tlb_debug_tick_cross_from"):
+            L.tlb_debug_tick_cross_from.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.tlb_debug_node_stall_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         _fault_lib = L
     return _fault_lib
@@ -241,6 +243,16 @@ def _bind(L):
         L.tlb_node_monitor_listen.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_monitor_pcm.restype = C.c_void_p
         L.tlb_node_monitor_pcm.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    if hasattr(L, "tlb_compare_device"):          # compare monitor
+        L.tlb_compare_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_compare_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_compare_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_tick_enable_compare.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_tick_compare.restype = C.c_void_p
+        L.tlb_tick_compare.argtypes = [C.c_void_p]
+        L.tlb_node_enable_compare.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_node_compare.restype = C.c_void_p
+        L.tlb_node_compare.argtypes = [C.c_void_p, C.c_int]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -302,6 +314,25 @@ DEC_BAD_MASK = DEC_BAD_SYNC | DEC_HEADER_MISMATCH | DEC_BAD_CRC16 | DEC_BAD_SCFC
 MONITOR_DTYPE = np.dtype([("frames", np.uint32), ("bad_frames", np.uint32), ("bad_run", np.uint32), ("flags_seen", np.uint32),
                           ("last_status", np.uint32), ("out_silence_ms", np.uint32), ("out_peak", np.int16, (2,)), ("reserved_", np.uint32)])
 MONITOR_WHAT = {"check": 1, "audio": 2}         # TLB_MONITOR_CHECK / TLB_MONITOR_AUDIO
+# tlb_compare_record / tlb_compare_params (include/toolame_batch.h): the compare monitor, one record per stream
+COMPARE_DTYPE = np.dtype([("sxx", np.int64, (2,)), ("syy", np.int64, (2,)), ("sxy", np.int64, (2,)), ("sxz", np.int64, (2,)),
+                          ("frames_compared", np.uint32), ("frames_judged", np.uint32), ("mismatch_frames", np.uint32), ("mismatch_run", np.uint32),
+                          ("swapped_frames", np.uint32), ("last_flags", np.uint32), ("reserved_", np.uint32, (2,))])
+COMPARE_PARAMS_DTYPE = np.dtype([("min_energy", np.int64), ("corr_num", np.int32), ("corr_den", np.int32)])
+COMPARE_DELAY = 481                             # TLB_COMPARE_DELAY
+COMPARE_JUDGED0, COMPARE_JUDGED1, COMPARE_MISMATCH, COMPARE_SWAPPED, COMPARE_SKIPPED = (1 << i for i in range(5))
+COMPARE_DEFAULTS = (1152 * 256 * 256, 3, 8)     # TLB_COMPARE_DEFAULT_MIN_ENERGY / _CORR_NUM / _CORR_DEN
+
+
+def compare_params(params=None):
+    """(min_energy, corr_num, corr_den), a dict with those keys, or None for the header's defaults -> COMPARE_PARAMS_DTYPE [1]"""
+    if params is None:
+        params = COMPARE_DEFAULTS
+    if isinstance(params, dict):
+        params = (params["min_energy"], params["corr_num"], params["corr_den"])
+    out = np.zeros(1, dtype=COMPARE_PARAMS_DTYPE)
+    out[0] = tuple(int(v) for v in params)
+    return out
 
 
 def _config_array(configs):
@@ -408,6 +439,21 @@ class Tick:
             return None
         return np.frombuffer((C.c_uint8 * (self.nstreams * MONITOR_DTYPE.itemsize)).from_address(p), dtype=MONITOR_DTYPE)
 
+    # -- compare monitor (tlb_compare_device behind the decode): after enable_monitor("audio"), before the first submit --
+    def enable_compare(self, params=None):
+        """params: (min_energy, corr_num, corr_den) or None for the defaults"""
+        rc = self.L.tlb_tick_enable_compare(self.h, compare_params(params).ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_compare")
+
+    @property
+    def compare(self):
+        """COMPARE_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when not enabled"""
+        p = self.L.tlb_tick_compare(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * COMPARE_DTYPE.itemsize)).from_address(p), dtype=COMPARE_DTYPE)
+
     def monitor_listen(self, s):
         """select ONE stream (-1: none) whose decoded frame comes back with every tick from the next submit on ("audio" only)"""
         rc = self.L.tlb_tick_monitor_listen(self.h, int(s))
@@ -427,6 +473,12 @@ class Tick:
         rc = self.L.tlb_debug_tick_damage_next(self.h, stream, byte, xor_mask, nth)
         if rc:
             raise ToolameError(rc, "tlb_debug_tick_damage_next")
+
+    def cross_from(self, a, b, nth=1):
+        """fault-injection TEST build only: from the nth submit from now on the frames of streams a and b (one group) leave in each other's slots"""
+        rc = self.L.tlb_debug_tick_cross_from(self.h, a, b, nth)
+        if rc:
+            raise ToolameError(rc, "tlb_debug_tick_cross_from")
 
     def submit(self):
         """queue one tick on the input set just filled and return at once; `pcm` then shows the other input set"""
@@ -672,6 +724,33 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_monitor_host")
         return record
+
+    def compare(self, in_pcm, dec_pcm, report, params=None, record=None):
+        """tlb_compare_host: the encoder's input in_pcm int16 [nframes, nstreams, 2, 1152] (None: the flush, one slot, the history does not
+        advance) against the decoded dec_pcm of the same call's output slots and their reports, into record COMPARE_DTYPE [nstreams] --
+        advanced in place when given, else a fresh all-zero one -- which is returned.  params: (min_energy, corr_num, corr_den) or None"""
+        rep = np.ascontiguousarray(report, dtype=FRAME_REPORT_DTYPE)
+        if rep.ndim != 2 or rep.shape[1] != self.nstreams:
+            raise ToolameError(18, f"report shape {rep.shape}")
+        nf = rep.shape[0]
+        dec = np.ascontiguousarray(dec_pcm, dtype=np.int16)
+        inp = None if in_pcm is None else np.ascontiguousarray(in_pcm, dtype=np.int16)
+        if dec.shape != (nf, self.nstreams, 2, SAMPLES) or (inp is not None and inp.shape != dec.shape):
+            raise ToolameError(18, f"pcm shape {dec.shape}")
+        if record is None:
+            record = np.zeros(self.nstreams, dtype=COMPARE_DTYPE)
+        if record.dtype != COMPARE_DTYPE or record.shape != (self.nstreams,) or not record.flags.c_contiguous:
+            raise ToolameError(18, "record: COMPARE_DTYPE [nstreams]")
+        rc = self.L.tlb_compare_host(self.h, inp.ctypes.data if inp is not None else None, dec.ctypes.data, rep.ctypes.data, nf,
+                                     compare_params(params).ctypes.data, record.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_compare_host")
+        return record
+
+    def compare_reset(self, stream=-1):
+        rc = self.L.tlb_compare_reset(self.h, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_compare_reset")
 
     def decode_device(self, d_frames_ptr, d_len_ptr, nframes, d_report_ptr, d_fields_ptr=None, d_pcm_ptr=None, stream=None):
         rc = self.L.tlb_decode_device(self.h, d_frames_ptr, d_len_ptr, nframes, d_report_ptr, d_fields_ptr, d_pcm_ptr, stream)
@@ -1059,6 +1138,17 @@ class Node:
         if not p:
             return None
         return np.frombuffer((C.c_uint8 * MONITOR_DTYPE.itemsize).from_address(p), dtype=MONITOR_DTYPE)[0].copy()
+
+    # compare monitor (Tick.enable_compare, per stream with node-wide indices)
+    def enable_compare(self, params=None):
+        self._rc(self.L.tlb_node_enable_compare(self.h, compare_params(params).ctypes.data), "tlb_node_enable_compare")
+
+    def compare(self, s):
+        """the stream's record (a COMPARE_DTYPE scalar, copied) of the step waited for last; None when not enabled and for a broken, late or stale shard"""
+        p = self.L.tlb_node_compare(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * COMPARE_DTYPE.itemsize).from_address(p), dtype=COMPARE_DTYPE)[0].copy()
 
     def monitor_listen(self, s):
         self._rc(self.L.tlb_node_monitor_listen(self.h, int(s)), "tlb_node_monitor_listen")
