@@ -7,7 +7,10 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]
+//   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
+//   encoder's rate on the device (tlb_tick_set_source): each tick reads tlb_tick_need() source frames per stream, not 1152.  Not together
+//   with --short-every.
 //   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth stream delivers M sample
 //   frames fewer than 1152; the library stretches what came over the frame as the reference does and counts the underruns.
 //   --monitor check|audio: the confidence monitor (tlb_tick_enable_monitor): every frame that leaves is checked on the device (audio: also
@@ -36,10 +39,10 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]\n", argv[0]);
         return 2;
     }
-    long rate = 48000;
+    long rate = 48000, source_rate = 0;
     long long now_s = 1700000000;
     int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     char mode = 0;
@@ -59,6 +62,7 @@ int main(int argc, char **argv)
         else if (k == "-t") now_s = std::atoll(v);
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
+        else if (k == "--source-rate") source_rate = std::atol(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -86,10 +90,11 @@ int main(int argc, char **argv)
     if (gain_db != 0.0 && tlb_tick_set_gain_db(t, -1, gain_db)) die("gain", 0);
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
+    if (source_rate) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
-    const size_t per_frame = 1152 * (size_t)channels;        // samples of one frame in the file
+    size_t per_frame = 1152 * (size_t)channels;              // samples of one frame in the file
     std::vector<int16_t> frame(per_frame);
     long frames = 0, packets = 0;
     int alarms = 0;                                              // compare monitor: times a stream's mismatch_run reached 3
@@ -115,7 +120,9 @@ int main(int argc, char **argv)
                     alarms++;
                 }
     };
-    while (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) == per_frame) {
+    for (;;) {
+        if (source_rate) per_frame = (size_t)tlb_tick_need(t, 0) * (size_t)channels;      // 1058 or 1059 frames at 44.1 kHz, 768 at 32 kHz: every stream is fed the one file, so all need the same
+        if (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) != per_frame) break;
         int16_t *in = tlb_tick_pcm(t);                       // pinned [nstreams][2304]; mono streams use the first 1152 values
         for (int s = 0; s < nstreams; s++) std::memcpy(in + (size_t)s * 2304, frame.data(), per_frame * sizeof(int16_t));
         if (short_every && frames % short_every == 0) {          // every set comes back all 1152: only the short streams are written

@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M] [--monitor check|audio] [--compare]
+//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]
 //   in.s16le: interleaved stereo 48 kHz; stream s starts reading at frame s (so the services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
 //   -o: the AF packets of the LAST stream of the node, length-prefixed (uint32 LE) -- the stream farthest from shard 0.
@@ -22,6 +22,8 @@
 //   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
 //   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
+//   --source-rate R: in.s16le is at R Hz (44100 or 32000) and is resampled to 48 kHz on the GPUs (tlb_node_set_source): service s starts
+//   reading at source frame 1152 s and takes tlb_node_need() consecutive frames every tick, wrapping around.  Not together with --short-every.
 //   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
 //   frame that leaves is decoded on its GPU and set against the audio that went in.  A service whose mismatch_run reaches 3 is printed when
 //   it does; one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any service got there.
@@ -49,6 +51,8 @@ struct Ctx {
     std::vector<uint64_t> *hash;                             // per shard: FNV-1a over every packet byte shipped
     std::vector<long> *packets, *bytes;
     int short_every, short_by;                               // 0: every read is full
+    long source_rate;                                        // 0: the file is at the encoder's rate
+    std::vector<size_t> *spos;                               // --source-rate: the next source frame of every service
 };
 
 // step 1 on shard `g`'s thread: the block's services copy their frame of this tick into the pinned input set
@@ -60,6 +64,14 @@ static void fill(void *vctx, int g, int first, int n)
         if (!dst) {                                              // a BROKEN or LATE shard takes no input (its block is off air until it is back); anything else is a bug
             if (tlb_node_shard_status(c.nd, g, nullptr) != TLB_SHARD_OK) return;
             die("no input set free", s);
+        }
+        if (c.source_rate) {                                     // need source frames from where the service stands, around the end of the file
+            const int need = tlb_node_need(c.nd, s);
+            if (need < 0) die("tlb_node_need", -need);
+            const size_t total = c.pcm->size() / 2;
+            size_t &at = (*c.spos)[(size_t)s];
+            for (int i = 0; i < need; i++, at = (at + 1) % total) std::memcpy(dst + 2 * i, c.pcm->data() + 2 * at, 2 * sizeof(int16_t));
+            continue;
         }
         const size_t f = ((size_t)s + (size_t)c.tick) % c.nframes_in;
         std::memcpy(dst, c.pcm->data() + f * 2304, 2304 * sizeof(int16_t));
@@ -89,11 +101,12 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]\n", argv[0]);
         return 2;
     }
     int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     double deadline_ms = 0;
+    long source_rate = 0;
     std::string devs, outpath;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
@@ -110,6 +123,7 @@ int main(int argc, char **argv)
         else if (k == "--deadline-ms") { deadline_ms = std::atof(v); if (!(deadline_ms > 0)) die("--deadline-ms wants a positive number", 0); }
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
+        else if (k == "--source-rate") source_rate = std::atol(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -162,13 +176,17 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
     if (monitor)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
+    if (source_rate)
+        if (int rc = tlb_node_set_source(nd, -1, source_rate)) die("tlb_node_set_source", rc);          // between steps; a restarted shard's sources are set again
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare)
         if (int rc = tlb_node_enable_compare(nd, &cparams)) die("tlb_node_enable_compare", rc);         // after the audio monitor, before the first submit
 
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by};
+    std::vector<size_t> spos((size_t)nstreams);
+    for (int s = 0; s < nstreams; s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, &spos};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick

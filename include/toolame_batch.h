@@ -733,6 +733,76 @@ const tlb_compare_record *tlb_tick_compare(const tlb_tick *t);
 int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params);
 const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Resample: 44.1 and 32 kHz sources (and their halves) to the encoder's rate, on the device, ahead of the ingest.
+ * Every entry point above takes PCM at tlb_stream_config.samplerate.  The reference's users never see that: its inputs convert before the
+ * samples reach AudioEnc::run() (src/VLCInput.cpp:208, `samplerate=` in the transcode chain; src/GSTInput.cpp:124-133, an audioresample
+ * element).  The reference has no resampler of its own to be bit-exact against, so this section DEFINES one, in integers.
+ *   source rate -> encoder rate     ratio L/M
+ *   44100 -> 48000, 22050 -> 24000  160/147
+ *   32000 -> 48000, 16000 -> 24000  3/2
+ * Any other pair is TLB_ERR_SAMPLERATE.  Downsampling (48 -> 24 kHz: twice the PCM on the host-to-device link, which is the limit) and
+ * 48 -> 44.1 kHz are out of scope.
+ * THE TAPS.  One table per ratio, int16 H[L][T], T = TLB_RESAMPLE_TAPS = 32, committed as csrc/tl_resample_taps.inc: the committed table is
+ * the definition, tools/gen_resample_taps.py the record of how it was made (N = L T; c = k - (N - 1) / 2; fc = 0.95 * 0.5 / L;
+ * h[k] = L 2 fc sinc(2 fc c) kaiser(N, 8)[k]; row p = h[p::L] scaled to sum 32768, rounded half up, the remainder added to the row's tap of
+ * largest magnitude).  Every row sums to exactly 32768; tlb_resample_taps() hands the table out.
+ * THE FORMULA.  For a stream, count output samples n and source frames from the stream's last reset; a source frame is an L/R pair, or one
+ * sample of a one-channel stream.  With q(n) = floor(n M / L) and p(n) = (n M) mod L:
+ *   acc(n) = sum over t = 0..T-1 of H[p(n)][t] * x[q(n) - t]      (x[j] = 0 for j < 0; the exact integer sum)
+ *   y(n)   = clamp((acc(n) + 16384) >> 15, -32768, 32767)         (arithmetic shift, i.e. floor)
+ * per channel, both channels with the same q and p.  Frame f of the stream is y(1152 f .. 1152 f + 1151); it consumes the source frames
+ * up to q(1152 (f + 1) - 1):
+ *   need(f) = q(1152 (f + 1) - 1) + 1 - (f > 0 ? q(1152 f - 1) + 1 : 0)
+ * 160/147: 1058 or 1059 in a cycle of five frames that add up to 5292; 3/2: always 768.  Never above 1152: a slot of 2304 values holds it.
+ * BUFFERS.  d_source and d_interleaved are both int16 [nframes][nstreams][2304] and must not overlap (TLB_ERR_ARG), 16-byte aligned.  The
+ * slot of a resampled stream holds the need source frames of that frame at its start (interleaved L R for two channels); nothing behind them
+ * is read.  The output slot is what tlb_ingest_device / _valid take: 1152 sample frames at the encoder's rate.  A stream without a source has
+ * its slot copied as it is: 2304 values, or the first 1152 of a one-channel stream (behind a one-channel stream's 1152 values nothing is written).
+ * The (frame, stream) slots of a call are independent units: slot f takes its T - 1 frames of history from the tail of slot f - 1's source
+ * frames in the same buffer, the call's first slot from the stream's state record, the last slot writes the record, and a slot's phase
+ * follows from the stream's frame counter plus f: the output does not depend on how a stream's frames are cut into calls.
+ * STATE per stream: T - 1 source frames and the frame position within the need cycle, on the device, allocated by the first
+ * tlb_resample_set_source of a batch -- a batch that never sets a source allocates nothing and makes the device calls it made before.  The host
+ * keeps its own copy of the position (advanced per call, cleared by the resets): tlb_resample_need never touches the device.
+ *   tlb_resample_set_source(b, stream, rate)  stream = -1: every stream; rate 0 or the stream's own encoder rate: off.  Waits for the queued
+ *                                 launches and zeroes the resampler state of the streams it names; the encoder is left alone.  An illegal
+ *                                 pair for any named stream: TLB_ERR_SAMPLERATE, nothing changed.
+ *   tlb_resample_source           the stream's source rate; 0: off
+ *   tlb_resample_need(b, s, ahead) source frames the stream's (ahead)-th next frame consumes (ahead = 0: the next one); 1152 for a stream
+ *                                 without a source; < 0: -TLB_ERR_ARG
+ *   tlb_resample_need_at          need(frame) from the rates alone, no batch, no GPU; < 0: -TLB_ERR_*
+ *   tlb_resample_taps             the committed table [L][T] and its L, M, T (each may be NULL); NULL: no such pair
+ * tlb_reset, tlb_stream_reset and tlb_stream_finish zero the resampler state of the streams they touch.  tlb_stream_reconfigure keeps the
+ * source rate when the new encoder rate still forms a legal pair with it; otherwise it refuses with TLB_ERR_SAMPLERATE and changes nothing.
+ * Asynchronous on `hip_stream`; calls of one batch must be ordered on one stream, like the encode calls.
+ * TICK PLANE.  tlb_tick_set_source(t, stream, rate) is legal while no tick is in flight (TLB_ERR_ARG otherwise).  While at least one stream
+ * has a source (when the last one is turned off again the object is back to what it queued before; its extra buffer stays), every submit queues the resampler on the group's run stream behind the copy-in and ahead of the ingest, into one more device buffer
+ * per group; an object that never sets one queues exactly what it queued before.  The copy-in still moves whole slots.  tlb_tick_need(t,
+ * stream) is the number of source frames the stream's slot in the CURRENT input set (tlb_tick_pcm) must hold for the next submit; it follows
+ * the host copy of the position, advanced at submit and reset by tlb_tick_stream_reset / _finish / _reconfigure; < 0: -TLB_ERR_ARG.
+ * SHORT READS and a source on the same tick or node object are refused (TLB_ERR_ARG), from either side and in either order: the stretch
+ * counts encoder-rate frames, and a source that delivers too few frames would need a second convention.  At the batch level the two compose
+ * by the caller's own ordering.
+ * NODE LEVEL.  tlb_node_set_source routes to the owning shard (stream = -1: every stream; between steps only; every pair is checked before a
+ * shard is changed, and after a device failure half way the shards already changed get back the sources they had) and is remembered:
+ * tlb_node_shard_restart sets the block's sources again, with fresh state (its streams start at need(0)).  tlb_node_need is the TICK plane's;
+ * a BATCH-plane node refuses it (-TLB_ERR_ARG): there the caller goes through tlb_node_batch() and tlb_resample_need.  A stream of a broken
+ * or late shard answers -TLB_ERR_HIP / -TLB_ERR_LATE.
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_RESAMPLE_TAPS 32
+int tlb_resample_set_source(tlb_batch *b, int stream, long source_rate);
+long tlb_resample_source(const tlb_batch *b, int stream);
+int tlb_resample_need(const tlb_batch *b, int stream, int ahead);
+int tlb_resample_need_at(long source_rate, long encoder_rate, long frame);
+const int16_t *tlb_resample_taps(long source_rate, long encoder_rate, int *L, int *M, int *T);
+int tlb_resample_device(tlb_batch *b, const int16_t *d_source, int nframes, int16_t *d_interleaved, void *hip_stream);
+int tlb_resample_host(tlb_batch *b, const int16_t *source, int nframes, int16_t *interleaved);
+int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate);
+int tlb_tick_need(const tlb_tick *t, int stream);
+int tlb_node_set_source(tlb_node *nd, int stream, long source_rate);
+int tlb_node_need(const tlb_node *nd, int stream);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

@@ -1,5 +1,5 @@
 // tl_kernels.h -- the one door between the host translation units (tlb_batch.cpp, tlb_egress.cpp, tlb_tick.cpp: plain C++, seconds to
-// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip, toolame_monitor.hip, toolame_compare.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
+// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip, toolame_monitor.hip, toolame_compare.hip, toolame_resample.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
 // `st` and returns hipGetLastError(); grid shapes that depend on the kernels' wave counts are computed from the constants below.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -10,6 +10,7 @@
 #include "edi_types.h"
 #include "mp2_dec_types.h"
 #include "mp2_compare.h"
+#include "mp2_resample.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -48,4 +49,8 @@ hipError_t tlk_monitor(hipStream_t st, const TlFrameReport *report, const int16_
 // toolame_compare.hip: tl_compare_kernel, one wavefront per stream over the stream's slots in order (csrc/mp2_compare.h); in / report may be NULL
 hipError_t tlk_compare(hipStream_t st, const int16_t *in, const int16_t *dec, const TlFrameReport *report, int16_t *hist, TlCompareRecord *record,
                        const TlCompareParams &P, const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int nframes);
+// toolame_resample.hip: tl_resample_kernel, one workgroup per (frame, stream) slot (csrc/mp2_resample.h); state uint32 [2][nstreams][32] and ratio
+// int32 [nstreams] may both be NULL (no stream has a source: every slot is copied)
+hipError_t tlk_resample(unsigned blocks, hipStream_t st, const int16_t *source, int16_t *out, uint32_t *state, const int32_t *ratio, const int16_t *taps,
+                        const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int nframes, int flip);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

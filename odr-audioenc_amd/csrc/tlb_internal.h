@@ -71,6 +71,13 @@ struct tlb_batch {
     uint8_t *d_dec_prev = nullptr;               // [nstreams][out_stride] the last slot of the call before
     unsigned long long *d_dec_bad = nullptr;     // frames with a TL_DEC_BAD_MASK flag since creation
     int16_t *d_cmp_hist = nullptr;               // compare monitor (tlb_compare.cpp): [nstreams][2][TL_CMP_HIST] the input the next decoded frame is set against, allocated by the first compare call
+    // resampler (tlb_resample.cpp), allocated by the first tlb_resample_set_source: a batch that never sets a source has none of it
+    uint32_t *d_rs_state = nullptr;              // [2][nstreams][TL_RS_STATE_WORDS]; a launch reads copy rs_flip and writes the other
+    int32_t *d_rs_ratio = nullptr;               // [nstreams] TL_RS_*
+    int16_t *d_rs_taps = nullptr;                // both tables: [160][32], then [3][32]
+    int rs_flip = 0;
+    std::vector<long> rs_rate;                   // [nstreams] source rate, 0: off (empty until the first set_source)
+    std::vector<int32_t> rs_ratio, rs_pos;       // host copies: TL_RS_* and the frame position in the need cycle
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
 };
 
@@ -105,4 +112,8 @@ int decode_prepare(tlb_batch *b);
 int compare_prepare(tlb_batch *b);
 int compare_launch(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_dec_pcm, const tlb_frame_report *d_report, int nframes,
                    const tlb_compare_params *params, tlb_compare_record *d_record, void *hip_stream);
+// tlb_resample.cpp: the resampler state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); the legality of a
+// stream's source with a new encoder rate (tlb_stream_reconfigure)
+int resample_clear_streams(tlb_batch *b, int s0, int n);
+bool resample_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -24,6 +24,7 @@
 
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
+#include "mp2_resample.h"
 #include "tlb_mailbox.h"
 #include "tlb_plan.h"
 #ifdef TLB_FAULT_INJECT
@@ -155,6 +156,7 @@ struct tlb_node {
     int monitor = 0;                             // tlb_node_enable_monitor(): TLB_MONITOR_* of every shard's tick object (a restarted shard's too)
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
+    std::vector<long> source;                    // tlb_node_set_source(): the source rate of every stream (0: off), set again on a restarted shard; empty: never set
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
@@ -291,6 +293,11 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         s.batch = tlb_create(s.device, s.n, nd->cfgs.data() + s.first, &e);
         if (!s.batch) return e ? e : TLB_ERR_HIP;
         if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) return TLB_ERR_HIP;
+    }
+    for (int k = 0; k < s.n && !nd->source.empty(); k++) {           // the caller's sources, with fresh state
+        const long r = nd->source[(size_t)(s.first + k)];
+        if (r == 0) continue;
+        if (int rc = s.tick ? tlb_tick_set_source(s.tick, k, r) : tlb_resample_set_source(s.batch, k, r)) return rc;
     }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
@@ -545,6 +552,7 @@ int32_t *tlb_node_xpad_len(tlb_node *nd, int stream)
 int tlb_node_enable_short_reads(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
+    for (long r : nd->source) if (r) return TLB_ERR_ARG;             // a source and short reads exclude each other (include/toolame_batch.h)
     if (nd->short_reads) return TLB_OK;
     const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
     if (!rc) nd->short_reads = true;
@@ -607,6 +615,51 @@ const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream)
         if (p) { if (stream) *stream = s->first + k; return p; }
     }
     return nullptr;
+}
+// A source rate for one stream or all: to the owning shards' objects, on their threads, between steps.  A broken shard answers TLB_ERR_HIP, a
+// late one TLB_ERR_LATE; with stream = -1 either stops the call before any shard is changed.  What went through is remembered for restarts.
+int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
+{
+    if (!nd || stream < -1 || stream >= nd->nstreams || source_rate < 0 || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
+    bool any = false;
+    for (int k = s0; k < s1; k++) {
+        const long enc = nd->cfgs[(size_t)k].samplerate;
+        if (source_rate == 0 || source_rate == enc) continue;
+        if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
+        any = true;
+    }
+    if (any && nd->short_reads) return TLB_ERR_ARG;
+    for (Shard *s : nd->shards) {
+        if (s->first >= s1 || s->first + s->n <= s0) continue;
+        if (s->late) return TLB_ERR_LATE;
+        if (!s->live()) return TLB_ERR_HIP;
+    }
+    if (nd->source.empty()) { if (!any) return TLB_OK; nd->source.assign((size_t)nd->nstreams, 0); }
+    for (Shard *s : nd->shards) {
+        if (s->first >= s1 || s->first + s->n <= s0) continue;
+        const int k = stream < 0 ? -1 : stream - s->first;
+        auto set = [&](Shard &sh, int kk, long r) { return sh.tick ? tlb_tick_set_source(sh.tick, kk, r) : tlb_resample_set_source(sh.batch, kk, r); };
+        const int rc = nd->one(s->index, [&](Shard &sh) { return set(sh, k, source_rate); });
+        if (rc) {                                                    // a device failure half way (the pairs were checked above): the shards already
+            for (Shard *u : nd->shards) {                            // changed, and this one, get the sources they had, with fresh state
+                if (u->index > s->index || u->first >= s1 || u->first + u->n <= s0) continue;
+                (void)nd->one(u->index, [&](Shard &sh) { for (int i = 0; i < sh.n; i++) (void)set(sh, i, nd->source[(size_t)(sh.first + i)]); return 0; });
+            }
+            return rc;
+        }
+    }
+    for (int i = s0; i < s1; i++) nd->source[(size_t)i] = source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate;
+    return TLB_OK;
+}
+int tlb_node_need(const tlb_node *nd, int stream)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK) return -TLB_ERR_ARG;
+    int k; Shard *s = nd->of(stream, &k);
+    if (!s) return -TLB_ERR_ARG;
+    if (s->late) return -TLB_ERR_LATE;
+    if (!s->live() || !s->tick) return -TLB_ERR_HIP;
+    return tlb_tick_need(s->tick, k);
 }
 int32_t *tlb_node_valid(tlb_node *nd, int stream)
 {

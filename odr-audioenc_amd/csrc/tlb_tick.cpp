@@ -14,6 +14,7 @@ struct TickGroup {
     tlb_batch *b = nullptr;
     int first = 0, n = 0, out_stride = 0, max_upf = 1, af_stride = 0, max_frags = 0, frag_stride = 0;
     int16_t *d_inter = nullptr, *d_pcm = nullptr, *d_peaks = nullptr;
+    int16_t *d_rs = nullptr;                                    // resampler (tlb_tick_set_source): d_inter at the encoder's rate, what the ingest reads
     uint8_t *d_xpad = nullptr; int32_t *d_xl = nullptr;
     uint8_t *d_frames = nullptr; int32_t *d_flen = nullptr;
     tlb_edi_state *d_state = nullptr; uint8_t *d_pkts = nullptr; int32_t *d_plen = nullptr;
@@ -56,6 +57,8 @@ struct tlb_tick {
     tlb_monitor_record *h_record[3] = {}; int16_t *h_listen[3] = {};
     int listen = -1;                             // the stream the NEXT submit carries (tlb_tick_monitor_listen); -1: none
     int listen_of[3] = {-1, -1, -1};             // ... the tick of each output set carried
+    bool resample = false;                       // at least one stream has a source: every submit queues the resampler between copy-in and ingest
+                                                 // (the groups' d_rs buffers, once made, stay until destroy)
     // compare monitor, off until tlb_tick_enable_compare(): needs the AUDIO monitor's decoded PCM; its records travel with the output sets too
     bool compare = false;
     tlb_compare_params cparams = {};
@@ -227,7 +230,7 @@ const uint32_t *tlb_tick_underruns(const tlb_tick *t) { return t && t->short_rea
 // call makes the device calls it always made.
 int tlb_tick_enable_short_reads(tlb_tick *t)
 {
-    if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
+    if (!t || t->finished || t->ticks > 0 || t->resample) return TLB_ERR_ARG;      // (a source and short reads exclude each other: include/toolame_batch.h)
     if (t->broken) return TLB_ERR_HIP;
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
@@ -327,6 +330,54 @@ const int16_t *tlb_tick_monitor_pcm(const tlb_tick *t, int *stream)
     const int s = t && t->monitor == TLB_MONITOR_AUDIO ? t->listen_of[t->out_set] : -1;
     if (stream) *stream = s;
     return s >= 0 ? t->h_listen[t->out_set] : nullptr;
+}
+// A source rate for one stream or all (tlb_resample_set_source of the group's batch), while no tick is in flight.  The first real source
+// gives every group its second device input buffer; from then on every submit runs the resampler.  An object that never sets one makes
+// the device calls it always made.
+int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
+{
+    if (!t || t->finished || stream < -1 || stream >= t->nstreams || source_rate < 0 || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    bool any = false;
+    for (auto &G : t->groups)                                        // every stream is checked before one is changed
+        for (int k = 0; k < G.n; k++) {
+            if (stream >= 0 && stream != G.first + k) continue;
+            const long enc = G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate;
+            if (source_rate == 0 || source_rate == enc) continue;
+            if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
+            any = true;
+        }
+    if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
+    if (any && t->short_reads) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(t->device));
+    if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer is made before one is committed
+        std::vector<void *> made;
+        hipError_t e = hipSuccess;
+        for (auto &G : t->groups) {
+            void *p = nullptr;
+            if ((e = hipMalloc(&p, (size_t)G.n * 2304 * sizeof(int16_t))) != hipSuccess) break;
+            made.push_back(p);
+            if ((e = hipMemset(p, 0, (size_t)G.n * 2304 * sizeof(int16_t))) != hipSuccess) break;
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();             // the memsets ran on the null stream, the tick's streams do not wait for it
+        if (e != hipSuccess) { for (void *p : made) (void)hipFree(p); HIPCHK(e); }
+        for (size_t g = 0; g < t->groups.size(); g++) { t->groups[g].d_rs = (int16_t *)made[g]; t->dev.push_back(made[g]); }
+    }
+    int rc = TLB_OK;
+    for (auto &G : t->groups) {
+        if (stream >= 0 && (stream < G.first || stream >= G.first + G.n)) continue;
+        if ((rc = tlb_resample_set_source(G.b, stream < 0 ? -1 : stream - G.first, source_rate))) break;
+    }
+    t->resample = false;                                             // "at least one source set", as the streams stand now
+    for (auto &G : t->groups)
+        for (int k = 0; k < G.n; k++) if (tlb_resample_source(G.b, k)) t->resample = true;
+    return rc;
+}
+int tlb_tick_need(const tlb_tick *t, int stream)
+{
+    if (!t || stream < 0 || stream >= t->nstreams) return -TLB_ERR_ARG;
+    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
+    return tlb_resample_need(G.b, stream - G.first, 0);
 }
 long tlb_tick_count(const tlb_tick *t) { return t ? t->ticks : 0; }
 int tlb_tick_set_gain_db(tlb_tick *t, int stream, double gain_db)
@@ -529,7 +580,8 @@ int tlb_tick_submit(tlb_tick *t)
         if (e == hipSuccess) e = hipStreamWaitEvent(t->s_run, G.ev_in, 0);
         if (e == hipSuccess && t->ticks > 0) e = hipStreamWaitEvent(t->s_run, G.ev_out, 0);
         if (e != hipSuccess) rc = TLB_ERR_HIP;
-        if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
+        if (!rc && t->resample) rc = tlb_resample_device(G.b, G.d_inter, 1, G.d_rs, t->s_run);
+        if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, t->resample ? G.d_rs : G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
         if (!rc && t->short_reads) rc = tlb_ingest_device_valid(G.b, G.d_inter, G.d_valid, 1, G.d_pcm, G.d_peaks, t->s_run);
         // (the counters here and not with the silence counter: the next tick's copy-in may overwrite d_valid once ev_ingested has passed)
         if (!rc && t->short_reads) rc = tlb_underrun_device(G.b, G.d_valid, 1, G.d_underrun_ms, G.d_underruns, t->s_run);

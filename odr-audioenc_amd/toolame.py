@@ -253,6 +253,20 @@ def _bind(L):
         L.tlb_node_enable_compare.argtypes = [C.c_void_p, C.c_void_p]
         L.tlb_node_compare.restype = C.c_void_p
         L.tlb_node_compare.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_resample_device"):         # device resampler
+        L.tlb_resample_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        L.tlb_resample_source.restype = C.c_long
+        L.tlb_resample_source.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_resample_need.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.tlb_resample_need_at.argtypes = [C.c_long, C.c_long, C.c_long]
+        L.tlb_resample_taps.restype = C.c_void_p
+        L.tlb_resample_taps.argtypes = [C.c_long, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.tlb_resample_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_resample_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_tick_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        L.tlb_tick_need.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        L.tlb_node_need.argtypes = [C.c_void_p, C.c_int]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -267,6 +281,23 @@ def _bind(L):
         L.tlb_node_set_deadline_ms.argtypes = [C.c_void_p, C.c_double]
         L.tlb_node_shard_deadline_status.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     return L
+
+
+def resample_need_at(source_rate, encoder_rate, frame):
+    """source frames frame `frame` (from the stream's reset) of a source_rate -> encoder_rate stream consumes: host arithmetic, no GPU"""
+    n = load_library().tlb_resample_need_at(int(source_rate), int(encoder_rate), int(frame))
+    if n < 0:
+        raise ToolameError(-n, "tlb_resample_need_at")
+    return n
+
+
+def resample_taps(source_rate, encoder_rate):
+    """the committed polyphase table of the pair -> (int16 [L, T] copy, L, M); None when the pair is not supported"""
+    l, m, tt = C.c_int(0), C.c_int(0), C.c_int(0)
+    p = load_library().tlb_resample_taps(int(source_rate), int(encoder_rate), C.byref(l), C.byref(m), C.byref(tt))
+    if not p:
+        return None
+    return np.ctypeslib.as_array((C.c_int16 * (l.value * tt.value)).from_address(p)).reshape(l.value, tt.value).copy(), l.value, m.value
 
 
 def lds_bytes_per_stream():
@@ -401,6 +432,19 @@ class Tick:
     @property
     def silence_ms(self):
         return self._view("tlb_tick_silence_ms", C.c_uint32, (self.nstreams,))
+
+    # -- device resampler (tlb_tick_set_source): legal while no tick is in flight; excludes short reads --
+    def set_source(self, source_rate, stream=-1):
+        rc = self.L.tlb_tick_set_source(self.h, stream, int(source_rate))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_set_source")
+
+    def need(self, s):
+        """source frames stream s's slot of `pcm` must hold for the next submit (1152 without a source)"""
+        n = self.L.tlb_tick_need(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_tick_need")
+        return n
 
     # -- short reads (src/odr-audioenc.cpp:335-373,910-935): opt in before the first submit --
     def enable_short_reads(self):
@@ -786,6 +830,38 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_set_gain_db")
 
+    # -- device resampler (tlb_resample_*): 44.1 / 22.05 kHz (160/147) and 32 / 16 kHz (3/2) sources to the encoder's rate --
+    def set_source(self, source_rate, stream=-1):
+        """0 or the stream's own rate: off; waits for queued launches and zeroes the resampler state of the streams it names"""
+        rc = self.L.tlb_resample_set_source(self.h, stream, int(source_rate))
+        if rc:
+            raise ToolameError(rc, "tlb_resample_set_source")
+
+    def source(self, s):
+        return int(self.L.tlb_resample_source(self.h, s))
+
+    def need(self, s, ahead=0):
+        n = self.L.tlb_resample_need(self.h, s, ahead)
+        if n < 0:
+            raise ToolameError(-n, "tlb_resample_need")
+        return n
+
+    def resample(self, source, out=None):
+        """int16 [nframes, nstreams, 2304], each slot holding need() source frames at its start -> the same shape at the encoder's rate,
+        what ingest() takes.  out: the array to write into (values the kernel does not write keep what it held); None: zeros"""
+        a = np.ascontiguousarray(source, dtype=np.int16)
+        nf = a.shape[0]
+        if a.shape != (nf, self.nstreams, 2 * SAMPLES):
+            raise ToolameError(18, f"source shape {a.shape}")
+        if out is None:
+            out = np.zeros_like(a)
+        if out.dtype != np.int16 or out.shape != a.shape or not out.flags.c_contiguous:
+            raise ToolameError(18, "out array")
+        rc = self.L.tlb_resample_host(self.h, a.ctypes.data, nf, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_resample_host")
+        return out
+
     def ingest(self, interleaved, valid=None):
         """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2]).
         valid: int32 [nframes, nstreams] sample frames each slot delivers -- a short read is stretched over the frame as the reference
@@ -1111,6 +1187,16 @@ class Node:
 
     def silence_ms(self, s):
         return int(self.L.tlb_node_silence_ms(self.h, s))
+
+    # device resampler (Tick.set_source / need with node-wide indices; remembered for shard restarts)
+    def set_source(self, source_rate, stream=-1):
+        self._rc(self.L.tlb_node_set_source(self.h, stream, int(source_rate)), "tlb_node_set_source")
+
+    def need(self, s):
+        n = self.L.tlb_node_need(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_node_need")
+        return n
 
     # short reads (Tick.enable_short_reads, per stream with node-wide indices)
     def enable_short_reads(self):

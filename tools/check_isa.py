@@ -39,6 +39,8 @@ LIMITS = [
     (re.compile(r"tl_ingest_valid_kernel"), dict(vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # compare monitor (csrc/toolame_compare.hip): a streaming kernel with eight 64-bit accumulators per lane; four waves' histories share a workgroup's LDS
     (re.compile(r"tl_compare_kernel"), dict(vgpr=128, lds=4 * 6560, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # resampler (csrc/toolame_resample.hip): a workgroup per slot with the ratio's table and the slot's source frames in LDS (17 168 bytes)
+    (re.compile(r"tl_resample_kernel"), dict(vgpr=128, lds=17168, vgpr_spill=0, sgpr_spill=0, scratch=0)),
 ]
 
 
