@@ -1,5 +1,5 @@
-// tl_kernels.h -- the one door between the host translation units (tlb_batch.cpp, tlb_egress.cpp, tlb_tick.cpp: plain C++, seconds to
-// compile) and the kernels (toolame_hip.hip, toolame_psy2.hip, toolame_dec.hip, toolame_ingest.hip, toolame_monitor.hip, toolame_compare.hip, toolame_resample.hip: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
+// tl_kernels.h -- the one door between the host translation units (csrc/Makefile: HOST_UNITS, plain C++, seconds to compile) and the
+// kernels (KERNEL_UNITS: the only files that see mp2_wave.h).  Each launcher queues ONE kernel on
 // `st` and returns hipGetLastError(); grid shapes that depend on the kernels' wave counts are computed from the constants below.
 #pragma once
 #include <hip/hip_runtime_api.h>

@@ -29,49 +29,26 @@ void tlb_destroy(tlb_batch *b)
 {
     if (!b) return;
     (void)hipSetDevice(b->device);
-    if (b->d_tables) (void)hipFree(b->d_tables);
     if (b->d_configs) (void)hipFree(b->d_configs);
-    if (b->d_stream_cfg) (void)hipFree(b->d_stream_cfg);
-    if (b->d_state) (void)hipFree(b->d_state);
-    if (b->d_gain) (void)hipFree(b->d_gain);
-    if (b->d_edi_version) (void)hipFree(b->d_edi_version);
-    if (b->d_frame_bytes) (void)hipFree(b->d_frame_bytes);
-    if (b->d_unit_bytes) (void)hipFree(b->d_unit_bytes);
-    if (b->d_edi_state_tmp) (void)hipFree(b->d_edi_state_tmp);
-    if (b->d_pseq_tmp) (void)hipFree(b->d_pseq_tmp);
-    for (int p = 0; p < 4; p++) if (b->d_list[p]) (void)hipFree(b->d_list[p]);
     for (int k = 0; k < 12; k++) if (b->stage[k]) (void)hipFree(b->stage[k]);
     for (int i = 0; i < TLB_HOST_CHUNKS; i++) { if (b->ev_in[i]) (void)hipEventDestroy(b->ev_in[i]); if (b->ev_run[i]) (void)hipEventDestroy(b->ev_run[i]); }
     if (b->s_in) (void)hipStreamDestroy(b->s_in);
     if (b->s_run) (void)hipStreamDestroy(b->s_run);
     if (b->s_out) (void)hipStreamDestroy(b->s_out);
-    if (b->d_newpend) (void)hipFree(b->d_newpend);
-    if (b->d_work) (void)hipFree(b->d_work);
-    if (b->d_newlag) (void)hipFree(b->d_newlag);
-    if (b->d_psy2_tables) (void)hipFree(b->d_psy2_tables);
-    if (b->d_psy2_state) (void)hipFree(b->d_psy2_state);
-    if (b->d_chain) (void)hipFree(b->d_chain);
-    if (b->d_partner) (void)hipFree(b->d_partner);
-    if (b->d_synth) (void)hipFree(b->d_synth);
-    if (b->d_dec_state) (void)hipFree(b->d_dec_state);
-    if (b->d_dec_prev) (void)hipFree(b->d_dec_prev);
-    if (b->d_dec_bad) (void)hipFree(b->d_dec_bad);
-    if (b->d_cmp_hist) (void)hipFree(b->d_cmp_hist);
-    if (b->d_rs_state) (void)hipFree(b->d_rs_state);
-    if (b->d_rs_ratio) (void)hipFree(b->d_rs_ratio);
-    if (b->d_rs_taps) (void)hipFree(b->d_rs_taps);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->ev_mid) (void)hipEventDestroy(b->ev_mid);
-    delete b;
+    delete b;                                    // (b->mem frees every other buffer)
 }
 
 // Everything that follows from WHICH stream has WHICH configuration: the per-model stream lists of the kernels, the psy-2 kernel's
 // chains, the padding flags, and -- allocated the first time a stream needs them -- the psy 2/4 tables and state and the slot
-// recurrence's scratch.  Called at creation and again when a stream is reconfigured (tlb_stream_reconfigure).
+// recurrence's scratch.  Called at creation and again when a stream is reconfigured (tlb_stream_reconfigure).  What it allocates is made
+// once and kept: staged in `m`, handed to the batch's owner as soon as it is complete.
 static int batch_build_lists(tlb_batch *b)
 {
     const int nstreams = b->nstreams;
+    TlbMem m;
     for (int p = 0; p < 4; p++) {
         std::vector<int32_t> ids;
         b->pads[p] = false;
@@ -79,7 +56,9 @@ static int batch_build_lists(tlb_batch *b)
         for (int s2 = 0; s2 < nstreams; s2++) { const int m = b->h_configs[b->h_stream_cfg[s2]].psy; if ((m == 4 ? 2 : m) == p) { ids.push_back(s2); b->pads[p] |= b->h_configs[b->h_stream_cfg[s2]].pad_frac != 0; } }
         b->n_list[p] = (int)ids.size();
         if (ids.empty()) continue;
-        if (!b->d_list[p]) HIPCHK(hipMalloc(&b->d_list[p], sizeof(int32_t) * (size_t)nstreams));       // room for every stream: a list only changes its content later
+        if (!b->d_list[p]) b->d_list[p] = m.scratch<int32_t>((size_t)nstreams);                        // room for every stream: a list only changes its content later
+        MEMCHK(m);
+        m.commit(b->mem);
         HIPCHK(hipMemcpy(b->d_list[p], ids.data(), sizeof(int32_t) * ids.size(), hipMemcpyHostToDevice));
     }
     {   // mono streams of the same configuration (hence the same model and kernel) in pairs: consecutive ones of the stream order
@@ -92,7 +71,9 @@ static int batch_build_lists(tlb_batch *b)
         }
         for (int s2 = 0; s2 < nstreams; s2++)
             if (partner[(size_t)s2] >= 0) { const int m = b->h_configs[b->h_stream_cfg[s2]].psy; b->list_pairs[m == 4 ? 2 : m] = true; }
-        if (!b->d_partner) HIPCHK(hipMalloc(&b->d_partner, sizeof(int32_t) * (size_t)nstreams));
+        if (!b->d_partner) b->d_partner = m.scratch<int32_t>((size_t)nstreams);
+        MEMCHK(m);
+        m.commit(b->mem);
         HIPCHK(hipMemcpy(b->d_partner, partner.data(), sizeof(int32_t) * (size_t)nstreams, hipMemcpyHostToDevice));
     }
     if (b->n_list[2]) {
@@ -103,11 +84,13 @@ static int batch_build_lists(tlb_batch *b)
                 tl_build_psy2_tables(&ht2[tl_psy2_slot(rates[i])], rates[i]);
                 tl_build_psy4_tables(&ht2[TL_PSY2_SLOTS + tl_psy2_slot(rates[i])], rates[i]);
             }
-            HIPCHK(hipMalloc(&b->d_psy2_tables, sizeof(TlPsy2Tables) * ht2.size()));
-            HIPCHK(hipMemcpy(b->d_psy2_tables, ht2.data(), sizeof(TlPsy2Tables) * ht2.size(), hipMemcpyHostToDevice));
-            HIPCHK(hipMalloc(&b->d_psy2_state, sizeof(TlPsy2State) * 2 * (size_t)nstreams));
-            HIPCHK(hipMemset(b->d_psy2_state, 0, sizeof(TlPsy2State) * 2 * (size_t)nstreams));
-            HIPCHK(hipMalloc(&b->d_chain, sizeof(int32_t) * 2 * (size_t)nstreams));
+            TlPsy2Tables *tb = m.scratch<TlPsy2Tables>(ht2.size());
+            TlPsy2State *ps = m.dev<TlPsy2State>(2 * (size_t)nstreams);
+            int32_t *ch = m.scratch<int32_t>(2 * (size_t)nstreams);
+            m.upload(tb, ht2.data(), sizeof(TlPsy2Tables) * ht2.size());
+            MEMCHK(m);                                               // all three or none
+            m.commit(b->mem);
+            b->d_psy2_tables = tb; b->d_psy2_state = ps; b->d_chain = ch;
         }
         std::vector<int32_t> chains;
         for (int ch = 0; ch < 2; ch++)
@@ -119,8 +102,9 @@ static int batch_build_lists(tlb_batch *b)
         HIPCHK(hipMemcpy(b->d_chain, chains.data(), sizeof(int32_t) * chains.size(), hipMemcpyHostToDevice));
     } else b->n_chain = 0;
     if ((b->pads[0] || b->pads[1] || b->pads[2] || b->pads[3]) && !b->d_newlag) {
-        HIPCHK(hipMalloc(&b->d_newlag, sizeof(double) * (size_t)nstreams));
-        HIPCHK(hipMemset(b->d_newlag, 0, sizeof(double) * (size_t)nstreams));
+        b->d_newlag = m.dev<double>((size_t)nstreams);
+        MEMCHK(m);
+        m.commit(b->mem);
     }
     return TLB_OK;
 }
@@ -148,28 +132,25 @@ static int tlb_create_impl(tlb_batch *b, int device, int nstreams, const tlb_str
     }
     HIPCHK(hipSetDevice(device));
     { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n > 0) b->num_cu = n; }
+    TlbMem &m = b->mem;                                              // straight into the batch's owner: a failure here ends in tlb_destroy
     TlTables *ht = new TlTables;
     tl_build_tables(ht);
-    hipError_t e = hipMalloc(&b->d_tables, sizeof(TlTables));
-    if (e == hipSuccess) e = hipMemcpy(b->d_tables, ht, sizeof(TlTables), hipMemcpyHostToDevice);
+    b->d_tables = m.scratch<TlTables>(1);
+    m.upload(b->d_tables, ht, sizeof(TlTables));
     delete ht;
-    HIPCHK(e);
     b->cfg_cap = b->h_configs.size() + 8;                             // room for a few reconfigurations before the array has to move
     HIPCHK(hipMalloc(&b->d_configs, sizeof(TlConfig) * b->cfg_cap));
     HIPCHK(hipMemcpy(b->d_configs, b->h_configs.data(), sizeof(TlConfig) * b->h_configs.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&b->d_stream_cfg, sizeof(int32_t) * nstreams));
-    HIPCHK(hipMemcpy(b->d_stream_cfg, b->h_stream_cfg.data(), sizeof(int32_t) * nstreams, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&b->d_state, sizeof(TlStreamState) * (size_t)nstreams));
-    HIPCHK(hipMemset(b->d_state, 0, sizeof(TlStreamState) * (size_t)nstreams));
+    b->d_stream_cfg = m.scratch<int32_t>((size_t)nstreams);
+    m.upload(b->d_stream_cfg, b->h_stream_cfg.data(), sizeof(int32_t) * (size_t)nstreams);
+    b->d_state = m.dev<TlStreamState>((size_t)nstreams);
     b->h_gain.assign((size_t)nstreams, 1.0);
-    HIPCHK(hipMalloc(&b->d_gain, sizeof(double) * (size_t)nstreams));
-    HIPCHK(hipMemcpy(b->d_gain, b->h_gain.data(), sizeof(double) * (size_t)nstreams, hipMemcpyHostToDevice));
+    b->d_gain = m.scratch<double>((size_t)nstreams);
+    m.upload(b->d_gain, b->h_gain.data(), sizeof(double) * (size_t)nstreams);
+    b->d_newpend = m.dev<uint32_t>(TL_MAX_FRAME_WORDS * (size_t)nstreams);
+    b->d_work = m.scratch<int32_t>(TL_HEAD_STRIDE * 9);
+    MEMCHK(m);
     if (int rc = batch_build_lists(b)) return rc;
-    {
-        HIPCHK(hipMalloc(&b->d_newpend, sizeof(uint32_t) * TL_MAX_FRAME_WORDS * (size_t)nstreams));
-        HIPCHK(hipMemset(b->d_newpend, 0, sizeof(uint32_t) * TL_MAX_FRAME_WORDS * (size_t)nstreams));
-        HIPCHK(hipMalloc(&b->d_work, sizeof(int32_t) * TL_HEAD_STRIDE * 9));
-    }
     HIPCHK(hipEventCreate(&b->ev0));
     HIPCHK(hipEventCreate(&b->ev1));
     HIPCHK(hipEventCreate(&b->ev_mid));
@@ -307,6 +288,7 @@ int tlb_out_stride(const tlb_batch *b) { return b ? b->out_stride : 0; }
 long tlb_frames_encoded(const tlb_batch *b) { return b ? b->frames : 0; }
 #ifdef TLB_FAULT_INJECT
 int tlb_debug_fail_next(tlb_batch *b, int nth) { if (!b || nth < 0) return TLB_ERR_ARG; b->fail_in = nth; return TLB_OK; }
+int tlb_debug_alloc_fail_next(int nth) { if (nth < 0) return TLB_ERR_ARG; TlbMem::fail_in.store(nth); return TLB_OK; }
 #endif
 
 }  // extern "C"
@@ -482,15 +464,13 @@ void tlb_host_free(void *p) { if (p) (void)hipHostFree(p); }
 // Diagnostic: per-stage s_memtime stamps [nframes][nstreams][32] (see TL_STAMP in mp2_wave.h).
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps)
 {
-    DevFree guard_;
     if (!b || !pcm || !stamps || nframes <= 0) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    int16_t *d_pcm = nullptr; uint8_t *d_out = nullptr; long long *d_st = nullptr;
-    DEVALLOC(d_pcm, slots * 2304 * sizeof(int16_t));
-    DEVALLOC(d_out, slots * (size_t)b->out_stride);
-    DEVALLOC(d_st, slots * 32 * sizeof(long long));
-    HIPCHK(hipMemset(d_st, 0, slots * 32 * sizeof(long long)));
+    TlbMem m;
+    int16_t *d_pcm = m.scratch<int16_t>(slots * 2304); uint8_t *d_out = m.scratch<uint8_t>(slots * (size_t)b->out_stride);
+    long long *d_st = m.dev<long long>(slots * 32);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_pcm, pcm, slots * 2304 * sizeof(int16_t), hipMemcpyHostToDevice));
     int rc = tlb_launch(b, d_pcm, nframes, nullptr, nullptr, d_out, nullptr, nullptr, d_st);
     HIPCHK(hipDeviceSynchronize());
@@ -548,7 +528,6 @@ int tlb_ingest_device_valid(tlb_batch *b, const int16_t *d_interleaved, const in
 int tlb_ingest_host_valid(tlb_batch *b, const int16_t *interleaved, const int32_t *valid, int nframes, int16_t *pcm, int16_t *peaks)
 {
     if (!valid) return tlb_ingest_host(b, interleaved, nframes, pcm, peaks);
-    DevFree guard_;
     if (!b || !interleaved || !pcm || !peaks || nframes <= 0) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams;
@@ -556,8 +535,9 @@ int tlb_ingest_host_valid(tlb_batch *b, const int16_t *interleaved, const int32_
     HIPCHK(stage_reserve(b, 10, slots * 2304 * 2));
     HIPCHK(stage_reserve(b, 11, slots * 2 * 2));
     int16_t *d_in = (int16_t *)b->stage[9], *d_out = (int16_t *)b->stage[10], *d_pk = (int16_t *)b->stage[11];
-    int32_t *d_valid = nullptr;
-    DEVALLOC(d_valid, slots * sizeof(int32_t));
+    TlbMem m;
+    int32_t *d_valid = m.scratch<int32_t>(slots);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_in, interleaved, slots * 2304 * 2, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_valid, valid, slots * sizeof(int32_t), hipMemcpyHostToDevice));
     int rc = tlb_ingest_device_valid(b, d_in, d_valid, nframes, d_out, d_pk, nullptr);
@@ -578,14 +558,12 @@ int tlb_underrun_device(tlb_batch *b, const int32_t *d_valid, int nframes, uint3
 
 int tlb_underrun_host(tlb_batch *b, const int32_t *valid, int nframes, uint32_t *underrun_ms, uint32_t *underruns)
 {
-    DevFree guard_;
     if (!b || !valid || !underrun_ms || !underruns || nframes <= 0) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams, n = (size_t)b->nstreams;
-    int32_t *d_v = nullptr; uint32_t *d_m = nullptr, *d_n = nullptr;
-    DEVALLOC(d_v, slots * sizeof(int32_t));
-    DEVALLOC(d_m, sizeof(uint32_t) * n);
-    DEVALLOC(d_n, sizeof(uint32_t) * n);
+    TlbMem m;
+    int32_t *d_v = m.scratch<int32_t>(slots); uint32_t *d_m = m.scratch<uint32_t>(n), *d_n = m.scratch<uint32_t>(n);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_v, valid, slots * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_m, underrun_ms, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_n, underruns, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
@@ -606,13 +584,12 @@ int tlb_silence_device(tlb_batch *b, const int16_t *d_peaks, int nframes, uint32
 
 int tlb_silence_host(tlb_batch *b, const int16_t *peaks, int nframes, uint32_t *silence_ms)
 {
-    DevFree guard_;
     if (!b || !peaks || !silence_ms || nframes <= 0) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    int16_t *d_p = nullptr; uint32_t *d_m = nullptr;
-    DEVALLOC(d_p, slots * 4);
-    DEVALLOC(d_m, sizeof(uint32_t) * (size_t)b->nstreams);
+    TlbMem m;
+    int16_t *d_p = m.scratch<int16_t>(slots * 2); uint32_t *d_m = m.scratch<uint32_t>((size_t)b->nstreams);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_p, peaks, slots * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_m, silence_ms, sizeof(uint32_t) * (size_t)b->nstreams, hipMemcpyHostToDevice));
     int rc = tlb_silence_device(b, d_p, nframes, d_m, nullptr);
@@ -645,13 +622,12 @@ int tlb_flush_device(tlb_batch *b, uint8_t *d_out, void *hip_stream) { return tl
 
 int tlb_flush_host_len(tlb_batch *b, uint8_t *out, int32_t *out_len)
 {
-    DevFree guard_;
     if (!b || !out) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
-    uint8_t *d = nullptr; int32_t *dl = nullptr;
     const size_t n = (size_t)b->nstreams * (size_t)b->out_stride;
-    DEVALLOC(d, n);
-    DEVALLOC(dl, sizeof(int32_t) * (size_t)b->nstreams);
+    TlbMem m;
+    uint8_t *d = m.scratch<uint8_t>(n); int32_t *dl = m.scratch<int32_t>((size_t)b->nstreams);
+    MEMCHK(m);
     int rc = tlb_flush_device_len(b, d, dl, nullptr);
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, d, n, hipMemcpyDeviceToHost);

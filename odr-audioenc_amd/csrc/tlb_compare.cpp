@@ -3,6 +3,7 @@
 // Host C++.  The tick plane (tlb_tick.cpp) queues it behind its group's decode.
 #include <stddef.h>
 #include "tlb_internal.h"
+#include "tlb_plan.h"
 
 static_assert(sizeof(tlb_compare_record) == sizeof(TlCompareRecord) && sizeof(tlb_compare_params) == sizeof(TlCompareParams), "C-ABI record and parameters");
 static_assert(offsetof(tlb_compare_record, sxx) == offsetof(TlCompareRecord, sxx) && offsetof(tlb_compare_record, syy) == offsetof(TlCompareRecord, syy) &&
@@ -16,16 +17,14 @@ static_assert(offsetof(tlb_compare_params, min_energy) == offsetof(TlComparePara
 static_assert(TLB_COMPARE_DELAY == TL_CMP_DELAY && TLB_SAMPLES_PER_FRAME == TL_CMP_FRAME && TLB_COMPARE_JUDGED0 == TL_CMP_JUDGED0 && TLB_COMPARE_JUDGED1 == TL_CMP_JUDGED1 &&
               TLB_COMPARE_MISMATCH == TL_CMP_MISMATCH && TLB_COMPARE_SWAPPED == TL_CMP_SWAPPED && TLB_COMPARE_SKIPPED == TL_CMP_SKIPPED, "delay and flags");
 
-static bool params_legal(const tlb_compare_params *p) { return p && p->min_energy >= 1 && p->corr_num > 0 && p->corr_num <= p->corr_den && p->corr_den <= 1024; }
-
 int compare_prepare(tlb_batch *b)
 {
     if (b->d_cmp_hist) return TLB_OK;
     HIPCHK(hipSetDevice(b->device));
-    const size_t bytes = sizeof(int16_t) * 2 * TL_CMP_HIST * (size_t)b->nstreams;
-    int16_t *h = nullptr;
-    HIPCHK(hipMalloc(&h, bytes));
-    if (hipMemset(h, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(h); return TLB_ERR_HIP; }
+    TlbMem m;
+    int16_t *h = m.dev<int16_t>(2 * TL_CMP_HIST * (size_t)b->nstreams);
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(b->mem);
     b->d_cmp_hist = h;
     return TLB_OK;
 }
@@ -33,7 +32,7 @@ int compare_prepare(tlb_batch *b)
 int compare_launch(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_dec_pcm, const tlb_frame_report *d_report, int nframes,
                    const tlb_compare_params *params, tlb_compare_record *d_record, void *hip_stream)
 {
-    if (!b || !d_dec_pcm || !d_record || !params_legal(params) || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
+    if (!b || !d_dec_pcm || !d_record || !tlb_compare_params_legal(params) || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
     if (!d_in_pcm && nframes != 1) return TLB_ERR_ARG;
     if ((((uintptr_t)d_in_pcm | (uintptr_t)d_dec_pcm) & 15u) || ((uintptr_t)d_report & 3u) || ((uintptr_t)d_record & 7u)) return TLB_ERR_ARG;      // the kernel moves 16-byte pieces of PCM
     if (b->broken) return TLB_ERR_HIP;           // the device's stream -> configuration table may disagree with the host's (tlb_reset)
@@ -58,17 +57,15 @@ int tlb_compare_device(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_d
 int tlb_compare_host(tlb_batch *b, const int16_t *in_pcm, const int16_t *dec_pcm, const tlb_frame_report *report, int nframes,
                      const tlb_compare_params *params, tlb_compare_record *record)
 {
-    if (!b || !dec_pcm || !report || !record || !params_legal(params) || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
+    if (!b || !dec_pcm || !report || !record || !tlb_compare_params_legal(params) || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
     if ((!in_pcm && nframes != 1) || (((uintptr_t)in_pcm | (uintptr_t)dec_pcm) & 1u) || ((uintptr_t)report & 3u) || ((uintptr_t)record & 7u)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams, rec_bytes = (size_t)b->nstreams * sizeof(tlb_compare_record);
     const size_t pcm_bytes = slots * 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t);
-    DevFree guard_;
-    tlb_frame_report *d_report = nullptr; int16_t *d_in = nullptr, *d_dec = nullptr; tlb_compare_record *d_record = nullptr;
-    DEVALLOC(d_report, slots * sizeof(tlb_frame_report));
-    DEVALLOC(d_record, rec_bytes);
-    DEVALLOC(d_dec, pcm_bytes);
-    if (in_pcm) DEVALLOC(d_in, pcm_bytes);
+    TlbMem m;
+    tlb_frame_report *d_report = m.scratch<tlb_frame_report>(slots); tlb_compare_record *d_record = m.scratch<tlb_compare_record>((size_t)b->nstreams);
+    int16_t *d_dec = m.scratch<int16_t>(pcm_bytes / 2), *d_in = in_pcm ? m.scratch<int16_t>(pcm_bytes / 2) : nullptr;
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_report, report, slots * sizeof(tlb_frame_report), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_record, record, rec_bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_dec, dec_pcm, pcm_bytes, hipMemcpyHostToDevice));

@@ -23,6 +23,10 @@ int tlb_debug_node_fail_next(tlb_node *nd, int shard, int nth);    /* ... of one
  * tlb_tick_wait has returned with the tick complete, sleeps `ms` on the shard's HOST thread and then returns `rc` (0: the tick's results
  * stand; non-zero: as a failing call would).  The device stays idle and healthy: no kernel spins, no event is left incomplete. */
 int tlb_debug_node_stall_next(tlb_node *nd, int shard, int nth, int ms, int rc);
+/* The nth allocation through the library's memory owner (csrc/tlb_mem.h: device or pinned) from now, PROCESS-WIDE, is refused without a call
+ * to the runtime (1 = the next; 0 disarms): the creation, first-use and opt-in paths then fail as they would when memory runs out.  The
+ * counter is atomic (node shards allocate on their own threads).  Nothing is launched and the device is not touched. */
+int tlb_debug_alloc_fail_next(int nth);
 #ifdef __cplusplus
 }
 #endif

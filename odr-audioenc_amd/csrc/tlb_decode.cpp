@@ -7,35 +7,23 @@ static_assert(TLB_DEC_EMPTY == TL_DEC_EMPTY && TLB_DEC_BAD_SYNC == TL_DEC_BAD_SY
               TLB_DEC_BAD_ALLOC == TL_DEC_BAD_ALLOC && TLB_DEC_OVERRUN == TL_DEC_OVERRUN && TLB_DEC_BAD_MASK == TL_DEC_BAD_MASK, "status flags");
 static_assert(sizeof(tlb_frame_report) == sizeof(TlFrameReport) && sizeof(tlb_frame_fields) == sizeof(TlFrameFields), "C-ABI records");
 
-static int dec_prepare(tlb_batch *b);
-int decode_prepare(tlb_batch *b) { return dec_prepare(b); }
-static int dec_prepare(tlb_batch *b)
+// The one pattern of a first-use allocation (csrc/tlb_mem.h): stage in a local owner, upload the tables, settle, commit, then set the fields.
+int decode_prepare(tlb_batch *b)
 {
-    if (b->d_dec_bad) return TLB_OK;
+    if (b->d_synth) return TLB_OK;
     const size_t n = (size_t)b->nstreams;
-    if (!b->d_synth) {
-        TlSynthTables *hy = new TlSynthTables;
-        tl_build_synth_tables(hy);
-        hipError_t e = hipMalloc(&b->d_synth, sizeof(TlSynthTables));
-        if (e == hipSuccess) e = hipMemcpy(b->d_synth, hy, sizeof(TlSynthTables), hipMemcpyHostToDevice);
-        delete hy;
-        HIPCHK(e);
-    }
-    if (!b->d_dec_state) {
-        HIPCHK(hipMalloc(&b->d_dec_state, sizeof(TlDecStream) * n));
-        HIPCHK(hipMemset(b->d_dec_state, 0, sizeof(TlDecStream) * n));
-    }
-    if (!b->d_dec_prev) {
-        HIPCHK(hipMalloc(&b->d_dec_prev, n * (size_t)b->out_stride));
-        HIPCHK(hipMemset(b->d_dec_prev, 0, n * (size_t)b->out_stride));
-    }
-    unsigned long long *bad = nullptr;
-    HIPCHK(hipMalloc(&bad, sizeof *bad));
-    if (hipMemset(bad, 0, sizeof *bad) != hipSuccess) { (void)hipFree(bad); return TLB_ERR_HIP; }
-    // the copies and memsets above ran on the null stream; the caller's stream may be a non-blocking one that nothing orders behind
-    // them, so the first call (only) waits for the device here
-    if (hipDeviceSynchronize() != hipSuccess) { (void)hipFree(bad); return TLB_ERR_HIP; }
-    b->d_dec_bad = bad;                          // last: its presence says that everything above is there
+    TlbMem m;
+    TlSynthTables *synth = m.scratch<TlSynthTables>(1);
+    TlDecStream *state = m.dev<TlDecStream>(n);
+    uint8_t *prev = m.dev<uint8_t>(n * (size_t)b->out_stride);
+    unsigned long long *bad = m.dev<unsigned long long>(1);
+    TlSynthTables *hy = new TlSynthTables;
+    tl_build_synth_tables(hy);
+    m.upload(synth, hy, sizeof(TlSynthTables));
+    delete hy;
+    if (!m.settle()) return TLB_ERR_HIP;         // the first call (only) waits for the device
+    m.commit(b->mem);
+    b->d_synth = synth; b->d_dec_state = state; b->d_dec_prev = prev; b->d_dec_bad = bad;
     return TLB_OK;
 }
 
@@ -49,7 +37,7 @@ int tlb_decode_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_le
     if (((uintptr_t)d_frames | (uintptr_t)d_report | (uintptr_t)d_len | (uintptr_t)d_fields | (uintptr_t)d_pcm) & 3u) return TLB_ERR_ARG;
     if (b->broken) return TLB_ERR_HIP;           // the device's stream -> configuration table may disagree with the host's (tlb_reset)
     HIPCHK(hipSetDevice(b->device));
-    if (int rc = dec_prepare(b)) return rc;
+    if (int rc = decode_prepare(b)) return rc;
     TlDecLaunch A;
     memset(&A, 0, sizeof A);
     A.tables = b->d_tables; A.configs = b->d_configs; A.stream_cfg = b->h_configs.size() == 1 ? nullptr : b->d_stream_cfg;
@@ -67,13 +55,11 @@ int tlb_decode_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int
     if (!b || !frames || !report || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    DevFree guard_;
-    uint8_t *d_frames = nullptr; int32_t *d_len = nullptr; tlb_frame_report *d_report = nullptr; tlb_frame_fields *d_fields = nullptr; int16_t *d_pcm = nullptr;
-    DEVALLOC(d_frames, slots * (size_t)b->out_stride);
-    DEVALLOC(d_report, slots * sizeof(tlb_frame_report));
-    if (len) DEVALLOC(d_len, slots * sizeof(int32_t));
-    if (fields) DEVALLOC(d_fields, slots * sizeof(tlb_frame_fields));
-    if (pcm) DEVALLOC(d_pcm, slots * 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t));
+    TlbMem m;
+    uint8_t *d_frames = m.scratch<uint8_t>(slots * (size_t)b->out_stride); tlb_frame_report *d_report = m.scratch<tlb_frame_report>(slots);
+    int32_t *d_len = len ? m.scratch<int32_t>(slots) : nullptr; tlb_frame_fields *d_fields = fields ? m.scratch<tlb_frame_fields>(slots) : nullptr;
+    int16_t *d_pcm = pcm ? m.scratch<int16_t>(slots * 2 * TLB_SAMPLES_PER_FRAME) : nullptr;
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_frames, frames, slots * (size_t)b->out_stride, hipMemcpyHostToDevice));
     if (len) HIPCHK(hipMemcpy(d_len, len, slots * sizeof(int32_t), hipMemcpyHostToDevice));
     if (int rc = tlb_decode_device(b, d_frames, d_len, nframes, d_report, d_fields, d_pcm, nullptr)) return rc;

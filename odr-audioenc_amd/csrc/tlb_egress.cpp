@@ -23,17 +23,15 @@ extern "C" {
 
 int tlb_zmq_frame_host(tlb_batch *b, const uint8_t *frames, const int16_t *peaks, int nframes, uint8_t *msgs)
 {
-    DevFree guard_;
     if (!b || !frames || !msgs || nframes <= 0) return TLB_ERR_ARG;
     if (!b->max_upf) return TLB_ERR_SAMPLERATE;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams, ms = 12 + (size_t)b->out_stride, pslots = slots * (size_t)b->max_upf;
-    uint8_t *d_f = nullptr, *d_m = nullptr; int16_t *d_p = nullptr;
-    DEVALLOC(d_f, slots * (size_t)b->out_stride);
-    DEVALLOC(d_m, pslots * ms);
-    HIPCHK(hipMemset(d_m, 0, pslots * ms));
+    TlbMem m;
+    uint8_t *d_f = m.scratch<uint8_t>(slots * (size_t)b->out_stride), *d_m = m.dev<uint8_t>(pslots * ms); int16_t *d_p = peaks ? m.scratch<int16_t>(slots * 2) : nullptr;
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_f, frames, slots * (size_t)b->out_stride, hipMemcpyHostToDevice));
-    if (peaks) { DEVALLOC(d_p, slots * 4); HIPCHK(hipMemcpy(d_p, peaks, slots * 4, hipMemcpyHostToDevice)); }
+    if (peaks) HIPCHK(hipMemcpy(d_p, peaks, slots * 4, hipMemcpyHostToDevice));
     int rc = tlb_zmq_frame_device(b, d_f, d_p, nframes, d_m, nullptr);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(msgs, d_m, pslots * ms, hipMemcpyDeviceToHost));
@@ -77,18 +75,17 @@ int edi_af_device(tlb_batch *b, const uint8_t *d_frames, const int16_t *d_levels
     HIPCHK(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (!b->d_edi_version) {
-        // all three buffers or none: a failure half way must not leave the batch looking initialised
-        DevFree guard_;
-        uint8_t *d_v = nullptr; int32_t *d_fb = nullptr, *d_ub = nullptr; TlEdiState *d_st = nullptr;
-        DEVALLOC(d_v, TL_EDI_MAX_VERSION);
-        DEVALLOC(d_fb, sizeof(int32_t) * (size_t)b->nstreams);
-        DEVALLOC(d_ub, sizeof(int32_t) * (size_t)b->nstreams);
-        DEVALLOC(d_st, sizeof(TlEdiState) * (size_t)b->nstreams);
-        std::vector<int32_t> fb((size_t)b->nstreams), ub((size_t)b->nstreams);
+        // all four buffers or none: a failure half way must not leave the batch looking initialised.  No zeroing and no settle: this is
+        // a tick's first egress, and every buffer is written on `st` (or by the blocking uploads here) before the kernel reads it
+        TlbMem m;
+        const size_t ns = (size_t)b->nstreams;
+        uint8_t *d_v = m.scratch<uint8_t>(TL_EDI_MAX_VERSION); int32_t *d_fb = m.scratch<int32_t>(ns), *d_ub = m.scratch<int32_t>(ns); TlEdiState *d_st = m.scratch<TlEdiState>(ns);
+        std::vector<int32_t> fb(ns), ub(ns);
         for (int s = 0; s < b->nstreams; s++) { fb[(size_t)s] = b->h_configs[b->h_stream_cfg[s]].frame_bytes; ub[(size_t)s] = 3 * b->h_configs[b->h_stream_cfg[s]].kbps; }
-        HIPCHK(hipMemcpy(d_fb, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_ub, ub.data(), sizeof(int32_t) * ub.size(), hipMemcpyHostToDevice));
-        guard_.v.clear();
+        m.upload(d_fb, fb.data(), sizeof(int32_t) * ns);
+        m.upload(d_ub, ub.data(), sizeof(int32_t) * ns);
+        MEMCHK(m);
+        m.commit(b->mem);
         b->d_edi_version = d_v; b->d_frame_bytes = d_fb; b->d_unit_bytes = d_ub; b->d_edi_state_tmp = d_st;
     }
     // the ODRv string goes to the device when it changes, not on every call (an asynchronous copy from pageable memory may be
@@ -113,22 +110,19 @@ extern "C" {
 int tlb_edi_af_host(tlb_batch *b, const uint8_t *frames, const int16_t *levels, int nframes, tlb_edi_state *state,
                     const char *version, int version_len, uint8_t *pkts, int32_t *pkt_len)
 {
-    DevFree guard_;
     if (!b || !frames || !state || !pkts || !pkt_len || nframes <= 0) return TLB_ERR_ARG;
     const int stride = tlb_edi_af_stride(b, version_len);
     if (!stride) return TLB_ERR_ARG;
     if (!b->max_upf) return TLB_ERR_SAMPLERATE;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams, pslots = slots * (size_t)b->max_upf;
-    uint8_t *d_f = nullptr, *d_p = nullptr; int16_t *d_l = nullptr; tlb_edi_state *d_s = nullptr; int32_t *d_n = nullptr;
-    DEVALLOC(d_f, slots * (size_t)b->out_stride);
-    DEVALLOC(d_p, pslots * (size_t)stride);
-    DEVALLOC(d_s, sizeof(tlb_edi_state) * (size_t)b->nstreams);
-    DEVALLOC(d_n, sizeof(int32_t) * pslots);
-    HIPCHK(hipMemset(d_p, 0, pslots * (size_t)stride));
+    TlbMem m;
+    uint8_t *d_f = m.scratch<uint8_t>(slots * (size_t)b->out_stride), *d_p = m.dev<uint8_t>(pslots * (size_t)stride); int16_t *d_l = levels ? m.scratch<int16_t>(slots * 2) : nullptr;
+    tlb_edi_state *d_s = m.scratch<tlb_edi_state>((size_t)b->nstreams); int32_t *d_n = m.scratch<int32_t>(pslots);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_f, frames, slots * (size_t)b->out_stride, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_s, state, sizeof(tlb_edi_state) * (size_t)b->nstreams, hipMemcpyHostToDevice));
-    if (levels) { DEVALLOC(d_l, slots * 4); HIPCHK(hipMemcpy(d_l, levels, slots * 4, hipMemcpyHostToDevice)); }
+    if (levels) HIPCHK(hipMemcpy(d_l, levels, slots * 4, hipMemcpyHostToDevice));
     int rc = tlb_edi_af_device(b, d_f, d_l, nframes, d_s, version, version_len, d_p, d_n, nullptr);
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(pkts, d_p, pslots * (size_t)stride, hipMemcpyDeviceToHost);
@@ -177,7 +171,12 @@ int tlb_edi_pft_device(tlb_batch *b, const uint8_t *d_af, const int32_t *d_af_le
     if (max_frags < mf || frag_stride < fs) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!b->d_pseq_tmp) HIPCHK(hipMalloc(&b->d_pseq_tmp, sizeof(uint16_t) * (size_t)b->nstreams));
+    if (!b->d_pseq_tmp) {                                            // (written whole by the kernel before the copy below reads it)
+        TlbMem m;
+        b->d_pseq_tmp = m.scratch<uint16_t>((size_t)b->nstreams);
+        MEMCHK(m);
+        m.commit(b->mem);
+    }
     TlPftArgs A;
     A.af = d_af; A.af_len = d_af_len; A.pseq = d_pseq; A.pseq_out = b->d_pseq_tmp;
     A.frags = d_frags; A.frag_len = d_frag_len; A.nfrag = d_nfrag;
@@ -192,19 +191,13 @@ int tlb_edi_pft_host(tlb_batch *b, const uint8_t *af, const int32_t *af_len, int
                      int fec, int chunk_len, int transport, int addr_source, int dest_port,
                      uint8_t *frags, int32_t *frag_len, int32_t *nfrag, int max_frags, int frag_stride)
 {
-    DevFree guard_;
     if (!b || !af || !af_len || !pseq || !frags || !frag_len || !nfrag || nframes <= 0 || af_stride <= 0 || max_frags <= 0 || frag_stride <= 0) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    uint8_t *d_a = nullptr, *d_f = nullptr; int32_t *d_l = nullptr, *d_fl = nullptr, *d_n = nullptr; uint16_t *d_p = nullptr;
-    DEVALLOC(d_a, slots * (size_t)af_stride);
-    DEVALLOC(d_l, slots * 4);
-    DEVALLOC(d_f, slots * (size_t)max_frags * (size_t)frag_stride);
-    DEVALLOC(d_fl, slots * (size_t)max_frags * 4);
-    DEVALLOC(d_n, slots * 4);
-    DEVALLOC(d_p, sizeof(uint16_t) * (size_t)b->nstreams);
-    HIPCHK(hipMemset(d_f, 0, slots * (size_t)max_frags * (size_t)frag_stride));
-    HIPCHK(hipMemset(d_fl, 0, slots * (size_t)max_frags * 4));
+    TlbMem m;
+    uint8_t *d_a = m.scratch<uint8_t>(slots * (size_t)af_stride), *d_f = m.dev<uint8_t>(slots * (size_t)max_frags * (size_t)frag_stride);
+    int32_t *d_l = m.scratch<int32_t>(slots), *d_fl = m.dev<int32_t>(slots * (size_t)max_frags), *d_n = m.scratch<int32_t>(slots); uint16_t *d_p = m.scratch<uint16_t>((size_t)b->nstreams);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_a, af, slots * (size_t)af_stride, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_l, af_len, slots * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_p, pseq, sizeof(uint16_t) * (size_t)b->nstreams, hipMemcpyHostToDevice));

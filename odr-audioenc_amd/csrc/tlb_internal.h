@@ -13,6 +13,7 @@
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
 #include "tl_kernels.h"
+#include "tlb_mem.h"
 
 static_assert(TL_MAX_XPAD == TLB_MAX_XPAD, "xpad record size");
 #define TLB_HOST_CHUNKS 4            // tlb_encode_host pipelines a big call in this many chunks of frames
@@ -78,6 +79,8 @@ struct tlb_batch {
     int rs_flip = 0;
     std::vector<long> rs_rate;                   // [nstreams] source rate, 0: off (empty until the first set_source)
     std::vector<int32_t> rs_ratio, rs_pos;       // host copies: TL_RS_* and the frame position in the need cycle
+    TlbMem mem;                                  // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
+                                                 // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
 };
 
@@ -94,9 +97,8 @@ static inline hipError_t stage_reserve(tlb_batch *b, int k, size_t bytes)
     fprintf(stderr, "libtoolame-dab-hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
     return TLB_ERR_HIP; } } while (0)
 
-// device scratch of the *_host convenience entry points: released on every exit path
-struct DevFree { std::vector<void *> v; ~DevFree() { for (void *p : v) (void)hipFree(p); } };
-#define DEVALLOC(ptr, bytes) do { HIPCHK(hipMalloc(&(ptr), (bytes))); guard_.v.push_back((void *)(ptr)); } while (0)
+// after a run of requests to a TlbMem (csrc/tlb_mem.h, which has printed the failing call): the one check
+#define MEMCHK(m) do { if ((m).failed()) return TLB_ERR_HIP; } while (0)
 
 // tlb_batch.cpp: one launch of the encode path on `st` (every entry point ends here)
 int tlb_launch(tlb_batch *b, const int16_t *d_pcm, int nframes, const uint8_t *d_xpad, const int32_t *d_xpad_len,
@@ -112,8 +114,9 @@ int decode_prepare(tlb_batch *b);
 int compare_prepare(tlb_batch *b);
 int compare_launch(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_dec_pcm, const tlb_frame_report *d_report, int nframes,
                    const tlb_compare_params *params, tlb_compare_record *d_record, void *hip_stream);
-// tlb_resample.cpp: the resampler state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); the legality of a
+// tlb_resample.cpp: the resampler's tables and state as the first real source makes them (waits for the device once); the resampler state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); the legality of a
 // stream's source with a new encoder rate (tlb_stream_reconfigure)
+int resample_prepare(tlb_batch *b);
 int resample_clear_streams(tlb_batch *b, int s0, int n);
 bool resample_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -29,11 +29,10 @@ int tlb_monitor_host(tlb_batch *b, const tlb_frame_report *report, const int16_t
     if (((uintptr_t)report | (uintptr_t)pcm | (uintptr_t)record) & 3u) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t slots = (size_t)nframes * (size_t)b->nstreams, rec_bytes = (size_t)b->nstreams * sizeof(tlb_monitor_record);
-    DevFree guard_;
-    tlb_frame_report *d_report = nullptr; int16_t *d_pcm = nullptr; tlb_monitor_record *d_record = nullptr;
-    DEVALLOC(d_report, slots * sizeof(tlb_frame_report));
-    DEVALLOC(d_record, rec_bytes);
-    if (pcm) DEVALLOC(d_pcm, slots * 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t));
+    TlbMem m;
+    tlb_frame_report *d_report = m.scratch<tlb_frame_report>(slots); tlb_monitor_record *d_record = m.scratch<tlb_monitor_record>((size_t)b->nstreams);
+    int16_t *d_pcm = pcm ? m.scratch<int16_t>(slots * 2 * TLB_SAMPLES_PER_FRAME) : nullptr;
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_report, report, slots * sizeof(tlb_frame_report), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_record, record, rec_bytes, hipMemcpyHostToDevice));
     if (pcm) HIPCHK(hipMemcpy(d_pcm, pcm, slots * 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyHostToDevice));

@@ -434,30 +434,20 @@ int tlb_node_shard_status(const tlb_node *nd, int shard, tlb_node_shard_info *in
 {
     if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return -TLB_ERR_ARG;
     const Shard &s = *nd->shards[(size_t)shard];
-    if (s.late) {                                                    // from the node's own record: its job still owns the shard's fields
-        if (info) {
-            memset(info, 0, sizeof *info);
-            info->shard = s.index; info->device = s.device; info->first = s.first; info->nstreams = s.n;
-            info->state = TLB_SHARD_LATE; info->last_err = s.kept.last_err;
-            info->failures = s.kept.failures; info->restarts = s.kept.restarts; info->lost_steps = s.kept.lost_steps;
-            memcpy(info->what, s.kept.what, sizeof info->what);
-            memcpy(info->device_name, s.device_name, sizeof info->device_name);
-            memcpy(info->pci, s.pci, sizeof info->pci); memcpy(info->uuid, s.uuid, sizeof info->uuid);
-            info->num_cu = s.num_cu; info->num_xcd = s.num_xcd; info->hbm_gb = s.hbm_gb;
-        }
-        return TLB_SHARD_LATE;
-    }
+    // a late shard is told from the node's own record (kept): its job still owns the shard's fields
+    const int state = s.late ? TLB_SHARD_LATE : s.live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN;
     if (info) {
         memset(info, 0, sizeof *info);
         info->shard = s.index; info->device = s.device; info->first = s.first; info->nstreams = s.n;
-        info->state = s.live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN; info->last_err = s.last_err;
-        info->failures = s.failures; info->restarts = s.restarts; info->lost_steps = s.lost_steps;
-        memcpy(info->what, s.what, sizeof info->what);
+        info->state = state; info->last_err = s.late ? s.kept.last_err : s.last_err;
+        info->failures = s.late ? s.kept.failures : s.failures; info->restarts = s.late ? s.kept.restarts : s.restarts;
+        info->lost_steps = s.late ? s.kept.lost_steps : s.lost_steps;
+        memcpy(info->what, s.late ? s.kept.what : s.what, sizeof info->what);
         memcpy(info->device_name, s.device_name, sizeof info->device_name);
         memcpy(info->pci, s.pci, sizeof info->pci); memcpy(info->uuid, s.uuid, sizeof info->uuid);
         info->num_cu = s.num_cu; info->num_xcd = s.num_xcd; info->hbm_gb = s.hbm_gb;
     }
-    return s.live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN;
+    return state;
 }
 // A fresh object for the block, made on the shard's own thread: its streams start "as a freshly started reference process" (tlb_stream_reset's
 // contract, for the whole block: no history, no pending frame, psy 2/4 state zero, the EDI senders re-initialised from now_s), with
@@ -577,8 +567,8 @@ const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream)
 int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params)
 {
     if (!nd || !params || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0 || nd->monitor != TLB_MONITOR_AUDIO) return TLB_ERR_ARG;
-    if (params->min_energy < 1 || params->corr_num <= 0 || params->corr_num > params->corr_den || params->corr_den > 1024) return TLB_ERR_ARG;
-    if (nd->compare) return params->min_energy == nd->cparams.min_energy && params->corr_num == nd->cparams.corr_num && params->corr_den == nd->cparams.corr_den ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    if (!tlb_compare_params_legal(params)) return TLB_ERR_ARG;
+    if (nd->compare) return tlb_compare_params_same(*params, nd->cparams) ? (int)TLB_OK : (int)TLB_ERR_ARG;
     const tlb_compare_params P = *params;
     const int rc = nd->all([P](Shard &s) { return s.tick ? tlb_tick_enable_compare(s.tick, &P) : (int)TLB_ERR_HIP; });
     if (!rc) { nd->cparams = P; nd->compare = true; }
@@ -623,12 +613,7 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
     if (!nd || stream < -1 || stream >= nd->nstreams || source_rate < 0 || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     bool any = false;
-    for (int k = s0; k < s1; k++) {
-        const long enc = nd->cfgs[(size_t)k].samplerate;
-        if (source_rate == 0 || source_rate == enc) continue;
-        if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
-        any = true;
-    }
+    if (int rc = tlb_source_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
     if (any && nd->short_reads) return TLB_ERR_ARG;
     for (Shard *s : nd->shards) {
         if (s->first >= s1 || s->first + s->n <= s0) continue;

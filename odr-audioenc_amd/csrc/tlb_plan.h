@@ -1,6 +1,7 @@
 // tlb_plan.h -- the ONE statement of what a block of streams becomes: which streams share a configuration record and which mono
 // streams share waves in pairs.  Used by tlb_create / tlb_stream_reconfigure (csrc/tlb_batch.cpp) and by the node level's planner
-// (tlb_node_plan_shard, csrc/tlb_node.cpp), so that the plan a caller is shown cannot drift from what the batch does.  Host C++ only.
+// (tlb_node_plan_shard, csrc/tlb_node.cpp), so that the plan a caller is shown cannot drift from what the batch does.  At the end, for
+// the same reason, the rules of the opt-in calls that batch, tick plane and node level all apply.  Host C++ only.
 #pragma once
 #include <stdint.h>
 
@@ -8,6 +9,7 @@
 
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
+#include "mp2_resample.h"
 
 // the knobs of toolame.h:13-48 that make a configuration record (the sixth, the PAD length of a frame, is per frame)
 static inline bool tlb_same_config(const tlb_stream_config &a, const tlb_stream_config &b)
@@ -55,3 +57,27 @@ static inline int tlb_plan_pairs(const std::vector<TlConfig> &configs, const std
 }
 // the kernel list a stream's model rides in: model 4 runs the psy-2 kernels on its own tables
 static inline int tlb_model_list(int psy) { return psy == 4 ? 2 : psy; }
+
+// ---- the opt-in rules the batch, the tick plane and the node level share ----
+// A source rate for the streams [s0, s1): every stream is checked before one is changed.  enc_rate(s) is the encoder rate of stream s.
+// A rate of 0 (off) or the encoder's own is no source.  Returns TLB_ERR_SAMPLERATE when some stream's (source, encoder) pair is no ratio the
+// resampler has, else 0; *any becomes true when some stream gets a real source (it is never cleared: ranges can be checked one after another).
+template <class EncRate> static inline int tlb_source_range(int s0, int s1, long source_rate, EncRate enc_rate, bool *any)
+{
+    for (int s = s0; s < s1; s++) {
+        const long enc = enc_rate(s);
+        if (source_rate == 0 || source_rate == enc) continue;
+        if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
+        *any = true;
+    }
+    return 0;
+}
+// the compare monitor's parameters: legal, and the same as the ones an earlier opt-in gave
+static inline bool tlb_compare_params_legal(const tlb_compare_params *p)
+{
+    return p && p->min_energy >= 1 && p->corr_num > 0 && p->corr_num <= p->corr_den && p->corr_den <= 1024;
+}
+static inline bool tlb_compare_params_same(const tlb_compare_params &a, const tlb_compare_params &b)
+{
+    return a.min_energy == b.min_energy && a.corr_num == b.corr_num && a.corr_den == b.corr_den;
+}

@@ -2,6 +2,7 @@
 // the need arithmetic (host only), the per-stream state (allocated by the first tlb_resample_set_source) and one launch of the kernel of
 // toolame_resample.hip through tl_kernels.h.  Host C++.  The tick plane (tlb_tick.cpp) queues it between its group's copy-in and ingest.
 #include "tlb_internal.h"
+#include "tlb_plan.h"
 #include "tl_resample_taps.inc"
 
 static_assert(sizeof tl_resample_taps_160_147 == 160 * TL_RS_TAPS * 2 && sizeof tl_resample_taps_3_2 == 3 * TL_RS_TAPS * 2, "table shapes");
@@ -34,20 +35,18 @@ int resample_clear_streams(tlb_batch *b, int s0, int n)
     return TLB_OK;
 }
 
-static int resample_prepare(tlb_batch *b)
+int resample_prepare(tlb_batch *b)
 {
     if (b->d_rs_state) return TLB_OK;
-    const size_t ns = (size_t)b->nstreams, sb = sizeof(uint32_t) * 2 * TL_RS_STATE_WORDS * ns;
-    uint32_t *st = nullptr; int32_t *ra = nullptr; int16_t *tp = nullptr;
-    hipError_t e = hipMalloc(&st, sb);
-    if (e == hipSuccess) e = hipMalloc(&ra, sizeof(int32_t) * ns);
-    if (e == hipSuccess) e = hipMalloc(&tp, sizeof tl_resample_taps_160_147 + sizeof tl_resample_taps_3_2);
-    if (e == hipSuccess) e = hipMemset(st, 0, sb);
-    if (e == hipSuccess) e = hipMemset(ra, 0, sizeof(int32_t) * ns);
-    if (e == hipSuccess) e = hipMemcpy(tp, tl_resample_taps_160_147, sizeof tl_resample_taps_160_147, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tp + 160 * TL_RS_TAPS, tl_resample_taps_3_2, sizeof tl_resample_taps_3_2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(st); (void)hipFree(ra); (void)hipFree(tp); HIPCHK(e); }
+    const size_t ns = (size_t)b->nstreams;
+    TlbMem m;
+    uint32_t *st = m.dev<uint32_t>(2 * TL_RS_STATE_WORDS * ns);
+    int32_t *ra = m.dev<int32_t>(ns);
+    int16_t *tp = m.scratch<int16_t>((160 + 3) * TL_RS_TAPS);
+    m.upload(tp, tl_resample_taps_160_147, sizeof tl_resample_taps_160_147);
+    m.upload(tp + 160 * TL_RS_TAPS, tl_resample_taps_3_2, sizeof tl_resample_taps_3_2);
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(b->mem);
     b->rs_rate.assign(ns, 0); b->rs_ratio.assign(ns, TL_RS_OFF); b->rs_pos.assign(ns, 0);
     b->d_rs_state = st; b->d_rs_ratio = ra; b->d_rs_taps = tp; b->rs_flip = 0;
     return TLB_OK;
@@ -80,12 +79,7 @@ int tlb_resample_set_source(tlb_batch *b, int stream, long source_rate)
     if (!b || stream < -1 || stream >= b->nstreams || source_rate < 0) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
     bool any = false;
-    for (int s = s0; s < s1; s++) {                                  // every stream is checked before one is changed
-        const long enc = encoder_rate(b, s);
-        if (source_rate == 0 || source_rate == enc) continue;
-        if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
-        any = true;
-    }
+    if (int rc = tlb_source_range(s0, s1, source_rate, [b](int s) { return encoder_rate(b, s); }, &any)) return rc;
     if (!any && !b->d_rs_state) return TLB_OK;                       // off, and never on: nothing to allocate or to clear
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
@@ -137,10 +131,9 @@ int tlb_resample_host(tlb_batch *b, const int16_t *source, int nframes, int16_t 
     if (!b || !source || !interleaved || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     const size_t bytes = (size_t)nframes * (size_t)b->nstreams * 2304 * sizeof(int16_t);
-    DevFree guard_;
-    int16_t *d_in = nullptr, *d_out = nullptr;
-    DEVALLOC(d_in, bytes);
-    DEVALLOC(d_out, bytes);
+    TlbMem m;
+    int16_t *d_in = m.scratch<int16_t>(bytes / 2), *d_out = m.scratch<int16_t>(bytes / 2);
+    MEMCHK(m);
     HIPCHK(hipMemcpy(d_in, source, bytes, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_out, interleaved, bytes, hipMemcpyHostToDevice));       // what the kernel does not write (behind a one-channel stream's 1152 samples) stays the caller's
     if (int rc = tlb_resample_device(b, d_in, nframes, d_out, nullptr)) return rc;

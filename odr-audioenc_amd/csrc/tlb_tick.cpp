@@ -1,5 +1,6 @@
 // tlb_tick.cpp -- the real-time loop body as one object (include/toolame_batch.h, tlb_tick_*).  Host C++ above the batch and egress entry points.
 #include "tlb_internal.h"
+#include "tlb_plan.h"
 
 // ------------------------------------------------------------------------------------------
 // The caller's real-time loop body as ONE call per tick (include/toolame_batch.h, tlb_tick_*): what AudioEnc::run() does for
@@ -69,7 +70,7 @@ struct tlb_tick {
 #endif
     int in_set = 0, out_set = 0;
     long waited = 0;                             // ticks whose results have been waited for (ticks: submitted)
-    std::vector<void *> pinned, dev;
+    TlbMem mem;                                  // owns every pinned and device buffer of the object and its groups (csrc/tlb_mem.h)
     hipStream_t s_in = nullptr, s_run = nullptr, s_out = nullptr;
     hipEvent_t ev0[3] = {}, ev1[3] = {};          // per output set: first copy-in queued / last copy-out done
     long ticks = 0;
@@ -99,13 +100,11 @@ void tlb_tick_destroy(tlb_tick *t)
         if (g.ev_out) (void)hipEventDestroy(g.ev_out);
         if (g.ev_mon) (void)hipEventDestroy(g.ev_mon);
     }
-    for (void *p : t->dev) (void)hipFree(p);
-    for (void *p : t->pinned) (void)hipHostFree(p);
     if (t->s_in) (void)hipStreamDestroy(t->s_in);
     if (t->s_run) (void)hipStreamDestroy(t->s_run);
     if (t->s_out) (void)hipStreamDestroy(t->s_out);
     for (int k = 0; k < 3; k++) { if (t->ev0[k]) (void)hipEventDestroy(t->ev0[k]); if (t->ev1[k]) (void)hipEventDestroy(t->ev1[k]); }
-    delete t;
+    delete t;                                    // (t->mem frees the buffers)
 }
 
 static int tick_create_impl(tlb_tick *t, int device, int nstreams, const tlb_stream_config *cfgs, const tlb_tick_config *tc)
@@ -146,47 +145,40 @@ static int tick_create_impl(tlb_tick *t, int device, int nstreams, const tlb_str
         n_frags += (size_t)G.n * (size_t)G.max_upf * (size_t)G.max_frags * (size_t)G.frag_stride;
     }
     HIPCHK(hipSetDevice(device));
-    auto pin = [&](size_t bytes) -> void * { void *p = nullptr; if (hipHostMalloc(&p, bytes ? bytes : 4, hipHostMallocDefault) != hipSuccess) return nullptr; memset(p, 0, bytes ? bytes : 4); t->pinned.push_back(p); return p; };
-    auto dev = [&](size_t bytes) -> void * { void *p = nullptr; if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr; (void)hipMemset(p, 0, bytes ? bytes : 4); t->dev.push_back(p); return p; };
+    TlbMem &m = t->mem;                                              // straight into the tick's owner: a failure here ends in tlb_tick_destroy
+    const size_t ns = (size_t)nstreams, xp = t->with_xpad ? ns : 0;
     uint8_t *h_msgs[3], *h_frames[3], *h_pkts[3], *h_frags[3]; int32_t *h_flen[3], *h_plen[3], *h_fraglen[3], *h_nfrag[3];
     for (int k = 0; k < 2; k++) {
-        t->h_inter[k] = (int16_t *)pin((size_t)nstreams * 2304 * sizeof(int16_t));
-        t->h_xpad[k] = (uint8_t *)pin(t->with_xpad ? (size_t)nstreams * TL_MAX_XPAD : 0);
-        t->h_xl[k] = (int32_t *)pin(t->with_xpad ? (size_t)nstreams * sizeof(int32_t) : 0);
-        if (!t->h_inter[k] || !t->h_xpad[k] || !t->h_xl[k]) return TLB_ERR_HIP;
+        t->h_inter[k] = m.pinned<int16_t>(ns * 2304);
+        t->h_xpad[k] = m.pinned<uint8_t>(xp * TL_MAX_XPAD); t->h_xl[k] = m.pinned<int32_t>(xp);
     }
     for (int k = 0; k < 3; k++) {
-        t->h_peaks[k] = (int16_t *)pin((size_t)nstreams * 2 * sizeof(int16_t));
-        t->h_silence[k] = (uint32_t *)pin((size_t)nstreams * sizeof(uint32_t));
-        h_msgs[k] = (uint8_t *)pin(n_msgs);
-        h_frames[k] = (uint8_t *)pin(n_frames); h_flen[k] = (int32_t *)pin((size_t)nstreams * sizeof(int32_t));
-        h_pkts[k] = (uint8_t *)pin(n_pkts); h_plen[k] = (int32_t *)pin(n_slots * sizeof(int32_t));
-        h_frags[k] = (uint8_t *)pin(n_frags); h_fraglen[k] = (int32_t *)pin(n_fragslots * sizeof(int32_t)); h_nfrag[k] = (int32_t *)pin(n_slots * sizeof(int32_t));
-        if (!t->h_peaks[k] || !t->h_silence[k] || !h_msgs[k] || !h_frames[k] || !h_flen[k] || !h_pkts[k] || !h_plen[k] ||
-            !h_frags[k] || !h_fraglen[k] || !h_nfrag[k]) return TLB_ERR_HIP;
+        t->h_peaks[k] = m.pinned<int16_t>(ns * 2); t->h_silence[k] = m.pinned<uint32_t>(ns);
+        h_msgs[k] = m.pinned<uint8_t>(n_msgs);
+        h_frames[k] = m.pinned<uint8_t>(n_frames); h_flen[k] = m.pinned<int32_t>(ns);
+        h_pkts[k] = m.pinned<uint8_t>(n_pkts); h_plen[k] = m.pinned<int32_t>(n_slots);
+        h_frags[k] = m.pinned<uint8_t>(n_frags); h_fraglen[k] = m.pinned<int32_t>(n_fragslots); h_nfrag[k] = m.pinned<int32_t>(n_slots);
     }
+    MEMCHK(m);
     std::vector<tlb_edi_state> st0;
     size_t o_frames = 0, o_slots = 0, o_pkts = 0, o_frags = 0, o_fragslots = 0, o_msgs = 0;
     for (auto &G : t->groups) {
         const size_t n = (size_t)G.n, slots = n * (size_t)G.max_upf;
-        G.d_inter = (int16_t *)dev(n * 2304 * 2); G.d_pcm = (int16_t *)dev(n * 2304 * 2); G.d_peaks = (int16_t *)dev(n * 4);
-        G.d_xpad = (uint8_t *)dev(t->with_xpad ? n * TL_MAX_XPAD : 0); G.d_xl = (int32_t *)dev(t->with_xpad ? n * 4 : 0);
-        G.d_frames = (uint8_t *)dev(n * (size_t)G.out_stride); G.d_flen = (int32_t *)dev(n * 4);
-        G.d_state = (tlb_edi_state *)dev(n * sizeof(tlb_edi_state));
-        G.d_pkts = (uint8_t *)dev(slots * (size_t)G.af_stride); G.d_plen = (int32_t *)dev(slots * 4);
-        G.d_pseq = (uint16_t *)dev(n * 2);
-        G.d_msgs = (uint8_t *)dev(slots * (size_t)G.msg_stride); G.d_silence = (uint32_t *)dev(n * 4);
-        if (!G.d_msgs || !G.d_silence) return TLB_ERR_HIP;
-        for (int k = 0; k < 3; k++) G.h_msgs[k] = h_msgs[k] + o_msgs;
-        o_msgs += slots * (size_t)G.msg_stride;
-        G.d_frags = (uint8_t *)dev(slots * (size_t)G.max_frags * (size_t)G.frag_stride); G.d_fraglen = (int32_t *)dev(slots * (size_t)G.max_frags * 4); G.d_nfrag = (int32_t *)dev(slots * 4);
-        if (!G.d_inter || !G.d_pcm || !G.d_peaks || !G.d_xpad || !G.d_xl || !G.d_frames || !G.d_flen || !G.d_state || !G.d_pkts || !G.d_plen || !G.d_pseq ||
-            !G.d_frags || !G.d_fraglen || !G.d_nfrag) return TLB_ERR_HIP;
+        G.d_inter = m.dev<int16_t>(n * 2304); G.d_pcm = m.dev<int16_t>(n * 2304); G.d_peaks = m.dev<int16_t>(n * 2);
+        G.d_xpad = m.dev<uint8_t>(t->with_xpad ? n * TL_MAX_XPAD : 0); G.d_xl = m.dev<int32_t>(t->with_xpad ? n : 0);
+        G.d_frames = m.dev<uint8_t>(n * (size_t)G.out_stride); G.d_flen = m.dev<int32_t>(n);
+        G.d_state = m.dev<tlb_edi_state>(n);
+        G.d_pkts = m.dev<uint8_t>(slots * (size_t)G.af_stride); G.d_plen = m.dev<int32_t>(slots);
+        G.d_pseq = m.dev<uint16_t>(n);
+        G.d_msgs = m.dev<uint8_t>(slots * (size_t)G.msg_stride); G.d_silence = m.dev<uint32_t>(n);
+        G.d_frags = m.dev<uint8_t>(slots * (size_t)G.max_frags * (size_t)G.frag_stride); G.d_fraglen = m.dev<int32_t>(slots * (size_t)G.max_frags); G.d_nfrag = m.dev<int32_t>(slots);
+        MEMCHK(m);
         for (int k = 0; k < 3; k++) {
+            G.h_msgs[k] = h_msgs[k] + o_msgs;
             G.h_frames[k] = h_frames[k] + o_frames; G.h_flen[k] = h_flen[k] + G.first; G.h_pkts[k] = h_pkts[k] + o_pkts; G.h_plen[k] = h_plen[k] + o_slots;
             G.h_frags[k] = h_frags[k] + o_frags; G.h_fraglen[k] = h_fraglen[k] + o_fragslots; G.h_nfrag[k] = h_nfrag[k] + o_slots;
         }
-        o_frames += n * (size_t)G.out_stride; o_slots += slots; o_pkts += slots * (size_t)G.af_stride;
+        o_frames += n * (size_t)G.out_stride; o_slots += slots; o_pkts += slots * (size_t)G.af_stride; o_msgs += slots * (size_t)G.msg_stride;
         o_fragslots += slots * (size_t)G.max_frags; o_frags += slots * (size_t)G.max_frags * (size_t)G.frag_stride;
         st0.resize(n);
         for (size_t i = 0; i < n; i++) tlb_edi_state_init(&st0[i], tc->now_s, tc->delay_ms, tc->tist, tc->tai_utc_offset);
@@ -235,25 +227,19 @@ int tlb_tick_enable_short_reads(tlb_tick *t)
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
     const size_t ns = (size_t)t->nstreams;
-    auto pin = [&](size_t bytes) -> void * { void *p = nullptr; if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr; memset(p, 0, bytes); t->pinned.push_back(p); return p; };
-    for (int k = 0; k < 2; k++) {
-        if (!(t->h_valid[k] = (int32_t *)pin(ns * sizeof(int32_t)))) return TLB_ERR_HIP;
-        for (size_t i = 0; i < ns; i++) t->h_valid[k][i] = TLB_SAMPLES_PER_FRAME;
-    }
-    for (int k = 0; k < 3; k++) {
-        t->h_underrun_ms[k] = (uint32_t *)pin(ns * sizeof(uint32_t)); t->h_underruns[k] = (uint32_t *)pin(ns * sizeof(uint32_t));
-        if (!t->h_underrun_ms[k] || !t->h_underruns[k]) return TLB_ERR_HIP;
-    }
-    for (auto &G : t->groups) {
-        void *p[3] = {};
-        for (int k = 0; k < 3; k++) {
-            HIPCHK(hipMalloc(&p[k], (size_t)G.n * 4));
-            t->dev.push_back(p[k]);
-            HIPCHK(hipMemset(p[k], 0, (size_t)G.n * 4));
-        }
-        G.d_valid = (int32_t *)p[0]; G.d_underrun_ms = (uint32_t *)p[1]; G.d_underruns = (uint32_t *)p[2];
-    }
-    HIPCHK(hipDeviceSynchronize());                                  // the memsets ran on the null stream, the tick's streams do not wait for it
+    // The opt-in pattern, all or nothing: stage every buffer in a local owner and the groups' fields in a copy of the groups, run
+    // the batches' *_prepare, settle, commit -- and only then do the object's fields and the option's flag change.
+    TlbMem m;
+    std::vector<TickGroup> gs = t->groups;
+    int32_t *h_valid[2]; uint32_t *h_ms[3], *h_n[3];
+    for (int k = 0; k < 2; k++) h_valid[k] = m.pinned<int32_t>(ns);
+    for (int k = 0; k < 3; k++) { h_ms[k] = m.pinned<uint32_t>(ns); h_n[k] = m.pinned<uint32_t>(ns); }
+    for (auto &G : gs) { G.d_valid = m.dev<int32_t>((size_t)G.n); G.d_underrun_ms = m.dev<uint32_t>((size_t)G.n); G.d_underruns = m.dev<uint32_t>((size_t)G.n); }
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(t->mem);
+    t->groups.swap(gs);
+    for (int k = 0; k < 2; k++) for (size_t i = 0; i < ns; i++) h_valid[k][i] = TLB_SAMPLES_PER_FRAME;
+    memcpy(t->h_valid, h_valid, sizeof h_valid); memcpy(t->h_underrun_ms, h_ms, sizeof h_ms); memcpy(t->h_underruns, h_n, sizeof h_n);
     t->short_reads = true;
     return TLB_OK;
 }
@@ -266,24 +252,21 @@ int tlb_tick_enable_monitor(tlb_tick *t, int what)
     if (t->broken) return TLB_ERR_HIP;
     if (t->monitor) return t->monitor == what ? (int)TLB_OK : (int)TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
-    const size_t ns = (size_t)t->nstreams, pcm_bytes = 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t);
-    auto pin = [&](size_t bytes) -> void * { void *p = nullptr; if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr; memset(p, 0, bytes); t->pinned.push_back(p); return p; };
-    for (int k = 0; k < 3; k++) {
-        t->h_record[k] = (tlb_monitor_record *)pin(ns * sizeof(tlb_monitor_record));
-        t->h_listen[k] = (int16_t *)pin(pcm_bytes);
-        if (!t->h_record[k] || !t->h_listen[k]) return TLB_ERR_HIP;
-    }
-    for (auto &G : t->groups) {
-        const size_t n = (size_t)G.n;
-        auto dev = [&](size_t bytes) -> void * { void *p = nullptr; if (hipMalloc(&p, bytes) != hipSuccess) return nullptr; t->dev.push_back(p); return hipMemset(p, 0, bytes) == hipSuccess ? p : nullptr; };
+    const size_t ns = (size_t)t->nstreams, pcm = 2 * TLB_SAMPLES_PER_FRAME;
+    for (auto &G : t->groups) if (!G.ev_mon) HIPCHK(hipEventCreateWithFlags(&G.ev_mon, hipEventDisableTiming));   // (a refused attempt keeps them for the next)
+    TlbMem m;
+    std::vector<TickGroup> gs = t->groups;
+    tlb_monitor_record *h_record[3]; int16_t *h_listen[3];
+    for (int k = 0; k < 3; k++) { h_record[k] = m.pinned<tlb_monitor_record>(ns); h_listen[k] = m.pinned<int16_t>(pcm); }
+    for (auto &G : gs) {
         if (int rc = decode_prepare(G.b)) return rc;
-        G.d_report = (tlb_frame_report *)dev(n * sizeof(tlb_frame_report));
-        G.d_record = (tlb_monitor_record *)dev(n * sizeof(tlb_monitor_record));
-        if (what == TLB_MONITOR_AUDIO) G.d_mpcm = (int16_t *)dev(n * pcm_bytes);
-        if (!G.d_report || !G.d_record || (what == TLB_MONITOR_AUDIO && !G.d_mpcm)) return TLB_ERR_HIP;
-        if (!G.ev_mon) HIPCHK(hipEventCreateWithFlags(&G.ev_mon, hipEventDisableTiming));
+        G.d_report = m.dev<tlb_frame_report>((size_t)G.n); G.d_record = m.dev<tlb_monitor_record>((size_t)G.n);
+        if (what == TLB_MONITOR_AUDIO) G.d_mpcm = m.dev<int16_t>((size_t)G.n * pcm);
     }
-    HIPCHK(hipDeviceSynchronize());                                  // the memsets ran on the null stream, the tick's streams do not wait for it
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(t->mem);
+    t->groups.swap(gs);
+    memcpy(t->h_record, h_record, sizeof h_record); memcpy(t->h_listen, h_listen, sizeof h_listen);
     t->monitor = what;
     return TLB_OK;
 }
@@ -293,27 +276,22 @@ const tlb_monitor_record *tlb_tick_monitor(const tlb_tick *t) { return t && t->m
 int tlb_tick_enable_compare(tlb_tick *t, const tlb_compare_params *params)
 {
     if (!t || !params || t->finished || t->ticks > 0 || t->monitor != TLB_MONITOR_AUDIO) return TLB_ERR_ARG;
-    if (params->min_energy < 1 || params->corr_num <= 0 || params->corr_num > params->corr_den || params->corr_den > 1024) return TLB_ERR_ARG;
+    if (!tlb_compare_params_legal(params)) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
-    if (t->compare) return params->min_energy == t->cparams.min_energy && params->corr_num == t->cparams.corr_num && params->corr_den == t->cparams.corr_den ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    if (t->compare) return tlb_compare_params_same(*params, t->cparams) ? (int)TLB_OK : (int)TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
-    const size_t ns = (size_t)t->nstreams;
-    for (int k = 0; k < 3; k++) {
-        void *p = nullptr;
-        if (hipHostMalloc(&p, ns * sizeof(tlb_compare_record), hipHostMallocDefault) != hipSuccess) return TLB_ERR_HIP;
-        memset(p, 0, ns * sizeof(tlb_compare_record));
-        t->pinned.push_back(p);
-        t->h_crecord[k] = (tlb_compare_record *)p;
-    }
-    for (auto &G : t->groups) {
+    TlbMem m;
+    std::vector<TickGroup> gs = t->groups;
+    tlb_compare_record *h_crecord[3];
+    for (int k = 0; k < 3; k++) h_crecord[k] = m.pinned<tlb_compare_record>((size_t)t->nstreams);
+    for (auto &G : gs) {
         if (int rc = compare_prepare(G.b)) return rc;
-        void *p = nullptr;
-        HIPCHK(hipMalloc(&p, (size_t)G.n * sizeof(tlb_compare_record)));
-        t->dev.push_back(p);
-        HIPCHK(hipMemset(p, 0, (size_t)G.n * sizeof(tlb_compare_record)));
-        G.d_crecord = (tlb_compare_record *)p;
+        G.d_crecord = m.dev<tlb_compare_record>((size_t)G.n);
     }
-    HIPCHK(hipDeviceSynchronize());                                  // the memsets ran on the null stream, the tick's streams do not wait for it
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(t->mem);
+    t->groups.swap(gs);
+    memcpy(t->h_crecord, h_crecord, sizeof h_crecord);
     t->cparams = *params;
     t->compare = true;
     return TLB_OK;
@@ -339,29 +317,26 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || source_rate < 0 || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     bool any = false;
-    for (auto &G : t->groups)                                        // every stream is checked before one is changed
-        for (int k = 0; k < G.n; k++) {
-            if (stream >= 0 && stream != G.first + k) continue;
-            const long enc = G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate;
-            if (source_rate == 0 || source_rate == enc) continue;
-            if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
-            any = true;
-        }
+    std::vector<char> real(t->groups.size(), 0);                     // per group: the call gives some stream of it a real source
+    for (size_t g = 0; g < real.size(); g++) {                       // every stream is checked before one is changed
+        const TickGroup &G = t->groups[g];
+        const int s0 = stream < 0 ? 0 : stream - G.first, s1 = stream < 0 ? G.n : s0 + 1;
+        if (s0 < 0 || s0 >= G.n) continue;
+        bool r = false;
+        if (int rc = tlb_source_range(s0, s1, source_rate, [&G](int k) { return (long)G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate; }, &r)) return rc;
+        real[g] = r; any |= r;
+    }
     if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
     if (any && t->short_reads) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
-    if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer is made before one is committed
-        std::vector<void *> made;
-        hipError_t e = hipSuccess;
-        for (auto &G : t->groups) {
-            void *p = nullptr;
-            if ((e = hipMalloc(&p, (size_t)G.n * 2304 * sizeof(int16_t))) != hipSuccess) break;
-            made.push_back(p);
-            if ((e = hipMemset(p, 0, (size_t)G.n * 2304 * sizeof(int16_t))) != hipSuccess) break;
-        }
-        if (e == hipSuccess) e = hipDeviceSynchronize();             // the memsets ran on the null stream, the tick's streams do not wait for it
-        if (e != hipSuccess) { for (void *p : made) (void)hipFree(p); HIPCHK(e); }
-        for (size_t g = 0; g < t->groups.size(); g++) { t->groups[g].d_rs = (int16_t *)made[g]; t->dev.push_back(made[g]); }
+    if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer, and the resampler of the batches that get
+        TlbMem m;                                                    // a source, before anything is committed or a stream is changed
+        std::vector<TickGroup> gs = t->groups;
+        for (auto &G : gs) G.d_rs = m.dev<int16_t>((size_t)G.n * 2304);
+        for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = resample_prepare(gs[g].b)) return rc;
+        if (!m.settle()) return TLB_ERR_HIP;
+        m.commit(t->mem);
+        t->groups.swap(gs);
     }
     int rc = TLB_OK;
     for (auto &G : t->groups) {
@@ -512,12 +487,12 @@ int tlb_debug_tick_cross_from(tlb_tick *t, int a, int b, int nth)
     if (!t || nth < 0 || a < 0 || b < 0 || a >= t->nstreams || b >= t->nstreams || a == b || t->group_of[(size_t)a] != t->group_of[(size_t)b]) return TLB_ERR_ARG;
     if (!t->d_cross_tmp) {
         HIPCHK(hipSetDevice(t->device));
-        void *p = nullptr;
         size_t widest = 0;                                           // one buffer for every later call: any group's slot fits
         for (auto &G : t->groups) if ((size_t)G.out_stride > widest) widest = (size_t)G.out_stride;
-        HIPCHK(hipMalloc(&p, widest + 16));
-        t->dev.push_back(p);
-        t->d_cross_tmp = (uint8_t *)p;
+        TlbMem m;
+        t->d_cross_tmp = m.scratch<uint8_t>(widest + 16);
+        MEMCHK(m);
+        m.commit(t->mem);
     }
     t->cross_nth = nth; t->cross_a = a; t->cross_b = b; t->cross_on = false;
     return TLB_OK;

@@ -77,6 +77,7 @@ def load_fault_library():
         if hasattr(L, "tlb_debug_tick_cross_from"):
             L.tlb_debug_tick_cross_from.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.tlb_debug_node_stall_next.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.tlb_debug_alloc_fail_next.argtypes = [C.c_int]
         _fault_lib = L
     return _fault_lib
 
