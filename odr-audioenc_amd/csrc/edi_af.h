@@ -166,9 +166,7 @@ TL_FN void tl_edi_af_packet(const TlEdiArgs &A, int s, int v)
         uint32_t acc = 0;
         const uint32_t p0 = (uint32_t)lane * C;
         uint32_t r = lane == 0 ? 0xffffu : 0u;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (uint32_t wi = 0; wi < 8; wi++) {
             uint32_t word = 0;
             if (4 * wi < C) {
@@ -201,9 +199,7 @@ TL_FN void tl_edi_af_packet(const TlEdiArgs &A, int s, int v)
         const uint32_t crc = (TL_WAVE_XOR_U32(part) ^ 0xffffu) & 0xffffu;
         TL_LANES_BEGIN
         const uint32_t p0 = (uint32_t)lane * C;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (uint32_t wi = 0; wi < 8; wi++) {
             const uint32_t q = p0 + 4 * wi;
             if (4 * wi < C && q < body + 2) {

@@ -82,9 +82,7 @@ TL_FN void tl_edi_pft_packet(const TlPftArgs &A, const TlPftTables &R, int s, in
             if (lane < TL_PFT_PARITY) {
                 uint32_t acc = 0;
                 for (uint32_t i0 = 0; i0 < k; i0 += 8) {             // eight independent products per round trip
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                     for (uint32_t q = 0; q < 8; q++) {
                         const uint32_t i = i0 + q, pos = ci * k + i;
                         const uint32_t d = (i < k && pos < l) ? af[pos] : 0u;

@@ -90,18 +90,6 @@ TL_FN double tl_mask_term_k(const TlMaskK &k, double dz, double av, double g, do
     const uint32_t hi = TL_SELECT(in, (uint32_t)(tu >> 32), k.far_hi);
     return tl_u2d(((uint64_t)hi << 32) | (tu & 0xffffffffull));
 }
-// 1 for a negative x, else 0.  On the device one shift of the high word, opaque to the compiler (which otherwise folds it into the
-// address arithmetic that follows as shift + and + add: three instructions where shift + shift-add do).
-TL_FN int tl_sign_bit(double x)
-{
-#ifdef TL_EMULATE
-    return (int)(tl_d2u(x) >> 63);
-#else
-    int r;
-    asm("v_lshrrev_b32 %0, 31, %1" : "=v"(r) : "v"((uint32_t)(tl_d2u(x) >> 32)));
-    return r;
-#endif
-}
 // The same term without a select for its shape.  dzp = masker bark - line bark = -dz (exactly: negation commutes with rounding).
 //  * which pair of slopes (inner G, outer H): dz < 0 -> (g, 17), else (17, n) -- the 16-byte window of the masker's record at
 //    &g + (dzp < 0): one address computed from the sign bit, one LDS read.  At dz = 0 either window serves (both products are 0).
@@ -159,13 +147,9 @@ TL_FN void tl_mask_spans(const TlMasker *mk, int nm, int ntone, double blo, doub
         uint32_t m = 0;
         for (int t8 = 0; t8 < 32 && tb + t8 < nm; t8 += 8) {
             double mb[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) mb[q] = mk[tb + t8 + q].bark;              // entries past nm (< TL_MASKER_MAX) are masked below
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) m |= (mb[q] > blo && mb[q] <= bhi) ? 1u << (t8 + q) : 0u;
         }
         const int left = nm - tb, tleft = ntone - tb;
@@ -188,9 +172,7 @@ TL_FN void tl_mask_spans_sorted(const double *TL_RESTRICT mb, int ntone, int nno
 {
     int tl = 0, th = 0, nl = 0, nh = 0;
     const double *nbk = mb + ntone;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int step = STEPS_T > STEPS_N ? STEPS_T : STEPS_N; step; step >>= 1) {
         const bool dt = step <= STEPS_T, dn = step <= STEPS_N;
         const int qtl = tl + step, qth = th + step, qnl = nl + step, qnh = nh + step;

@@ -32,10 +32,8 @@ TL_FN void tl_filterbank(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, const
                 L(xb)[8 * b + ((0 - j) & 7)] = c < nch ? w.u.fbk.pcm[c][TL_HIST + 32 * b + 31 - yb - 64 * j] : 0;
             }
         TL_LANES_END
-        TlMainLds::YpRows yp = w.yp_rows();
-#ifndef TL_EMULATE
+        TlMainLds::YpRows yp = w.yp;
 #pragma unroll
-#endif
         for (int b0 = 0; b0 < 36; b0 += FB) {
             TL_LANES_BEGIN
             const int c = lane & 1, i = lane >> 1;
@@ -47,25 +45,17 @@ TL_FN void tl_filterbank(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, const
                 // the batch's new samples (two per block) and its first coefficients are all requested before the first block is computed
                 int na[FB], nb[FB];
                 double cf[8], ta[FB];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int bb = 0; bb < FB; bb++) {
                     // X[k] = pcm[t0 + 31 - k], t0 = index of the block's first new sample
                     na[bb] = w.u.fbk.pcm[c][TL_HIST + 32 * (b0 + bb) + 31 - ya];
                     nb[bb] = w.u.fbk.pcm[c][TL_HIST + 32 * (b0 + bb) + 31 - yb];
                 }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int j = 0; j < 8; j++) cf[j] = enw_s[ya + 64 * j];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int bb = 0; bb < FB; bb++) { TL_KEEP(na[bb]); TL_KEEP(nb[bb]); }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int bb = 0; bb < FB; bb++) {
                     const int b = b0 + bb, q = 8 * (b & 1), h = b >> 1;
                     L(xa)[q + (h & 7)] = na[bb];
@@ -73,13 +63,9 @@ TL_FN void tl_filterbank(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, const
                     for (int j = 1; j < 8; j++) t += (double)L(xa)[q + ((h - j) & 7)] * cf[j];
                     ta[bb] = t;
                 }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int j = 0; j < 8; j++) cf[j] = enw_s[yb + 64 * j];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int bb = 0; bb < FB; bb++) {
                     const int b = b0 + bb, q = 8 * (b & 1), h = b >> 1;
                     L(xb)[q + (h & 7)] = nb[bb];
@@ -107,16 +93,7 @@ TL_FN void tl_filterbank(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, const
             for (int bb = 0; bb < FB; bb++) L(part)[bb] = acc[bb];
             TL_LANES_END
             PA(double, oth, FB);
-#ifdef TL_EMULATE
-            for (int lane = 0; lane < 64; ++lane)
-                for (int bb = 0; bb < FB; bb++) oth[lane][bb] = part[2 * (31 - (lane >> 1)) + (lane & 1)][bb];
-#else
-            {
-                const int lane_ = (int)(threadIdx.x & 63u), partner = 2 * (31 - (lane_ >> 1)) + (lane_ & 1);
-#pragma unroll
-                for (int bb = 0; bb < FB; bb++) oth[bb] = __shfl(part[bb], partner, 64);
-            }
-#endif
+            TL_MIRROR_SB_F64(oth, part, FB);
             // s[i] = s0 + s1 on the lanes of the even chains, s[31 - i] = s0 - s1 on the others: two BRANCHES, so that each half of the wave
             // runs one addition per block under its own execution mask -- as selects both results are computed for every lane and two
             // v_cndmask per block pick one (4 instructions per block against 1 + 1)

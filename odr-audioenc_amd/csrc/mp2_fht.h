@@ -17,9 +17,7 @@
 TL_FN void tl_fht_head(double (&e)[16], const double (*TL_RESTRICT tw)[4])
 {
     const double SQRT2 = 1.4142135623730951454746218587388284504414;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int g = 0; g < 16; g += 4) {                               // fft.c:1092-1102
         const double f1 = e[g] - e[g + 1], f0 = e[g] + e[g + 1], f3 = e[g + 2] - e[g + 3], f2 = e[g + 2] + e[g + 3];
         e[g + 2] = f0 - f2; e[g] = f0 + f2; e[g + 3] = f1 - f3; e[g + 1] = f1 + f3;
@@ -48,9 +46,7 @@ TL_FN int tl_rev6(int lane) { int r = 0; for (int b = 0; b < 6; b++) r |= ((lane
 TL_FN void tl_fht_store(double *x, int lane, const double (&e)[16])
 {
     const int l = tl_rev6(lane), base = ((16 * l) ^ (l >> 1)) << 3;  // FX(16*l + t) = base ^ t for t < 16 (as byte offsets: tl_fht_at)
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int t = 0; t < 16; t++) *tl_fht_at(x, base ^ (t << 3)) = e[t];
 }
 // Twiddles (c1,s1,c2,s2) of the (up to) two general butterflies a lane runs in pass K, and where the butterflies are (TlTables::fht_fg_lane:
@@ -141,26 +137,16 @@ TL_FN void tl_psy_spectrum(TlPsyLds &w, const TlTables *TL_RESTRICT T, const TlP
         // the sixteen PCM samples are this unit's first touch of its input (HBM, not L2): all of them are requested before anything is
         // used; the window's coefficients (L2) follow in two batches of eight (sixteen doubles more in flight would spill)
         int vs[16];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 16; it++) vs[it] = it < 3 ? hs[64 * it] : cs[64 * it];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 16; it++) TL_KEEP(vs[it]);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int half = 0; half < 16; half += 8) {
             double h[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) h[q] = hann[lane + 64 * (half + q)];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) {
                 const int it = half + q;
                 const int r4 = ((it & 1) << 3) | ((it & 2) << 1) | ((it & 4) >> 1) | ((it & 8) >> 3);
@@ -187,9 +173,7 @@ TL_FN void tl_psy_spectrum(TlPsyLds &w, const TlTables *TL_RESTRICT T, const TlP
         constexpr int q1 = TL_FX(256), q2 = TL_FX(512), q3 = TL_FX(768);
         PA(double, fv, 8); PA(double, gv, 8);
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 2; it++) {
             const int g = lane + 64 * it;                            // general butterflies i = 1 + g (g < 127); g = 127: the trivial one
             // (byte offsets; the table's entry 127 of this pass is the trivial butterfly: f0 at 0, g0 at FX(kx))
@@ -200,9 +184,7 @@ TL_FN void tl_psy_spectrum(TlPsyLds &w, const TlTables *TL_RESTRICT T, const TlP
         TL_LANES_END
         TL_LANES_BEGIN
         const double SQRT2 = 1.4142135623730951454746218587388284504414;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 2; it++) {
             const int g = lane + 64 * it;
             const double fi0 = L(fv)[4 * it], fi1 = L(fv)[4 * it + 1], fi2 = L(fv)[4 * it + 2], fi3 = L(fv)[4 * it + 3];

@@ -68,16 +68,10 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
         for (int gr = 0; gr < 3; gr++) {
             PV(double, jm);
             TL_LANES_BEGIN L(jm) = 0.0; TL_LANES_END
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int j = 11; j >= 0; j--) {
                 PV(double, other);
-#ifdef TL_EMULATE
-                for (int lane = 0; lane < 64; ++lane) other[lane] = smp[lane ^ 1][gr * 12 + j];
-#else
-                other = tld_swap1_f64(smp[gr * 12 + j]);
-#endif
+                TL_SWAP1_F64(other, , smp, [gr * 12 + j]);
                 TL_LANES_BEGIN
                 double t = fabs(.5 * (L(smp)[gr * 12 + j] + L(other)));     // ch0 lane: .5*(L+R)
                 if (j == 11 || t > L(jm)) L(jm) = t;
@@ -184,14 +178,10 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
         if (lane < 2 * sblimit) {
             const int ln = L(a_ln), maxAlloc = (1 << L(a_nbal)) - 1;
             double sv[15];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 15; q++) sv[q] = B->snr_line[ln][q];
             int n1 = 0, n2 = 0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 15; q++) {
                 const bool inr = q < maxAlloc - 1;
                 n1 += (inr && !((sv[q] - L(a_smr)) >= 0.0)) ? 1 : 0;
@@ -340,23 +330,17 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
             }
             TL_LANES_END
             const int rounds = (q_n + 15) >> 4;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int gr = 0; gr < 3; gr++) {
                 TL_LANES_BEGIN
                 if (L(q_ba)) {                                          // the granule's samples and scalefactor to the cell's block: seven 16-byte stores
                     TlQGran *blk = &qg[L(q_rank)];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                     for (int j = 0; j < 12; j += 2) TL_ST2(&blk->s[j], L(smp)[gr * 12 + j], L(smp)[gr * 12 + j + 1]);
                     TL_ST2(&blk->sf, L(q_sf)[gr], L(q_rsf)[gr]);
                 }
                 TL_LANES_END
-#ifndef TL_EMULATE
 #pragma nounroll
-#endif
                 for (int k = 0; k < rounds; k++) {
                     TL_LANES_BEGIN
                     const int cell = 16 * k + (lane >> 2), j = lane & 3;
@@ -391,20 +375,14 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
                 }
             }
         } else {
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int r = 0; r < 12; r++) {
             const int gr = r >> 2, j0 = (r & 3) * 3;
             PA(double, oth, 3);
-#ifdef TL_EMULATE
-            for (int lane = 0; lane < 64; ++lane) for (int x = 0; x < 3; x++) oth[lane][x] = smp[lane ^ 1][gr * 12 + j0 + x];
-#else
             if (any_joint) {
 #pragma unroll
-                for (int x = 0; x < 3; x++) oth[x] = tld_swap1_f64(smp[gr * 12 + j0 + x]);
-            } else { oth[0] = oth[1] = oth[2] = 0.0; }
-#endif
+                for (int x = 0; x < 3; x++) TL_SWAP1_F64(oth, [x], smp, [gr * 12 + j0 + x]);
+            } else { TL_SPLAT(oth, [0], 0.0); TL_SPLAT(oth, [1], 0.0); TL_SPLAT(oth, [2], 0.0); }      // (no lane reads them then)
             TL_LANES_BEGIN
             const int c = lane & 1, sb = lane >> 1;
             unsigned v[3] = {0, 0, 0};
@@ -461,13 +439,9 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
             const uint16_t *xt = &K->crc_xpow[e0];
             const unsigned v = preset ? 0xffu : ((frame[byte >> 2] >> (24 - 8 * (byte & 3))) & 0xffu) >> (8 - cnt);
             unsigned x8[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int k = 0; k < 8; k++) x8[k] = xt[k];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int k = 0; k < 8; k++) acc ^= (0u - ((v >> k) & 1u)) & x8[k];            // bits past cnt are zero
         }
         L(part) = acc;
@@ -514,9 +488,7 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
         unsigned xp = K->crc8_xpow[e0 < 0 ? 0 : e0 > 319 ? 319 : e0];
         unsigned acc = 0;
         const unsigned rb = L(rcrc);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int b = 0; b < 9; b++) {                                // acc = rec(x) * x^(8 + after) mod P, shift-and-add in GF(2)
             acc ^= ((rb >> b) & 1u) ? xp : 0u;
             xp = ((xp << 1) & 0xffu) ^ ((xp & 0x80u) ? 0x1Du : 0u);
@@ -674,9 +646,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
         L(a_smr) = live ? w.smr[c][sb] : 0.0;
         TL_LANES_END
         int adb[2];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int u = 0; u < 2; u++) {
             lg_frame[u] = C->frame_bytes + padding[u];                                       // availbits.c:64
             adb[u] = lg_frame[u] * 8 - (C->dab_ext * 8 + (xpad_len[u] ? xpad_len[u] : 2) * 8);    // toolame.c:292-301
@@ -708,9 +678,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
     TL_WAVE_EXSCAN_I32(o_scf, f_scf); TL_WAVE_EXSCAN_I32(o_smp, f_smp);
     const int s_ba = TL_WAVE_SUM_I32(f_ba), s_sel = TL_WAVE_SUM_I32(f_sel), s_scf = TL_WAVE_SUM_I32(f_scf), s_smp = TL_WAVE_SUM_I32(f_smp);
     int p_sel[2], p_scf[2], p_smp[2], n_smp[2];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int u = 0; u < 2; u++) {
         const int sh = 16 * u;
         p_sel[u] = 48 + ((s_ba >> sh) & 0xffff); p_scf[u] = p_sel[u] + ((s_sel >> sh) & 0xffff); p_smp[u] = p_scf[u] + ((s_scf >> sh) & 0xffff);
@@ -757,9 +725,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
         L(q_pos) = (c ? p_smp[1] : p_smp[0]) + ((L(o_smp) >> sh) & 0xffff);
         L(q_rstep) = c ? n_smp[1] : n_smp[0];
         TL_LANES_END
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int r = 0; r < 12; r++) {
             const int gr = r >> 2, j0 = (r & 3) * 3;
             TL_LANES_BEGIN
@@ -803,13 +769,9 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
             const uint16_t *xt = &K->crc_xpow[e0];                   // as in tl_encode_frame: the power table instead of stepping x^e
             const unsigned v = preset ? 0xffu : ((frame[byte >> 2] >> (24 - 8 * (byte & 3))) & 0xffu) >> (8 - cnt);
             unsigned x8[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int k = 0; k < 8; k++) x8[k] = xt[k];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int k = 0; k < 8; k++) acc ^= (0u - ((v >> k) & 1u)) & x8[k];
         }
         L(part0) = u == 0 ? acc : 0u; L(part1) = u == 1 ? acc : 0u;
@@ -852,9 +814,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
         unsigned xp = K->crc8_xpow[e0 < 0 ? 0 : e0 > 319 ? 319 : e0];
         unsigned acc = 0;
         const unsigned rb = L(rcrc);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int b = 0; b < 9; b++) {
             acc ^= ((rb >> b) & 1u) ? xp : 0u;
             xp = ((xp << 1) & 0xffu) ^ ((xp & 0x80u) ? 0x1Du : 0u);
@@ -882,9 +842,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
         TL_LANES_END
     }
     // ---- X-PAD + F-PAD bytes (toolame.c:515-524,544-551), straight from the launch's X-PAD records ----
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int u = 0; u < 2; u++)
         if (xpad_len[u]) {
             const int xl = xpad_len[u], xstart = lg_frame[u] - C->dab_ext - xl;
@@ -896,9 +854,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
             TL_LANES_END
         }
     // ---- emit: each unit files its frame and its ScF-CRC (tl_finish_stream puts the CRC into the frame before it) ----
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int u = 0; u < 2; u++) {
         const int nwords = (lg_frame[u] + 3) >> 2;
         const uint32_t *frame = w.u.frame[u];

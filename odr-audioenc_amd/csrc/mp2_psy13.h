@@ -100,19 +100,13 @@ template <bool PSY3>
 TL_FN uint32_t tl_cand_left(const double *px, int c, int run, double pk)
 {
     double b[11];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int j = 2; j <= 12; j++) b[j - 2] = px[c - j];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int j = 2; j <= 12; j++) TL_KEEP(b[j - 2]);
     const double max = pk - 7;
     uint32_t lf = 0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int j = 2; j <= 12; j++) lf |= (PSY3 ? (pk - b[j - 2]) < 7.0 : max < b[j - 2]) ? 1u << (j - 2) : 0u;
     return lf & (run >= 2 ? (1u << (run - 1)) - 1u : 0u);
 }
@@ -148,17 +142,11 @@ TL_FN TlPsy1Ch tl_psy1_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const d
             const int i0 = lane + 256 * h;
             double e[4], v[4];
             bool nr[4];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 4; q++) e[q] = energy[TL_EX(i0 + 64 * q)];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 4; q++) v[q] = tl_power_db_main(e[q], TL_LOGTAB(db), &nr[q]);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 4; q++) {
                 const int i = i0 + 64 * q;
                 px[i] = v[q];                                           // (a filed line's value is overwritten by tl_power_near1)
@@ -177,16 +165,12 @@ TL_FN TlPsy1Ch tl_psy1_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const d
     TL_LANES_BEGIN
     if (lane < (TL_EXP_LEVEL >= 7 ? 0 : 30)) {
         double e[16];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int j = 0; j < 16; j++) e[j] = energy[16 * lane + (j ^ (lane & 15))];      // == energy[TL_EX(16 * lane + j)]
         // 1E-20 + sum of 2^30 e[j] in line order (psycho_1.c:252-257) as 2^30 times (1E-20 / 2^30 + sum of e[j]): scaling every operand of a
         // chain of additions by a power of two scales every partial sum exactly (no operand is anywhere near the subnormal range)
         double sum = 1E-20 * (1.0 / 1073741824);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int j = 0; j < 16; j++) sum += e[j];
         const double spk = 10.0 * tlm_log10_pn(1073741824 * sum, TL_LOGTAB(db));
         L(rec)[ch] = spk;                                           // final as it is: straight to the record (nothing to park)
@@ -376,14 +360,10 @@ TL_FN TlPsy1Ch tl_psy1_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const d
         int nvalid = 0;
         PA(uint32_t, linfo, 8); PA(double, lrw, 8);                 // the table reads of all eight chunks in one batch
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int c8 = 0; c8 < 8; c8++) { L(linfo)[c8] = C->p1_lineinfo[64 * c8 + lane]; L(lrw)[c8] = C->p1_linerw[64 * c8 + lane]; }
         TL_LANES_END
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int base = 0; base < (TL_EXP_LEVEL >= 4 ? 0 : 512); base += 64) {
             PV(bool, ok); PV(double, tv); PV(double, pvv); PV(int, bnd);
             TL_LANES_BEGIN
@@ -436,13 +416,9 @@ TL_FN void tl_psy1_weights2(TlPsyLds &w, int nbands, PARG(int, r0), PARG(int, r1
         int i = i0;
         for (; i + 16 <= i1; i += 16) {                             // sixteen operands per LDS round trip, summed in order
             double t[16];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 16; q++) t[q] = vt[i + q];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 16; q++) weight += t[q];
         }
         for (; i < i1; i++) weight += vt[i];
@@ -488,13 +464,9 @@ TL_FN void tl_psy1_chain2(TlPsyLds &w, const double *TL_RESTRICT db, int nbands,
         int i = i0;
         for (; i + 8 <= i1; i += 8) {                               // eight steps' operands per LDS round trip
             double p[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) p[q] = vp[i + q];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) sum = tl_add_db(db, p[q], sum);
         }
         for (; i + 4 <= i1; i += 4) {
@@ -1037,13 +1009,9 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     TL_LANES_BEGIN
     L(r0) = lane < nbands ? (int)w.bandoff[lane] : 0; L(r1) = lane < nbands ? (int)w.bandoff[lane + 1] : 0;
     const double *vp = TL_PX(w), *vt = w.u.fft;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int k = 0; k < 8; k++) L(pvp)[k] = lane + 64 * k < 504 ? vp[lane + 64 * k] : 0.0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int k = 0; k < 8; k++) L(pvt)[k] = lane + 64 * k < 504 ? vt[lane + 64 * k] : 0.0;
     const int hi = 64 + lane < TL_TONE_MAX ? 64 + lane : 0;
     L(pcc) = (int)((uint32_t)(uint16_t)w.conf_c[lane] | ((uint32_t)(uint16_t)w.conf_c[hi] << 16));
@@ -1058,9 +1026,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
         TL_DBG_BACK(5);
         tl_psy1_finish(w, db, C, 1, s1, rec, sp1);
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) { TL_PX(w)[lane + 64 * k] = L(pvp)[k]; w.u.fft[lane + 64 * k] = L(pvt)[k]; }
         if (lane <= nbands) w.bandoff[lane] = (int16_t)(lane < nbands ? L(r0) : 0);
         TL_LANES_END
@@ -1075,9 +1041,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
         // ---- both channels' weight sums on the two halves: channel 0's terms go where channel 1's levels are (swapped through the
         //      registers that held them), then the levels of both channels take the places the chains read them from ----
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) {
             const double v = TL_PX(w)[lane + 64 * k];
             TL_PX(w)[lane + 64 * k] = L(pvt)[k]; L(pvt)[k] = v;         // pvt: channel 1's levels from here on
@@ -1085,9 +1049,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
         TL_LANES_END
         if (TL_EXP_LEVEL < 3) tl_psy1_weights2(w, nbands, r0, r1, wt);
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int k = 0; k < 8; k++) if (lane + 64 * k < 504) { w.u.fft[lane + 64 * k] = L(pvp)[k]; TL_PX(w)[lane + 64 * k] = L(pvt)[k]; }
         TL_LANES_END
         TL_STAMP(sp1, 4);
@@ -1129,12 +1091,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
         TL_DBG_BACK(1);
         // ---- a tone list too long for a half: the per-channel order.  back(1): its sums and weights move from lanes 32+b to lanes b ----
         PV(double, bsum1); PV(double, wt1);
-#ifdef TL_EMULATE
-        for (int lane = 0; lane < 64; ++lane) { bsum1[lane] = bsum[(lane + 32) & 63]; wt1[lane] = wt[(lane + 32) & 63]; }
-#else
-        bsum1 = __shfl(bsum, (int)((threadIdx.x + 32u) & 63u), 64);
-        wt1 = __shfl(wt, (int)((threadIdx.x + 32u) & 63u), 64);
-#endif
+        TL_ROT32_F64(bsum1, bsum); TL_ROT32_F64(wt1, wt);
         if (TL_EXP_LEVEL < 3) tl_psy1_centres(w, nbands, bsum1, wt1, blo, bhi);
         tl_psy1_back(w, db, C, 1, s1, rec, sp1, false);
     }
@@ -1180,17 +1137,11 @@ TL_FN int tl_psy3_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double
         {
             double e[4], v[4];
             bool nr[4];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 4; q++) { const int i = lane + 64 * (4 * h + q); e[q] = energy[TL_EX(i == 0 ? 512 : i)]; }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 4; q++) v[q] = tl_power_db_main(e[q], TL_LOGTAB(db), &nr[q]);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 4; q++) { const int i = lane + 64 * (4 * h + q); px[i == 0 ? 512 : i] = v[q]; }
             if (h == 0 && lane == 0) px[0] = 0.0;
             L(n0) = nr[0]; L(n1) = nr[1]; L(n2) = nr[2]; L(n3) = nr[3];
@@ -1204,14 +1155,10 @@ TL_FN int tl_psy3_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double
     }
     if (ndef) tl_power_near1(w, 0, ndef);
     TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int k = 0; k < 8; k++) { const int i = lane + 64 * k; L(pxa)[k] = i == 0 ? TL_DBMIN : px[i]; }
     TL_LANES_END
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int it = 0; it < 8; it++) {
         PV(double, pxv); PV(double, pxm);
         TL_LANES_BEGIN L(pxv) = L(pxa)[it]; TL_LANES_END
@@ -1330,14 +1277,10 @@ TL_FN int tl_psy3_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double
         int nvalid = 0;
         PA(uint32_t, linfo, 9);                                     // the table reads of all nine chunks in one batch
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int c8 = 0; c8 < 9; c8++) L(linfo)[c8] = 64 * c8 + lane < 520 ? C->p3_lineinfo[64 * c8 + lane] : 0u;
         TL_LANES_END
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int base = 0; base < 576; base += 64) {                // lines 1..512
             PV(bool, ok); PV(double, ev); PV(int, dj); PV(double, pvv); PV(int, bnd);
             TL_LANES_BEGIN
@@ -1379,13 +1322,9 @@ TL_FN void tl_psy3_moments(TlPsyLds &w, int nb, PARG(double, es), PARG(double, c
         int i = i0;
         for (; i + 8 <= i1; i += 8) {                               // operands of eight steps per LDS round trip, summed in order
             double e[8], c[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) { e[q] = ve[i + q]; c[q] = (int)vj[i + q] * e[q]; }     // (j - lo) * e, psycho_3.c:287
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) { esum += e[q]; cw += c[q]; }
         }
         for (; i < i1; i++) { esum += ve[i]; cw += (int)vj[i] * ve[i]; }
@@ -1433,13 +1372,9 @@ TL_FN void tl_psy3_chain2(TlPsyLds &w, const double *TL_RESTRICT db, int nb, PAR
         int i = i0;
         for (; i + 8 <= i1; i += 8) {                               // eight steps' operands per LDS round trip
             double p[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) p[q] = vp[i + q];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 8; q++) sum = tl_add_db(db, p[q], sum);
         }
         for (; i + 4 <= i1; i += 4) {
@@ -1622,9 +1557,7 @@ TL_FN void tl_psy3_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     tl_psy3_moments(w, nb, es0, cg0);
     TL_LANES_BEGIN
     L(r0) = lane < nb ? (int)w.bandoff[lane] : 0; L(r1) = lane < nb ? (int)w.bandoff[lane + 1] : 0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int k = 0; k < 8; k++) L(pvp)[k] = TL_PX(w)[lane + 64 * k];
     const int hi = 64 + lane < TL_TONE_MAX ? 64 + lane : 0;
     L(pcc) = (int)((uint32_t)(uint16_t)w.conf_c[lane] | ((uint32_t)(uint16_t)w.conf_c[hi] << 16));
@@ -1634,19 +1567,13 @@ TL_FN void tl_psy3_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
     PV(double, es1); PV(double, cg1); PV(double, bsum); PV(double, bsum1);
     tl_psy3_moments(w, nb, es1, cg1);
     TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int k = 0; k < 8; k++) w.u.fft[lane + 64 * k] = L(pvp)[k];   // channel 1's energies are summed: the buffer's lower half is free
     TL_LANES_END
     TL_STAMP(sp1, 4);                                                   // both channels' chains: sp1[4] -> sp0[4] (tools/stage_profile.py)
     TL_PRIO(1); tl_psy3_chain2(w, db, nb, r0, r1, bsum); TL_PRIO(0);
     TL_STAMP(sp0, 4);
-#ifdef TL_EMULATE
-    for (int lane = 0; lane < 64; ++lane) bsum1[lane] = bsum[(lane + 32) & 63];
-#else
-    bsum1 = __shfl(bsum, (int)((threadIdx.x + 32u) & 63u), 64);
-#endif
+    TL_ROT32_F64(bsum1, bsum);
     tl_psy3_back(w, db, C, 1, nconf1, bsum1, es1, cg1, rec, sp1, false);
     TL_LANES_BEGIN
     const int hi = 64 + lane < TL_TONE_MAX ? 64 + lane : 0;

@@ -16,14 +16,6 @@
 // anywhere: two SEED passes (transform, square root, arctangent -- no unpredictability, nothing after it) over the 1152
 // samples before it rebuild exactly the state the chain would have carried there.  During a run the state lives in the wave's
 // REGISTERS: line lane + 64 it in slot `it` of r1/p1 (previous pass) and r2/p2 (the pass before), line 512 in four LDS words.
-// glibc's sincos table as the kernel holds it in LDS: the rows' halves apart -- (sn, ssn) of row k at [2 k], (cs, ccs) at [220 + 2 k] -- instead of
-// 32-byte rows: a 16-byte gather of sixteen lanes then spreads over sixteen bank quads, not eight (row k's first half alone sat on banks 8 k .. 8 k + 3,
-// the other four idle during that read).  `row` = 4 k as tlm_sincos_reduce returns it.  The emulation reads glibc's own layout.
-#ifdef TL_EMULATE
-#define TL_SCT(t, row, j) ((t)[(row) + (j)])
-#else
-#define TL_SCT(t, row, j) ((t)[((row) >> 1) + ((j) & 1) + 220 * ((j) >> 1)])
-#endif
 #define TL_P2_L512(w) ((w).px + 532)     /* r1, r2, p1, p2 of line 512 (c[] ends at px[512], the padded fthr[] at px[528]) */
 template <bool SEED>
 TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy2Tables *TL_RESTRICT P, const TlPcmView &pv, int ch, int pass,
@@ -51,23 +43,17 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
             const int16_t *pvh = ch ? pv.hist[1] : pv.hist[0], *pvc = ch ? pv.cur[1] : pv.cur[0];
             tl_fht_twiddles<4>(L(twc), L(fgc), T, lane);
             double e[16];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int half = 0; half < 16; half += 8) {
                 int16_t v[8]; double h[8];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int q = 0; q < 8; q++) {
                     const int i = lane + 64 * (half + q);
                     if (pass == 0) v[q] = i < TL_HIST ? pvh[i] : pvc[i - TL_HIST];
                     else v[q] = pvc[96 + i];
                     h[q] = win[i];
                 }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int q = 0; q < 8; q++) {
                     const int it = half + q;
                     const int r4 = ((it & 1) << 3) | ((it & 2) << 1) | ((it & 4) >> 1) | ((it & 8) >> 3);
@@ -83,9 +69,7 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
         TL_LANES_BEGIN
         tl_fht_twiddles<8>(L(twa), L(fga), T, lane);
         if (load_state) {
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int it = 0; it < 8; it++) {
                 const int j = lane + 64 * it;
                 L(r1)[it] = load_state->r[ch][0][j]; L(r2)[it] = load_state->r[ch][1][j]; L(p1)[it] = load_state->phi[ch][0][j]; L(p2)[it] = load_state->phi[ch][1][j];
@@ -108,9 +92,7 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
         // fft.c:1274) and line 0 needs none either and no sincos of its phase (phi = 0, fft.c:1257-1259), so in step 0 lane 0 puts
         // line 512's PREDICTED phase through its first sincos slot and finishes that line with a few extra operations.
         PV(double, e512);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 8; it++) {
             PV(double, xa); PV(double, xb); PV(double, xc);
             TL_LANES_BEGIN
@@ -237,9 +219,7 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
         {
             const double *sb = &P->s_band[0][0];
             TL_LAUNDER(sb);                                              // (loads through it stay behind this point)
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < TL_P2_B; q++) { L(sva)[q] = sb[64 * q + lane]; L(svb)[q] = sb[64 * (TL_P2_B + q) + lane]; }
         }
         TL_LANES_END
@@ -255,9 +235,7 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
             const int p0 = np - 32 + l, p1 = l;
             const bool ok0 = p0 >= 0, ok1 = p1 < np - 32;
             const int lo0 = P->part_lo[ok0 ? p0 : 0], hi0 = P->part_hi[ok0 ? p0 : 0], lo1 = P->part_lo[ok1 ? p1 : 0], hi1 = P->part_hi[ok1 ? p1 : 0];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int r = 0; r < 2; r++) {
                 const bool ok = r ? ok1 : ok0;
                 const int hi = r ? hi1 : hi0;
@@ -266,31 +244,19 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
                 if (ok) {
                     double ev[4];
                     if (j + 4 <= hi) {
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                         for (int q = 0; q < 4; q++) ev[q] = arr[j + q];
-#ifndef TL_EMULATE
 #pragma unroll 2
-#endif
                         for (; j + 8 <= hi; j += 4) {
                             double en[4];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                             for (int q = 0; q < 4; q++) en[q] = arr[j + 4 + q];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                             for (int q = 0; q < 4; q++) acc += ev[q];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                             for (int q = 0; q < 4; q++) ev[q] = en[q];
                         }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                         for (int q = 0; q < 4; q++) acc += ev[q];
                         j += 4;
                     }
@@ -362,27 +328,19 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
         TL_LANES_BEGIN
         {
             int pj[9]; double aj[9], tj[9];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 9; q++) { const int j = lane + 64 * q < 512 ? lane + 64 * q : 512; pj[q] = P->partition[j]; aj[q] = P->absthr[j]; }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 9; q++) { tj[q] = nb[pj[q]]; L(ej)[q] = energy[lane + 64 * q < 512 ? lane + 64 * q : 512]; }
             const int jp = lane + (lane >> 5);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 9; q++) { if (lane + 64 * q <= 512) cw[jp + 66 * q] = TLM_MAX_NN(aj[q], tj[q]); }      // (= tj > aj ? tj : aj: no NaN among permissible noise and threshold in quiet)
         }
         TL_LANES_END
         TL_LANES_BEGIN
         {
             const int jp = lane + (lane >> 5);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int q = 0; q < 9; q++) { if (lane + 64 * q <= 512) x[jp + 66 * q] = L(ej)[q]; }
         }
         TL_LANES_END
@@ -401,9 +359,7 @@ TL_FN void tl_psy2_pass(TlPsy2Lds &w, const TlTables *TL_RESTRICT T, const TlPsy
             const int sb = lane & 31;
             const double *a = (lane < 32 ? cw : x) + 16 * sb + (sb >> 1);
             double m = 60802371420160.0, t = 0.0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int k = 0; k < 16; k++) { const double v = a[k]; m = TLM_MIN_NN(m, v); t += v; }
             { const double v = a[16 + (sb & 1)]; m = TLM_MIN_NN(m, v); t += v; }
             L(sb_min) = m; L(sb_sum) = t;

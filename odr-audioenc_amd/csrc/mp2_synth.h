@@ -12,11 +12,6 @@
 #pragma once
 #include "mp2_unpack.h"
 
-#ifdef TL_EMULATE
-#define TL_SCHED_FENCE() ((void)0)
-#else
-#define TL_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)      /* the scheduler moves nothing across this point */
-#endif
 #define TL_SYNTH_BATCH 15                          // sample vectors requantised at a time (five rounds of triples) = entries of the register ring,
                                                    // which is indexed with constants inside a batch
 static_assert(TL_SYNTH_BATCH == TL_SYNTH_HIST && TL_SYNTH_BATCH % 3 == 0, "a batch is whole rounds and covers the history");
@@ -117,9 +112,7 @@ TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, cons
         L(q) = 0.0; L(qprev) = 0.0;
         TL_LANES_END
         // batch 0: the last 15 sample vectors of the slot before (its rounds 7..11); batches 1..3: rounds 0..4, 5..9, 10..11 of the slot itself
-#ifndef TL_EMULATE
 #pragma unroll 1
-#endif
         for (int b = 0; b < 4; b++) {
             const int nvec = b < 3 ? TL_SYNTH_BATCH : 36 - 2 * TL_SYNTH_BATCH;
             if (b == 0 && !hist) {
@@ -128,18 +121,14 @@ TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, cons
                 TL_LANES_END
             } else if (b == 0) tl_requantise(w, w.d[0].frame, B, K, Y, sdp, xp, c, 7, 12);
             else tl_requantise(w, w.d[1].frame, B, K, Y, sd, xc, c, 5 * (b - 1), b < 3 ? 5 * b : 12);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int u = 0; u < TL_SYNTH_BATCH; u++) {
                 if (u >= nvec) continue;                                  // (the last batch is six vectors)
                 const double *sv = w.s + u * 32;
                 TL_LANES_BEGIN
                 // matrixing: V_t[lane] = sum_k N[lane][k] S_t[k]; every lane reads the same 32 samples (LDS broadcasts, 16 bytes each), four partial sums
                 double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int k = 0; k < 32; k += 8) {
                     double s0, s1, s2, s3, s4, s5, s6, s7;
                     TL_LD2(sv + k, s0, s1); TL_LD2(sv + k + 2, s2, s3); TL_LD2(sv + k + 4, s4, s5); TL_LD2(sv + k + 6, s6, s7);
@@ -150,9 +139,7 @@ TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, cons
                 L(ring)[u] = (a0 + a1) + (a2 + a3);
                 // windowing: this lane's eight terms, V_t, V_{t-2}, ... V_{t-14} (the ring holds the last 15 vectors: slot (t mod 15))
                 double b0 = 0.0, b1 = 0.0;
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
                 for (int i = 0; i < 8; i += 2) {
                     b0 += dwin[lane + 64 * i] * L(ring)[(u + 2 * TL_SYNTH_BATCH - 2 * i) % TL_SYNTH_BATCH];
                     b1 += dwin[lane + 64 * i + 64] * L(ring)[(u + 2 * TL_SYNTH_BATCH - 2 - 2 * i) % TL_SYNTH_BATCH];

@@ -117,9 +117,7 @@ TL_FN void tl_psy2_chain(TlPsy2Lds &w, const TlLaunch &A, int s, int ch, int f0,
         TL_LANES_END
     } else {
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 8; it++) { L(r1)[it] = 0.0; L(r2)[it] = 0.0; L(p1)[it] = 0.0; L(p2)[it] = 0.0; }
         if (lane == 0) { l5[0] = 0.0; l5[1] = 0.0; l5[2] = 0.0; l5[3] = 0.0; }
         L(snr0) = 0.0;
@@ -138,9 +136,7 @@ TL_FN void tl_psy2_chain(TlPsy2Lds &w, const TlLaunch &A, int s, int ch, int f0,
     if (f1 == A.nframes) {
         TlPsy2State *S = &A.psy2_state[2 * (size_t)s + (size_t)(1 - A.psy2_flip)];
         TL_LANES_BEGIN
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int it = 0; it < 8; it++) {
             const int j = lane + 64 * it;
             S->r[ch][0][j] = L(r1)[it]; S->r[ch][1][j] = L(r2)[it]; S->phi[ch][0][j] = L(p1)[it]; S->phi[ch][1][j] = L(p2)[it];
@@ -176,34 +172,22 @@ TL_FN void tl_stage_pcm(TlMainLds &w, const TlPcmView &pv, int nch)
         constexpr int HP = TL_HIST / 4, CP = 1152 / 4;                      // 120 + 288 pieces per channel
         constexpr int HT = (HP + 63) / 64, CT = (CP + 63) / 64;             // trips per run: 2 and 5, the last ones partial (56 and 32 lanes)
         uint64_t vh[2][HT], vc[2][CT];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int c = 0; c < 2; c++) {
             if (c >= nch) break;                                            // (wave-uniform)
             const uint64_t *h = (const uint64_t *)(c ? pv.hist[1] : pv.hist[0]), *q = (const uint64_t *)(c ? pv.cur[1] : pv.cur[0]);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int it = 0; it < HT; it++) { vh[c][it] = 0; if (64 * it + 64 <= HP || lane < HP - 64 * it) vh[c][it] = h[lane + 64 * it]; }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int it = 0; it < CT; it++) { vc[c][it] = 0; if (64 * it + 64 <= CP || lane < CP - 64 * it) vc[c][it] = q[lane + 64 * it]; }
         }
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int c = 0; c < 2; c++) {
             if (c >= nch) break;
             uint64_t *d = (uint64_t *)&w.u.fbk.pcm[c][0];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int it = 0; it < HT; it++) if (64 * it + 64 <= HP || lane < HP - 64 * it) d[lane + 64 * it] = vh[c][it];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
             for (int it = 0; it < CT; it++) if (64 * it + 64 <= CP || lane < CP - 64 * it) d[HP + lane + 64 * it] = vc[c][it];
         }
     }
@@ -263,9 +247,7 @@ TL_FN void tl_main_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, const 
     const TlPsyOut *po[2];
     const uint8_t *xsrc[2];
     int xl[2], padding[2];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
     for (int u = 0; u < 2; u++) {
         const size_t slot = (size_t)f * (size_t)A.nstreams + (size_t)ss[u];
         fo[u].bytes = f + 1 < A.nframes ? A.out + (slot + (size_t)A.nstreams) * (size_t)A.out_stride : nullptr;

@@ -197,9 +197,7 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
         TL_WAVE_EXSCAN_I32(lex, rlen);
         const int fb[5] = {0, 4, 8, 16, 30};
         int gend[4], gfirst[4], glast[4];
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int g = 0; g < 4; g++) {
             gfirst[g] = fb[g]; glast[g] = fb[g + 1] > sblimit ? sblimit : fb[g + 1];
             gend[g] = (g < C->dab_ext && glast[g] > gfirst[g]) ? TL_READLANE_I32(lex, 2 * glast[g]) : 0;
@@ -220,9 +218,7 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
         L(part8) = (L(rlen) && sb < sblimit) ? acc : 0u;
         TL_LANES_END
         TL_WAVE_INCL_XSCAN_U32(pscan, part8);
-#ifndef TL_EMULATE
 #pragma unroll
-#endif
         for (int g = 0; g < 4; g++)
             if (g < C->dab_ext && glast[g] > gfirst[g]) {
                 uint32_t v = (uint32_t)TL_READLANE_I32(pscan, 2 * glast[g] - 1);

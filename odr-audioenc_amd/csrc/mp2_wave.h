@@ -12,6 +12,9 @@
 //   * -DTL_EMULATE (g++, tests only): TL_LANES_BEGIN/END are `for (lane = 0..63)` loops and
 //     per-lane "registers" are [64] arrays, so the CPU test-suite executes exactly the device
 //     algorithm (same arithmetic, same order) and compares it with the oracle.
+// The block below is where the two part: whatever has a device form and an emulation form (a cross-lane exchange, a builtin, an asm
+// idiom) is a named primitive with both halves HERE, and the stage headers use it without asking which build they are in.  Loop pragmas
+// (#pragma unroll / nounroll) are written bare: emulation builds pass -Wno-unknown-pragmas and g++ ignores them.
 //
 // Exactness rules: fp64 everywhere, no FMA contraction (-ffp-contract=off),
 // every reduction that the reference performs sequentially is owned by ONE lane and performed in
@@ -62,6 +65,11 @@ TL_FN void tlh_par_sum_i32(int (&d)[64], const int (&v)[64])
 #define TL_PAR_SUM_I32(dst, src) tlh_par_sum_i32(dst, src)
 #define TL_BALLOT(name) tlh_ballot(name)
 #define TL_SWAP1_U64(dst, src) do { for (int l_ = 0; l_ < 64; l_++) dst[l_] = src[l_ ^ 1]; } while (0)
+#define TL_SWAP1_F64(dst, di, src, si) do { for (int l_ = 0; l_ < 64; l_++) dst[l_] di = src[l_ ^ 1] si; } while (0)      /* register `src si` of lane ^ 1 (the subband's other channel) */
+#define TL_SPLAT(dst, di, val) do { for (int l_ = 0; l_ < 64; l_++) dst[l_] di = (val); } while (0)                      /* one value in register `dst di` of every lane, outside a lane scope */
+#define TL_ROT32_F64(dst, src) do { for (int l_ = 0; l_ < 64; l_++) dst[l_] = src[(l_ + 32) & 63]; } while (0)           /* the value of lane + 32: the wave's halves change places */
+// n registers of the lane that owns the mirrored subband 31 - sb of the same channel (the filterbank's other chain, mp2_fb.h)
+#define TL_MIRROR_SB_F64(dst, src, n) do { for (int l_ = 0; l_ < 64; l_++) for (int k_ = 0; k_ < (n); k_++) dst[l_][k_] = src[2 * (31 - (l_ >> 1)) + (l_ & 1)][k_]; } while (0)
 #define TL_WAVE_ARGMIN_U64(name) tlh_argmin_u64(name)
 #define TL_WAVE_MIN_U64(name) tlh_min_u64(name)
 #define TL_WAVE_SUM_I32(name) tlh_sum_i32(name)
@@ -79,6 +87,9 @@ TL_FN void tlh_par_sum_i32(int (&d)[64], const int (&v)[64])
 #define TL_LD2(p, a, b) do { const double *p_ = (p); (a) = p_[0]; (b) = p_[1]; } while (0)
 #define TL_ST2(p, a, b) do { double *p_ = (p); p_[0] = (a); p_[1] = (b); } while (0)
 #define TL_RANK_BELOW(mask) __builtin_popcountll((mask) & ((1ull << lane) - 1ull))     /* set bits of a ballot below this lane */
+TL_FN int tl_sign_bit(double x) { return (int)(tl_d2u(x) >> 63); }                     /* 1 for a negative x, else 0 */
+#define TL_SCHED_FENCE() ((void)0)
+#define TL_SCT(t, row, j) ((t)[(row) + (j)])                                           /* glibc's own layout of its sincos table */
 #else
 #define TL_FN __device__ __forceinline__
 #define TL_LANES_BEGIN { int lane_ = (int)(threadIdx.x & 63u); asm volatile("" : "+v"(lane_)); __builtin_assume(lane_ >= 0 && lane_ < 64); const int lane = lane_;
@@ -100,45 +111,36 @@ TL_FN double tld_swap1_f64(double v) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0xB1, 0xf, 0xf, true);
     return tl_u2d(((uint64_t)hi << 32) | lo);
 }
-TL_FN uint32_t tld_min_u32(uint32_t v) {
-    // DPP reduction (gfx9): row_shr 1,2,4,8 -> row minimum in lane 15 of each row; row_bcast15 / row_bcast31
-    // carry it across rows; lane 63 holds the wave minimum.  Shifted-in lanes read the identity.
-    uint32_t t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, 0x111, 0xf, 0xf, false); v = t < v ? t : v;
-    t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, 0x112, 0xf, 0xf, false); v = t < v ? t : v;
-    t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, 0x114, 0xf, 0xf, false); v = t < v ? t : v;
-    t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, 0x118, 0xf, 0xf, false); v = t < v ? t : v;
-    t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, 0x142, 0xa, 0xf, false); v = t < v ? t : v;
-    t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, 0x143, 0xc, 0xf, false); v = t < v ? t : v;
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+// The combining operations of the DPP reductions below: f(the value DPP brings from another lane, the lane's own value) -- in this order,
+// and with the DPP steps written out in the ladder rather than wrapped in a function of their own, the compiler orders each
+// instruction's operands as it did for the hand-written ladders.
+struct TldMin { template <class T> static TL_FN T f(T a, T b) { return a < b ? a : b; } };
+struct TldAdd { template <class T> static TL_FN T f(T a, T b) { return a + b; } };
+struct TldXor { template <class T> static TL_FN T f(T a, T b) { return a ^ b; } };
+// The ladder (gfx9): row_shr 1,2,4,8 -> inclusive scan inside each row of 16, the row's total in its lane 15; row_bcast15 / row_bcast31
+// carry it across rows.  Every lane ends with OP over lanes 0 .. itself, lane 63 with OP over the wave: DPP only, no ds_bpermute, no
+// per-lane address registers.  Shifted-in lanes read `id`, OP's identity.
+template <class OP, class T> TL_FN T tld_ladder(T v, const T id)
+{
+    v = OP::f((T)__builtin_amdgcn_update_dpp((int)id, (int)v, 0x111, 0xf, 0xf, false), v);
+    v = OP::f((T)__builtin_amdgcn_update_dpp((int)id, (int)v, 0x112, 0xf, 0xf, false), v);
+    v = OP::f((T)__builtin_amdgcn_update_dpp((int)id, (int)v, 0x114, 0xf, 0xf, false), v);
+    v = OP::f((T)__builtin_amdgcn_update_dpp((int)id, (int)v, 0x118, 0xf, 0xf, false), v);
+    v = OP::f((T)__builtin_amdgcn_update_dpp((int)id, (int)v, 0x142, 0xa, 0xf, false), v);
+    v = OP::f((T)__builtin_amdgcn_update_dpp((int)id, (int)v, 0x143, 0xc, 0xf, false), v);
+    return v;
 }
+TL_FN uint32_t tld_min_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)tld_ladder<TldMin>(v, 0xffffffffu), 63); }
 TL_FN uint64_t tld_min_u64(uint64_t v) {
     const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
     const uint32_t mhi = tld_min_u32(hi);
     const uint32_t mlo = tld_min_u32(hi == mhi ? lo : 0xffffffffu);
     return ((uint64_t)mhi << 32) | mlo;
 }
-TL_FN int tld_incl_scan_i32(int v) {
-    // inclusive prefix sum over the 64 lanes with DPP only (no ds_bpermute, no per-lane address registers):
-    // Hillis-Steele inside each row of 16 (row_shr 1,2,4,8), then row_bcast15 / row_bcast31 across rows.
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-TL_FN uint32_t tld_xor_u32(uint32_t x) {
-    int v = (int)x;
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return (uint32_t)__builtin_amdgcn_readlane(v, 63);
-}
+TL_FN int tld_incl_scan_i32(int v) { return tld_ladder<TldAdd>(v, 0); }                 // inclusive prefix sum over the 64 lanes
+TL_FN uint32_t tld_incl_xscan_u32(uint32_t x) { return tld_ladder<TldXor>(x, 0u); }     // inclusive XOR prefix, same ladder as the integer sum scan
+#define TL_WAVE_INCL_XSCAN_U32(dst, src) dst = tld_incl_xscan_u32(src)
+TL_FN uint32_t tld_xor_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)tld_incl_xscan_u32(x), 63); }
 TL_FN int tld_sum_i32(int v) { return __builtin_amdgcn_readlane(tld_incl_scan_i32(v), 63); }
 TL_FN int tld_exscan_i32(int v) { return tld_incl_scan_i32(v) - v; }
 TL_FN int tld_argmin_u64(uint64_t v)
@@ -154,41 +156,28 @@ TL_FN int tld_argmin_u64(uint64_t v)
     const uint64_t even = m & 0x5555555555555555ull;
     return __builtin_ctzll(even ? even : m);
 }
+template <int SH> TL_FN double tld_row_shr_f64(double v)
+{   // the value SH lanes down the row of 16; the row's first SH lanes keep their own
+    const uint64_t u = tl_d2u(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)u, (int)(uint32_t)u, 0x110 | SH, 0xf, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(u >> 32), (int)(uint32_t)(u >> 32), 0x110 | SH, 0xf, 0xf, false);
+    return tl_u2d(((uint64_t)hi << 32) | lo);
+}
 TL_FN double tld_row16_max_f64(double v)
 {   // maximum over each row of 16 lanes, valid in the row's lane 15 (row_shr 1,2,4,8; shifted-in lanes keep their own value)
-#pragma unroll
-    for (int sh = 1; sh <= 8; sh <<= 1) {
-        const uint64_t u = tl_d2u(v);
-        const int ctl = 0x110 | sh;
-        uint32_t lo, hi;
-        switch (sh) {
-        case 1: lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)u, (int)(uint32_t)u, 0x111, 0xf, 0xf, false); hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(u >> 32), (int)(uint32_t)(u >> 32), 0x111, 0xf, 0xf, false); break;
-        case 2: lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)u, (int)(uint32_t)u, 0x112, 0xf, 0xf, false); hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(u >> 32), (int)(uint32_t)(u >> 32), 0x112, 0xf, 0xf, false); break;
-        case 4: lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)u, (int)(uint32_t)u, 0x114, 0xf, 0xf, false); hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(u >> 32), (int)(uint32_t)(u >> 32), 0x114, 0xf, 0xf, false); break;
-        default: lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)u, (int)(uint32_t)u, 0x118, 0xf, 0xf, false); hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(u >> 32), (int)(uint32_t)(u >> 32), 0x118, 0xf, 0xf, false); break;
-        }
-        (void)ctl;
-        const double o = tl_u2d(((uint64_t)hi << 32) | lo);
-        v = v < o ? o : v;
-    }
+    double o;
+    o = tld_row_shr_f64<1>(v); v = v < o ? o : v;
+    o = tld_row_shr_f64<2>(v); v = v < o ? o : v;
+    o = tld_row_shr_f64<4>(v); v = v < o ? o : v;
+    o = tld_row_shr_f64<8>(v); v = v < o ? o : v;
     return v;
 }
 #define TL_ROW16_MAX_F64(dst, src) dst = tld_row16_max_f64(src)
-TL_FN uint32_t tld_incl_xscan_u32(uint32_t x)
-{   // inclusive XOR prefix over the 64 lanes, same DPP ladder as the integer sum scan
-    int v = (int)x;
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v ^= __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return (uint32_t)v;
-}
-#define TL_WAVE_INCL_XSCAN_U32(dst, src) dst = tld_incl_xscan_u32(src)
 // Butterflies over the 32 lanes of one parity, the result in every lane (no readlane, no scalar round trip): row_ror 2 / 4 / 8 inside
 // the rows of 16, then the two gfx950 row / half swaps (v_permlane16_swap, v_permlane32_swap: with both operands the same register
-// the two results hold each lane's value and its counterpart's in the other row / half).
+// the two results hold each lane's value and its counterpart's in the other row / half).  Written out for each of the two: as one
+// template over the operation either the minimum's or the sum's swap steps come out with their operands exchanged (the same values,
+// other instruction words -- profiles/refactor_wave_codeobjects.txt).
 TL_FN uint32_t tld_par_min_u32(uint32_t v)
 {
     uint32_t t;
@@ -219,6 +208,11 @@ TL_FN int tld_par_sum_i32(int v)
 #define TL_PAR_SUM_I32(dst, src) dst = tld_par_sum_i32(src)
 #define TL_BALLOT(name) ((uint64_t)__ballot(name))
 #define TL_SWAP1_U64(dst, src) dst = tl_d2u(tld_swap1_f64(tl_u2d(src)))
+#define TL_SWAP1_F64(dst, di, src, si) dst di = tld_swap1_f64(src si)
+#define TL_SPLAT(dst, di, val) dst di = (val)
+#define TL_ROT32_F64(dst, src) dst = __shfl(src, (int)((threadIdx.x + 32u) & 63u), 64)
+#define TL_MIRROR_SB_F64(dst, src, n) do { const int lane_ = (int)(threadIdx.x & 63u), partner_ = 2 * (31 - (lane_ >> 1)) + (lane_ & 1); \
+                                           _Pragma("unroll") for (int k_ = 0; k_ < (n); k_++) dst[k_] = __shfl(src[k_], partner_, 64); } while (0)
 #define TL_WAVE_ARGMIN_U64(name) tld_argmin_u64(name)
 #define TL_WAVE_MIN_U64(name) tld_min_u64(name)
 #define TL_WAVE_SUM_I32(name) tld_sum_i32(name)
@@ -241,6 +235,14 @@ typedef const struct TlLaunch *TlKArg;                                        /*
 #define TL_KARG TlKArg
 #define TL_LAUNDER(p) asm volatile("" : "+s"(p))       /* keeps loads through p inside the frame loop (no hoisting into long-lived VGPRs) */
 #define TL_TIE(p, v) asm volatile("" : "+s"(p), "+v"(v))   /* loads through p are requested after v has been computed, not before: a software pipeline's order, pinned */
+// 1 for a negative x, else 0: one shift of the high word, opaque to the compiler (which otherwise folds it into the address arithmetic that
+// follows as shift + and + add: three instructions where shift + shift-add do)
+TL_FN int tl_sign_bit(double x) { int r; asm("v_lshrrev_b32 %0, 31, %1" : "=v"(r) : "v"((uint32_t)(tl_d2u(x) >> 32))); return r; }
+#define TL_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)      /* the scheduler moves nothing across this point */
+// glibc's sincos table as the psy-2 kernel holds it in LDS: the rows' halves apart -- (sn, ssn) of row k at [2 k], (cs, ccs) at [220 + 2 k] -- instead of
+// 32-byte rows: a 16-byte gather of sixteen lanes then spreads over sixteen bank quads, not eight (row k's first half alone sat on banks 8 k .. 8 k + 3,
+// the other four idle during that read).  `row` = 4 k as tlm_sincos_reduce returns it.  The emulation reads glibc's own layout.
+#define TL_SCT(t, row, j) ((t)[((row) >> 1) + ((j) & 1) + 220 * ((j) >> 1)])
 #define TL_PIN(x) asm volatile("" : "+v"(x))           /* a constant made once, here, in a vector register: machine LICM is off (csrc/Makefile), so a literal used inside a hot loop
                                                           is otherwise re-made by a v_mov on every trip */
 #endif
@@ -386,12 +388,7 @@ struct TlMainLds {
     uint8_t balloc[2][32];
     uint8_t minidx[2][32];
     uint8_t xpad[TL_MAX_XPAD];
-    typedef double (*YpRows)[TL_YP_ROW * 3 + 16];
-#ifdef TL_EMULATE
-    YpRows yp_rows() { return yp; }
-#else
-    __device__ YpRows yp_rows() { return yp; }
-#endif
+    typedef double (*YpRows)[TL_YP_ROW * 3 + 16];   // yp, as the filterbank walks it
 };
 // The quantiser's re-deal (mp2_pack.h K6): a frame whose live cells (bit_alloc != 0) are few leaves the lanes of the others idle through
 // all twelve rounds of three samples.  Such a frame ranks its live cells, passes their samples through LDS a granule at a time and gives
