@@ -7,7 +7,11 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K]
+//   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
+//   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
+//   header's padding bit, service s takes frame (tick + s) of it (wrapping round), one tick per frame of the file.  No PCM crosses the
+//   link; in.s16le is not opened (give "-").  Not together with --short-every or --source-rate.
 //   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
 //   encoder's rate on the device (tlb_tick_set_source): each tick reads tlb_tick_need() source frames per stream, not 1152.  Not together
 //   with --short-every.
@@ -39,7 +43,7 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
@@ -47,6 +51,8 @@ int main(int argc, char **argv)
     int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     char mode = 0;
     double gain_db = 0.0;
+    const char *feed_path = nullptr;
+    int feed_kbps = 0;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
@@ -63,6 +69,8 @@ int main(int argc, char **argv)
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
         else if (k == "--source-rate") source_rate = std::atol(v);
+        else if (k == "--feed") feed_path = v;
+        else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -72,8 +80,30 @@ int main(int argc, char **argv)
     if (nstreams < 1) die("streams", nstreams);
     if (short_every < 0 || short_by < 0 || short_by > 1152 || (short_every > 0) != (short_by > 0)) die("--short-every N --short-by M: N >= 1 and 1 <= M <= 1152, both or neither", 0);
 
-    std::FILE *fi = std::fopen(argv[1], "rb");
-    if (!fi) die("cannot open input", 0);
+    if ((feed_path != nullptr) != (feed_kbps > 0)) die("--feed FILE.mp2 --feed-bitrate K: both or neither", 0);
+    std::FILE *fi = feed_path ? nullptr : std::fopen(argv[1], "rb");
+    if (!feed_path && !fi) die("cannot open input", 0);
+    tlb_feed_config feed = {rate, feed_kbps, channels};
+    std::vector<uint8_t> mp2;
+    std::vector<size_t> fpos, flen;                              // --feed: where each frame lies in the file
+    if (feed_path) {
+        if (int rc = tlb_feed_check_config(&feed)) die("--feed-bitrate: no legal Layer II configuration at this rate and channel count", rc);
+        std::FILE *ff = std::fopen(feed_path, "rb");
+        if (!ff) die("cannot open the feed", 0);
+        uint8_t buf[1 << 15];
+        size_t n;
+        while ((n = std::fread(buf, 1, sizeof buf, ff)) > 0) mp2.insert(mp2.end(), buf, buf + n);
+        std::fclose(ff);
+        const size_t base = (size_t)tlb_feed_frame_bytes(&feed);
+        for (size_t o = 0; o + 4 <= mp2.size();) {               // the sync word, the arithmetic length, one more with the padding bit
+            if (mp2[o] != 0xff || (mp2[o + 1] & 0xf0) != 0xf0) die("the feed has no sync word where a frame should begin, at byte", (int)o);
+            const size_t len = base + ((mp2[o + 2] >> 1) & 1u);
+            if (o + len > mp2.size()) break;
+            fpos.push_back(o); flen.push_back(len);
+            o += len;
+        }
+        if (fpos.empty()) die("the feed is shorter than one frame", 0);
+    }
     std::FILE *fo = std::fopen(argv[2], "wb");
     if (!fo) die("cannot open output", 0);
 
@@ -91,12 +121,13 @@ int main(int argc, char **argv)
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
     if (source_rate) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
+    if (feed_path) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);                   // likewise
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
     size_t per_frame = 1152 * (size_t)channels;              // samples of one frame in the file
     std::vector<int16_t> frame(per_frame);
-    long frames = 0, packets = 0;
+    long frames = 0, packets = 0, bad_feed = 0;
     int alarms = 0;                                              // compare monitor: times a stream's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any stream has shown after a tick
     const auto t0 = std::chrono::steady_clock::now();
@@ -120,7 +151,22 @@ int main(int argc, char **argv)
                     alarms++;
                 }
     };
-    for (;;) {
+    for (; feed_path && frames < (long)fpos.size();) {           // one tick per frame of the feed
+        uint8_t *fr = tlb_tick_feed(t);                          // pinned [nstreams][tlb_tick_feed_stride()], re-fetched every tick like the PCM
+        int32_t *ln = tlb_tick_feed_len(t);                      // pinned [nstreams]: every set comes back all 0
+        const size_t stride = (size_t)tlb_tick_feed_stride(t);
+        for (int s = 0; s < nstreams; s++) {
+            const size_t k = ((size_t)frames + (size_t)s) % fpos.size();
+            std::memcpy(fr + stride * (size_t)s, &mp2[fpos[k]], flen[k]);
+            ln[s] = (int32_t)flen[k];
+        }
+        if (int rc = tlb_tick_run(t)) die("tlb_tick_run", rc);
+        const tlb_frame_report *rep = tlb_tick_feed_report(t);   // a frame that did not pass went in as silence
+        for (int s = 0; s < nstreams; s++) bad_feed += (rep[s].status & TLB_DEC_BAD_MASK) != 0;
+        emit();
+        frames++;
+    }
+    for (; !feed_path;) {
         if (source_rate) per_frame = (size_t)tlb_tick_need(t, 0) * (size_t)channels;      // 1058 or 1059 frames at 44.1 kHz, 768 at 32 kHz: every stream is fed the one file, so all need the same
         if (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) != per_frame) break;
         int16_t *in = tlb_tick_pcm(t);                       // pinned [nstreams][2304]; mono streams use the first 1152 values
@@ -141,6 +187,7 @@ int main(int argc, char **argv)
         const uint32_t *ms = tlb_tick_underrun_ms(t), *n = tlb_tick_underruns(t);
         std::fprintf(stderr, "editick: stream 0: %u short reads, %u ms since its last full read\n", n[0], ms[0]);
     }
+    if (feed_path) std::fprintf(stderr, "editick: feed: %zu frames of %d kbps in the file, %ld feed frames did not pass\n", fpos.size(), feed_kbps, bad_feed);
     unsigned long checked = 0, bad = 0;
     if (monitor) {
         const tlb_monitor_record *r = tlb_tick_monitor(t);
@@ -158,7 +205,7 @@ int main(int argc, char **argv)
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",
                  frames, nstreams, packets, sec, sec > 0 ? (double)frames * nstreams / sec : 0.0);
     tlb_tick_destroy(t);
-    std::fclose(fi);
+    if (fi) std::fclose(fi);
     std::fclose(fo);
     return bad ? 3 : alarms ? 4 : 0;
 }

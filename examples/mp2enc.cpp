@@ -10,6 +10,9 @@
 // usage: mp2enc in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [--verify]
 // --verify: every frame is read back on the device right after it was encoded (tlb_decode_host: header, CRC-16, ScF-CRC, bit budget);
 // any TLB_DEC_BAD_MASK flag ends the run with exit status 3.
+// --from-mp2: the input is an MPEG Layer II file, a transcode: its first header gives the feed's rate, bitrate and channel count (which are
+// then the encoder's rate and channel count, -r and -c are not needed), the file is cut into frames by the arithmetic length and each
+// header's padding bit, and the frames are decoded on the device into the ingest's input (tlb_feed_host) instead of PCM being read.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -29,17 +32,18 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [--verify]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [--verify] [--from-mp2]\n", argv[0]);
         return 2;
     }
     long rate = 48000;
     int channels = 2, kbps = 128, psy = 1, nstreams = 1;
     char mode = 0;
     double gain_db = 0.0;
-    bool verify = false;
+    bool verify = false, from_mp2 = false;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--verify") { verify = true; i -= 1; continue; }
+        if (k == "--from-mp2") { from_mp2 = true; i -= 1; continue; }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") rate = std::atol(v);
@@ -51,22 +55,46 @@ int main(int argc, char **argv)
         else if (k == "-n") nstreams = std::atoi(v);
         else die("unknown option", 0);
     }
-    if (!mode) mode = channels == 1 ? 'm' : 'j';             // odr-audioenc's defaults (src/odr-audioenc.cpp:697-709)
-    if (channels != 1 && channels != 2) die("1 or 2 channels", channels);
     if (nstreams < 1) die("streams", nstreams);
 
-    // the whole input, cut to whole frames of 1152 samples per channel
+    // the whole input: PCM cut to whole frames of 1152 samples per channel, or (--from-mp2) Layer II frames
     std::FILE *fi = std::fopen(argv[1], "rb");
     if (!fi) die("cannot open input", 0);
     std::vector<int16_t> in;
-    {
+    std::vector<uint8_t> mp2;
+    if (from_mp2) {
+        uint8_t buf[1 << 15];
+        size_t n;
+        while ((n = std::fread(buf, 1, sizeof buf, fi)) > 0) mp2.insert(mp2.end(), buf, buf + n);
+    } else {
         int16_t buf[1 << 15];
         size_t n;
         while ((n = std::fread(buf, sizeof(int16_t), sizeof buf / sizeof buf[0], fi)) > 0) in.insert(in.end(), buf, buf + n);
-        std::fclose(fi);
     }
+    std::fclose(fi);
+    tlb_feed_config feed = {0, 0, 0};
+    std::vector<size_t> fpos, flen;                           // --from-mp2: where each frame lies in the file
+    if (from_mp2) {
+        if (mp2.size() < 4 || mp2[0] != 0xff || (mp2[1] & 0xf6) != 0xf4) die("the input does not begin with a Layer II header", 0);
+        const int lsf = !(mp2[1] & 0x08), bi = mp2[2] >> 4, fi2 = (mp2[2] >> 2) & 3;
+        static const int kb[2][16] = {{0, 32, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320, 384, 0}, {0, 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128, 144, 160, 0}};
+        static const long fs[2][4] = {{44100, 48000, 32000, 0}, {22050, 24000, 16000, 0}};
+        feed = tlb_feed_config{fs[lsf][fi2], kb[lsf][bi], (mp2[3] >> 6) == 3 ? 1 : 2};
+        if (tlb_feed_check_config(&feed) != TLB_OK) die("the input's first header names no legal Layer II configuration", tlb_feed_check_config(&feed));
+        rate = feed.samplerate; channels = feed.channels;
+        const size_t base = (size_t)tlb_feed_frame_bytes(&feed);
+        for (size_t o = 0; o + 4 <= mp2.size();) {            // the sync word, the arithmetic length, one more with the padding bit
+            if (mp2[o] != 0xff || (mp2[o + 1] & 0xf0) != 0xf0) die("the input has no sync word where a frame should begin, at byte", (int)o);
+            const size_t n = base + ((mp2[o + 2] >> 1) & 1u);
+            if (o + n > mp2.size()) break;
+            fpos.push_back(o); flen.push_back(n);
+            o += n;
+        }
+    }
+    if (!mode) mode = channels == 1 ? 'm' : 'j';             // odr-audioenc's defaults (src/odr-audioenc.cpp:697-709)
+    if (channels != 1 && channels != 2) die("1 or 2 channels", channels);
     const size_t per_frame = 1152u * (size_t)channels;
-    const int nframes = (int)(in.size() / per_frame);
+    const int nframes = from_mp2 ? (int)fpos.size() : (int)(in.size() / per_frame);
     if (nframes == 0) die("input shorter than one frame", 0);
 
     std::vector<tlb_stream_config> cfg((size_t)nstreams, tlb_stream_config{rate, mode, kbps, psy, 0});
@@ -74,6 +102,9 @@ int main(int argc, char **argv)
     tlb_batch *enc = tlb_create(0, nstreams, cfg.data(), &err);
     if (!enc) die("tlb_create", err);
     if (gain_db != 0.0 && (err = tlb_set_gain_db(enc, -1, gain_db)) != TLB_OK) die("tlb_set_gain_db", err);
+
+    if (from_mp2 && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
+    const int fstride = tlb_feed_stride(enc);
 
     const int stride = tlb_out_stride(enc);
     std::FILE *fo = std::fopen(argv[2], "wb");
@@ -83,6 +114,10 @@ int main(int argc, char **argv)
     std::vector<int16_t> inter((size_t)chunk * nstreams * 2304), pcm((size_t)chunk * nstreams * 2304), peaks((size_t)chunk * nstreams * 2);
     std::vector<uint8_t> out((size_t)chunk * nstreams * stride);
     std::vector<int32_t> len((size_t)chunk * nstreams);
+    std::vector<uint8_t> ffr(from_mp2 ? (size_t)chunk * nstreams * fstride : 0);
+    std::vector<int32_t> fln(from_mp2 ? (size_t)chunk * nstreams : 0);
+    long bad_feed = 0;
+    std::vector<tlb_frame_report> frep(from_mp2 ? (size_t)chunk * nstreams : 0);
     long written = 0, checked = 0;
     std::vector<tlb_frame_report> report(verify ? (size_t)chunk * nstreams : 0);
     // TEST-ONLY hook of this example (tests/test_decode_gpu.py): a byte offset into the first call's frame buffer, flipped before the check
@@ -102,8 +137,16 @@ int main(int argc, char **argv)
     for (int f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = nframes - f0 < chunk ? nframes - f0 : chunk;
         for (int f = 0; f < nf; f++)                         // every stream of the batch gets the same programme
-            for (int s = 0; s < nstreams; s++)
-                std::memcpy(&inter[((size_t)f * nstreams + s) * 2304], &in[(size_t)(f0 + f) * per_frame], per_frame * sizeof(int16_t));
+            for (int s = 0; s < nstreams; s++) {
+                const size_t slot = (size_t)f * nstreams + s;
+                if (from_mp2) { std::memcpy(&ffr[slot * fstride], &mp2[fpos[(size_t)(f0 + f)]], flen[(size_t)(f0 + f)]); fln[slot] = (int32_t)flen[(size_t)(f0 + f)]; }
+                else std::memcpy(&inter[slot * 2304], &in[(size_t)(f0 + f) * per_frame], per_frame * sizeof(int16_t));
+            }
+        if (from_mp2) {                                      // the decode, into what the ingest reads; a frame that does not pass goes in as silence
+            if ((err = tlb_feed_host(enc, ffr.data(), fln.data(), nf, inter.data(), frep.data())) != TLB_OK) die("tlb_feed_host", err);
+            // (stream 0's reports stand for all: every stream of the batch is given the same file)
+            for (size_t i = 0; i < (size_t)nf * nstreams; i += (size_t)nstreams) bad_feed += (frep[i].status & TLB_DEC_BAD_MASK) != 0;
+        }
         if ((err = tlb_ingest_host(enc, inter.data(), nf, pcm.data(), peaks.data())) != TLB_OK) die("tlb_ingest_host", err);
         if ((err = tlb_encode_host_len(enc, pcm.data(), nf, nullptr, nullptr, out.data(), len.data(), nullptr)) != TLB_OK) die("tlb_encode_host_len", err);
         if (verify) {
@@ -126,6 +169,8 @@ int main(int argc, char **argv)
     std::fclose(fo);
     std::fprintf(stderr, "mp2enc: %d frames x %d stream(s) in %.3f s = %.0f frames/s (%.0f x real time per stream); %ld bytes written; %s\n",
                  nframes, nstreams, dt, (double)nframes * nstreams / dt, (double)nframes * 1152.0 / (double)rate / dt, written, tlb_version());
+    if (from_mp2) std::fprintf(stderr, "mp2enc: transcoded from %ld Hz, %d kbps, %d channel(s): %d frames, %ld did not pass and went in as silence\n",
+                               feed.samplerate, feed.bitrate, feed.channels, nframes, bad_feed);
     if (verify) std::fprintf(stderr, "mp2enc: verify ok: %ld frames read back on the device, %ld bad\n", checked, tlb_decode_bad_frames(enc));
     tlb_destroy(enc);
     return 0;

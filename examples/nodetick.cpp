@@ -22,6 +22,10 @@
 //   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
 //   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
+//   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file (48 kHz, two channels, K kbps) decoded on the GPUs ahead
+//   of the ingest (tlb_node_set_feed): the file is cut into frames by the arithmetic length and each header's padding bit, service s takes
+//   frame (tick + s) of it, wrapping round; no PCM crosses the link and in.s16le is not opened (give "-").  Not together with --short-every
+//   or --source-rate.
 //   --source-rate R: in.s16le is at R Hz (44100 or 32000) and is resampled to 48 kHz on the GPUs (tlb_node_set_source): service s starts
 //   reading at source frame 1152 s and takes tlb_node_need() consecutive frames every tick, wrapping around.  Not together with --short-every.
 //   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
@@ -53,12 +57,26 @@ struct Ctx {
     int short_every, short_by;                               // 0: every read is full
     long source_rate;                                        // 0: the file is at the encoder's rate
     std::vector<size_t> *spos;                               // --source-rate: the next source frame of every service
+    const std::vector<uint8_t> *mp2;                         // --feed: the file and where its frames lie (NULL: PCM input)
+    const std::vector<size_t> *fpos, *flen;
 };
 
 // step 1 on shard `g`'s thread: the block's services copy their frame of this tick into the pinned input set
 static void fill(void *vctx, int g, int first, int n)
 {
     Ctx &c = *(Ctx *)vctx;
+    for (int s = first; s < first + n && c.mp2; s++) {          // --feed: the service's frame of this tick into its slot of the pinned feed set
+        uint8_t *slot = tlb_node_feed(c.nd, s);
+        int32_t *len = tlb_node_feed_len(c.nd, s);
+        if (!slot || !len) {
+            if (tlb_node_shard_status(c.nd, g, nullptr) != TLB_SHARD_OK) return;
+            die("no feed set free", s);
+        }
+        const size_t f = ((size_t)s + (size_t)c.tick) % c.fpos->size();
+        std::memcpy(slot, c.mp2->data() + (*c.fpos)[f], (*c.flen)[f]);
+        *len = (int32_t)(*c.flen)[f];                            // untouched, it reads 0: an empty slot
+    }
+    if (c.mp2) return;
     for (int s = first; s < first + n; s++) {
         int16_t *dst = tlb_node_pcm(c.nd, s);
         if (!dst) {                                              // a BROKEN or LATE shard takes no input (its block is off air until it is back); anything else is a bug
@@ -101,13 +119,14 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K]\n", argv[0]);
         return 2;
     }
     int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     double deadline_ms = 0;
     long source_rate = 0;
-    std::string devs, outpath;
+    int feed_kbps = 0;
+    std::string devs, outpath, feed_path;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
@@ -124,6 +143,8 @@ int main(int argc, char **argv)
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
         else if (k == "--source-rate") source_rate = std::atol(v);
+        else if (k == "--feed") feed_path = v;
+        else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -141,8 +162,30 @@ int main(int argc, char **argv)
     if (devices.empty()) { if (G <= 0) G = ndev; for (int g = 0; g < G; g++) devices.push_back(g % ndev); }
     G = (int)devices.size();
 
+    if (feed_path.empty() != (feed_kbps <= 0)) die("--feed FILE.mp2 --feed-bitrate K: both or neither", 0);
+    tlb_feed_config feed = {48000, feed_kbps, 2};
+    std::vector<uint8_t> mp2;
+    std::vector<size_t> fpos, flen;
+    if (!feed_path.empty()) {
+        if (int rc = tlb_feed_check_config(&feed)) die("--feed-bitrate: no legal Layer II bitrate at 48 kHz", rc);
+        std::FILE *ff = std::fopen(feed_path.c_str(), "rb");
+        if (!ff) die("cannot open the feed", 0);
+        uint8_t buf[1 << 15];
+        size_t got;
+        while ((got = std::fread(buf, 1, sizeof buf, ff)) > 0) mp2.insert(mp2.end(), buf, buf + got);
+        std::fclose(ff);
+        const size_t base = (size_t)tlb_feed_frame_bytes(&feed);
+        for (size_t o = 0; o + 4 <= mp2.size();) {               // the sync word, the arithmetic length, one more with the padding bit
+            if (mp2[o] != 0xff || (mp2[o + 1] & 0xf0) != 0xf0) die("the feed has no sync word where a frame should begin, at byte", (int)o);
+            const size_t len = base + ((mp2[o + 2] >> 1) & 1u);
+            if (o + len > mp2.size()) break;
+            fpos.push_back(o); flen.push_back(len);
+            o += len;
+        }
+        if (fpos.empty()) die("the feed is shorter than one frame", 0);
+    }
     std::vector<int16_t> pcm;
-    {
+    if (feed_path.empty()) {
         std::FILE *fi = std::fopen(argv[1], "rb");
         if (!fi) die("cannot open input", 0);
         int16_t buf[2304];
@@ -150,7 +193,7 @@ int main(int argc, char **argv)
         std::fclose(fi);
     }
     const size_t nframes_in = pcm.size() / 2304;
-    if (!nframes_in) die("input shorter than one frame", 0);
+    if (feed_path.empty() && !nframes_in) die("input shorter than one frame", 0);
 
     // the fleet: every service 48 kHz joint stereo (odr-audioenc's default mode, src/odr-audioenc.cpp:697-709)
     std::vector<tlb_stream_config> cfg((size_t)nstreams, tlb_stream_config{48000, 'j', kbps, psy, 0});
@@ -178,6 +221,8 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
     if (source_rate)
         if (int rc = tlb_node_set_source(nd, -1, source_rate)) die("tlb_node_set_source", rc);          // between steps; a restarted shard's sources are set again
+    if (!feed_path.empty())
+        if (int rc = tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare)
         if (int rc = tlb_node_enable_compare(nd, &cparams)) die("tlb_node_enable_compare", rc);         // after the audio monitor, before the first submit
@@ -185,8 +230,8 @@ int main(int argc, char **argv)
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
     std::vector<size_t> spos((size_t)nstreams);
-    for (int s = 0; s < nstreams; s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, &spos};
+    for (int s = 0; s < nstreams && !pcm.empty(); s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick

@@ -803,6 +803,111 @@ int tlb_tick_need(const tlb_tick *t, int stream);
 int tlb_node_set_source(tlb_node *nd, int stream, long source_rate);
 int tlb_node_need(const tlb_node *nd, int stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Layer II feeds: a stream's source arrives as MP2 frames SOMEBODY ELSE encoded and is decoded on the device, ahead of the ingest.
+ * Every entry point above takes PCM, 4608 bytes per stream and frame over the host-to-device link.  The reference's users need not: its
+ * VLC and GStreamer inputs take a compressed feed and decode it before AudioEnc::run() sees a sample (src/VLCInput.cpp, src/GSTInput.cpp),
+ * and MPEG Layer II is what studio links, satellite feeds and re-multiplexed services carry.  A 192 kbps feed frame is 576 bytes.
+ * A FEED is a per-stream configuration of its own -- sample rate, bitrate, channels (1 | 2) -- and tlb_feed_*() decodes a feed frame into
+ * the stream's slot of tlb_ingest_device's input, with the parser, requantiser and fp64 synthesis filterbank of tlb_decode_*() above.
+ * IN THIS VERSION the feed's samplerate must be the stream's and its channels the stream's channel count (else TLB_ERR_SAMPLERATE /
+ * TLB_ERR_MODE from tlb_feed_set): a feed at another rate needs a per-stream sample queue in front of the resampler, a stereo feed for a
+ * mono service needs a downmix; both are out of scope.  The bitrate is the feed's own.
+ *   d_frames      uint8 [nframes][nstreams][tlb_feed_stride()]
+ *   d_len         int32 [nframes][nstreams], required; 0 (or less) = an empty slot
+ *   d_interleaved int16 [nframes][nstreams][2304], tlb_ingest_device's input: a fed stream's slot gets 1152 sample frames, L R L R for two
+ *                 channels, 1152 samples at the slot's start for one (nothing is written behind them).  THE SLOT OF A STREAM WITHOUT A
+ *                 FEED IS NOT TOUCHED: a mixed batch fills those with PCM as before, in any order with this call.
+ *   d_report      tlb_frame_report [nframes][nstreams] or NULL; the slot of a stream without a feed has status TLB_DEC_EMPTY
+ * HEADER RULES for a feed frame (a frame "passes" as above: no TLB_DEC_BAD_MASK flag, not EMPTY):
+ *   - sync, ID, layer, bitrate index and sampling-frequency index must be the feed's configuration's (BAD_SYNC, HEADER_MISMATCH);
+ *   - the protection bit is read per frame: with a CRC-16 the fields start at bit 48 and the CRC is verified (BAD_CRC16), without one
+ *     they start at bit 32 and crc_stored = crc_computed = 0;
+ *   - private, copyright, original and emphasis bits are ignored;
+ *   - the mode is the frame's: a two-channel feed accepts stereo, joint stereo with any bound and dual channel, a one-channel feed mono
+ *     only; anything else is HEADER_MISMATCH;
+ *   - the padding bit is honoured where the rate has padding slots (44.1 / 22.05 kHz; set elsewhere: HEADER_MISMATCH).  A slot longer
+ *     than its frame is a HEADER_MISMATCH, a shorter one OVERRUN, as are fields that need more bits than the frame has;
+ *   - no ScF-CRC is looked for: BAD_SCFCRC and SCFCRC_UNCHECKED are never set.  What follows the samples is ancillary data.
+ * No read leaves the slot whatever its bytes say.  Rounding and saturation are tlb_decode_*()'s.  A frame that did not pass, or an empty
+ * slot, yields 1152 zeros per channel and counts as silence in its successor's filter history.  The output does not depend on how a
+ * stream's frames are cut into calls: a call leaves each fed stream's last slot -- bytes, length, status -- behind for the next, in arrays
+ * of its own (not the decoder's), allocated by the first tlb_feed_set: a batch that never sets a feed allocates nothing and makes exactly
+ * the device calls it made before.
+ *   tlb_feed_check_config(cfg)    host only, no GPU: TLB_OK / TLB_ERR_SAMPLERATE / TLB_ERR_BITRATE / TLB_ERR_MODE (channels not 1 | 2).
+ *                                 The bitrate must be one the rate's table has: every combination the encoder itself accepts for 'm'
+ *                                 (one channel) or 's' / 'j' / 'd' (two).  THE STANDARD'S MPEG-1 LIMITS BETWEEN MODE AND BITRATE ARE NOT
+ *                                 ENFORCED (32, 48, 56, 80 kbps are accepted for two channels, 224 kbps and more for one): the encoder
+ *                                 does not enforce them either, and a frame it made at such a cell must be acceptable as a feed.
+ *   tlb_feed_frame_bytes(cfg)     host only: the frame's length without a padding slot; < 0: -TLB_ERR_*
+ *   tlb_feed_set(b, stream, cfg)  stream = -1: every stream; cfg = NULL: the feed is removed (the stream is back to PCM input).  Legal between
+ *                                 launches (it waits for the queued ones), resets the feed history of the streams it names.  Every named
+ *                                 stream is checked before anything changes.
+ *   tlb_feed_get(b, stream, cfg)  1 and *cfg (may be NULL) when the stream has a feed, 0 when not; < 0: -TLB_ERR_ARG
+ *   tlb_feed_stride(b)            the longest feed frame over the batch, with its padding slot where the rate has one, rounded up to 4;
+ *                                 0: no stream has a feed.  It changes with tlb_feed_set: ask again after every set.
+ *   tlb_feed_reset(b, stream)     the stream's next feed frame is decoded as after silence (stream = -1: all); tlb_reset, tlb_stream_reset,
+ *                                 tlb_stream_finish and tlb_stream_reconfigure do the same for the streams they touch.
+ * tlb_stream_reconfigure to a sample rate or channel count the stream's feed no longer fits REMOVES the feed (the call itself succeeds):
+ * set a new one afterwards.
+ * Asynchronous on `hip_stream`; feed calls of one batch must be ordered on one stream, ahead of the ingest that reads their output.  Every
+ * buffer must be 4-byte aligned, as for tlb_decode_device.  Argument errors -- a NULL batch, frames, lengths or PCM pointer, nframes <= 0,
+ * a misaligned pointer, no stream with a feed -- return TLB_ERR_ARG and change nothing.  tlb_feed_host takes host buffers; its
+ * `interleaved` is read and written (the slots the kernel does not write come back as they went in).
+ * One wavefront per (stream, frame) with a feed.
+ * TICK PLANE.  tlb_tick_set_feed(t, stream, cfg) is legal while no tick is in flight (TLB_ERR_ARG otherwise; stream = -1: every stream,
+ * cfg = NULL: removed; every named stream is checked before one is changed).  While at least one stream has a feed, every submit queues
+ * the copy-in of the feed bytes and lengths, then the feed kernel, then the ingest, on the tick's existing streams and events; an object that
+ * never sets one queues exactly what it queued before.  A GROUP ALL OF WHOSE STREAMS HAVE FEEDS SKIPS ITS PCM COPY-IN -- 576 + 4 bytes
+ * per stream and tick at 192 kbps instead of 4608 --; a mixed group copies its PCM as before and the feed kernel then overwrites the fed
+ * streams' slots; a group without a fed stream queues nothing new.  (The groups are the contiguous stream ranges of tlb_tick_config.ngroups.)
+ *   tlb_tick_feed_stride(t)  bytes per slot of tlb_tick_feed(): the widest feed the object has had, rounded as tlb_feed_stride (it only
+ *                            grows); 0 while no stream has a feed
+ *   tlb_tick_feed(t)         uint8 [nstreams][tlb_tick_feed_stride()], tlb_tick_feed_len(t) int32 [nstreams]: pinned input buffers that
+ *                            alternate with the input sets of tlb_tick_pcm().  RE-FETCH them after every submit and after every
+ *                            tlb_tick_set_feed (a wider feed replaces the frame buffers).  NULL while two ticks are in flight and
+ *                            while no stream has a feed.  A set of lengths is all 0 (empty slots) whenever the caller sees it untouched.
+ *   tlb_tick_feed_report(t)  tlb_frame_report [nstreams] of the tick waited for last (it comes back with the silence counter); a stream
+ *                            without a feed reads TLB_DEC_EMPTY; NULL while no stream has a feed
+ * On one tick object feeds exclude SHORT READS and exclude SOURCE RATES (TLB_ERR_ARG, from either side and in either order): a feed
+ * frame is always 1152 sample frames at the stream's own rate.  Feeds compose with the monitor and the compare monitor, which see the
+ * planar PCM behind the ingest.  The stream life-cycle calls reset the feed history of the stream they touch;
+ * tlb_tick_stream_reconfigure removes a feed that no longer fits, as above.
+ * tlb_tick_set_feed is all or nothing for the feeds: after a device failure half way the groups already changed get back the feeds they
+ * had (with fresh history); buffers that were widened for the call stay.  After tlb_tick_finish, which runs no feed kernel,
+ * tlb_tick_feed_report shows the last tick's reports once more.
+ * NODE LEVEL.  tlb_node_set_feed routes to the owning shard (stream = -1: every stream; between steps only, TLB_ERR_ARG otherwise; every
+ * named stream is checked before a shard is changed; a broken shard answers TLB_ERR_HIP, a late one TLB_ERR_LATE; after a device failure
+ * half way the shards already changed get back the feeds they had) and is remembered: tlb_node_shard_restart sets the block's feeds again,
+ * with fresh history, and tlb_node_stream_reconfigure forgets a feed that no longer fits.  On a TICK-plane node feeds exclude short reads
+ * and source rates as on a tick object; on a BATCH-plane node the call is tlb_feed_set of the shard's batch and the caller decodes through
+ * tlb_node_batch() and tlb_feed_device.  TICK plane only: tlb_node_feed(nd, stream) and tlb_node_feed_len(nd, stream) point at the STREAM'S
+ * slot and length in its shard's current input set (tlb_node_feed_stride(nd, stream) bytes of room: shards differ), RE-FETCHED like
+ * tlb_node_pcm; NULL for a broken or late shard, while two ticks are in flight and while no stream of the shard has a feed.
+ * tlb_node_feed_report(nd, stream) is the stream's report of the step waited for last; NULL for a broken, late or stale shard and while no
+ * stream of the shard has a feed.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { long samplerate; int bitrate; int channels; } tlb_feed_config;   /* channels 1 | 2 */
+int tlb_feed_check_config(const tlb_feed_config *cfg);
+int tlb_feed_frame_bytes(const tlb_feed_config *cfg);
+int tlb_feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg);
+int tlb_feed_get(const tlb_batch *b, int stream, tlb_feed_config *cfg);
+int tlb_feed_stride(const tlb_batch *b);
+int tlb_feed_reset(tlb_batch *b, int stream);
+int tlb_feed_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report,
+                    void *hip_stream);
+int tlb_feed_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int nframes, int16_t *interleaved, tlb_frame_report *report);
+int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg);
+uint8_t *tlb_node_feed(tlb_node *nd, int stream);
+int32_t *tlb_node_feed_len(tlb_node *nd, int stream);
+int tlb_node_feed_stride(const tlb_node *nd, int stream);
+const tlb_frame_report *tlb_node_feed_report(const tlb_node *nd, int stream);
+int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg);
+int tlb_tick_feed_stride(const tlb_tick *t);
+uint8_t *tlb_tick_feed(tlb_tick *t);
+int32_t *tlb_tick_feed_len(tlb_tick *t);
+const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

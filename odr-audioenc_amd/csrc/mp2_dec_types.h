@@ -61,3 +61,20 @@ struct TlDecLaunch {
     unsigned long long *bad;          // frames with a TL_DEC_BAD_MASK flag so far
     int32_t nstreams, nframes, out_stride, pad_;
 };
+
+// One launch of the Layer II feed path (mp2_feed.h, toolame_feed.hip, tlb_feed.cpp): frames somebody else encoded, decoded into the
+// ingest's input.  A fed stream has a configuration record of its OWN here (its bitrate need not be the encoder's), and a history of
+// its own in the layout of the decoder's (TlDecStream: prev_len and prev_status are used, the ScF-CRC tail is not).
+struct TlFeedLaunch {
+    const TlTables *tables;
+    const TlConfig *configs;          // the feeds' records
+    const int32_t *feed_cfg;          // [nstreams] index into configs; -1: the stream has no feed
+    const TlSynthTables *synth;
+    const uint8_t *frames;            // [nframes][nstreams][stride]
+    const int32_t *len;               // [nframes][nstreams]; 0: an empty slot
+    TlFrameReport *report;            // [nframes][nstreams]
+    int16_t *pcm;                     // [nframes][nstreams][2304] interleaved: the ingest's input
+    TlDecStream *state;               // [nstreams]
+    uint8_t *prev;                    // [nstreams][prev_stride] the last slot of the launch before
+    int32_t nstreams, nframes, stride, prev_stride;       // both multiples of 4, each at least the longest frame of any feed of the batch
+};

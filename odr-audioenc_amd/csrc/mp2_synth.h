@@ -61,51 +61,21 @@ TL_FN void tl_synth_zero(int16_t *out, int n)
     TL_LANES_END
 }
 
-// ---- the unit of stage B: slot f of stream s -> 2 x 1152 samples.  Reads the reports stage A wrote for this slot and the one before. ----
+// ---- synthesis of ONE frame from its parsed side information (sd, xc over w.d[1]) and, with `hist`, that of the slot before it (sdp, xp over
+// w.d[0]; without: silence).  Sample i of channel c goes to out[c * cstep + i * sstep]: planar for the frame check / decode path (1152, 1),
+// interleaved for a feed (1, nch; mp2_feed.h).
 // `dwin`: the synthesis window TlSynthTables::d where the lanes re-read their eight coefficients per vector (the workgroup's LDS copy on the
 // device: 16 registers less than holding them).
-TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, const double *TL_RESTRICT dwin)
+TL_FN void tl_synth_frame(TlSynthLds &w, const TlBlockShared *TL_RESTRICT B, const TlPackTables *TL_RESTRICT K, const TlSynthTables *TL_RESTRICT Y, int nch,
+                          bool hist, const TlDecSide &sdp, const TlDecCells &xp, const TlDecSide &sd, const TlDecCells &xc, int16_t *out, int cstep, int sstep,
+                          const double *TL_RESTRICT dwin)
 {
-    const TlConfig *C = &A.configs[A.stream_cfg ? A.stream_cfg[s] : 0];
-    const TlBlockShared *B = &A.tables->shared;
-    const TlPackTables *K = &A.tables->pack;
-    const TlSynthTables *Y = A.synth;
-    const int nch = C->nch;
-    const size_t slot = (size_t)f * A.nstreams + s;
-    int16_t *out = A.pcm + slot * 2 * 1152;
-    if (A.report[slot].status & (TL_DEC_BAD_MASK | TL_DEC_EMPTY)) { tl_synth_zero(out, 2 * 1152); return; }
-    if (nch == 1) tl_synth_zero(out + 1152, 1152);
-
-    TlDecSide sdp, sd;
-    TlDecCells xp, xc;
-    bool hist = false;
-    {   // the slot before: in this launch, or what the launch before left
-        const uint8_t *psrc; int plen; uint32_t pst;
-        if (f > 0) {
-            const size_t ps = slot - (size_t)A.nstreams;
-            psrc = A.frames + ps * A.out_stride; plen = A.len ? A.len[ps] : A.out_stride; pst = A.report[ps].status;
-        } else { psrc = A.prev + (size_t)s * A.out_stride; plen = A.state[s].prev_len; pst = A.state[s].prev_status; }
-        plen = plen < A.out_stride ? plen : A.out_stride;
-        hist = plen > 0 && !(pst & (TL_DEC_BAD_MASK | TL_DEC_EMPTY));
-        if (hist) {
-            tl_dec_load(w.d[0], psrc, plen);
-            tl_dec_side<false>(w.d[0], B, K, C, plen, sdp, xp.ba, xp.qi, xp.scf, xp.sel, xp.o_smp);
-        }
-    }
-    {
-        int len = A.len ? A.len[slot] : A.out_stride;
-        len = len < A.out_stride ? len : A.out_stride;
-        tl_dec_load(w.d[1], A.frames + slot * A.out_stride, len);
-        tl_dec_side<false>(w.d[1], B, K, C, len, sd, xc.ba, xc.qi, xc.scf, xc.sel, xc.o_smp);
-    }
-
-    // ---- synthesis, a channel at a time ----
     PA(double, nk, 32);
     TL_LANES_BEGIN
     for (int k = 0; k < 32; k++) L(nk)[k] = Y->n[k][lane];
     TL_LANES_END
     for (int c = 0; c < nch; c++) {
-        int16_t *oc = out + c * 1152;
+        int16_t *oc = out + c * cstep;
         PA(double, ring, TL_SYNTH_BATCH); PV(double, q); PV(double, qprev);
         TL_LANES_BEGIN
         for (int i = 0; i < TL_SYNTH_BATCH; i++) L(ring)[i] = 0.0;
@@ -153,7 +123,7 @@ TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, cons
                         double x = (L(q) + hi) * 32768.0;
                         x = rint(x);
                         x = x > 32767.0 ? 32767.0 : x < -32768.0 ? -32768.0 : x;
-                        oc[((b - 1) * TL_SYNTH_BATCH + u) * 32 + lane] = (int16_t)(int)x;
+                        oc[(((b - 1) * TL_SYNTH_BATCH + u) * 32 + lane) * sstep] = (int16_t)(int)x;
                     }
                     TL_LANES_END
                 }
@@ -161,4 +131,42 @@ TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, cons
             }
         }
     }
+}
+
+// ---- the unit of stage B: slot f of stream s -> 2 x 1152 samples.  Reads the reports stage A wrote for this slot and the one before. ----
+TL_FN void tl_synth_unit(TlSynthLds &w, const TlDecLaunch &A, int s, int f, const double *TL_RESTRICT dwin)
+{
+    const TlConfig *C = &A.configs[A.stream_cfg ? A.stream_cfg[s] : 0];
+    const TlBlockShared *B = &A.tables->shared;
+    const TlPackTables *K = &A.tables->pack;
+    const TlSynthTables *Y = A.synth;
+    const int nch = C->nch;
+    const size_t slot = (size_t)f * A.nstreams + s;
+    int16_t *out = A.pcm + slot * 2 * 1152;
+    if (A.report[slot].status & (TL_DEC_BAD_MASK | TL_DEC_EMPTY)) { tl_synth_zero(out, 2 * 1152); return; }
+    if (nch == 1) tl_synth_zero(out + 1152, 1152);
+
+    TlDecSide sdp, sd;
+    TlDecCells xp, xc;
+    bool hist = false;
+    {   // the slot before: in this launch, or what the launch before left
+        const uint8_t *psrc; int plen; uint32_t pst;
+        if (f > 0) {
+            const size_t ps = slot - (size_t)A.nstreams;
+            psrc = A.frames + ps * A.out_stride; plen = A.len ? A.len[ps] : A.out_stride; pst = A.report[ps].status;
+        } else { psrc = A.prev + (size_t)s * A.out_stride; plen = A.state[s].prev_len; pst = A.state[s].prev_status; }
+        plen = plen < A.out_stride ? plen : A.out_stride;
+        hist = plen > 0 && !(pst & (TL_DEC_BAD_MASK | TL_DEC_EMPTY));
+        if (hist) {
+            tl_dec_load(w.d[0], psrc, plen);
+            tl_dec_side<false>(w.d[0], B, K, C, plen, sdp, xp.ba, xp.qi, xp.scf, xp.sel, xp.o_smp);
+        }
+    }
+    {
+        int len = A.len ? A.len[slot] : A.out_stride;
+        len = len < A.out_stride ? len : A.out_stride;
+        tl_dec_load(w.d[1], A.frames + slot * A.out_stride, len);
+        tl_dec_side<false>(w.d[1], B, K, C, len, sd, xc.ba, xc.qi, xc.scf, xc.sel, xc.o_smp);
+    }
+    tl_synth_frame(w, B, K, Y, nch, hist, sdp, xp, sd, xc, out, 1152, 1, dwin);
 }

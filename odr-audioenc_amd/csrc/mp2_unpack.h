@@ -16,6 +16,7 @@ struct TlDecLds {
 struct TlDecSide {
     uint32_t status;                 // BAD_SYNC, HEADER_MISMATCH, BAD_CRC16, BAD_ALLOC, OVERRUN as far as the frame alone shows them
     int mode, mode_ext, jsbound, frame_len;      // frame_len: what the configuration and the padding bit say
+    int start;                                   // first bit behind the header and its CRC-16: 48, or 32 in a feed frame without protection
     int p_smp, n_smp, audio_bits, maxpos;        // first sample bit, sample bits of one round of triples, end of the samples; last readable bit
     uint32_t crc_stored, crc_computed;
     uint32_t scfcrc[4];              // ScF-CRC of band groups 0..3 computed from the scalefactors (0 where the frame protects none)
@@ -53,7 +54,11 @@ TL_FN void tl_dec_load(TlDecLds &w, const uint8_t *TL_RESTRICT src, int nbytes)
 // cell's sample field inside one round of triples.  A joint-stereo cell of channel 1 above the bound gets channel 0's code, record and
 // offset (the shared samples) and its own scalefactors.  `sel` < 0 in cells that transmit none.
 // Every read position is clamped to the loaded bytes, every table index comes from a field no wider than its table.
-template <bool CRC>
+// FEED: the frame is somebody else's (mp2_feed.h), C the feed's configuration.  Sync, ID, layer, bitrate and sampling-frequency index must
+// be C's; the protection bit is read (with a CRC-16 the fields start at bit 48 and the CRC is verified, without one at bit 32); private,
+// copyright, original and emphasis are ignored; a two-channel feed's frames may be stereo, joint stereo with any bound or dual channel, a
+// one-channel feed's are mono; behind the samples comes ancillary data: no PAD is reserved and no ScF-CRC is computed.
+template <bool CRC, bool FEED = false>
 TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const TlPackTables *TL_RESTRICT K, const TlConfig *TL_RESTRICT C,
                        int nbytes, TlDecSide &sd, PARG(int, ba), PARG(unsigned, qi), PARGA(int, scf, 3), PARG(int, sel), PARG(int, o_smp))
 {
@@ -67,11 +72,15 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
     sd.mode = mode; sd.mode_ext = mode_ext;
     // ID, layer II, protection on, bitrate and sampling-frequency index, private bit, copyright / original / emphasis as the packer writes them
     const uint32_t want = ((uint32_t)C->version << 19) | (2u << 17) | ((uint32_t)C->br_idx << 12) | ((uint32_t)C->fs_idx << 10);
-    if ((h & 0x000ffd0fu) != want) st |= TL_DEC_HEADER_MISMATCH;
+    const uint32_t hdr_mask = FEED ? 0x000efc00u : 0x000ffd0fu;
+    if ((h & hdr_mask) != want) st |= TL_DEC_HEADER_MISMATCH;
+    const int start = FEED && ((h >> 16) & 1u) ? 32 : 48;
+    sd.start = start;
     if (padding && C->pad_frac == 0) st |= TL_DEC_HEADER_MISMATCH;
     // the mode: a joint-stereo stream's frames are stereo or joint stereo with any bound (the encoder chooses per frame), every other
     // stream's frames carry the configuration's mode and extension
-    const bool mode_ok = C->mode0 == 1 ? (mode == 1 || (mode == 0 && mode_ext == 0)) : (mode == C->mode0 && mode_ext == C->mode_ext0);
+    const bool mode_ok = FEED ? (C->nch == 2 ? mode != 3 : mode == 3)
+                       : C->mode0 == 1 ? (mode == 1 || (mode == 0 && mode_ext == 0)) : (mode == C->mode0 && mode_ext == C->mode_ext0);
     if (!mode_ok) { st |= TL_DEC_HEADER_MISMATCH; mode = C->mode0; mode_ext = C->mode_ext0; }
     const int jsbound = mode == 1 ? (4 * (mode_ext + 1) < sblimit ? 4 * (mode_ext + 1) : sblimit) : sblimit;
     sd.jsbound = jsbound;
@@ -91,7 +100,7 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
     const int n_ba = TL_WAVE_SUM_I32(f_ba);
     TL_LANES_BEGIN
     const int c = lane & 1, sb = lane >> 1;
-    int p = 48 + L(o_ba);
+    int p = start + L(o_ba);
     p = p < maxpos ? p : maxpos;
     w.balloc[c][sb] = (uint8_t)tl_get_bits48(frame, p, L(f_ba));
     TL_LANES_END
@@ -113,7 +122,7 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
     // ---- scfsi ----
     TL_WAVE_EXSCAN_I32(o_sel, f_sel);
     const int n_sel = TL_WAVE_SUM_I32(f_sel);
-    const int p_sel = 48 + n_ba, p_scf = p_sel + n_sel;
+    const int p_sel = start + n_ba, p_scf = p_sel + n_sel;
     PV(int, f_scf); PV(int, o_scf);
     TL_LANES_BEGIN
     int p = p_sel + L(o_sel);
@@ -154,15 +163,15 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
     // ---- bit budget: the fields and the smallest PAD (ScF-CRC + F-PAD) fit the frame; the slot holds the whole frame ----
     {
         const int have = nbytes < sd.frame_len ? nbytes : sd.frame_len;
-        if (sd.audio_bits > 8 * (have - C->dab_ext - 2) || nbytes < sd.frame_len) st |= TL_DEC_OVERRUN;
+        if (sd.audio_bits > 8 * (FEED ? have : have - C->dab_ext - 2) || nbytes < sd.frame_len) st |= TL_DEC_OVERRUN;
     }
-    sd.crc_stored = (frame[1] >> 16) & 0xffffu;
+    sd.crc_stored = start == 48 ? (frame[1] >> 16) & 0xffffu : 0u;
     sd.crc_computed = 0;
     sd.scfcrc[0] = sd.scfcrc[1] = sd.scfcrc[2] = sd.scfcrc[3] = 0;
-    if (CRC) {
+    if (CRC && start == 48) {
         // CRC-16 over header bits 16..31, bit_alloc and scfsi (crc.c:12-41), folded a byte per lane as the packer folds it (mp2_pack.h):
         // n <= 16 + 188 + 120 bits whatever the bytes say, so lanes 0..40 carry the message and 62 / 63 the preset
-        const int n = 16 + (p_scf - 48);
+        const int n = 16 + (p_scf - start);
         PV(uint32_t, part);
         TL_LANES_BEGIN
         uint32_t acc = 0;
@@ -180,6 +189,8 @@ TL_FN void tl_dec_side(TlDecLds &w, const TlBlockShared *TL_RESTRICT B, const Tl
         TL_LANES_END
         sd.crc_computed = TL_WAVE_XOR_U32(part) & 0xffffu;
         if (sd.crc_computed != sd.crc_stored) st |= TL_DEC_BAD_CRC16;
+    }
+    if (CRC && !FEED) {
         // ScF-CRC (crc.c:58-113): per band group the CRC-8 of the three MSBs of the transmitted scalefactors, as the packer computes it
         PV(int, rlen); PV(uint32_t, rcrc); PV(int, lex);
         TL_LANES_BEGIN

@@ -38,6 +38,8 @@ hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state
                      uint8_t *out, int32_t *out_len, int nstreams, int out_stride);
 // toolame_dec.hip: tl_unpack_kernel over every (stream, slot) of the launch, tl_synth_kernel when A.pcm is set, then tl_dec_carry_kernel per stream
 hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
+// toolame_feed.hip: tl_feed_kernel over every (stream, slot) of the launch, then tl_feed_carry_kernel per stream
+hipError_t tlk_feed(hipStream_t st, const TlFeedLaunch &A);
 // toolame_ingest.hip: tl_ingest_valid_kernel (one workgroup per slot, valid int32 [nframes][nstreams]) and tl_underrun_kernel (256 threads, one per stream)
 hipError_t tlk_ingest_valid(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid, int16_t *out, int16_t *peaks, const double *gain,
                             const TlConfig *configs, const int32_t *stream_cfg, int nstreams);

@@ -30,6 +30,7 @@ void tlb_destroy(tlb_batch *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->d_configs) (void)hipFree(b->d_configs);
+    if (b->d_feed_rep) (void)hipFree(b->d_feed_rep);
     for (int k = 0; k < 12; k++) if (b->stage[k]) (void)hipFree(b->stage[k]);
     for (int i = 0; i < TLB_HOST_CHUNKS; i++) { if (b->ev_in[i]) (void)hipEventDestroy(b->ev_in[i]); if (b->ev_run[i]) (void)hipEventDestroy(b->ev_run[i]); }
     if (b->s_in) (void)hipStreamDestroy(b->s_in);
@@ -179,6 +180,7 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
     if (b->d_pseq_tmp) HIPCHK(hipMemset(b->d_pseq_tmp + s0, 0, sizeof(uint16_t) * (size_t)n));
     if (b->d_dec_state) HIPCHK(hipMemset(b->d_dec_state + s0, 0, sizeof(TlDecStream) * (size_t)n));      // the decoder's next frame of these streams is a first frame
     if (b->d_cmp_hist) HIPCHK(hipMemset(b->d_cmp_hist + (size_t)s0 * 2 * TL_CMP_HIST, 0, sizeof(int16_t) * 2 * TL_CMP_HIST * (size_t)n));      // ... and the compare monitor has no input to set their next frame against
+    if (int rc = feed_clear_streams(b, s0, n)) return rc;            // ... and a feed's next frame is decoded as after silence
     return resample_clear_streams(b, s0, n);                         // ... and the resampler starts these streams' sources at frame 0 again
 }
 
@@ -279,6 +281,7 @@ int tlb_stream_reconfigure(tlb_batch *b, int stream, const tlb_stream_config *cf
         HIPCHK(hipMemcpy(b->d_frame_bytes + stream, &fb, sizeof fb, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b->d_unit_bytes + stream, &ub, sizeof ub, hipMemcpyHostToDevice));
     }
+    if (int rc = feed_after_reconfigure(b, stream)) return rc;       // a feed at another rate or channel count than the stream's new ones is removed
     return batch_clear_streams(b, stream, 1);
 }
 

@@ -8,22 +8,33 @@ static_assert(TLB_DEC_EMPTY == TL_DEC_EMPTY && TLB_DEC_BAD_SYNC == TL_DEC_BAD_SY
 static_assert(sizeof(tlb_frame_report) == sizeof(TlFrameReport) && sizeof(tlb_frame_fields) == sizeof(TlFrameFields), "C-ABI records");
 
 // The one pattern of a first-use allocation (csrc/tlb_mem.h): stage in a local owner, upload the tables, settle, commit, then set the fields.
-int decode_prepare(tlb_batch *b)
+int synth_prepare(tlb_batch *b)
 {
     if (b->d_synth) return TLB_OK;
-    const size_t n = (size_t)b->nstreams;
     TlbMem m;
     TlSynthTables *synth = m.scratch<TlSynthTables>(1);
-    TlDecStream *state = m.dev<TlDecStream>(n);
-    uint8_t *prev = m.dev<uint8_t>(n * (size_t)b->out_stride);
-    unsigned long long *bad = m.dev<unsigned long long>(1);
     TlSynthTables *hy = new TlSynthTables;
     tl_build_synth_tables(hy);
     m.upload(synth, hy, sizeof(TlSynthTables));
     delete hy;
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(b->mem);
+    b->d_synth = synth;
+    return TLB_OK;
+}
+
+int decode_prepare(tlb_batch *b)
+{
+    if (b->d_dec_state) return TLB_OK;
+    if (int rc = synth_prepare(b)) return rc;
+    const size_t n = (size_t)b->nstreams;
+    TlbMem m;
+    TlDecStream *state = m.dev<TlDecStream>(n);
+    uint8_t *prev = m.dev<uint8_t>(n * (size_t)b->out_stride);
+    unsigned long long *bad = m.dev<unsigned long long>(1);
     if (!m.settle()) return TLB_ERR_HIP;         // the first call (only) waits for the device
     m.commit(b->mem);
-    b->d_synth = synth; b->d_dec_state = state; b->d_dec_prev = prev; b->d_dec_bad = bad;
+    b->d_dec_state = state; b->d_dec_prev = prev; b->d_dec_bad = bad;
     return TLB_OK;
 }
 

@@ -1,0 +1,236 @@
+// tlb_feed.cpp -- the batch-level entry points of the Layer II feeds (include/toolame_batch.h, tlb_feed_*): the legality of a feed
+// configuration (host only), the per-stream feed table and history (allocated by the first tlb_feed_set) and one launch of the kernels of
+// toolame_feed.hip through tl_kernels.h.  Host C++.
+#include "tlb_internal.h"
+
+static char feed_mode(int channels) { return channels == 1 ? 'm' : 's'; }
+// the feed's kernel-side record: the stream configuration a frame of that rate, bitrate and channel count has (allocation table, sblimit,
+// frame length, header indices); the mode is the frame's own and the model plays no part
+static int feed_build(TlConfig *c, const tlb_feed_config *cfg)
+{
+    if (!cfg) return TLB_ERR_ARG;
+    if (cfg->channels != 1 && cfg->channels != 2) return TLB_ERR_MODE;
+    if (cfg->bitrate <= 0) return TLB_ERR_BITRATE;
+    return tl_build_config(c, cfg->samplerate, feed_mode(cfg->channels), cfg->bitrate, 1, 0);
+}
+static bool feed_same(const tlb_feed_config &a, const tlb_feed_config &b) { return a.samplerate == b.samplerate && a.bitrate == b.bitrate && a.channels == b.channels; }
+static int slot_bytes(const TlConfig &c) { return (c.frame_bytes + (c.pad_frac != 0 ? 1 : 0) + 3) & ~3; }
+
+int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
+{
+    if (int rc = tlb_feed_check_config(cfg)) return rc;
+    for (int s = s0; s < s1; s++) {
+        const tlb_stream_config &sc = b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]];
+        if (cfg->samplerate != sc.samplerate) return TLB_ERR_SAMPLERATE;
+        if (cfg->channels != (sc.mode == 'm' ? 1 : 2)) return TLB_ERR_MODE;
+    }
+    return TLB_OK;
+}
+
+int feed_slot_bytes(const tlb_feed_config *cfg)
+{
+    TlConfig *c = new TlConfig;
+    const int n = feed_build(c, cfg) ? 0 : slot_bytes(*c);
+    delete c;
+    return n;
+}
+
+int feed_clear_streams(tlb_batch *b, int s0, int n)
+{
+    if (!b->d_feed_state) return TLB_OK;
+    HIPCHK(hipMemset(b->d_feed_state + s0, 0, sizeof(TlDecStream) * (size_t)n));
+    return TLB_OK;
+}
+
+// the first tlb_feed_set: the synthesis tables (shared with the decoder), the stream -> feed table (all -1) and the history records
+static int feed_prepare(tlb_batch *b)
+{
+    if (b->d_feed_cfg) return TLB_OK;
+    if (int rc = synth_prepare(b)) return rc;
+    const size_t n = (size_t)b->nstreams;
+    TlbMem m;
+    int32_t *fc = m.scratch<int32_t>(n);
+    TlDecStream *st = m.dev<TlDecStream>(n);
+    std::vector<int32_t> none(n, -1);
+    m.upload(fc, none.data(), sizeof(int32_t) * n);
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(b->mem);
+    b->feed_cfg.assign(n, tlb_feed_config{0, 0, 0}); b->feed_idx.assign(n, -1);
+    b->d_feed_cfg = fc; b->d_feed_state = st;
+    return TLB_OK;
+}
+
+// room for `count` records in d_feed_configs and for slots of `stride` bytes in d_feed_prev; what they hold is kept (the device is idle)
+static int feed_reserve(tlb_batch *b, size_t count, int stride)
+{
+    // each of the two has an owner of its own (csrc/tlb_mem.h): the new buffer is staged and filled in a new owner, and only when it is
+    // complete do the owners change places -- the old buffer goes with the old owner, a failure leaves everything as it was
+    if (count > b->feed_cfg_cap) {
+        std::unique_ptr<TlbMem> m(new TlbMem);
+        const size_t cap = count + 4;
+        TlConfig *nd = m->scratch<TlConfig>(cap);
+        if (!b->h_feed_configs.empty()) m->upload(nd, b->h_feed_configs.data(), sizeof(TlConfig) * b->h_feed_configs.size());
+        if (!m->settle()) return TLB_ERR_HIP;
+        b->feed_cfg_mem.swap(m);
+        b->d_feed_configs = nd; b->feed_cfg_cap = cap;
+    }
+    if (stride > b->feed_prev_stride) {
+        std::unique_ptr<TlbMem> m(new TlbMem);
+        uint8_t *np = m->dev<uint8_t>((size_t)b->nstreams * (size_t)stride);
+        if (m->failed()) return TLB_ERR_HIP;
+        if (b->d_feed_prev)
+            HIPCHK(hipMemcpy2D(np, (size_t)stride, b->d_feed_prev, (size_t)b->feed_prev_stride, (size_t)b->feed_prev_stride, (size_t)b->nstreams, hipMemcpyDeviceToDevice));
+        if (!m->settle()) return TLB_ERR_HIP;
+        b->feed_prev_mem.swap(m);
+        b->d_feed_prev = np; b->feed_prev_stride = stride;
+    }
+    return TLB_OK;
+}
+
+// streams [s0, s1) get feed record `idx` (-1: none); their history starts again
+static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_config &cfg)
+{
+    std::vector<int32_t> v((size_t)(s1 - s0), idx);
+    HIPCHK(hipMemcpy(b->d_feed_cfg + s0, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
+    for (int s = s0; s < s1; s++) { b->feed_idx[(size_t)s] = idx; b->feed_cfg[(size_t)s] = cfg; }
+    return feed_clear_streams(b, s0, s1 - s0);
+}
+
+int feed_after_reconfigure(tlb_batch *b, int stream)
+{
+    if (b->feed_idx.empty() || b->feed_idx[(size_t)stream] < 0) return TLB_OK;
+    const tlb_stream_config &sc = b->h_uniq[(size_t)b->h_stream_cfg[(size_t)stream]];
+    const tlb_feed_config &fc = b->feed_cfg[(size_t)stream];
+    if (fc.samplerate == sc.samplerate && fc.channels == (sc.mode == 'm' ? 1 : 2)) return TLB_OK;
+    return feed_assign(b, stream, stream + 1, -1, tlb_feed_config{0, 0, 0});
+}
+
+int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride)
+{
+    if (!b || !d_frames || !d_len || !d_interleaved || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
+    // the kernels move frames and PCM as 32-bit words and store 32-bit report fields
+    if (((uintptr_t)d_frames | (uintptr_t)d_len | (uintptr_t)d_interleaved | (uintptr_t)d_report) & 3u) return TLB_ERR_ARG;
+    if (tlb_feed_stride(b) == 0 || stride < tlb_feed_stride(b) || (stride & 3)) return TLB_ERR_ARG;      // (0: no stream has a feed)
+    if (b->broken) return TLB_ERR_HIP;
+    HIPCHK(hipSetDevice(b->device));
+    if (!d_report) {                             // the history pass reads the last slot's status: a report buffer of the batch's own, grow-only
+        const size_t bytes = (size_t)nframes * (size_t)b->nstreams * sizeof(tlb_frame_report);
+        if (b->feed_rep_cap < bytes) {
+            HIPCHK(hipDeviceSynchronize());      // (a launch before may still write the one it replaces)
+            if (b->d_feed_rep) { (void)hipFree(b->d_feed_rep); b->d_feed_rep = nullptr; b->feed_rep_cap = 0; }
+            HIPCHK(hipMalloc(&b->d_feed_rep, bytes));
+            b->feed_rep_cap = bytes;
+        }
+        d_report = (tlb_frame_report *)b->d_feed_rep;
+    }
+    TlFeedLaunch A;
+    memset(&A, 0, sizeof A);
+    A.tables = b->d_tables; A.configs = b->d_feed_configs; A.feed_cfg = b->d_feed_cfg; A.synth = b->d_synth;
+    A.frames = d_frames; A.len = d_len; A.report = (TlFrameReport *)d_report; A.pcm = d_interleaved;
+    A.state = b->d_feed_state; A.prev = b->d_feed_prev; A.prev_stride = b->feed_prev_stride;
+    A.nstreams = b->nstreams; A.nframes = nframes; A.stride = stride;
+    HIPCHK(tlk_feed((hipStream_t)hip_stream, A));
+    return TLB_OK;
+}
+
+extern "C" {
+
+int tlb_feed_check_config(const tlb_feed_config *cfg)
+{
+    TlConfig *c = new TlConfig;
+    const int rc = feed_build(c, cfg);
+    delete c;
+    return rc;
+}
+
+int tlb_feed_frame_bytes(const tlb_feed_config *cfg)
+{
+    TlConfig *c = new TlConfig;
+    const int rc = feed_build(c, cfg);
+    const int n = rc ? -rc : c->frame_bytes;
+    delete c;
+    return n;
+}
+
+int tlb_feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg)
+{
+    if (!b || stream < -1 || stream >= b->nstreams) return TLB_ERR_ARG;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
+    if (!cfg) {
+        if (!b->d_feed_cfg) return TLB_OK;                           // off, and never on: nothing to allocate or to clear
+        HIPCHK(hipSetDevice(b->device));
+        HIPCHK(hipDeviceSynchronize());
+        return feed_assign(b, s0, s1, -1, tlb_feed_config{0, 0, 0});
+    }
+    if (int rc = feed_fits(b, s0, s1, cfg)) return rc;               // every named stream is checked before anything changes
+    int idx = -1;
+    for (size_t i = 0; i < b->h_feed_uniq.size(); i++) if (feed_same(b->h_feed_uniq[i], *cfg)) idx = (int)i;
+    TlConfig *c = new TlConfig;
+    struct Free { TlConfig *c; ~Free() { delete c; } } free_{c};
+    if (idx >= 0) *c = b->h_feed_configs[(size_t)idx];
+    else if (int rc = feed_build(c, cfg)) return rc;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (int rc = feed_prepare(b)) return rc;
+    if (int rc = feed_reserve(b, b->h_feed_configs.size() + (idx < 0 ? 1 : 0), slot_bytes(*c))) return rc;
+    if (idx < 0) {
+        idx = (int)b->h_feed_configs.size();
+        HIPCHK(hipMemcpy(b->d_feed_configs + idx, c, sizeof(TlConfig), hipMemcpyHostToDevice));
+        b->h_feed_configs.push_back(*c); b->h_feed_uniq.push_back(*cfg);
+    }
+    return feed_assign(b, s0, s1, idx, *cfg);
+}
+
+int tlb_feed_get(const tlb_batch *b, int stream, tlb_feed_config *cfg)
+{
+    if (!b || stream < 0 || stream >= b->nstreams) return -TLB_ERR_ARG;
+    const bool on = !b->feed_idx.empty() && b->feed_idx[(size_t)stream] >= 0;
+    if (cfg) *cfg = on ? b->feed_cfg[(size_t)stream] : tlb_feed_config{0, 0, 0};
+    return on ? 1 : 0;
+}
+
+int tlb_feed_stride(const tlb_batch *b)
+{
+    int stride = 0;
+    if (b) for (int idx : b->feed_idx) if (idx >= 0 && slot_bytes(b->h_feed_configs[(size_t)idx]) > stride) stride = slot_bytes(b->h_feed_configs[(size_t)idx]);
+    return stride;
+}
+
+int tlb_feed_reset(tlb_batch *b, int stream)
+{
+    if (!b || stream < -1 || stream >= b->nstreams) return TLB_ERR_ARG;
+    if (!b->d_feed_state) return TLB_OK;         // never fed: every stream's next frame is a first frame already
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());
+    return stream < 0 ? feed_clear_streams(b, 0, b->nstreams) : feed_clear_streams(b, stream, 1);
+}
+
+int tlb_feed_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report,
+                    void *hip_stream)
+{
+    return feed_launch(b, d_frames, d_len, nframes, d_interleaved, d_report, hip_stream, tlb_feed_stride(b));
+}
+
+
+int tlb_feed_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int nframes, int16_t *interleaved, tlb_frame_report *report)
+{
+    if (!b || !frames || !len || !interleaved || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30)) return TLB_ERR_ARG;
+    const int stride = tlb_feed_stride(b);
+    if (stride == 0) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t slots = (size_t)nframes * (size_t)b->nstreams;
+    TlbMem m;
+    uint8_t *d_frames = m.scratch<uint8_t>(slots * (size_t)stride); int32_t *d_len = m.scratch<int32_t>(slots);
+    int16_t *d_pcm = m.scratch<int16_t>(slots * 2304); tlb_frame_report *d_report = m.scratch<tlb_frame_report>(slots);
+    MEMCHK(m);
+    HIPCHK(hipMemcpy(d_frames, frames, slots * (size_t)stride, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_len, len, slots * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_pcm, interleaved, slots * 2304 * sizeof(int16_t), hipMemcpyHostToDevice));      // what the kernel does not write (streams without a feed, behind a one-channel feed's 1152 samples) stays the caller's
+    if (int rc = tlb_feed_device(b, d_frames, d_len, nframes, d_pcm, d_report, nullptr)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(interleaved, d_pcm, slots * 2304 * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (report) HIPCHK(hipMemcpy(report, d_report, slots * sizeof(tlb_frame_report), hipMemcpyDeviceToHost));
+    return TLB_OK;
+}
+
+}  // extern "C"

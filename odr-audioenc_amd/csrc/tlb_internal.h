@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <deque>
+#include <memory>
 #include <vector>
 
 #include "../../include/toolame_batch.h"
@@ -79,6 +80,20 @@ struct tlb_batch {
     int rs_flip = 0;
     std::vector<long> rs_rate;                   // [nstreams] source rate, 0: off (empty until the first set_source)
     std::vector<int32_t> rs_ratio, rs_pos;       // host copies: TL_RS_* and the frame position in the need cycle
+    // Layer II feeds (tlb_feed.cpp), allocated by the first tlb_feed_set: a batch that never sets a feed has none of it
+    std::vector<tlb_feed_config> feed_cfg;       // [nstreams] the stream's feed (empty until the first set)
+    std::vector<int32_t> feed_idx;               // [nstreams] its record in h_feed_configs, -1: no feed
+    std::vector<tlb_feed_config> h_feed_uniq;    // the three knobs of h_feed_configs[i]; grow-only
+    std::vector<TlConfig> h_feed_configs;
+    TlConfig *d_feed_configs = nullptr;          // replaced when it grows: an owner of its own (feed_cfg_mem), as has d_feed_prev (feed_prev_mem)
+    std::unique_ptr<TlbMem> feed_cfg_mem, feed_prev_mem;
+    size_t feed_cfg_cap = 0;
+    int32_t *d_feed_cfg = nullptr;               // [nstreams] feed_idx on the device
+    TlDecStream *d_feed_state = nullptr;         // [nstreams] the feed history, separate from the decoder's
+    uint8_t *d_feed_prev = nullptr;              // [nstreams][feed_prev_stride] the last slot of the call before; replaced when a longer feed frame arrives
+    int feed_prev_stride = 0;
+    void *d_feed_rep = nullptr;                  // reports of a tlb_feed_device call that asked for none (grow-only)
+    size_t feed_rep_cap = 0;
     TlbMem mem;                                  // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -107,8 +122,19 @@ int tlb_launch(tlb_batch *b, const int16_t *d_pcm, int nframes, const uint8_t *d
 int zmq_frame_device(tlb_batch *b, const uint8_t *d_frames, const int16_t *d_peaks, int nframes, uint8_t *d_msgs, void *hip_stream, const int32_t *d_frame_len);
 int edi_af_device(tlb_batch *b, const uint8_t *d_frames, const int16_t *d_levels, int nframes, tlb_edi_state *d_state,
                   const char *version, int version_len, uint8_t *d_pkts, int32_t *d_pkt_len, void *hip_stream, const int32_t *d_frame_len);
-// tlb_decode.cpp: the decoder's tables and per-stream state, as the first decode call makes them (it waits for the device once)
+// tlb_decode.cpp: the decoder's tables and per-stream state, as the first decode call makes them (it waits for the device once); the
+// synthesis tables alone, which the feeds share
 int decode_prepare(tlb_batch *b);
+int synth_prepare(tlb_batch *b);
+// tlb_feed.cpp: the feed history of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); after a reconfiguration,
+// the stream's feed removed when its rate or channel count no longer is the stream's
+int feed_clear_streams(tlb_batch *b, int s0, int n);
+int feed_after_reconfigure(tlb_batch *b, int stream);
+// ... what the tick plane needs of it: is cfg legal and does it fit streams [s0, s1) (nothing changes); the slot a frame of cfg needs;
+// tlb_feed_device with slots of `stride` bytes, at least tlb_feed_stride(b) (a tick object has ONE stride for all its groups)
+int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
+int feed_slot_bytes(const tlb_feed_config *cfg);
+int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
 // tlb_compare.cpp: the history as the first compare call makes it; the launch itself with a report that may be NULL (every slot skipped:
 // a tick that has no frames yet still advances the history)
 int compare_prepare(tlb_batch *b);

@@ -157,7 +157,9 @@ struct tlb_node {
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
     std::vector<long> source;                    // tlb_node_set_source(): the source rate of every stream (0: off), set again on a restarted shard; empty: never set
+    std::vector<tlb_feed_config> feed;           // tlb_node_set_feed(): the feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
+    bool any_feed() const { for (const tlb_feed_config &f : feed) if (f.bitrate) return true; return false; }
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
@@ -298,6 +300,11 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         const long r = nd->source[(size_t)(s.first + k)];
         if (r == 0) continue;
         if (int rc = s.tick ? tlb_tick_set_source(s.tick, k, r) : tlb_resample_set_source(s.batch, k, r)) return rc;
+    }
+    for (int k = 0; k < s.n && !nd->feed.empty(); k++) {             // the caller's feeds, with fresh history
+        const tlb_feed_config &f = nd->feed[(size_t)(s.first + k)];
+        if (!f.bitrate) continue;
+        if (int rc = s.tick ? tlb_tick_set_feed(s.tick, k, &f) : tlb_feed_set(s.batch, k, &f)) return rc;
     }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
@@ -543,6 +550,7 @@ int tlb_node_enable_short_reads(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
     for (long r : nd->source) if (r) return TLB_ERR_ARG;             // a source and short reads exclude each other (include/toolame_batch.h)
+    if (nd->any_feed()) return TLB_ERR_ARG;                          // ... and so do a feed and short reads
     if (nd->short_reads) return TLB_OK;
     const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
     if (!rc) nd->short_reads = true;
@@ -614,7 +622,7 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     bool any = false;
     if (int rc = tlb_source_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
-    if (any && nd->short_reads) return TLB_ERR_ARG;
+    if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && nd->any_feed()))) return TLB_ERR_ARG;
     for (Shard *s : nd->shards) {
         if (s->first >= s1 || s->first + s->n <= s0) continue;
         if (s->late) return TLB_ERR_LATE;
@@ -636,6 +644,74 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
     }
     for (int i = s0; i < s1; i++) nd->source[(size_t)i] = source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate;
     return TLB_OK;
+}
+// A Layer II feed for one stream or all (cfg = NULL: removed): to the owning shards' objects, on their threads, between steps.  Every named
+// stream is checked before a shard is changed; a broken shard answers TLB_ERR_HIP, a late one TLB_ERR_LATE, before anything changes; after
+// a device failure half way the shards already changed get back the feeds they had.  What went through is remembered for restarts.
+int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
+{
+    if (!nd || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
+    if (cfg) {
+        if (int rc = tlb_feed_check_config(cfg)) return rc;
+        for (int i = s0; i < s1; i++) {
+            if (cfg->samplerate != nd->cfgs[(size_t)i].samplerate) return TLB_ERR_SAMPLERATE;
+            if (cfg->channels != (nd->cfgs[(size_t)i].mode == 'm' ? 1 : 2)) return TLB_ERR_MODE;
+        }
+        if (nd->plane == TLB_NODE_TICK) {                            // feeds exclude short reads and sources on one object (include/toolame_batch.h)
+            if (nd->short_reads) return TLB_ERR_ARG;
+            for (long r : nd->source) if (r) return TLB_ERR_ARG;
+        }
+    }
+    for (Shard *s : nd->shards) {
+        if (s->first >= s1 || s->first + s->n <= s0) continue;
+        if (s->late) return TLB_ERR_LATE;
+        if (!s->live()) return TLB_ERR_HIP;
+    }
+    if (nd->feed.empty()) { if (!cfg) return TLB_OK; nd->feed.assign((size_t)nd->nstreams, tlb_feed_config{0, 0, 0}); }
+    auto set = [](Shard &sh, int kk, const tlb_feed_config *c) { return sh.tick ? tlb_tick_set_feed(sh.tick, kk, c) : tlb_feed_set(sh.batch, kk, c); };
+    for (Shard *s : nd->shards) {
+        if (s->first >= s1 || s->first + s->n <= s0) continue;
+        const int k = stream < 0 ? -1 : stream - s->first;
+        const int rc = nd->one(s->index, [&](Shard &sh) { return set(sh, k, cfg); });
+        if (rc) {
+            for (Shard *u : nd->shards) {
+                if (u->index > s->index || u->first >= s1 || u->first + u->n <= s0) continue;
+                (void)nd->one(u->index, [&](Shard &sh) {
+                    for (int i = 0; i < sh.n; i++) { const tlb_feed_config &f = nd->feed[(size_t)(sh.first + i)]; (void)set(sh, i, f.bitrate ? &f : nullptr); }
+                    return 0;
+                });
+            }
+            return rc;
+        }
+    }
+    for (int i = s0; i < s1; i++) nd->feed[(size_t)i] = cfg ? *cfg : tlb_feed_config{0, 0, 0};
+    return TLB_OK;
+}
+// the stream's slot of its shard's feed buffers (tlb_tick_feed / _feed_len of the shard's tick object): NULL for a broken or a late shard, while
+// two ticks are in flight and while no stream of the shard has a feed
+uint8_t *tlb_node_feed(tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
+    uint8_t *p = s && s->tick ? tlb_tick_feed(s->tick) : nullptr;
+    return p ? p + (size_t)k * (size_t)tlb_tick_feed_stride(s->tick) : nullptr;
+}
+int32_t *tlb_node_feed_len(tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
+    int32_t *p = s && s->tick ? tlb_tick_feed_len(s->tick) : nullptr;
+    return p ? p + k : nullptr;
+}
+int tlb_node_feed_stride(const tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
+    return s && s->tick ? tlb_tick_feed_stride(s->tick) : 0;
+}
+const tlb_frame_report *tlb_node_feed_report(const tlb_node *nd, int stream)
+{
+    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
+    const tlb_frame_report *p = s && s->tick ? tlb_tick_feed_report(s->tick) : nullptr;
+    return p ? p + k : nullptr;
 }
 int tlb_node_need(const tlb_node *nd, int stream)
 {
@@ -806,6 +882,10 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
     if (!s->live()) return TLB_ERR_HIP;
     const int rc = nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reconfigure(sh.tick, k, cfg) : tlb_stream_reconfigure(sh.batch, k, cfg); });
     if (!rc) nd->cfgs[(size_t)stream] = *cfg;                        // a restart of the shard re-creates the stream as it is NOW
+    if (!rc && !nd->feed.empty()) {                                  // a feed the new rate or channel count no longer fits has been removed
+        tlb_feed_config &f = nd->feed[(size_t)stream];
+        if (f.bitrate && (f.samplerate != cfg->samplerate || f.channels != (cfg->mode == 'm' ? 1 : 2))) f = tlb_feed_config{0, 0, 0};
+    }
     return rc;
 }
 

@@ -2,6 +2,8 @@
 #include "tlb_internal.h"
 #include "tlb_plan.h"
 
+#include <memory>
+
 // ------------------------------------------------------------------------------------------
 // The caller's real-time loop body as ONE call per tick (include/toolame_batch.h, tlb_tick_*): what AudioEnc::run() does for
 // one stream every 24 ms -- gain / peak / de-interleave (src/odr-audioenc.cpp:1030-1051,1139-1152), toolame_encode_frame
@@ -33,6 +35,9 @@ struct TickGroup {
     // confidence monitor (tlb_tick_enable_monitor): the decode call's reports (and PCM under AUDIO) of this tick's frames, the folded records
     tlb_frame_report *d_report = nullptr; int16_t *d_mpcm = nullptr; tlb_monitor_record *d_record = nullptr;
     tlb_compare_record *d_crecord = nullptr;                    // compare monitor (tlb_tick_enable_compare): the group's records
+    // Layer II feeds (tlb_tick_set_feed): the group's slice of the tick's feed frames and lengths, the feed call's reports
+    uint8_t *d_feed = nullptr; int32_t *d_feed_len = nullptr; tlb_frame_report *d_feed_report = nullptr;
+    bool any_fed = false, all_fed = false;                      // some / every stream of the group has a feed (all: the group's PCM is not copied in)
     hipEvent_t ev_mon = nullptr;                                // decode + fold (+ compare) done: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
@@ -60,6 +65,14 @@ struct tlb_tick {
     int listen_of[3] = {-1, -1, -1};             // ... the tick of each output set carried
     bool resample = false;                       // at least one stream has a source: every submit queues the resampler between copy-in and ingest
                                                  // (the groups' d_rs buffers, once made, stay until destroy)
+    // Layer II feeds, off until the first tlb_tick_set_feed: the frames and their lengths travel with the input sets, the reports with the
+    // output sets.  feed_stride is ONE slot width for every group (the widest feed the object has had: it only grows); the frame buffers
+    // are replaced when it grows and have an owner of their own (feed_mem: the old owner goes when the new one is complete), the rest
+    // belongs to `mem`.
+    bool feed = false;                           // at least one stream has a feed
+    int feed_stride = 0;
+    uint8_t *h_feed[2] = {}; int32_t *h_feed_len[2] = {}; tlb_frame_report *h_feed_report[3] = {};
+    std::unique_ptr<TlbMem> feed_mem;            // owns h_feed[] and the groups' d_feed
     // compare monitor, off until tlb_tick_enable_compare(): needs the AUDIO monitor's decoded PCM; its records travel with the output sets too
     bool compare = false;
     tlb_compare_params cparams = {};
@@ -222,7 +235,7 @@ const uint32_t *tlb_tick_underruns(const tlb_tick *t) { return t && t->short_rea
 // call makes the device calls it always made.
 int tlb_tick_enable_short_reads(tlb_tick *t)
 {
-    if (!t || t->finished || t->ticks > 0 || t->resample) return TLB_ERR_ARG;      // (a source and short reads exclude each other: include/toolame_batch.h)
+    if (!t || t->finished || t->ticks > 0 || t->resample || t->feed) return TLB_ERR_ARG;      // (a source or a feed and short reads exclude each other: include/toolame_batch.h)
     if (t->broken) return TLB_ERR_HIP;
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
@@ -327,7 +340,7 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
         real[g] = r; any |= r;
     }
     if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
-    if (any && t->short_reads) return TLB_ERR_ARG;
+    if (any && (t->short_reads || t->feed)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
     if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer, and the resampler of the batches that get
         TlbMem m;                                                    // a source, before anything is committed or a stream is changed
@@ -348,6 +361,89 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
         for (int k = 0; k < G.n; k++) if (tlb_resample_source(G.b, k)) t->resample = true;
     return rc;
 }
+// A Layer II feed for one stream or all (tlb_feed_set of the group's batch), while no tick is in flight.  The first feed gives the object
+// its pinned feed buffers and every group its device ones; a wider feed than any before replaces the frame buffers (RE-FETCH).  An object
+// that never sets one makes the device calls it always made.
+static void tick_feed_refresh(tlb_tick *t)
+{
+    t->feed = false;
+    for (auto &G : t->groups) {
+        int fed = 0;
+        for (int k = 0; k < G.n; k++) fed += tlb_feed_get(G.b, k, nullptr) > 0;
+        G.any_fed = fed > 0; G.all_fed = fed == G.n;
+        t->feed |= G.any_fed;
+        // a group without a fed stream runs no feed kernel: its streams read EMPTY (no tick is in flight, or the device has been waited for)
+        if (!G.any_fed && t->h_feed_report[0])
+            for (int k = 0; k < 3; k++) for (int i = 0; i < G.n; i++) { tlb_frame_report r = {}; r.status = TLB_DEC_EMPTY; t->h_feed_report[k][G.first + i] = r; }
+    }
+}
+int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
+{
+    if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (!cfg && !t->h_feed_len[0]) return TLB_OK;                    // off, and never on: nothing to allocate or to clear
+    if (cfg) {
+        if (t->short_reads || t->resample) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads and sources)
+        for (auto &G : t->groups) {                                  // every stream is checked before one is changed
+            const int s0 = stream < 0 ? 0 : stream - G.first, s1 = stream < 0 ? G.n : s0 + 1;
+            if (s0 < 0 || s0 >= G.n) continue;
+            if (int rc = feed_fits(G.b, s0, s1, cfg)) return rc;
+        }
+    }
+    HIPCHK(hipSetDevice(t->device));
+    const size_t ns = (size_t)t->nstreams;
+    if (!t->h_feed_len[0]) {                                         // the first feed: lengths and reports, made once
+        TlbMem m;
+        std::vector<TickGroup> gs = t->groups;
+        int32_t *h_len[2]; tlb_frame_report *h_rep[3];
+        for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(ns);
+        for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(ns);
+        for (auto &G : gs) { G.d_feed_len = m.dev<int32_t>((size_t)G.n); G.d_feed_report = m.dev<tlb_frame_report>((size_t)G.n); }
+        if (!m.settle()) return TLB_ERR_HIP;
+        m.commit(t->mem);
+        t->groups.swap(gs);
+        memcpy(t->h_feed_len, h_len, sizeof h_len); memcpy(t->h_feed_report, h_rep, sizeof h_rep);
+    }
+    const int want = cfg ? feed_slot_bytes(cfg) : 0;
+    if (want > t->feed_stride) {                                     // wider slots: new frame buffers, all of them before any is let go (no tick is in flight)
+        std::unique_ptr<TlbMem> m(new TlbMem);                       // stage, settle, then the owners change places: the narrower buffers go with the old one
+        uint8_t *h[2];
+        std::vector<uint8_t *> d(t->groups.size(), nullptr);
+        for (int k = 0; k < 2; k++) h[k] = m->pinned<uint8_t>(ns * (size_t)want);
+        for (size_t g = 0; g < d.size(); g++) d[g] = m->scratch<uint8_t>((size_t)t->groups[g].n * (size_t)want);
+        if (!m->settle()) return TLB_ERR_HIP;
+        t->feed_mem.swap(m);
+        for (int k = 0; k < 2; k++) t->h_feed[k] = h[k];
+        for (size_t g = 0; g < d.size(); g++) t->groups[g].d_feed = d[g];
+        t->feed_stride = want;
+    }
+    // what the named streams have now: after a device failure half way the groups already changed get it back (fresh history), so that
+    // "all or nothing" holds for the feeds themselves; the wider buffers stay
+    std::vector<tlb_feed_config> before(ns, tlb_feed_config{0, 0, 0});
+    for (auto &G : t->groups) for (int k = 0; k < G.n; k++) (void)tlb_feed_get(G.b, k, &before[(size_t)(G.first + k)]);
+    int rc = TLB_OK;
+    for (auto &G : t->groups) {
+        if (stream >= 0 && (stream < G.first || stream >= G.first + G.n)) continue;
+        if ((rc = tlb_feed_set(G.b, stream < 0 ? -1 : stream - G.first, cfg))) {
+            for (auto &U : t->groups) {
+                if (U.first > G.first || (stream >= 0 && (stream < U.first || stream >= U.first + U.n))) continue;
+                for (int k = 0; k < U.n; k++) {
+                    if (stream >= 0 && stream != U.first + k) continue;
+                    const tlb_feed_config &f = before[(size_t)(U.first + k)];
+                    (void)tlb_feed_set(U.b, k, f.bitrate ? &f : nullptr);
+                }
+            }
+            break;
+        }
+    }
+    tick_feed_refresh(t);
+    for (int k = 0; k < 2; k++) memset(t->h_feed_len[k], 0, ns * sizeof(int32_t));
+    return rc;
+}
+uint8_t *tlb_tick_feed(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed[t->in_set] : nullptr; }
+int32_t *tlb_tick_feed_len(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed_len[t->in_set] : nullptr; }
+int tlb_tick_feed_stride(const tlb_tick *t) { return t && t->feed ? t->feed_stride : 0; }
+const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t) { return t && t->feed ? t->h_feed_report[t->out_set] : nullptr; }
 int tlb_tick_need(const tlb_tick *t, int stream)
 {
     if (!t || stream < 0 || stream >= t->nstreams) return -TLB_ERR_ARG;
@@ -395,7 +491,9 @@ int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config
     int k; TickGroup *G = tick_group_of(t, stream, &k);
     if (!G || t->finished) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
-    return tlb_stream_reconfigure(G->b, k, cfg);
+    const int rc = tlb_stream_reconfigure(G->b, k, cfg);
+    if (t->feed) tick_feed_refresh(t);                               // (a feed the stream's new rate or channel count no longer fits has been removed)
+    return rc;
 }
 
 // egress of the frames sitting in G.d_frames + copy-out, queued on s_run / s_out
@@ -428,6 +526,8 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
+    // (tlb_tick_finish runs no feed kernel: its set shows the last tick's reports once more)
+    if (G.any_fed) HIPCHK(hipMemcpyAsync(t->h_feed_report[set] + G.first, G.d_feed_report, n * sizeof(tlb_frame_report), hipMemcpyDeviceToHost, t->s_out));
     if (t->short_reads) {
         HIPCHK(hipMemcpyAsync(t->h_underrun_ms[set] + G.first, G.d_underrun_ms, n * 4, hipMemcpyDeviceToHost, t->s_out));
         HIPCHK(hipMemcpyAsync(t->h_underruns[set] + G.first, G.d_underruns, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -546,7 +646,10 @@ int tlb_tick_submit(tlb_tick *t)
         int rc = TLB_OK;
         hipError_t e = hipSuccess;
         if (t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_ingested, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
+        // a group all of whose streams have feeds takes no PCM over the link: the feed kernel writes every slot the ingest reads
+        if (e == hipSuccess && !G.all_fed) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed, t->h_feed[set] + (size_t)G.first * (size_t)t->feed_stride, n * (size_t)t->feed_stride, hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed_len, t->h_feed_len[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->short_reads) e = hipMemcpyAsync(G.d_valid, t->h_valid[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->with_xpad && t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_encoded, 0);
         if (e == hipSuccess && t->with_xpad) e = hipMemcpyAsync(G.d_xpad, t->h_xpad[set] + (size_t)G.first * TL_MAX_XPAD, n * TL_MAX_XPAD, hipMemcpyHostToDevice, t->s_in);
@@ -555,6 +658,7 @@ int tlb_tick_submit(tlb_tick *t)
         if (e == hipSuccess) e = hipStreamWaitEvent(t->s_run, G.ev_in, 0);
         if (e == hipSuccess && t->ticks > 0) e = hipStreamWaitEvent(t->s_run, G.ev_out, 0);
         if (e != hipSuccess) rc = TLB_ERR_HIP;
+        if (!rc && G.any_fed) rc = feed_launch(G.b, G.d_feed, G.d_feed_len, 1, G.d_inter, G.d_feed_report, t->s_run, t->feed_stride);      // behind the copy-in, ahead of the ingest: a mixed group's fed slots are overwritten
         if (!rc && t->resample) rc = tlb_resample_device(G.b, G.d_inter, 1, G.d_rs, t->s_run);
         if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, t->resample ? G.d_rs : G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
         if (!rc && t->short_reads) rc = tlb_ingest_device_valid(G.b, G.d_inter, G.d_valid, 1, G.d_pcm, G.d_peaks, t->s_run);
@@ -587,6 +691,7 @@ int tlb_tick_wait(tlb_tick *t)
     t->out_set = set;
     // the retired tick's input set goes back to the caller (now, or after the next submit): untouched streams are full reads
     if (t->short_reads) { int32_t *v = t->h_valid[t->waited & 1]; for (int i = 0; i < t->nstreams; i++) v[i] = TLB_SAMPLES_PER_FRAME; }
+    if (t->h_feed_len[0]) memset(t->h_feed_len[t->waited & 1], 0, (size_t)t->nstreams * sizeof(int32_t));      // ... and feed slots are empty
     t->waited++;
     return TLB_OK;
 }

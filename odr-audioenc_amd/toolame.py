@@ -46,6 +46,22 @@ class _CConfig(C.Structure):
                 ("pad_len", C.c_int)]
 
 
+@dataclass(frozen=True)
+class FeedConfig:
+    """tlb_feed_config: a stream's source arrives as MPEG Layer II frames of this rate, bitrate and channel count (1 | 2)"""
+    samplerate: int = 48000
+    bitrate: int = 192
+    channels: int = 2
+
+
+class _CFeedConfig(C.Structure):
+    _fields_ = [("samplerate", C.c_long), ("bitrate", C.c_int), ("channels", C.c_int)]
+
+
+def _c_feed(cfg):
+    return _CFeedConfig(int(cfg.samplerate), int(cfg.bitrate), int(cfg.channels))
+
+
 _lib = None
 
 
@@ -268,6 +284,25 @@ def _bind(L):
         L.tlb_tick_need.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_node_need.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_feed_set"):               # Layer II feeds
+        L.tlb_feed_check_config.argtypes = [C.c_void_p]
+        L.tlb_feed_frame_bytes.argtypes = [C.c_void_p]
+        L.tlb_feed_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_feed_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_feed_stride.argtypes = [C.c_void_p]
+        L.tlb_feed_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_feed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_tick_set_feed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        for f in ("tlb_tick_feed", "tlb_tick_feed_len", "tlb_tick_feed_report"):
+            getattr(L, f).restype = C.c_void_p
+            getattr(L, f).argtypes = [C.c_void_p]
+        L.tlb_tick_feed_stride.argtypes = [C.c_void_p]
+        L.tlb_node_set_feed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        for f in ("tlb_node_feed", "tlb_node_feed_len", "tlb_node_feed_report"):
+            getattr(L, f).restype = C.c_void_p
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_feed_stride.argtypes = [C.c_void_p, C.c_int]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -299,6 +334,21 @@ def resample_taps(source_rate, encoder_rate):
     if not p:
         return None
     return np.ctypeslib.as_array((C.c_int16 * (l.value * tt.value)).from_address(p)).reshape(l.value, tt.value).copy(), l.value, m.value
+
+
+def feed_check_config(cfg):
+    """tlb_feed_check_config: 0, or the library's code for an illegal sample rate (1), channel count (2) or bitrate (4); host arithmetic, no GPU"""
+    c = _c_feed(cfg)
+    return load_library().tlb_feed_check_config(C.byref(c))
+
+
+def feed_frame_bytes(cfg):
+    """bytes of a feed frame without its padding slot: host arithmetic, no GPU"""
+    c = _c_feed(cfg)
+    n = load_library().tlb_feed_frame_bytes(C.byref(c))
+    if n < 0:
+        raise ToolameError(-n, "tlb_feed_frame_bytes")
+    return n
 
 
 def lds_bytes_per_stream():
@@ -446,6 +496,36 @@ class Tick:
         if n < 0:
             raise ToolameError(-n, "tlb_tick_need")
         return n
+
+    # -- Layer II feeds (tlb_tick_set_feed): legal while no tick is in flight; exclude short reads and sources --
+    def set_feed(self, stream, cfg):
+        """stream = -1: every stream; cfg = None removes the feed.  `feed`, `feed_len` must be fetched again afterwards."""
+        c = _c_feed(cfg) if cfg is not None else None
+        rc = self.L.tlb_tick_set_feed(self.h, stream, C.byref(c) if c is not None else None)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_set_feed")
+
+    @property
+    def feed_stride(self):
+        return self.L.tlb_tick_feed_stride(self.h)
+
+    @property
+    def feed(self):
+        """uint8 [nstreams, feed_stride] of the input set to fill next: a fed stream's frame; None when no feed is set or while two ticks are in flight"""
+        return self._view("tlb_tick_feed", C.c_uint8, (self.nstreams, self.feed_stride)) if self.feed_stride else None
+
+    @property
+    def feed_len(self):
+        """int32 [nstreams] of the input set to fill next: the frame's bytes, 0 (an empty slot) unless the caller writes more"""
+        return self._view("tlb_tick_feed_len", C.c_int32, (self.nstreams,))
+
+    @property
+    def feed_report(self):
+        """FRAME_REPORT_DTYPE [nstreams] of the tick waited for last; None when no feed is set"""
+        p = self.L.tlb_tick_feed_report(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * FRAME_REPORT_DTYPE.itemsize)).from_address(p), dtype=FRAME_REPORT_DTYPE)
 
     # -- short reads (src/odr-audioenc.cpp:335-373,910-935): opt in before the first submit --
     def enable_short_reads(self):
@@ -748,6 +828,59 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_decode_host")
         return rep, fl, pcm
+
+    # -- Layer II feeds: a stream's source arrives as MP2 frames and is decoded into the ingest's input (tlb_feed_*) --
+    def set_feed(self, stream, cfg):
+        """stream = -1: every stream; cfg = None removes the feed.  The feed's rate and channel count must be the stream's."""
+        c = _c_feed(cfg) if cfg is not None else None
+        rc = self.L.tlb_feed_set(self.h, stream, C.byref(c) if c is not None else None)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_set")
+
+    def get_feed(self, stream):
+        c = _CFeedConfig()
+        n = self.L.tlb_feed_get(self.h, stream, C.byref(c))
+        if n < 0:
+            raise ToolameError(-n, "tlb_feed_get")
+        return FeedConfig(c.samplerate, c.bitrate, c.channels) if n else None
+
+    @property
+    def feed_stride(self):
+        """bytes per slot of feed(): it changes with set_feed"""
+        return self.L.tlb_feed_stride(self.h)
+
+    def feed_reset(self, stream=-1):
+        rc = self.L.tlb_feed_reset(self.h, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_reset")
+
+    def feed(self, frames, lens, interleaved=None):
+        """frames uint8 [nframes, nstreams, feed_stride], lens int32 [nframes, nstreams] (0: an empty slot) ->
+        (interleaved int16 [nframes, nstreams, 2304] as ingest() takes it, reports FRAME_REPORT_DTYPE [nframes, nstreams]).
+        `interleaved`: the PCM of the streams WITHOUT a feed, whose slots the call does not touch (None: zeros); it is not changed, a copy is returned."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        nf = frames.shape[0]
+        if frames.shape != (nf, self.nstreams, self.feed_stride):
+            raise ToolameError(18, f"frames shape {frames.shape}")
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        if ln.shape != (nf, self.nstreams):
+            raise ToolameError(18, "lens shape")
+        if interleaved is None:
+            out = np.zeros((nf, self.nstreams, 2 * SAMPLES), dtype=np.int16)
+        else:
+            out = np.array(interleaved, dtype=np.int16, order="C", copy=True)
+            if out.shape != (nf, self.nstreams, 2 * SAMPLES):
+                raise ToolameError(18, f"interleaved shape {out.shape}")
+        rep = np.zeros((nf, self.nstreams), dtype=FRAME_REPORT_DTYPE)
+        rc = self.L.tlb_feed_host(self.h, frames.ctypes.data, ln.ctypes.data, nf, out.ctypes.data, rep.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_host")
+        return out, rep
+
+    def feed_device(self, d_frames_ptr, d_len_ptr, nframes, d_interleaved_ptr, d_report_ptr=None, stream=None):
+        rc = self.L.tlb_feed_device(self.h, d_frames_ptr, d_len_ptr, nframes, d_interleaved_ptr, d_report_ptr, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_device")
 
     def monitor(self, report, pcm=None, record=None):
         """tlb_monitor_host: fold reports FRAME_REPORT_DTYPE [nframes, nstreams] (and the decoded pcm int16 [nframes, nstreams, 2, 1152] or
@@ -1198,6 +1331,31 @@ class Node:
         if n < 0:
             raise ToolameError(-n, "tlb_node_need")
         return n
+
+    # Layer II feeds (Tick.set_feed, per stream with node-wide indices)
+    def set_feed(self, stream, cfg):
+        """stream = -1: every stream; cfg = None removes the feed; between steps only"""
+        c = _c_feed(cfg) if cfg is not None else None
+        self._rc(self.L.tlb_node_set_feed(self.h, stream, C.byref(c) if c is not None else None), "tlb_node_set_feed")
+
+    def feed(self, s):
+        """the stream's slot (uint8 view) in its shard's current input set; None when its shard has no feed, while two ticks are in flight and
+        for a broken or late shard"""
+        p = self.L.tlb_node_feed(self.h, s)
+        n = self.L.tlb_node_feed_stride(self.h, s)
+        return np.ctypeslib.as_array((C.c_uint8 * n).from_address(p)) if p and n else None
+
+    def feed_len(self, s):
+        """the stream's int32 length as a one-element view (write [0]); 0, an empty slot, unless the caller writes more"""
+        p = self.L.tlb_node_feed_len(self.h, s)
+        return np.ctypeslib.as_array((C.c_int32 * 1).from_address(p)) if p else None
+
+    def feed_report(self, s):
+        """the stream's report (a FRAME_REPORT_DTYPE scalar, copied) of the step waited for last; None for a broken, late or stale shard"""
+        p = self.L.tlb_node_feed_report(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * FRAME_REPORT_DTYPE.itemsize).from_address(p), dtype=FRAME_REPORT_DTYPE)[0].copy()
 
     # short reads (Tick.enable_short_reads, per stream with node-wide indices)
     def enable_short_reads(self):

@@ -35,6 +35,8 @@ LIMITS = [
     # frame check / decode (csrc/toolame_dec.hip): the synthesis kernel holds the matrixing row and the V ring in registers and runs three waves per SIMD
     (re.compile(r"tl_synth_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
     (re.compile(r"tl_unpack_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
+    # Layer II feeds (csrc/toolame_feed.hip): the parser and the synthesis of the two kernels above in one, at the synthesis kernel's occupancy
+    (re.compile(r"tl_feed_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
     # ingest with short reads (csrc/toolame_ingest.hip): a streaming kernel, nothing may spill and the gather's index arithmetic must not go through scratch
     (re.compile(r"tl_ingest_valid_kernel"), dict(vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # compare monitor (csrc/toolame_compare.hip): a streaming kernel with eight 64-bit accumulators per lane; four waves' histories share a workgroup's LDS
