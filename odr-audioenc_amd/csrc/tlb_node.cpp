@@ -25,6 +25,7 @@
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
 #include "mp2_resample.h"
+#include "tlb_blocks.h"
 #include "tlb_mailbox.h"
 #include "tlb_plan.h"
 #ifdef TLB_FAULT_INJECT
@@ -88,12 +89,16 @@ struct Shard : TlbMailbox {
         int last_err;
         char what[TLB_NODE_WHAT_LEN];
     } kept = {};
-    void keep()                                  // before a job that may go late is posted (the shard is idle: its fields are readable)
+    Kept own() const                             // the shard's record as its own fields have it (readable while it is not late)
     {
-        kept.steps = steps; kept.frames = frames; kept.failures = failures; kept.restarts = restarts; kept.lost_steps = lost_steps;
-        kept.busy_ns = busy_ns; kept.device_ms = device_ms; kept.last_err = last_err;
-        memcpy(kept.what, what, sizeof what);
+        Kept k = {steps, frames, failures, restarts, lost_steps, busy_ns, device_ms, last_err, {}};
+        memcpy(k.what, what, sizeof what);
+        return k;
     }
+    void keep() { kept = own(); }                // before a job that may go late is posted (the shard is idle: its fields are readable)
+    // What the node may see of this shard now.  A late shard is told from the node's own record (kept): its job still owns the shard's fields.
+    Kept seen() const { return late ? kept : own(); }
+    int state() const { return late ? TLB_SHARD_LATE : live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN; }
 #ifdef TLB_FAULT_INJECT
     int stall_nth = 0, stall_ms = 0, stall_rc = 0;        // tlb_debug_node_stall_next: set between jobs, read inside wait jobs
 #endif
@@ -145,7 +150,7 @@ struct tlb_node {
     std::vector<tlb_stream_config> cfgs;         // the CURRENT configuration of every stream (reconfigurations applied): what a restarted shard is made from
     std::vector<double> gain_db;                 // the caller's gains, re-applied to a restarted shard
     std::vector<Shard *> shards;
-    std::vector<int> shard_of;
+    TlbBlocks blocks;                            // the cut of the streams into the shards' blocks, stream -> shard (csrc/tlb_blocks.h)
     bool finished = false;
     // node-level clock: first submit -> last wait of a step
     std::deque<double> t_submit;
@@ -254,10 +259,8 @@ struct tlb_node {
     }
     Shard *of(int stream, int *local) const
     {
-        if (stream < 0 || stream >= nstreams) return nullptr;
-        Shard *s = shards[(size_t)shard_of[(size_t)stream]];
-        *local = stream - s->first;
-        return s;
+        const int g = blocks.owner(stream, local);
+        return g < 0 ? nullptr : shards[(size_t)g];
     }
     // the owning shard of a stream if its results may be read: NULL for a broken shard (its buffers hold a half-finished step), a late
     // one, and one that did not take part in the step last waited for
@@ -271,6 +274,38 @@ struct tlb_node {
     {
         Shard *s = of(stream, local);
         return s && s->on() ? s : nullptr;
+    }
+    // ... whether a call may change it: a late shard answers TLB_ERR_LATE, a broken one TLB_ERR_HIP
+    static int usable(const Shard &s) { return s.late ? (int)TLB_ERR_LATE : !s.live() ? (int)TLB_ERR_HIP : (int)TLB_OK; }
+    // The gate of the calls on ONE stream: its owner in *s and its shard-local id in *local, TLB_ERR_ARG when there is no such stream (*s is
+    // NULL then), else usable()'s answer.
+    int gate(int stream, Shard **s, int *local) const
+    {
+        *s = of(stream, local);
+        return *s ? usable(**s) : (int)TLB_ERR_ARG;
+    }
+    // A per-stream setting that is remembered for restarts -- shard_make() sets `kept` again on a fresh object -- for one stream or all
+    // (tlb_node_set_source, tlb_node_set_feed, after their own checks).  Every shard the call touches is asked before one is changed: a
+    // broken one stops the call with TLB_ERR_HIP, a late one with TLB_ERR_LATE.  `kept` is made by the first call that turns the setting
+    // on (`on`); clearing what was never on is TLB_OK and touches nothing.  apply(shard, k, v) runs on the owning shards' threads, in shard
+    // order, k = -1 for a whole block.  After a device failure half way (the values were checked by the caller) the shards already changed,
+    // and the failing one, get what `kept` says they had, stream by stream -- with fresh state, since setting a stream is all its object
+    // offers.  What went through is remembered: keep(i) for every named stream i.
+    template <class T, class Apply, class Keep> int set_remembered(int stream, std::vector<T> &kept, bool on, const T &v, Apply apply, Keep keep)
+    {
+        if (int rc = blocks.visit(stream, [&](int g, int) { return usable(*shards[(size_t)g]); })) return rc;
+        if (kept.empty()) { if (!on) return TLB_OK; kept.assign((size_t)nstreams, T{}); }
+        auto restore = [&](Shard &sh) {
+            for (int i = 0; i < sh.n; i++) (void)apply(sh, i, kept[(size_t)(sh.first + i)]);
+            return 0;
+        };
+        if (int rc = blocks.visit(stream, [&](int g, int k) {
+                const int r = one(g, [&](Shard &sh) { return apply(sh, k, v); });
+                for (int u = stream < 0 ? 0 : g; r && u <= g; u++) (void)one(u, restore);      // (the touched shards up to the failing one)
+                return r;
+            })) return rc;
+        for (int i = stream < 0 ? 0 : stream; i < (stream < 0 ? nstreams : stream + 1); i++) kept[(size_t)i] = keep(i);
+        return TLB_OK;
     }
 };
 
@@ -290,7 +325,8 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (nd->short_reads) if (int rc = tlb_tick_enable_short_reads(s.tick)) return rc;
         if (nd->monitor) if (int rc = tlb_tick_enable_monitor(s.tick, nd->monitor)) return rc;
         if (nd->compare) if (int rc = tlb_tick_enable_compare(s.tick, &nd->cparams)) return rc;
-        if (nd->monitor && nd->listen >= s.first && nd->listen < s.first + s.n) if (int rc = tlb_tick_monitor_listen(s.tick, nd->listen - s.first)) return rc;
+        int k;
+        if (nd->monitor && nd->of(nd->listen, &k) == &s) if (int rc = tlb_tick_monitor_listen(s.tick, k)) return rc;
     } else {
         s.batch = tlb_create(s.device, s.n, nd->cfgs.data() + s.first, &e);
         if (!s.batch) return e ? e : TLB_ERR_HIP;
@@ -340,19 +376,40 @@ void shard_identify(Shard &s)
     if (hipDeviceGetAttribute(&x, hipDeviceAttributeNumberOfXccs, s.device) == hipSuccess) s.num_xcd = x;
 }
 
+// ---- the per-stream accessors of the TICK plane ----
+// One stream's answer from its shard's tick object: fn(tick, shard-local id), or `empty` -- no node, no such stream, no tick object (BATCH
+// plane), or a shard that the gate says may not be asked (READ: tlb_node::read, the results; INPUT: tlb_node::input, the input set).  The
+// accessors that report a length pass `len`: it is cleared when the gate refuses; otherwise the tick object's accessor writes it.
+// Gate and fn are template arguments: a sender calls tlb_node_packet once per stream and unit, and pays two calls for it as before.
+enum Gate { READ, INPUT };
+template <Gate G, class R, class Fn> inline R ask(const tlb_node *nd, int stream, R empty, Fn fn, int *len = nullptr)
+{
+    int k; Shard *s = !nd ? nullptr : G == READ ? nd->read(stream, &k) : nd->input(stream, &k);
+    if (!s && len) *len = 0;
+    return s && s->tick ? fn(s->tick, k) : empty;
+}
+// ... the stream's slot of a per-stream array that the tick object hands out whole: GET(tick) + k * stride, NULL where GET answers NULL
+template <Gate G, auto GET> inline auto slot(const tlb_node *nd, int stream, size_t stride = 1)
+{
+    using P = decltype(GET(nullptr));
+    return ask<G>(nd, stream, P(nullptr), [stride](tlb_tick *t, int k) { P p = GET(t); return p ? p + (size_t)k * stride : P(nullptr); });
+}
+// ... or what that slot holds, 0 where there is none
+template <Gate G, auto GET> inline auto value(const tlb_node *nd, int stream)
+{
+    const auto p = slot<G, GET>(nd, stream);
+    return p ? *p : 0;
+}
+
 }  // namespace
 
 extern "C" {
 
 void tlb_node_partition(int nstreams, int nshards, int shard, int *first, int *n)
 {
-    int f = 0, c = 0;
-    if (nstreams > 0 && nshards > 0 && shard >= 0 && shard < nshards) {
-        f = (int)((long long)nstreams * shard / nshards);
-        c = (int)((long long)nstreams * (shard + 1) / nshards) - f;
-    }
-    if (first) *first = f;
-    if (n) *n = c;
+    const TlbBlock b = TlbBlocks(nstreams, nshards).block(shard);
+    if (first) *first = b.first;
+    if (n) *n = b.n;
 }
 
 int tlb_node_plan_shard(int nstreams, const tlb_stream_config *cfgs, int nshards, int shard,
@@ -409,12 +466,11 @@ tlb_node *tlb_node_create(int nshards, const int *devices, int nstreams, const t
     nd->cfg.tick.version = nullptr; nd->cfg.tick.version_len = 0;    // (the caller's pointer is not kept)
     nd->cfgs.assign(cfgs, cfgs + nstreams);
     nd->gain_db.assign((size_t)nstreams, 0.0);
-    nd->shard_of.resize((size_t)nstreams);
+    nd->blocks = TlbBlocks(nstreams, nshards);
     for (int g = 0; g < nshards; g++) {
         Shard *s = new Shard;
         s->index = g; s->device = devices[g];
-        tlb_node_partition(nstreams, nshards, g, &s->first, &s->n);
-        for (int k = s->first; k < s->first + s->n; k++) nd->shard_of[(size_t)k] = g;
+        s->first = nd->blocks.block(g).first; s->n = nd->blocks.block(g).n;
         nd->shards.push_back(s);
         s->start([s] { (void)hipSetDevice(s->device); });            // HIP's current device is per thread; the tlb_* calls set it again themselves
     }
@@ -433,7 +489,7 @@ tlb_node *tlb_node_create(int nshards, const int *devices, int nstreams, const t
 
 int tlb_node_nshards(const tlb_node *nd) { return nd ? (int)nd->shards.size() : 0; }
 int tlb_node_nstreams(const tlb_node *nd) { return nd ? nd->nstreams : 0; }
-int tlb_node_shard_of(const tlb_node *nd, int stream) { return nd && stream >= 0 && stream < nd->nstreams ? nd->shard_of[(size_t)stream] : -1; }
+int tlb_node_shard_of(const tlb_node *nd, int stream) { return nd ? nd->blocks.owner(stream) : -1; }
 const char *tlb_node_describe(const tlb_node *nd) { return nd ? nd->describe.c_str() : ""; }
 
 // ---- health of one shard ----
@@ -441,20 +497,18 @@ int tlb_node_shard_status(const tlb_node *nd, int shard, tlb_node_shard_info *in
 {
     if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return -TLB_ERR_ARG;
     const Shard &s = *nd->shards[(size_t)shard];
-    // a late shard is told from the node's own record (kept): its job still owns the shard's fields
-    const int state = s.late ? TLB_SHARD_LATE : s.live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN;
     if (info) {
+        const Shard::Kept k = s.seen();
         memset(info, 0, sizeof *info);
         info->shard = s.index; info->device = s.device; info->first = s.first; info->nstreams = s.n;
-        info->state = state; info->last_err = s.late ? s.kept.last_err : s.last_err;
-        info->failures = s.late ? s.kept.failures : s.failures; info->restarts = s.late ? s.kept.restarts : s.restarts;
-        info->lost_steps = s.late ? s.kept.lost_steps : s.lost_steps;
-        memcpy(info->what, s.late ? s.kept.what : s.what, sizeof info->what);
+        info->state = s.state(); info->last_err = k.last_err;
+        info->failures = k.failures; info->restarts = k.restarts; info->lost_steps = k.lost_steps;
+        memcpy(info->what, k.what, sizeof info->what);
         memcpy(info->device_name, s.device_name, sizeof info->device_name);
         memcpy(info->pci, s.pci, sizeof info->pci); memcpy(info->uuid, s.uuid, sizeof info->uuid);
         info->num_cu = s.num_cu; info->num_xcd = s.num_xcd; info->hbm_gb = s.hbm_gb;
     }
-    return state;
+    return s.state();
 }
 // A fresh object for the block, made on the shard's own thread: its streams start "as a freshly started reference process" (tlb_stream_reset's
 // contract, for the whole block: no history, no pending frame, psy 2/4 state zero, the EDI senders re-initialised from now_s), with
@@ -488,8 +542,8 @@ int tlb_node_counters(const tlb_node *nd, tlb_node_counter *per_shard, tlb_node_
         tlb_node_counter c;
         memset(&c, 0, sizeof c);
         c.shard = s.index; c.device = s.device; c.first = s.first; c.nstreams = s.n;
-        if (s.late) { c.steps = s.kept.steps; c.frames = s.kept.frames; c.busy_ns = s.kept.busy_ns; c.device_ms = s.kept.device_ms; }
-        else { c.steps = s.steps; c.frames = s.frames; c.busy_ns = s.busy_ns; c.device_ms = s.device_ms; }
+        const Shard::Kept k = s.seen();
+        c.steps = k.steps; c.frames = k.frames; c.busy_ns = k.busy_ns; c.device_ms = k.device_ms;
         if (per_shard) per_shard[g] = c;
         t.frames += c.frames;
         if (g == 0 || c.steps < t.steps) t.steps = c.steps;
@@ -516,7 +570,7 @@ int tlb_node_shard_deadline_status(const tlb_node *nd, int shard, tlb_node_shard
 {
     if (!nd || shard < 0 || shard >= (int)nd->shards.size()) return -TLB_ERR_ARG;
     const Shard &s = *nd->shards[(size_t)shard];
-    const int st = s.late ? TLB_SHARD_LATE : s.live() ? TLB_SHARD_OK : TLB_SHARD_BROKEN;
+    const int st = s.state();
     if (info) {
         memset(info, 0, sizeof *info);
         info->state = st;
@@ -527,24 +581,9 @@ int tlb_node_shard_deadline_status(const tlb_node *nd, int shard, tlb_node_shard
 }
 
 // ---- TICK plane ----
-int16_t *tlb_node_pcm(tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    int16_t *p = s && s->tick ? tlb_tick_pcm(s->tick) : nullptr;
-    return p ? p + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME : nullptr;
-}
-uint8_t *tlb_node_xpad(tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    uint8_t *p = s && s->tick ? tlb_tick_xpad(s->tick) : nullptr;
-    return p ? p + (size_t)k * TLB_MAX_XPAD : nullptr;
-}
-int32_t *tlb_node_xpad_len(tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    int32_t *p = s && s->tick ? tlb_tick_xpad_len(s->tick) : nullptr;
-    return p ? p + k : nullptr;
-}
+int16_t *tlb_node_pcm(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_pcm>(nd, stream, 2 * TLB_SAMPLES_PER_FRAME); }
+uint8_t *tlb_node_xpad(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_xpad>(nd, stream, TLB_MAX_XPAD); }
+int32_t *tlb_node_xpad_len(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_xpad_len>(nd, stream); }
 // Short reads (tlb_tick_enable_short_reads of every shard, on the shards' threads): before the first submit, TICK plane only.
 int tlb_node_enable_short_reads(tlb_node *nd)
 {
@@ -565,12 +604,7 @@ int tlb_node_enable_monitor(tlb_node *nd, int what)
     if (!rc) nd->monitor = what;
     return rc;
 }
-const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const tlb_monitor_record *p = s && s->tick ? tlb_tick_monitor(s->tick) : nullptr;
-    return p ? p + k : nullptr;
-}
+const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_monitor>(nd, stream); }
 // The compare monitor (tlb_tick_enable_compare of every shard): after tlb_node_enable_monitor(TLB_MONITOR_AUDIO), before the first submit.
 int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params)
 {
@@ -582,12 +616,7 @@ int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params)
     if (!rc) { nd->cparams = P; nd->compare = true; }
     return rc;
 }
-const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const tlb_compare_record *p = s && s->tick ? tlb_tick_compare(s->tick) : nullptr;
-    return p ? p + k : nullptr;
-}
+const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_compare>(nd, stream); }
 // One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'
 // tick objects that their next submit reads; no shard but a late one runs a job between the node's calls, and a late one is left alone
 // (it cannot be the stream's shard: TLB_ERR_LATE).
@@ -595,8 +624,7 @@ int tlb_node_monitor_listen(tlb_node *nd, int stream)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= nd->nstreams) return TLB_ERR_ARG;
     int k = 0; Shard *own = stream >= 0 ? nd->of(stream, &k) : nullptr;
-    if (own && own->late) return TLB_ERR_LATE;
-    if (own && !own->live()) return TLB_ERR_HIP;
+    if (own) if (int rc = nd->usable(*own)) return rc;
     for (Shard *s : nd->shards)
         if (s->on() && s->tick) (void)tlb_tick_monitor_listen(s->tick, s == own ? k : -1);
     nd->listen = stream;
@@ -614,8 +642,7 @@ const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream)
     }
     return nullptr;
 }
-// A source rate for one stream or all: to the owning shards' objects, on their threads, between steps.  A broken shard answers TLB_ERR_HIP, a
-// late one TLB_ERR_LATE; with stream = -1 either stops the call before any shard is changed.  What went through is remembered for restarts.
+// A source rate for one stream or all: to the owning shards' objects, on their threads, between steps (tlb_node::set_remembered).
 int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
 {
     if (!nd || stream < -1 || stream >= nd->nstreams || source_rate < 0 || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
@@ -623,31 +650,12 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
     bool any = false;
     if (int rc = tlb_source_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
     if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && nd->any_feed()))) return TLB_ERR_ARG;
-    for (Shard *s : nd->shards) {
-        if (s->first >= s1 || s->first + s->n <= s0) continue;
-        if (s->late) return TLB_ERR_LATE;
-        if (!s->live()) return TLB_ERR_HIP;
-    }
-    if (nd->source.empty()) { if (!any) return TLB_OK; nd->source.assign((size_t)nd->nstreams, 0); }
-    for (Shard *s : nd->shards) {
-        if (s->first >= s1 || s->first + s->n <= s0) continue;
-        const int k = stream < 0 ? -1 : stream - s->first;
-        auto set = [&](Shard &sh, int kk, long r) { return sh.tick ? tlb_tick_set_source(sh.tick, kk, r) : tlb_resample_set_source(sh.batch, kk, r); };
-        const int rc = nd->one(s->index, [&](Shard &sh) { return set(sh, k, source_rate); });
-        if (rc) {                                                    // a device failure half way (the pairs were checked above): the shards already
-            for (Shard *u : nd->shards) {                            // changed, and this one, get the sources they had, with fresh state
-                if (u->index > s->index || u->first >= s1 || u->first + u->n <= s0) continue;
-                (void)nd->one(u->index, [&](Shard &sh) { for (int i = 0; i < sh.n; i++) (void)set(sh, i, nd->source[(size_t)(sh.first + i)]); return 0; });
-            }
-            return rc;
-        }
-    }
-    for (int i = s0; i < s1; i++) nd->source[(size_t)i] = source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate;
-    return TLB_OK;
+    return nd->set_remembered(stream, nd->source, any, source_rate,
+        [](Shard &sh, int k, long r) { return sh.tick ? tlb_tick_set_source(sh.tick, k, r) : tlb_resample_set_source(sh.batch, k, r); },
+        [&](int i) { return source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate; });      // (the encoder's own rate is no source)
 }
-// A Layer II feed for one stream or all (cfg = NULL: removed): to the owning shards' objects, on their threads, between steps.  Every named
-// stream is checked before a shard is changed; a broken shard answers TLB_ERR_HIP, a late one TLB_ERR_LATE, before anything changes; after
-// a device failure half way the shards already changed get back the feeds they had.  What went through is remembered for restarts.
+// A Layer II feed for one stream or all (cfg = NULL: removed; remembered as bitrate 0), the same way.  Every named stream is checked
+// before a shard is asked.
 int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
 {
     if (!nd || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
@@ -663,71 +671,34 @@ int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
             for (long r : nd->source) if (r) return TLB_ERR_ARG;
         }
     }
-    for (Shard *s : nd->shards) {
-        if (s->first >= s1 || s->first + s->n <= s0) continue;
-        if (s->late) return TLB_ERR_LATE;
-        if (!s->live()) return TLB_ERR_HIP;
-    }
-    if (nd->feed.empty()) { if (!cfg) return TLB_OK; nd->feed.assign((size_t)nd->nstreams, tlb_feed_config{0, 0, 0}); }
-    auto set = [](Shard &sh, int kk, const tlb_feed_config *c) { return sh.tick ? tlb_tick_set_feed(sh.tick, kk, c) : tlb_feed_set(sh.batch, kk, c); };
-    for (Shard *s : nd->shards) {
-        if (s->first >= s1 || s->first + s->n <= s0) continue;
-        const int k = stream < 0 ? -1 : stream - s->first;
-        const int rc = nd->one(s->index, [&](Shard &sh) { return set(sh, k, cfg); });
-        if (rc) {
-            for (Shard *u : nd->shards) {
-                if (u->index > s->index || u->first >= s1 || u->first + u->n <= s0) continue;
-                (void)nd->one(u->index, [&](Shard &sh) {
-                    for (int i = 0; i < sh.n; i++) { const tlb_feed_config &f = nd->feed[(size_t)(sh.first + i)]; (void)set(sh, i, f.bitrate ? &f : nullptr); }
-                    return 0;
-                });
-            }
-            return rc;
-        }
-    }
-    for (int i = s0; i < s1; i++) nd->feed[(size_t)i] = cfg ? *cfg : tlb_feed_config{0, 0, 0};
-    return TLB_OK;
+    const tlb_feed_config v = cfg ? *cfg : tlb_feed_config{0, 0, 0};
+    return nd->set_remembered(stream, nd->feed, cfg != nullptr, v,
+        [](Shard &sh, int k, const tlb_feed_config &f) {
+            const tlb_feed_config *c = f.bitrate ? &f : nullptr;      // (bitrate 0 is "none": tlb_feed_check_config above lets no caller's cfg through with it)
+            return sh.tick ? tlb_tick_set_feed(sh.tick, k, c) : tlb_feed_set(sh.batch, k, c);
+        },
+        [&](int) { return v; });
 }
 // the stream's slot of its shard's feed buffers (tlb_tick_feed / _feed_len of the shard's tick object): NULL for a broken or a late shard, while
 // two ticks are in flight and while no stream of the shard has a feed
 uint8_t *tlb_node_feed(tlb_node *nd, int stream)
 {
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    uint8_t *p = s && s->tick ? tlb_tick_feed(s->tick) : nullptr;
-    return p ? p + (size_t)k * (size_t)tlb_tick_feed_stride(s->tick) : nullptr;
+    return ask<INPUT>(nd, stream, (uint8_t *)nullptr, [](tlb_tick *t, int k) {
+        uint8_t *p = tlb_tick_feed(t);
+        return p ? p + (size_t)k * (size_t)tlb_tick_feed_stride(t) : nullptr;      // (one slot width for the whole object: the tick's own)
+    });
 }
-int32_t *tlb_node_feed_len(tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    int32_t *p = s && s->tick ? tlb_tick_feed_len(s->tick) : nullptr;
-    return p ? p + k : nullptr;
-}
-int tlb_node_feed_stride(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    return s && s->tick ? tlb_tick_feed_stride(s->tick) : 0;
-}
-const tlb_frame_report *tlb_node_feed_report(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const tlb_frame_report *p = s && s->tick ? tlb_tick_feed_report(s->tick) : nullptr;
-    return p ? p + k : nullptr;
-}
+int32_t *tlb_node_feed_len(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_feed_len>(nd, stream); }
+int tlb_node_feed_stride(const tlb_node *nd, int stream) { return ask<INPUT>(nd, stream, 0, [](tlb_tick *t, int) { return tlb_tick_feed_stride(t); }); }
+const tlb_frame_report *tlb_node_feed_report(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_feed_report>(nd, stream); }
 int tlb_node_need(const tlb_node *nd, int stream)
 {
     if (!nd || nd->plane != TLB_NODE_TICK) return -TLB_ERR_ARG;
-    int k; Shard *s = nd->of(stream, &k);
-    if (!s) return -TLB_ERR_ARG;
-    if (s->late) return -TLB_ERR_LATE;
-    if (!s->live() || !s->tick) return -TLB_ERR_HIP;
-    return tlb_tick_need(s->tick, k);
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return -rc;
+    return s->tick ? tlb_tick_need(s->tick, k) : -TLB_ERR_HIP;
 }
-int32_t *tlb_node_valid(tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->input(stream, &k) : nullptr;
-    int32_t *p = s && s->tick ? tlb_tick_valid(s->tick) : nullptr;
-    return p ? p + k : nullptr;
-}
+int32_t *tlb_node_valid(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_valid>(nd, stream); }
 
 int tlb_node_submit(tlb_node *nd)
 {
@@ -781,63 +752,27 @@ int tlb_node_finish(tlb_node *nd)
     nd->finished = true;
     return rc;
 }
-int tlb_node_units(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    return s && s->tick ? tlb_tick_units(s->tick, k) : 0;
-}
-const int16_t *tlb_node_peaks(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const int16_t *p = s && s->tick ? tlb_tick_peaks(s->tick) : nullptr;
-    return p ? p + 2 * (size_t)k : nullptr;
-}
-uint32_t tlb_node_silence_ms(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const uint32_t *p = s && s->tick ? tlb_tick_silence_ms(s->tick) : nullptr;
-    return p ? p[k] : 0;
-}
-uint32_t tlb_node_underrun_ms(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const uint32_t *p = s && s->tick ? tlb_tick_underrun_ms(s->tick) : nullptr;
-    return p ? p[k] : 0;
-}
-uint32_t tlb_node_underruns(const tlb_node *nd, int stream)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    const uint32_t *p = s && s->tick ? tlb_tick_underruns(s->tick) : nullptr;
-    return p ? p[k] : 0;
-}
+int tlb_node_units(const tlb_node *nd, int stream) { return ask<READ>(nd, stream, 0, [](tlb_tick *t, int k) { return tlb_tick_units(t, k); }); }
+const int16_t *tlb_node_peaks(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_peaks>(nd, stream, 2); }
+uint32_t tlb_node_silence_ms(const tlb_node *nd, int stream) { return value<READ, tlb_tick_silence_ms>(nd, stream); }
+uint32_t tlb_node_underrun_ms(const tlb_node *nd, int stream) { return value<READ, tlb_tick_underrun_ms>(nd, stream); }
+uint32_t tlb_node_underruns(const tlb_node *nd, int stream) { return value<READ, tlb_tick_underruns>(nd, stream); }
 const uint8_t *tlb_node_frame(const tlb_node *nd, int stream, int *len)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    if (!s && len) *len = 0;
-    return s && s->tick ? tlb_tick_frame(s->tick, k, len) : nullptr;
+    return ask<READ>(nd, stream, (const uint8_t *)nullptr, [=](tlb_tick *t, int k) { return tlb_tick_frame(t, k, len); }, len);
 }
 const uint8_t *tlb_node_packet(const tlb_node *nd, int stream, int unit, int *len)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    if (!s && len) *len = 0;
-    return s && s->tick ? tlb_tick_packet(s->tick, k, unit, len) : nullptr;
+    return ask<READ>(nd, stream, (const uint8_t *)nullptr, [=](tlb_tick *t, int k) { return tlb_tick_packet(t, k, unit, len); }, len);
 }
 const uint8_t *tlb_node_message(const tlb_node *nd, int stream, int unit, int *len)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    if (!s && len) *len = 0;
-    return s && s->tick ? tlb_tick_message(s->tick, k, unit, len) : nullptr;
+    return ask<READ>(nd, stream, (const uint8_t *)nullptr, [=](tlb_tick *t, int k) { return tlb_tick_message(t, k, unit, len); }, len);
 }
-int tlb_node_fragments(const tlb_node *nd, int stream, int unit)
-{
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    return s && s->tick ? tlb_tick_fragments(s->tick, k, unit) : 0;
-}
+int tlb_node_fragments(const tlb_node *nd, int stream, int unit) { return ask<READ>(nd, stream, 0, [=](tlb_tick *t, int k) { return tlb_tick_fragments(t, k, unit); }); }
 const uint8_t *tlb_node_fragment(const tlb_node *nd, int stream, int unit, int kf, int *len)
 {
-    int k; Shard *s = nd ? nd->read(stream, &k) : nullptr;
-    if (!s && len) *len = 0;
-    return s && s->tick ? tlb_tick_fragment(s->tick, k, unit, kf, len) : nullptr;
+    return ask<READ>(nd, stream, (const uint8_t *)nullptr, [=](tlb_tick *t, int k) { return tlb_tick_fragment(t, k, unit, kf, len); }, len);
 }
 
 // ---- both planes: gain, life cycle of one stream (on the owning shard's thread, like every other call on the shard's object) ----
@@ -853,33 +788,29 @@ int tlb_node_set_gain_db(tlb_node *nd, int stream, double gain_db)
         return nd->live("set_gain_db", [&](Shard &s) { return f(s, -1); });
     }
     nd->gain_db[(size_t)stream] = gain_db;
-    int k; Shard *s = nd->of(stream, &k);
-    if (s->late) { s->gain_missed = true; return TLB_ERR_LATE; }
-    if (!s->live()) return TLB_ERR_HIP;
+    int k; Shard *s;
+    const int rc = nd->gate(stream, &s, &k);
+    if (rc == TLB_ERR_LATE) s->gain_missed = true;
+    if (rc) return rc;
     return nd->one(s->index, [&](Shard &sh) { return f(sh, k); });
 }
 int tlb_node_stream_reset(tlb_node *nd, int stream)
 {
-    int k; Shard *s = nd ? nd->of(stream, &k) : nullptr;
-    if (!s) return TLB_ERR_ARG;
-    if (s->late) return TLB_ERR_LATE;
-    if (!s->live()) return TLB_ERR_HIP;
+    int k; Shard *s;
+    if (int rc = nd ? nd->gate(stream, &s, &k) : (int)TLB_ERR_ARG) return rc;
     return nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reset(sh.tick, k) : tlb_stream_reset(sh.batch, k); });
 }
 int tlb_node_stream_finish(tlb_node *nd, int stream, uint8_t *out, size_t out_size)
 {
-    int k; Shard *s = nd ? nd->of(stream, &k) : nullptr;
-    if (!s) return -TLB_ERR_ARG;
-    if (s->late) return -TLB_ERR_LATE;
-    if (!s->live()) return -TLB_ERR_HIP;
+    int k; Shard *s;
+    if (int rc = nd ? nd->gate(stream, &s, &k) : (int)TLB_ERR_ARG) return -rc;
     return nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_finish(sh.tick, k, out, out_size) : tlb_stream_finish(sh.batch, k, out, out_size); });
 }
 int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_config *cfg)
 {
-    int k; Shard *s = nd ? nd->of(stream, &k) : nullptr;
-    if (!s || !cfg) return TLB_ERR_ARG;
-    if (s->late) return TLB_ERR_LATE;
-    if (!s->live()) return TLB_ERR_HIP;
+    int k; Shard *s;
+    if (!nd || !cfg) return TLB_ERR_ARG;
+    if (int rc = nd->gate(stream, &s, &k)) return rc;
     const int rc = nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reconfigure(sh.tick, k, cfg) : tlb_stream_reconfigure(sh.batch, k, cfg); });
     if (!rc) nd->cfgs[(size_t)stream] = *cfg;                        // a restart of the shard re-creates the stream as it is NOW
     if (!rc && !nd->feed.empty()) {                                  // a feed the new rate or channel count no longer fits has been removed

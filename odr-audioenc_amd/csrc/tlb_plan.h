@@ -1,7 +1,8 @@
 // tlb_plan.h -- the ONE statement of what a block of streams becomes: which streams share a configuration record and which mono
 // streams share waves in pairs.  Used by tlb_create / tlb_stream_reconfigure (csrc/tlb_batch.cpp) and by the node level's planner
 // (tlb_node_plan_shard, csrc/tlb_node.cpp), so that the plan a caller is shown cannot drift from what the batch does.  At the end, for
-// the same reason, the rules of the opt-in calls that batch, tick plane and node level all apply.  Host C++ only.
+// the same reason, the rules of the opt-in calls that batch, tick plane and node level all apply.  How the streams are cut into blocks
+// (shards, stream groups) is not here: csrc/tlb_blocks.h.  Host C++ only.
 #pragma once
 #include <stdint.h>
 

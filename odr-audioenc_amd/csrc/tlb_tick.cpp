@@ -1,4 +1,5 @@
 // tlb_tick.cpp -- the real-time loop body as one object (include/toolame_batch.h, tlb_tick_*).  Host C++ above the batch and egress entry points.
+#include "tlb_blocks.h"
 #include "tlb_internal.h"
 #include "tlb_plan.h"
 
@@ -48,7 +49,7 @@ struct tlb_tick {
     char version[TL_EDI_MAX_VERSION] = {};
     int fec = 0, chunk_len = 207, transport = 0, addr_source = 0, dest_port = 0;
     std::vector<TickGroup> groups;
-    std::vector<int> group_of;                   // stream -> group
+    TlbBlocks blocks;                            // the cut of the streams into the groups, stream -> group (csrc/tlb_blocks.h)
     // pinned host buffers (tlb_tick_submit / tlb_tick_wait): two INPUT sets -- the caller fills input set `in_set` while the tick
     // submitted before is still on its way (with two ticks in flight neither set is free: the input accessors return NULL) -- and
     // three OUTPUT sets; results are read from `out_set`, the set of the tick waited for last
@@ -131,12 +132,11 @@ static int tick_create_impl(tlb_tick *t, int device, int nstreams, const tlb_str
     int ng = tc->ngroups > 0 ? tc->ngroups : (nstreams >= 65536 ? 8 : nstreams >= 8192 ? 4 : nstreams >= 2048 ? 2 : 1);      // more groups = a shorter tail behind the last copy-in
     if (ng > nstreams) ng = nstreams;
     t->groups.resize((size_t)ng);
-    t->group_of.resize((size_t)nstreams);
+    t->blocks = TlbBlocks(nstreams, ng);
     size_t n_frames = 0, n_pkts = 0, n_slots = 0, n_frags = 0, n_fragslots = 0, n_msgs = 0;
     for (int g = 0; g < ng; g++) {
         TickGroup &G = t->groups[(size_t)g];
-        G.first = (int)((long)nstreams * g / ng); G.n = (int)((long)nstreams * (g + 1) / ng) - G.first;
-        for (int s = G.first; s < G.first + G.n; s++) t->group_of[(size_t)s] = g;
+        G.first = t->blocks.block(g).first; G.n = t->blocks.block(g).n;
         int err = 0;
         G.b = tlb_create(device, G.n, cfgs + G.first, &err);
         if (!G.b) return err ? err : TLB_ERR_HIP;
@@ -217,6 +217,13 @@ tlb_tick *tlb_tick_create(int device, int nstreams, const tlb_stream_config *cfg
     if (err) *err = rc;
     if (rc) { tlb_tick_destroy(t); return nullptr; }
     return t;
+}
+
+// the group that owns a stream and the stream's id inside it (t->blocks); NULL for no object and for a stream outside it
+static const TickGroup *tick_group_of(const tlb_tick *t, int stream, int *local)
+{
+    const int g = t ? t->blocks.owner(stream, local) : -1;
+    return g < 0 ? nullptr : &t->groups[(size_t)g];
 }
 
 // The input accessors hand out the set the NEXT submit will read.  With two ticks in flight both sets belong to queued copy-ins (the
@@ -329,16 +336,16 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
 {
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || source_rate < 0 || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
     bool any = false;
     std::vector<char> real(t->groups.size(), 0);                     // per group: the call gives some stream of it a real source
-    for (size_t g = 0; g < real.size(); g++) {                       // every stream is checked before one is changed
-        const TickGroup &G = t->groups[g];
-        const int s0 = stream < 0 ? 0 : stream - G.first, s1 = stream < 0 ? G.n : s0 + 1;
-        if (s0 < 0 || s0 >= G.n) continue;
-        bool r = false;
-        if (int rc = tlb_source_range(s0, s1, source_rate, [&G](int k) { return (long)G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate; }, &r)) return rc;
-        real[g] = r; any |= r;
-    }
+    if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) {     // every stream is checked before one is changed
+            const TickGroup &G = t->groups[(size_t)g];
+            bool r = false;
+            const int e = tlb_source_range(l0, l1, source_rate, [&G](int k) { return (long)G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate; }, &r);
+            real[(size_t)g] = r; any |= r;
+            return e;
+        })) return rc;
     if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
     if (any && (t->short_reads || t->feed)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
@@ -351,11 +358,7 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
         m.commit(t->mem);
         t->groups.swap(gs);
     }
-    int rc = TLB_OK;
-    for (auto &G : t->groups) {
-        if (stream >= 0 && (stream < G.first || stream >= G.first + G.n)) continue;
-        if ((rc = tlb_resample_set_source(G.b, stream < 0 ? -1 : stream - G.first, source_rate))) break;
-    }
+    const int rc = t->blocks.visit(stream, [&](int g, int k) { return tlb_resample_set_source(t->groups[(size_t)g].b, k, source_rate); });
     t->resample = false;                                             // "at least one source set", as the streams stand now
     for (auto &G : t->groups)
         for (int k = 0; k < G.n; k++) if (tlb_resample_source(G.b, k)) t->resample = true;
@@ -382,13 +385,11 @@ int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     if (!cfg && !t->h_feed_len[0]) return TLB_OK;                    // off, and never on: nothing to allocate or to clear
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
     if (cfg) {
         if (t->short_reads || t->resample) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads and sources)
-        for (auto &G : t->groups) {                                  // every stream is checked before one is changed
-            const int s0 = stream < 0 ? 0 : stream - G.first, s1 = stream < 0 ? G.n : s0 + 1;
-            if (s0 < 0 || s0 >= G.n) continue;
-            if (int rc = feed_fits(G.b, s0, s1, cfg)) return rc;
-        }
+        // every stream is checked before one is changed
+        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return feed_fits(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
     }
     HIPCHK(hipSetDevice(t->device));
     const size_t ns = (size_t)t->nstreams;
@@ -421,21 +422,18 @@ int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
     // "all or nothing" holds for the feeds themselves; the wider buffers stay
     std::vector<tlb_feed_config> before(ns, tlb_feed_config{0, 0, 0});
     for (auto &G : t->groups) for (int k = 0; k < G.n; k++) (void)tlb_feed_get(G.b, k, &before[(size_t)(G.first + k)]);
-    int rc = TLB_OK;
-    for (auto &G : t->groups) {
-        if (stream >= 0 && (stream < G.first || stream >= G.first + G.n)) continue;
-        if ((rc = tlb_feed_set(G.b, stream < 0 ? -1 : stream - G.first, cfg))) {
-            for (auto &U : t->groups) {
-                if (U.first > G.first || (stream >= 0 && (stream < U.first || stream >= U.first + U.n))) continue;
-                for (int k = 0; k < U.n; k++) {
-                    if (stream >= 0 && stream != U.first + k) continue;
-                    const tlb_feed_config &f = before[(size_t)(U.first + k)];
-                    (void)tlb_feed_set(U.b, k, f.bitrate ? &f : nullptr);
-                }
+    const int rc = t->blocks.visit(stream, [&](int g, int k) {
+        const int e = tlb_feed_set(t->groups[(size_t)g].b, k, cfg);
+        if (e) t->blocks.visit_range(s0, s1, [&](int u, int l0, int l1) {      // the named streams of the groups up to and including this one
+            const TickGroup &U = t->groups[(size_t)u];
+            for (int i = l0; i < l1 && u <= g; i++) {
+                const tlb_feed_config &f = before[(size_t)(U.first + i)];
+                (void)tlb_feed_set(U.b, i, f.bitrate ? &f : nullptr);
             }
-            break;
-        }
-    }
+            return 0;
+        });
+        return e;
+    });
     tick_feed_refresh(t);
     for (int k = 0; k < 2; k++) memset(t->h_feed_len[k], 0, ns * sizeof(int32_t));
     return rc;
@@ -446,49 +444,37 @@ int tlb_tick_feed_stride(const tlb_tick *t) { return t && t->feed ? t->feed_stri
 const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t) { return t && t->feed ? t->h_feed_report[t->out_set] : nullptr; }
 int tlb_tick_need(const tlb_tick *t, int stream)
 {
-    if (!t || stream < 0 || stream >= t->nstreams) return -TLB_ERR_ARG;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    return tlb_resample_need(G.b, stream - G.first, 0);
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    return G ? tlb_resample_need(G->b, k, 0) : -TLB_ERR_ARG;
 }
 long tlb_tick_count(const tlb_tick *t) { return t ? t->ticks : 0; }
 int tlb_tick_set_gain_db(tlb_tick *t, int stream, double gain_db)
 {
     if (!t || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
-    for (auto &G : t->groups) {
-        if (stream >= 0 && (stream < G.first || stream >= G.first + G.n)) continue;
-        if (int rc = tlb_set_gain_db(G.b, stream < 0 ? -1 : stream - G.first, gain_db)) return rc;
-    }
-    return TLB_OK;
+    return t->blocks.visit(stream, [&](int g, int k) { return tlb_set_gain_db(t->groups[(size_t)g].b, k, gain_db); });
 }
 
 // Life cycle of one stream of a tick object (tlb_stream_reset / _finish / _reconfigure of its group's batch).  The EDI sender state
 // of the stream (SEQ, DLFC, timestamps) is NOT touched: the receiver sees one continuous sender whose encoder was restarted, as
 // with the reference, whose output object outlives an encoder re-initialisation.  Until the stream's next frame is final its
 // slots are empty (length 0).
-static TickGroup *tick_group_of(tlb_tick *t, int stream, int *local)
-{
-    if (!t || stream < 0 || stream >= t->nstreams) return nullptr;
-    TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    *local = stream - G.first;
-    return &G;
-}
 int tlb_tick_stream_reset(tlb_tick *t, int stream)
 {
-    int k; TickGroup *G = tick_group_of(t, stream, &k);
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
     if (!G || t->finished) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     return tlb_stream_reset(G->b, k);
 }
 int tlb_tick_stream_finish(tlb_tick *t, int stream, uint8_t *out, size_t out_size)
 {
-    int k; TickGroup *G = tick_group_of(t, stream, &k);
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
     if (!G || t->finished) return -TLB_ERR_ARG;
     if (t->broken) return -TLB_ERR_HIP;
     return tlb_stream_finish(G->b, k, out, out_size);
 }
 int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config *cfg)
 {
-    int k; TickGroup *G = tick_group_of(t, stream, &k);
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
     if (!G || t->finished) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     const int rc = tlb_stream_reconfigure(G->b, k, cfg);
@@ -575,7 +561,7 @@ int tlb_debug_tick_fail_next(tlb_tick *t, int nth) { if (!t || nth < 0) return T
 // and what the monitor sees are the same damaged bytes.  Host-queued copies on s_run, the stream waited for in between: nothing faults.
 int tlb_debug_tick_damage_next(tlb_tick *t, int stream, int byte, int xor_mask, int nth)
 {
-    if (!t || nth < 0 || stream < 0 || stream >= t->nstreams || byte < 0 || byte >= t->groups[(size_t)t->group_of[(size_t)stream]].out_stride) return TLB_ERR_ARG;
+    if (!t || nth < 0 || stream < 0 || stream >= t->nstreams || byte < 0 || byte >= t->groups[(size_t)t->blocks.owner(stream)].out_stride) return TLB_ERR_ARG;
     t->damage_nth = nth; t->damage_stream = stream; t->damage_byte = byte; t->damage_xor = (uint8_t)xor_mask;
     return TLB_OK;
 }
@@ -584,7 +570,7 @@ int tlb_debug_tick_damage_next(tlb_tick *t, int stream, int byte, int xor_mask, 
 // that are valid in every respect.  Both streams must lie in one group.  Device-to-device copies queued on s_run; nothing faults.
 int tlb_debug_tick_cross_from(tlb_tick *t, int a, int b, int nth)
 {
-    if (!t || nth < 0 || a < 0 || b < 0 || a >= t->nstreams || b >= t->nstreams || a == b || t->group_of[(size_t)a] != t->group_of[(size_t)b]) return TLB_ERR_ARG;
+    if (!t || nth < 0 || a < 0 || b < 0 || a >= t->nstreams || b >= t->nstreams || a == b || t->blocks.owner(a) != t->blocks.owner(b)) return TLB_ERR_ARG;
     if (!t->d_cross_tmp) {
         HIPCHK(hipSetDevice(t->device));
         size_t widest = 0;                                           // one buffer for every later call: any group's slot fits
@@ -727,53 +713,52 @@ int tlb_tick_finish(tlb_tick *t)
 }
 
 const uint32_t *tlb_tick_silence_ms(const tlb_tick *t) { return t ? t->h_silence[t->out_set] : nullptr; }
+// the per-unit outputs of a group are unit-major: slot (unit, local stream) of its packets / messages / fragment counts
+static size_t tick_slot(const TickGroup &G, int unit, int k) { return (size_t)unit * (size_t)G.n + (size_t)k; }
 const uint8_t *tlb_tick_message(const tlb_tick *t, int stream, int unit, int *len)
 {   // ZeroMQ message = zmq_frame_header_t + unit; the header's datasize field says how much follows (0: absent)
-    if (!t || stream < 0 || stream >= t->nstreams || t->egress != TLB_TICK_ZMQ) return nullptr;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    if (unit < 0 || unit >= G.max_upf) return nullptr;
-    const uint8_t *m = G.h_msgs[t->out_set] + ((size_t)unit * (size_t)G.n + (size_t)(stream - G.first)) * (size_t)G.msg_stride;
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    if (!G || t->egress != TLB_TICK_ZMQ || unit < 0 || unit >= G->max_upf) return nullptr;
+    const uint8_t *m = G->h_msgs[t->out_set] + tick_slot(*G, unit, k) * (size_t)G->msg_stride;
     uint32_t ds; memcpy(&ds, m + 4, 4);
     if (len) *len = ds ? (int)(12 + ds) : 0;                         // (a set no tick has written yet is all zeros)
     return m;
 }
 int tlb_tick_units(const tlb_tick *t, int stream)
 {
-    if (!t || stream < 0 || stream >= t->nstreams) return 0;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    if (!G) return 0;
     if (t->egress == TLB_TICK_FRAMES) return 1;
-    return tlb_egress_units_per_frame(G.b, stream - G.first);
+    return tlb_egress_units_per_frame(G->b, k);
 }
 const uint8_t *tlb_tick_frame(const tlb_tick *t, int stream, int *len)
 {
-    if (!t || stream < 0 || stream >= t->nstreams || t->egress != TLB_TICK_FRAMES) return nullptr;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    if (len) *len = G.h_flen[t->out_set][stream - G.first];
-    return G.h_frames[t->out_set] + (size_t)(stream - G.first) * (size_t)G.out_stride;
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    if (!G || t->egress != TLB_TICK_FRAMES) return nullptr;
+    if (len) *len = G->h_flen[t->out_set][k];
+    return G->h_frames[t->out_set] + (size_t)k * (size_t)G->out_stride;
 }
 const uint8_t *tlb_tick_packet(const tlb_tick *t, int stream, int unit, int *len)
 {
-    if (!t || stream < 0 || stream >= t->nstreams || t->egress != TLB_TICK_EDI_AF) return nullptr;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    if (unit < 0 || unit >= G.max_upf) return nullptr;
-    const size_t slot = (size_t)unit * (size_t)G.n + (size_t)(stream - G.first);
-    if (len) *len = G.h_plen[t->out_set][slot];
-    return G.h_pkts[t->out_set] + slot * (size_t)G.af_stride;
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    if (!G || t->egress != TLB_TICK_EDI_AF || unit < 0 || unit >= G->max_upf) return nullptr;
+    const size_t slot = tick_slot(*G, unit, k);
+    if (len) *len = G->h_plen[t->out_set][slot];
+    return G->h_pkts[t->out_set] + slot * (size_t)G->af_stride;
 }
 int tlb_tick_fragments(const tlb_tick *t, int stream, int unit)
 {
-    if (!t || stream < 0 || stream >= t->nstreams || t->egress != TLB_TICK_EDI_PFT) return 0;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    if (unit < 0 || unit >= G.max_upf) return 0;
-    return G.h_nfrag[t->out_set][(size_t)unit * (size_t)G.n + (size_t)(stream - G.first)];
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    if (!G || t->egress != TLB_TICK_EDI_PFT || unit < 0 || unit >= G->max_upf) return 0;
+    return G->h_nfrag[t->out_set][tick_slot(*G, unit, k)];
 }
 const uint8_t *tlb_tick_fragment(const tlb_tick *t, int stream, int unit, int k, int *len)
 {
     if (k < 0 || k >= tlb_tick_fragments(t, stream, unit)) return nullptr;
-    const TickGroup &G = t->groups[(size_t)t->group_of[(size_t)stream]];
-    const size_t slot = (size_t)unit * (size_t)G.n + (size_t)(stream - G.first);
-    if (len) *len = G.h_fraglen[t->out_set][slot * (size_t)G.max_frags + (size_t)k];
-    return G.h_frags[t->out_set] + (slot * (size_t)G.max_frags + (size_t)k) * (size_t)G.frag_stride;
+    int ks; const TickGroup *G = tick_group_of(t, stream, &ks);
+    const size_t frag = tick_slot(*G, unit, ks) * (size_t)G->max_frags + (size_t)k;
+    if (len) *len = G->h_fraglen[t->out_set][frag];
+    return G->h_frags[t->out_set] + frag * (size_t)G->frag_stride;
 }
 float tlb_tick_last_ms(tlb_tick *t)
 {   // first copy-in queued -> last copy-out done, on the device's clock
