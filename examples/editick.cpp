@@ -7,11 +7,13 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
 //   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
 //   header's padding bit, service s takes frame (tick + s) of it (wrapping round), one tick per frame of the file.  No PCM crosses the
 //   link; in.s16le is not opened (give "-").  Not together with --short-every or --source-rate.
+//   --feed-rate R, --feed-channels C: the file is at another (legal) rate or channel count than the encoder's, an ADAPTED feed
+//   (tlb_tick_set_feed_adapted): on the ticks tlb_tick_feed_want says want no frame the slot stays empty and the file does not advance.
 //   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
 //   encoder's rate on the device (tlb_tick_set_source): each tick reads tlb_tick_need() source frames per stream, not 1152.  Not together
 //   with --short-every.
@@ -43,7 +45,7 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
@@ -52,7 +54,8 @@ int main(int argc, char **argv)
     char mode = 0;
     double gain_db = 0.0;
     const char *feed_path = nullptr;
-    int feed_kbps = 0;
+    int feed_kbps = 0, feed_channels = 0;
+    long feed_rate = 0;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
@@ -71,6 +74,8 @@ int main(int argc, char **argv)
         else if (k == "--source-rate") source_rate = std::atol(v);
         else if (k == "--feed") feed_path = v;
         else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
+        else if (k == "--feed-rate") feed_rate = std::atol(v);
+        else if (k == "--feed-channels") feed_channels = std::atoi(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -83,7 +88,8 @@ int main(int argc, char **argv)
     if ((feed_path != nullptr) != (feed_kbps > 0)) die("--feed FILE.mp2 --feed-bitrate K: both or neither", 0);
     std::FILE *fi = feed_path ? nullptr : std::fopen(argv[1], "rb");
     if (!feed_path && !fi) die("cannot open input", 0);
-    tlb_feed_config feed = {rate, feed_kbps, channels};
+    tlb_feed_config feed = {feed_rate ? feed_rate : rate, feed_kbps, feed_channels ? feed_channels : channels};      // the encoder's unless told otherwise
+    const bool adapt = feed.samplerate != rate || feed.channels != channels;
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;                              // --feed: where each frame lies in the file
     if (feed_path) {
@@ -121,7 +127,8 @@ int main(int argc, char **argv)
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
     if (source_rate) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
-    if (feed_path) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);                   // likewise
+    if (feed_path && !adapt) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);         // likewise
+    if (feed_path && adapt) if (int rc = tlb_tick_set_feed_adapted(t, -1, &feed)) die("tlb_tick_set_feed_adapted", rc);
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
@@ -151,15 +158,19 @@ int main(int argc, char **argv)
                     alarms++;
                 }
     };
-    for (; feed_path && frames < (long)fpos.size();) {           // one tick per frame of the feed
+    size_t used = 0;                                             // feed frames stream 0 has been given; stream s is s frames ahead in the file
+    for (; feed_path;) {                                         // one tick per wanted frame of the feed, and the ticks between that want none
+        const bool want = tlb_tick_feed_want(t, 0) > 0;          // (every stream has the one configuration: all want a frame or none does)
+        if (want && used == fpos.size()) break;
         uint8_t *fr = tlb_tick_feed(t);                          // pinned [nstreams][tlb_tick_feed_stride()], re-fetched every tick like the PCM
         int32_t *ln = tlb_tick_feed_len(t);                      // pinned [nstreams]: every set comes back all 0
         const size_t stride = (size_t)tlb_tick_feed_stride(t);
-        for (int s = 0; s < nstreams; s++) {
-            const size_t k = ((size_t)frames + (size_t)s) % fpos.size();
+        for (int s = 0; s < nstreams && want; s++) {
+            const size_t k = (used + (size_t)s) % fpos.size();
             std::memcpy(fr + stride * (size_t)s, &mp2[fpos[k]], flen[k]);
             ln[s] = (int32_t)flen[k];
         }
+        used += want;
         if (int rc = tlb_tick_run(t)) die("tlb_tick_run", rc);
         const tlb_frame_report *rep = tlb_tick_feed_report(t);   // a frame that did not pass went in as silence
         for (int s = 0; s < nstreams; s++) bad_feed += (rep[s].status & TLB_DEC_BAD_MASK) != 0;

@@ -11,8 +11,10 @@
 // --verify: every frame is read back on the device right after it was encoded (tlb_decode_host: header, CRC-16, ScF-CRC, bit budget);
 // any TLB_DEC_BAD_MASK flag ends the run with exit status 3.
 // --from-mp2: the input is an MPEG Layer II file, a transcode: its first header gives the feed's rate, bitrate and channel count (which are
-// then the encoder's rate and channel count, -r and -c are not needed), the file is cut into frames by the arithmetic length and each
+// then the encoder's rate and channel count unless -r / -c say otherwise), the file is cut into frames by the arithmetic length and each
 // header's padding bit, and the frames are decoded on the device into the ingest's input (tlb_feed_host) instead of PCM being read.
+// With -r or -c another (legal) rate or channel count than the file's, the feed is an ADAPTED one (tlb_feed_set_adapted): 44.1 kHz for a
+// 48 kHz encoder, stereo for mono, ...; a slot of the call then holds a frame only on the ticks tlb_feed_want_at says want one.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -39,15 +41,15 @@ int main(int argc, char **argv)
     int channels = 2, kbps = 128, psy = 1, nstreams = 1;
     char mode = 0;
     double gain_db = 0.0;
-    bool verify = false, from_mp2 = false;
+    bool verify = false, from_mp2 = false, rate_given = false, channels_given = false;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--verify") { verify = true; i -= 1; continue; }
         if (k == "--from-mp2") { from_mp2 = true; i -= 1; continue; }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
-        if (k == "-r") rate = std::atol(v);
-        else if (k == "-c") channels = std::atoi(v);
+        if (k == "-r") { rate = std::atol(v); rate_given = true; }
+        else if (k == "-c") { channels = std::atoi(v); channels_given = true; }
         else if (k == "-b") kbps = std::atoi(v);
         else if (k == "-m") mode = v[0];
         else if (k == "-p") psy = std::atoi(v);
@@ -74,6 +76,7 @@ int main(int argc, char **argv)
     std::fclose(fi);
     tlb_feed_config feed = {0, 0, 0};
     std::vector<size_t> fpos, flen;                           // --from-mp2: where each frame lies in the file
+    std::vector<long> tick_frame;                             // ... and the frame tick f's slot holds (-1: none is wanted on that tick)
     if (from_mp2) {
         if (mp2.size() < 4 || mp2[0] != 0xff || (mp2[1] & 0xf6) != 0xf4) die("the input does not begin with a Layer II header", 0);
         const int lsf = !(mp2[1] & 0x08), bi = mp2[2] >> 4, fi2 = (mp2[2] >> 2) & 3;
@@ -81,7 +84,8 @@ int main(int argc, char **argv)
         static const long fs[2][4] = {{44100, 48000, 32000, 0}, {22050, 24000, 16000, 0}};
         feed = tlb_feed_config{fs[lsf][fi2], kb[lsf][bi], (mp2[3] >> 6) == 3 ? 1 : 2};
         if (tlb_feed_check_config(&feed) != TLB_OK) die("the input's first header names no legal Layer II configuration", tlb_feed_check_config(&feed));
-        rate = feed.samplerate; channels = feed.channels;
+        if (!rate_given) rate = feed.samplerate;
+        if (!channels_given) channels = feed.channels;
         const size_t base = (size_t)tlb_feed_frame_bytes(&feed);
         for (size_t o = 0; o + 4 <= mp2.size();) {            // the sync word, the arithmetic length, one more with the padding bit
             if (mp2[o] != 0xff || (mp2[o + 1] & 0xf0) != 0xf0) die("the input has no sync word where a frame should begin, at byte", (int)o);
@@ -90,11 +94,17 @@ int main(int argc, char **argv)
             fpos.push_back(o); flen.push_back(n);
             o += n;
         }
+        for (long f = 0, k = 0;; f++) {                       // one tick per 1152 OUTPUT frames, until a wanted frame is not there
+            const int w = tlb_feed_want_at(feed.samplerate, rate, f);
+            if (w < 0) die("the input's rate and -r form no legal pair", -w);
+            if (w && k == (long)fpos.size()) break;
+            tick_frame.push_back(w ? k++ : -1);
+        }
     }
     if (!mode) mode = channels == 1 ? 'm' : 'j';             // odr-audioenc's defaults (src/odr-audioenc.cpp:697-709)
     if (channels != 1 && channels != 2) die("1 or 2 channels", channels);
     const size_t per_frame = 1152u * (size_t)channels;
-    const int nframes = from_mp2 ? (int)fpos.size() : (int)(in.size() / per_frame);
+    const int nframes = from_mp2 ? (int)tick_frame.size() : (int)(in.size() / per_frame);
     if (nframes == 0) die("input shorter than one frame", 0);
 
     std::vector<tlb_stream_config> cfg((size_t)nstreams, tlb_stream_config{rate, mode, kbps, psy, 0});
@@ -103,7 +113,9 @@ int main(int argc, char **argv)
     if (!enc) die("tlb_create", err);
     if (gain_db != 0.0 && (err = tlb_set_gain_db(enc, -1, gain_db)) != TLB_OK) die("tlb_set_gain_db", err);
 
-    if (from_mp2 && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
+    const bool adapt = from_mp2 && (rate != feed.samplerate || channels != feed.channels);
+    if (from_mp2 && !adapt && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
+    if (adapt && (err = tlb_feed_set_adapted(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set_adapted", err);
     const int fstride = tlb_feed_stride(enc);
 
     const int stride = tlb_out_stride(enc);
@@ -139,8 +151,11 @@ int main(int argc, char **argv)
         for (int f = 0; f < nf; f++)                         // every stream of the batch gets the same programme
             for (int s = 0; s < nstreams; s++) {
                 const size_t slot = (size_t)f * nstreams + s;
-                if (from_mp2) { std::memcpy(&ffr[slot * fstride], &mp2[fpos[(size_t)(f0 + f)]], flen[(size_t)(f0 + f)]); fln[slot] = (int32_t)flen[(size_t)(f0 + f)]; }
-                else std::memcpy(&inter[slot * 2304], &in[(size_t)(f0 + f) * per_frame], per_frame * sizeof(int16_t));
+                if (from_mp2) {
+                    const long k = tick_frame[(size_t)(f0 + f)];
+                    fln[slot] = k < 0 ? 0 : (int32_t)flen[(size_t)k];
+                    if (k >= 0) std::memcpy(&ffr[slot * fstride], &mp2[fpos[(size_t)k]], flen[(size_t)k]);
+                } else std::memcpy(&inter[slot * 2304], &in[(size_t)(f0 + f) * per_frame], per_frame * sizeof(int16_t));
             }
         if (from_mp2) {                                      // the decode, into what the ingest reads; a frame that does not pass goes in as silence
             if ((err = tlb_feed_host(enc, ffr.data(), fln.data(), nf, inter.data(), frep.data())) != TLB_OK) die("tlb_feed_host", err);
@@ -169,8 +184,8 @@ int main(int argc, char **argv)
     std::fclose(fo);
     std::fprintf(stderr, "mp2enc: %d frames x %d stream(s) in %.3f s = %.0f frames/s (%.0f x real time per stream); %ld bytes written; %s\n",
                  nframes, nstreams, dt, (double)nframes * nstreams / dt, (double)nframes * 1152.0 / (double)rate / dt, written, tlb_version());
-    if (from_mp2) std::fprintf(stderr, "mp2enc: transcoded from %ld Hz, %d kbps, %d channel(s): %d frames, %ld did not pass and went in as silence\n",
-                               feed.samplerate, feed.bitrate, feed.channels, nframes, bad_feed);
+    if (from_mp2) std::fprintf(stderr, "mp2enc: transcoded from %ld Hz, %d kbps, %d channel(s): %zu frames, %ld did not pass and went in as silence\n",
+                               feed.samplerate, feed.bitrate, feed.channels, fpos.size(), bad_feed);
     if (verify) std::fprintf(stderr, "mp2enc: verify ok: %ld frames read back on the device, %ld bad\n", checked, tlb_decode_bad_frames(enc));
     tlb_destroy(enc);
     return 0;

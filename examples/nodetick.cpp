@@ -25,7 +25,8 @@
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file (48 kHz, two channels, K kbps) decoded on the GPUs ahead
 //   of the ingest (tlb_node_set_feed): the file is cut into frames by the arithmetic length and each header's padding bit, service s takes
 //   frame (tick + s) of it, wrapping round; no PCM crosses the link and in.s16le is not opened (give "-").  Not together with --short-every
-//   or --source-rate.
+//   or --source-rate.  --feed-rate R, --feed-channels C: the file is at another (legal) rate or channel count than the services', an ADAPTED
+//   feed (tlb_node_set_feed_adapted): a service's slot gets its next frame only on the ticks tlb_node_feed_want says want one.
 //   --source-rate R: in.s16le is at R Hz (44100 or 32000) and is resampled to 48 kHz on the GPUs (tlb_node_set_source): service s starts
 //   reading at source frame 1152 s and takes tlb_node_need() consecutive frames every tick, wrapping around.  Not together with --short-every.
 //   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
@@ -59,6 +60,7 @@ struct Ctx {
     std::vector<size_t> *spos;                               // --source-rate: the next source frame of every service
     const std::vector<uint8_t> *mp2;                         // --feed: the file and where its frames lie (NULL: PCM input)
     const std::vector<size_t> *fpos, *flen;
+    std::vector<size_t> *fcur;                               // --feed-rate / --feed-channels (an adapted feed): the next frame of every service; NULL: a strict feed
 };
 
 // step 1 on shard `g`'s thread: the block's services copy their frame of this tick into the pinned input set
@@ -72,7 +74,11 @@ static void fill(void *vctx, int g, int first, int n)
             if (tlb_node_shard_status(c.nd, g, nullptr) != TLB_SHARD_OK) return;
             die("no feed set free", s);
         }
-        const size_t f = ((size_t)s + (size_t)c.tick) % c.fpos->size();
+        size_t f = ((size_t)s + (size_t)c.tick) % c.fpos->size();
+        if (c.fcur) {                                            // an adapted feed: a frame only where this tick wants one, and the file advances only then
+            if (tlb_node_feed_want(c.nd, s) <= 0) continue;
+            f = (*c.fcur)[(size_t)s]++ % c.fpos->size();
+        }
         std::memcpy(slot, c.mp2->data() + (*c.fpos)[f], (*c.flen)[f]);
         *len = (int32_t)(*c.flen)[f];                            // untouched, it reads 0: an empty slot
     }
@@ -119,13 +125,14 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
     int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
     double deadline_ms = 0;
     long source_rate = 0;
-    int feed_kbps = 0;
+    int feed_kbps = 0, feed_channels = 2;
+    long feed_rate = 48000;
     std::string devs, outpath, feed_path;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
@@ -145,6 +152,8 @@ int main(int argc, char **argv)
         else if (k == "--source-rate") source_rate = std::atol(v);
         else if (k == "--feed") feed_path = v;
         else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
+        else if (k == "--feed-rate") feed_rate = std::atol(v);
+        else if (k == "--feed-channels") feed_channels = std::atoi(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -163,11 +172,12 @@ int main(int argc, char **argv)
     G = (int)devices.size();
 
     if (feed_path.empty() != (feed_kbps <= 0)) die("--feed FILE.mp2 --feed-bitrate K: both or neither", 0);
-    tlb_feed_config feed = {48000, feed_kbps, 2};
+    tlb_feed_config feed = {feed_rate, feed_kbps, feed_channels};   // the services' own rate and channel count unless told otherwise
+    const bool adapt = feed_rate != 48000 || feed_channels != 2;
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;
     if (!feed_path.empty()) {
-        if (int rc = tlb_feed_check_config(&feed)) die("--feed-bitrate: no legal Layer II bitrate at 48 kHz", rc);
+        if (int rc = tlb_feed_check_config(&feed)) die("--feed-bitrate: no legal Layer II configuration at this rate and channel count", rc);
         std::FILE *ff = std::fopen(feed_path.c_str(), "rb");
         if (!ff) die("cannot open the feed", 0);
         uint8_t buf[1 << 15];
@@ -222,16 +232,17 @@ int main(int argc, char **argv)
     if (source_rate)
         if (int rc = tlb_node_set_source(nd, -1, source_rate)) die("tlb_node_set_source", rc);          // between steps; a restarted shard's sources are set again
     if (!feed_path.empty())
-        if (int rc = tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
+        if (int rc = adapt ? tlb_node_set_feed_adapted(nd, -1, &feed) : tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare)
         if (int rc = tlb_node_enable_compare(nd, &cparams)) die("tlb_node_enable_compare", rc);         // after the audio monitor, before the first submit
 
     std::vector<uint64_t> hash((size_t)G, 1469598103934665603ull);
     std::vector<long> packets((size_t)G, 0), bytes((size_t)G, 0);
-    std::vector<size_t> spos((size_t)nstreams);
+    std::vector<size_t> spos((size_t)nstreams), fcur((size_t)nstreams);
+    for (int s = 0; s < nstreams; s++) fcur[(size_t)s] = (size_t)s;     // an adapted feed: service s starts s frames into the file
     for (int s = 0; s < nstreams && !pcm.empty(); s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen};
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt ? &fcur : nullptr};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick

@@ -582,6 +582,7 @@ enum {
     TLB_DEC_EMPTY = 0x01, TLB_DEC_BAD_SYNC = 0x02, TLB_DEC_HEADER_MISMATCH = 0x04, TLB_DEC_BAD_CRC16 = 0x08, TLB_DEC_BAD_SCFCRC = 0x10,
     TLB_DEC_SCFCRC_UNCHECKED = 0x20, TLB_DEC_BAD_ALLOC = 0x40, TLB_DEC_OVERRUN = 0x80,
     TLB_DEC_BAD_MASK = 0x02 | 0x04 | 0x08 | 0x10 | 0x40 | 0x80,
+    TLB_DEC_UNWANTED = 0x100,     /* adapted feeds only (below): the slot held bytes on a tick whose slot is not read; not in TLB_DEC_BAD_MASK */
 };
 typedef struct { uint32_t status; uint16_t crc_stored, crc_computed; uint8_t mode, mode_ext; uint16_t audio_bits; } tlb_frame_report;
 typedef struct { uint8_t bit_alloc[2][32], scfsi[2][32], scalar[2][3][32]; uint16_t subband[2][3][12][32]; } tlb_frame_fields;
@@ -810,9 +811,45 @@ int tlb_node_need(const tlb_node *nd, int stream);
  * and MPEG Layer II is what studio links, satellite feeds and re-multiplexed services carry.  A 192 kbps feed frame is 576 bytes.
  * A FEED is a per-stream configuration of its own -- sample rate, bitrate, channels (1 | 2) -- and tlb_feed_*() decodes a feed frame into
  * the stream's slot of tlb_ingest_device's input, with the parser, requantiser and fp64 synthesis filterbank of tlb_decode_*() above.
- * IN THIS VERSION the feed's samplerate must be the stream's and its channels the stream's channel count (else TLB_ERR_SAMPLERATE /
- * TLB_ERR_MODE from tlb_feed_set): a feed at another rate needs a per-stream sample queue in front of the resampler, a stereo feed for a
- * mono service needs a downmix; both are out of scope.  The bitrate is the feed's own.
+ * tlb_feed_set, tlb_tick_set_feed and tlb_node_set_feed take a feed whose samplerate is the stream's and whose channels are the stream's
+ * channel count (else TLB_ERR_SAMPLERATE / TLB_ERR_MODE).  The bitrate is the feed's own.
+ * ADAPTED FEEDS.  A feed is ADAPTED when it is set through tlb_feed_set_adapted(b, stream, cfg) (tlb_tick_set_feed_adapted,
+ * tlb_node_set_feed_adapted) and cfg does not match every named stream; a cfg that does is the strict feed above, with the same device
+ * calls.  Legal pairs (feed rate Fs, stream rate Es): Fs = Es (ratio 1/1) and the four pairs of the resampler, 44100 -> 48000, 22050 ->
+ * 24000 (L/M = 160/147), 32000 -> 48000, 16000 -> 24000 (3/2); anything else is TLB_ERR_SAMPLERATE.  Channels may be 1 or 2 on either
+ * side.  Bitrate and configuration legality are tlb_feed_check_config's.
+ * SCHEDULE.  A feed frame is 1152 source frames, a tick consumes 1058 / 1059 (160/147) or 768 (3/2) of them, so a frame is not wanted on
+ * every tick.  With q(n) = floor(n M / L) and ticks f counted from the stream's last reset:
+ *   S(f) = f > 0 ? q(1152 f - 1) + 1 : 0     source frames consumed before tick f (S(f + 1) - S(f) is tlb_resample_need_at)
+ *   K(f) = ceil(S(f + 1) / 1152), K(-1) = 0  feed frames that must have arrived by tick f
+ *   want(f) = K(f) - K(f - 1)                0 or 1, never 0 on two consecutive ticks
+ * 160/147: 147 of every 160 ticks are wanted, the first unwanted ones are 12, 24, 36, 49; 3/2: ticks 2, 5, 8, ... are unwanted; 1/1: every
+ * tick is wanted.  Before any tick at most 1145 (160/147) or 768 (3/2) decoded source frames are unconsumed.
+ * AUDIO.  d_k: the 1152 sample frames tlb_feed_* defines for the stream's k-th WANTED slot under the feed's configuration (an empty or
+ * not passing slot gives zeros, the synthesis history runs over consecutive wanted slots, a bad or empty slot is silence for its successor).
+ * Channel map, on the decoded int16: a two-channel feed for a one-channel stream is x = (L + R + 1) >> 1 (arithmetic shift), applied
+ * BEFORE the resampler; a one-channel feed for a two-channel stream is resampled once and the output written to both channels.  y(n) is
+ * the resampler's formula above over x = d_0 d_1 ... (for 1/1, y = x), and tick f's ingest slot gets y(1152 f .. 1152 f + 1151),
+ * interleaved as the ingest reads it; nothing is written behind it.  The output does not depend on how a stream's ticks are cut into calls.
+ * A slot on an UNWANTED tick is not read and its bytes do not enter the feed history: its report is TLB_DEC_EMPTY, and TLB_DEC_EMPTY |
+ * TLB_DEC_UNWANTED when its length was > 0 (the caller broke the schedule); the tick's PCM is produced from the queue either way.
+ * tlb_feed_reset, tlb_reset, tlb_stream_reset and tlb_stream_finish zero the position and the queue of the streams they touch: the next
+ * tick is tick 0.  tlb_stream_reconfigure keeps an adapted feed when (Fs, new Es) is still a legal pair, whatever the channel counts,
+ * with fresh state, and removes it otherwise.  The stream's own tlb_resample_* state is a separate object and is not touched.
+ *   tlb_feed_set_adapted(b, stream, cfg)  stream = -1: all; cfg NULL: as tlb_feed_set(.., NULL); every named stream is checked before
+ *                                 anything changes.  The first adapted feed allocates the queue state (about 9.5 KB per stream of the
+ *                                 batch) and a source plane (4.6 KB per stream and tick of the longest call): a batch that never sets one
+ *                                 allocates nothing new and queues the device calls it queued before.
+ *   tlb_feed_adapted(b, stream)   1 / 0; < 0: -TLB_ERR_ARG
+ *   tlb_feed_want(b, stream, ahead)  1 / 0 for the stream's (ahead)-th next tick, from the host's own copy of the position (advanced by
+ *                                 every tlb_feed_device call, cleared by the resets; no device access, like tlb_resample_need); 1 for a
+ *                                 strict feed; < 0: -TLB_ERR_ARG (also: the stream has no feed)
+ *   tlb_feed_want_at(Fs, Es, tick)  host only, no batch, no GPU; < 0: -TLB_ERR_SAMPLERATE (no legal pair), -TLB_ERR_ARG (tick < 0)
+ * tlb_feed_device / _host, tlb_feed_stride, tlb_feed_get and the tick and node buffers and reports are the same for both kinds, and a
+ * batch may hold strict feeds, adapted feeds and streams without a feed together: the strict launch runs first where a stream has a
+ * strict feed, then one sequence of three kernels (decode, resample, carry) per call, however many ticks it holds, with no host
+ * synchronisation inside a call.  A call over a batch with adapted feeds holds at most 8192 ticks (TLB_ERR_ARG beyond).
+ * NOT BUILT: downsampling (48 -> 24 kHz, 48 -> 44.1 kHz) and a channel map for PCM sources.
  *   d_frames      uint8 [nframes][nstreams][tlb_feed_stride()]
  *   d_len         int32 [nframes][nstreams], required; 0 (or less) = an empty slot
  *   d_interleaved int16 [nframes][nstreams][2304], tlb_ingest_device's input: a fed stream's slot gets 1152 sample frames, L R L R for two
@@ -876,6 +913,11 @@ int tlb_node_need(const tlb_node *nd, int stream);
  * tlb_tick_set_feed is all or nothing for the feeds: after a device failure half way the groups already changed get back the feeds they
  * had (with fresh history); buffers that were widened for the call stay.  After tlb_tick_finish, which runs no feed kernel,
  * tlb_tick_feed_report shows the last tick's reports once more.
+ * tlb_tick_set_feed_adapted(t, stream, cfg) is tlb_tick_set_feed for an adapted feed: the same conditions (no tick in flight), the same
+ * exclusions (short reads, source rates, from either side), the same all-or-nothing rule, the same buffers and reports; a group all of
+ * whose streams are fed still skips its PCM copy-in, and the monitor and the compare monitor compose with it unchanged.
+ *   tlb_tick_feed_want(t, stream)  1 / 0: does the stream's slot of the input set to fill next want a frame (1 for a strict feed); the
+ *                            position advances with every submit; < 0: -TLB_ERR_ARG (also: the stream has no feed)
  * NODE LEVEL.  tlb_node_set_feed routes to the owning shard (stream = -1: every stream; between steps only, TLB_ERR_ARG otherwise; every
  * named stream is checked before a shard is changed; a broken shard answers TLB_ERR_HIP, a late one TLB_ERR_LATE; after a device failure
  * half way the shards already changed get back the feeds they had) and is remembered: tlb_node_shard_restart sets the block's feeds again,
@@ -886,6 +928,10 @@ int tlb_node_need(const tlb_node *nd, int stream);
  * tlb_node_pcm; NULL for a broken or late shard, while two ticks are in flight and while no stream of the shard has a feed.
  * tlb_node_feed_report(nd, stream) is the stream's report of the step waited for last; NULL for a broken, late or stale shard and while no
  * stream of the shard has a feed.
+ * tlb_node_set_feed_adapted is tlb_node_set_feed for an adapted feed, remembered as such: tlb_node_shard_restart sets the block's adapted
+ * feeds again at tick 0 and tlb_node_stream_reconfigure forgets one whose rates no longer form a legal pair.  tlb_node_feed_want(nd, stream)
+ * is tlb_tick_feed_want of the stream's shard (TICK plane; a broken or late shard answers as tlb_node_need does; a BATCH-plane node
+ * answers -TLB_ERR_ARG: ask the shard's batch with tlb_feed_want).
  * ------------------------------------------------------------------------------------------ */
 typedef struct { long samplerate; int bitrate; int channels; } tlb_feed_config;   /* channels 1 | 2 */
 int tlb_feed_check_config(const tlb_feed_config *cfg);
@@ -897,6 +943,14 @@ int tlb_feed_reset(tlb_batch *b, int stream);
 int tlb_feed_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report,
                     void *hip_stream);
 int tlb_feed_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int nframes, int16_t *interleaved, tlb_frame_report *report);
+int tlb_feed_set_adapted(tlb_batch *b, int stream, const tlb_feed_config *cfg);
+int tlb_feed_adapted(const tlb_batch *b, int stream);
+int tlb_feed_want(const tlb_batch *b, int stream, int ahead);
+int tlb_feed_want_at(long feed_rate, long stream_rate, long tick);
+int tlb_tick_set_feed_adapted(tlb_tick *t, int stream, const tlb_feed_config *cfg);
+int tlb_tick_feed_want(const tlb_tick *t, int stream);
+int tlb_node_set_feed_adapted(tlb_node *nd, int stream, const tlb_feed_config *cfg);
+int tlb_node_feed_want(const tlb_node *nd, int stream);
 int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg);
 uint8_t *tlb_node_feed(tlb_node *nd, int stream);
 int32_t *tlb_node_feed_len(tlb_node *nd, int stream);

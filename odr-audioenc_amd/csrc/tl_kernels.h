@@ -11,6 +11,7 @@
 #include "mp2_dec_types.h"
 #include "mp2_compare.h"
 #include "mp2_resample.h"
+#include "mp2_feed_adapt.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -40,6 +41,8 @@ hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state
 hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
 // toolame_feed.hip: tl_feed_kernel over every (stream, slot) of the launch, then tl_feed_carry_kernel per stream
 hipError_t tlk_feed(hipStream_t st, const TlFeedLaunch &A);
+// toolame_feed_adapt.hip: the decode kernel over every (stream, slot) of the call, the resample kernel (one workgroup per slot), then the carry kernel per stream
+hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A);
 // toolame_ingest.hip: tl_ingest_valid_kernel (one workgroup per slot, valid int32 [nframes][nstreams]) and tl_underrun_kernel (256 threads, one per stream)
 hipError_t tlk_ingest_valid(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid, int16_t *out, int16_t *peaks, const double *gain,
                             const TlConfig *configs, const int32_t *stream_cfg, int nstreams);

@@ -1,7 +1,15 @@
 // tlb_feed.cpp -- the batch-level entry points of the Layer II feeds (include/toolame_batch.h, tlb_feed_*): the legality of a feed
 // configuration (host only), the per-stream feed table and history (allocated by the first tlb_feed_set) and one launch of the kernels of
 // toolame_feed.hip through tl_kernels.h.  Host C++.
+// ADAPTED feeds (tlb_feed_set_adapted; csrc/mp2_feed_adapt.h): the schedule (host only), the queue state and the source plane (allocated by
+// the first adapted feed that does not match its stream) and the launch of toolame_feed_adapt.hip behind the strict one.
 #include "tlb_internal.h"
+
+static_assert(TLB_DEC_UNWANTED == TL_DEC_UNWANTED && !(TL_DEC_UNWANTED & TL_DEC_BAD_MASK), "status flags");
+// the ratio of a legal (feed rate, stream rate) pair: TL_RS_OFF for equal rates, -1: none
+static int adapt_ratio(long feed, long enc) { return feed == enc ? TL_RS_OFF : tl_rs_ratio_of(feed, enc) != TL_RS_OFF ? tl_rs_ratio_of(feed, enc) : -1; }
+static long enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
+static bool adapted(const tlb_batch *b, int s) { return !b->fa_ratio.empty() && b->fa_ratio[(size_t)s] >= 0; }
 
 static char feed_mode(int channels) { return channels == 1 ? 'm' : 's'; }
 // the feed's kernel-side record: the stream configuration a frame of that rate, bitrate and channel count has (allocation table, sblimit,
@@ -27,6 +35,13 @@ int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
     return TLB_OK;
 }
 
+int feed_fits_adapted(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
+{
+    if (int rc = tlb_feed_check_config(cfg)) return rc;
+    for (int s = s0; s < s1; s++) if (adapt_ratio(cfg->samplerate, enc_rate(b, s)) < 0) return TLB_ERR_SAMPLERATE;
+    return TLB_OK;
+}
+
 int feed_slot_bytes(const tlb_feed_config *cfg)
 {
     TlConfig *c = new TlConfig;
@@ -39,6 +54,12 @@ int feed_clear_streams(tlb_batch *b, int s0, int n)
 {
     if (!b->d_feed_state) return TLB_OK;
     HIPCHK(hipMemset(b->d_feed_state + s0, 0, sizeof(TlDecStream) * (size_t)n));
+    if (!b->d_fa_carry) return TLB_OK;
+    for (int k = 0; k < 2; k++) {                                    // an adapted stream's next tick is tick 0 and its queue is empty
+        HIPCHK(hipMemset(b->d_fa_carry + ((size_t)k * (size_t)b->nstreams + (size_t)s0) * (TL_FA_CARRY * 2), 0, sizeof(int16_t) * TL_FA_CARRY * 2 * (size_t)n));
+        HIPCHK(hipMemset(b->d_fa_pos + (size_t)k * (size_t)b->nstreams + (size_t)s0, 0, sizeof(int32_t) * (size_t)n));
+    }
+    for (int s = s0; s < s0 + n; s++) b->fa_pos[(size_t)s] = 0;
     return TLB_OK;
 }
 
@@ -57,6 +78,41 @@ static int feed_prepare(tlb_batch *b)
     m.commit(b->mem);
     b->feed_cfg.assign(n, tlb_feed_config{0, 0, 0}); b->feed_idx.assign(n, -1);
     b->d_feed_cfg = fc; b->d_feed_state = st;
+    return TLB_OK;
+}
+
+// room for `frames` ticks per stream in the source plane: grow-only launch scratch with an owner of its own (the device is idle)
+static int adapt_plane_reserve(tlb_batch *b, int frames)
+{
+    if (frames <= b->fa_plane_frames) return TLB_OK;
+    std::unique_ptr<TlbMem> m(new TlbMem);
+    int16_t *pl = m->scratch<int16_t>((size_t)b->nstreams * (size_t)frames * 2304);
+    if (!m->settle()) return TLB_ERR_HIP;
+    b->fa_plane_mem.swap(m);
+    b->d_fa_plane = pl; b->fa_plane_frames = frames;
+    return TLB_OK;
+}
+
+// the first adapted feed: the stream -> record and ratio tables, the queue heads and positions (two copies), the resampler's tables and
+// a plane for calls of one tick (what a tick object makes); staged, settled, then committed
+static int adapt_prepare(tlb_batch *b)
+{
+    if (b->d_fa_cfg) return TLB_OK;
+    const size_t n = (size_t)b->nstreams;
+    int L, M, T;
+    const int16_t *t160 = tlb_resample_taps(44100, 48000, &L, &M, &T), *t3 = tlb_resample_taps(32000, 48000, &L, &M, &T);
+    TlbMem m;
+    int32_t *fc = m.scratch<int32_t>(n), *ra = m.dev<int32_t>(n), *po = m.dev<int32_t>(2 * n);
+    int16_t *ca = m.dev<int16_t>(2 * n * TL_FA_CARRY * 2), *tp = m.scratch<int16_t>((160 + 3) * TL_RS_TAPS);
+    std::vector<int32_t> none(n, -1);
+    m.upload(fc, none.data(), sizeof(int32_t) * n);
+    m.upload(tp, t160, sizeof(int16_t) * 160 * TL_RS_TAPS);
+    m.upload(tp + 160 * TL_RS_TAPS, t3, sizeof(int16_t) * 3 * TL_RS_TAPS);
+    if (m.failed()) return TLB_ERR_HIP;
+    if (int rc = adapt_plane_reserve(b, 1)) return rc;               // (settles; a plane without the rest is scratch nobody reads)
+    m.commit(b->mem);
+    b->fa_ratio.assign(n, -1); b->fa_pos.assign(n, 0);
+    b->d_fa_cfg = fc; b->d_fa_ratio = ra; b->d_fa_pos = po; b->d_fa_carry = ca; b->d_fa_taps = tp; b->fa_flip = 0;
     return TLB_OK;
 }
 
@@ -88,10 +144,20 @@ static int feed_reserve(tlb_batch *b, size_t count, int stride)
 }
 
 // streams [s0, s1) get feed record `idx` (-1: none); their history starts again
-static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_config &cfg)
+// adapt: the record goes into the adapted path's table and the strict kernel sees a stream without a feed
+static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_config &cfg, bool adapt = false)
 {
-    std::vector<int32_t> v((size_t)(s1 - s0), idx);
+    std::vector<int32_t> v((size_t)(s1 - s0), adapt ? -1 : idx);
     HIPCHK(hipMemcpy(b->d_feed_cfg + s0, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
+    if (b->d_fa_cfg) {
+        std::vector<int32_t> a((size_t)(s1 - s0), adapt ? idx : -1), r((size_t)(s1 - s0), 0);
+        for (int s = s0; s < s1 && adapt; s++) r[(size_t)(s - s0)] = adapt_ratio(cfg.samplerate, enc_rate(b, s));
+        HIPCHK(hipMemcpy(b->d_fa_cfg + s0, a.data(), sizeof(int32_t) * a.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b->d_fa_ratio + s0, r.data(), sizeof(int32_t) * r.size(), hipMemcpyHostToDevice));
+        for (int s = s0; s < s1; s++) b->fa_ratio[(size_t)s] = adapt && idx >= 0 ? r[(size_t)(s - s0)] : -1;
+        b->n_adapted = 0;
+        for (int32_t x : b->fa_ratio) b->n_adapted += x >= 0;
+    }
     for (int s = s0; s < s1; s++) { b->feed_idx[(size_t)s] = idx; b->feed_cfg[(size_t)s] = cfg; }
     return feed_clear_streams(b, s0, s1 - s0);
 }
@@ -100,8 +166,10 @@ int feed_after_reconfigure(tlb_batch *b, int stream)
 {
     if (b->feed_idx.empty() || b->feed_idx[(size_t)stream] < 0) return TLB_OK;
     const tlb_stream_config &sc = b->h_uniq[(size_t)b->h_stream_cfg[(size_t)stream]];
-    const tlb_feed_config &fc = b->feed_cfg[(size_t)stream];
-    if (fc.samplerate == sc.samplerate && fc.channels == (sc.mode == 'm' ? 1 : 2)) return TLB_OK;
+    const tlb_feed_config fc = b->feed_cfg[(size_t)stream];
+    if (adapted(b, stream)) {                                        // kept while the rates still form a legal pair, whatever the channel counts; the caller clears the state
+        if (adapt_ratio(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed_idx[(size_t)stream], fc, true);
+    } else if (fc.samplerate == sc.samplerate && fc.channels == (sc.mode == 'm' ? 1 : 2)) return TLB_OK;
     return feed_assign(b, stream, stream + 1, -1, tlb_feed_config{0, 0, 0});
 }
 
@@ -123,13 +191,33 @@ int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int
         }
         d_report = (tlb_frame_report *)b->d_feed_rep;
     }
+    int n_strict = 0;
+    for (int s = 0; s < b->nstreams; s++) n_strict += b->feed_idx[(size_t)s] >= 0 && !adapted(b, s);
+    if (b->n_adapted) {
+        if (nframes > TL_FA_MAX_FRAMES) return TLB_ERR_ARG;
+        if (nframes > b->fa_plane_frames) {
+            HIPCHK(hipDeviceSynchronize());      // (a launch before may still read the one it replaces)
+            if (int rc = adapt_plane_reserve(b, nframes)) return rc;
+        }
+    }
     TlFeedLaunch A;
     memset(&A, 0, sizeof A);
     A.tables = b->d_tables; A.configs = b->d_feed_configs; A.feed_cfg = b->d_feed_cfg; A.synth = b->d_synth;
     A.frames = d_frames; A.len = d_len; A.report = (TlFrameReport *)d_report; A.pcm = d_interleaved;
     A.state = b->d_feed_state; A.prev = b->d_feed_prev; A.prev_stride = b->feed_prev_stride;
     A.nstreams = b->nstreams; A.nframes = nframes; A.stride = stride;
-    HIPCHK(tlk_feed((hipStream_t)hip_stream, A));
+    if (n_strict || !b->n_adapted) HIPCHK(tlk_feed((hipStream_t)hip_stream, A));
+    if (!b->n_adapted) return TLB_OK;
+    // the adapted streams, behind the strict launch (to which they are streams without a feed): decode, resample, carry
+    TlFeedAdaptLaunch D;
+    memset(&D, 0, sizeof D);
+    D.F = A; D.F.feed_cfg = b->d_fa_cfg;
+    D.ratio = b->d_fa_ratio; D.sconfigs = b->d_configs; D.stream_cfg = b->d_stream_cfg; D.taps = b->d_fa_taps;
+    D.plane = b->d_fa_plane; D.carry = b->d_fa_carry; D.pos = b->d_fa_pos; D.flip = b->fa_flip; D.strict_ran = n_strict > 0;
+    HIPCHK(tlk_feed_adapt((hipStream_t)hip_stream, D));
+    b->fa_flip ^= 1;
+    for (int s = 0; s < b->nstreams; s++)
+        if (adapted(b, s)) b->fa_pos[(size_t)s] = (int32_t)(((long long)b->fa_pos[(size_t)s] + nframes) % tl_fa_cycle(b->fa_ratio[(size_t)s]));
     return TLB_OK;
 }
 
@@ -152,7 +240,7 @@ int tlb_feed_frame_bytes(const tlb_feed_config *cfg)
     return n;
 }
 
-int tlb_feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg)
+static int feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg, bool adapt)
 {
     if (!b || stream < -1 || stream >= b->nstreams) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
@@ -162,7 +250,8 @@ int tlb_feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg)
         HIPCHK(hipDeviceSynchronize());
         return feed_assign(b, s0, s1, -1, tlb_feed_config{0, 0, 0});
     }
-    if (int rc = feed_fits(b, s0, s1, cfg)) return rc;               // every named stream is checked before anything changes
+    if (adapt && feed_fits(b, s0, s1, cfg) == TLB_OK) adapt = false; // a configuration that matches every named stream IS a strict feed
+    if (int rc = adapt ? feed_fits_adapted(b, s0, s1, cfg) : feed_fits(b, s0, s1, cfg)) return rc;       // every named stream is checked before anything changes
     int idx = -1;
     for (size_t i = 0; i < b->h_feed_uniq.size(); i++) if (feed_same(b->h_feed_uniq[i], *cfg)) idx = (int)i;
     TlConfig *c = new TlConfig;
@@ -172,13 +261,39 @@ int tlb_feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg)
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = feed_prepare(b)) return rc;
+    if (adapt) if (int rc = adapt_prepare(b)) return rc;
     if (int rc = feed_reserve(b, b->h_feed_configs.size() + (idx < 0 ? 1 : 0), slot_bytes(*c))) return rc;
     if (idx < 0) {
         idx = (int)b->h_feed_configs.size();
         HIPCHK(hipMemcpy(b->d_feed_configs + idx, c, sizeof(TlConfig), hipMemcpyHostToDevice));
         b->h_feed_configs.push_back(*c); b->h_feed_uniq.push_back(*cfg);
     }
-    return feed_assign(b, s0, s1, idx, *cfg);
+    return feed_assign(b, s0, s1, idx, *cfg, adapt);
+}
+
+int tlb_feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg) { return feed_set(b, stream, cfg, false); }
+int tlb_feed_set_adapted(tlb_batch *b, int stream, const tlb_feed_config *cfg) { return feed_set(b, stream, cfg, true); }
+
+int tlb_feed_adapted(const tlb_batch *b, int stream)
+{
+    if (!b || stream < 0 || stream >= b->nstreams) return -TLB_ERR_ARG;
+    return adapted(b, stream) ? 1 : 0;
+}
+
+int tlb_feed_want_at(long feed_rate, long stream_rate, long tick)
+{
+    const int ratio = adapt_ratio(feed_rate, stream_rate);
+    if (ratio < 0) return -TLB_ERR_SAMPLERATE;
+    if (tick < 0) return -TLB_ERR_ARG;
+    return tl_fa_want((int)(tick % tl_fa_cycle(ratio)), ratio);     // the schedule repeats with the cycle
+}
+
+int tlb_feed_want(const tlb_batch *b, int stream, int ahead)
+{
+    if (!b || stream < 0 || stream >= b->nstreams || ahead < 0 || b->feed_idx.empty() || b->feed_idx[(size_t)stream] < 0) return -TLB_ERR_ARG;
+    if (!adapted(b, stream)) return 1;
+    const int ratio = b->fa_ratio[(size_t)stream];
+    return tl_fa_want((int)(((long long)b->fa_pos[(size_t)stream] + ahead) % tl_fa_cycle(ratio)), ratio);
 }
 
 int tlb_feed_get(const tlb_batch *b, int stream, tlb_feed_config *cfg)

@@ -94,7 +94,20 @@ struct tlb_batch {
     int feed_prev_stride = 0;
     void *d_feed_rep = nullptr;                  // reports of a tlb_feed_device call that asked for none (grow-only)
     size_t feed_rep_cap = 0;
-    TlbMem mem;                                  // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
+    // adapted feeds (tlb_feed_set_adapted; csrc/mp2_feed_adapt.h), allocated by the first one that does not match its stream.  An adapted
+    // stream keeps its record in feed_cfg / feed_idx and its history in d_feed_state / d_feed_prev, but reads -1 in d_feed_cfg: the strict
+    // kernel sees it as a stream without a feed
+    std::vector<int32_t> fa_ratio;               // [nstreams] -1: not adapted, else TL_RS_* of (feed rate, stream rate) (empty until the first adapted feed)
+    std::vector<int32_t> fa_pos;                 // [nstreams] host copy of the tick counter modulo the cycle
+    int n_adapted = 0;
+    int32_t *d_fa_cfg = nullptr, *d_fa_ratio = nullptr;      // [nstreams] feed record (-1: not adapted), TL_RS_*
+    int16_t *d_fa_carry = nullptr;               // [2][nstreams][TL_FA_CARRY * 2]; a call reads copy fa_flip and writes the other
+    int32_t *d_fa_pos = nullptr;                 // [2][nstreams]
+    int16_t *d_fa_taps = nullptr;                // both tables, a copy of the feeds' own (the resampler's state is a separate object)
+    int16_t *d_fa_plane = nullptr;               // [nstreams][fa_plane_frames * 2304] grow-only launch scratch with an owner of its own
+    std::unique_ptr<TlbMem> fa_plane_mem;
+    int fa_plane_frames = 0, fa_flip = 0;
+    TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
 };
@@ -133,6 +146,7 @@ int feed_after_reconfigure(tlb_batch *b, int stream);
 // ... what the tick plane needs of it: is cfg legal and does it fit streams [s0, s1) (nothing changes); the slot a frame of cfg needs;
 // tlb_feed_device with slots of `stride` bytes, at least tlb_feed_stride(b) (a tick object has ONE stride for all its groups)
 int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
+int feed_fits_adapted(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);      // ... for tlb_feed_set_adapted: a legal rate pair, any channel counts
 int feed_slot_bytes(const tlb_feed_config *cfg);
 int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
 // tlb_compare.cpp: the history as the first compare call makes it; the launch itself with a report that may be NULL (every slot skipped:

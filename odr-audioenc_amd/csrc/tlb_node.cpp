@@ -162,9 +162,10 @@ struct tlb_node {
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
     std::vector<long> source;                    // tlb_node_set_source(): the source rate of every stream (0: off), set again on a restarted shard; empty: never set
-    std::vector<tlb_feed_config> feed;           // tlb_node_set_feed(): the feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
+    struct Feed : tlb_feed_config { int adapted; };      // adapted: set through tlb_node_set_feed_adapted, and set again that way
+    std::vector<Feed> feed;           // tlb_node_set_feed(): the feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
-    bool any_feed() const { for (const tlb_feed_config &f : feed) if (f.bitrate) return true; return false; }
+    bool any_feed() const { for (const Feed &f : feed) if (f.bitrate) return true; return false; }
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
@@ -338,9 +339,9 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (int rc = s.tick ? tlb_tick_set_source(s.tick, k, r) : tlb_resample_set_source(s.batch, k, r)) return rc;
     }
     for (int k = 0; k < s.n && !nd->feed.empty(); k++) {             // the caller's feeds, with fresh history
-        const tlb_feed_config &f = nd->feed[(size_t)(s.first + k)];
+        const tlb_node::Feed &f = nd->feed[(size_t)(s.first + k)];
         if (!f.bitrate) continue;
-        if (int rc = s.tick ? tlb_tick_set_feed(s.tick, k, &f) : tlb_feed_set(s.batch, k, &f)) return rc;
+        if (int rc = s.tick ? (f.adapted ? tlb_tick_set_feed_adapted : tlb_tick_set_feed)(s.tick, k, &f) : (f.adapted ? tlb_feed_set_adapted : tlb_feed_set)(s.batch, k, &f)) return rc;
     }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
@@ -656,13 +657,15 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
 }
 // A Layer II feed for one stream or all (cfg = NULL: removed; remembered as bitrate 0), the same way.  Every named stream is checked
 // before a shard is asked.
-int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
+static bool node_rates_adapt(long feed, long enc) { return feed == enc || tl_rs_ratio_of(feed, enc) != TL_RS_OFF; }
+static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, bool adapt)
 {
     if (!nd || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     if (cfg) {
         if (int rc = tlb_feed_check_config(cfg)) return rc;
         for (int i = s0; i < s1; i++) {
+            if (adapt) { if (!node_rates_adapt(cfg->samplerate, nd->cfgs[(size_t)i].samplerate)) return TLB_ERR_SAMPLERATE; continue; }
             if (cfg->samplerate != nd->cfgs[(size_t)i].samplerate) return TLB_ERR_SAMPLERATE;
             if (cfg->channels != (nd->cfgs[(size_t)i].mode == 'm' ? 1 : 2)) return TLB_ERR_MODE;
         }
@@ -671,13 +674,25 @@ int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
             for (long r : nd->source) if (r) return TLB_ERR_ARG;
         }
     }
-    const tlb_feed_config v = cfg ? *cfg : tlb_feed_config{0, 0, 0};
+    tlb_node::Feed v = {};
+    if (cfg) { v.samplerate = cfg->samplerate; v.bitrate = cfg->bitrate; v.channels = cfg->channels; v.adapted = adapt; }
     return nd->set_remembered(stream, nd->feed, cfg != nullptr, v,
-        [](Shard &sh, int k, const tlb_feed_config &f) {
+        [](Shard &sh, int k, const tlb_node::Feed &f) {
             const tlb_feed_config *c = f.bitrate ? &f : nullptr;      // (bitrate 0 is "none": tlb_feed_check_config above lets no caller's cfg through with it)
+            if (f.adapted) return sh.tick ? tlb_tick_set_feed_adapted(sh.tick, k, c) : tlb_feed_set_adapted(sh.batch, k, c);
             return sh.tick ? tlb_tick_set_feed(sh.tick, k, c) : tlb_feed_set(sh.batch, k, c);
         },
         [&](int) { return v; });
+}
+int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg) { return node_set_feed(nd, stream, cfg, false); }
+int tlb_node_set_feed_adapted(tlb_node *nd, int stream, const tlb_feed_config *cfg) { return node_set_feed(nd, stream, cfg, true); }
+// is a feed frame wanted in the stream's slot of its shard's current input set (TICK plane; broken and late shards answer as tlb_node_need does)
+int tlb_node_feed_want(const tlb_node *nd, int stream)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK) return -TLB_ERR_ARG;
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return -rc;
+    return s->tick ? tlb_tick_feed_want(s->tick, k) : -TLB_ERR_HIP;
 }
 // the stream's slot of its shard's feed buffers (tlb_tick_feed / _feed_len of the shard's tick object): NULL for a broken or a late shard, while
 // two ticks are in flight and while no stream of the shard has a feed
@@ -814,8 +829,9 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
     const int rc = nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reconfigure(sh.tick, k, cfg) : tlb_stream_reconfigure(sh.batch, k, cfg); });
     if (!rc) nd->cfgs[(size_t)stream] = *cfg;                        // a restart of the shard re-creates the stream as it is NOW
     if (!rc && !nd->feed.empty()) {                                  // a feed the new rate or channel count no longer fits has been removed
-        tlb_feed_config &f = nd->feed[(size_t)stream];
-        if (f.bitrate && (f.samplerate != cfg->samplerate || f.channels != (cfg->mode == 'm' ? 1 : 2))) f = tlb_feed_config{0, 0, 0};
+        tlb_node::Feed &f = nd->feed[(size_t)stream];
+        const bool fits = f.adapted ? node_rates_adapt(f.samplerate, cfg->samplerate) : f.samplerate == cfg->samplerate && f.channels == (cfg->mode == 'm' ? 1 : 2);
+        if (f.bitrate && !fits) f = tlb_node::Feed{};
     }
     return rc;
 }

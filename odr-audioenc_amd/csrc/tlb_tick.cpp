@@ -380,7 +380,8 @@ static void tick_feed_refresh(tlb_tick *t)
             for (int k = 0; k < 3; k++) for (int i = 0; i < G.n; i++) { tlb_frame_report r = {}; r.status = TLB_DEC_EMPTY; t->h_feed_report[k][G.first + i] = r; }
     }
 }
-int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
+// adapt: through tlb_feed_set_adapted (a legal rate pair and any channel counts instead of the stream's own)
+static int tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg, bool adapt)
 {
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
@@ -389,7 +390,7 @@ int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
     if (cfg) {
         if (t->short_reads || t->resample) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads and sources)
         // every stream is checked before one is changed
-        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return feed_fits(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
+        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return (adapt ? feed_fits_adapted : feed_fits)(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
     }
     HIPCHK(hipSetDevice(t->device));
     const size_t ns = (size_t)t->nstreams;
@@ -421,14 +422,18 @@ int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
     // what the named streams have now: after a device failure half way the groups already changed get it back (fresh history), so that
     // "all or nothing" holds for the feeds themselves; the wider buffers stay
     std::vector<tlb_feed_config> before(ns, tlb_feed_config{0, 0, 0});
-    for (auto &G : t->groups) for (int k = 0; k < G.n; k++) (void)tlb_feed_get(G.b, k, &before[(size_t)(G.first + k)]);
+    std::vector<char> before_adapted(ns, 0);
+    for (auto &G : t->groups) for (int k = 0; k < G.n; k++) {
+        (void)tlb_feed_get(G.b, k, &before[(size_t)(G.first + k)]);
+        before_adapted[(size_t)(G.first + k)] = tlb_feed_adapted(G.b, k) > 0;
+    }
     const int rc = t->blocks.visit(stream, [&](int g, int k) {
-        const int e = tlb_feed_set(t->groups[(size_t)g].b, k, cfg);
+        const int e = (adapt ? tlb_feed_set_adapted : tlb_feed_set)(t->groups[(size_t)g].b, k, cfg);
         if (e) t->blocks.visit_range(s0, s1, [&](int u, int l0, int l1) {      // the named streams of the groups up to and including this one
             const TickGroup &U = t->groups[(size_t)u];
             for (int i = l0; i < l1 && u <= g; i++) {
                 const tlb_feed_config &f = before[(size_t)(U.first + i)];
-                (void)tlb_feed_set(U.b, i, f.bitrate ? &f : nullptr);
+                (void)(before_adapted[(size_t)(U.first + i)] ? tlb_feed_set_adapted : tlb_feed_set)(U.b, i, f.bitrate ? &f : nullptr);
             }
             return 0;
         });
@@ -437,6 +442,14 @@ int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
     tick_feed_refresh(t);
     for (int k = 0; k < 2; k++) memset(t->h_feed_len[k], 0, ns * sizeof(int32_t));
     return rc;
+}
+int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_set_feed(t, stream, cfg, false); }
+int tlb_tick_set_feed_adapted(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_set_feed(t, stream, cfg, true); }
+// is a feed frame wanted in the stream's slot of the input set to fill next (the group's batch advances its position with every submit)
+int tlb_tick_feed_want(const tlb_tick *t, int stream)
+{
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    return G ? tlb_feed_want(G->b, k, 0) : -TLB_ERR_ARG;
 }
 uint8_t *tlb_tick_feed(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed[t->in_set] : nullptr; }
 int32_t *tlb_tick_feed_len(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed_len[t->in_set] : nullptr; }

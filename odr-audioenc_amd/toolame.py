@@ -303,6 +303,15 @@ def _bind(L):
             getattr(L, f).restype = C.c_void_p
             getattr(L, f).argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_feed_stride.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_feed_set_adapted"):       # adapted feeds: another rate or channel count than the stream's
+        L.tlb_feed_set_adapted.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_feed_adapted.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_feed_want.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.tlb_feed_want_at.argtypes = [C.c_long, C.c_long, C.c_long]
+        L.tlb_tick_set_feed_adapted.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_tick_feed_want.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_set_feed_adapted.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_node_feed_want.argtypes = [C.c_void_p, C.c_int]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -340,6 +349,14 @@ def feed_check_config(cfg):
     """tlb_feed_check_config: 0, or the library's code for an illegal sample rate (1), channel count (2) or bitrate (4); host arithmetic, no GPU"""
     c = _c_feed(cfg)
     return load_library().tlb_feed_check_config(C.byref(c))
+
+
+def feed_want_at(feed_rate, rate, tick):
+    """tlb_feed_want_at: 1 / 0, is a feed frame of `feed_rate` wanted on tick `tick` (from the reset) of a stream at `rate`; host arithmetic, no GPU"""
+    n = load_library().tlb_feed_want_at(feed_rate, rate, tick)
+    if n < 0:
+        raise ToolameError(-n, "tlb_feed_want_at")
+    return n
 
 
 def feed_frame_bytes(cfg):
@@ -391,6 +408,7 @@ FRAME_REPORT_DTYPE = np.dtype([("status", np.uint32), ("crc_stored", np.uint16),
 FRAME_FIELDS_DTYPE = np.dtype([("bit_alloc", np.uint8, (2, 32)), ("scfsi", np.uint8, (2, 32)), ("scalar", np.uint8, (2, 3, 32)),
                                ("subband", np.uint16, (2, 3, 12, 32))])
 DEC_EMPTY, DEC_BAD_SYNC, DEC_HEADER_MISMATCH, DEC_BAD_CRC16, DEC_BAD_SCFCRC, DEC_SCFCRC_UNCHECKED, DEC_BAD_ALLOC, DEC_OVERRUN = (1 << i for i in range(8))
+DEC_UNWANTED = 0x100                             # adapted feeds: the slot held bytes on a tick whose slot is not read
 DEC_BAD_MASK = DEC_BAD_SYNC | DEC_HEADER_MISMATCH | DEC_BAD_CRC16 | DEC_BAD_SCFCRC | DEC_BAD_ALLOC | DEC_OVERRUN
 # tlb_monitor_record (include/toolame_batch.h): the confidence monitor's fold, one per stream
 MONITOR_DTYPE = np.dtype([("frames", np.uint32), ("bad_frames", np.uint32), ("bad_run", np.uint32), ("flags_seen", np.uint32),
@@ -498,12 +516,20 @@ class Tick:
         return n
 
     # -- Layer II feeds (tlb_tick_set_feed): legal while no tick is in flight; exclude short reads and sources --
-    def set_feed(self, stream, cfg):
-        """stream = -1: every stream; cfg = None removes the feed.  `feed`, `feed_len` must be fetched again afterwards."""
+    def set_feed(self, stream, cfg, adapt=False):
+        """stream = -1: every stream; cfg = None removes the feed.  `feed`, `feed_len` must be fetched again afterwards.
+        adapt: tlb_tick_set_feed_adapted -- the feed may have another (legal) rate or channel count than the stream; see feed_want."""
         c = _c_feed(cfg) if cfg is not None else None
-        rc = self.L.tlb_tick_set_feed(self.h, stream, C.byref(c) if c is not None else None)
+        rc = (self.L.tlb_tick_set_feed_adapted if adapt else self.L.tlb_tick_set_feed)(self.h, stream, C.byref(c) if c is not None else None)
         if rc:
             raise ToolameError(rc, "tlb_tick_set_feed")
+
+    def feed_want(self, s):
+        """1 / 0: is a feed frame wanted in stream s's slot of the input set to fill next (always 1 for a strict feed)"""
+        n = self.L.tlb_tick_feed_want(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_tick_feed_want")
+        return n
 
     @property
     def feed_stride(self):
@@ -830,10 +856,11 @@ class Batch:
         return rep, fl, pcm
 
     # -- Layer II feeds: a stream's source arrives as MP2 frames and is decoded into the ingest's input (tlb_feed_*) --
-    def set_feed(self, stream, cfg):
-        """stream = -1: every stream; cfg = None removes the feed.  The feed's rate and channel count must be the stream's."""
+    def set_feed(self, stream, cfg, adapt=False):
+        """stream = -1: every stream; cfg = None removes the feed.  The feed's rate and channel count must be the stream's, unless
+        adapt: tlb_feed_set_adapted -- a legal rate pair (equal, 44.1 -> 48, 22.05 -> 24, 32 -> 48, 16 -> 24 kHz) and 1 or 2 channels on either side."""
         c = _c_feed(cfg) if cfg is not None else None
-        rc = self.L.tlb_feed_set(self.h, stream, C.byref(c) if c is not None else None)
+        rc = (self.L.tlb_feed_set_adapted if adapt else self.L.tlb_feed_set)(self.h, stream, C.byref(c) if c is not None else None)
         if rc:
             raise ToolameError(rc, "tlb_feed_set")
 
@@ -843,6 +870,19 @@ class Batch:
         if n < 0:
             raise ToolameError(-n, "tlb_feed_get")
         return FeedConfig(c.samplerate, c.bitrate, c.channels) if n else None
+
+    def feed_adapted(self, s):
+        n = self.L.tlb_feed_adapted(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_feed_adapted")
+        return bool(n)
+
+    def feed_want(self, s, ahead=0):
+        """1 / 0: is a feed frame wanted on stream s's (ahead)-th next tick (always 1 for a strict feed); host arithmetic"""
+        n = self.L.tlb_feed_want(self.h, s, ahead)
+        if n < 0:
+            raise ToolameError(-n, "tlb_feed_want")
+        return n
 
     @property
     def feed_stride(self):
@@ -1333,10 +1373,17 @@ class Node:
         return n
 
     # Layer II feeds (Tick.set_feed, per stream with node-wide indices)
-    def set_feed(self, stream, cfg):
-        """stream = -1: every stream; cfg = None removes the feed; between steps only"""
+    def set_feed(self, stream, cfg, adapt=False):
+        """stream = -1: every stream; cfg = None removes the feed; between steps only.  adapt: tlb_node_set_feed_adapted"""
         c = _c_feed(cfg) if cfg is not None else None
-        self._rc(self.L.tlb_node_set_feed(self.h, stream, C.byref(c) if c is not None else None), "tlb_node_set_feed")
+        self._rc((self.L.tlb_node_set_feed_adapted if adapt else self.L.tlb_node_set_feed)(self.h, stream, C.byref(c) if c is not None else None), "tlb_node_set_feed")
+
+    def feed_want(self, s):
+        """1 / 0: is a feed frame wanted in the stream's slot of its shard's current input set (TICK plane)"""
+        n = self.L.tlb_node_feed_want(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_node_feed_want")
+        return n
 
     def feed(self, s):
         """the stream's slot (uint8 view) in its shard's current input set; None when its shard has no feed, while two ticks are in flight and
