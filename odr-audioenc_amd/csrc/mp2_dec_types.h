@@ -78,3 +78,5 @@ struct TlFeedLaunch {
     uint8_t *prev;                    // [nstreams][prev_stride] the last slot of the launch before
     int32_t nstreams, nframes, stride, prev_stride;       // both multiples of 4, each at least the longest frame of any feed of the batch
 };
+// the slot a feed of record c needs: its longest frame (with the padding slot where the rate has one), rounded up to 4
+static inline int tl_feed_slot_bytes(const TlConfig &c) { return (c.frame_bytes + (c.pad_frac != 0 ? 1 : 0) + 3) & ~3; }

@@ -7,14 +7,14 @@
 // Everything repeats after tl_fa_cycle ticks (160 ticks = 147 feed frames for 160/147; 3 ticks = 2 frames for 3/2), so a stream's position
 // is its tick counter modulo the cycle and all that the kernels compute from it are DIFFERENCES of S and K, which the modulus leaves alone.
 // Three kernels per call, in this order on one stream (toolame_feed_adapt.hip):
-//   decode    one wavefront per (tick, stream): tl_feed_unit's body under the feed's configuration for a wanted slot of an adapted
+//   decode    one wavefront per (tick, stream): the feed decode itself (mp2_feed.h: tl_feed_decode) for a wanted slot of an adapted
 //             stream, into row K(p) - 1 - K(p0 - 1) of the stream's part of the call's source plane (p0: the position at the call's start,
-//             p = p0 + f); the history is the previous WANTED slot: tick f - 1 or f - 2 of the call, or the carried bytes
+//             p = p0 + f); the slot before is the previous WANTED one: tick f - 1 or f - 2 of the call, or the carried bytes
 //   resample  one workgroup of TL_RS_WAVES waves per (tick, stream): the ratio's table and the source frames [S(p) - 31, S(p + 1)) into LDS
 //             -- from the stream's carried head for frames before the call's first decoded one, from the plane for the rest, the stereo to
 //             mono map applied on the way --, one barrier, tl_resample_wave unchanged
 //   carry     one wavefront per stream: the last TL_FA_CARRY source frames before the next call's first decoded one (into the OTHER copy:
-//             a call with one tick keeps most of what it was given), the new position, the last wanted slot's bytes, length and status
+//             a call with one tick keeps most of what it was given), the new position, and tl_feed_keep of the last wanted slot
 // TL_FA_CARRY: before any tick at most 1145 decoded frames are unconsumed and a tick reads 31 frames of history: 1176, rounded to 1184 so
 // that a one-channel stream's copy is a multiple of 16 bytes.  Lane-SPMD source for gfx950 and, with TL_EMULATE, lane loops; include after
 // mp2_feed.h with TL_FA_BODY defined (toolame_feed_adapt.hip and the emulation: the one kernel unit and the one test that want the body; tl_kernels.h
@@ -27,6 +27,8 @@
 #define TL_DEC_UNWANTED 0x100u        // an adapted feed's slot held bytes on a tick whose slot is not read (TLB_DEC_UNWANTED); not in TL_DEC_BAD_MASK
 #define TL_FA_CARRY 1184
 #define tl_fa_cycle(ratio) ((ratio) == TL_RS_160_147 ? 160 : (ratio) == TL_RS_3_2 ? 3 : 1)
+// the ratio of a legal (feed rate, stream rate) pair: TL_RS_OFF for equal rates; -1: none
+static inline int tl_fa_ratio_of(long feed, long enc) { return feed == enc ? TL_RS_OFF : tl_rs_ratio_of(feed, enc) != TL_RS_OFF ? tl_rs_ratio_of(feed, enc) : -1; }
 
 // ratio: TL_RS_160_147, TL_RS_3_2 or TL_RS_OFF (here: 1/1).  constexpr: host and device.  32-bit arithmetic: f is a position in the
 // cycle plus a tick of one call, and a call with adapted feeds has at most TL_FA_MAX_FRAMES ticks ((1152 f - 1) 147 < 2^31 up to f = 12 680).
@@ -59,51 +61,28 @@ struct TlFeedAdaptLaunch {
 TL_FN const int16_t *tl_fa_carry_of(const TlFeedAdaptLaunch &A, int copy, int s) { return A.carry + ((size_t)copy * (size_t)A.F.nstreams + (size_t)s) * (TL_FA_CARRY * 2); }
 TL_FN const int16_t *tl_fa_plane_of(const TlFeedAdaptLaunch &A, int s) { return A.plane + (size_t)s * (size_t)A.F.nframes * 2304; }
 
-// ---- decode: slot f of stream s -> its report and, for a wanted slot, 1152 source frames in the stream's plane ----
+// source frame `g` of a stream, counted from the call's first decoded frame: below 0 in the carried head `cin`, else in the plane `pl`
+TL_FN const int16_t *tl_fa_frame(const int16_t *TL_RESTRICT cin, const int16_t *TL_RESTRICT pl, int g, int fch) { return g < 0 ? cin + (TL_FA_CARRY + g) * fch : pl + g * fch; }
+
+// ---- decode: slot f of stream s -> its report and, for a wanted slot, 1152 source frames in the stream's plane.  What is here is the
+// schedule; the decode is tl_feed_decode. ----
 TL_FN void tl_fa_decode_unit(TlSynthLds &w, const TlFeedAdaptLaunch &A, int s, int f, const double *TL_RESTRICT dwin)
 {
     const TlFeedLaunch &F = A.F;
     const size_t slot = (size_t)f * F.nstreams + s;
     TlFrameReport *rep = &F.report[slot];
     const int ci = F.feed_cfg[s];
-    if (ci < 0) { if (!A.strict_ran) tl_feed_report(rep, TL_DEC_EMPTY, nullptr); return; }
+    if (ci < 0) { if (!A.strict_ran) tl_dec_report(rep, TL_DEC_EMPTY, nullptr); return; }
     const int ratio = TL_UNI_I(A.ratio[s]);                          // (uniform over the wave, and kept in scalar registers)
     const int p0 = TL_UNI_I(A.pos[(size_t)A.flip * (size_t)F.nstreams + (size_t)s]), p = p0 + f;
-    int len = F.len[slot];
-    len = len < F.stride ? len : F.stride;                           // (no read leaves the slot)
-    if (!tl_fa_want(p, ratio)) { tl_feed_report(rep, len > 0 ? TL_DEC_EMPTY | TL_DEC_UNWANTED : TL_DEC_EMPTY, nullptr); return; }
+    if (!tl_fa_want(p, ratio)) { tl_dec_report(rep, F.len[slot] > 0 ? TL_DEC_EMPTY | TL_DEC_UNWANTED : TL_DEC_EMPTY, nullptr); return; }
     const TlConfig *C = &F.configs[ci];
-    const TlBlockShared *B = &F.tables->shared;
-    const TlPackTables *K = &F.tables->pack;
-    const int nch = C->nch;
     const int row = TL_UNI_I(tl_fa_K(p, ratio) - 1 - tl_fa_K(p0 - 1, ratio));    // 0 .. f
-    int16_t *out = (int16_t *)tl_fa_plane_of(A, s) + TL_UNI_I(row * 1152 * nch);           // (32 bits: at most TL_FA_MAX_FRAMES rows)
-    if (len <= 0) { tl_feed_report(rep, TL_DEC_EMPTY, nullptr); tl_synth_zero(out, 1152 * nch); return; }
-
-    TlDecSide sdp, sd;
-    TlDecCells xp, xc;
-    const uint32_t st = tl_feed_parse(w.d[1], B, K, C, F.frames + slot * F.stride, len, sd, xc);
-    tl_feed_report(rep, st, &sd);
-    if (st & TL_DEC_BAD_MASK) { tl_synth_zero(out, 1152 * nch); return; }
-
-    bool hist;
-    {   // the WANTED slot before: never more than one unwanted tick lies between two wanted ones
-        int pf = f - 1;
-        if (pf >= 0 && !tl_fa_want(p - 1, ratio)) pf--;
-        pf = TL_UNI_I(pf);
-        const uint8_t *psrc; int plen, pmax;
-        if (pf >= 0) {
-            const size_t ps = (size_t)pf * F.nstreams + s;
-            psrc = F.frames + ps * F.stride; plen = F.len[ps]; pmax = F.stride; hist = true;
-        } else {
-            psrc = F.prev + (size_t)s * F.prev_stride; plen = F.state[s].prev_len; pmax = F.prev_stride;
-            hist = !(F.state[s].prev_status & (TL_DEC_BAD_MASK | TL_DEC_EMPTY));
-        }
-        plen = plen < pmax ? plen : pmax;
-        hist = hist && plen > 0;
-        if (hist) hist = !(tl_feed_parse(w.d[0], B, K, C, psrc, plen, sdp, xp) & TL_DEC_BAD_MASK);
-    }
-    tl_synth_frame(w, B, K, F.synth, nch, hist, sdp, xp, sd, xc, out, 1, nch, dwin);
+    int16_t *out = (int16_t *)tl_fa_plane_of(A, s) + TL_UNI_I(row * 1152 * C->nch);        // (32 bits: at most TL_FA_MAX_FRAMES rows)
+    int pf = f - 1;                                                  // the WANTED slot before: never more than one unwanted tick lies between two wanted ones
+    if (pf >= 0 && !tl_fa_want(p - 1, ratio)) pf--;
+    pf = TL_UNI_I(pf);                                               // (-1 = TL_FEED_CARRIED: the call has no wanted slot before this one)
+    tl_feed_decode(w, F, C, s, f, pf, out, dwin);
 }
 
 // ---- resample: what is uniform over the workgroup of slot (f, s) ----
@@ -130,7 +109,7 @@ TL_FN TlFaSlot tl_fa_slot(const TlFeedAdaptLaunch &A, int s, int f)
 // source frame `g` (counted from the call's first decoded frame) under the channel map: L | R << 16 for two channels to two, else one sample
 TL_FN uint32_t tl_fa_source(const int16_t *TL_RESTRICT cin, const int16_t *TL_RESTRICT pl, int g, int fch, int sch)
 {
-    const int16_t *p = g < 0 ? cin + (TL_FA_CARRY + g) * fch : pl + g * fch;
+    const int16_t *p = tl_fa_frame(cin, pl, g, fch);
     if (fch == 1) return (uint32_t)(uint16_t)p[0];
     const uint32_t u = *(const uint32_t *)p;
     if (sch == 2) return u;
@@ -197,25 +176,13 @@ TL_FN void tl_fa_carry(const TlFeedAdaptLaunch &A, int s)
     int16_t *cout = (int16_t *)tl_fa_carry_of(A, A.flip ^ 1, s);
     int lf = F.nframes - 1;                                          // the call's last wanted slot; -1: it had none (one unwanted tick)
     if (!tl_fa_want(p0 + lf, ratio)) lf--;
-    const size_t slot = (size_t)(lf < 0 ? 0 : lf) * F.nstreams + s;
-    const int keep = F.stride < F.prev_stride ? F.stride : F.prev_stride;
-    int len = F.len[slot];
-    len = len < 0 ? 0 : len < keep ? len : keep;
-    const uint32_t st = F.report[slot].status;
-    const uint32_t *src = (const uint32_t *)(F.frames + slot * F.stride);
-    uint32_t *dst = (uint32_t *)(F.prev + (size_t)s * F.prev_stride);
-    TlDecStream *ds = &F.state[s];
+    if (lf >= 0) tl_feed_keep(F, s, (size_t)lf * F.nstreams + s);
     TL_LANES_BEGIN
     if (ratio != TL_RS_OFF)                                          // (1/1 reads nothing before its own tick)
         for (int j = lane; j < TL_FA_CARRY; j += 64) {
-            const int g = first + j;
-            const int16_t *p = g < 0 ? cin + (TL_FA_CARRY + g) * fch : pl + g * fch;
+            const int16_t *p = tl_fa_frame(cin, pl, first + j, fch);
             if (fch == 2) ((uint32_t *)cout)[j] = *(const uint32_t *)p; else cout[j] = p[0];
         }
-    if (lf >= 0) {
-        for (int i = lane; i < (keep >> 2); i += 64) dst[i] = src[i];
-        if (lane == 0) { ds->prev_len = len; ds->prev_status = st; }
-    }
     if (lane == 0) A.pos[(size_t)(A.flip ^ 1) * (size_t)F.nstreams + (size_t)s] = (p0 + F.nframes) % tl_fa_cycle(ratio);
     TL_LANES_END
 }

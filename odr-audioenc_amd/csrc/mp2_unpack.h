@@ -285,6 +285,19 @@ TL_FN bool tl_dec_tail(const TlDecLaunch &A, const TlConfig *TL_RESTRICT C, int 
     return true;
 }
 
+// a slot's report, by lane 0: the status word and what the frame's side information says (sd = NULL: an empty slot, every field 0)
+TL_FN void tl_dec_report(TlFrameReport *rep, uint32_t st, const TlDecSide *sd)
+{
+    TL_LANES_BEGIN
+    if (lane == 0) {
+        rep->status = st;
+        rep->crc_stored = sd ? (uint16_t)sd->crc_stored : 0; rep->crc_computed = sd ? (uint16_t)sd->crc_computed : 0;
+        rep->mode = sd ? (uint8_t)sd->mode : 0; rep->mode_ext = sd ? (uint8_t)sd->mode_ext : 0;
+        rep->audio_bits = sd ? (uint16_t)(sd->audio_bits < 65535 ? sd->audio_bits : 65535) : 0;
+    }
+    TL_LANES_END
+}
+
 // ---- the unit of stage A: slot f of stream s -> its report and, when asked for, its fields.  Returns the status word. ----
 TL_FN uint32_t tl_unpack_unit(TlDecLds &w, const TlDecLaunch &A, int s, int f)
 {
@@ -298,6 +311,8 @@ TL_FN uint32_t tl_unpack_unit(TlDecLds &w, const TlDecLaunch &A, int s, int f)
     int len = A.len ? A.len[slot] : A.out_stride;
     len = len < A.out_stride ? len : A.out_stride;
     if (len <= 0) {
+        // this one report stays inline: through tl_dec_report(rep, TL_DEC_EMPTY, nullptr) its twelve constant bytes are stored as dwordx2 + dword
+        // instead of one dwordx3, and the decoder's kernels (the monitor's per-tick path) are kept instruction for instruction as they were
         TL_LANES_BEGIN
         if (lane == 0) { rep->status = TL_DEC_EMPTY; rep->crc_stored = rep->crc_computed = 0; rep->mode = rep->mode_ext = 0; rep->audio_bits = 0; }
         if (fl) for (int i = lane; i < (int)(sizeof(TlFrameFields) / 4); i += 64) ((uint32_t *)fl)[i] = 0;
@@ -316,12 +331,7 @@ TL_FN uint32_t tl_unpack_unit(TlDecLds &w, const TlDecLaunch &A, int s, int f)
         else if (C->dab_ext > 2 ? (tail[0] != sd.scfcrc[3] || tail[1] != sd.scfcrc[2] || tail[2] != sd.scfcrc[1] || tail[3] != sd.scfcrc[0])
                                 : (tail[0] != sd.scfcrc[1] || tail[1] != sd.scfcrc[0])) st |= TL_DEC_BAD_SCFCRC;
     }
-    TL_LANES_BEGIN
-    if (lane == 0) {
-        rep->status = st; rep->crc_stored = (uint16_t)sd.crc_stored; rep->crc_computed = (uint16_t)sd.crc_computed;
-        rep->mode = (uint8_t)sd.mode; rep->mode_ext = (uint8_t)sd.mode_ext; rep->audio_bits = (uint16_t)(sd.audio_bits < 65535 ? sd.audio_bits : 65535);
-    }
-    TL_LANES_END
+    tl_dec_report(rep, st, &sd);
     if (fl) {
         TL_LANES_BEGIN
         const int c = lane & 1, sb = lane >> 1;

@@ -1,4 +1,5 @@
-// tl_kernel_util.h -- what the kernels' translation units (toolame_hip.hip, toolame_psy2.hip) share beside mp2_wave.h.
+// tl_kernel_util.h -- what the kernels' translation units share beside mp2_wave.h: the work list of the persistent encode kernels
+// (toolame_hip.hip, toolame_psy2.hip) and the prologue of the wave-per-unit kernels (toolame_dec.hip, toolame_feed.hip, toolame_feed_adapt.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,3 +28,22 @@ static __device__ __forceinline__ int tl_next_unit(int32_t *counter)
                  : "=&v"(u), "=&s"(saved) : "v"(0), "v"(1), "s"(counter) : "memory");
     return __builtin_amdgcn_readfirstlane(u);
 }
+
+// ---- kernels of one wavefront per unit, WAVES units per workgroup ----
+// this wave's index in the launch, wave-uniform (a stream index for the carry kernels)
+template <int WAVES, class T = int> static __device__ __forceinline__ T tl_wave_index()
+{
+    return (T)blockIdx.x * WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+// ... as a unit of a launch of nframes x nstreams slots: slot f = u / nstreams of stream s = u % nstreams; false past the end
+template <int WAVES> static __device__ __forceinline__ bool tl_wave_unit(int nstreams, int nframes, int &s, int &f)
+{
+    const long long u = tl_wave_index<WAVES, long long>();
+    if (u >= (long long)nstreams * nframes) return false;
+    f = (int)(u / nstreams); s = (int)(u % nstreams);
+    return true;
+}
+// the synthesis window (TlSynthTables::d) into the workgroup's `dwin[512]` in LDS, and the barrier behind it: every wave of the WAVES comes
+// here before it may leave.  A macro: the copy is compiled in the kernel's own body, where `dwin` is the LDS array and not a pointer to it.
+#define TL_STAGE_DWIN(WAVES, dwin, synth) \
+    do { for (int i = (int)threadIdx.x; i < 512; i += 64 * (WAVES)) (dwin)[i] = (synth)->d[i]; __syncthreads(); } while (0)

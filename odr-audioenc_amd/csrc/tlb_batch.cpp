@@ -30,7 +30,6 @@ void tlb_destroy(tlb_batch *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->d_configs) (void)hipFree(b->d_configs);
-    if (b->d_feed_rep) (void)hipFree(b->d_feed_rep);
     for (int k = 0; k < 12; k++) if (b->stage[k]) (void)hipFree(b->stage[k]);
     for (int i = 0; i < TLB_HOST_CHUNKS; i++) { if (b->ev_in[i]) (void)hipEventDestroy(b->ev_in[i]); if (b->ev_run[i]) (void)hipEventDestroy(b->ev_run[i]); }
     if (b->s_in) (void)hipStreamDestroy(b->s_in);

@@ -6,8 +6,6 @@
 #include "tlb_internal.h"
 
 static_assert(TLB_DEC_UNWANTED == TL_DEC_UNWANTED && !(TL_DEC_UNWANTED & TL_DEC_BAD_MASK), "status flags");
-// the ratio of a legal (feed rate, stream rate) pair: TL_RS_OFF for equal rates, -1: none
-static int adapt_ratio(long feed, long enc) { return feed == enc ? TL_RS_OFF : tl_rs_ratio_of(feed, enc) != TL_RS_OFF ? tl_rs_ratio_of(feed, enc) : -1; }
 static long enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
 static bool adapted(const tlb_batch *b, int s) { return !b->fa_ratio.empty() && b->fa_ratio[(size_t)s] >= 0; }
 
@@ -22,7 +20,6 @@ static int feed_build(TlConfig *c, const tlb_feed_config *cfg)
     return tl_build_config(c, cfg->samplerate, feed_mode(cfg->channels), cfg->bitrate, 1, 0);
 }
 static bool feed_same(const tlb_feed_config &a, const tlb_feed_config &b) { return a.samplerate == b.samplerate && a.bitrate == b.bitrate && a.channels == b.channels; }
-static int slot_bytes(const TlConfig &c) { return (c.frame_bytes + (c.pad_frac != 0 ? 1 : 0) + 3) & ~3; }
 
 int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 {
@@ -38,14 +35,14 @@ int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 int feed_fits_adapted(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 {
     if (int rc = tlb_feed_check_config(cfg)) return rc;
-    for (int s = s0; s < s1; s++) if (adapt_ratio(cfg->samplerate, enc_rate(b, s)) < 0) return TLB_ERR_SAMPLERATE;
+    for (int s = s0; s < s1; s++) if (tl_fa_ratio_of(cfg->samplerate, enc_rate(b, s)) < 0) return TLB_ERR_SAMPLERATE;
     return TLB_OK;
 }
 
 int feed_slot_bytes(const tlb_feed_config *cfg)
 {
     TlConfig *c = new TlConfig;
-    const int n = feed_build(c, cfg) ? 0 : slot_bytes(*c);
+    const int n = feed_build(c, cfg) ? 0 : tl_feed_slot_bytes(*c);
     delete c;
     return n;
 }
@@ -99,15 +96,11 @@ static int adapt_prepare(tlb_batch *b)
 {
     if (b->d_fa_cfg) return TLB_OK;
     const size_t n = (size_t)b->nstreams;
-    int L, M, T;
-    const int16_t *t160 = tlb_resample_taps(44100, 48000, &L, &M, &T), *t3 = tlb_resample_taps(32000, 48000, &L, &M, &T);
     TlbMem m;
     int32_t *fc = m.scratch<int32_t>(n), *ra = m.dev<int32_t>(n), *po = m.dev<int32_t>(2 * n);
-    int16_t *ca = m.dev<int16_t>(2 * n * TL_FA_CARRY * 2), *tp = m.scratch<int16_t>((160 + 3) * TL_RS_TAPS);
+    int16_t *ca = m.dev<int16_t>(2 * n * TL_FA_CARRY * 2), *tp = resample_taps_upload(m);
     std::vector<int32_t> none(n, -1);
     m.upload(fc, none.data(), sizeof(int32_t) * n);
-    m.upload(tp, t160, sizeof(int16_t) * 160 * TL_RS_TAPS);
-    m.upload(tp + 160 * TL_RS_TAPS, t3, sizeof(int16_t) * 3 * TL_RS_TAPS);
     if (m.failed()) return TLB_ERR_HIP;
     if (int rc = adapt_plane_reserve(b, 1)) return rc;               // (settles; a plane without the rest is scratch nobody reads)
     m.commit(b->mem);
@@ -151,7 +144,7 @@ static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_con
     HIPCHK(hipMemcpy(b->d_feed_cfg + s0, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
     if (b->d_fa_cfg) {
         std::vector<int32_t> a((size_t)(s1 - s0), adapt ? idx : -1), r((size_t)(s1 - s0), 0);
-        for (int s = s0; s < s1 && adapt; s++) r[(size_t)(s - s0)] = adapt_ratio(cfg.samplerate, enc_rate(b, s));
+        for (int s = s0; s < s1 && adapt; s++) r[(size_t)(s - s0)] = tl_fa_ratio_of(cfg.samplerate, enc_rate(b, s));
         HIPCHK(hipMemcpy(b->d_fa_cfg + s0, a.data(), sizeof(int32_t) * a.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b->d_fa_ratio + s0, r.data(), sizeof(int32_t) * r.size(), hipMemcpyHostToDevice));
         for (int s = s0; s < s1; s++) b->fa_ratio[(size_t)s] = adapt && idx >= 0 ? r[(size_t)(s - s0)] : -1;
@@ -168,7 +161,7 @@ int feed_after_reconfigure(tlb_batch *b, int stream)
     const tlb_stream_config &sc = b->h_uniq[(size_t)b->h_stream_cfg[(size_t)stream]];
     const tlb_feed_config fc = b->feed_cfg[(size_t)stream];
     if (adapted(b, stream)) {                                        // kept while the rates still form a legal pair, whatever the channel counts; the caller clears the state
-        if (adapt_ratio(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed_idx[(size_t)stream], fc, true);
+        if (tl_fa_ratio_of(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed_idx[(size_t)stream], fc, true);
     } else if (fc.samplerate == sc.samplerate && fc.channels == (sc.mode == 'm' ? 1 : 2)) return TLB_OK;
     return feed_assign(b, stream, stream + 1, -1, tlb_feed_config{0, 0, 0});
 }
@@ -182,14 +175,16 @@ int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int
     if (b->broken) return TLB_ERR_HIP;
     HIPCHK(hipSetDevice(b->device));
     if (!d_report) {                             // the history pass reads the last slot's status: a report buffer of the batch's own, grow-only
-        const size_t bytes = (size_t)nframes * (size_t)b->nstreams * sizeof(tlb_frame_report);
-        if (b->feed_rep_cap < bytes) {
+        const size_t slots = (size_t)nframes * (size_t)b->nstreams;
+        if (b->feed_rep_slots < slots) {
             HIPCHK(hipDeviceSynchronize());      // (a launch before may still write the one it replaces)
-            if (b->d_feed_rep) { (void)hipFree(b->d_feed_rep); b->d_feed_rep = nullptr; b->feed_rep_cap = 0; }
-            HIPCHK(hipMalloc(&b->d_feed_rep, bytes));
-            b->feed_rep_cap = bytes;
+            std::unique_ptr<TlbMem> m(new TlbMem);
+            tlb_frame_report *nr = m->scratch<tlb_frame_report>(slots);
+            if (m->failed()) return TLB_ERR_HIP;
+            b->feed_rep_mem.swap(m);
+            b->d_feed_rep = nr; b->feed_rep_slots = slots;
         }
-        d_report = (tlb_frame_report *)b->d_feed_rep;
+        d_report = b->d_feed_rep;
     }
     int n_strict = 0;
     for (int s = 0; s < b->nstreams; s++) n_strict += b->feed_idx[(size_t)s] >= 0 && !adapted(b, s);
@@ -262,7 +257,7 @@ static int feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg, bool a
     HIPCHK(hipDeviceSynchronize());
     if (int rc = feed_prepare(b)) return rc;
     if (adapt) if (int rc = adapt_prepare(b)) return rc;
-    if (int rc = feed_reserve(b, b->h_feed_configs.size() + (idx < 0 ? 1 : 0), slot_bytes(*c))) return rc;
+    if (int rc = feed_reserve(b, b->h_feed_configs.size() + (idx < 0 ? 1 : 0), tl_feed_slot_bytes(*c))) return rc;
     if (idx < 0) {
         idx = (int)b->h_feed_configs.size();
         HIPCHK(hipMemcpy(b->d_feed_configs + idx, c, sizeof(TlConfig), hipMemcpyHostToDevice));
@@ -282,7 +277,7 @@ int tlb_feed_adapted(const tlb_batch *b, int stream)
 
 int tlb_feed_want_at(long feed_rate, long stream_rate, long tick)
 {
-    const int ratio = adapt_ratio(feed_rate, stream_rate);
+    const int ratio = tl_fa_ratio_of(feed_rate, stream_rate);
     if (ratio < 0) return -TLB_ERR_SAMPLERATE;
     if (tick < 0) return -TLB_ERR_ARG;
     return tl_fa_want((int)(tick % tl_fa_cycle(ratio)), ratio);     // the schedule repeats with the cycle
@@ -307,7 +302,7 @@ int tlb_feed_get(const tlb_batch *b, int stream, tlb_feed_config *cfg)
 int tlb_feed_stride(const tlb_batch *b)
 {
     int stride = 0;
-    if (b) for (int idx : b->feed_idx) if (idx >= 0 && slot_bytes(b->h_feed_configs[(size_t)idx]) > stride) stride = slot_bytes(b->h_feed_configs[(size_t)idx]);
+    if (b) for (int idx : b->feed_idx) if (idx >= 0 && tl_feed_slot_bytes(b->h_feed_configs[(size_t)idx]) > stride) stride = tl_feed_slot_bytes(b->h_feed_configs[(size_t)idx]);
     return stride;
 }
 

@@ -92,8 +92,9 @@ struct tlb_batch {
     TlDecStream *d_feed_state = nullptr;         // [nstreams] the feed history, separate from the decoder's
     uint8_t *d_feed_prev = nullptr;              // [nstreams][feed_prev_stride] the last slot of the call before; replaced when a longer feed frame arrives
     int feed_prev_stride = 0;
-    void *d_feed_rep = nullptr;                  // reports of a tlb_feed_device call that asked for none (grow-only)
-    size_t feed_rep_cap = 0;
+    tlb_frame_report *d_feed_rep = nullptr;      // reports of a tlb_feed_device call that asked for none: grow-only launch scratch with an owner of its own
+    std::unique_ptr<TlbMem> feed_rep_mem;
+    size_t feed_rep_slots = 0;
     // adapted feeds (tlb_feed_set_adapted; csrc/mp2_feed_adapt.h), allocated by the first one that does not match its stream.  An adapted
     // stream keeps its record in feed_cfg / feed_idx and its history in d_feed_state / d_feed_prev, but reads -1 in d_feed_cfg: the strict
     // kernel sees it as a stream without a feed
@@ -157,6 +158,7 @@ int compare_launch(tlb_batch *b, const int16_t *d_in_pcm, const int16_t *d_dec_p
 // tlb_resample.cpp: the resampler's tables and state as the first real source makes them (waits for the device once); the resampler state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); the legality of a
 // stream's source with a new encoder rate (tlb_stream_reconfigure)
 int resample_prepare(tlb_batch *b);
+int16_t *resample_taps_upload(TlbMem &m);        // both tables in one buffer of m: [160][32], then [3][32] (the resampler's copy, and the adapted feeds')
 int resample_clear_streams(tlb_batch *b, int s0, int n);
 bool resample_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -35,6 +35,14 @@ int resample_clear_streams(tlb_batch *b, int s0, int n)
     return TLB_OK;
 }
 
+int16_t *resample_taps_upload(TlbMem &m)
+{
+    int16_t *tp = m.scratch<int16_t>((160 + 3) * TL_RS_TAPS);
+    m.upload(tp, tl_resample_taps_160_147, sizeof tl_resample_taps_160_147);
+    m.upload(tp + 160 * TL_RS_TAPS, tl_resample_taps_3_2, sizeof tl_resample_taps_3_2);
+    return tp;
+}
+
 int resample_prepare(tlb_batch *b)
 {
     if (b->d_rs_state) return TLB_OK;
@@ -42,9 +50,7 @@ int resample_prepare(tlb_batch *b)
     TlbMem m;
     uint32_t *st = m.dev<uint32_t>(2 * TL_RS_STATE_WORDS * ns);
     int32_t *ra = m.dev<int32_t>(ns);
-    int16_t *tp = m.scratch<int16_t>((160 + 3) * TL_RS_TAPS);
-    m.upload(tp, tl_resample_taps_160_147, sizeof tl_resample_taps_160_147);
-    m.upload(tp + 160 * TL_RS_TAPS, tl_resample_taps_3_2, sizeof tl_resample_taps_3_2);
+    int16_t *tp = resample_taps_upload(m);
     if (!m.settle()) return TLB_ERR_HIP;
     m.commit(b->mem);
     b->rs_rate.assign(ns, 0); b->rs_ratio.assign(ns, TL_RS_OFF); b->rs_pos.assign(ns, 0);

@@ -14,22 +14,13 @@
 #define TL_DEC_WAVES 4
 static_assert(3 * (TL_DEC_WAVES * sizeof(TlSynthLds) + 4096 + TL_LDS_GRANULE) <= 160 * 1024, "three workgroups of the synthesis kernel per CU: three waves per SIMD");
 
-// unit u = slot f = u / nstreams of stream s = u % nstreams; (-1, .) past the end
-static __device__ __forceinline__ bool tl_dec_unit(const TlDecLaunch &A, int &s, int &f)
-{
-    const long long u = (long long)blockIdx.x * TL_DEC_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (u >= (long long)A.nstreams * A.nframes) return false;
-    f = (int)(u / A.nstreams); s = (int)(u % A.nstreams);
-    return true;
-}
-
 __global__ void __launch_bounds__(64 * TL_DEC_WAVES) tl_unpack_kernel(TlDecLaunch A)
 {
     __shared__ TlDecLds lds[TL_DEC_WAVES];
     int wave_v = (int)(threadIdx.x >> 6);
     asm volatile("" : "+v"(wave_v));
     int s, f;
-    if (!tl_dec_unit(A, s, f)) return;
+    if (!tl_wave_unit<TL_DEC_WAVES>(A.nstreams, A.nframes, s, f)) return;
     const uint32_t st = tl_unpack_unit(lds[wave_v], A, s, f);
     if ((st & TL_DEC_BAD_MASK) && (threadIdx.x & 63u) == 0) atomicAdd(A.bad, 1ull);
 }
@@ -38,18 +29,17 @@ __global__ void __launch_bounds__(64 * TL_DEC_WAVES) __attribute__((amdgpu_waves
 {
     __shared__ TlSynthLds lds[TL_DEC_WAVES];
     __shared__ double dwin[512];
-    for (int i = (int)threadIdx.x; i < 512; i += 64 * TL_DEC_WAVES) dwin[i] = A.synth->d[i];
-    __syncthreads();
+    TL_STAGE_DWIN(TL_DEC_WAVES, dwin, A.synth);
     int wave_v = (int)(threadIdx.x >> 6);
     asm volatile("" : "+v"(wave_v));
     int s, f;
-    if (!tl_dec_unit(A, s, f)) return;
+    if (!tl_wave_unit<TL_DEC_WAVES>(A.nstreams, A.nframes, s, f)) return;
     tl_synth_unit(lds[wave_v], A, s, f, dwin);
 }
 
 __global__ void __launch_bounds__(64 * TL_DEC_WAVES) tl_dec_carry_kernel(TlDecLaunch A)
 {
-    const int s = (int)blockIdx.x * TL_DEC_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int s = tl_wave_index<TL_DEC_WAVES>();
     if (s < A.nstreams) tl_dec_carry(A, s);
 }
 

@@ -1,6 +1,6 @@
-// toolame_feed.hip -- the kernels of the Layer II feed path (tlb_feed_*): tl_feed_kernel (mp2_feed.h: parse, verify, requantise and
-// synthesise a feed frame into the ingest's input slot) and the pass that leaves each fed stream's last slot for the next launch.  A
-// translation unit of its own: no other kernel's code object is touched by anything here.
+// toolame_feed.hip -- the kernels of the Layer II feed path (tlb_feed_*): tl_feed_kernel (mp2_feed.h: tl_feed_decode -- parse, verify,
+// requantise and synthesise a feed frame -- into the ingest's input slot) and the pass that leaves each fed stream's last slot for the
+// next launch (tl_feed_keep).  A translation unit of its own: no other kernel's code object is touched by anything here.
 // One wavefront per (stream, frame) unit, four units per workgroup; a unit's working set is its wave's LDS block and registers.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,19 +19,17 @@ __global__ void __launch_bounds__(64 * TL_FEED_WAVES) __attribute__((amdgpu_wave
 {
     __shared__ TlSynthLds lds[TL_FEED_WAVES];
     __shared__ double dwin[512];
-    for (int i = (int)threadIdx.x; i < 512; i += 64 * TL_FEED_WAVES) dwin[i] = A.synth->d[i];
-    __syncthreads();
+    TL_STAGE_DWIN(TL_FEED_WAVES, dwin, A.synth);
     int wave_v = (int)(threadIdx.x >> 6);
     asm volatile("" : "+v"(wave_v));
-    // unit u = slot f = u / nstreams of stream s = u % nstreams
-    const long long u = (long long)blockIdx.x * TL_FEED_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (u >= (long long)A.nstreams * A.nframes) return;
-    tl_feed_unit(lds[wave_v], A, (int)(u % A.nstreams), (int)(u / A.nstreams), dwin);
+    int s, f;
+    if (!tl_wave_unit<TL_FEED_WAVES>(A.nstreams, A.nframes, s, f)) return;
+    tl_feed_unit(lds[wave_v], A, s, f, dwin);
 }
 
 __global__ void __launch_bounds__(64 * TL_FEED_WAVES) tl_feed_carry_kernel(TlFeedLaunch A)
 {
-    const int s = (int)blockIdx.x * TL_FEED_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int s = tl_wave_index<TL_FEED_WAVES>();
     if (s < A.nstreams) tl_feed_carry(A, s);
 }
 

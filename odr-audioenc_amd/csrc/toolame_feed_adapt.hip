@@ -1,7 +1,7 @@
 // toolame_feed_adapt.hip -- the kernels of the ADAPTED Layer II feeds (tlb_feed_set_adapted; csrc/mp2_feed_adapt.h): decode a wanted slot
-// into the stream's source plane, resample a tick's source frames out of the carried head and the plane into the ingest's input slot,
-// leave the head, the position and the last wanted slot for the next call.  A translation unit of its own: no other kernel's code object
-// is touched by anything here.
+// into the stream's source plane (the strict feed's decode, mp2_feed.h: tl_feed_decode), resample a tick's source frames out of the
+// carried head and the plane into the ingest's input slot, leave the head, the position and the last wanted slot for the next call.  A
+// translation unit of its own: no other kernel's code object is touched by anything here.
 // decode: one wavefront per (tick, stream), four per workgroup, the synthesis kernel's LDS and occupancy (three waves per SIMD).
 // resample: one workgroup of TL_RS_WAVES waves per (tick, stream), the resample kernel's 17.2 KB of LDS plus 2.3 KB for the outputs of a
 // one-channel feed that go to both channels.  Every branch around a barrier is uniform over the workgroup.
@@ -24,14 +24,12 @@ __global__ void __launch_bounds__(64 * TL_FA_WAVES) __attribute__((amdgpu_waves_
 {
     __shared__ TlSynthLds lds[TL_FA_WAVES];
     __shared__ double dwin[512];
-    for (int i = (int)threadIdx.x; i < 512; i += 64 * TL_FA_WAVES) dwin[i] = A.F.synth->d[i];
-    __syncthreads();
+    TL_STAGE_DWIN(TL_FA_WAVES, dwin, A.F.synth);
     int wave_v = (int)(threadIdx.x >> 6);
     asm volatile("" : "+v"(wave_v));
-    // unit u = slot f = u / nstreams of stream s = u % nstreams
-    const long long u = (long long)blockIdx.x * TL_FA_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (u >= (long long)A.F.nstreams * A.F.nframes) return;
-    tl_fa_decode_unit(lds[wave_v], A, (int)(u % A.F.nstreams), (int)(u / A.F.nstreams), dwin);
+    int s, f;
+    if (!tl_wave_unit<TL_FA_WAVES>(A.F.nstreams, A.F.nframes, s, f)) return;
+    tl_fa_decode_unit(lds[wave_v], A, s, f, dwin);
 }
 
 __global__ void __launch_bounds__(64 * TL_RS_WAVES) tl_feed_adapt_resample_kernel(TlFeedAdaptLaunch A)
@@ -54,7 +52,7 @@ __global__ void __launch_bounds__(64 * TL_RS_WAVES) tl_feed_adapt_resample_kerne
 
 __global__ void __launch_bounds__(64 * TL_FA_WAVES) tl_feed_adapt_carry_kernel(TlFeedAdaptLaunch A)
 {
-    const int s = (int)blockIdx.x * TL_FA_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int s = tl_wave_index<TL_FA_WAVES>();
     if (s < A.F.nstreams) tl_fa_carry(A, s);
 }
 

@@ -1,9 +1,10 @@
-// mp2_feed_san_main.cpp -- TEST-ONLY driver of the feed emulation (mp2_feed_emu.cpp) as a program of its own, so that it can be linked
-// with AddressSanitizer + UBSan (tests/test_feed_emu.py builds it; nothing is preloaded into anything).  Reads a case file, decodes every
-// batch in it on a reset feed decoder, writes every result to the output file; the test compares them with the plain build's.
-//   case file: int32 nstreams, ncases; per stream int64 samplerate, int32 kbps, channels (0: no feed);
-//              per case int32 nframes; uint8 frames[nframes][nstreams][stride]; int32 len[nframes][nstreams]
-//   output:    per case report[nframes][nstreams], pcm[nframes][nstreams][2304] (every sample 0x1111 before the call)
+// mp2_feed_san_main.cpp -- TEST-ONLY driver of the feed emulation (mp2_feed_emu.cpp: strict and adapted feeds) as a program of its own, so
+// that it can be linked with AddressSanitizer + UBSan (tests/feedlib.py builds it; nothing is preloaded into anything).  Reads a case file,
+// runs every case's calls on a reset object, writes every result to the output file; the test compares them with the plain build's.
+// A strict case is one call per case, adapted = 0 and the stream's rate and channels the feed's own.
+//   case file: int32 nstreams, ncases; per stream int64 samplerate, int32 kbps, channels (0: no feed), adapted, int64 stream rate, int32 stream channels;
+//              per case int32 ncalls; per call int32 nframes; uint8 frames[nframes][nstreams][stride]; int32 len[nframes][nstreams]
+//   output:    per call report[nframes][nstreams], pcm[nframes][nstreams][2304] (every sample 0x1111 before the call)
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,7 +12,7 @@
 #include <vector>
 
 extern "C" {
-void *feed_create(int nstreams, const long *fs, const int *kbps, const int *channels, int *err);
+void *feed_create(int nstreams, const long *fs, const int *kbps, const int *channels, const int *adapted, const long *enc_rate, const int *enc_nch, int *err);
 void feed_destroy(void *h);
 int feed_stride(void *h);
 int feed_sizeof_report(void);
@@ -28,30 +29,36 @@ int main(int argc, char **argv)
     if (!fi || !fo) return 2;
     int32_t ns, ncases;
     rd(fi, &ns, 4); rd(fi, &ncases, 4);
-    std::vector<long> fs((size_t)ns);
-    std::vector<int> kbps((size_t)ns), ch((size_t)ns);
+    std::vector<long> fs((size_t)ns), er((size_t)ns);
+    std::vector<int> kbps((size_t)ns), ch((size_t)ns), ad((size_t)ns), en((size_t)ns);
     for (int s = 0; s < ns; s++) {
-        int64_t r; int32_t v[2];
-        rd(fi, &r, 8); rd(fi, v, 8);
-        fs[(size_t)s] = (long)r; kbps[(size_t)s] = v[0]; ch[(size_t)s] = v[1];
+        int64_t r; int32_t v[3];
+        rd(fi, &r, 8); rd(fi, v, 12);
+        fs[(size_t)s] = (long)r; kbps[(size_t)s] = v[0]; ch[(size_t)s] = v[1]; ad[(size_t)s] = v[2];
+        rd(fi, &r, 8); rd(fi, v, 4);
+        er[(size_t)s] = (long)r; en[(size_t)s] = v[0];
     }
     int err = 0;
-    void *h = feed_create(ns, fs.data(), kbps.data(), ch.data(), &err);
+    void *h = feed_create(ns, fs.data(), kbps.data(), ch.data(), ad.data(), er.data(), en.data(), &err);
     if (!h) return 3;
     const size_t stride = (size_t)feed_stride(h);
     for (int k = 0; k < ncases; k++) {
-        int32_t nf;
-        rd(fi, &nf, 4);
-        const size_t slots = (size_t)nf * (size_t)ns;
-        // exactly as long as the data: a read past a slot's end, or past the last slot, is a read past the allocation
-        std::vector<uint8_t> frames(slots * stride), report(slots * (size_t)feed_sizeof_report());
-        std::vector<int32_t> len(slots);
-        std::vector<int16_t> pcm(slots * 2304, (int16_t)0x1111);
-        rd(fi, frames.data(), frames.size());
-        rd(fi, len.data(), 4 * slots);
+        int32_t ncalls;
+        rd(fi, &ncalls, 4);
         feed_reset(h, -1);
-        if (feed_decode(h, frames.data(), len.data(), nf, pcm.data(), report.data())) return 4;
-        fwrite(report.data(), 1, report.size(), fo); fwrite(pcm.data(), 2, pcm.size(), fo);
+        for (int c = 0; c < ncalls; c++) {
+            int32_t nf;
+            rd(fi, &nf, 4);
+            const size_t slots = (size_t)nf * (size_t)ns;
+            // exactly as long as the data: a read past a slot's end, or past the last slot, is a read past the allocation
+            std::vector<uint8_t> frames(slots * stride), report(slots * (size_t)feed_sizeof_report());
+            std::vector<int32_t> len(slots);
+            std::vector<int16_t> pcm(slots * 2304, (int16_t)0x1111);
+            rd(fi, frames.data(), frames.size());
+            rd(fi, len.data(), 4 * slots);
+            if (feed_decode(h, frames.data(), len.data(), nf, pcm.data(), report.data())) return 4;
+            fwrite(report.data(), 1, report.size(), fo); fwrite(pcm.data(), 2, pcm.size(), fo);
+        }
     }
     feed_destroy(h);
     fclose(fi);

@@ -1,13 +1,9 @@
 """Support for the adapted-feed tests (test_feed_adapt_*.py): the schedule's closed form in Python ints, the numpy oracle -- feedlib's decode
 of the WANTED frames, the channel map, resamplelib's formula, cut into ticks; it shares no code with the emulation --, the emulation of the
-kernels (tests/emu/mp2_feed_adapt_emu.cpp, compiled into a temporary directory), and the stream set and inputs the test files share.
+kernels through feedlib (tests/emu/mp2_feed_emu.cpp, the one feed emulation), and the stream set and inputs the test files share.
 A plain module: nothing here is collected by pytest."""
 import ctypes as C
-import os
-import struct
-import subprocess
 import tempfile
-from pathlib import Path
 
 import numpy as np
 
@@ -132,99 +128,36 @@ def written(streams, nticks):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-_FLAGS = F._FLAGS + ["-Wno-unused-but-set-variable", "-Wno-maybe-uninitialized"]
-_SRC = [str(ROOT / "tests" / "emu" / "mp2_feed_adapt_emu.cpp"), str(ROOT / "odr-audioenc_amd" / "csrc" / "mp2_host.cpp")]
+# the emulation, the sanitizer driver and the ctypes layer are feedlib's; here: a stream set as feedlib's rows, the calls cut by cut
 _emu_so = None
 
 
+def rows_of(streams):
+    return [(fcfg_of(st), int(st["adapt"]), st["enc"][0], enc_nch(st)) for st in streams]
+
+
 def build_emu():
-    """tests/emu/mp2_feed_adapt_emu.cpp + csrc/mp2_host.cpp -> a temporary directory, once per process"""
+    """feedlib.build_emu into a temporary directory, once per process"""
     global _emu_so
     if _emu_so is None:
-        so = Path(tempfile.mkdtemp(prefix="faemu")) / "libmp2feedadaptemu.so"
-        subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + _FLAGS + ["-o", str(so)] + _SRC + ["-lm"], check=True)
-        _emu_so = so
+        _emu_so = F.build_emu(tempfile.mkdtemp(prefix="faemu"))
     return _emu_so
 
 
-def build_san_driver(outdir):
-    """tests/emu/mp2_feed_adapt_san_main.cpp + the emulation + csrc/mp2_host.cpp as ONE program under AddressSanitizer + UBSan (linked, not preloaded)"""
-    exe = Path(outdir) / "mp2_feed_adapt_san"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + _FLAGS + ["-o", str(exe),
-                    str(ROOT / "tests" / "emu" / "mp2_feed_adapt_san_main.cpp")] + _SRC + ["-lm"], check=True)
-    return exe
+build_san_driver = F.build_san_driver
 
 
 def run_san_driver(exe, workdir, streams, cases):
     """cases: [[(frames, lens), ...]]: per case the calls of one run from the reset -> per case (report, pcm) over all its ticks, as the
     sanitized program wrote them (every sample POISON before each call)"""
-    fin, fout = Path(workdir) / "cases.bin", Path(workdir) / "results.bin"
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<ii", len(streams), len(cases)))
-        for st in streams:
-            c = fcfg_of(st)
-            f.write(struct.pack("<qiiiqi", c["samplerate"] if c else 0, c["bitrate"] if c else 0, c["channels"] if c else 0, int(st["adapt"]), st["enc"][0], enc_nch(st)))
-        for calls in cases:
-            f.write(struct.pack("<i", len(calls)))
-            for fr, ln in calls:
-                f.write(struct.pack("<i", fr.shape[0]))
-                f.write(np.ascontiguousarray(fr, dtype=np.uint8).tobytes())
-                f.write(np.ascontiguousarray(ln, dtype=np.int32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([str(exe), str(fin), str(fout)], capture_output=True, text=True, env=env, timeout=1200)
-    assert r.returncode == 0 and "sanitized ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-6000:]
-    blob, pos, out = fout.read_bytes(), 0, []
-    ns = len(streams)
-    for calls in cases:
-        reps, pcms = [], []
-        for fr, _ in calls:
-            nf = fr.shape[0]
-            n = F.REPORT_DTYPE.itemsize * nf * ns
-            reps.append(np.frombuffer(blob[pos:pos + n], dtype=F.REPORT_DTYPE).reshape(nf, ns)); pos += n
-            n = 2 * nf * ns * 2 * N
-            pcms.append(np.frombuffer(blob[pos:pos + n], dtype=np.int16).reshape(nf, ns, 2 * N)); pos += n
-        out.append((np.concatenate(reps), np.concatenate(pcms)))
-    assert pos == len(blob)
-    return out
+    return [(np.concatenate([r for r, _ in calls]), np.concatenate([p for _, p in calls])) for calls in F.run_san_rows(exe, workdir, rows_of(streams), cases)]
 
 
-class FeedAdaptEmu:
+class FeedAdaptEmu(F.FeedEmu):
     """a stream set on the emulated strict + adapted feed path; decode() mirrors tlb_feed_host with an output buffer that holds POISON"""
 
     def __init__(self, streams):
-        L = self.L = C.CDLL(str(build_emu()))
-        L.fa_create.restype = C.c_void_p
-        L.fa_create.argtypes = [C.c_int] + [C.c_void_p] * 7
-        L.fa_destroy.argtypes = [C.c_void_p]
-        L.fa_stride.argtypes = [C.c_void_p]
-        L.fa_reset.argtypes = [C.c_void_p, C.c_int]
-        L.fa_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        assert L.fa_sizeof_report() == F.REPORT_DTYPE.itemsize
-        n = self.n = len(streams)
-        fc = [fcfg_of(st) for st in streams]
-        fs = (C.c_long * n)(*[c["samplerate"] if c else 0 for c in fc])
-        kb = (C.c_int * n)(*[c["bitrate"] if c else 0 for c in fc])
-        ch = (C.c_int * n)(*[c["channels"] if c else 0 for c in fc])
-        ad = (C.c_int * n)(*[int(st["adapt"]) for st in streams])
-        er = (C.c_long * n)(*[st["enc"][0] for st in streams])
-        en = (C.c_int * n)(*[enc_nch(st) for st in streams])
-        err = C.c_int(0)
-        self.h = L.fa_create(n, fs, kb, ch, ad, er, en, C.byref(err))
-        assert self.h, err.value
-        self.stride = L.fa_stride(self.h)
-
-    def decode(self, frames, lens, init=None):
-        frames = np.ascontiguousarray(frames, dtype=np.uint8)
-        nf = frames.shape[0]
-        assert frames.shape == (nf, self.n, self.stride)
-        ln = np.ascontiguousarray(lens, dtype=np.int32)
-        assert ln.shape == (nf, self.n)
-        rep = np.zeros((nf, self.n), dtype=F.REPORT_DTYPE)
-        pcm = np.full((nf, self.n, 2 * N), POISON, dtype=np.int16) if init is None else np.array(init, dtype=np.int16, order="C", copy=True)
-        rc = self.L.fa_decode(self.h, frames.ctypes.data, ln.ctypes.data, nf, pcm.ctypes.data, rep.ctypes.data)
-        assert rc == 0, rc
-        return pcm, rep
+        super().__init__(build_emu(), None, rows_of(streams))
 
     def run_cuts(self, frames, lens, cuts):
         """the ticks of (frames, lens) call by call -> (pcm, report) over all of them"""
@@ -234,22 +167,14 @@ class FeedAdaptEmu:
             f0 += n
         return np.concatenate([p for p, _ in out]), np.concatenate([r for _, r in out])
 
-    def reset(self, s=-1):
-        assert self.L.fa_reset(self.h, s) == 0
-
-    def close(self):
-        if self.h:
-            self.L.fa_destroy(self.h)
-            self.h = None
-
 
 def resample_plane(fs, es, fch, sch, x, nticks):
     """the emulation's resample stage alone over a source plane x int16 [>= K(nticks - 1) * 1152][fch] -> int16 [nticks][2304] (POISON where nothing is written)"""
     L = C.CDLL(str(build_emu()))
-    L.fa_resample_plane.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.feed_resample_plane.argtypes = [C.c_long, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     x = np.ascontiguousarray(x, dtype=np.int16)
     out = np.full((nticks, 2 * N), POISON, dtype=np.int16)
-    rc = L.fa_resample_plane(fs, es, fch, sch, x.ctypes.data, nticks, out.ctypes.data)
+    rc = L.feed_resample_plane(fs, es, fch, sch, x.ctypes.data, nticks, out.ctypes.data)
     assert rc == 0, rc
     return out
 

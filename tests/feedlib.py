@@ -1,5 +1,5 @@
-"""Support for the Layer II feed tests (test_feed_abi.py, test_feed_emu.py, test_feed_gpu.py): the emulation of the feed kernels (compiled
-into a temporary directory), the numpy statement of a feed's decode built on declib's reader, requantiser and synthesis, the three
+"""Support for the Layer II feed tests (test_feed_abi.py, test_feed_emu.py, test_feed_gpu.py, and through feedadaptlib test_feed_adapt_*.py):
+the emulation of the feed kernels, strict and adapted (compiled into a temporary directory), its sanitizer driver and ctypes layer, the numpy statement of a feed's decode built on declib's reader, requantiser and synthesis, the three
 transforms that make a project-encoded frame "foreign" without changing its audio, and the cases and hostile inputs the tests share.
 A plain module: nothing here is collected by pytest."""
 import ctypes as C
@@ -195,74 +195,96 @@ def slots_to_arrays(slot_lists, stride):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# the emulation
-_FLAGS = ["-std=c++17", "-mfma", "-ffp-contract=off", "-fno-strict-aliasing", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas"]
+# the emulation: ONE for strict and adapted feeds (tests/emu/mp2_feed_emu.cpp); feedadaptlib adds what is specific to adapted feeds.
+# A stream is a row (fcfg or None, adapted, the stream's rate, the stream's channels); a strict feed's stream has the feed's rate and channels.
+_FLAGS = ["-std=c++17", "-mfma", "-ffp-contract=off", "-fno-strict-aliasing", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas",
+          "-Wno-unused-but-set-variable", "-Wno-maybe-uninitialized"]
+_SRC = [str(ROOT / "tests" / "emu" / "mp2_feed_emu.cpp"), str(ROOT / "odr-audioenc_amd" / "csrc" / "mp2_host.cpp")]
+
+
+def strict_rows(fcfgs):
+    return [(c, 0, c["samplerate"] if c else 0, c["channels"] if c else 0) for c in fcfgs]
 
 
 def build_emu(outdir):
     """tests/emu/mp2_feed_emu.cpp + csrc/mp2_host.cpp -> outdir/libmp2feedemu.so"""
     so = Path(outdir) / "libmp2feedemu.so"
-    subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + _FLAGS + ["-o", str(so), str(ROOT / "tests" / "emu" / "mp2_feed_emu.cpp"),
-                    str(ROOT / "odr-audioenc_amd" / "csrc" / "mp2_host.cpp"), "-lm"], check=True)
+    subprocess.run(["g++", "-O2", "-fPIC", "-shared"] + _FLAGS + ["-o", str(so)] + _SRC + ["-lm"], check=True)
     return so
 
 
 def build_san_driver(outdir):
     """tests/emu/mp2_feed_san_main.cpp + the emulation + csrc/mp2_host.cpp as ONE program under AddressSanitizer + UBSan (linked, not preloaded)"""
     exe = Path(outdir) / "mp2_feed_san"
-    emu = ROOT / "tests" / "emu"
     subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + _FLAGS + ["-o", str(exe),
-                    str(emu / "mp2_feed_san_main.cpp"), str(emu / "mp2_feed_emu.cpp"), str(ROOT / "odr-audioenc_amd" / "csrc" / "mp2_host.cpp"), "-lm"], check=True)
+                    str(ROOT / "tests" / "emu" / "mp2_feed_san_main.cpp")] + _SRC + ["-lm"], check=True)
     return exe
 
 
-def run_san_driver(exe, workdir, fcfgs, cases):
-    """fcfgs: per stream a feed configuration or None; cases: [(frames, lens)] -> [(report, pcm)] as the sanitized program wrote them"""
+def run_san_rows(exe, workdir, rows, cases):
+    """cases: [[(frames, lens), ...]]: per case the calls of one run from the reset -> per case [(report, pcm)] per call, as the sanitized
+    program wrote them (every sample POISON before each call)"""
     fin, fout = Path(workdir) / "cases.bin", Path(workdir) / "results.bin"
     with open(fin, "wb") as f:
-        f.write(struct.pack("<ii", len(fcfgs), len(cases)))
-        for c in fcfgs:
-            f.write(struct.pack("<qii", c["samplerate"] if c else 0, c["bitrate"] if c else 0, c["channels"] if c else 0))
-        for fr, ln in cases:
-            f.write(struct.pack("<i", fr.shape[0]))
-            f.write(np.ascontiguousarray(fr, dtype=np.uint8).tobytes())
-            f.write(np.ascontiguousarray(ln, dtype=np.int32).tobytes())
+        f.write(struct.pack("<ii", len(rows), len(cases)))
+        for c, adapt, rate, nch in rows:
+            f.write(struct.pack("<qiiiqi", c["samplerate"] if c else 0, c["bitrate"] if c else 0, c["channels"] if c else 0, int(adapt), rate, nch))
+        for calls in cases:
+            f.write(struct.pack("<i", len(calls)))
+            for fr, ln in calls:
+                f.write(struct.pack("<i", fr.shape[0]))
+                f.write(np.ascontiguousarray(fr, dtype=np.uint8).tobytes())
+                f.write(np.ascontiguousarray(ln, dtype=np.int32).tobytes())
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([str(exe), str(fin), str(fout)], capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0 and "sanitized ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-6000:]
     blob, pos, out = fout.read_bytes(), 0, []
-    for fr, _ in cases:
-        nf, ns = fr.shape[0], fr.shape[1]
+    for calls in cases:
         res = []
-        for dt, shape in ((REPORT_DTYPE, (nf, ns)), (np.dtype(np.int16), (nf, ns, 2304))):
-            n = dt.itemsize * int(np.prod(shape))
-            res.append(np.frombuffer(blob[pos:pos + n], dtype=dt).reshape(shape))
-            pos += n
-        out.append(tuple(res))
+        for fr, _ in calls:
+            nf, ns = fr.shape[0], fr.shape[1]
+            one = []
+            for dt, shape in ((REPORT_DTYPE, (nf, ns)), (np.dtype(np.int16), (nf, ns, 2304))):
+                n = dt.itemsize * int(np.prod(shape))
+                one.append(np.frombuffer(blob[pos:pos + n], dtype=dt).reshape(shape))
+                pos += n
+            res.append(tuple(one))
+        out.append(res)
     assert pos == len(blob)
     return out
 
 
-class FeedEmu:
-    """N streams on the emulated feed path; fcfgs: per stream dict(samplerate, bitrate, channels) or None (no feed).  decode() mirrors
-    tlb_feed_host with an output buffer that holds POISON before the call."""
+def run_san_driver(exe, workdir, fcfgs, cases):
+    """fcfgs: per stream a feed configuration or None; cases: [(frames, lens)] -> [(report, pcm)] as the sanitized program wrote them"""
+    return [calls[0] for calls in run_san_rows(exe, workdir, strict_rows(fcfgs), [[c] for c in cases])]
 
-    def __init__(self, so, fcfgs):
+
+class FeedEmu:
+    """N streams on the emulated feed path.  Either fcfgs: per stream dict(samplerate, bitrate, channels) or None (no feed), every feed a
+    strict one; or rows (fcfgs is then not read): per stream the tuple (fcfg or None, set through the adapted entry point, the stream's
+    rate, the stream's channels), as feedadaptlib.rows_of makes them.  decode() mirrors tlb_feed_host with an output buffer that holds
+    POISON before the call."""
+
+    def __init__(self, so, fcfgs, rows=None):
         L = self.L = C.CDLL(str(so))
         L.feed_create.restype = C.c_void_p
-        L.feed_create.argtypes = [C.c_int] + [C.c_void_p] * 4
+        L.feed_create.argtypes = [C.c_int] + [C.c_void_p] * 7
         L.feed_destroy.argtypes = [C.c_void_p]
         L.feed_stride.argtypes = [C.c_void_p]
         L.feed_reset.argtypes = [C.c_void_p, C.c_int]
         L.feed_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         assert L.feed_sizeof_report() == REPORT_DTYPE.itemsize
-        n = self.n = len(fcfgs)
-        fs = (C.c_long * n)(*[c["samplerate"] if c else 0 for c in fcfgs])
-        kb = (C.c_int * n)(*[c["bitrate"] if c else 0 for c in fcfgs])
-        ch = (C.c_int * n)(*[c["channels"] if c else 0 for c in fcfgs])
+        rows = strict_rows(fcfgs) if rows is None else rows
+        n = self.n = len(rows)
+        fs = (C.c_long * n)(*[c["samplerate"] if c else 0 for c, _, _, _ in rows])
+        kb = (C.c_int * n)(*[c["bitrate"] if c else 0 for c, _, _, _ in rows])
+        ch = (C.c_int * n)(*[c["channels"] if c else 0 for c, _, _, _ in rows])
+        ad = (C.c_int * n)(*[int(a) for _, a, _, _ in rows])
+        er = (C.c_long * n)(*[r for _, _, r, _ in rows])
+        en = (C.c_int * n)(*[k for _, _, _, k in rows])
         err = C.c_int(0)
-        self.h = L.feed_create(n, fs, kb, ch, C.byref(err))
+        self.h = L.feed_create(n, fs, kb, ch, ad, er, en, C.byref(err))
         assert self.h, err.value
         self.stride = L.feed_stride(self.h)
 

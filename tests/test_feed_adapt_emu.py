@@ -211,7 +211,7 @@ def test_hostile_input_is_flagged_and_contained(one_call):
 
 def test_hostile_input_is_clean_under_asan_ubsan(tmp_path):
     """the same hostile sets, and noise under every kind of length over the whole stream set, through the lane-loop build linked as a
-    program with AddressSanitizer + UBSan (tests/emu/mp2_feed_adapt_san_main.cpp; its buffers are exactly as long as the data).  Clean,
+    program with AddressSanitizer + UBSan (tests/emu/mp2_feed_san_main.cpp; its buffers are exactly as long as the data).  Clean,
     and the same reports and PCM as the plain build."""
     exe = A.build_san_driver(tmp_path)
     streams, lists, _ = hostile_lists()

@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """What ADAPTED Layer II feeds cost and save in a tick (tlb_tick_set_feed_adapted), on the GPU.
 
-    python tools/tick_feed_adapt_cost.py [--streams 16384] [--ticks 100] [--rounds 5] [--psy 3] [--parent-lib PATH] [--out profiles/tick_feed_adapt.txt]
+    python tools/tick_feed_adapt_cost.py [--streams 16384] [--ticks 100] [--rounds 5] [--psy 3] [--parent-lib PATH] [--check-ticks 4] [--out profiles/tick_feed_adapt.txt]
 
 Tick objects of 48 kHz stereo 128 kbps, egress EDI AF:
     (a) `pcm`      PCM in, no feed set
     (b) `feed`     every stream with a strict 192 kbps feed, no PCM over the link
     (c) `adapted`  every stream with a 44.1 kHz 128 kbps two-channel ADAPTED feed (a frame on the ticks that want one), no PCM over the link
     (d) `source`   the same rate as PCM: set_source(44100), 1058 / 1059 source frames per slot
-    `parent_pcm`, `parent_feed`: (a) and (b) with the library built from the PARENT commit (--parent-lib: its libtoolame_dab_hip.so; left
-    out without it).  (a) and (b) queue the device calls the parent queues: they must lie within the spread the parent's legs show.
+    `parent_pcm`, `parent_feed`, `parent_adapted`: (a), (b) and (c) with the library built from the PARENT commit (--parent-lib: its
+    libtoolame_dab_hip.so; left out without it).  They queue the device calls the parent queues: each must lie within the spread the
+    parent's legs show, and after the warm-up round `feed` / `parent_feed` and `adapted` / `parent_adapted` are stepped --check-ticks ticks
+    side by side and must deliver byte-identical AF packets for every stream (asserted).
 The legs are interleaved round by round in one process on one box.  A round runs `ticks` ticks per leg overlapped as an application does
 (submit, submit, wait, submit, wait, ...) and keeps the median FINISHED-TICK INTERVAL (wall clock between two waits returning) and the
 median and maximum of tlb_tick_last_ms (device clock: first copy-in queued -> last copy-out done).  The input sets are filled once; a
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--psy", type=int, default=3)
+    ap.add_argument("--check-ticks", type=int, default=4)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -69,12 +72,12 @@ def main():
     src.close()
     assert all(len(f) in (417, 418) for f in aframes)
     plib = T._bind(C.CDLL(str(args.parent_lib))) if args.parent_lib else None
-    legs = ["pcm", "feed", "adapted", "source"] + (["parent_pcm", "parent_feed"] if plib else [])
-    fed = {"feed": (fc, frames), "parent_feed": (fc, frames), "adapted": (fa, aframes)}
+    legs = ["pcm", "feed", "adapted", "source"] + (["parent_pcm", "parent_feed", "parent_adapted"] if plib else [])
+    fed = {"feed": (fc, frames), "parent_feed": (fc, frames), "adapted": (fa, aframes), "parent_adapted": (fa, aframes)}
     objs, link = {}, {}
     for name in legs:
         t = M.Tick(cfg, egress="af", version=b"odr-audioenc_amd bench", lib=plib if name.startswith("parent") else None)
-        if name == "adapted":
+        if name.endswith("adapted"):
             t.set_feed(-1, fa, adapt=True)
         elif name in fed:
             t.set_feed(-1, fc)
@@ -100,13 +103,27 @@ def main():
 
     def submit(name, t):
         nsub[name] += 1
-        if name == "adapted":                                        # every stream has the one schedule: stream 0 answers for all
+        if name.endswith("adapted"):                                 # every stream has the one schedule: stream 0 answers for all
             if t.feed_want(0):
                 t.feed_len[:] = len(aframes[(nsub[name] - 1) & 1])   # (the two input sets take turns; each holds one of the two frames)
         elif name in fed:
             t.feed_len[:] = 576
         t.submit()
+
+    def same_packets(a, b):
+        """both legs have run the same ticks so far: the next ones side by side, every stream's AF packets compared"""
+        for i in range(args.check_ticks):
+            for name in (a, b):
+                submit(name, objs[name])
+            for name in (a, b):
+                objs[name].wait()
+            for s in range(ns):
+                pa = objs[a].packets(s)
+                assert pa and pa == objs[b].packets(s), f"{a} / {b}: tick {i} of the check, stream {s}: the AF packets differ"
     for rnd in range(args.rounds + 1):                               # round 0 is the warm-up: code objects loaded, every buffer touched
+        if rnd == 1 and plib:
+            same_packets("feed", "parent_feed")
+            same_packets("adapted", "parent_adapted")
         for name, t in objs.items():
             dev, done = np.empty(args.ticks), np.empty(args.ticks)
             submit(name, t)
@@ -123,6 +140,7 @@ def main():
     res = {"what": f"{ns} streams (48 kHz stereo 128 kbps psy {args.psy}, EDI AF), {args.ticks} overlapped ticks per round and leg, {args.rounds} rounds interleaved; "
                    "interval_ms = wall clock between finished ticks, median_ms / max_ms = tlb_tick_last_ms",
            "legs": {k: {m: stats(v) for m, v in d.items()} for k, d in out.items()},
+           "same_af_packets": {"ticks": args.check_ticks, "pairs": ["feed/parent_feed", "adapted/parent_adapted"]} if plib else None,
            "link_bytes_per_tick": link, "link_bytes_per_stream": {k: v // ns for k, v in link.items()}}
     for t in objs.values():
         t.close()
