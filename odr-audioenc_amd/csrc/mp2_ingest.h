@@ -1,8 +1,9 @@
-// mp2_ingest.h -- the ingest glue of the caller's loop with SHORT READS: what AudioEnc::run() does to a frame between its input queue and
+// mp2_ingest.h -- the ingest glue of the caller's loop: what AudioEnc::run() does to a frame between its input queue and
 // toolame_encode_frame() (src/odr-audioenc.cpp): the stretch of a short read over the frame (expand_missing_samples, :335-373, called at
-// :910-917), then gain and peak (:1030-1051) and the de-interleave (:1139-1152); and the underrun bookkeeping that goes with it (:919-935).
-// One workgroup of TL_INGEST_WAVES waves per (frame, stream) slot; tl_ingest_wave is one wave's share, written with the lane macros of
-// mp2_wave.h so that tests/emu/mp2_ingest_emu.cpp runs the same text as lane loops.
+// :910-917), then gain and peak (:1030-1051) and the de-interleave (:1139-1152); and the two counters that go with it, underruns (:919-935)
+// and silence (:1053-1079).  One workgroup of TL_INGEST_WAVES waves per (frame, stream) slot; tl_ingest_wave is one wave's share, written
+// with the lane macros of mp2_wave.h so that tests/emu/mp2_ingest_emu.cpp runs the same text as lane loops.  Both ingest kernels of
+// toolame_ingest.hip are this text: tl_ingest_kernel (no `valid` array) is tl_ingest_wave<true> alone.
 //
 // The stretch.  `valid` whole sample frames (an L/R pair, or one sample of a one-channel input) were delivered, missing = 1152 - valid.
 // The queue zero-fills what it could not deliver (src/SampleQueue.h:217-276), so the stretch reads a buffer whose tail is ZERO whatever
@@ -42,7 +43,7 @@ TL_FN int tl_ingest_clamp(int valid) { return valid < 0 ? 0 : valid > TL_INGEST_
 TL_FN int tl_stretch_src(int i, int q) { return i < 1 ? 0 : i - (int)((unsigned)(i - 1) / (unsigned)q); }
 
 // Wave `wave` of the TL_INGEST_WAVES of a slot: src = the slot's 2304 interleaved values (a one-channel stream uses the first 1152),
-// dst = its planar [2][1152] output, valid already clamped (FULL: valid == 1152).  A full slot moves 16 bytes per lane and step, as tl_ingest_kernel does; a short
+// dst = its planar [2][1152] output, valid already clamped (FULL: valid == 1152).  A full slot moves 16 bytes per lane and step (16-byte loads, 8-byte stores); a short
 // one gathers the same four words frame by frame (4 bytes an L/R pair, 2 bytes a mono sample), zero where the source frame lies behind
 // `valid`.  From there on the two are one text: gain with the reference's double-multiply-and-truncate, the positive peak of the values at
 // even / odd positions (the level loop walks the buffer as L/R pairs in mono too, :1034-1051), the de-interleave.  The wave's two peaks
@@ -117,4 +118,18 @@ TL_FN void tl_underrun_stream(const int32_t *TL_RESTRICT valid, uint32_t *TL_RES
         n += is_short ? 1u : 0u;
     }
     underrun_ms[s] = ms; underruns[s] = n;
+}
+
+// Silence accounting of one stream over the frames of a call, in order (:1053-1079): a frame whose peaks are both 0 adds its duration to
+// the stream's counter, any other frame resets it; the decision (`measured_silence_ms > 1000 * silence_timeout`) stays with the caller.
+// peaks [nframes][nstreams][2].
+TL_FN void tl_silence_stream(const int16_t *TL_RESTRICT peaks, uint32_t *TL_RESTRICT silence_ms, uint32_t frame_ms, int s, int nstreams, int nframes)
+{
+    uint32_t ms = silence_ms[s];
+    for (int f = 0; f < nframes; f++) {
+        const size_t slot = (size_t)f * (size_t)nstreams + (size_t)s;
+        const int pl = peaks[slot * 2], pr = peaks[slot * 2 + 1];
+        ms = (pl > pr ? pl : pr) == 0 ? ms + frame_ms : 0u;
+    }
+    silence_ms[s] = ms;
 }

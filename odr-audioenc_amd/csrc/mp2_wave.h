@@ -4,7 +4,7 @@
 // (/root/reference/libtoolame-dab/toolame.c:267-554): 64 lanes cooperate on one frame of one stream,
 // all per-frame working state lives in LDS / registers, HBM sees PCM in and frame bytes out.
 // Units of work (tl_frame_unit, tl_main_unit, tl_psy2_chain, tl_finish_stream at the end of the file) are what
-// the kernels in toolame_hip.hip hand to their waves.
+// the encode-path kernels (toolame_hip.hip, toolame_psy2.hip) hand to their waves; the other kernel units use the lane primitives below.
 //
 // The file is written in a lane-SPMD style that compiles two ways from the same source:
 //   * hipcc --offload-arch=gfx950 : TL_LANES_BEGIN/END open a per-lane scope, cross-lane

@@ -1,5 +1,5 @@
-// tl_kernel_util.h -- what the kernels' translation units share beside mp2_wave.h: the work list of the persistent encode kernels
-// (toolame_hip.hip, toolame_psy2.hip) and the prologue of the wave-per-unit kernels (toolame_dec.hip, toolame_feed.hip, toolame_feed_adapt.hip).
+// tl_kernel_util.h -- what the kernels' translation units share beside mp2_wave.h: the work list of the persistent kernels of the encode
+// path (toolame_hip.hip, toolame_psy2.hip) and the prologue of the wave-per-unit kernels (toolame_dec.hip, toolame_feed.hip, toolame_feed_adapt.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,3 +47,21 @@ template <int WAVES> static __device__ __forceinline__ bool tl_wave_unit(int nst
 // here before it may leave.  A macro: the copy is compiled in the kernel's own body, where `dwin` is the LDS array and not a pointer to it.
 #define TL_STAGE_DWIN(WAVES, dwin, synth) \
     do { for (int i = (int)threadIdx.x; i < 512; i += 64 * (WAVES)) (dwin)[i] = (synth)->d[i]; __syncthreads(); } while (0)
+// the opening of the two encode kernels, compiled in the kernel's own body like TL_STAGE_DWIN: FIRST (the frame kernel's dB-sum table), then the
+// encoder's tables into the workgroup's `sh` (TlMainShared) and the barrier; it leaves B (a TlBlockShared pointer whose dbtable part lies before
+// the copied block: the encode path never touches B->dbtable), the wave's index uniform (wave) and as a vector register (wave_v, laundered), and grp
+#define TL_ENCODE_PROLOGUE(sh, T, FIRST) \
+    { \
+        FIRST; \
+        const double *src = (const double *)&(T)->shared.scalefactor[0]; \
+        double *dst = (double *)&(sh).bytes[0]; \
+        for (int i = (int)threadIdx.x; i < (int)(sizeof((sh).bytes) / 8); i += 64 * TL_MAIN_WAVES) dst[i] = src[i]; \
+        for (int i = (int)threadIdx.x; i < 512; i += 64 * TL_MAIN_WAVES) (sh).enw_s[i] = (T)->enwindow_s[i]; \
+        for (int i = (int)threadIdx.x; i < (int)(sizeof(TlPackTables) / 8); i += 64 * TL_MAIN_WAVES) ((double *)&(sh).pack)[i] = ((const double *)&(T)->pack)[i]; \
+    } \
+    __syncthreads(); \
+    const TlBlockShared *B = (const TlBlockShared *)((const char *)&(sh).bytes[0] - offsetof(TlBlockShared, scalefactor)); \
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); \
+    const int grp = (int)blockIdx.x & 7; \
+    int wave_v = (int)(threadIdx.x >> 6); \
+    asm volatile("" : "+v"(wave_v))

@@ -22,30 +22,31 @@
 #define TL_PSY2_WAVES 12
 #endif
 
+// toolame_hip.hip (tl_psy2_kernel: toolame_psy2.hip): the encode path
 hipError_t tlk_slots(unsigned blocks, hipStream_t st, const TlLaunch &A);                         // tl_slots_kernel, 256 threads
 hipError_t tlk_frame(int psy, bool pairs, bool stereo, unsigned blocks, hipStream_t st, const TlLaunch &A);    // tl_frame_kernel<1|3, pairs, stereo ? 2 : 0>
 hipError_t tlk_main(int psy, bool pairs, bool stereo, unsigned blocks, hipStream_t st, const TlLaunch &A);     // tl_main_kernel<0|2, pairs, stereo ? 2 : 0>
 hipError_t tlk_psy2(unsigned blocks, hipStream_t st, const TlLaunch &A);                          // tl_psy2_kernel
 hipError_t tlk_finish(unsigned blocks, hipStream_t st, const TlLaunch &A);                        // tl_finish_kernel, 256 threads = 4 streams
-hipError_t tlk_ingest(unsigned blocks, hipStream_t st, const int16_t *in, int16_t *out, int16_t *peaks, const double *gain,
-                      const TlConfig *configs, const int32_t *stream_cfg, int nstreams);
-hipError_t tlk_silence(unsigned blocks, hipStream_t st, const int16_t *peaks, uint32_t *silence_ms, const TlConfig *configs,
-                       const int32_t *stream_cfg, int nstreams, int nframes);
+hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state, const TlConfig *configs, const int32_t *stream_cfg,
+                     uint8_t *out, int32_t *out_len, int nstreams, int out_stride);
+// toolame_egress.hip: tl_zmq_frame_kernel (one workgroup per message slot), tl_edi_af_kernel and tl_edi_pft_kernel (one wavefront per packet)
 hipError_t tlk_zmq_frame(unsigned blocks, hipStream_t st, const uint8_t *frames, const int16_t *peaks, uint8_t *msgs, const TlConfig *configs,
                          const int32_t *stream_cfg, int nstreams, int out_stride, int msg_stride, int max_upf, const int32_t *frame_len);
 hipError_t tlk_edi_af(unsigned bx, unsigned by, hipStream_t st, const TlEdiArgs &A);
 hipError_t tlk_edi_pft(unsigned bx, unsigned by, hipStream_t st, const TlPftArgs &A, const TlTables *T);
-hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state, const TlConfig *configs, const int32_t *stream_cfg,
-                     uint8_t *out, int32_t *out_len, int nstreams, int out_stride);
 // toolame_dec.hip: tl_unpack_kernel over every (stream, slot) of the launch, tl_synth_kernel when A.pcm is set, then tl_dec_carry_kernel per stream
 hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
 // toolame_feed.hip: tl_feed_kernel over every (stream, slot) of the launch, then tl_feed_carry_kernel per stream
 hipError_t tlk_feed(hipStream_t st, const TlFeedLaunch &A);
 // toolame_feed_adapt.hip: the decode kernel over every (stream, slot) of the call, the resample kernel (one workgroup per slot), then the carry kernel per stream
 hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A);
-// toolame_ingest.hip: tl_ingest_valid_kernel (one workgroup per slot, valid int32 [nframes][nstreams]) and tl_underrun_kernel (256 threads, one per stream)
-hipError_t tlk_ingest_valid(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid, int16_t *out, int16_t *peaks, const double *gain,
-                            const TlConfig *configs, const int32_t *stream_cfg, int nstreams);
+// toolame_ingest.hip: tl_ingest_valid_kernel, or tl_ingest_kernel when valid (int32 [nframes][nstreams]) is NULL (one workgroup per slot);
+// tl_silence_kernel and tl_underrun_kernel (256 threads, one per stream)
+hipError_t tlk_ingest(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid /* may be NULL */, int16_t *out, int16_t *peaks, const double *gain,
+                      const TlConfig *configs, const int32_t *stream_cfg, int nstreams);
+hipError_t tlk_silence(unsigned blocks, hipStream_t st, const int16_t *peaks, uint32_t *silence_ms, const TlConfig *configs,
+                       const int32_t *stream_cfg, int nstreams, int nframes);
 hipError_t tlk_underrun(unsigned blocks, hipStream_t st, const int32_t *valid, uint32_t *underrun_ms, uint32_t *underruns, const TlConfig *configs,
                         const int32_t *stream_cfg, int nstreams, int nframes);
 // toolame_monitor.hip: tl_monitor_kernel, one wavefront per stream over the stream's slots in order (csrc/mp2_monitor.h); record uint32 [nstreams][8]

@@ -1,7 +1,6 @@
 // tlb_batch.cpp -- the batch object of include/toolame_batch.h part (2): creation, the per-model kernel lists, ONE launch of the encode path
-// (tlb_launch), the host-buffer entry points with their copy pipeline, the caller's ingest glue and silence counter, the life cycle of one
-// stream, flush, the reference's send schedule, the libm self-check and the timing accessors.  Host C++: the kernels are reached through
-// tl_kernels.h.
+// (tlb_launch), the host-buffer entry points with their copy pipeline, the life cycle of one stream, flush, the reference's send schedule,
+// the libm self-check and the timing accessors.  Host C++: the kernels are reached through tl_kernels.h.
 #include "tlb_internal.h"
 #include "tlb_plan.h"
 #include "tl_libm.h"
@@ -30,7 +29,7 @@ void tlb_destroy(tlb_batch *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->d_configs) (void)hipFree(b->d_configs);
-    for (int k = 0; k < 12; k++) if (b->stage[k]) (void)hipFree(b->stage[k]);
+    for (int k = 0; k < TLB_STAGE_COUNT; k++) if (b->stage[k]) (void)hipFree(b->stage[k]);
     for (int i = 0; i < TLB_HOST_CHUNKS; i++) { if (b->ev_in[i]) (void)hipEventDestroy(b->ev_in[i]); if (b->ev_run[i]) (void)hipEventDestroy(b->ev_run[i]); }
     if (b->s_in) (void)hipStreamDestroy(b->s_in);
     if (b->s_run) (void)hipStreamDestroy(b->s_run);
@@ -318,10 +317,10 @@ int tlb_launch(tlb_batch *b, const int16_t *d_pcm, int nframes, const uint8_t *d
     A.nstreams = b->nstreams; A.nframes = nframes; A.out_stride = b->out_stride;
     {   // TlPsyOut records of this launch (psy-2 kernel -> encode kernel, models 2 and 4 only) and ScF-CRC bytes, grow-only.  NOTE: one buffer per batch -- launches of
         // one batch are ordered on one stream (they share the stream state anyway)
-        if (b->n_list[2]) HIPCHK(stage_reserve(b, 5, (size_t)nframes * (size_t)b->nstreams * sizeof(TlPsyOut)));
-        HIPCHK(stage_reserve(b, 6, (size_t)nframes * (size_t)b->nstreams * 4));
-        A.psy_out = (TlPsyOut *)b->stage[5]; A.scfcrc = (uint8_t *)b->stage[6]; A.newpend = b->d_newpend; A.work = b->d_work;
-        if (b->pads[0] || b->pads[1] || b->pads[2] || b->pads[3]) HIPCHK(stage_reserve(b, 7, (size_t)nframes * (size_t)b->nstreams));
+        if (b->n_list[2]) HIPCHK(stage_reserve(b, TLB_STAGE_PSY_OUT, (size_t)nframes * (size_t)b->nstreams * sizeof(TlPsyOut)));
+        HIPCHK(stage_reserve(b, TLB_STAGE_SCFCRC, (size_t)nframes * (size_t)b->nstreams * 4));
+        A.psy_out = (TlPsyOut *)b->stage[TLB_STAGE_PSY_OUT]; A.scfcrc = (uint8_t *)b->stage[TLB_STAGE_SCFCRC]; A.newpend = b->d_newpend; A.work = b->d_work;
+        if (b->pads[0] || b->pads[1] || b->pads[2] || b->pads[3]) HIPCHK(stage_reserve(b, TLB_STAGE_PADBITS, (size_t)nframes * (size_t)b->nstreams));
     }
     HIPCHK(hipEventRecord(b->ev0, st));
     b->have_mid = false;
@@ -330,7 +329,7 @@ int tlb_launch(tlb_batch *b, const int16_t *d_pcm, int nframes, const uint8_t *d
         A.stream_list = b->n_list[p] == b->nstreams ? nullptr : b->d_list[p]; A.nlist = b->n_list[p];      // one model in the batch: the list is 0, 1, 2, ... and the kernels need no look at it
         // persistent waves, twelve per CU (three per SIMD) in every kernel; they take their units off a counter
         const long units = (long)b->n_list[p] * nframes;
-        A.padbits = b->pads[p] ? (uint8_t *)b->stage[7] : nullptr; A.newlag = b->d_newlag;
+        A.padbits = b->pads[p] ? (uint8_t *)b->stage[TLB_STAGE_PADBITS] : nullptr; A.newlag = b->d_newlag;
         if (b->pads[p]) HIPCHK(tlk_slots((unsigned)((b->n_list[p] + 255) / 256), st, A));
         if (!b->work_clean) HIPCHK(hipMemsetAsync(b->d_work, 0, sizeof(int32_t) * TL_HEAD_STRIDE * 9, st));     // only after a launch that failed half way
         b->work_clean = false;
@@ -394,15 +393,15 @@ int tlb_encode_host_len(tlb_batch *b, const int16_t *pcm, int nframes, const uin
     const size_t slots = (size_t)nframes * (size_t)b->nstreams;
     const size_t n_pcm = slots * 2304 * sizeof(int16_t), n_out = slots * (size_t)b->out_stride;
     const bool with_xpad = xpad && xpad_len;
-    HIPCHK(stage_reserve(b, 0, n_pcm));
-    HIPCHK(stage_reserve(b, 1, n_out));
-    if (with_xpad) { HIPCHK(stage_reserve(b, 2, slots * TL_MAX_XPAD)); HIPCHK(stage_reserve(b, 3, slots * sizeof(int32_t))); }
-    if (taps) HIPCHK(stage_reserve(b, 4, slots * sizeof(TlTaps)));
-    if (out_len) HIPCHK(stage_reserve(b, 8, slots * sizeof(int32_t)));
-    int32_t *d_len = out_len ? (int32_t *)b->stage[8] : nullptr;
-    int16_t *d_pcm = (int16_t *)b->stage[0]; uint8_t *d_out = (uint8_t *)b->stage[1];
-    uint8_t *d_xpad = with_xpad ? (uint8_t *)b->stage[2] : nullptr; int32_t *d_xl = with_xpad ? (int32_t *)b->stage[3] : nullptr;
-    TlTaps *d_taps = taps ? (TlTaps *)b->stage[4] : nullptr;
+    HIPCHK(stage_reserve(b, TLB_STAGE_PCM, n_pcm));
+    HIPCHK(stage_reserve(b, TLB_STAGE_OUT, n_out));
+    if (with_xpad) { HIPCHK(stage_reserve(b, TLB_STAGE_XPAD, slots * TL_MAX_XPAD)); HIPCHK(stage_reserve(b, TLB_STAGE_XPAD_LEN, slots * sizeof(int32_t))); }
+    if (taps) HIPCHK(stage_reserve(b, TLB_STAGE_TAPS, slots * sizeof(TlTaps)));
+    if (out_len) HIPCHK(stage_reserve(b, TLB_STAGE_OUT_LEN, slots * sizeof(int32_t)));
+    int32_t *d_len = out_len ? (int32_t *)b->stage[TLB_STAGE_OUT_LEN] : nullptr;
+    int16_t *d_pcm = (int16_t *)b->stage[TLB_STAGE_PCM]; uint8_t *d_out = (uint8_t *)b->stage[TLB_STAGE_OUT];
+    uint8_t *d_xpad = with_xpad ? (uint8_t *)b->stage[TLB_STAGE_XPAD] : nullptr; int32_t *d_xl = with_xpad ? (int32_t *)b->stage[TLB_STAGE_XPAD_LEN] : nullptr;
+    TlTaps *d_taps = taps ? (TlTaps *)b->stage[TLB_STAGE_TAPS] : nullptr;
     // Big calls go through in up to four chunks of whole frames on three streams: while the kernels of chunk c run, chunk c+1
     // comes in over PCIe and chunk c-1 goes out (the link is full duplex; with pinned host buffers, tlb_host_alloc, the
     // copies run at link rate).  The kernels themselves stay in frame order on one stream -- the streams' state passes from
@@ -418,8 +417,8 @@ int tlb_encode_host_len(tlb_batch *b, const int16_t *pcm, int nframes, const uin
     }
     // TlPsyOut / ScF-CRC scratch sized for the largest chunk up front (tlb_launch would otherwise re-allocate between chunks)
     {
-        if (b->n_list[2]) HIPCHK(stage_reserve(b, 5, (size_t)per * (size_t)b->nstreams * sizeof(TlPsyOut)));
-        HIPCHK(stage_reserve(b, 6, (size_t)per * (size_t)b->nstreams * 4));
+        if (b->n_list[2]) HIPCHK(stage_reserve(b, TLB_STAGE_PSY_OUT, (size_t)per * (size_t)b->nstreams * sizeof(TlPsyOut)));
+        HIPCHK(stage_reserve(b, TLB_STAGE_SCFCRC, (size_t)per * (size_t)b->nstreams * 4));
     }
     HIPCHK(hipMemsetAsync(d_out, 0, n_out, b->s_in));              // bytes the kernels do not write (slot 0 of the first call, tails of short frames) read as 0
     if (taps) HIPCHK(hipMemsetAsync(d_taps, 0, slots * sizeof(TlTaps), b->s_in));
@@ -478,127 +477,6 @@ int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long l
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(stamps, d_st, slots * 32 * sizeof(long long), hipMemcpyDeviceToHost));
 
-    return rc;
-}
-
-int tlb_set_gain_db(tlb_batch *b, int stream, double gain_db)
-{   // const double linear_gain_correction = pow(10.0, gain_dB / 20.0);  (src/odr-audioenc.cpp:1032)
-    if (!b || stream < -1 || stream >= b->nstreams) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const double g = pow(10.0, gain_db / 20.0);
-    for (int s2 = 0; s2 < b->nstreams; s2++) if (stream < 0 || s2 == stream) b->h_gain[(size_t)s2] = g;
-    HIPCHK(hipMemcpy(b->d_gain, b->h_gain.data(), sizeof(double) * (size_t)b->nstreams, hipMemcpyHostToDevice));
-    return TLB_OK;
-}
-
-int tlb_ingest_device(tlb_batch *b, const int16_t *d_interleaved, int nframes, int16_t *d_pcm, int16_t *d_peaks, void *hip_stream)
-{
-    if (!b || !d_interleaved || !d_pcm || !d_peaks || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(tlk_ingest((unsigned)((size_t)nframes * (size_t)b->nstreams), (hipStream_t)hip_stream, d_interleaved, d_pcm, d_peaks, b->d_gain, b->d_configs, b->d_stream_cfg, b->nstreams));
-    return TLB_OK;
-}
-
-int tlb_ingest_host(tlb_batch *b, const int16_t *interleaved, int nframes, int16_t *pcm, int16_t *peaks)
-{   // device staging kept between calls, like tlb_encode_host (an application calls this once per chunk of frames)
-    if (!b || !interleaved || !pcm || !peaks || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    HIPCHK(stage_reserve(b, 9, slots * 2304 * 2));
-    HIPCHK(stage_reserve(b, 10, slots * 2304 * 2));
-    HIPCHK(stage_reserve(b, 11, slots * 2 * 2));
-    int16_t *d_in = (int16_t *)b->stage[9], *d_out = (int16_t *)b->stage[10], *d_pk = (int16_t *)b->stage[11];
-    HIPCHK(hipMemcpy(d_in, interleaved, slots * 2304 * 2, hipMemcpyHostToDevice));
-    int rc = tlb_ingest_device(b, d_in, nframes, d_out, d_pk, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pcm, d_out, slots * 2304 * 2, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(peaks, d_pk, slots * 2 * 2, hipMemcpyDeviceToHost));
-    return rc;
-}
-
-// Ingest with short reads (csrc/mp2_ingest.h): d_valid int32 [nframes][nstreams], the whole sample frames each slot delivers.  Without the
-// array this IS tlb_ingest_device -- the same kernel, the same launch.
-int tlb_ingest_device_valid(tlb_batch *b, const int16_t *d_interleaved, const int32_t *d_valid, int nframes, int16_t *d_pcm, int16_t *d_peaks, void *hip_stream)
-{
-    if (!d_valid) return tlb_ingest_device(b, d_interleaved, nframes, d_pcm, d_peaks, hip_stream);
-    if (!b || !d_interleaved || !d_pcm || !d_peaks || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(tlk_ingest_valid((unsigned)((size_t)nframes * (size_t)b->nstreams), (hipStream_t)hip_stream, d_interleaved, d_valid, d_pcm, d_peaks, b->d_gain, b->d_configs, b->d_stream_cfg, b->nstreams));
-    return TLB_OK;
-}
-
-int tlb_ingest_host_valid(tlb_batch *b, const int16_t *interleaved, const int32_t *valid, int nframes, int16_t *pcm, int16_t *peaks)
-{
-    if (!valid) return tlb_ingest_host(b, interleaved, nframes, pcm, peaks);
-    if (!b || !interleaved || !pcm || !peaks || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    HIPCHK(stage_reserve(b, 9, slots * 2304 * 2));
-    HIPCHK(stage_reserve(b, 10, slots * 2304 * 2));
-    HIPCHK(stage_reserve(b, 11, slots * 2 * 2));
-    int16_t *d_in = (int16_t *)b->stage[9], *d_out = (int16_t *)b->stage[10], *d_pk = (int16_t *)b->stage[11];
-    TlbMem m;
-    int32_t *d_valid = m.scratch<int32_t>(slots);
-    MEMCHK(m);
-    HIPCHK(hipMemcpy(d_in, interleaved, slots * 2304 * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_valid, valid, slots * sizeof(int32_t), hipMemcpyHostToDevice));
-    int rc = tlb_ingest_device_valid(b, d_in, d_valid, nframes, d_out, d_pk, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pcm, d_out, slots * 2304 * 2, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(peaks, d_pk, slots * 2 * 2, hipMemcpyDeviceToHost));
-    return rc;
-}
-
-// Underrun bookkeeping of the caller (src/odr-audioenc.cpp:919-935; tl_underrun_stream): the 60-second decision stays with the caller
-int tlb_underrun_device(tlb_batch *b, const int32_t *d_valid, int nframes, uint32_t *d_underrun_ms, uint32_t *d_underruns, void *hip_stream)
-{
-    if (!b || !d_valid || !d_underrun_ms || !d_underruns || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(tlk_underrun((unsigned)((b->nstreams + 255) / 256), (hipStream_t)hip_stream, d_valid, d_underrun_ms, d_underruns, b->d_configs, b->d_stream_cfg, b->nstreams, nframes));
-    return TLB_OK;
-}
-
-int tlb_underrun_host(tlb_batch *b, const int32_t *valid, int nframes, uint32_t *underrun_ms, uint32_t *underruns)
-{
-    if (!b || !valid || !underrun_ms || !underruns || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t slots = (size_t)nframes * (size_t)b->nstreams, n = (size_t)b->nstreams;
-    TlbMem m;
-    int32_t *d_v = m.scratch<int32_t>(slots); uint32_t *d_m = m.scratch<uint32_t>(n), *d_n = m.scratch<uint32_t>(n);
-    MEMCHK(m);
-    HIPCHK(hipMemcpy(d_v, valid, slots * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_m, underrun_ms, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_n, underruns, sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    int rc = tlb_underrun_device(b, d_v, nframes, d_m, d_n, nullptr);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(underrun_ms, d_m, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(underruns, d_n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-    return rc;
-}
-
-int tlb_silence_device(tlb_batch *b, const int16_t *d_peaks, int nframes, uint32_t *d_silence_ms, void *hip_stream)
-{
-    if (!b || !d_peaks || !d_silence_ms || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(tlk_silence((unsigned)((b->nstreams + 255) / 256), (hipStream_t)hip_stream, d_peaks, d_silence_ms, b->d_configs, b->d_stream_cfg, b->nstreams, nframes));
-    return TLB_OK;
-}
-
-int tlb_silence_host(tlb_batch *b, const int16_t *peaks, int nframes, uint32_t *silence_ms)
-{
-    if (!b || !peaks || !silence_ms || nframes <= 0) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-    TlbMem m;
-    int16_t *d_p = m.scratch<int16_t>(slots * 2); uint32_t *d_m = m.scratch<uint32_t>((size_t)b->nstreams);
-    MEMCHK(m);
-    HIPCHK(hipMemcpy(d_p, peaks, slots * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_m, silence_ms, sizeof(uint32_t) * (size_t)b->nstreams, hipMemcpyHostToDevice));
-    int rc = tlb_silence_device(b, d_p, nframes, d_m, nullptr);
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(silence_ms, d_m, sizeof(uint32_t) * (size_t)b->nstreams, hipMemcpyDeviceToHost);
-
-    if (e != hipSuccess) return TLB_ERR_HIP;
     return rc;
 }
 

@@ -19,6 +19,15 @@
 static_assert(TL_MAX_XPAD == TLB_MAX_XPAD, "xpad record size");
 #define TLB_HOST_CHUNKS 4            // tlb_encode_host pipelines a big call in this many chunks of frames
 
+// the staging slots of tlb_batch::stage
+enum TlbStage {
+    TLB_STAGE_PCM, TLB_STAGE_OUT, TLB_STAGE_XPAD, TLB_STAGE_XPAD_LEN, TLB_STAGE_TAPS,      // tlb_encode_host: what the caller's buffers are copied to and from
+    TLB_STAGE_PSY_OUT, TLB_STAGE_SCFCRC, TLB_STAGE_PADBITS,                                // tlb_launch: TlPsyOut records (models 2/4), ScF-CRC bytes, padding bits
+    TLB_STAGE_OUT_LEN,                                                                     // tlb_encode_host_len: frame lengths
+    TLB_STAGE_INGEST_IN, TLB_STAGE_INGEST_OUT, TLB_STAGE_INGEST_PEAKS,                     // tlb_ingest_host: interleaved in, planar out, peaks
+    TLB_STAGE_COUNT
+};
+
 struct tlb_batch {
     int device = 0, nstreams = 0, out_stride = 0;
     long frames = 0;
@@ -53,8 +62,8 @@ struct tlb_batch {
     bool timed = false;
     // device staging of the host-buffer entry point (tlb_encode_host): grow-only, created on first use, so a caller that
     // feeds one frame per call (the legacy shim) pays for no allocation after its first frame
-    void *stage[12] = {};                        // pcm, out, xpad, xpad_len, taps; [5] = TlPsyOut records (models 2/4), [6] = ScF-CRC bytes, [7] = padding bits, [8] = frame lengths (host entry); [9..11] = tlb_ingest_host: interleaved in, planar out, peaks
-    size_t stage_cap[12] = {};
+    void *stage[TLB_STAGE_COUNT] = {};
+    size_t stage_cap[TLB_STAGE_COUNT] = {};
     hipStream_t s_in = nullptr, s_run = nullptr, s_out = nullptr;   // host-buffer entry point: copy-in / kernels / copy-out
     hipEvent_t ev_in[TLB_HOST_CHUNKS] = {}, ev_run[TLB_HOST_CHUNKS] = {};
     uint32_t *d_newpend = nullptr;               // split path: the launch's last frame of every stream
@@ -113,7 +122,7 @@ struct tlb_batch {
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
 };
 
-static inline hipError_t stage_reserve(tlb_batch *b, int k, size_t bytes)
+static inline hipError_t stage_reserve(tlb_batch *b, TlbStage k, size_t bytes)
 {
     if (b->stage_cap[k] >= bytes) return hipSuccess;
     if (b->stage[k]) { (void)hipFree(b->stage[k]); b->stage[k] = nullptr; b->stage_cap[k] = 0; }

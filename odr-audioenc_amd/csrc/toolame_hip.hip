@@ -1,6 +1,6 @@
-// toolame_hip.hip -- the gfx950 kernels of the library and their launchers (tl_kernels.h).  The C-ABI of include/toolame_batch.h lives in
-// tlb_batch.cpp (batches), tlb_egress.cpp (ZeroMQ / EDI / PFT), tlb_tick.cpp (the real-time tick), tlb_node.cpp (all GPUs of a host) and
-// toolame_legacy.cpp (the reference's nine functions).
+// toolame_hip.hip -- the encode path: the gfx950 kernels that take PCM to frame bytes (slots, main, frame, finish, flush; the psy-2 kernel
+// is toolame_psy2.hip) and their launchers (tl_kernels.h).  The kernels of everything around the path are units of their own (csrc/Makefile,
+// KERNEL_UNITS); the C-ABI of include/toolame_batch.h lives in the host units (HOST_UNITS: tlb_batch.cpp has the launch of this path).
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared (see csrc/Makefile).
 // -ffp-contract=off is load-bearing: the reference is built -std=c99 (no FMA contraction,
@@ -14,8 +14,6 @@
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
 #include "mp2_wave.h"
-#include "edi_af.h"
-#include "edi_pft.h"
 #include "tl_kernel_util.h"
 #include "tl_kernels.h"
 
@@ -86,26 +84,13 @@ static_assert((sizeof(TlMainShared) + TL_MAIN_WAVES * sizeof(TlMainLds) + TL_LDS
 // PAIRS: the list contains mono streams that share waves in pairs (TlLaunch::partner, tl_encode_pair).  A second instantiation, so
 // that the kernel of lists without pairs -- every all-stereo batch -- carries none of the pair code (with it inline the register
 // allocation of the stereo path moved from 152 to 168 VGPRs and psy-1 stereo lost 1.1 %).
+static_assert(sizeof(TlPackTables) % 8 == 0, "copied as doubles");
 template <int PSY, bool PAIRS, int NCH = 0>     // 0: model 0 (no psy kernel); 2: models 2 and 4 (after tl_psy2_kernel); NCH = 2: a list of two-channel streams only (as tl_frame_kernel)
 __global__ void __launch_bounds__(64 * TL_MAIN_WAVES) __attribute__((amdgpu_waves_per_eu(TL_MAIN_WPE, TL_MAIN_WPE))) tl_main_kernel(TlLaunch A)
 {
     __shared__ TlMainShared sh;
     __shared__ TlMainLds lds[TL_MAIN_WAVES];
-    {
-        const double *src = (const double *)&A.tables->shared.scalefactor[0];
-        double *dst = (double *)&sh.bytes[0];
-        for (int i = (int)threadIdx.x; i < (int)(sizeof(sh.bytes) / 8); i += 64 * TL_MAIN_WAVES) dst[i] = src[i];
-        for (int i = (int)threadIdx.x; i < 512; i += 64 * TL_MAIN_WAVES) sh.enw_s[i] = A.tables->enwindow_s[i];
-        static_assert(sizeof(TlPackTables) % 8 == 0, "copied as doubles");
-        for (int i = (int)threadIdx.x; i < (int)(sizeof(TlPackTables) / 8); i += 64 * TL_MAIN_WAVES) ((double *)&sh.pack)[i] = ((const double *)&A.tables->pack)[i];
-    }
-    __syncthreads();
-    // the encode path never touches B->dbtable: a TlBlockShared pointer whose dbtable part lies before the copied block
-    const TlBlockShared *B = (const TlBlockShared *)((const char *)&sh.bytes[0] - offsetof(TlBlockShared, scalefactor));
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int grp = (int)blockIdx.x & 7;
-    int wave_v = (int)(threadIdx.x >> 6);
-    asm volatile("" : "+v"(wave_v));
+    TL_ENCODE_PROLOGUE(sh, A.tables, (void)0);
     TlMainLds &wl = lds[wave_v];
     for (int hop = 0, k, f, first = ((int)blockIdx.x >> 3) * TL_MAIN_WAVES + wave; tl_take_unit(A.work + TL_HEAD_STRIDE, A.nlist, A.nframes, grp, hop, k, f, first); first = -1) {
         const int s = A.stream_list ? __builtin_amdgcn_readfirstlane(A.stream_list[k]) : k;      // no list: the launch's streams are ALL streams, position = id (one round trip to L2 less per unit)
@@ -132,20 +117,7 @@ __global__ void __launch_bounds__(64 * TL_MAIN_WAVES) __attribute__((amdgpu_wave
     __shared__ __attribute__((aligned(16))) double dbt[1258];     // dB-sum table + glibc's log table (TlTables::dblog)
     __shared__ TlMainShared sh;
     __shared__ TlFrameLds lds[TL_MAIN_WAVES];
-    {
-        for (int i = (int)threadIdx.x; i < 1258; i += 64 * TL_MAIN_WAVES) dbt[i] = A.tables->dblog[i];
-        const double *src = (const double *)&A.tables->shared.scalefactor[0];
-        double *dst = (double *)&sh.bytes[0];
-        for (int i = (int)threadIdx.x; i < (int)(sizeof(sh.bytes) / 8); i += 64 * TL_MAIN_WAVES) dst[i] = src[i];
-        for (int i = (int)threadIdx.x; i < 512; i += 64 * TL_MAIN_WAVES) sh.enw_s[i] = A.tables->enwindow_s[i];
-        for (int i = (int)threadIdx.x; i < (int)(sizeof(TlPackTables) / 8); i += 64 * TL_MAIN_WAVES) ((double *)&sh.pack)[i] = ((const double *)&A.tables->pack)[i];
-    }
-    __syncthreads();
-    const TlBlockShared *B = (const TlBlockShared *)((const char *)&sh.bytes[0] - offsetof(TlBlockShared, scalefactor));
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int grp = (int)blockIdx.x & 7;
-    int wave_v = (int)(threadIdx.x >> 6);
-    asm volatile("" : "+v"(wave_v));
+    TL_ENCODE_PROLOGUE(sh, A.tables, for (int i = (int)threadIdx.x; i < 1258; i += 64 * TL_MAIN_WAVES) dbt[i] = A.tables->dblog[i]);
     TlFrameLds &wl = lds[wave_v];
     for (int hop = 0, k, f, first = ((int)blockIdx.x >> 3) * TL_MAIN_WAVES + wave; tl_take_unit(A.work + TL_HEAD_STRIDE, A.nlist, A.nframes, grp, hop, k, f, first); first = -1) {
         const int s = A.stream_list ? __builtin_amdgcn_readfirstlane(A.stream_list[k]) : k;      // no list: the launch's streams are ALL streams, position = id (one round trip to L2 less per unit)
@@ -180,128 +152,6 @@ __global__ void __launch_bounds__(256) tl_finish_kernel(TlLaunch A)
     const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
     if (k >= A.nlist) return;
     tl_finish_stream(A, A.stream_list ? __builtin_amdgcn_readfirstlane(A.stream_list[k]) : k);
-}
-
-// Ingest glue of the caller (src/odr-audioenc.cpp:1030-1051 gain + peak, :1139-1152
-// de-interleave): interleaved s16le -> planar [2][1152], optional linear gain with the reference's
-// double-multiply-and-truncate, positive peak per channel.  Pure streaming kernel: 16 B loads, 8 B stores.
-// in  [nframes][nstreams][2304] int16 (L R L R ...; mono streams use the first 1152 values)
-// out [nframes][nstreams][2][1152] int16, peaks [nframes][nstreams][2] int16
-__global__ void __launch_bounds__(256) tl_ingest_kernel(const int16_t *__restrict__ in, int16_t *__restrict__ out,
-                                                       int16_t *__restrict__ peaks, const double *__restrict__ gain,
-                                                       const TlConfig *configs, const int32_t *stream_cfg, int nstreams)
-{
-    const size_t slot = blockIdx.x;
-    const int s = (int)(slot % (size_t)nstreams);
-    const int nch = configs[stream_cfg[s]].nch;
-    const double g = gain[s];
-    const int16_t *src = in + slot * 2304;
-    int16_t *dst = out + slot * 2304;
-    int pk0 = 0, pk1 = 0;
-    // the level loop of the reference always walks the buffer as L/R pairs, also in mono (odr-audioenc.cpp:1034-1051)
-    const int nquads = nch == 2 ? 288 : 144;                    // 16 bytes = 4 L/R pairs per step
-    for (int q = (int)threadIdx.x; q < nquads; q += 256) {
-        const uint4 v = ((const uint4 *)src)[q];
-        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
-        int16_t l[4], r[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            int a = (int16_t)(w4[k] & 0xffff), b = (int16_t)(w4[k] >> 16);
-            if (g != 1.0) { a = (int16_t)(int)((double)a * g); b = (int16_t)(int)((double)b * g); }
-            l[k] = (int16_t)a; r[k] = (int16_t)b;
-            pk0 = a > pk0 ? a : pk0; pk1 = b > pk1 ? b : pk1;
-        }
-        if (nch == 2) {
-            ((uint2 *)dst)[q] = make_uint2((uint16_t)l[0] | ((uint32_t)(uint16_t)l[1] << 16), (uint16_t)l[2] | ((uint32_t)(uint16_t)l[3] << 16));
-            ((uint2 *)(dst + 1152))[q] = make_uint2((uint16_t)r[0] | ((uint32_t)(uint16_t)r[1] << 16), (uint16_t)r[2] | ((uint32_t)(uint16_t)r[3] << 16));
-        } else {                                                 // mono: consecutive samples, channel 0 only
-            ((uint4 *)dst)[q] = make_uint4((uint16_t)l[0] | ((uint32_t)(uint16_t)r[0] << 16), (uint16_t)l[1] | ((uint32_t)(uint16_t)r[1] << 16),
-                                           (uint16_t)l[2] | ((uint32_t)(uint16_t)r[2] << 16), (uint16_t)l[3] | ((uint32_t)(uint16_t)r[3] << 16));
-        }
-    }
-    if (nch == 1) for (int q = (int)threadIdx.x; q < 288; q += 256) ((uint2 *)(dst + 1152))[q] = make_uint2(0u, 0u);
-    __shared__ int red[2][4];
-    for (int o = 32; o; o >>= 1) { int t0 = __shfl_xor(pk0, o, 64), t1 = __shfl_xor(pk1, o, 64); pk0 = t0 > pk0 ? t0 : pk0; pk1 = t1 > pk1 ? t1 : pk1; }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = pk0; red[1][threadIdx.x >> 6] = pk1; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        int m = red[threadIdx.x][0];
-        for (int k = 1; k < 4; k++) m = red[threadIdx.x][k] > m ? red[threadIdx.x][k] : m;
-        peaks[slot * 2 + threadIdx.x] = (int16_t)m;
-    }
-}
-
-// Silence accounting of the caller (src/odr-audioenc.cpp:1053-1079): a frame whose peaks are both 0
-// adds its duration (integer milliseconds, as the reference computes it) to the stream's counter, any other frame resets it.
-// One thread per stream, frames in order.
-__constant__ int32_t tl_fs_hz[2][3] = {{22050, 24000, 16000}, {44100, 48000, 32000}};     // [MPEG version][sampling_frequency index], common.c:118-144
-__global__ void __launch_bounds__(256) tl_silence_kernel(const int16_t *__restrict__ peaks, uint32_t *__restrict__ silence_ms, const TlConfig *configs,
-                                                          const int32_t *stream_cfg, int nstreams, int nframes)
-{
-    const int s = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (s >= nstreams) return;
-    const TlConfig &c = configs[stream_cfg[s]];
-    const unsigned long rate = (unsigned long)tl_fs_hz[c.version][c.fs_idx], nch = (unsigned long)c.nch;
-    const uint32_t frame_ms = (uint32_t)(1000ul * (1152ul * 2ul * nch) / (2ul * nch * rate));
-    uint32_t ms = silence_ms[s];
-    for (int f = 0; f < nframes; f++) {
-        const size_t slot = (size_t)f * (size_t)nstreams + (size_t)s;
-        const int pl = peaks[slot * 2], pr = peaks[slot * 2 + 1];
-        ms = (pl > pr ? pl : pr) == 0 ? ms + frame_ms : 0u;
-    }
-    silence_ms[s] = ms;
-}
-
-// ZeroMQ wire format of the step after the path (src/Outputs.h:76-99, Outputs.cpp:101-138):
-// packed header {u16 version=1, u16 encoder=2 (MPEG L2), u32 datasize, i16 level_left, i16 level_right} + the unit's bytes.
-// One message per UNIT of 3 * bitrate bytes (src/odr-audioenc.cpp:1211-1219): message slot v = f * max_upf + u carries bytes
-// [u * unit, (u + 1) * unit) of frame f; a stream with fewer units per frame leaves its surplus slots empty (datasize 0 in an
-// all-zero header).  msgs [nframes * max_upf][nstreams][msg_stride]; one block per slot.
-__global__ void tl_zmq_frame_kernel(const uint8_t *__restrict__ frames, const int16_t *__restrict__ peaks, uint8_t *__restrict__ msgs,
-                                    const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int out_stride, int msg_stride, int max_upf,
-                                    const int32_t *__restrict__ frame_len)
-{
-    const size_t pslot = blockIdx.x;
-    const int s = (int)(pslot % (size_t)nstreams), v = (int)(pslot / (size_t)nstreams), f = v / max_upf, u = v - f * max_upf;
-    const size_t slot = (size_t)f * (size_t)nstreams + (size_t)s;
-    const TlConfig &c = configs[stream_cfg[s]];
-    const int n = 3 * c.kbps, upf = c.frame_bytes / n;
-    uint8_t *m = msgs + pslot * (size_t)msg_stride;
-    if (u >= upf || (frame_len && frame_len[slot] == 0)) { if (threadIdx.x < 3) ((uint32_t *)m)[threadIdx.x] = 0u; return; }   // no unit here / no frame in this slot
-    if (threadIdx.x < 3) {
-        const int pl = peaks ? peaks[slot * 2] : 0, pr = peaks ? peaks[slot * 2 + 1] : 0;
-        const uint32_t w = threadIdx.x == 0 ? (1u | (2u << 16)) : threadIdx.x == 1 ? (uint32_t)n
-                                            : ((uint32_t)(uint16_t)pl | ((uint32_t)(uint16_t)pr << 16));
-        ((uint32_t *)m)[threadIdx.x] = w;
-    }
-    const uint32_t *src = (const uint32_t *)(frames + slot * (size_t)out_stride + (size_t)u * n);      // unit sizes are multiples of 4
-    for (int i = (int)threadIdx.x; i < (n >> 2); i += (int)blockDim.x) ((uint32_t *)m)[3 + i] = src[i];
-}
-
-// EDI AF packets of the step after the path (EDI part; csrc/edi_af.h): one wavefront per packet,
-// blockIdx.y = packet slot (frame * max_upf + unit) of the call, four streams per workgroup.
-__global__ void __launch_bounds__(256) tl_edi_af_kernel(TlEdiArgs A)
-{
-    const int s = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    if (s >= A.nstreams) return;
-    tl_edi_af_packet(A, s, (int)blockIdx.y);      // blockIdx.y = packet slot
-}
-
-// EDI PFT layer (csrc/edi_pft.h): one wavefront per AF packet, blockIdx.y = frame of the call.  The Reed-Solomon tables
-// (11 KB) are copied into LDS once per workgroup: the encoder's look-ups are dependent and must not go to global memory.
-__global__ void __launch_bounds__(256) tl_edi_pft_kernel(TlPftArgs A, const TlTables *T)
-{
-    __shared__ uint8_t s_log[256], s_exp[512], s_mlog[207 * TL_PFT_PARITY];
-    __shared__ TlPftScratch scratch[4];
-    for (int i = (int)threadIdx.x; i < 256; i += 256) s_log[i] = T->rs_log[i];
-    for (int i = (int)threadIdx.x; i < 512; i += 256) s_exp[i] = T->rs_exp[i];
-    for (int i = (int)threadIdx.x; i < 207 * TL_PFT_PARITY; i += 256) s_mlog[i] = (&T->rs_mlog[0][0])[i];
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int s = (int)blockIdx.x * 4 + wave;
-    if (s >= A.nstreams) return;
-    const TlPftTables R = {s_log, s_exp, s_mlog};
-    tl_edi_pft_packet(A, R, s, (int)blockIdx.y, scratch[wave]);
 }
 
 // pending frame (big-endian words in the stream state) -> bytes
@@ -344,23 +194,6 @@ hipError_t tlk_main(int psy, bool pairs, bool stereo, unsigned blocks, hipStream
 }
 hipError_t tlk_psy2(unsigned blocks, hipStream_t st, const TlLaunch &A) { TLK_GO(tl_psy2_kernel, dim3(blocks), dim3(64 * TL_PSY2_WAVES), 0, st, A); }
 hipError_t tlk_finish(unsigned blocks, hipStream_t st, const TlLaunch &A) { TLK_GO(tl_finish_kernel, dim3(blocks), dim3(256), 0, st, A); }
-hipError_t tlk_ingest(unsigned blocks, hipStream_t st, const int16_t *in, int16_t *out, int16_t *peaks, const double *gain,
-                      const TlConfig *configs, const int32_t *stream_cfg, int nstreams)
-{
-    TLK_GO(tl_ingest_kernel, dim3(blocks), dim3(256), 0, st, in, out, peaks, gain, configs, stream_cfg, nstreams);
-}
-hipError_t tlk_silence(unsigned blocks, hipStream_t st, const int16_t *peaks, uint32_t *silence_ms, const TlConfig *configs,
-                       const int32_t *stream_cfg, int nstreams, int nframes)
-{
-    TLK_GO(tl_silence_kernel, dim3(blocks), dim3(256), 0, st, peaks, silence_ms, configs, stream_cfg, nstreams, nframes);
-}
-hipError_t tlk_zmq_frame(unsigned blocks, hipStream_t st, const uint8_t *frames, const int16_t *peaks, uint8_t *msgs, const TlConfig *configs,
-                         const int32_t *stream_cfg, int nstreams, int out_stride, int msg_stride, int max_upf, const int32_t *frame_len)
-{
-    TLK_GO(tl_zmq_frame_kernel, dim3(blocks), dim3(128), 0, st, frames, peaks, msgs, configs, stream_cfg, nstreams, out_stride, msg_stride, max_upf, frame_len);
-}
-hipError_t tlk_edi_af(unsigned bx, unsigned by, hipStream_t st, const TlEdiArgs &A) { TLK_GO(tl_edi_af_kernel, dim3(bx, by), dim3(256), 0, st, A); }
-hipError_t tlk_edi_pft(unsigned bx, unsigned by, hipStream_t st, const TlPftArgs &A, const TlTables *T) { TLK_GO(tl_edi_pft_kernel, dim3(bx, by), dim3(256), 0, st, A, T); }
 hipError_t tlk_flush(unsigned blocks, hipStream_t st, const TlStreamState *state, const TlConfig *configs, const int32_t *stream_cfg,
                      uint8_t *out, int32_t *out_len, int nstreams, int out_stride)
 {

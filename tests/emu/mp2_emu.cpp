@@ -37,7 +37,7 @@ void *emu_create(int nstreams, const long *fs, const char *mode, const int *kbps
     e->state.resize(nstreams);
     memset(e->state.data(), 0, sizeof(TlStreamState) * nstreams);
     for (int s = 0; s < nstreams; s++) {
-        // one TlConfig per DISTINCT configuration, as the device batch keeps them (toolame_hip.hip tlb_create): mono streams pair up by config index
+        // one TlConfig per DISTINCT configuration, as the device batch keeps them (tlb_batch.cpp tlb_create, tlb_plan.h): mono streams pair up by config index
         int ci = -1;
         for (int t = 0; t < s && ci < 0; t++)
             if (fs[t] == fs[s] && mode[t] == mode[s] && kbps[t] == kbps[s] && psy[t] == psy[s] && pad[t] == pad[s]) ci = e->stream_cfg[t];
@@ -124,7 +124,7 @@ int emu_encode_len(void *h, const int16_t *pcm, int nframes, const uint8_t *xpad
         }
     }
     if (pads) for (int s = 0; s < A.nstreams; s++) tl_slots_stream(A, s);
-    // mono streams of one configuration share waves in pairs, as the device path pairs them (toolame_hip.hip batch_build_lists)
+    // mono streams of one configuration share waves in pairs, as the device path pairs them (tlb_batch.cpp batch_build_lists, tlb_plan.h)
     std::vector<int32_t> partner((size_t)A.nstreams, -1);
     {
         std::vector<int> open(e->configs.size(), -1);

@@ -1,6 +1,6 @@
-// mp2_ingest_emu.cpp -- TEST-ONLY host emulation of the ingest kernels with short reads (csrc/mp2_ingest.h compiled with -DTL_EMULATE:
+// mp2_ingest_emu.cpp -- TEST-ONLY host emulation of the kernels of the caller's glue (csrc/mp2_ingest.h compiled with -DTL_EMULATE:
 // every lane region is a loop over 64 lanes, a slot's workgroup a loop over its waves).  tests/ingestlib.py compiles it into a temporary
-// directory; the product library never contains or loads it.  The entry points mirror tlb_ingest_host_valid / tlb_underrun_host.
+// directory; the product library never contains or loads it.  The entry points mirror tlb_ingest_host_valid / tlb_underrun_host / tlb_silence_host.
 #define TL_EMULATE 1
 #include <math.h>
 #include <stdlib.h>
@@ -36,6 +36,14 @@ int ing_underrun(const int32_t *valid, int nframes, int nstreams, const int32_t 
     if (!valid || !underrun_ms || !underruns || nframes <= 0 || nstreams <= 0) return 18;
     for (int s = nstreams - 1; s >= 0; s--)
         tl_underrun_stream(valid, underrun_ms, underruns, tl_frame_ms(version[s], fs_idx[s], nch[s]), s, nstreams, nframes);
+    return 0;
+}
+// peaks [nframes][nstreams][2]; version / fs_idx / nch as above; the counter [nstreams], read-modify-write
+int ing_silence(const int16_t *peaks, int nframes, int nstreams, const int32_t *version, const int32_t *fs_idx, const int32_t *nch, uint32_t *silence_ms)
+{
+    if (!peaks || !silence_ms || nframes <= 0 || nstreams <= 0) return 18;
+    for (int s = nstreams - 1; s >= 0; s--)
+        tl_silence_stream(peaks, silence_ms, tl_frame_ms(version[s], fs_idx[s], nch[s]), s, nstreams, nframes);
     return 0;
 }
 int ing_src(int i, int valid)

@@ -1,6 +1,6 @@
-"""Support for the short-read tests (test_short_reads_emu.py, test_short_reads_gpu.py): the emulation of the ingest kernels with short
-reads (tests/emu/mp2_ingest_emu.cpp, compiled into a temporary directory) and a numpy statement of the three cases of
-include/toolame_batch.h (tlb_ingest_device_valid)."""
+"""Support for the short-read tests (test_short_reads_emu.py, test_short_reads_gpu.py): the emulation of the kernels of the caller's glue
+(tests/emu/mp2_ingest_emu.cpp, compiled into a temporary directory), a numpy statement of the three cases of include/toolame_batch.h
+(tlb_ingest_device_valid) and the two counters as plain loops."""
 import ctypes as C
 import math
 import subprocess
@@ -32,6 +32,7 @@ class IngestEmu:
         L = self.L = C.CDLL(str(so))
         L.ing_ingest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ing_underrun.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ing_silence.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ing_src.argtypes = [C.c_int, C.c_int]
 
     def ingest(self, inter, valid, nch, gains_db):
@@ -59,6 +60,17 @@ class IngestEmu:
         nc = np.ascontiguousarray(nch, dtype=np.int32)
         assert underrun_ms.dtype == np.uint32 and underruns.dtype == np.uint32 and underrun_ms.shape == (ns,) and underruns.shape == (ns,)
         rc = self.L.ing_underrun(v.ctypes.data, nf, ns, ver.ctypes.data, fsi.ctypes.data, nc.ctypes.data, underrun_ms.ctypes.data, underruns.ctypes.data)
+        assert rc == 0, rc
+
+    def silence(self, peaks, rates, nch, silence_ms):
+        """one call over peaks [nf][ns][2] int16; the uint32 [ns] array is updated in place"""
+        pk = np.ascontiguousarray(peaks, dtype=np.int16)
+        nf, ns = pk.shape[:2]
+        assert pk.shape == (nf, ns, 2) and silence_ms.dtype == np.uint32 and silence_ms.shape == (ns,)
+        ver = np.array([FS_IDX[r][0] for r in rates], dtype=np.int32)
+        fsi = np.array([FS_IDX[r][1] for r in rates], dtype=np.int32)
+        nc = np.ascontiguousarray(nch, dtype=np.int32)
+        rc = self.L.ing_silence(pk.ctypes.data, nf, ns, ver.ctypes.data, fsi.ctypes.data, nc.ctypes.data, silence_ms.ctypes.data)
         assert rc == 0, rc
 
 
@@ -133,6 +145,41 @@ def underrun_python(valid, rates, ms0, n0):
             else:
                 ms[s] = 0
     return ms, n
+
+
+def silence_python(peaks, rates, ms0):
+    """a frame whose peaks are both 0 adds its whole milliseconds, any other frame resets the counter (src/odr-audioenc.cpp:1053-1079)"""
+    ms = [int(x) for x in ms0]
+    for f in range(peaks.shape[0]):
+        for s in range(peaks.shape[1]):
+            ms[s] = ms[s] + frame_ms(rates[s]) if max(int(peaks[f, s, 0]), int(peaks[f, s, 1])) == 0 else 0
+    return ms
+
+
+# the batch of the silence tests (test_short_reads_emu.py, test_hip_parity.py): every rate with two channels and with one, 16 frames fed in
+# these cuts, counters that do not start at 0.  Streams in fours, by column: always silent; never silent; silent but for the last frame;
+# silent but for peaks (0, 3) once in the middle
+SILENCE_RATES = [48000, 32000, 24000, 16000, 44100, 22050]
+SILENCE_CUTS = (1, 7, 3, 2, 1, 2)
+
+
+def silence_case():
+    """-> (rates [12], nch [12], peaks [16][12][2] int16, start [12] uint32)"""
+    rates = SILENCE_RATES + SILENCE_RATES
+    nch = [2] * 6 + [1] * 6
+    nf, ns = sum(SILENCE_CUTS), len(rates)
+    rng = np.random.default_rng(1053)
+    peaks = np.zeros((nf, ns, 2), dtype=np.int16)
+    for s in range(ns):
+        col = s % 4
+        if col == 1:
+            peaks[:, s] = rng.integers(1, 32768, size=(nf, 2))
+        elif col == 2:
+            peaks[-1, s] = (int(rng.integers(1, 32768)), 0)
+        elif col == 3:
+            peaks[nf // 2, s] = (0, 3)
+    start = (1000 + 7 * np.arange(ns)).astype(np.uint32)
+    return rates, nch, peaks, start
 
 
 def fixture():

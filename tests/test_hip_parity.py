@@ -730,6 +730,39 @@ def test_ingest_gain_peak_deinterleave(M):
     b.close()
 
 
+def test_silence_every_rate(M):
+    """the silence counter on the device at all six rates with two channels and with one (ingestlib.silence_case: counters that do not
+    start at 0, ragged calls), against the oracle's mp2o_silence_ms frame by frame"""
+    import ctypes as C
+    import ingestlib as I
+    import sweeplib as SW
+    rates, nch, peaks, start = I.silence_case()
+    legal = SW.legal_configs()
+    cfgs = []
+    for fs, n in zip(rates, nch):
+        mode = "m" if n == 1 else "s"
+        kbps = next(k for r, m, k in legal if r == fs and m == mode)
+        cfgs.append(M.StreamConfig(samplerate=fs, mode=mode, bitrate=kbps))
+    L = O.lib()
+    nf, ns = peaks.shape[:2]
+    want = np.zeros((nf + 1, ns), dtype=np.uint32)                   # want[f]: the counters before frame f
+    want[0] = start
+    for f in range(nf):
+        for s in range(ns):
+            want[f + 1, s] = L.mp2o_silence_ms(int(want[f, s]), np.ascontiguousarray(peaks[f, s]).ctypes.data, nch[s], rates[s])
+    b = M.Batch(cfgs)
+    HL = M.load_library()
+    HL.tlb_silence_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    ms, pos = start.copy(), 0
+    for cut in I.SILENCE_CUTS:
+        assert HL.tlb_silence_host(b.h, np.ascontiguousarray(peaks[pos:pos + cut]).ctypes.data, cut, ms.ctypes.data) == 0
+        pos += cut
+        assert np.array_equal(ms, want[pos]), (pos, ms, want[pos])
+    assert pos == nf and I.silence_python(peaks, rates, start) == [int(x) for x in ms]
+    assert ms[0] == int(start[0]) + nf * 24 and ms[4] == int(start[4]) + nf * 26 and ms[1] == 0      # 48 kHz and 44.1 kHz always silent, 32 kHz never
+    b.close()
+
+
 def test_zmq_frame_header(M):
     """SURVEY 8f N2 (ZeroMQ part): struct zmq_frame_header_t + frame, src/Outputs.h:76-89, Outputs.cpp:101-138."""
     import ctypes as C

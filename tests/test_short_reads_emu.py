@@ -1,7 +1,7 @@
 """Ingest with short reads (csrc/mp2_ingest.h) on the lane-loop emulation, without a GPU: against the output of the reference's own
 expand_missing_samples on a ramp (tests/golden/short_reads.npz), against a numpy statement of the three cases on random PCM with junk
-behind `valid`, against the existing ingest path where every read is full, and the underrun counters against a plain loop.  The emulation
-library is compiled by this module into a temporary directory."""
+behind `valid`, against the existing ingest path where every read is full, the underrun counters against a plain loop and the silence
+counter against the oracle.  The emulation library is compiled by this module into a temporary directory."""
 import ctypes as C
 import re
 import shutil
@@ -157,6 +157,40 @@ def test_underrun_counters(emu, rate):
     one_ms, one_n = np.zeros(ns, np.uint32), np.zeros(ns, np.uint32)
     emu.underrun(valid, rates, nch, one_ms, one_n)
     assert np.array_equal(one_ms, ms) and np.array_equal(one_n, n)
+
+
+def test_silence_counter_every_rate(emu):
+    """the silence counter (tl_silence_stream, what tl_silence_kernel runs) against the oracle's mp2o_silence_ms frame by frame: all six
+    rates with two channels and with one, counters that do not start at 0, in ragged calls and one frame a call"""
+    L = O.lib()
+    rates, nch, peaks, start = I.silence_case()
+    nf, ns = peaks.shape[:2]
+    want = np.zeros((nf + 1, ns), dtype=np.uint32)                   # want[f]: the counters before frame f
+    want[0] = start
+    for f in range(nf):
+        for s in range(ns):
+            want[f + 1, s] = L.mp2o_silence_ms(int(want[f, s]), np.ascontiguousarray(peaks[f, s]).ctypes.data, nch[s], rates[s])
+    assert [int(x) for x in want[nf]] == I.silence_python(peaks, rates, start)
+    ms, pos = start.copy(), 0
+    for cut in I.SILENCE_CUTS:
+        emu.silence(peaks[pos:pos + cut], rates, nch, ms)
+        pos += cut
+        assert np.array_equal(ms, want[pos]), pos
+    assert pos == nf
+    ms = start.copy()
+    for f in range(nf):
+        emu.silence(peaks[f:f + 1], rates, nch, ms)
+        assert np.array_equal(ms, want[f + 1]), f
+    # the columns: always silent, never silent, one frame with audio last, peaks (0, 3) once in the middle
+    per = [int(L.mp2o_silence_ms(0, np.zeros(2, np.int16).ctypes.data, nch[s], rates[s])) for s in range(ns)]
+    for s in range(ns):
+        col = s % 4
+        assert ms[s] == (int(start[s]) + nf * per[s], 0, 0, (nf - 1 - nf // 2) * per[s])[col], s
+        step = np.zeros(1, np.uint32)
+        emu.silence(np.zeros((1, 1, 2), np.int16), rates[s:s + 1], nch[s:s + 1], step)
+        assert step[0] == per[s], s
+        if rates[s] != 22050:                                        # 22.05 kHz: whatever the oracle returns
+            assert per[s] == {48000: 24, 32000: 36, 24000: 48, 16000: 72, 44100: 26}[rates[s]], s
 
 
 def test_new_symbols_are_declared_exported_and_loadable():

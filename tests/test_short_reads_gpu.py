@@ -1,6 +1,6 @@
 """Ingest with short reads on the GPU (csrc/toolame_ingest.hip, tlb_tick_* / tlb_node_* with short reads enabled): the device against the
-lane-loop emulation byte for byte, a tick object with short reads against one fed the stretched PCM as full reads, the alternation rule of
-the valid array, the node's per-stream accessors, and a tick object that never enables the feature."""
+lane-loop emulation byte for byte with the `valid` array and without it, a tick object with short reads against one fed the stretched PCM
+as full reads, the alternation rule of the valid array, the node's per-stream accessors, and a tick object that never enables the feature."""
 import shutil
 
 import numpy as np
@@ -68,6 +68,30 @@ def test_device_equals_emulation(M, emu):
     a1, p1 = b.ingest(inter[:5], np.full((5, ns), 1152, np.int32))
     a2, p2 = b.ingest(inter[:5], np.full((5, ns), 2000, np.int32))
     assert a0.tobytes() == a1.tobytes() == a2.tobytes() and p0.tobytes() == p1.tobytes() == p2.tobytes()
+    b.close()
+
+
+def test_device_without_the_array_equals_emulation(M, emu):
+    """the same mixed batch (stereo and mono, six rates, gains of 0 dB and others), 3 frames, no `valid` array: tl_ingest_kernel's planar
+    PCM and peaks equal the emulation's byte for byte, and tl_ingest_valid_kernel's with every slot at 1152"""
+    cfgs, nch, ns, nf = _cfgs(M, MIX), _nch(MIX), len(MIX), 3
+    rng = np.random.default_rng(31)
+    inter = rng.integers(-32768, 32768, size=(nf, ns, 2 * I.FRAMES), dtype=np.int64).astype(np.int16)
+    inter[0, 0, :8] = [32767, -32768, 0, 1, -1, 12345, -12345, 2]
+    inter[1, 4] = 0                                                  # a silent stereo slot and a silent mono one: peaks (0, 0)
+    inter[2, 1, :I.FRAMES] = 0
+    b = M.Batch(cfgs)
+    for s, g in enumerate(GAINS):
+        b.set_gain_db(g, s)
+    want_pcm, want_pk = emu.ingest(inter, None, nch, GAINS)
+    pcm, pk = b.ingest(inter)
+    assert pcm.tobytes() == want_pcm.tobytes() and pk.tobytes() == want_pk.tobytes()
+    pcm_v, pk_v = b.ingest(inter, np.full((nf, ns), 1152, np.int32))
+    assert pcm_v.tobytes() == pcm.tobytes() and pk_v.tobytes() == pk.tobytes()
+    assert tuple(pk[1, 4]) == (0, 0) and tuple(pk[2, 1]) == (0, 0) and pk.max() > 0
+    for s in range(ns):
+        if nch[s] == 1:
+            assert not pcm[:, s, 1].any(), s                         # a mono stream's second plane is zero fill
     b.close()
 
 

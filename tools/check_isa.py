@@ -39,6 +39,7 @@ LIMITS = [
     (re.compile(r"tl_feed_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, pairs2_frac=0.0)),
     # ingest with short reads (csrc/toolame_ingest.hip): a streaming kernel, nothing may spill and the gather's index arithmetic must not go through scratch
     (re.compile(r"tl_ingest_valid_kernel"), dict(vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    (re.compile(r"tl_ingest_kernel"), dict(vgpr_spill=0, sgpr_spill=0, scratch=0)),          # ... and its twin without the `valid` array, the full-read text alone
     # compare monitor (csrc/toolame_compare.hip): a streaming kernel with eight 64-bit accumulators per lane; four waves' histories share a workgroup's LDS
     (re.compile(r"tl_compare_kernel"), dict(vgpr=128, lds=4 * 6560, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # resampler (csrc/toolame_resample.hip): a workgroup per slot with the ratio's table and the slot's source frames in LDS (17 168 bytes)

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Cost of the ingest path with short reads (csrc/toolame_ingest.hip) against the existing ingest kernel, on the GPU.
+"""Cost of the ingest kernels (csrc/toolame_ingest.hip), with short reads and without, against each other and another build, on the GPU.
 
     python tools/ingest_short_measure.py kernel [--streams 131072] [--rounds 7] [--launches 50] [--legs existing,valid_full,valid_1pct] [--parent-lib PATH]
     python tools/ingest_short_measure.py tick   [--streams 131072] [--rounds 5] [--ticks 100] [--parent-lib PATH]
 
 kernel: device-resident buffers, one frame of every stream per launch, `launches` launches between two device events, the legs interleaved
-round by round -- `existing` = tlb_ingest_device (tl_ingest_kernel), `valid_full` = tlb_ingest_device_valid with every slot at 1152,
+round by round -- `existing` = tlb_ingest_device (tl_ingest_kernel: the full-slot text of csrc/mp2_ingest.h that tl_ingest_valid_kernel
+shares, alone), `valid_full` = tlb_ingest_device_valid with every slot at 1152,
 `valid_1pct` = the same with about 1 % of the slots short by 1..115 frames (the range that is stretched).  With --parent-lib the library of
-another build (the parent commit's) is loaded beside this one and runs a leg `parent_existing` in the same rounds.  Run it under
+another build (the parent commit's; before the two kernels shared a text its tl_ingest_kernel was a copy of its own in toolame_hip.hip) is loaded
+beside this one and runs a leg `parent_existing` in the same rounds.  Run it under
 `rocprofv3 --kernel-trace --stats` with ONE leg per process for per-kernel times (the two builds' kernels carry the same names).
 tick: the `tick_pipeline` shape of bench.py (tlb_tick_run, pinned PCM -> PCIe -> ingest -> encode -> EDI AF -> PCIe, psy 3) for a tick object
 that never enables short reads, one that does (every read full), one with about 1 % of the streams short per tick, and -- with
