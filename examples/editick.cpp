@@ -16,7 +16,9 @@
 //   (tlb_tick_set_feed_adapted): on the ticks tlb_tick_feed_want says want no frame the slot stays empty and the file does not advance.
 //   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
 //   encoder's rate on the device (tlb_tick_set_source): each tick reads tlb_tick_need() source frames per stream, not 1152.  Not together
-//   with --short-every.
+//   with --short-every.  R above the rate of a 24000 Hz encoder (48000, 44100, 32000) is a DOWN source (tlb_tick_set_down_source): each tick
+//   reads tlb_tick_down_need() source frames per stream (2304 at 48 kHz) into the stream's wide slot (tlb_tick_down), and the device
+//   filters and decimates them.
 //   --short-every N --short-by M: short reads (src/odr-audioenc.cpp:335-373,910-935): on every Nth tick every Nth stream delivers M sample
 //   frames fewer than 1152; the library stretches what came over the frame as the reference does and counts the underruns.
 //   --monitor check|audio: the confidence monitor (tlb_tick_enable_monitor): every frame that leaves is checked on the device (audio: also
@@ -126,14 +128,16 @@ int main(int argc, char **argv)
     if (gain_db != 0.0 && tlb_tick_set_gain_db(t, -1, gain_db)) die("gain", 0);
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
-    if (source_rate) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
+    const bool down = source_rate > rate;                    // a source above the encoder's rate goes through the decimator and its wide slots
+    if (source_rate && !down) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
+    if (down) if (int rc = tlb_tick_set_down_source(t, -1, source_rate)) die("tlb_tick_set_down_source", rc);             // likewise
     if (feed_path && !adapt) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);         // likewise
     if (feed_path && adapt) if (int rc = tlb_tick_set_feed_adapted(t, -1, &feed)) die("tlb_tick_set_feed_adapted", rc);
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
     size_t per_frame = 1152 * (size_t)channels;              // samples of one frame in the file
-    std::vector<int16_t> frame(per_frame);
+    std::vector<int16_t> frame(down ? 2304 * (size_t)channels : per_frame);
     long frames = 0, packets = 0, bad_feed = 0;
     int alarms = 0;                                              // compare monitor: times a stream's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any stream has shown after a tick
@@ -178,10 +182,11 @@ int main(int argc, char **argv)
         frames++;
     }
     for (; !feed_path;) {
-        if (source_rate) per_frame = (size_t)tlb_tick_need(t, 0) * (size_t)channels;      // 1058 or 1059 frames at 44.1 kHz, 768 at 32 kHz: every stream is fed the one file, so all need the same
+        if (source_rate) per_frame = (size_t)(down ? tlb_tick_down_need(t, 0) : tlb_tick_need(t, 0)) * (size_t)channels;      // 1058 or 1059 frames at 44.1 kHz, 768 at 32 kHz; 2304 for 48 -> 24 kHz: every stream is fed the one file, so all need the same
         if (std::fread(frame.data(), sizeof(int16_t), per_frame, fi) != per_frame) break;
         int16_t *in = tlb_tick_pcm(t);                       // pinned [nstreams][2304]; mono streams use the first 1152 values
-        for (int s = 0; s < nstreams; s++) std::memcpy(in + (size_t)s * 2304, frame.data(), per_frame * sizeof(int16_t));
+        for (int s = 0; s < nstreams; s++)                   // a down source: the stream's wide slot (pinned, 4608 values, re-fetched every tick like the PCM) instead
+            std::memcpy(down ? tlb_tick_down(t, s) : in + (size_t)s * 2304, frame.data(), per_frame * sizeof(int16_t));
         if (short_every && frames % short_every == 0) {          // every set comes back all 1152: only the short streams are written
             int32_t *valid = tlb_tick_valid(t);                  // pinned [nstreams], re-fetched like the PCM
             for (int s = 0; s < nstreams; s += short_every) valid[s] = 1152 - short_by;

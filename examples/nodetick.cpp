@@ -10,9 +10,10 @@
 //   two ticks are kept in flight: while tick t's packets are shipped, tick t+1 is on the GPUs and tick t+2's PCM is being filled.
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
-// usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
+// usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
 //                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]
-//   in.s16le: interleaved stereo 48 kHz; stream s starts reading at frame s (so the services differ), wrapping around.
+//   in.s16le: interleaved stereo at the services' rate (-r: 48000, the default, or 24000); stream s starts reading at frame s (so the
+//   services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
 //   -o: the AF packets of the LAST stream of the node, length-prefixed (uint32 LE) -- the stream farthest from shard 0.
 //   --deadline-ms: the node's tick deadline (include/toolame_batch.h, TICK DEADLINE): a shard that misses it goes off air on its own
@@ -22,13 +23,15 @@
 //   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
 //   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
-//   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file (48 kHz, two channels, K kbps) decoded on the GPUs ahead
+//   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file (the services' rate, two channels, K kbps) decoded on the GPUs ahead
 //   of the ingest (tlb_node_set_feed): the file is cut into frames by the arithmetic length and each header's padding bit, service s takes
 //   frame (tick + s) of it, wrapping round; no PCM crosses the link and in.s16le is not opened (give "-").  Not together with --short-every
 //   or --source-rate.  --feed-rate R, --feed-channels C: the file is at another (legal) rate or channel count than the services', an ADAPTED
 //   feed (tlb_node_set_feed_adapted): a service's slot gets its next frame only on the ticks tlb_node_feed_want says want one.
 //   --source-rate R: in.s16le is at R Hz (44100 or 32000) and is resampled to 48 kHz on the GPUs (tlb_node_set_source): service s starts
 //   reading at source frame 1152 s and takes tlb_node_need() consecutive frames every tick, wrapping around.  Not together with --short-every.
+//   With -r 24000, R = 48000, 44100 or 32000 is a DOWN source (tlb_node_set_down_source): the tlb_node_down_need() frames of a tick go into
+//   the service's wide slot (tlb_node_down) and are filtered and decimated on the GPUs.
 //   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
 //   frame that leaves is decoded on its GPU and set against the audio that went in.  A service whose mismatch_run reaches 3 is printed when
 //   it does; one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any service got there.
@@ -57,6 +60,7 @@ struct Ctx {
     std::vector<long> *packets, *bytes;
     int short_every, short_by;                               // 0: every read is full
     long source_rate;                                        // 0: the file is at the encoder's rate
+    bool down;                                               // --source-rate above the services' rate: through the wide slots and the decimator
     std::vector<size_t> *spos;                               // --source-rate: the next source frame of every service
     const std::vector<uint8_t> *mp2;                         // --feed: the file and where its frames lie (NULL: PCM input)
     const std::vector<size_t> *fpos, *flen;
@@ -90,8 +94,9 @@ static void fill(void *vctx, int g, int first, int n)
             die("no input set free", s);
         }
         if (c.source_rate) {                                     // need source frames from where the service stands, around the end of the file
-            const int need = tlb_node_need(c.nd, s);
+            const int need = c.down ? tlb_node_down_need(c.nd, s) : tlb_node_need(c.nd, s);
             if (need < 0) die("tlb_node_need", -need);
+            if (c.down && !(dst = tlb_node_down(c.nd, s))) die("no wide slot free", s);      // (its shard took tlb_node_pcm a moment ago)
             const size_t total = c.pcm->size() / 2;
             size_t &at = (*c.spos)[(size_t)s];
             for (int i = 0; i < need; i++, at = (at + 1) % total) std::memcpy(dst + 2 * i, c.pcm->data() + 2 * at, 2 * sizeof(int16_t));
@@ -125,14 +130,15 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
     int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
+    long rate = 48000;
     double deadline_ms = 0;
     long source_rate = 0;
     int feed_kbps = 0, feed_channels = 2;
-    long feed_rate = 48000;
+    long feed_rate = 0;                                      // 0: the services' own
     std::string devs, outpath, feed_path;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
@@ -143,6 +149,7 @@ int main(int argc, char **argv)
         else if (k == "-G") G = std::atoi(v);
         else if (k == "-d") devs = v;
         else if (k == "-k") ticks = std::atoi(v);
+        else if (k == "-r") rate = std::atol(v);
         else if (k == "-b") kbps = std::atoi(v);
         else if (k == "-p") psy = std::atoi(v);
         else if (k == "-o") outpath = v;
@@ -172,8 +179,9 @@ int main(int argc, char **argv)
     G = (int)devices.size();
 
     if (feed_path.empty() != (feed_kbps <= 0)) die("--feed FILE.mp2 --feed-bitrate K: both or neither", 0);
+    if (!feed_rate) feed_rate = rate;
     tlb_feed_config feed = {feed_rate, feed_kbps, feed_channels};   // the services' own rate and channel count unless told otherwise
-    const bool adapt = feed_rate != 48000 || feed_channels != 2;
+    const bool adapt = feed_rate != rate || feed_channels != 2;
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;
     if (!feed_path.empty()) {
@@ -205,8 +213,8 @@ int main(int argc, char **argv)
     const size_t nframes_in = pcm.size() / 2304;
     if (feed_path.empty() && !nframes_in) die("input shorter than one frame", 0);
 
-    // the fleet: every service 48 kHz joint stereo (odr-audioenc's default mode, src/odr-audioenc.cpp:697-709)
-    std::vector<tlb_stream_config> cfg((size_t)nstreams, tlb_stream_config{48000, 'j', kbps, psy, 0});
+    // the fleet: every service joint stereo (odr-audioenc's default mode, src/odr-audioenc.cpp:697-709) at 48 kHz unless told otherwise
+    std::vector<tlb_stream_config> cfg((size_t)nstreams, tlb_stream_config{rate, 'j', kbps, psy, 0});
     static const char version[] = "nodetick example";
     tlb_node_config nc;
     std::memset(&nc, 0, sizeof nc);
@@ -229,8 +237,11 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
     if (monitor)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
-    if (source_rate)
+    const bool down = source_rate > rate;
+    if (source_rate && !down)
         if (int rc = tlb_node_set_source(nd, -1, source_rate)) die("tlb_node_set_source", rc);          // between steps; a restarted shard's sources are set again
+    if (down)
+        if (int rc = tlb_node_set_down_source(nd, -1, source_rate)) die("tlb_node_set_down_source", rc);      // likewise
     if (!feed_path.empty())
         if (int rc = adapt ? tlb_node_set_feed_adapted(nd, -1, &feed) : tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
@@ -242,7 +253,7 @@ int main(int argc, char **argv)
     std::vector<size_t> spos((size_t)nstreams), fcur((size_t)nstreams);
     for (int s = 0; s < nstreams; s++) fcur[(size_t)s] = (size_t)s;     // an adapted feed: service s starts s frames into the file
     for (int s = 0; s < nstreams && !pcm.empty(); s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt ? &fcur : nullptr};
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, down, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt ? &fcur : nullptr};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick

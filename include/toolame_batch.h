@@ -742,8 +742,8 @@ const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream);
  *   source rate -> encoder rate     ratio L/M
  *   44100 -> 48000, 22050 -> 24000  160/147
  *   32000 -> 48000, 16000 -> 24000  3/2
- * Any other pair is TLB_ERR_SAMPLERATE.  Downsampling (48 -> 24 kHz: twice the PCM on the host-to-device link, which is the limit) and
- * 48 -> 44.1 kHz are out of scope.
+ * Any other pair is TLB_ERR_SAMPLERATE here.  Sources ABOVE a 24 kHz encoder's rate (48, 44.1 and 32 kHz) are a family of their own with
+ * wider slots: "Down sources" below (tlb_decimate_*).  48 -> 44.1 / 32 kHz is out of scope.
  * THE TAPS.  One table per ratio, int16 H[L][T], T = TLB_RESAMPLE_TAPS = 32, committed as csrc/tl_resample_taps.inc: the committed table is
  * the definition, tools/gen_resample_taps.py the record of how it was made (N = L T; c = k - (N - 1) / 2; fc = 0.95 * 0.5 / L;
  * h[k] = L 2 fc sinc(2 fc c) kaiser(N, 8)[k]; row p = h[p::L] scaled to sum 32768, rounded half up, the remainder added to the row's tap of
@@ -803,6 +803,86 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate);
 int tlb_tick_need(const tlb_tick *t, int stream);
 int tlb_node_set_source(tlb_node *nd, int stream, long source_rate);
 int tlb_node_need(const tlb_node *nd, int stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Down sources: 48, 44.1 and 32 kHz sources for a 24 kHz encoder, low-pass filtered and decimated on the device, ahead of the ingest.
+ * Half-rate services usually get studio audio at 48 kHz; the reference's inputs convert it before AudioEnc::run() sees a sample
+ * (src/VLCInput.cpp:208, src/GSTInput.cpp:124-133).  Per TICK a 48 kHz source moves twice the PCM of the service; per SECOND it does not: a
+ * 24 kHz frame lasts 48 ms, so 9216 bytes per 48 ms are the 4608 bytes per 24 ms every 48 kHz service moves.  A family of its own beside
+ * tlb_resample_* (which is unchanged): wider slots, regular frames, 64 taps.  Defined in integers, as the resampler is.
+ *   source rate -> encoder rate     ratio L/M
+ *   48000 -> 24000                  1/2
+ *   32000 -> 24000                  3/4
+ *   44100 -> 24000                  80/147
+ * Any other pair is TLB_ERR_SAMPLERATE.
+ * THE TAPS.  One table per ratio, int16 H[L][T], T = TLB_DECIMATE_TAPS = 64, committed as csrc/tl_decimate_taps.inc: the committed table is
+ * the definition, tools/gen_decimate_taps.py the record of how it was made (the resampler's recipe with the cutoff on the OUTPUT side:
+ * N = L T; c = k - (N - 1) / 2; fc = 0.95 * 0.5 / M; h[k] = L 2 fc sinc(2 fc c) kaiser(N, 8)[k]; row p = h[p::L] scaled to sum 32768, rounded
+ * half up, the remainder added to the row's tap of largest magnitude).  Every row sums to exactly 32768.  From the table: within +- 0.01 dB up
+ * to 0.8 x the output's Nyquist frequency, - 75.7 / - 78.6 / - 85.7 dB (1/2, 3/4, 80/147) from 1.2 x upwards (32 taps would give - 40 dB).
+ * THE FORMULA.  For a stream, count output samples n and source frames from the stream's last reset; a source frame is an L/R pair, or one
+ * sample of a one-channel stream.  With q(n) = floor((n M + M - 1) / L) and p(n) = (n M + M - 1) mod L:
+ *   acc(n) = sum over t = 0..T-1 of H[p(n)][t] * x[q(n) - t]      (x[j] = 0 for j < 0; the exact integer sum)
+ *   y(n)   = clamp((acc(n) + 16384) >> 15, -32768, 32767)         (arithmetic shift, i.e. floor)
+ * per channel, both channels with the same q and p.  The offset M - 1 makes the frames regular: frame f of the stream is
+ * y(1152 f .. 1152 f + 1151) and consumes the source frames [S(f), S(f + 1)), S(f) = ceil(1152 f M / L), f = 0 included:
+ *   need(f) = S(f + 1) - S(f)
+ * 1/2: always 2304; 3/4: always 1536; 80/147: 2117, 2117, 2117, 2117, 2116 in a cycle of five frames that add up to 10 584.  Never above
+ * 2304 frames: a WIDE slot of TLB_DECIMATE_SLOT = 4608 values holds it.
+ * BUFFERS.  d_wide is int16 [nframes][nstreams][4608], d_interleaved int16 [nframes][nstreams][2304]; both 16-byte aligned, and they must
+ * not overlap (TLB_ERR_ARG).  The wide slot of a stream with a down source holds the need source frames of that frame at its start
+ * (interleaved L R for two channels); nothing behind them is read.  Its output slot is what tlb_ingest_device takes: 1152 sample frames at
+ * 24 kHz, interleaved L R, or 1152 samples of a one-channel stream with nothing written behind them.  The slots of a stream WITHOUT a down
+ * source are left alone, both of them: not read, not written -- its PCM is the caller's to put into d_interleaved.
+ * The (frame, stream) slots of a call are independent units, as the resampler's are: slot f takes its T - 1 frames of history from the tail of
+ * slot f - 1 in the same buffer, the call's first slot from the stream's state record, the last slot writes the record: the output does not
+ * depend on how a stream's frames are cut into calls.
+ * STATE per stream: T - 1 source frames and the frame position within the need cycle, on the device, allocated by the first real
+ * tlb_decimate_set_source of a batch -- a batch that never sets one allocates nothing and queues nothing (tlb_decimate_device then returns
+ * after its argument checks).  The host keeps its own copy of the position: tlb_decimate_need never touches the device.
+ *   tlb_decimate_set_source(b, stream, rate)  stream = -1: every stream; rate 0 or the stream's own encoder rate: off.  Waits for the queued
+ *                                 launches and zeroes the decimator state of the streams it names; the encoder is left alone.  An illegal
+ *                                 pair for any named stream: TLB_ERR_SAMPLERATE, nothing changed.  A stream that has a tlb_resample_* source:
+ *                                 TLB_ERR_ARG, nothing changed (a stream has one source).
+ *   tlb_decimate_source           the stream's down source rate; 0: off
+ *   tlb_decimate_need(b, s, ahead) source frames the stream's (ahead)-th next frame consumes; 1152 for a stream without a down source;
+ *                                 < 0: -TLB_ERR_ARG
+ *   tlb_decimate_need_at          need(frame) from the rates alone, no batch, no GPU; < 0: -TLB_ERR_*
+ *   tlb_decimate_taps             the committed table [L][T] and its L, M, T (each may be NULL); NULL: no such pair
+ * tlb_reset, tlb_stream_reset and tlb_stream_finish zero the decimator state of the streams they touch.  tlb_stream_reconfigure keeps the
+ * source rate when the new encoder rate still forms a legal pair with it; otherwise it refuses with TLB_ERR_SAMPLERATE and changes nothing.
+ * Asynchronous on `hip_stream`; calls of one batch must be ordered on one stream.  With feeds and short reads the batch level composes by the
+ * caller's own ordering, as the resampler does.
+ * TICK PLANE.  tlb_tick_set_down_source(t, stream, rate) is legal while no tick is in flight (TLB_ERR_ARG otherwise).  The first real down
+ * source gives the object its wide buffers: pinned ones that travel with the two input sets, one device buffer per group.  tlb_tick_down(t,
+ * stream) is the stream's wide slot (4608 values) in the CURRENT input set, NULL with two ticks in flight or while no stream has a down source;
+ * tlb_tick_down_need(t, stream) the source frames it must hold for the next submit.  While at least one stream has a down source every submit
+ * copies in the group's PCM (unless EVERY stream of the group has a down source) and the group's wide slice, and queues the decimator on the
+ * run stream ahead of the ingest, writing the streams' slots of the group's PCM buffer; an object that never sets one queues exactly what it
+ * queued before.  Down sources, sources (tlb_tick_set_source), feeds and short reads exclude one another on one tick or node object
+ * (TLB_ERR_ARG), from either side and in either order.
+ * NODE LEVEL.  tlb_node_set_down_source / tlb_node_down / tlb_node_down_need route to the owning shard as tlb_node_set_source / tlb_node_need
+ * do, with the same rules: every pair is checked before a shard is changed, a change made before a device failure half way is rolled back,
+ * the source is remembered for tlb_node_shard_restart (fresh state) and forgotten by a tlb_node_stream_reconfigure it no longer pairs with;
+ * a stream of a broken or late shard answers NULL, -TLB_ERR_HIP or -TLB_ERR_LATE.
+ * NOT BUILT: a channel map for PCM sources (the host's (L + R + 1) >> 1 is cheap, the filter is not); 48 kHz FEEDS for 24 kHz services (two
+ * feed frames per slot); 48 -> 44.1 / 32 kHz; encoder rates other than 24 kHz.
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_DECIMATE_TAPS 64
+#define TLB_DECIMATE_SLOT 4608
+int tlb_decimate_set_source(tlb_batch *b, int stream, long source_rate);
+long tlb_decimate_source(const tlb_batch *b, int stream);
+int tlb_decimate_need(const tlb_batch *b, int stream, int ahead);
+int tlb_decimate_need_at(long source_rate, long encoder_rate, long frame);
+const int16_t *tlb_decimate_taps(long source_rate, long encoder_rate, int *L, int *M, int *T);
+int tlb_decimate_device(tlb_batch *b, const int16_t *d_wide, int nframes, int16_t *d_interleaved, void *hip_stream);
+int tlb_decimate_host(tlb_batch *b, const int16_t *wide, int nframes, int16_t *interleaved);
+int tlb_tick_set_down_source(tlb_tick *t, int stream, long source_rate);
+int16_t *tlb_tick_down(tlb_tick *t, int stream);
+int tlb_tick_down_need(const tlb_tick *t, int stream);
+int tlb_node_set_down_source(tlb_node *nd, int stream, long source_rate);
+int16_t *tlb_node_down(tlb_node *nd, int stream);
+int tlb_node_down_need(const tlb_node *nd, int stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Layer II feeds: a stream's source arrives as MP2 frames SOMEBODY ELSE encoded and is decoded on the device, ahead of the ingest.

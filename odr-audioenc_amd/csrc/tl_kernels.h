@@ -11,6 +11,7 @@
 #include "mp2_dec_types.h"
 #include "mp2_compare.h"
 #include "mp2_resample.h"
+#include "mp2_decimate.h"
 #include "mp2_feed_adapt.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
@@ -58,5 +59,9 @@ hipError_t tlk_compare(hipStream_t st, const int16_t *in, const int16_t *dec, co
 // toolame_resample.hip: tl_resample_kernel, one workgroup per (frame, stream) slot (csrc/mp2_resample.h); state uint32 [2][nstreams][32] and ratio
 // int32 [nstreams] may both be NULL (no stream has a source: every slot is copied)
 hipError_t tlk_resample(unsigned blocks, hipStream_t st, const int16_t *source, int16_t *out, uint32_t *state, const int32_t *ratio, const int16_t *taps,
+                        const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int nframes, int flip);
+// toolame_decimate.hip: tl_decimate_kernel, one workgroup per (frame, stream) slot (csrc/mp2_decimate.h); wide int16 [nframes][nstreams][4608], state
+// uint32 [2][nstreams][64], ratio int32 [nstreams] (TL_DC_*; the slots of a TL_DC_OFF stream are left alone)
+hipError_t tlk_decimate(unsigned blocks, hipStream_t st, const int16_t *wide, int16_t *out, uint32_t *state, const int32_t *ratio, const int16_t *taps,
                         const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int nframes, int flip);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

@@ -179,7 +179,8 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
     if (b->d_dec_state) HIPCHK(hipMemset(b->d_dec_state + s0, 0, sizeof(TlDecStream) * (size_t)n));      // the decoder's next frame of these streams is a first frame
     if (b->d_cmp_hist) HIPCHK(hipMemset(b->d_cmp_hist + (size_t)s0 * 2 * TL_CMP_HIST, 0, sizeof(int16_t) * 2 * TL_CMP_HIST * (size_t)n));      // ... and the compare monitor has no input to set their next frame against
     if (int rc = feed_clear_streams(b, s0, n)) return rc;            // ... and a feed's next frame is decoded as after silence
-    return resample_clear_streams(b, s0, n);                         // ... and the resampler starts these streams' sources at frame 0 again
+    if (int rc = resample_clear_streams(b, s0, n)) return rc;        // ... and the resampler starts these streams' sources at frame 0 again
+    return decimate_clear_streams(b, s0, n);                         // ... and so does the decimator
 }
 
 int tlb_reset(tlb_batch *b)
@@ -236,7 +237,7 @@ int tlb_stream_reconfigure(tlb_batch *b, int stream, const tlb_stream_config *cf
     TlConfig c;
     if (found < 0) { if (int rc = tl_build_config(&c, cfg->samplerate, cfg->mode, cfg->bitrate, cfg->psy_model, cfg->pad_len)) return rc; }
     else c = b->h_configs[(size_t)found];
-    if (!resample_rate_fits(b, stream, cfg->samplerate)) return TLB_ERR_SAMPLERATE;      // the stream's source rate and the new encoder rate form no legal pair
+    if (!resample_rate_fits(b, stream, cfg->samplerate) || !decimate_rate_fits(b, stream, cfg->samplerate)) return TLB_ERR_SAMPLERATE;      // the stream's source rate and the new encoder rate form no legal pair
     // the caller's buffers were sized from tlb_out_stride() and tlb_egress_max_units_per_frame(): the new configuration must fit them
     if (((c.frame_bytes + (c.pad_frac != 0 ? 1 : 0) + 3) & ~3) > b->out_stride) return TLB_ERR_ARG;
     {

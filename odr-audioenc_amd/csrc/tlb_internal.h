@@ -89,6 +89,13 @@ struct tlb_batch {
     int rs_flip = 0;
     std::vector<long> rs_rate;                   // [nstreams] source rate, 0: off (empty until the first set_source)
     std::vector<int32_t> rs_ratio, rs_pos;       // host copies: TL_RS_* and the frame position in the need cycle
+    // decimator (tlb_decimate.cpp), allocated by the first tlb_decimate_set_source: a batch that never sets a down source has none of it
+    uint32_t *d_dc_state = nullptr;              // [2][nstreams][TL_DC_STATE_WORDS]; a launch reads copy dc_flip and writes the other
+    int32_t *d_dc_ratio = nullptr;               // [nstreams] TL_DC_*
+    int16_t *d_dc_taps = nullptr;                // the three tables: [80][64], [3][64], [1][64]
+    int dc_flip = 0;
+    std::vector<long> dc_rate;                   // [nstreams] source rate, 0: off (empty until the first set_source)
+    std::vector<int32_t> dc_ratio, dc_pos;       // host copies: TL_DC_* and the frame position in the need cycle
     // Layer II feeds (tlb_feed.cpp), allocated by the first tlb_feed_set: a batch that never sets a feed has none of it
     std::vector<tlb_feed_config> feed_cfg;       // [nstreams] the stream's feed (empty until the first set)
     std::vector<int32_t> feed_idx;               // [nstreams] its record in h_feed_configs, -1: no feed
@@ -170,4 +177,8 @@ int resample_prepare(tlb_batch *b);
 int16_t *resample_taps_upload(TlbMem &m);        // both tables in one buffer of m: [160][32], then [3][32] (the resampler's copy, and the adapted feeds')
 int resample_clear_streams(tlb_batch *b, int s0, int n);
 bool resample_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
+// tlb_decimate.cpp: the same three for the decimator's down sources
+int decimate_prepare(tlb_batch *b);
+int decimate_clear_streams(tlb_batch *b, int s0, int n);
+bool decimate_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -162,6 +162,8 @@ struct tlb_node {
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
     std::vector<long> source;                    // tlb_node_set_source(): the source rate of every stream (0: off), set again on a restarted shard; empty: never set
+    std::vector<long> down;                      // tlb_node_set_down_source(): the down source rate of every stream (0: off), set again on a restarted shard; empty: never set
+    bool any_down() const { for (long r : down) if (r) return true; return false; }
     struct Feed : tlb_feed_config { int adapted; };      // adapted: set through tlb_node_set_feed_adapted, and set again that way
     std::vector<Feed> feed;           // tlb_node_set_feed(): the feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
@@ -337,6 +339,11 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         const long r = nd->source[(size_t)(s.first + k)];
         if (r == 0) continue;
         if (int rc = s.tick ? tlb_tick_set_source(s.tick, k, r) : tlb_resample_set_source(s.batch, k, r)) return rc;
+    }
+    for (int k = 0; k < s.n && !nd->down.empty(); k++) {             // the caller's down sources, with fresh state
+        const long r = nd->down[(size_t)(s.first + k)];
+        if (r == 0) continue;
+        if (int rc = s.tick ? tlb_tick_set_down_source(s.tick, k, r) : tlb_decimate_set_source(s.batch, k, r)) return rc;
     }
     for (int k = 0; k < s.n && !nd->feed.empty(); k++) {             // the caller's feeds, with fresh history
         const tlb_node::Feed &f = nd->feed[(size_t)(s.first + k)];
@@ -590,7 +597,7 @@ int tlb_node_enable_short_reads(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
     for (long r : nd->source) if (r) return TLB_ERR_ARG;             // a source and short reads exclude each other (include/toolame_batch.h)
-    if (nd->any_feed()) return TLB_ERR_ARG;                          // ... and so do a feed and short reads
+    if (nd->any_feed() || nd->any_down()) return TLB_ERR_ARG;        // ... and so do a feed or a down source and short reads
     if (nd->short_reads) return TLB_OK;
     const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
     if (!rc) nd->short_reads = true;
@@ -650,10 +657,35 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     bool any = false;
     if (int rc = tlb_source_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
-    if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && nd->any_feed()))) return TLB_ERR_ARG;
+    if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && (nd->any_feed() || nd->any_down())))) return TLB_ERR_ARG;
     return nd->set_remembered(stream, nd->source, any, source_rate,
         [](Shard &sh, int k, long r) { return sh.tick ? tlb_tick_set_source(sh.tick, k, r) : tlb_resample_set_source(sh.batch, k, r); },
         [&](int i) { return source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate; });      // (the encoder's own rate is no source)
+}
+// A down source for one stream or all, the same way (tlb_tick_set_down_source / tlb_decimate_set_source of the owning shards' objects).
+int tlb_node_set_down_source(tlb_node *nd, int stream, long source_rate)
+{
+    if (!nd || stream < -1 || stream >= nd->nstreams || source_rate < 0 || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
+    bool any = false;
+    if (int rc = tlb_down_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
+    if (any && nd->plane == TLB_NODE_TICK) {                         // down sources exclude short reads, sources and feeds on one object (include/toolame_batch.h)
+        if (nd->short_reads || nd->any_feed()) return TLB_ERR_ARG;
+        for (long r : nd->source) if (r) return TLB_ERR_ARG;
+    }
+    return nd->set_remembered(stream, nd->down, any, source_rate,
+        [](Shard &sh, int k, long r) { return sh.tick ? tlb_tick_set_down_source(sh.tick, k, r) : tlb_decimate_set_source(sh.batch, k, r); },
+        [&](int i) { return source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate; });      // (the encoder's own rate is no source)
+}
+// the stream's wide slot in its shard's current input set: NULL for a broken or a late shard, while two ticks are in flight and while no
+// stream of the shard has a down source
+int16_t *tlb_node_down(tlb_node *nd, int stream) { return ask<INPUT>(nd, stream, (int16_t *)nullptr, [](tlb_tick *t, int k) { return tlb_tick_down(t, k); }); }
+int tlb_node_down_need(const tlb_node *nd, int stream)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK) return -TLB_ERR_ARG;
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return -rc;
+    return s->tick ? tlb_tick_down_need(s->tick, k) : -TLB_ERR_HIP;
 }
 // A Layer II feed for one stream or all (cfg = NULL: removed; remembered as bitrate 0), the same way.  Every named stream is checked
 // before a shard is asked.
@@ -672,6 +704,7 @@ static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, b
         if (nd->plane == TLB_NODE_TICK) {                            // feeds exclude short reads and sources on one object (include/toolame_batch.h)
             if (nd->short_reads) return TLB_ERR_ARG;
             for (long r : nd->source) if (r) return TLB_ERR_ARG;
+            if (nd->any_down()) return TLB_ERR_ARG;
         }
     }
     tlb_node::Feed v = {};
@@ -828,6 +861,7 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
     if (int rc = nd->gate(stream, &s, &k)) return rc;
     const int rc = nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reconfigure(sh.tick, k, cfg) : tlb_stream_reconfigure(sh.batch, k, cfg); });
     if (!rc) nd->cfgs[(size_t)stream] = *cfg;                        // a restart of the shard re-creates the stream as it is NOW
+    if (!rc && !nd->down.empty() && tl_dc_ratio_of(nd->down[(size_t)stream], cfg->samplerate) == TL_DC_OFF) nd->down[(size_t)stream] = 0;      // (a down source that no longer pairs is forgotten)
     if (!rc && !nd->feed.empty()) {                                  // a feed the new rate or channel count no longer fits has been removed
         tlb_node::Feed &f = nd->feed[(size_t)stream];
         const bool fits = f.adapted ? node_rates_adapt(f.samplerate, cfg->samplerate) : f.samplerate == cfg->samplerate && f.channels == (cfg->mode == 'm' ? 1 : 2);

@@ -11,6 +11,7 @@
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
 #include "mp2_resample.h"
+#include "mp2_decimate.h"
 
 // the knobs of toolame.h:13-48 that make a configuration record (the sixth, the PAD length of a frame, is per frame)
 static inline bool tlb_same_config(const tlb_stream_config &a, const tlb_stream_config &b)
@@ -69,6 +70,17 @@ template <class EncRate> static inline int tlb_source_range(int s0, int s1, long
         const long enc = enc_rate(s);
         if (source_rate == 0 || source_rate == enc) continue;
         if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
+        *any = true;
+    }
+    return 0;
+}
+// The same for a DOWN source (the decimator, csrc/mp2_decimate.h).
+template <class EncRate> static inline int tlb_down_range(int s0, int s1, long source_rate, EncRate enc_rate, bool *any)
+{
+    for (int s = s0; s < s1; s++) {
+        const long enc = enc_rate(s);
+        if (source_rate == 0 || source_rate == enc) continue;
+        if (tl_dc_ratio_of(source_rate, enc) == TL_DC_OFF) return TLB_ERR_SAMPLERATE;
         *any = true;
     }
     return 0;

@@ -39,6 +39,9 @@ struct TickGroup {
     // Layer II feeds (tlb_tick_set_feed): the group's slice of the tick's feed frames and lengths, the feed call's reports
     uint8_t *d_feed = nullptr; int32_t *d_feed_len = nullptr; tlb_frame_report *d_feed_report = nullptr;
     bool any_fed = false, all_fed = false;                      // some / every stream of the group has a feed (all: the group's PCM is not copied in)
+    // down sources (tlb_tick_set_down_source): the group's slice of the tick's wide slots; the decimator writes the streams' slots of d_inter
+    int16_t *d_wide = nullptr;
+    bool any_down = false, all_down = false;                    // some / every stream of the group has a down source (all: the group's PCM is not copied in)
     hipEvent_t ev_mon = nullptr;                                // decode + fold (+ compare) done: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
@@ -66,6 +69,9 @@ struct tlb_tick {
     int listen_of[3] = {-1, -1, -1};             // ... the tick of each output set carried
     bool resample = false;                       // at least one stream has a source: every submit queues the resampler between copy-in and ingest
                                                  // (the groups' d_rs buffers, once made, stay until destroy)
+    // down sources, off until the first real tlb_tick_set_down_source: the wide slots [nstreams][TLB_DECIMATE_SLOT] travel with the input sets
+    bool down = false;                           // at least one stream has a down source
+    int16_t *h_wide[2] = {};
     // Layer II feeds, off until the first tlb_tick_set_feed: the frames and their lengths travel with the input sets, the reports with the
     // output sets.  feed_stride is ONE slot width for every group (the widest feed the object has had: it only grows); the frame buffers
     // are replaced when it grows and have an owner of their own (feed_mem: the old owner goes when the new one is complete), the rest
@@ -242,7 +248,7 @@ const uint32_t *tlb_tick_underruns(const tlb_tick *t) { return t && t->short_rea
 // call makes the device calls it always made.
 int tlb_tick_enable_short_reads(tlb_tick *t)
 {
-    if (!t || t->finished || t->ticks > 0 || t->resample || t->feed) return TLB_ERR_ARG;      // (a source or a feed and short reads exclude each other: include/toolame_batch.h)
+    if (!t || t->finished || t->ticks > 0 || t->resample || t->feed || t->down) return TLB_ERR_ARG;      // (a source, a down source or a feed and short reads exclude each other: include/toolame_batch.h)
     if (t->broken) return TLB_ERR_HIP;
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
@@ -347,7 +353,7 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
             return e;
         })) return rc;
     if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
-    if (any && (t->short_reads || t->feed)) return TLB_ERR_ARG;
+    if (any && (t->short_reads || t->feed || t->down)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
     if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer, and the resampler of the batches that get
         TlbMem m;                                                    // a source, before anything is committed or a stream is changed
@@ -363,6 +369,59 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
     for (auto &G : t->groups)
         for (int k = 0; k < G.n; k++) if (tlb_resample_source(G.b, k)) t->resample = true;
     return rc;
+}
+// A down source for one stream or all (tlb_decimate_set_source of the group's batch), while no tick is in flight.  The first real one gives
+// the object its pinned wide buffers and every group its device one; from then on, while some stream has a down source, every submit copies
+// the wide slices of the groups that have one and runs the decimator ahead of their ingest.  An object that never sets one makes the device
+// calls it always made.
+int tlb_tick_set_down_source(tlb_tick *t, int stream, long source_rate)
+{
+    if (!t || t->finished || stream < -1 || stream >= t->nstreams || source_rate < 0 || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
+    bool any = false;
+    std::vector<char> real(t->groups.size(), 0);                     // per group: the call gives some stream of it a real down source
+    if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) {     // every stream is checked before one is changed
+            const TickGroup &G = t->groups[(size_t)g];
+            bool r = false;
+            const int e = tlb_down_range(l0, l1, source_rate, [&G](int k) { return (long)G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate; }, &r);
+            real[(size_t)g] = r; any |= r;
+            return e;
+        })) return rc;
+    if (!any && !t->h_wide[0]) return TLB_OK;                        // off, and never on: nothing to allocate or to clear
+    if (any && (t->short_reads || t->feed || t->resample)) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(t->device));
+    if (!t->h_wide[0]) {                                             // first real down source: the wide buffers, and the decimator of the batches that get
+        TlbMem m;                                                    // one, before anything is committed or a stream is changed
+        std::vector<TickGroup> gs = t->groups;
+        int16_t *h[2];
+        for (int k = 0; k < 2; k++) h[k] = m.pinned<int16_t>((size_t)t->nstreams * TLB_DECIMATE_SLOT);
+        for (auto &G : gs) G.d_wide = m.dev<int16_t>((size_t)G.n * TLB_DECIMATE_SLOT);
+        for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = decimate_prepare(gs[g].b)) return rc;
+        if (!m.settle()) return TLB_ERR_HIP;
+        m.commit(t->mem);
+        t->groups.swap(gs);
+        memcpy(t->h_wide, h, sizeof h);
+    }
+    const int rc = t->blocks.visit(stream, [&](int g, int k) { return tlb_decimate_set_source(t->groups[(size_t)g].b, k, source_rate); });
+    t->down = false;                                                 // "at least one down source set", as the streams stand now
+    for (auto &G : t->groups) {
+        int n = 0;
+        for (int k = 0; k < G.n; k++) n += tlb_decimate_source(G.b, k) != 0;
+        G.any_down = n > 0; G.all_down = n == G.n;
+        t->down |= G.any_down;
+    }
+    return rc;
+}
+int16_t *tlb_tick_down(tlb_tick *t, int stream)
+{
+    if (!tick_input_free(t) || !t->down || stream < 0 || stream >= t->nstreams) return nullptr;
+    return t->h_wide[t->in_set] + (size_t)stream * TLB_DECIMATE_SLOT;
+}
+int tlb_tick_down_need(const tlb_tick *t, int stream)
+{
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    return G ? tlb_decimate_need(G->b, k, 0) : -TLB_ERR_ARG;
 }
 // A Layer II feed for one stream or all (tlb_feed_set of the group's batch), while no tick is in flight.  The first feed gives the object
 // its pinned feed buffers and every group its device ones; a wider feed than any before replaces the frame buffers (RE-FETCH).  An object
@@ -388,7 +447,7 @@ static int tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg, bo
     if (!cfg && !t->h_feed_len[0]) return TLB_OK;                    // off, and never on: nothing to allocate or to clear
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
     if (cfg) {
-        if (t->short_reads || t->resample) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads and sources)
+        if (t->short_reads || t->resample || t->down) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads, sources and down sources)
         // every stream is checked before one is changed
         if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return (adapt ? feed_fits_adapted : feed_fits)(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
     }
@@ -646,9 +705,11 @@ int tlb_tick_submit(tlb_tick *t)
         hipError_t e = hipSuccess;
         if (t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_ingested, 0);
         // a group all of whose streams have feeds takes no PCM over the link: the feed kernel writes every slot the ingest reads
-        if (e == hipSuccess && !G.all_fed) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
+        // ... nor does a group all of whose streams have down sources: its wide slice comes in instead and the decimator writes every slot
+        if (e == hipSuccess && !G.all_fed && !G.all_down) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed, t->h_feed[set] + (size_t)G.first * (size_t)t->feed_stride, n * (size_t)t->feed_stride, hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed_len, t->h_feed_len[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && G.any_down) e = hipMemcpyAsync(G.d_wide, t->h_wide[set] + (size_t)G.first * TLB_DECIMATE_SLOT, n * TLB_DECIMATE_SLOT * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->short_reads) e = hipMemcpyAsync(G.d_valid, t->h_valid[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->with_xpad && t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_encoded, 0);
         if (e == hipSuccess && t->with_xpad) e = hipMemcpyAsync(G.d_xpad, t->h_xpad[set] + (size_t)G.first * TL_MAX_XPAD, n * TL_MAX_XPAD, hipMemcpyHostToDevice, t->s_in);
@@ -659,6 +720,7 @@ int tlb_tick_submit(tlb_tick *t)
         if (e != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc && G.any_fed) rc = feed_launch(G.b, G.d_feed, G.d_feed_len, 1, G.d_inter, G.d_feed_report, t->s_run, t->feed_stride);      // behind the copy-in, ahead of the ingest: a mixed group's fed slots are overwritten
         if (!rc && t->resample) rc = tlb_resample_device(G.b, G.d_inter, 1, G.d_rs, t->s_run);
+        if (!rc && G.any_down) rc = tlb_decimate_device(G.b, G.d_wide, 1, G.d_inter, t->s_run);      // behind the copy-in, ahead of the ingest: a mixed group's decimated slots are overwritten
         if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, t->resample ? G.d_rs : G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
         if (!rc && t->short_reads) rc = tlb_ingest_device_valid(G.b, G.d_inter, G.d_valid, 1, G.d_pcm, G.d_peaks, t->s_run);
         // (the counters here and not with the silence counter: the next tick's copy-in may overwrite d_valid once ev_ingested has passed)

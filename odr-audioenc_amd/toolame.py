@@ -284,6 +284,24 @@ def _bind(L):
         L.tlb_tick_need.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_node_need.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_decimate_device"):         # device decimator (down sources)
+        L.tlb_decimate_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        L.tlb_decimate_source.restype = C.c_long
+        L.tlb_decimate_source.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_decimate_need.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.tlb_decimate_need_at.argtypes = [C.c_long, C.c_long, C.c_long]
+        L.tlb_decimate_taps.restype = C.c_void_p
+        L.tlb_decimate_taps.argtypes = [C.c_long, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.tlb_decimate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_decimate_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_tick_set_down_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        L.tlb_tick_down.restype = C.c_void_p
+        L.tlb_tick_down.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_tick_down_need.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_set_down_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
+        L.tlb_node_down.restype = C.c_void_p
+        L.tlb_node_down.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_down_need.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "tlb_feed_set"):               # Layer II feeds
         L.tlb_feed_check_config.argtypes = [C.c_void_p]
         L.tlb_feed_frame_bytes.argtypes = [C.c_void_p]
@@ -340,6 +358,26 @@ def resample_taps(source_rate, encoder_rate):
     """the committed polyphase table of the pair -> (int16 [L, T] copy, L, M); None when the pair is not supported"""
     l, m, tt = C.c_int(0), C.c_int(0), C.c_int(0)
     p = load_library().tlb_resample_taps(int(source_rate), int(encoder_rate), C.byref(l), C.byref(m), C.byref(tt))
+    if not p:
+        return None
+    return np.ctypeslib.as_array((C.c_int16 * (l.value * tt.value)).from_address(p)).reshape(l.value, tt.value).copy(), l.value, m.value
+
+
+DECIMATE_SLOT = 4608      # int16 per wide slot (TLB_DECIMATE_SLOT)
+
+
+def decimate_need_at(source_rate, encoder_rate, frame):
+    """source frames frame `frame` (from the stream's reset) of a down source (48 / 44.1 / 32 kHz -> 24 kHz) consumes: host arithmetic, no GPU"""
+    n = load_library().tlb_decimate_need_at(int(source_rate), int(encoder_rate), int(frame))
+    if n < 0:
+        raise ToolameError(-n, "tlb_decimate_need_at")
+    return n
+
+
+def decimate_taps(source_rate, encoder_rate):
+    """the committed polyphase table of the down pair -> (int16 [L, T] copy, L, M); None when the pair is not supported"""
+    l, m, tt = C.c_int(0), C.c_int(0), C.c_int(0)
+    p = load_library().tlb_decimate_taps(int(source_rate), int(encoder_rate), C.byref(l), C.byref(m), C.byref(tt))
     if not p:
         return None
     return np.ctypeslib.as_array((C.c_int16 * (l.value * tt.value)).from_address(p)).reshape(l.value, tt.value).copy(), l.value, m.value
@@ -513,6 +551,24 @@ class Tick:
         n = self.L.tlb_tick_need(self.h, s)
         if n < 0:
             raise ToolameError(-n, "tlb_tick_need")
+        return n
+
+    # -- down sources (tlb_tick_set_down_source): legal while no tick is in flight; exclude short reads, sources and feeds --
+    def set_down_source(self, source_rate, stream=-1):
+        rc = self.L.tlb_tick_set_down_source(self.h, stream, int(source_rate))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_set_down_source")
+
+    def down(self, s):
+        """stream s's wide slot (int16 [4608] view) in the input set to fill next; None with two ticks in flight or without any down source"""
+        p = self.L.tlb_tick_down(self.h, s)
+        return np.ctypeslib.as_array((C.c_int16 * DECIMATE_SLOT).from_address(p)) if p else None
+
+    def down_need(self, s):
+        """source frames stream s's wide slot must hold for the next submit (1152 without a down source)"""
+        n = self.L.tlb_tick_down_need(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_tick_down_need")
         return n
 
     # -- Layer II feeds (tlb_tick_set_feed): legal while no tick is in flight; exclude short reads and sources --
@@ -1036,6 +1092,39 @@ class Batch:
             raise ToolameError(rc, "tlb_resample_host")
         return out
 
+    # -- device decimator (tlb_decimate_*): 48 (1/2), 32 (3/4) and 44.1 kHz (80/147) sources for a 24 kHz stream --
+    def set_down_source(self, source_rate, stream=-1):
+        """0 or the stream's own rate: off; waits for queued launches and zeroes the decimator state of the streams it names"""
+        rc = self.L.tlb_decimate_set_source(self.h, stream, int(source_rate))
+        if rc:
+            raise ToolameError(rc, "tlb_decimate_set_source")
+
+    def down_source(self, s):
+        return int(self.L.tlb_decimate_source(self.h, s))
+
+    def down_need(self, s, ahead=0):
+        n = self.L.tlb_decimate_need(self.h, s, ahead)
+        if n < 0:
+            raise ToolameError(-n, "tlb_decimate_need")
+        return n
+
+    def decimate(self, wide, out=None):
+        """int16 [nframes, nstreams, 4608], each slot of a stream with a down source holding down_need() source frames at its start ->
+        int16 [nframes, nstreams, 2304] at the encoder's rate, what ingest() takes.  out: the array to write into (the slots of streams
+        without a down source and whatever else the kernel does not write keep what it held); None: zeros"""
+        a = np.ascontiguousarray(wide, dtype=np.int16)
+        nf = a.shape[0]
+        if a.shape != (nf, self.nstreams, DECIMATE_SLOT):
+            raise ToolameError(18, f"wide shape {a.shape}")
+        if out is None:
+            out = np.zeros((nf, self.nstreams, 2 * SAMPLES), dtype=np.int16)
+        if out.dtype != np.int16 or out.shape != (nf, self.nstreams, 2 * SAMPLES) or not out.flags.c_contiguous:
+            raise ToolameError(18, "out array")
+        rc = self.L.tlb_decimate_host(self.h, a.ctypes.data, nf, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_decimate_host")
+        return out
+
     def ingest(self, interleaved, valid=None):
         """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2]).
         valid: int32 [nframes, nstreams] sample frames each slot delivers -- a short read is stretched over the frame as the reference
@@ -1370,6 +1459,22 @@ class Node:
         n = self.L.tlb_node_need(self.h, s)
         if n < 0:
             raise ToolameError(-n, "tlb_node_need")
+        return n
+
+    # down sources (Tick.set_down_source / down / down_need with node-wide indices; remembered for shard restarts)
+    def set_down_source(self, source_rate, stream=-1):
+        self._rc(self.L.tlb_node_set_down_source(self.h, stream, int(source_rate)), "tlb_node_set_down_source")
+
+    def down(self, s):
+        """the stream's wide slot (int16 [4608] view) in its shard's current input set; None when its shard has no down source, while two
+        ticks are in flight and for a broken or late shard"""
+        p = self.L.tlb_node_down(self.h, s)
+        return np.ctypeslib.as_array((C.c_int16 * DECIMATE_SLOT).from_address(p)) if p else None
+
+    def down_need(self, s):
+        n = self.L.tlb_node_down_need(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_node_down_need")
         return n
 
     # Layer II feeds (Tick.set_feed, per stream with node-wide indices)

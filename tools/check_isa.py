@@ -44,6 +44,8 @@ LIMITS = [
     (re.compile(r"tl_compare_kernel"), dict(vgpr=128, lds=4 * 6560, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # resampler (csrc/toolame_resample.hip): a workgroup per slot with the ratio's table and the slot's source frames in LDS (17 168 bytes)
     (re.compile(r"tl_resample_kernel"), dict(vgpr=128, lds=17168, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # decimator (csrc/toolame_decimate.hip): the same shape with 64 taps and wide slots: 11 520 bytes of table + 9472 of source frames
+    (re.compile(r"tl_decimate_kernel"), dict(vgpr=128, lds=20992, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # adapted feeds (csrc/toolame_feed_adapt.hip): the feed kernel's body and occupancy; the resample kernel's LDS plus 1152 int16 of outputs
     (re.compile(r"tl_feed_adapt_decode_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
     (re.compile(r"tl_feed_adapt_resample_kernel"), dict(vgpr=128, lds=17168 + 2304, vgpr_spill=0, sgpr_spill=0, scratch=0)),
