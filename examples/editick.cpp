@@ -14,6 +14,8 @@
 //   link; in.s16le is not opened (give "-").  Not together with --short-every or --source-rate.
 //   --feed-rate R, --feed-channels C: the file is at another (legal) rate or channel count than the encoder's, an ADAPTED feed
 //   (tlb_tick_set_feed_adapted): on the ticks tlb_tick_feed_want says want no frame the slot stays empty and the file does not advance.
+//   R above the rate of a 24000 Hz encoder (48000, 44100, 32000) is a DOWN FEED (tlb_tick_set_down_feed): every tick takes the one or two
+//   frames tlb_tick_down_feed_want asks for into the stream's two slots, and the device decodes, filters and decimates them.
 //   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
 //   encoder's rate on the device (tlb_tick_set_source): each tick reads tlb_tick_need() source frames per stream, not 1152.  Not together
 //   with --short-every.  R above the rate of a 24000 Hz encoder (48000, 44100, 32000) is a DOWN source (tlb_tick_set_down_source): each tick
@@ -91,7 +93,8 @@ int main(int argc, char **argv)
     std::FILE *fi = feed_path ? nullptr : std::fopen(argv[1], "rb");
     if (!feed_path && !fi) die("cannot open input", 0);
     tlb_feed_config feed = {feed_rate ? feed_rate : rate, feed_kbps, feed_channels ? feed_channels : channels};      // the encoder's unless told otherwise
-    const bool adapt = feed.samplerate != rate || feed.channels != channels;
+    const bool down_feed = feed_path && feed.samplerate > rate;  // a feed above the encoder's rate: two slots per tick, decoded and decimated
+    const bool adapt = !down_feed && (feed.samplerate != rate || feed.channels != channels);
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;                              // --feed: where each frame lies in the file
     if (feed_path) {
@@ -131,7 +134,8 @@ int main(int argc, char **argv)
     const bool down = source_rate > rate;                    // a source above the encoder's rate goes through the decimator and its wide slots
     if (source_rate && !down) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
     if (down) if (int rc = tlb_tick_set_down_source(t, -1, source_rate)) die("tlb_tick_set_down_source", rc);             // likewise
-    if (feed_path && !adapt) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);         // likewise
+    if (down_feed) { if (int rc = tlb_tick_set_down_feed(t, -1, &feed)) die("tlb_tick_set_down_feed", rc); }      // likewise
+    else if (feed_path && !adapt) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);
     if (feed_path && adapt) if (int rc = tlb_tick_set_feed_adapted(t, -1, &feed)) die("tlb_tick_set_feed_adapted", rc);
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
@@ -163,7 +167,26 @@ int main(int argc, char **argv)
                 }
     };
     size_t used = 0;                                             // feed frames stream 0 has been given; stream s is s frames ahead in the file
-    for (; feed_path;) {                                         // one tick per wanted frame of the feed, and the ticks between that want none
+    for (; down_feed;) {                                         // a down feed: one or two frames of the file per tick, as the schedule says
+        const size_t want = (size_t)tlb_tick_down_feed_want(t, 0);   // (every stream has the one configuration: all want the same)
+        if (used + want > fpos.size()) break;
+        uint8_t *fr = tlb_tick_down_feed(t);                         // pinned [nstreams][2][tlb_tick_down_feed_stride()], re-fetched every tick like the PCM
+        int32_t *ln = tlb_tick_down_feed_len(t);                     // pinned [nstreams][2]: every set comes back all 0
+        const size_t stride = (size_t)tlb_tick_down_feed_stride(t);
+        for (int s = 0; s < nstreams; s++)
+            for (size_t j = 0; j < want; j++) {
+                const size_t k = (used + j + (size_t)s) % fpos.size();
+                std::memcpy(fr + stride * (2 * (size_t)s + j), &mp2[fpos[k]], flen[k]);
+                ln[2 * s + (int)j] = (int32_t)flen[k];
+            }
+        used += want;
+        if (int rc = tlb_tick_run(t)) die("tlb_tick_run", rc);
+        const tlb_frame_report *rep = tlb_tick_down_feed_report(t);  // [nstreams][2]; a frame that did not pass went in as silence
+        for (int s = 0; s < 2 * nstreams; s++) bad_feed += (rep[s].status & TLB_DEC_BAD_MASK) != 0;
+        emit();
+        frames++;
+    }
+    for (; feed_path && !down_feed;) {                           // one tick per wanted frame of the feed, and the ticks between that want none
         const bool want = tlb_tick_feed_want(t, 0) > 0;          // (every stream has the one configuration: all want a frame or none does)
         if (want && used == fpos.size()) break;
         uint8_t *fr = tlb_tick_feed(t);                          // pinned [nstreams][tlb_tick_feed_stride()], re-fetched every tick like the PCM

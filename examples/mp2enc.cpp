@@ -15,6 +15,8 @@
 // header's padding bit, and the frames are decoded on the device into the ingest's input (tlb_feed_host) instead of PCM being read.
 // With -r or -c another (legal) rate or channel count than the file's, the feed is an ADAPTED one (tlb_feed_set_adapted): 44.1 kHz for a
 // 48 kHz encoder, stereo for mono, ...; a slot of the call then holds a frame only on the ticks tlb_feed_want_at says want one.
+// A 48, 44.1 or 32 kHz file with -r 24000 is a DOWN FEED (tlb_feed_down_set): a tick has two slots and takes the one or two frames
+// tlb_feed_down_want_at asks for; the device decodes, filters and decimates them (tlb_feed_down_host).
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -77,6 +79,8 @@ int main(int argc, char **argv)
     tlb_feed_config feed = {0, 0, 0};
     std::vector<size_t> fpos, flen;                           // --from-mp2: where each frame lies in the file
     std::vector<long> tick_frame;                             // ... and the frame tick f's slot holds (-1: none is wanted on that tick)
+    std::vector<int> tick_want;                               // a down feed: the frames tick f holds, tick_frame[f] being the first
+    bool down = false;                                        // the file's rate is above the encoder's: a down feed
     if (from_mp2) {
         if (mp2.size() < 4 || mp2[0] != 0xff || (mp2[1] & 0xf6) != 0xf4) die("the input does not begin with a Layer II header", 0);
         const int lsf = !(mp2[1] & 0x08), bi = mp2[2] >> 4, fi2 = (mp2[2] >> 2) & 3;
@@ -94,7 +98,15 @@ int main(int argc, char **argv)
             fpos.push_back(o); flen.push_back(n);
             o += n;
         }
-        for (long f = 0, k = 0;; f++) {                       // one tick per 1152 OUTPUT frames, until a wanted frame is not there
+        down = feed.samplerate > rate;
+        for (long f = 0, k = 0; down; f++) {                  // one tick per 1152 OUTPUT frames, one or two frames each, until a wanted frame is not there
+            const int w = tlb_feed_down_want_at(feed.samplerate, rate, f);
+            if (w < 0) die("the input's rate and -r form no legal pair", -w);
+            if (k + w > (long)fpos.size()) break;
+            tick_frame.push_back(k); tick_want.push_back(w);
+            k += w;
+        }
+        for (long f = 0, k = 0; !down; f++) {                 // one tick per 1152 OUTPUT frames, until a wanted frame is not there
             const int w = tlb_feed_want_at(feed.samplerate, rate, f);
             if (w < 0) die("the input's rate and -r form no legal pair", -w);
             if (w && k == (long)fpos.size()) break;
@@ -113,10 +125,12 @@ int main(int argc, char **argv)
     if (!enc) die("tlb_create", err);
     if (gain_db != 0.0 && (err = tlb_set_gain_db(enc, -1, gain_db)) != TLB_OK) die("tlb_set_gain_db", err);
 
-    const bool adapt = from_mp2 && (rate != feed.samplerate || channels != feed.channels);
-    if (from_mp2 && !adapt && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
+    const bool adapt = from_mp2 && !down && (rate != feed.samplerate || channels != feed.channels);
+    if (down && (err = tlb_feed_down_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_down_set", err);
+    if (from_mp2 && !adapt && !down && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
     if (adapt && (err = tlb_feed_set_adapted(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set_adapted", err);
-    const int fstride = tlb_feed_stride(enc);
+    const int fstride = down ? tlb_feed_down_stride(enc) : tlb_feed_stride(enc);
+    const size_t per_tick = down ? 2 : 1;                     // feed slots per stream and tick
 
     const int stride = tlb_out_stride(enc);
     std::FILE *fo = std::fopen(argv[2], "wb");
@@ -126,10 +140,10 @@ int main(int argc, char **argv)
     std::vector<int16_t> inter((size_t)chunk * nstreams * 2304), pcm((size_t)chunk * nstreams * 2304), peaks((size_t)chunk * nstreams * 2);
     std::vector<uint8_t> out((size_t)chunk * nstreams * stride);
     std::vector<int32_t> len((size_t)chunk * nstreams);
-    std::vector<uint8_t> ffr(from_mp2 ? (size_t)chunk * nstreams * fstride : 0);
-    std::vector<int32_t> fln(from_mp2 ? (size_t)chunk * nstreams : 0);
+    std::vector<uint8_t> ffr(from_mp2 ? (size_t)chunk * nstreams * per_tick * fstride : 0);
+    std::vector<int32_t> fln(from_mp2 ? (size_t)chunk * nstreams * per_tick : 0);
     long bad_feed = 0;
-    std::vector<tlb_frame_report> frep(from_mp2 ? (size_t)chunk * nstreams : 0);
+    std::vector<tlb_frame_report> frep(from_mp2 ? (size_t)chunk * nstreams * per_tick : 0);
     long written = 0, checked = 0;
     std::vector<tlb_frame_report> report(verify ? (size_t)chunk * nstreams : 0);
     // TEST-ONLY hook of this example (tests/test_decode_gpu.py): a byte offset into the first call's frame buffer, flipped before the check
@@ -151,13 +165,23 @@ int main(int argc, char **argv)
         for (int f = 0; f < nf; f++)                         // every stream of the batch gets the same programme
             for (int s = 0; s < nstreams; s++) {
                 const size_t slot = (size_t)f * nstreams + s;
-                if (from_mp2) {
+                if (down) {
+                    for (size_t j = 0; j < 2; j++) {
+                        const long k = tick_frame[(size_t)(f0 + f)] + (long)j;
+                        const bool on = (int)j < tick_want[(size_t)(f0 + f)];
+                        fln[2 * slot + j] = on ? (int32_t)flen[(size_t)k] : 0;
+                        if (on) std::memcpy(&ffr[(2 * slot + j) * fstride], &mp2[fpos[(size_t)k]], flen[(size_t)k]);
+                    }
+                } else if (from_mp2) {
                     const long k = tick_frame[(size_t)(f0 + f)];
                     fln[slot] = k < 0 ? 0 : (int32_t)flen[(size_t)k];
                     if (k >= 0) std::memcpy(&ffr[slot * fstride], &mp2[fpos[(size_t)k]], flen[(size_t)k]);
                 } else std::memcpy(&inter[slot * 2304], &in[(size_t)(f0 + f) * per_frame], per_frame * sizeof(int16_t));
             }
-        if (from_mp2) {                                      // the decode, into what the ingest reads; a frame that does not pass goes in as silence
+        if (down) {                                          // decode, filter and decimate, into what the ingest reads
+            if ((err = tlb_feed_down_host(enc, ffr.data(), fln.data(), inter.data(), frep.data(), nf)) != TLB_OK) die("tlb_feed_down_host", err);
+            for (size_t i = 0; i < (size_t)nf * nstreams; i += (size_t)nstreams) bad_feed += ((frep[2 * i].status | frep[2 * i + 1].status) & TLB_DEC_BAD_MASK) != 0;
+        } else if (from_mp2) {                               // the decode, into what the ingest reads; a frame that does not pass goes in as silence
             if ((err = tlb_feed_host(enc, ffr.data(), fln.data(), nf, inter.data(), frep.data())) != TLB_OK) die("tlb_feed_host", err);
             // (stream 0's reports stand for all: every stream of the batch is given the same file)
             for (size_t i = 0; i < (size_t)nf * nstreams; i += (size_t)nstreams) bad_feed += (frep[i].status & TLB_DEC_BAD_MASK) != 0;

@@ -27,7 +27,9 @@
 //   of the ingest (tlb_node_set_feed): the file is cut into frames by the arithmetic length and each header's padding bit, service s takes
 //   frame (tick + s) of it, wrapping round; no PCM crosses the link and in.s16le is not opened (give "-").  Not together with --short-every
 //   or --source-rate.  --feed-rate R, --feed-channels C: the file is at another (legal) rate or channel count than the services', an ADAPTED
-//   feed (tlb_node_set_feed_adapted): a service's slot gets its next frame only on the ticks tlb_node_feed_want says want one.
+//   feed (tlb_node_set_feed_adapted): a service's slot gets its next frame only on the ticks tlb_node_feed_want says want one.  R above the
+//   rate of 24000 Hz services (48000, 44100, 32000) is a DOWN FEED (tlb_node_set_down_feed): a service's two slots get its next one or two
+//   frames, as tlb_node_down_feed_want says.
 //   --source-rate R: in.s16le is at R Hz (44100 or 32000) and is resampled to 48 kHz on the GPUs (tlb_node_set_source): service s starts
 //   reading at source frame 1152 s and takes tlb_node_need() consecutive frames every tick, wrapping around.  Not together with --short-every.
 //   With -r 24000, R = 48000, 44100 or 32000 is a DOWN source (tlb_node_set_down_source): the tlb_node_down_need() frames of a tick go into
@@ -65,12 +67,28 @@ struct Ctx {
     const std::vector<uint8_t> *mp2;                         // --feed: the file and where its frames lie (NULL: PCM input)
     const std::vector<size_t> *fpos, *flen;
     std::vector<size_t> *fcur;                               // --feed-rate / --feed-channels (an adapted feed): the next frame of every service; NULL: a strict feed
+    bool down_feed;                                          // --feed-rate above the services' rate: two slots per tick, one or two frames as the schedule says
 };
 
 // step 1 on shard `g`'s thread: the block's services copy their frame of this tick into the pinned input set
 static void fill(void *vctx, int g, int first, int n)
 {
     Ctx &c = *(Ctx *)vctx;
+    for (int s = first; s < first + n && c.down_feed; s++) {    // a down feed: the service's next one or two frames into its two slots
+        uint8_t *slot = tlb_node_down_feed(c.nd, s);
+        int32_t *len = tlb_node_down_feed_len(c.nd, s);
+        if (!slot || !len) {
+            if (tlb_node_shard_status(c.nd, g, nullptr) != TLB_SHARD_OK) return;
+            die("no down-feed set free", s);
+        }
+        const size_t stride = (size_t)tlb_node_down_feed_stride(c.nd, s);
+        for (int j = 0; j < tlb_node_down_feed_want(c.nd, s); j++) {
+            const size_t f = (*c.fcur)[(size_t)s]++ % c.fpos->size();
+            std::memcpy(slot + stride * (size_t)j, c.mp2->data() + (*c.fpos)[f], (*c.flen)[f]);
+            len[j] = (int32_t)(*c.flen)[f];                          // untouched, it reads 0: an empty slot
+        }
+    }
+    if (c.down_feed) return;
     for (int s = first; s < first + n && c.mp2; s++) {          // --feed: the service's frame of this tick into its slot of the pinned feed set
         uint8_t *slot = tlb_node_feed(c.nd, s);
         int32_t *len = tlb_node_feed_len(c.nd, s);
@@ -181,7 +199,8 @@ int main(int argc, char **argv)
     if (feed_path.empty() != (feed_kbps <= 0)) die("--feed FILE.mp2 --feed-bitrate K: both or neither", 0);
     if (!feed_rate) feed_rate = rate;
     tlb_feed_config feed = {feed_rate, feed_kbps, feed_channels};   // the services' own rate and channel count unless told otherwise
-    const bool adapt = feed_rate != rate || feed_channels != 2;
+    const bool down_feed = !feed_path.empty() && feed_rate > rate;   // a feed above the services' rate (tlb_node_set_down_feed)
+    const bool adapt = !down_feed && (feed_rate != rate || feed_channels != 2);
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;
     if (!feed_path.empty()) {
@@ -242,7 +261,8 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_set_source(nd, -1, source_rate)) die("tlb_node_set_source", rc);          // between steps; a restarted shard's sources are set again
     if (down)
         if (int rc = tlb_node_set_down_source(nd, -1, source_rate)) die("tlb_node_set_down_source", rc);      // likewise
-    if (!feed_path.empty())
+    if (down_feed) { if (int rc = tlb_node_set_down_feed(nd, -1, &feed)) die("tlb_node_set_down_feed", rc); }       // between steps; a restarted shard's down feeds are set again at tick 0
+    else if (!feed_path.empty())
         if (int rc = adapt ? tlb_node_set_feed_adapted(nd, -1, &feed) : tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare)
@@ -253,7 +273,7 @@ int main(int argc, char **argv)
     std::vector<size_t> spos((size_t)nstreams), fcur((size_t)nstreams);
     for (int s = 0; s < nstreams; s++) fcur[(size_t)s] = (size_t)s;     // an adapted feed: service s starts s frames into the file
     for (int s = 0; s < nstreams && !pcm.empty(); s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, down, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt ? &fcur : nullptr};
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, down, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt || down_feed ? &fcur : nullptr, down_feed};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick

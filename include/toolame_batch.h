@@ -865,8 +865,8 @@ int tlb_node_need(const tlb_node *nd, int stream);
  * do, with the same rules: every pair is checked before a shard is changed, a change made before a device failure half way is rolled back,
  * the source is remembered for tlb_node_shard_restart (fresh state) and forgotten by a tlb_node_stream_reconfigure it no longer pairs with;
  * a stream of a broken or late shard answers NULL, -TLB_ERR_HIP or -TLB_ERR_LATE.
- * NOT BUILT: a channel map for PCM sources (the host's (L + R + 1) >> 1 is cheap, the filter is not); 48 kHz FEEDS for 24 kHz services (two
- * feed frames per slot); 48 -> 44.1 / 32 kHz; encoder rates other than 24 kHz.
+ * NOT BUILT: a channel map for PCM sources (the host's (L + R + 1) >> 1 is cheap, the filter is not); 48 -> 44.1 / 32 kHz; encoder rates
+ * other than 24 kHz.  (48, 44.1 and 32 kHz FEEDS for 24 kHz services: "Down feeds" below, tlb_feed_down_*.)
  * ------------------------------------------------------------------------------------------ */
 #define TLB_DECIMATE_TAPS 64
 #define TLB_DECIMATE_SLOT 4608
@@ -929,7 +929,8 @@ int tlb_node_down_need(const tlb_node *nd, int stream);
  * batch may hold strict feeds, adapted feeds and streams without a feed together: the strict launch runs first where a stream has a
  * strict feed, then one sequence of three kernels (decode, resample, carry) per call, however many ticks it holds, with no host
  * synchronisation inside a call.  A call over a batch with adapted feeds holds at most 8192 ticks (TLB_ERR_ARG beyond).
- * NOT BUILT: downsampling (48 -> 24 kHz, 48 -> 44.1 kHz) and a channel map for PCM sources.
+ * NOT BUILT: 48 -> 44.1 / 32 kHz, 24 kHz feeds for 48 kHz services and a channel map for PCM sources.  A 48, 44.1 or 32 kHz feed for a
+ * 24 kHz service is a family of its own, "Down feeds" below (tlb_feed_down_*): tlb_feed_want_at answers -TLB_ERR_SAMPLERATE for those pairs.
  *   d_frames      uint8 [nframes][nstreams][tlb_feed_stride()]
  *   d_len         int32 [nframes][nstreams], required; 0 (or less) = an empty slot
  *   d_interleaved int16 [nframes][nstreams][2304], tlb_ingest_device's input: a fed stream's slot gets 1152 sample frames, L R L R for two
@@ -1041,6 +1042,101 @@ int tlb_tick_feed_stride(const tlb_tick *t);
 uint8_t *tlb_tick_feed(tlb_tick *t);
 int32_t *tlb_tick_feed_len(tlb_tick *t);
 const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t);
+
+/* ---------------------------------------------------------------------------------------------
+ * Down feeds: 48, 44.1 and 32 kHz Layer II feeds for 24 kHz services, decoded AND decimated on the device, ahead of the ingest.
+ * Half-rate services get their contribution as 48 kHz MPEG Layer II over studio links and satellite; the reference's inputs decode and
+ * convert it in one chain (src/VLCInput.cpp, src/GSTInput.cpp: decode, samplerate=, channels=).  As wide PCM through
+ * tlb_tick_set_down_source such a stream costs 9216 bytes per tick on the link, as two 192 kbps feed frames 1152 + 8.  A family of its own
+ * beside tlb_feed_* (unchanged, in behaviour and in code objects: tlb_feed_want is 0 or 1 with one slot per tick), the way tlb_decimate_*
+ * stands beside tlb_resample_*.  The decode is tlb_feed_*'s, the filter tlb_decimate_*'s; what is new is the schedule with up to TWO feed
+ * frames per tick and the queue between decoder and decimator.
+ * LEGAL PAIRS (feed rate Fs, stream rate Es): the decimator's three, 48000 -> 24000 (L/M = 1/2), 32000 -> 24000 (3/4), 44100 -> 24000
+ * (80/147); anything else is TLB_ERR_SAMPLERATE.  Channels may be 1 or 2 on either side.  Bitrate and legality are tlb_feed_check_config's.
+ * SCHEDULE.  Ticks f are counted from the stream's last reset, in the decimator's own terms:
+ *   S(f) = ceil(1152 f M / L)                 source frames consumed before tick f; S(f + 1) - S(f) is tlb_decimate_need_at
+ *   K(f) = ceil(S(f + 1) / 1152), K(-1) = 0   feed frames that must have arrived by tick f
+ *   want(f) = K(f) - K(f - 1)                 1 or 2
+ * 1/2: 2 on every tick, nothing is left over; 3/4: 2, 1, 1, 2, 1, 1, ... (3 ticks = 4 feed frames), at most 768 decoded source frames are
+ * unconsumed before a tick; 80/147: one frame on 13 of every 80 ticks -- the first are 6, 12, 18, 24, 30, 36, 43, 49 --, two otherwise (80
+ * ticks = 147 feed frames), at most 1137 unconsumed.  A stream's position is its tick counter modulo that period (1, 3, 80), kept on the
+ * device and, as a copy, on the host; with it all arithmetic is 32-bit.
+ * SLOTS.  A tick has TWO slots per stream, [.][s][0] and [.][s][1].  On a tick with want = 1 slot 1 is not read and its bytes do not enter
+ * the history: its report is TLB_DEC_EMPTY, and TLB_DEC_EMPTY | TLB_DEC_UNWANTED when its length was > 0.  Both slots of a stream without
+ * a down feed report TLB_DEC_EMPTY.
+ * AUDIO.  d_k: the 1152 sample frames tlb_feed_* defines for the stream's k-th WANTED frame under the feed's configuration (header rules,
+ * rounding and saturation as there); an empty or not passing frame is zeros; the synthesis history runs over consecutive wanted frames; a
+ * bad or empty frame is silence for its successor.  Channel map on the decoded int16, as for adapted feeds: two to one is (L + R + 1) >> 1,
+ * applied BEFORE the filter; one to two is filtered once and written to both channels.  y(n) is tlb_decimate_*'s formula, unchanged (the
+ * same q, p, table and rounding, 16-tap quarters summed in 32 bits and the quarters in 64), over x = d_0 d_1 ...; tick f's ingest slot gets
+ * y(1152 f .. 1152 f + 1151), interleaved as the ingest reads it; nothing is written behind it.  The output does not depend on how a
+ * stream's ticks are cut into calls.
+ *   d_frames      uint8 [nframes][nstreams][2][tlb_feed_down_stride()]
+ *   d_len         int32 [nframes][nstreams][2], required; 0 (or less) = an empty slot
+ *   d_interleaved int16 [nframes][nstreams][2304], tlb_ingest_device's input.  THE SLOT OF A STREAM WITHOUT A DOWN FEED IS NOT TOUCHED.
+ *   d_report      tlb_frame_report [nframes][nstreams][2] or NULL
+ *   tlb_feed_down_set(b, stream, cfg)  stream = -1: all; cfg = NULL: removed.  Every named stream is checked before anything changes.  It
+ *                                 waits for the queued launches and zeroes the named streams' position, queue and history.  The first real
+ *                                 one allocates (about 11.4 KB per stream of the batch: two copies of a queue head of 1200 source frames,
+ *                                 one history slot of 1728 bytes) and a source plane (9.2 KB per stream and tick of the longest call): a
+ *                                 batch that never sets one allocates nothing and queues exactly the device calls it queued before.
+ *   tlb_feed_down_get(b, stream, cfg)  1 and *cfg (may be NULL) / 0; < 0: -TLB_ERR_ARG
+ *   tlb_feed_down_want(b, stream, ahead)  1 or 2 for the stream's (ahead)-th next tick, from the host's copy of the position (advanced by
+ *                                 every tlb_feed_down_device call, cleared by the resets; no device access); < 0: -TLB_ERR_ARG (also: the
+ *                                 stream has no down feed)
+ *   tlb_feed_down_want_at(Fs, Es, tick)  host only, no batch, no GPU; < 0: -TLB_ERR_SAMPLERATE (no legal pair), -TLB_ERR_ARG (tick < 0)
+ *   tlb_feed_down_stride(b)       the longest down-feed frame of the batch with its padding slot, rounded up to 4; 0: there is none
+ *   tlb_feed_down_reset(b, stream)  the stream's next tick is tick 0, after silence (stream = -1: all)
+ * A STREAM HAS ONE SOURCE.  A down feed on a stream that has a feed (strict or adapted), a tlb_resample_* source or a tlb_decimate_*
+ * source is TLB_ERR_ARG, and so is setting any of those on a stream that has a down feed; removing ("off") is always allowed.  A batch may
+ * hold all four families on different streams: each call leaves the other families' slots alone.
+ * tlb_reset, tlb_stream_reset and tlb_stream_finish zero the position, the queue and the history of the streams they touch.
+ * tlb_stream_reconfigure keeps a down feed, with fresh state, while (Fs, new Es) is still a legal pair, whatever the channel counts, and
+ * removes it otherwise (the call itself succeeds).
+ * Three kernels per call (decode: one wavefront per tick, stream and slot; decimate: one workgroup per tick and stream; carry: one
+ * wavefront per stream), however many ticks it holds, with no host synchronisation between them.  Asynchronous on `hip_stream`; calls of
+ * one batch must be ordered on one stream, ahead of the ingest.  At most 8192 ticks per call; the argument-error rules are
+ * tlb_feed_device's (a NULL batch, frames, lengths or PCM pointer, nframes <= 0, a misaligned pointer, no stream with a down feed:
+ * TLB_ERR_ARG, nothing changed).  tlb_feed_down_host takes host buffers; its `interleaved` is read and written.
+ * TICK PLANE.  tlb_tick_set_down_feed(t, stream, cfg) is legal while no tick is in flight, all or nothing as tlb_tick_set_feed is.
+ * tlb_tick_down_feed(t) is uint8 [nstreams][2][tlb_tick_down_feed_stride()], tlb_tick_down_feed_len(t) int32 [nstreams][2],
+ * tlb_tick_down_feed_report(t) tlb_frame_report [nstreams][2]; lifetime and re-fetch rules are tlb_tick_feed's (pinned, alternating with
+ * the input sets, NULL while two ticks are in flight and while no stream has a down feed, lengths all 0 whenever the caller sees a set
+ * untouched).  tlb_tick_down_feed_want(t, stream) is 1 or 2 for the input set to fill next.  While a stream has a down feed every submit
+ * copies in the group's frames and lengths and queues the three kernels on the run stream ahead of the ingest, under the events that
+ * order feeds; A GROUP ALL OF WHOSE STREAMS HAVE DOWN FEEDS SKIPS ITS PCM COPY-IN; an object that never sets one queues exactly what it
+ * queued before.  On one tick or node object down feeds exclude feeds, sources, down sources and short reads (TLB_ERR_ARG from either
+ * side, in either order).
+ * NODE LEVEL.  tlb_node_set_down_feed routes to the owning shards as tlb_node_set_feed does (every named stream is checked before a shard
+ * is changed, a change made before a device failure half way is rolled back) and is remembered: tlb_node_shard_restart sets the block's
+ * down feeds again at tick 0, tlb_node_stream_reconfigure forgets one that no longer pairs.  tlb_node_down_feed / _len / _report point at
+ * the STREAM's two slots, lengths and reports (tlb_node_down_feed_stride(nd, stream) bytes per slot), tlb_node_down_feed_want is
+ * tlb_tick_down_feed_want of the stream's shard; broken, late and stale shards answer as for tlb_node_feed.  On a BATCH-plane node the
+ * call is tlb_feed_down_set of the shard's batch and tlb_node_down_feed_want answers -TLB_ERR_ARG.
+ * NOT BUILT: 48 -> 44.1 / 32 kHz, 24 kHz feeds for 48 kHz services, down feeds together with short reads, mixing down feeds with the other
+ * source families on ONE tick or node object (batches may mix them).
+ * ------------------------------------------------------------------------------------------ */
+int tlb_feed_down_set(tlb_batch *b, int stream, const tlb_feed_config *cfg);
+int tlb_feed_down_get(const tlb_batch *b, int stream, tlb_feed_config *cfg);
+int tlb_feed_down_want(const tlb_batch *b, int stream, int ahead);
+int tlb_feed_down_want_at(long feed_rate, long stream_rate, long tick);
+int tlb_feed_down_stride(const tlb_batch *b);
+int tlb_feed_down_reset(tlb_batch *b, int stream);
+int tlb_feed_down_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int16_t *d_interleaved, tlb_frame_report *d_report, int nframes,
+                         void *hip_stream);
+int tlb_feed_down_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int16_t *interleaved, tlb_frame_report *report, int nframes);
+int tlb_tick_set_down_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg);
+int tlb_tick_down_feed_stride(const tlb_tick *t);
+uint8_t *tlb_tick_down_feed(tlb_tick *t);
+int32_t *tlb_tick_down_feed_len(tlb_tick *t);
+int tlb_tick_down_feed_want(const tlb_tick *t, int stream);
+const tlb_frame_report *tlb_tick_down_feed_report(const tlb_tick *t);
+int tlb_node_set_down_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg);
+int tlb_node_down_feed_stride(const tlb_node *nd, int stream);
+uint8_t *tlb_node_down_feed(tlb_node *nd, int stream);
+int32_t *tlb_node_down_feed_len(tlb_node *nd, int stream);
+int tlb_node_down_feed_want(const tlb_node *nd, int stream);
+const tlb_frame_report *tlb_node_down_feed_report(const tlb_node *nd, int stream);
 
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);

@@ -13,6 +13,7 @@
 #include "mp2_resample.h"
 #include "mp2_decimate.h"
 #include "mp2_feed_adapt.h"
+#include "mp2_feed_down.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -42,6 +43,8 @@ hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
 hipError_t tlk_feed(hipStream_t st, const TlFeedLaunch &A);
 // toolame_feed_adapt.hip: the decode kernel over every (stream, slot) of the call, the resample kernel (one workgroup per slot), then the carry kernel per stream
 hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A);
+// toolame_feed_down.hip: the decode kernel over every (stream, slot) of the call with two slots per tick, the decimate kernel (one workgroup per tick and stream), then the carry kernel per stream
+hipError_t tlk_feed_down(hipStream_t st, const TlFeedDownLaunch &A);
 // toolame_ingest.hip: tl_ingest_valid_kernel, or tl_ingest_kernel when valid (int32 [nframes][nstreams]) is NULL (one workgroup per slot);
 // tl_silence_kernel and tl_underrun_kernel (256 threads, one per stream)
 hipError_t tlk_ingest(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid /* may be NULL */, int16_t *out, int16_t *peaks, const double *gain,

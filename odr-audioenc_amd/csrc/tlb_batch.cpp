@@ -179,6 +179,7 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
     if (b->d_dec_state) HIPCHK(hipMemset(b->d_dec_state + s0, 0, sizeof(TlDecStream) * (size_t)n));      // the decoder's next frame of these streams is a first frame
     if (b->d_cmp_hist) HIPCHK(hipMemset(b->d_cmp_hist + (size_t)s0 * 2 * TL_CMP_HIST, 0, sizeof(int16_t) * 2 * TL_CMP_HIST * (size_t)n));      // ... and the compare monitor has no input to set their next frame against
     if (int rc = feed_clear_streams(b, s0, n)) return rc;            // ... and a feed's next frame is decoded as after silence
+    if (int rc = feed_down_clear_streams(b, s0, n)) return rc;       // ... and a down feed's next tick is tick 0
     if (int rc = resample_clear_streams(b, s0, n)) return rc;        // ... and the resampler starts these streams' sources at frame 0 again
     return decimate_clear_streams(b, s0, n);                         // ... and so does the decimator
 }
@@ -281,6 +282,7 @@ int tlb_stream_reconfigure(tlb_batch *b, int stream, const tlb_stream_config *cf
         HIPCHK(hipMemcpy(b->d_unit_bytes + stream, &ub, sizeof ub, hipMemcpyHostToDevice));
     }
     if (int rc = feed_after_reconfigure(b, stream)) return rc;       // a feed at another rate or channel count than the stream's new ones is removed
+    if (int rc = feed_down_after_reconfigure(b, stream)) return rc;  // ... and a down feed whose rate no longer pairs with the stream's new one
     return batch_clear_streams(b, stream, 1);
 }
 

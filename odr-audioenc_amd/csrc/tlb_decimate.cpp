@@ -34,6 +34,13 @@ int decimate_clear_streams(tlb_batch *b, int s0, int n)
     return TLB_OK;
 }
 
+int16_t *decimate_taps_upload(TlbMem &m)
+{
+    int16_t *tp = m.scratch<int16_t>(TL_DC_TABLE_ROWS * TL_DC_TAPS);
+    for (int r = TL_DC_80_147; r <= TL_DC_1_2; r++) m.upload(tp + tl_dc_first_row(r) * TL_DC_TAPS, table_of(r), sizeof(int16_t) * TL_DC_TAPS * (size_t)tl_dc_L(r));
+    return tp;
+}
+
 int decimate_prepare(tlb_batch *b)
 {
     if (b->d_dc_state) return TLB_OK;
@@ -41,8 +48,7 @@ int decimate_prepare(tlb_batch *b)
     TlbMem m;
     uint32_t *st = m.dev<uint32_t>(2 * TL_DC_STATE_WORDS * ns);
     int32_t *ra = m.dev<int32_t>(ns);
-    int16_t *tp = m.scratch<int16_t>(TL_DC_TABLE_ROWS * TL_DC_TAPS);
-    for (int r = TL_DC_80_147; r <= TL_DC_1_2; r++) m.upload(tp + tl_dc_first_row(r) * TL_DC_TAPS, table_of(r), sizeof(int16_t) * TL_DC_TAPS * (size_t)tl_dc_L(r));
+    int16_t *tp = decimate_taps_upload(m);
     if (!m.settle()) return TLB_ERR_HIP;
     m.commit(b->mem);
     b->dc_rate.assign(ns, 0); b->dc_ratio.assign(ns, TL_DC_OFF); b->dc_pos.assign(ns, 0);
@@ -76,9 +82,9 @@ int tlb_decimate_set_source(tlb_batch *b, int stream, long source_rate)
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
     bool any = false;
     if (int rc = tlb_down_range(s0, s1, source_rate, [b](int s) { return encoder_rate(b, s); }, &any)) return rc;
-    // a stream has one source: an up source (tlb_resample_set_source) and a down source on the same 24 kHz stream are refused
+    // a stream has one source: an up source (tlb_resample_set_source) or a down feed (tlb_feed_down_set) and a down source on the same 24 kHz stream are refused
     for (int s = s0; any && s < s1; s++)
-        if (tl_dc_ratio_of(source_rate, encoder_rate(b, s)) != TL_DC_OFF && tlb_resample_source(b, s)) return TLB_ERR_ARG;
+        if (tl_dc_ratio_of(source_rate, encoder_rate(b, s)) != TL_DC_OFF && (tlb_resample_source(b, s) || feed_down_on(b, s))) return TLB_ERR_ARG;
     if (!any && !b->d_dc_state) return TLB_OK;                       // off, and never on: nothing to allocate or to clear
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());

@@ -245,6 +245,7 @@ static int feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg, bool a
         HIPCHK(hipDeviceSynchronize());
         return feed_assign(b, s0, s1, -1, tlb_feed_config{0, 0, 0});
     }
+    for (int s = s0; s < s1; s++) if (feed_down_on(b, s)) return TLB_ERR_ARG;      // a stream has one source: not beside a down feed (tlb_feed_down_set)
     if (adapt && feed_fits(b, s0, s1, cfg) == TLB_OK) adapt = false; // a configuration that matches every named stream IS a strict feed
     if (int rc = adapt ? feed_fits_adapted(b, s0, s1, cfg) : feed_fits(b, s0, s1, cfg)) return rc;       // every named stream is checked before anything changes
     int idx = -1;

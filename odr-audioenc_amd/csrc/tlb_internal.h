@@ -124,6 +124,25 @@ struct tlb_batch {
     int16_t *d_fa_plane = nullptr;               // [nstreams][fa_plane_frames * 2304] grow-only launch scratch with an owner of its own
     std::unique_ptr<TlbMem> fa_plane_mem;
     int fa_plane_frames = 0, fa_flip = 0;
+    // down feeds (tlb_feed_down.cpp; csrc/mp2_feed_down.h), allocated by the first tlb_feed_down_set: a batch that never sets one has none of
+    // it.  Records, history and reports of their own: nothing is shared with the feeds above but the synthesis tables
+    std::vector<tlb_feed_config> fd_cfg;         // [nstreams] the stream's down feed (empty until the first set)
+    std::vector<int32_t> fd_idx;                 // [nstreams] its record in h_fd_configs, -1: none
+    std::vector<int32_t> fd_ratio, fd_pos;       // [nstreams] TL_DC_* of (feed rate, stream rate); host copy of the tick counter modulo the cycle
+    std::vector<tlb_feed_config> h_fd_uniq;      // the three knobs of h_fd_configs[i]; grow-only
+    std::vector<TlConfig> h_fd_configs;
+    TlConfig *d_fd_configs = nullptr;            // replaced when it grows: an owner of its own
+    std::unique_ptr<TlbMem> fd_cfg_mem, fd_plane_mem, fd_rep_mem;
+    size_t fd_cfg_cap = 0, fd_rep_slots = 0;
+    int n_down = 0, fd_plane_frames = 0, fd_flip = 0;
+    int32_t *d_fd_cfg = nullptr, *d_fd_ratio = nullptr;      // [nstreams] fd_idx, fd_ratio on the device
+    int32_t *d_fd_pos = nullptr;                 // [2][nstreams]; a call reads copy fd_flip and writes the other
+    int16_t *d_fd_carry = nullptr;               // [2][nstreams][TL_FD_CARRY * 2], likewise
+    TlDecStream *d_fd_state = nullptr;           // [nstreams] length and status of the last wanted slot of the call before
+    uint8_t *d_fd_prev = nullptr;                // [nstreams][TL_FD_PREV_STRIDE] its bytes
+    int16_t *d_fd_taps = nullptr;                // the decimator's three tables, a copy of the down feeds' own
+    int16_t *d_fd_plane = nullptr;               // [nstreams][fd_plane_frames * TL_FD_PLANE] grow-only launch scratch with an owner of its own
+    tlb_frame_report *d_fd_rep = nullptr;        // reports of a call that asked for none, likewise
     TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -181,4 +200,15 @@ bool resample_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
 int decimate_prepare(tlb_batch *b);
 int decimate_clear_streams(tlb_batch *b, int s0, int n);
 bool decimate_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
+int16_t *decimate_taps_upload(TlbMem &m);        // the three tables in one buffer of m: [80][64], [3][64], [1][64] (the decimator's copy, and the down feeds')
+// tlb_feed_down.cpp: has the stream a down feed (a stream has ONE source: the other families ask before they set theirs); the position,
+// queue and history of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); after a reconfiguration, the stream's
+// down feed removed when its rate no longer pairs with the stream's
+bool feed_down_on(const tlb_batch *b, int stream);
+int feed_down_clear_streams(tlb_batch *b, int s0, int n);
+int feed_down_after_reconfigure(tlb_batch *b, int stream);
+// ... what the tick plane needs of it: is cfg legal and does it pair with streams [s0, s1) (nothing changes); tlb_feed_down_device with
+// slots of `stride` bytes, at least tlb_feed_down_stride(b)
+int feed_down_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
+int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int16_t *d_interleaved, tlb_frame_report *d_report, int nframes, void *hip_stream, int stride);
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -168,6 +168,8 @@ struct tlb_node {
     std::vector<Feed> feed;           // tlb_node_set_feed(): the feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
     bool any_feed() const { for (const Feed &f : feed) if (f.bitrate) return true; return false; }
+    std::vector<Feed> dfeed;          // tlb_node_set_down_feed(): the down feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
+    bool any_dfeed() const { for (const Feed &f : dfeed) if (f.bitrate) return true; return false; }
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
@@ -349,6 +351,11 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         const tlb_node::Feed &f = nd->feed[(size_t)(s.first + k)];
         if (!f.bitrate) continue;
         if (int rc = s.tick ? (f.adapted ? tlb_tick_set_feed_adapted : tlb_tick_set_feed)(s.tick, k, &f) : (f.adapted ? tlb_feed_set_adapted : tlb_feed_set)(s.batch, k, &f)) return rc;
+    }
+    for (int k = 0; k < s.n && !nd->dfeed.empty(); k++) {            // the caller's down feeds, at tick 0
+        const tlb_node::Feed &f = nd->dfeed[(size_t)(s.first + k)];
+        if (!f.bitrate) continue;
+        if (int rc = s.tick ? tlb_tick_set_down_feed(s.tick, k, &f) : tlb_feed_down_set(s.batch, k, &f)) return rc;
     }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
@@ -597,7 +604,7 @@ int tlb_node_enable_short_reads(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
     for (long r : nd->source) if (r) return TLB_ERR_ARG;             // a source and short reads exclude each other (include/toolame_batch.h)
-    if (nd->any_feed() || nd->any_down()) return TLB_ERR_ARG;        // ... and so do a feed or a down source and short reads
+    if (nd->any_feed() || nd->any_down() || nd->any_dfeed()) return TLB_ERR_ARG;      // ... and so do a feed, a down source or a down feed and short reads
     if (nd->short_reads) return TLB_OK;
     const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
     if (!rc) nd->short_reads = true;
@@ -657,7 +664,7 @@ int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     bool any = false;
     if (int rc = tlb_source_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
-    if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && (nd->any_feed() || nd->any_down())))) return TLB_ERR_ARG;
+    if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && (nd->any_feed() || nd->any_down() || nd->any_dfeed())))) return TLB_ERR_ARG;
     return nd->set_remembered(stream, nd->source, any, source_rate,
         [](Shard &sh, int k, long r) { return sh.tick ? tlb_tick_set_source(sh.tick, k, r) : tlb_resample_set_source(sh.batch, k, r); },
         [&](int i) { return source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate; });      // (the encoder's own rate is no source)
@@ -670,7 +677,7 @@ int tlb_node_set_down_source(tlb_node *nd, int stream, long source_rate)
     bool any = false;
     if (int rc = tlb_down_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
     if (any && nd->plane == TLB_NODE_TICK) {                         // down sources exclude short reads, sources and feeds on one object (include/toolame_batch.h)
-        if (nd->short_reads || nd->any_feed()) return TLB_ERR_ARG;
+        if (nd->short_reads || nd->any_feed() || nd->any_dfeed()) return TLB_ERR_ARG;
         for (long r : nd->source) if (r) return TLB_ERR_ARG;
     }
     return nd->set_remembered(stream, nd->down, any, source_rate,
@@ -704,7 +711,7 @@ static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, b
         if (nd->plane == TLB_NODE_TICK) {                            // feeds exclude short reads and sources on one object (include/toolame_batch.h)
             if (nd->short_reads) return TLB_ERR_ARG;
             for (long r : nd->source) if (r) return TLB_ERR_ARG;
-            if (nd->any_down()) return TLB_ERR_ARG;
+            if (nd->any_down() || nd->any_dfeed()) return TLB_ERR_ARG;
         }
     }
     tlb_node::Feed v = {};
@@ -739,6 +746,49 @@ uint8_t *tlb_node_feed(tlb_node *nd, int stream)
 int32_t *tlb_node_feed_len(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_feed_len>(nd, stream); }
 int tlb_node_feed_stride(const tlb_node *nd, int stream) { return ask<INPUT>(nd, stream, 0, [](tlb_tick *t, int) { return tlb_tick_feed_stride(t); }); }
 const tlb_frame_report *tlb_node_feed_report(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_feed_report>(nd, stream); }
+// A down feed for one stream or all (cfg = NULL: removed; remembered as bitrate 0), the same way (tlb_tick_set_down_feed / tlb_feed_down_set
+// of the owning shards' objects).  Every named stream is checked before a shard is asked.
+int tlb_node_set_down_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
+{
+    if (!nd || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
+    if (cfg) {
+        if (int rc = tlb_feed_check_config(cfg)) return rc;
+        for (int i = s0; i < s1; i++) if (tl_dc_ratio_of(cfg->samplerate, nd->cfgs[(size_t)i].samplerate) == TL_DC_OFF) return TLB_ERR_SAMPLERATE;
+        if (nd->plane == TLB_NODE_TICK) {                            // (the legal pairs are the decimator's three) down feeds exclude short reads, sources, down sources and feeds on one object (include/toolame_batch.h)
+            if (nd->short_reads || nd->any_feed() || nd->any_down()) return TLB_ERR_ARG;
+            for (long r : nd->source) if (r) return TLB_ERR_ARG;
+        }
+    }
+    tlb_node::Feed v = {};
+    if (cfg) { v.samplerate = cfg->samplerate; v.bitrate = cfg->bitrate; v.channels = cfg->channels; }
+    return nd->set_remembered(stream, nd->dfeed, cfg != nullptr, v,
+        [](Shard &sh, int k, const tlb_node::Feed &f) {
+            const tlb_feed_config *c = f.bitrate ? &f : nullptr;
+            return sh.tick ? tlb_tick_set_down_feed(sh.tick, k, c) : tlb_feed_down_set(sh.batch, k, c);
+        },
+        [&](int) { return v; });
+}
+// the feed frames wanted in the stream's two slots of its shard's current input set (TICK plane; broken and late shards answer as tlb_node_need does)
+int tlb_node_down_feed_want(const tlb_node *nd, int stream)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK) return -TLB_ERR_ARG;
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return -rc;
+    return s->tick ? tlb_tick_down_feed_want(s->tick, k) : -TLB_ERR_HIP;
+}
+// the stream's two slots of its shard's down-feed buffers: NULL for a broken or a late shard, while two ticks are in flight and while no
+// stream of the shard has a down feed
+uint8_t *tlb_node_down_feed(tlb_node *nd, int stream)
+{
+    return ask<INPUT>(nd, stream, (uint8_t *)nullptr, [](tlb_tick *t, int k) {
+        uint8_t *p = tlb_tick_down_feed(t);
+        return p ? p + 2 * (size_t)k * (size_t)tlb_tick_down_feed_stride(t) : nullptr;      // (one slot width for the whole object: the tick's own)
+    });
+}
+int32_t *tlb_node_down_feed_len(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_down_feed_len>(nd, stream, 2); }
+int tlb_node_down_feed_stride(const tlb_node *nd, int stream) { return ask<INPUT>(nd, stream, 0, [](tlb_tick *t, int) { return tlb_tick_down_feed_stride(t); }); }
+const tlb_frame_report *tlb_node_down_feed_report(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_down_feed_report>(nd, stream, 2); }
 int tlb_node_need(const tlb_node *nd, int stream)
 {
     if (!nd || nd->plane != TLB_NODE_TICK) return -TLB_ERR_ARG;
@@ -867,6 +917,7 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
         const bool fits = f.adapted ? node_rates_adapt(f.samplerate, cfg->samplerate) : f.samplerate == cfg->samplerate && f.channels == (cfg->mode == 'm' ? 1 : 2);
         if (f.bitrate && !fits) f = tlb_node::Feed{};
     }
+    if (!rc && !nd->dfeed.empty() && tl_dc_ratio_of(nd->dfeed[(size_t)stream].samplerate, cfg->samplerate) == TL_DC_OFF) nd->dfeed[(size_t)stream] = tlb_node::Feed{};      // (a down feed that no longer pairs has been removed)
     return rc;
 }
 

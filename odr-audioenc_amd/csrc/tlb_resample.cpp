@@ -86,6 +86,9 @@ int tlb_resample_set_source(tlb_batch *b, int stream, long source_rate)
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
     bool any = false;
     if (int rc = tlb_source_range(s0, s1, source_rate, [b](int s) { return encoder_rate(b, s); }, &any)) return rc;
+    // a stream has one source: not beside a down feed (tlb_feed_down_set)
+    for (int s = s0; any && s < s1; s++)
+        if (tl_rs_ratio_of(source_rate, encoder_rate(b, s)) != TL_RS_OFF && feed_down_on(b, s)) return TLB_ERR_ARG;
     if (!any && !b->d_rs_state) return TLB_OK;                       // off, and never on: nothing to allocate or to clear
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());

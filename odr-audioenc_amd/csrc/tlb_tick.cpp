@@ -39,6 +39,9 @@ struct TickGroup {
     // Layer II feeds (tlb_tick_set_feed): the group's slice of the tick's feed frames and lengths, the feed call's reports
     uint8_t *d_feed = nullptr; int32_t *d_feed_len = nullptr; tlb_frame_report *d_feed_report = nullptr;
     bool any_fed = false, all_fed = false;                      // some / every stream of the group has a feed (all: the group's PCM is not copied in)
+    // down feeds (tlb_tick_set_down_feed): the same three with TWO slots per stream
+    uint8_t *d_dfeed = nullptr; int32_t *d_dfeed_len = nullptr; tlb_frame_report *d_dfeed_report = nullptr;
+    bool any_dfed = false, all_dfed = false;                    // some / every stream of the group has a down feed (all: the group's PCM is not copied in)
     // down sources (tlb_tick_set_down_source): the group's slice of the tick's wide slots; the decimator writes the streams' slots of d_inter
     int16_t *d_wide = nullptr;
     bool any_down = false, all_down = false;                    // some / every stream of the group has a down source (all: the group's PCM is not copied in)
@@ -80,6 +83,12 @@ struct tlb_tick {
     int feed_stride = 0;
     uint8_t *h_feed[2] = {}; int32_t *h_feed_len[2] = {}; tlb_frame_report *h_feed_report[3] = {};
     std::unique_ptr<TlbMem> feed_mem;            // owns h_feed[] and the groups' d_feed
+    // down feeds, off until the first tlb_tick_set_down_feed: as the feeds' buffers, with two slots per stream ([nstreams][2][dfeed_stride],
+    // lengths and reports [nstreams][2]) and owners of their own
+    bool dfeed = false;                          // at least one stream has a down feed
+    int dfeed_stride = 0;
+    uint8_t *h_dfeed[2] = {}; int32_t *h_dfeed_len[2] = {}; tlb_frame_report *h_dfeed_report[3] = {};
+    std::unique_ptr<TlbMem> dfeed_mem;           // owns h_dfeed[] and the groups' d_dfeed
     // compare monitor, off until tlb_tick_enable_compare(): needs the AUDIO monitor's decoded PCM; its records travel with the output sets too
     bool compare = false;
     tlb_compare_params cparams = {};
@@ -248,7 +257,7 @@ const uint32_t *tlb_tick_underruns(const tlb_tick *t) { return t && t->short_rea
 // call makes the device calls it always made.
 int tlb_tick_enable_short_reads(tlb_tick *t)
 {
-    if (!t || t->finished || t->ticks > 0 || t->resample || t->feed || t->down) return TLB_ERR_ARG;      // (a source, a down source or a feed and short reads exclude each other: include/toolame_batch.h)
+    if (!t || t->finished || t->ticks > 0 || t->resample || t->feed || t->down || t->dfeed) return TLB_ERR_ARG;      // (a source, a down source, a feed or a down feed and short reads exclude each other: include/toolame_batch.h)
     if (t->broken) return TLB_ERR_HIP;
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
@@ -353,7 +362,7 @@ int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
             return e;
         })) return rc;
     if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
-    if (any && (t->short_reads || t->feed || t->down)) return TLB_ERR_ARG;
+    if (any && (t->short_reads || t->feed || t->down || t->dfeed)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
     if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer, and the resampler of the batches that get
         TlbMem m;                                                    // a source, before anything is committed or a stream is changed
@@ -389,7 +398,7 @@ int tlb_tick_set_down_source(tlb_tick *t, int stream, long source_rate)
             return e;
         })) return rc;
     if (!any && !t->h_wide[0]) return TLB_OK;                        // off, and never on: nothing to allocate or to clear
-    if (any && (t->short_reads || t->feed || t->resample)) return TLB_ERR_ARG;
+    if (any && (t->short_reads || t->feed || t->resample || t->dfeed)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
     if (!t->h_wide[0]) {                                             // first real down source: the wide buffers, and the decimator of the batches that get
         TlbMem m;                                                    // one, before anything is committed or a stream is changed
@@ -447,7 +456,7 @@ static int tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg, bo
     if (!cfg && !t->h_feed_len[0]) return TLB_OK;                    // off, and never on: nothing to allocate or to clear
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
     if (cfg) {
-        if (t->short_reads || t->resample || t->down) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads, sources and down sources)
+        if (t->short_reads || t->resample || t->down || t->dfeed) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads, sources, down sources and down feeds)
         // every stream is checked before one is changed
         if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return (adapt ? feed_fits_adapted : feed_fits)(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
     }
@@ -514,6 +523,89 @@ uint8_t *tlb_tick_feed(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->
 int32_t *tlb_tick_feed_len(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed_len[t->in_set] : nullptr; }
 int tlb_tick_feed_stride(const tlb_tick *t) { return t && t->feed ? t->feed_stride : 0; }
 const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t) { return t && t->feed ? t->h_feed_report[t->out_set] : nullptr; }
+// A down feed for one stream or all (tlb_feed_down_set of the group's batch), while no tick is in flight: tick_set_feed with two slots per
+// stream.  An object that never sets one makes the device calls it always made.
+static void tick_dfeed_refresh(tlb_tick *t)
+{
+    t->dfeed = false;
+    for (auto &G : t->groups) {
+        int fed = 0;
+        for (int k = 0; k < G.n; k++) fed += tlb_feed_down_get(G.b, k, nullptr) > 0;
+        G.any_dfed = fed > 0; G.all_dfed = fed == G.n;
+        t->dfeed |= G.any_dfed;
+        // a group without a fed stream runs no down-feed kernel: its slots read EMPTY (no tick is in flight, or the device has been waited for)
+        if (!G.any_dfed && t->h_dfeed_report[0])
+            for (int k = 0; k < 3; k++) for (int i = 0; i < 2 * G.n; i++) { tlb_frame_report r = {}; r.status = TLB_DEC_EMPTY; t->h_dfeed_report[k][2 * G.first + i] = r; }
+    }
+}
+int tlb_tick_set_down_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
+{
+    if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (!cfg && !t->h_dfeed_len[0]) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
+    if (cfg) {
+        if (t->short_reads || t->resample || t->down || t->feed) return TLB_ERR_ARG;       // (include/toolame_batch.h: down feeds exclude short reads, sources, down sources and feeds)
+        // every stream is checked before one is changed
+        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return feed_down_fits(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
+    }
+    HIPCHK(hipSetDevice(t->device));
+    const size_t ns = (size_t)t->nstreams;
+    if (!t->h_dfeed_len[0]) {                                        // the first down feed: lengths and reports, made once
+        TlbMem m;
+        std::vector<TickGroup> gs = t->groups;
+        int32_t *h_len[2]; tlb_frame_report *h_rep[3];
+        for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(2 * ns);
+        for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(2 * ns);
+        for (auto &G : gs) { G.d_dfeed_len = m.dev<int32_t>(2 * (size_t)G.n); G.d_dfeed_report = m.dev<tlb_frame_report>(2 * (size_t)G.n); }
+        if (!m.settle()) return TLB_ERR_HIP;
+        m.commit(t->mem);
+        t->groups.swap(gs);
+        memcpy(t->h_dfeed_len, h_len, sizeof h_len); memcpy(t->h_dfeed_report, h_rep, sizeof h_rep);
+    }
+    const int want = cfg ? feed_slot_bytes(cfg) : 0;
+    if (want > t->dfeed_stride) {                                    // wider slots: new frame buffers, all of them before any is let go (no tick is in flight)
+        std::unique_ptr<TlbMem> m(new TlbMem);                       // stage, settle, then the owners change places: the narrower buffers go with the old one
+        uint8_t *h[2];
+        std::vector<uint8_t *> d(t->groups.size(), nullptr);
+        for (int k = 0; k < 2; k++) h[k] = m->pinned<uint8_t>(2 * ns * (size_t)want);
+        for (size_t g = 0; g < d.size(); g++) d[g] = m->scratch<uint8_t>(2 * (size_t)t->groups[g].n * (size_t)want);
+        if (!m->settle()) return TLB_ERR_HIP;
+        t->dfeed_mem.swap(m);
+        for (int k = 0; k < 2; k++) t->h_dfeed[k] = h[k];
+        for (size_t g = 0; g < d.size(); g++) t->groups[g].d_dfeed = d[g];
+        t->dfeed_stride = want;
+    }
+    // what the named streams have now: after a device failure half way the groups already changed get it back (fresh state), so that
+    // "all or nothing" holds for the down feeds themselves; the wider buffers stay
+    std::vector<tlb_feed_config> before(ns, tlb_feed_config{0, 0, 0});
+    for (auto &G : t->groups) for (int k = 0; k < G.n; k++) (void)tlb_feed_down_get(G.b, k, &before[(size_t)(G.first + k)]);
+    const int rc = t->blocks.visit(stream, [&](int g, int k) {
+        const int e = tlb_feed_down_set(t->groups[(size_t)g].b, k, cfg);
+        if (e) t->blocks.visit_range(s0, s1, [&](int u, int l0, int l1) {      // the named streams of the groups up to and including this one
+            const TickGroup &U = t->groups[(size_t)u];
+            for (int i = l0; i < l1 && u <= g; i++) {
+                const tlb_feed_config &f = before[(size_t)(U.first + i)];
+                (void)tlb_feed_down_set(U.b, i, f.bitrate ? &f : nullptr);
+            }
+            return 0;
+        });
+        return e;
+    });
+    tick_dfeed_refresh(t);
+    for (int k = 0; k < 2; k++) memset(t->h_dfeed_len[k], 0, 2 * ns * sizeof(int32_t));
+    return rc;
+}
+// the feed frames wanted in the stream's slots of the input set to fill next (the group's batch advances its position with every submit)
+int tlb_tick_down_feed_want(const tlb_tick *t, int stream)
+{
+    int k; const TickGroup *G = tick_group_of(t, stream, &k);
+    return G ? tlb_feed_down_want(G->b, k, 0) : -TLB_ERR_ARG;
+}
+uint8_t *tlb_tick_down_feed(tlb_tick *t) { return tick_input_free(t) && t->dfeed ? t->h_dfeed[t->in_set] : nullptr; }
+int32_t *tlb_tick_down_feed_len(tlb_tick *t) { return tick_input_free(t) && t->dfeed ? t->h_dfeed_len[t->in_set] : nullptr; }
+int tlb_tick_down_feed_stride(const tlb_tick *t) { return t && t->dfeed ? t->dfeed_stride : 0; }
+const tlb_frame_report *tlb_tick_down_feed_report(const tlb_tick *t) { return t && t->dfeed ? t->h_dfeed_report[t->out_set] : nullptr; }
 int tlb_tick_need(const tlb_tick *t, int stream)
 {
     int k; const TickGroup *G = tick_group_of(t, stream, &k);
@@ -551,6 +643,7 @@ int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config
     if (t->broken) return TLB_ERR_HIP;
     const int rc = tlb_stream_reconfigure(G->b, k, cfg);
     if (t->feed) tick_feed_refresh(t);                               // (a feed the stream's new rate or channel count no longer fits has been removed)
+    if (t->dfeed) tick_dfeed_refresh(t);                             // (... and so has a down feed whose rate no longer pairs with the stream's)
     return rc;
 }
 
@@ -586,6 +679,7 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
     // (tlb_tick_finish runs no feed kernel: its set shows the last tick's reports once more)
     if (G.any_fed) HIPCHK(hipMemcpyAsync(t->h_feed_report[set] + G.first, G.d_feed_report, n * sizeof(tlb_frame_report), hipMemcpyDeviceToHost, t->s_out));
+    if (G.any_dfed) HIPCHK(hipMemcpyAsync(t->h_dfeed_report[set] + 2 * (size_t)G.first, G.d_dfeed_report, 2 * n * sizeof(tlb_frame_report), hipMemcpyDeviceToHost, t->s_out));
     if (t->short_reads) {
         HIPCHK(hipMemcpyAsync(t->h_underrun_ms[set] + G.first, G.d_underrun_ms, n * 4, hipMemcpyDeviceToHost, t->s_out));
         HIPCHK(hipMemcpyAsync(t->h_underruns[set] + G.first, G.d_underruns, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -706,9 +800,12 @@ int tlb_tick_submit(tlb_tick *t)
         if (t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_ingested, 0);
         // a group all of whose streams have feeds takes no PCM over the link: the feed kernel writes every slot the ingest reads
         // ... nor does a group all of whose streams have down sources: its wide slice comes in instead and the decimator writes every slot
-        if (e == hipSuccess && !G.all_fed && !G.all_down) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
+        // ... nor a group all of whose streams have down feeds
+        if (e == hipSuccess && !G.all_fed && !G.all_down && !G.all_dfed) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed, t->h_feed[set] + (size_t)G.first * (size_t)t->feed_stride, n * (size_t)t->feed_stride, hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed_len, t->h_feed_len[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && G.any_dfed) e = hipMemcpyAsync(G.d_dfeed, t->h_dfeed[set] + 2 * (size_t)G.first * (size_t)t->dfeed_stride, 2 * n * (size_t)t->dfeed_stride, hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && G.any_dfed) e = hipMemcpyAsync(G.d_dfeed_len, t->h_dfeed_len[set] + 2 * (size_t)G.first, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && G.any_down) e = hipMemcpyAsync(G.d_wide, t->h_wide[set] + (size_t)G.first * TLB_DECIMATE_SLOT, n * TLB_DECIMATE_SLOT * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->short_reads) e = hipMemcpyAsync(G.d_valid, t->h_valid[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->with_xpad && t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_encoded, 0);
@@ -719,6 +816,7 @@ int tlb_tick_submit(tlb_tick *t)
         if (e == hipSuccess && t->ticks > 0) e = hipStreamWaitEvent(t->s_run, G.ev_out, 0);
         if (e != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc && G.any_fed) rc = feed_launch(G.b, G.d_feed, G.d_feed_len, 1, G.d_inter, G.d_feed_report, t->s_run, t->feed_stride);      // behind the copy-in, ahead of the ingest: a mixed group's fed slots are overwritten
+        if (!rc && G.any_dfed) rc = feed_down_launch(G.b, G.d_dfeed, G.d_dfeed_len, G.d_inter, G.d_dfeed_report, 1, t->s_run, t->dfeed_stride);      // likewise: decode, decimate, carry
         if (!rc && t->resample) rc = tlb_resample_device(G.b, G.d_inter, 1, G.d_rs, t->s_run);
         if (!rc && G.any_down) rc = tlb_decimate_device(G.b, G.d_wide, 1, G.d_inter, t->s_run);      // behind the copy-in, ahead of the ingest: a mixed group's decimated slots are overwritten
         if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, t->resample ? G.d_rs : G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
@@ -753,6 +851,7 @@ int tlb_tick_wait(tlb_tick *t)
     // the retired tick's input set goes back to the caller (now, or after the next submit): untouched streams are full reads
     if (t->short_reads) { int32_t *v = t->h_valid[t->waited & 1]; for (int i = 0; i < t->nstreams; i++) v[i] = TLB_SAMPLES_PER_FRAME; }
     if (t->h_feed_len[0]) memset(t->h_feed_len[t->waited & 1], 0, (size_t)t->nstreams * sizeof(int32_t));      // ... and feed slots are empty
+    if (t->h_dfeed_len[0]) memset(t->h_dfeed_len[t->waited & 1], 0, 2 * (size_t)t->nstreams * sizeof(int32_t));
     t->waited++;
     return TLB_OK;
 }

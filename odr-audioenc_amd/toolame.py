@@ -330,6 +330,27 @@ def _bind(L):
         L.tlb_tick_feed_want.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_set_feed_adapted.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.tlb_node_feed_want.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_feed_down_set"):          # down feeds: 48, 44.1 and 32 kHz Layer II feeds for 24 kHz streams, two slots per tick
+        L.tlb_feed_down_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_feed_down_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_feed_down_want.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.tlb_feed_down_want_at.argtypes = [C.c_long, C.c_long, C.c_long]
+        L.tlb_feed_down_stride.argtypes = [C.c_void_p]
+        L.tlb_feed_down_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_feed_down_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_feed_down_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.tlb_tick_set_down_feed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        for f in ("tlb_tick_down_feed", "tlb_tick_down_feed_len", "tlb_tick_down_feed_report"):
+            getattr(L, f).restype = C.c_void_p
+            getattr(L, f).argtypes = [C.c_void_p]
+        L.tlb_tick_down_feed_stride.argtypes = [C.c_void_p]
+        L.tlb_tick_down_feed_want.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_set_down_feed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        for f in ("tlb_node_down_feed", "tlb_node_down_feed_len", "tlb_node_down_feed_report"):
+            getattr(L, f).restype = C.c_void_p
+            getattr(L, f).argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_down_feed_stride.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_down_feed_want.argtypes = [C.c_void_p, C.c_int]
     L.toolame_set_samplerate.argtypes = [C.c_long]
     L.toolame_set_channel_mode.argtypes = [C.c_char]
     L.toolame_encode_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
@@ -394,6 +415,14 @@ def feed_want_at(feed_rate, rate, tick):
     n = load_library().tlb_feed_want_at(feed_rate, rate, tick)
     if n < 0:
         raise ToolameError(-n, "tlb_feed_want_at")
+    return n
+
+
+def down_feed_want_at(feed_rate, rate, tick):
+    """tlb_feed_down_want_at: 1 / 2, the feed frames of `feed_rate` wanted on tick `tick` (from the reset) of a stream at `rate` (24 kHz); host arithmetic, no GPU"""
+    n = load_library().tlb_feed_down_want_at(feed_rate, rate, tick)
+    if n < 0:
+        raise ToolameError(-n, "tlb_feed_down_want_at")
     return n
 
 
@@ -608,6 +637,43 @@ class Tick:
         if not p:
             return None
         return np.frombuffer((C.c_uint8 * (self.nstreams * FRAME_REPORT_DTYPE.itemsize)).from_address(p), dtype=FRAME_REPORT_DTYPE)
+
+    # -- down feeds (tlb_tick_set_down_feed): legal while no tick is in flight; exclude short reads, sources, down sources and feeds --
+    def set_down_feed(self, stream, cfg):
+        """stream = -1: every stream; cfg = None removes the down feed.  `down_feed`, `down_feed_len` must be fetched again afterwards."""
+        c = _c_feed(cfg) if cfg is not None else None
+        rc = self.L.tlb_tick_set_down_feed(self.h, stream, C.byref(c) if c is not None else None)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_set_down_feed")
+
+    def down_feed_want(self, s):
+        """1 / 2: the feed frames wanted in stream s's two slots of the input set to fill next"""
+        n = self.L.tlb_tick_down_feed_want(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_tick_down_feed_want")
+        return n
+
+    @property
+    def down_feed_stride(self):
+        return self.L.tlb_tick_down_feed_stride(self.h)
+
+    @property
+    def down_feed(self):
+        """uint8 [nstreams, 2, down_feed_stride] of the input set to fill next; None when no down feed is set or while two ticks are in flight"""
+        return self._view("tlb_tick_down_feed", C.c_uint8, (self.nstreams, 2, self.down_feed_stride)) if self.down_feed_stride else None
+
+    @property
+    def down_feed_len(self):
+        """int32 [nstreams, 2] of the input set to fill next: the frames' bytes, 0 (an empty slot) unless the caller writes more"""
+        return self._view("tlb_tick_down_feed_len", C.c_int32, (self.nstreams, 2)) if self.down_feed_stride else None
+
+    @property
+    def down_feed_report(self):
+        """FRAME_REPORT_DTYPE [nstreams, 2] of the tick waited for last; None when no down feed is set"""
+        p = self.L.tlb_tick_down_feed_report(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (2 * self.nstreams * FRAME_REPORT_DTYPE.itemsize)).from_address(p), dtype=FRAME_REPORT_DTYPE).reshape(self.nstreams, 2)
 
     # -- short reads (src/odr-audioenc.cpp:335-373,910-935): opt in before the first submit --
     def enable_short_reads(self):
@@ -977,6 +1043,68 @@ class Batch:
         rc = self.L.tlb_feed_device(self.h, d_frames_ptr, d_len_ptr, nframes, d_interleaved_ptr, d_report_ptr, stream)
         if rc:
             raise ToolameError(rc, "tlb_feed_device")
+
+    # -- down feeds: a 48, 44.1 or 32 kHz Layer II feed for a 24 kHz stream, decoded and decimated into the ingest's input (tlb_feed_down_*) --
+    def set_down_feed(self, stream, cfg):
+        """stream = -1: every stream; cfg = None removes the down feed.  Legal pairs: 48 / 44.1 / 32 kHz -> 24 kHz, 1 or 2 channels on either
+        side; a stream that has a feed, a source or a down source is refused (a stream has one source)."""
+        c = _c_feed(cfg) if cfg is not None else None
+        rc = self.L.tlb_feed_down_set(self.h, stream, C.byref(c) if c is not None else None)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_down_set")
+
+    def down_feed_cfg(self, stream):
+        c = _CFeedConfig()
+        n = self.L.tlb_feed_down_get(self.h, stream, C.byref(c))
+        if n < 0:
+            raise ToolameError(-n, "tlb_feed_down_get")
+        return FeedConfig(c.samplerate, c.bitrate, c.channels) if n else None
+
+    def down_feed_want(self, s, ahead=0):
+        """1 / 2: the feed frames wanted on stream s's (ahead)-th next tick; host arithmetic"""
+        n = self.L.tlb_feed_down_want(self.h, s, ahead)
+        if n < 0:
+            raise ToolameError(-n, "tlb_feed_down_want")
+        return n
+
+    @property
+    def down_feed_stride(self):
+        """bytes per slot of down_feed(): it changes with set_down_feed"""
+        return self.L.tlb_feed_down_stride(self.h)
+
+    def down_feed_reset(self, stream=-1):
+        rc = self.L.tlb_feed_down_reset(self.h, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_down_reset")
+
+    def down_feed(self, frames, lens, interleaved=None):
+        """frames uint8 [nframes, nstreams, 2, down_feed_stride], lens int32 [nframes, nstreams, 2] (0: an empty slot; slot 1 is read on a
+        tick that wants two frames) -> (interleaved int16 [nframes, nstreams, 2304] as ingest() takes it, reports FRAME_REPORT_DTYPE
+        [nframes, nstreams, 2]).  `interleaved`: the PCM of the streams WITHOUT a down feed, whose slots the call does not touch (None:
+        zeros); it is not changed, a copy is returned."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        nf = frames.shape[0]
+        if frames.shape != (nf, self.nstreams, 2, self.down_feed_stride):
+            raise ToolameError(18, f"frames shape {frames.shape}")
+        ln = np.ascontiguousarray(lens, dtype=np.int32)
+        if ln.shape != (nf, self.nstreams, 2):
+            raise ToolameError(18, "lens shape")
+        if interleaved is None:
+            out = np.zeros((nf, self.nstreams, 2 * SAMPLES), dtype=np.int16)
+        else:
+            out = np.array(interleaved, dtype=np.int16, order="C", copy=True)
+            if out.shape != (nf, self.nstreams, 2 * SAMPLES):
+                raise ToolameError(18, f"interleaved shape {out.shape}")
+        rep = np.zeros((nf, self.nstreams, 2), dtype=FRAME_REPORT_DTYPE)
+        rc = self.L.tlb_feed_down_host(self.h, frames.ctypes.data, ln.ctypes.data, out.ctypes.data, rep.ctypes.data, nf)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_down_host")
+        return out, rep
+
+    def down_feed_device(self, d_frames_ptr, d_len_ptr, d_interleaved_ptr, nframes, d_report_ptr=None, stream=None):
+        rc = self.L.tlb_feed_down_device(self.h, d_frames_ptr, d_len_ptr, d_interleaved_ptr, d_report_ptr, nframes, stream)
+        if rc:
+            raise ToolameError(rc, "tlb_feed_down_device")
 
     def monitor(self, report, pcm=None, record=None):
         """tlb_monitor_host: fold reports FRAME_REPORT_DTYPE [nframes, nstreams] (and the decoded pcm int16 [nframes, nstreams, 2, 1152] or
@@ -1508,6 +1636,38 @@ class Node:
         if not p:
             return None
         return np.frombuffer((C.c_uint8 * FRAME_REPORT_DTYPE.itemsize).from_address(p), dtype=FRAME_REPORT_DTYPE)[0].copy()
+
+    # down feeds (Tick.set_down_feed, per stream with node-wide indices)
+    def set_down_feed(self, stream, cfg):
+        """stream = -1: every stream; cfg = None removes the down feed; between steps only"""
+        c = _c_feed(cfg) if cfg is not None else None
+        self._rc(self.L.tlb_node_set_down_feed(self.h, stream, C.byref(c) if c is not None else None), "tlb_node_set_down_feed")
+
+    def down_feed_want(self, s):
+        """1 / 2: the feed frames wanted in the stream's two slots of its shard's current input set (TICK plane)"""
+        n = self.L.tlb_node_down_feed_want(self.h, s)
+        if n < 0:
+            raise ToolameError(-n, "tlb_node_down_feed_want")
+        return n
+
+    def down_feed(self, s):
+        """the stream's two slots (uint8 view [2, stride]) in its shard's current input set; None when its shard has no down feed, while two
+        ticks are in flight and for a broken or late shard"""
+        p = self.L.tlb_node_down_feed(self.h, s)
+        n = self.L.tlb_node_down_feed_stride(self.h, s)
+        return np.ctypeslib.as_array((C.c_uint8 * (2 * n)).from_address(p)).reshape(2, n) if p and n else None
+
+    def down_feed_len(self, s):
+        """the stream's two lengths (int32 view [2]) in its shard's current input set"""
+        p = self.L.tlb_node_down_feed_len(self.h, s)
+        return np.ctypeslib.as_array((C.c_int32 * 2).from_address(p)) if p else None
+
+    def down_feed_report(self, s):
+        """the stream's two reports (FRAME_REPORT_DTYPE [2], copied) of the step waited for last; None for a broken, late or stale shard"""
+        p = self.L.tlb_node_down_feed_report(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (2 * FRAME_REPORT_DTYPE.itemsize)).from_address(p), dtype=FRAME_REPORT_DTYPE).copy()
 
     # short reads (Tick.enable_short_reads, per stream with node-wide indices)
     def enable_short_reads(self):

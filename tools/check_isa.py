@@ -49,6 +49,9 @@ LIMITS = [
     # adapted feeds (csrc/toolame_feed_adapt.hip): the feed kernel's body and occupancy; the resample kernel's LDS plus 1152 int16 of outputs
     (re.compile(r"tl_feed_adapt_decode_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
     (re.compile(r"tl_feed_adapt_resample_kernel"), dict(vgpr=128, lds=17168 + 2304, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # down feeds (csrc/toolame_feed_down.hip): the feed kernel's body and occupancy; the decimate kernel's LDS plus 1152 int16 of outputs
+    (re.compile(r"tl_feed_down_decode_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
+    (re.compile(r"tl_feed_down_decimate_kernel"), dict(vgpr=128, lds=20992 + 2304, vgpr_spill=0, sgpr_spill=0, scratch=0)),
 ]
 
 
