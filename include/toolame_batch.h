@@ -768,7 +768,8 @@ const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream);
  * keeps its own copy of the position (advanced per call, cleared by the resets): tlb_resample_need never touches the device.
  *   tlb_resample_set_source(b, stream, rate)  stream = -1: every stream; rate 0 or the stream's own encoder rate: off.  Waits for the queued
  *                                 launches and zeroes the resampler state of the streams it names; the encoder is left alone.  An illegal
- *                                 pair for any named stream: TLB_ERR_SAMPLERATE, nothing changed.
+ *                                 pair for any named stream: TLB_ERR_SAMPLERATE, nothing changed.  A stream that has a tlb_decimate_* down
+ *                                 source: TLB_ERR_ARG, nothing changed (a stream has one source).
  *   tlb_resample_source           the stream's source rate; 0: off
  *   tlb_resample_need(b, s, ahead) source frames the stream's (ahead)-th next frame consumes (ahead = 0: the next one); 1152 for a stream
  *                                 without a source; < 0: -TLB_ERR_ARG

@@ -16,7 +16,6 @@ static int need_of(int ratio, long frame)
     const long long L = tl_dc_L(ratio), M = tl_dc_M(ratio), f = frame % tl_dc_cycle(ratio);      // the phase repeats with the cycle
     return (int)((1152 * (f + 1) * M + L - 1) / L - (1152 * f * M + L - 1) / L);
 }
-static long encoder_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
 static const int16_t *table_of(int ratio) { return ratio == TL_DC_80_147 ? &tl_decimate_taps_80_147[0][0] : ratio == TL_DC_3_4 ? &tl_decimate_taps_3_4[0][0] : &tl_decimate_taps_1_2[0][0]; }
 
 bool decimate_rate_fits(const tlb_batch *b, int stream, long rate)
@@ -81,16 +80,15 @@ int tlb_decimate_set_source(tlb_batch *b, int stream, long source_rate)
     if (!b || stream < -1 || stream >= b->nstreams || source_rate < 0) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
     bool any = false;
-    if (int rc = tlb_down_range(s0, s1, source_rate, [b](int s) { return encoder_rate(b, s); }, &any)) return rc;
-    // a stream has one source: an up source (tlb_resample_set_source) or a down feed (tlb_feed_down_set) and a down source on the same 24 kHz stream are refused
-    for (int s = s0; any && s < s1; s++)
-        if (tl_dc_ratio_of(source_rate, encoder_rate(b, s)) != TL_DC_OFF && (tlb_resample_source(b, s) || feed_down_on(b, s))) return TLB_ERR_ARG;
+    if (int rc = tlb_rate_range(s0, s1, source_rate, tlb_down_pair, [b](int s) { return batch_enc_rate(b, s); }, &any)) return rc;
+    for (int s = s0; any && s < s1; s++)                             // a stream has one source (csrc/tlb_inputs.h)
+        if (tlb_down_pair(source_rate, batch_enc_rate(b, s)) && !batch_may_set(b, s, TLB_IN_DOWN_SOURCE)) return TLB_ERR_ARG;
     if (!any && !b->d_dc_state) return TLB_OK;                       // off, and never on: nothing to allocate or to clear
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = decimate_prepare(b)) return rc;
     std::vector<int32_t> ratio((size_t)(s1 - s0));
-    for (int s = s0; s < s1; s++) ratio[(size_t)(s - s0)] = tl_dc_ratio_of(source_rate, encoder_rate(b, s));
+    for (int s = s0; s < s1; s++) ratio[(size_t)(s - s0)] = tl_dc_ratio_of(source_rate, batch_enc_rate(b, s));
     HIPCHK(hipMemcpy(b->d_dc_ratio + s0, ratio.data(), sizeof(int32_t) * ratio.size(), hipMemcpyHostToDevice));
     for (int s = s0; s < s1; s++) {
         b->dc_ratio[(size_t)s] = ratio[(size_t)(s - s0)];

@@ -6,20 +6,18 @@
 #include "tlb_internal.h"
 
 static_assert(TLB_DEC_UNWANTED == TL_DEC_UNWANTED && !(TL_DEC_UNWANTED & TL_DEC_BAD_MASK), "status flags");
-static long enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
 static bool adapted(const tlb_batch *b, int s) { return !b->fa_ratio.empty() && b->fa_ratio[(size_t)s] >= 0; }
 
 static char feed_mode(int channels) { return channels == 1 ? 'm' : 's'; }
 // the feed's kernel-side record: the stream configuration a frame of that rate, bitrate and channel count has (allocation table, sblimit,
 // frame length, header indices); the mode is the frame's own and the model plays no part
-static int feed_build(TlConfig *c, const tlb_feed_config *cfg)
+int feed_build(TlConfig *c, const tlb_feed_config *cfg)
 {
     if (!cfg) return TLB_ERR_ARG;
     if (cfg->channels != 1 && cfg->channels != 2) return TLB_ERR_MODE;
     if (cfg->bitrate <= 0) return TLB_ERR_BITRATE;
     return tl_build_config(c, cfg->samplerate, feed_mode(cfg->channels), cfg->bitrate, 1, 0);
 }
-static bool feed_same(const tlb_feed_config &a, const tlb_feed_config &b) { return a.samplerate == b.samplerate && a.bitrate == b.bitrate && a.channels == b.channels; }
 
 int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 {
@@ -35,7 +33,7 @@ int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 int feed_fits_adapted(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 {
     if (int rc = tlb_feed_check_config(cfg)) return rc;
-    for (int s = s0; s < s1; s++) if (tl_fa_ratio_of(cfg->samplerate, enc_rate(b, s)) < 0) return TLB_ERR_SAMPLERATE;
+    for (int s = s0; s < s1; s++) if (tl_fa_ratio_of(cfg->samplerate, batch_enc_rate(b, s)) < 0) return TLB_ERR_SAMPLERATE;
     return TLB_OK;
 }
 
@@ -73,7 +71,7 @@ static int feed_prepare(tlb_batch *b)
     m.upload(fc, none.data(), sizeof(int32_t) * n);
     if (!m.settle()) return TLB_ERR_HIP;
     m.commit(b->mem);
-    b->feed_cfg.assign(n, tlb_feed_config{0, 0, 0}); b->feed_idx.assign(n, -1);
+    b->feed.start(n);
     b->d_feed_cfg = fc; b->d_feed_state = st;
     return TLB_OK;
 }
@@ -109,30 +107,19 @@ static int adapt_prepare(tlb_batch *b)
     return TLB_OK;
 }
 
-// room for `count` records in d_feed_configs and for slots of `stride` bytes in d_feed_prev; what they hold is kept (the device is idle)
-static int feed_reserve(tlb_batch *b, size_t count, int stride)
+// room for slots of `stride` bytes in d_feed_prev; what it holds is kept (the device is idle).  An owner of its own (csrc/tlb_mem.h): the new
+// buffer is staged and filled in a new owner, and only when it is complete do the owners change places
+static int feed_prev_reserve(tlb_batch *b, int stride)
 {
-    // each of the two has an owner of its own (csrc/tlb_mem.h): the new buffer is staged and filled in a new owner, and only when it is
-    // complete do the owners change places -- the old buffer goes with the old owner, a failure leaves everything as it was
-    if (count > b->feed_cfg_cap) {
-        std::unique_ptr<TlbMem> m(new TlbMem);
-        const size_t cap = count + 4;
-        TlConfig *nd = m->scratch<TlConfig>(cap);
-        if (!b->h_feed_configs.empty()) m->upload(nd, b->h_feed_configs.data(), sizeof(TlConfig) * b->h_feed_configs.size());
-        if (!m->settle()) return TLB_ERR_HIP;
-        b->feed_cfg_mem.swap(m);
-        b->d_feed_configs = nd; b->feed_cfg_cap = cap;
-    }
-    if (stride > b->feed_prev_stride) {
-        std::unique_ptr<TlbMem> m(new TlbMem);
-        uint8_t *np = m->dev<uint8_t>((size_t)b->nstreams * (size_t)stride);
-        if (m->failed()) return TLB_ERR_HIP;
-        if (b->d_feed_prev)
-            HIPCHK(hipMemcpy2D(np, (size_t)stride, b->d_feed_prev, (size_t)b->feed_prev_stride, (size_t)b->feed_prev_stride, (size_t)b->nstreams, hipMemcpyDeviceToDevice));
-        if (!m->settle()) return TLB_ERR_HIP;
-        b->feed_prev_mem.swap(m);
-        b->d_feed_prev = np; b->feed_prev_stride = stride;
-    }
+    if (stride <= b->feed_prev_stride) return TLB_OK;
+    std::unique_ptr<TlbMem> m(new TlbMem);
+    uint8_t *np = m->dev<uint8_t>((size_t)b->nstreams * (size_t)stride);
+    if (m->failed()) return TLB_ERR_HIP;
+    if (b->d_feed_prev)
+        HIPCHK(hipMemcpy2D(np, (size_t)stride, b->d_feed_prev, (size_t)b->feed_prev_stride, (size_t)b->feed_prev_stride, (size_t)b->nstreams, hipMemcpyDeviceToDevice));
+    if (!m->settle()) return TLB_ERR_HIP;
+    b->feed_prev_mem.swap(m);
+    b->d_feed_prev = np; b->feed_prev_stride = stride;
     return TLB_OK;
 }
 
@@ -144,24 +131,24 @@ static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_con
     HIPCHK(hipMemcpy(b->d_feed_cfg + s0, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
     if (b->d_fa_cfg) {
         std::vector<int32_t> a((size_t)(s1 - s0), adapt ? idx : -1), r((size_t)(s1 - s0), 0);
-        for (int s = s0; s < s1 && adapt; s++) r[(size_t)(s - s0)] = tl_fa_ratio_of(cfg.samplerate, enc_rate(b, s));
+        for (int s = s0; s < s1 && adapt; s++) r[(size_t)(s - s0)] = tl_fa_ratio_of(cfg.samplerate, batch_enc_rate(b, s));
         HIPCHK(hipMemcpy(b->d_fa_cfg + s0, a.data(), sizeof(int32_t) * a.size(), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b->d_fa_ratio + s0, r.data(), sizeof(int32_t) * r.size(), hipMemcpyHostToDevice));
         for (int s = s0; s < s1; s++) b->fa_ratio[(size_t)s] = adapt && idx >= 0 ? r[(size_t)(s - s0)] : -1;
         b->n_adapted = 0;
         for (int32_t x : b->fa_ratio) b->n_adapted += x >= 0;
     }
-    for (int s = s0; s < s1; s++) { b->feed_idx[(size_t)s] = idx; b->feed_cfg[(size_t)s] = cfg; }
+    for (int s = s0; s < s1; s++) { b->feed.idx[(size_t)s] = idx; b->feed.cfg[(size_t)s] = cfg; }
     return feed_clear_streams(b, s0, s1 - s0);
 }
 
 int feed_after_reconfigure(tlb_batch *b, int stream)
 {
-    if (b->feed_idx.empty() || b->feed_idx[(size_t)stream] < 0) return TLB_OK;
+    if (!b->feed.on(stream)) return TLB_OK;
     const tlb_stream_config &sc = b->h_uniq[(size_t)b->h_stream_cfg[(size_t)stream]];
-    const tlb_feed_config fc = b->feed_cfg[(size_t)stream];
+    const tlb_feed_config fc = b->feed.cfg[(size_t)stream];
     if (adapted(b, stream)) {                                        // kept while the rates still form a legal pair, whatever the channel counts; the caller clears the state
-        if (tl_fa_ratio_of(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed_idx[(size_t)stream], fc, true);
+        if (tl_fa_ratio_of(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed.idx[(size_t)stream], fc, true);
     } else if (fc.samplerate == sc.samplerate && fc.channels == (sc.mode == 'm' ? 1 : 2)) return TLB_OK;
     return feed_assign(b, stream, stream + 1, -1, tlb_feed_config{0, 0, 0});
 }
@@ -174,20 +161,9 @@ int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int
     if (tlb_feed_stride(b) == 0 || stride < tlb_feed_stride(b) || (stride & 3)) return TLB_ERR_ARG;      // (0: no stream has a feed)
     if (b->broken) return TLB_ERR_HIP;
     HIPCHK(hipSetDevice(b->device));
-    if (!d_report) {                             // the history pass reads the last slot's status: a report buffer of the batch's own, grow-only
-        const size_t slots = (size_t)nframes * (size_t)b->nstreams;
-        if (b->feed_rep_slots < slots) {
-            HIPCHK(hipDeviceSynchronize());      // (a launch before may still write the one it replaces)
-            std::unique_ptr<TlbMem> m(new TlbMem);
-            tlb_frame_report *nr = m->scratch<tlb_frame_report>(slots);
-            if (m->failed()) return TLB_ERR_HIP;
-            b->feed_rep_mem.swap(m);
-            b->d_feed_rep = nr; b->feed_rep_slots = slots;
-        }
-        d_report = b->d_feed_rep;
-    }
+    if (int rc = b->feed.report((size_t)nframes * (size_t)b->nstreams, &d_report)) return rc;
     int n_strict = 0;
-    for (int s = 0; s < b->nstreams; s++) n_strict += b->feed_idx[(size_t)s] >= 0 && !adapted(b, s);
+    for (int s = 0; s < b->nstreams; s++) n_strict += b->feed.on(s) && !adapted(b, s);
     if (b->n_adapted) {
         if (nframes > TL_FA_MAX_FRAMES) return TLB_ERR_ARG;
         if (nframes > b->fa_plane_frames) {
@@ -197,7 +173,7 @@ int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int
     }
     TlFeedLaunch A;
     memset(&A, 0, sizeof A);
-    A.tables = b->d_tables; A.configs = b->d_feed_configs; A.feed_cfg = b->d_feed_cfg; A.synth = b->d_synth;
+    A.tables = b->d_tables; A.configs = b->feed.d_configs; A.feed_cfg = b->d_feed_cfg; A.synth = b->d_synth;
     A.frames = d_frames; A.len = d_len; A.report = (TlFrameReport *)d_report; A.pcm = d_interleaved;
     A.state = b->d_feed_state; A.prev = b->d_feed_prev; A.prev_stride = b->feed_prev_stride;
     A.nstreams = b->nstreams; A.nframes = nframes; A.stride = stride;
@@ -245,25 +221,21 @@ static int feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg, bool a
         HIPCHK(hipDeviceSynchronize());
         return feed_assign(b, s0, s1, -1, tlb_feed_config{0, 0, 0});
     }
-    for (int s = s0; s < s1; s++) if (feed_down_on(b, s)) return TLB_ERR_ARG;      // a stream has one source: not beside a down feed (tlb_feed_down_set)
+    for (int s = s0; s < s1; s++) if (!batch_may_set(b, s, TLB_IN_FEED)) return TLB_ERR_ARG;      // a stream has one source (csrc/tlb_inputs.h)
     if (adapt && feed_fits(b, s0, s1, cfg) == TLB_OK) adapt = false; // a configuration that matches every named stream IS a strict feed
     if (int rc = adapt ? feed_fits_adapted(b, s0, s1, cfg) : feed_fits(b, s0, s1, cfg)) return rc;       // every named stream is checked before anything changes
-    int idx = -1;
-    for (size_t i = 0; i < b->h_feed_uniq.size(); i++) if (feed_same(b->h_feed_uniq[i], *cfg)) idx = (int)i;
+    int idx = b->feed.find(*cfg);
     TlConfig *c = new TlConfig;
     struct Free { TlConfig *c; ~Free() { delete c; } } free_{c};
-    if (idx >= 0) *c = b->h_feed_configs[(size_t)idx];
+    if (idx >= 0) *c = b->feed.h_configs[(size_t)idx];
     else if (int rc = feed_build(c, cfg)) return rc;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = feed_prepare(b)) return rc;
     if (adapt) if (int rc = adapt_prepare(b)) return rc;
-    if (int rc = feed_reserve(b, b->h_feed_configs.size() + (idx < 0 ? 1 : 0), tl_feed_slot_bytes(*c))) return rc;
-    if (idx < 0) {
-        idx = (int)b->h_feed_configs.size();
-        HIPCHK(hipMemcpy(b->d_feed_configs + idx, c, sizeof(TlConfig), hipMemcpyHostToDevice));
-        b->h_feed_configs.push_back(*c); b->h_feed_uniq.push_back(*cfg);
-    }
+    if (int rc = b->feed.reserve(b->feed.h_configs.size() + (idx < 0 ? 1 : 0))) return rc;
+    if (int rc = feed_prev_reserve(b, tl_feed_slot_bytes(*c))) return rc;
+    if (int rc = b->feed.add(*cfg, *c, &idx)) return rc;
     return feed_assign(b, s0, s1, idx, *cfg, adapt);
 }
 
@@ -286,7 +258,7 @@ int tlb_feed_want_at(long feed_rate, long stream_rate, long tick)
 
 int tlb_feed_want(const tlb_batch *b, int stream, int ahead)
 {
-    if (!b || stream < 0 || stream >= b->nstreams || ahead < 0 || b->feed_idx.empty() || b->feed_idx[(size_t)stream] < 0) return -TLB_ERR_ARG;
+    if (!b || stream < 0 || stream >= b->nstreams || ahead < 0 || !b->feed.on(stream)) return -TLB_ERR_ARG;
     if (!adapted(b, stream)) return 1;
     const int ratio = b->fa_ratio[(size_t)stream];
     return tl_fa_want((int)(((long long)b->fa_pos[(size_t)stream] + ahead) % tl_fa_cycle(ratio)), ratio);
@@ -295,17 +267,12 @@ int tlb_feed_want(const tlb_batch *b, int stream, int ahead)
 int tlb_feed_get(const tlb_batch *b, int stream, tlb_feed_config *cfg)
 {
     if (!b || stream < 0 || stream >= b->nstreams) return -TLB_ERR_ARG;
-    const bool on = !b->feed_idx.empty() && b->feed_idx[(size_t)stream] >= 0;
-    if (cfg) *cfg = on ? b->feed_cfg[(size_t)stream] : tlb_feed_config{0, 0, 0};
+    const bool on = b->feed.on(stream);
+    if (cfg) *cfg = on ? b->feed.cfg[(size_t)stream] : tlb_feed_config{0, 0, 0};
     return on ? 1 : 0;
 }
 
-int tlb_feed_stride(const tlb_batch *b)
-{
-    int stride = 0;
-    if (b) for (int idx : b->feed_idx) if (idx >= 0 && tl_feed_slot_bytes(b->h_feed_configs[(size_t)idx]) > stride) stride = tl_feed_slot_bytes(b->h_feed_configs[(size_t)idx]);
-    return stride;
-}
+int tlb_feed_stride(const tlb_batch *b) { return b ? b->feed.stride() : 0; }
 
 int tlb_feed_reset(tlb_batch *b, int stream)
 {

@@ -2,19 +2,14 @@
 // Layer II feed for a 24 kHz stream.  The schedule (host only), the per-stream feed table, history, queue heads and positions (allocated by
 // the first tlb_feed_down_set), the call-sized source plane and one launch of the three kernels of toolame_feed_down.hip through
 // tl_kernels.h.  Host C++.  A family of its own beside tlb_feed_* (csrc/tlb_feed.cpp), which it leaves as it is: it shares that family's
-// legality check and the decimator's committed tables and nothing else -- records, history and reports are its own.
+// legality check and record builder, the FeedTable type (csrc/tlb_internal.h) and the decimator's committed tables -- the records, history
+// and reports themselves are its own.
 #include "tlb_internal.h"
-
-static long enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
-static bool feed_same(const tlb_feed_config &a, const tlb_feed_config &b) { return a.samplerate == b.samplerate && a.bitrate == b.bitrate && a.channels == b.channels; }
-static int feed_build(TlConfig *c, const tlb_feed_config *cfg) { return tl_build_config(c, cfg->samplerate, cfg->channels == 1 ? 'm' : 's', cfg->bitrate, 1, 0); }
-
-bool feed_down_on(const tlb_batch *b, int s) { return !b->fd_idx.empty() && b->fd_idx[(size_t)s] >= 0; }
 
 int feed_down_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg)
 {
     if (int rc = tlb_feed_check_config(cfg)) return rc;
-    for (int s = s0; s < s1; s++) if (tl_fd_ratio_of(cfg->samplerate, enc_rate(b, s)) == TL_DC_OFF) return TLB_ERR_SAMPLERATE;
+    for (int s = s0; s < s1; s++) if (tl_fd_ratio_of(cfg->samplerate, batch_enc_rate(b, s)) == TL_DC_OFF) return TLB_ERR_SAMPLERATE;
     return TLB_OK;
 }
 
@@ -60,23 +55,8 @@ static int down_prepare(tlb_batch *b)
     if (m.failed()) return TLB_ERR_HIP;
     if (int rc = plane_reserve(b, 1)) return rc;                     // (settles; a plane without the rest is scratch nobody reads)
     m.commit(b->mem);
-    b->fd_cfg.assign(n, tlb_feed_config{0, 0, 0}); b->fd_idx.assign(n, -1); b->fd_ratio.assign(n, TL_DC_OFF); b->fd_pos.assign(n, 0);
+    b->fd.start(n); b->fd_ratio.assign(n, TL_DC_OFF); b->fd_pos.assign(n, 0);
     b->d_fd_cfg = fc; b->d_fd_ratio = ra; b->d_fd_pos = po; b->d_fd_state = st; b->d_fd_prev = pv; b->d_fd_carry = ca; b->d_fd_taps = tp; b->fd_flip = 0;
-    return TLB_OK;
-}
-
-// room for `count` records in d_fd_configs; what it holds is kept (the device is idle).  The new buffer is staged and filled in a new
-// owner, and only when it is complete do the owners change places (csrc/tlb_mem.h)
-static int configs_reserve(tlb_batch *b, size_t count)
-{
-    if (count <= b->fd_cfg_cap) return TLB_OK;
-    std::unique_ptr<TlbMem> m(new TlbMem);
-    const size_t cap = count + 4;
-    TlConfig *nd = m->scratch<TlConfig>(cap);
-    if (!b->h_fd_configs.empty()) m->upload(nd, b->h_fd_configs.data(), sizeof(TlConfig) * b->h_fd_configs.size());
-    if (!m->settle()) return TLB_ERR_HIP;
-    b->fd_cfg_mem.swap(m);
-    b->d_fd_configs = nd; b->fd_cfg_cap = cap;
     return TLB_OK;
 }
 
@@ -84,24 +64,24 @@ static int configs_reserve(tlb_batch *b, size_t count)
 static int down_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_config &cfg)
 {
     std::vector<int32_t> v((size_t)(s1 - s0), idx), r((size_t)(s1 - s0), TL_DC_OFF);
-    for (int s = s0; s < s1 && idx >= 0; s++) r[(size_t)(s - s0)] = tl_fd_ratio_of(cfg.samplerate, enc_rate(b, s));
+    for (int s = s0; s < s1 && idx >= 0; s++) r[(size_t)(s - s0)] = tl_fd_ratio_of(cfg.samplerate, batch_enc_rate(b, s));
     HIPCHK(hipMemcpy(b->d_fd_cfg + s0, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b->d_fd_ratio + s0, r.data(), sizeof(int32_t) * r.size(), hipMemcpyHostToDevice));
-    for (int s = s0; s < s1; s++) { b->fd_idx[(size_t)s] = idx; b->fd_cfg[(size_t)s] = cfg; b->fd_ratio[(size_t)s] = r[(size_t)(s - s0)]; }
+    for (int s = s0; s < s1; s++) { b->fd.idx[(size_t)s] = idx; b->fd.cfg[(size_t)s] = cfg; b->fd_ratio[(size_t)s] = r[(size_t)(s - s0)]; }
     b->n_down = 0;
-    for (int32_t x : b->fd_idx) b->n_down += x >= 0;
+    for (int32_t x : b->fd.idx) b->n_down += x >= 0;
     return feed_down_clear_streams(b, s0, s1 - s0);
 }
 
 int feed_down_after_reconfigure(tlb_batch *b, int stream)
 {
-    if (!feed_down_on(b, stream)) return TLB_OK;
-    const tlb_feed_config fc = b->fd_cfg[(size_t)stream];
-    if (tl_fd_ratio_of(fc.samplerate, enc_rate(b, stream)) != TL_DC_OFF) return TLB_OK;      // kept, whatever the channel counts; the caller clears the state
+    if (!b->fd.on(stream)) return TLB_OK;
+    const tlb_feed_config fc = b->fd.cfg[(size_t)stream];
+    if (tl_fd_ratio_of(fc.samplerate, batch_enc_rate(b, stream)) != TL_DC_OFF) return TLB_OK;      // kept, whatever the channel counts; the caller clears the state
     return down_assign(b, stream, stream + 1, -1, tlb_feed_config{0, 0, 0});
 }
 
-int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int16_t *d_interleaved, tlb_frame_report *d_report, int nframes, void *hip_stream, int stride)
+int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride)
 {
     if (!b || !d_frames || !d_len || !d_interleaved || nframes <= 0 || nframes > TL_FD_MAX_FRAMES || (long long)nframes * b->nstreams > (1ll << 29)) return TLB_ERR_ARG;
     // the kernels move frames and PCM as 32-bit words and store 32-bit report fields
@@ -109,25 +89,14 @@ int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len
     if (tlb_feed_down_stride(b) == 0 || stride < tlb_feed_down_stride(b) || (stride & 3)) return TLB_ERR_ARG;      // (0: no stream has a down feed)
     if (b->broken) return TLB_ERR_HIP;
     HIPCHK(hipSetDevice(b->device));
-    if (!d_report) {                             // the carry pass reads the last wanted slot's status: a report buffer of the batch's own, grow-only
-        const size_t slots = 2 * (size_t)nframes * (size_t)b->nstreams;
-        if (b->fd_rep_slots < slots) {
-            HIPCHK(hipDeviceSynchronize());      // (a launch before may still write the one it replaces)
-            std::unique_ptr<TlbMem> m(new TlbMem);
-            tlb_frame_report *nr = m->scratch<tlb_frame_report>(slots);
-            if (m->failed()) return TLB_ERR_HIP;
-            b->fd_rep_mem.swap(m);
-            b->d_fd_rep = nr; b->fd_rep_slots = slots;
-        }
-        d_report = b->d_fd_rep;
-    }
+    if (int rc = b->fd.report(2 * (size_t)nframes * (size_t)b->nstreams, &d_report)) return rc;
     if (nframes > b->fd_plane_frames) {
         HIPCHK(hipDeviceSynchronize());          // (a launch before may still read the one it replaces)
         if (int rc = plane_reserve(b, nframes)) return rc;
     }
     TlFeedDownLaunch D;
     memset(&D, 0, sizeof D);
-    D.F.tables = b->d_tables; D.F.configs = b->d_fd_configs; D.F.feed_cfg = b->d_fd_cfg; D.F.synth = b->d_synth;
+    D.F.tables = b->d_tables; D.F.configs = b->fd.d_configs; D.F.feed_cfg = b->d_fd_cfg; D.F.synth = b->d_synth;
     D.F.frames = d_frames; D.F.len = d_len; D.F.report = (TlFrameReport *)d_report; D.F.pcm = d_interleaved;
     D.F.state = b->d_fd_state; D.F.prev = b->d_fd_prev; D.F.prev_stride = TL_FD_PREV_STRIDE;
     D.F.nstreams = b->nstreams; D.F.nframes = nframes; D.F.stride = stride;
@@ -136,7 +105,7 @@ int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len
     HIPCHK(tlk_feed_down((hipStream_t)hip_stream, D));
     b->fd_flip ^= 1;
     for (int s = 0; s < b->nstreams; s++)
-        if (feed_down_on(b, s)) b->fd_pos[(size_t)s] = (int32_t)(((long long)b->fd_pos[(size_t)s] + nframes) % tl_fd_cycle(b->fd_ratio[(size_t)s]));
+        if (b->fd.on(s)) b->fd_pos[(size_t)s] = (int32_t)(((long long)b->fd_pos[(size_t)s] + nframes) % tl_fd_cycle(b->fd_ratio[(size_t)s]));
     return TLB_OK;
 }
 
@@ -153,33 +122,26 @@ int tlb_feed_down_set(tlb_batch *b, int stream, const tlb_feed_config *cfg)
         return down_assign(b, s0, s1, -1, tlb_feed_config{0, 0, 0});
     }
     if (int rc = feed_down_fits(b, s0, s1, cfg)) return rc;          // every named stream is checked before anything changes
-    // a stream has one source: a feed (strict or adapted), an up source or a down source on a named stream is refused
-    for (int s = s0; s < s1; s++)
-        if (tlb_feed_get(b, s, nullptr) > 0 || tlb_resample_source(b, s) || tlb_decimate_source(b, s)) return TLB_ERR_ARG;
-    int idx = -1;
-    for (size_t i = 0; i < b->h_fd_uniq.size(); i++) if (feed_same(b->h_fd_uniq[i], *cfg)) idx = (int)i;
+    for (int s = s0; s < s1; s++) if (!batch_may_set(b, s, TLB_IN_DOWN_FEED)) return TLB_ERR_ARG;      // a stream has one source (csrc/tlb_inputs.h)
+    int idx = b->fd.find(*cfg);
     TlConfig *c = new TlConfig;
     struct Free { TlConfig *c; ~Free() { delete c; } } free_{c};
-    if (idx >= 0) *c = b->h_fd_configs[(size_t)idx];
+    if (idx >= 0) *c = b->fd.h_configs[(size_t)idx];
     else if (int rc = feed_build(c, cfg)) return rc;
     if (tl_feed_slot_bytes(*c) > TL_FD_PREV_STRIDE) return TLB_ERR_BITRATE;      // (no Layer II frame is that long)
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = down_prepare(b)) return rc;
-    if (int rc = configs_reserve(b, b->h_fd_configs.size() + (idx < 0 ? 1 : 0))) return rc;
-    if (idx < 0) {
-        idx = (int)b->h_fd_configs.size();
-        HIPCHK(hipMemcpy(b->d_fd_configs + idx, c, sizeof(TlConfig), hipMemcpyHostToDevice));
-        b->h_fd_configs.push_back(*c); b->h_fd_uniq.push_back(*cfg);
-    }
+    if (int rc = b->fd.reserve(b->fd.h_configs.size() + (idx < 0 ? 1 : 0))) return rc;
+    if (int rc = b->fd.add(*cfg, *c, &idx)) return rc;
     return down_assign(b, s0, s1, idx, *cfg);
 }
 
 int tlb_feed_down_get(const tlb_batch *b, int stream, tlb_feed_config *cfg)
 {
     if (!b || stream < 0 || stream >= b->nstreams) return -TLB_ERR_ARG;
-    const bool on = feed_down_on(b, stream);
-    if (cfg) *cfg = on ? b->fd_cfg[(size_t)stream] : tlb_feed_config{0, 0, 0};
+    const bool on = b->fd.on(stream);
+    if (cfg) *cfg = on ? b->fd.cfg[(size_t)stream] : tlb_feed_config{0, 0, 0};
     return on ? 1 : 0;
 }
 
@@ -193,17 +155,12 @@ int tlb_feed_down_want_at(long feed_rate, long stream_rate, long tick)
 
 int tlb_feed_down_want(const tlb_batch *b, int stream, int ahead)
 {
-    if (!b || stream < 0 || stream >= b->nstreams || ahead < 0 || !feed_down_on(b, stream)) return -TLB_ERR_ARG;
+    if (!b || stream < 0 || stream >= b->nstreams || ahead < 0 || !b->fd.on(stream)) return -TLB_ERR_ARG;
     const int ratio = b->fd_ratio[(size_t)stream];
     return tl_fd_want((int)(((long long)b->fd_pos[(size_t)stream] + ahead) % tl_fd_cycle(ratio)), ratio);
 }
 
-int tlb_feed_down_stride(const tlb_batch *b)
-{
-    int stride = 0;
-    if (b) for (int idx : b->fd_idx) if (idx >= 0 && tl_feed_slot_bytes(b->h_fd_configs[(size_t)idx]) > stride) stride = tl_feed_slot_bytes(b->h_fd_configs[(size_t)idx]);
-    return stride;
-}
+int tlb_feed_down_stride(const tlb_batch *b) { return b ? b->fd.stride() : 0; }
 
 int tlb_feed_down_reset(tlb_batch *b, int stream)
 {
@@ -217,7 +174,7 @@ int tlb_feed_down_reset(tlb_batch *b, int stream)
 int tlb_feed_down_device(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int16_t *d_interleaved, tlb_frame_report *d_report, int nframes,
                          void *hip_stream)
 {
-    return feed_down_launch(b, d_frames, d_len, d_interleaved, d_report, nframes, hip_stream, tlb_feed_down_stride(b));
+    return feed_down_launch(b, d_frames, d_len, nframes, d_interleaved, d_report, hip_stream, tlb_feed_down_stride(b));
 }
 
 int tlb_feed_down_host(tlb_batch *b, const uint8_t *frames, const int32_t *len, int16_t *interleaved, tlb_frame_report *report, int nframes)

@@ -14,6 +14,7 @@
 #include "../../include/toolame_batch.h"
 #include "mp2_host.h"
 #include "tl_kernels.h"
+#include "tlb_inputs.h"
 #include "tlb_mem.h"
 
 static_assert(TL_MAX_XPAD == TLB_MAX_XPAD, "xpad record size");
@@ -26,6 +27,79 @@ enum TlbStage {
     TLB_STAGE_OUT_LEN,                                                                     // tlb_encode_host_len: frame lengths
     TLB_STAGE_INGEST_IN, TLB_STAGE_INGEST_OUT, TLB_STAGE_INGEST_PEAKS,                     // tlb_ingest_host: interleaved in, planar out, peaks
     TLB_STAGE_COUNT
+};
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+    fprintf(stderr, "libtoolame-dab-hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+    return TLB_ERR_HIP; } } while (0)
+
+// after a run of requests to a TlbMem (csrc/tlb_mem.h, which has printed the failing call): the one check
+#define MEMCHK(m) do { if ((m).failed()) return TLB_ERR_HIP; } while (0)
+
+static inline bool feed_same(const tlb_feed_config &a, const tlb_feed_config &b) { return a.samplerate == b.samplerate && a.bitrate == b.bitrate && a.channels == b.channels; }
+// What a feed family (tlb_feed_*, tlb_feed_down_*) keeps of its records at batch level: the feed of every stream, the grow-only table of
+// distinct records on host and device, and the report buffer of a launch that was given none.  Empty until the family's first set.
+struct FeedTable {
+    std::vector<tlb_feed_config> cfg;            // [nstreams] the stream's feed
+    std::vector<int32_t> idx;                    // [nstreams] its record in h_configs, -1: none
+    std::vector<tlb_feed_config> uniq;           // the three knobs of h_configs[i]; grow-only
+    std::vector<TlConfig> h_configs;
+    TlConfig *d_configs = nullptr;               // replaced when it grows: an owner of its own, as has d_rep
+    std::unique_ptr<TlbMem> mem, rep_mem;
+    size_t cap = 0, rep_slots = 0;
+    tlb_frame_report *d_rep = nullptr;           // grow-only launch scratch
+
+    void start(size_t nstreams) { cfg.assign(nstreams, tlb_feed_config{0, 0, 0}); idx.assign(nstreams, -1); }
+    bool on(int s) const { return !idx.empty() && idx[(size_t)s] >= 0; }
+    int find(const tlb_feed_config &c) const     // the record with these knobs, -1: none yet
+    {
+        int at = -1;
+        for (size_t i = 0; i < uniq.size(); i++) if (feed_same(uniq[i], c)) at = (int)i;
+        return at;
+    }
+    // the widest slot a frame of some stream's record needs; 0: no stream has a feed
+    int stride() const
+    {
+        int w = 0;
+        for (int i : idx) if (i >= 0 && tl_feed_slot_bytes(h_configs[(size_t)i]) > w) w = tl_feed_slot_bytes(h_configs[(size_t)i]);
+        return w;
+    }
+    // room for `count` records in d_configs; what it holds is kept (the device is idle).  The new buffer is staged and filled in a new
+    // owner, and only when it is complete do the owners change places (csrc/tlb_mem.h): a failure leaves everything as it was
+    int reserve(size_t count)
+    {
+        if (count <= cap) return TLB_OK;
+        std::unique_ptr<TlbMem> m(new TlbMem);
+        TlConfig *nd = m->scratch<TlConfig>(count + 4);
+        if (!h_configs.empty()) m->upload(nd, h_configs.data(), sizeof(TlConfig) * h_configs.size());
+        if (!m->settle()) return TLB_ERR_HIP;
+        mem.swap(m);
+        d_configs = nd; cap = count + 4;
+        return TLB_OK;
+    }
+    // the record of c (built as rec), added behind the others when *at is -1; room for it has been reserved
+    int add(const tlb_feed_config &c, const TlConfig &rec, int *at)
+    {
+        if (*at >= 0) return TLB_OK;
+        HIPCHK(hipMemcpy(d_configs + h_configs.size(), &rec, sizeof(TlConfig), hipMemcpyHostToDevice));
+        *at = (int)h_configs.size();
+        h_configs.push_back(rec); uniq.push_back(c);
+        return TLB_OK;
+    }
+    // a launch without a report buffer: the kernels' history pass reads the last slot's status, so the family lends one of `slots` records
+    int report(size_t slots, tlb_frame_report **d_report)
+    {
+        if (*d_report) return TLB_OK;
+        if (rep_slots < slots) {
+            HIPCHK(hipDeviceSynchronize());      // (a launch before may still write the one it replaces)
+            std::unique_ptr<TlbMem> m(new TlbMem);
+            tlb_frame_report *nr = m->scratch<tlb_frame_report>(slots);
+            if (m->failed()) return TLB_ERR_HIP;
+            rep_mem.swap(m);
+            d_rep = nr; rep_slots = slots;
+        }
+        *d_report = d_rep;
+        return TLB_OK;
+    }
 };
 
 struct tlb_batch {
@@ -97,22 +171,14 @@ struct tlb_batch {
     std::vector<long> dc_rate;                   // [nstreams] source rate, 0: off (empty until the first set_source)
     std::vector<int32_t> dc_ratio, dc_pos;       // host copies: TL_DC_* and the frame position in the need cycle
     // Layer II feeds (tlb_feed.cpp), allocated by the first tlb_feed_set: a batch that never sets a feed has none of it
-    std::vector<tlb_feed_config> feed_cfg;       // [nstreams] the stream's feed (empty until the first set)
-    std::vector<int32_t> feed_idx;               // [nstreams] its record in h_feed_configs, -1: no feed
-    std::vector<tlb_feed_config> h_feed_uniq;    // the three knobs of h_feed_configs[i]; grow-only
-    std::vector<TlConfig> h_feed_configs;
-    TlConfig *d_feed_configs = nullptr;          // replaced when it grows: an owner of its own (feed_cfg_mem), as has d_feed_prev (feed_prev_mem)
-    std::unique_ptr<TlbMem> feed_cfg_mem, feed_prev_mem;
-    size_t feed_cfg_cap = 0;
-    int32_t *d_feed_cfg = nullptr;               // [nstreams] feed_idx on the device
+    FeedTable feed;                              // the streams' feeds and their records
+    std::unique_ptr<TlbMem> feed_prev_mem;       // d_feed_prev is replaced when it grows: an owner of its own
+    int32_t *d_feed_cfg = nullptr;               // [nstreams] feed.idx on the device
     TlDecStream *d_feed_state = nullptr;         // [nstreams] the feed history, separate from the decoder's
     uint8_t *d_feed_prev = nullptr;              // [nstreams][feed_prev_stride] the last slot of the call before; replaced when a longer feed frame arrives
     int feed_prev_stride = 0;
-    tlb_frame_report *d_feed_rep = nullptr;      // reports of a tlb_feed_device call that asked for none: grow-only launch scratch with an owner of its own
-    std::unique_ptr<TlbMem> feed_rep_mem;
-    size_t feed_rep_slots = 0;
     // adapted feeds (tlb_feed_set_adapted; csrc/mp2_feed_adapt.h), allocated by the first one that does not match its stream.  An adapted
-    // stream keeps its record in feed_cfg / feed_idx and its history in d_feed_state / d_feed_prev, but reads -1 in d_feed_cfg: the strict
+    // stream keeps its record in `feed` and its history in d_feed_state / d_feed_prev, but reads -1 in d_feed_cfg: the strict
     // kernel sees it as a stream without a feed
     std::vector<int32_t> fa_ratio;               // [nstreams] -1: not adapted, else TL_RS_* of (feed rate, stream rate) (empty until the first adapted feed)
     std::vector<int32_t> fa_pos;                 // [nstreams] host copy of the tick counter modulo the cycle
@@ -126,23 +192,17 @@ struct tlb_batch {
     int fa_plane_frames = 0, fa_flip = 0;
     // down feeds (tlb_feed_down.cpp; csrc/mp2_feed_down.h), allocated by the first tlb_feed_down_set: a batch that never sets one has none of
     // it.  Records, history and reports of their own: nothing is shared with the feeds above but the synthesis tables
-    std::vector<tlb_feed_config> fd_cfg;         // [nstreams] the stream's down feed (empty until the first set)
-    std::vector<int32_t> fd_idx;                 // [nstreams] its record in h_fd_configs, -1: none
+    FeedTable fd;                                // the streams' down feeds and their records
     std::vector<int32_t> fd_ratio, fd_pos;       // [nstreams] TL_DC_* of (feed rate, stream rate); host copy of the tick counter modulo the cycle
-    std::vector<tlb_feed_config> h_fd_uniq;      // the three knobs of h_fd_configs[i]; grow-only
-    std::vector<TlConfig> h_fd_configs;
-    TlConfig *d_fd_configs = nullptr;            // replaced when it grows: an owner of its own
-    std::unique_ptr<TlbMem> fd_cfg_mem, fd_plane_mem, fd_rep_mem;
-    size_t fd_cfg_cap = 0, fd_rep_slots = 0;
+    std::unique_ptr<TlbMem> fd_plane_mem;
     int n_down = 0, fd_plane_frames = 0, fd_flip = 0;
-    int32_t *d_fd_cfg = nullptr, *d_fd_ratio = nullptr;      // [nstreams] fd_idx, fd_ratio on the device
+    int32_t *d_fd_cfg = nullptr, *d_fd_ratio = nullptr;      // [nstreams] fd.idx, fd_ratio on the device
     int32_t *d_fd_pos = nullptr;                 // [2][nstreams]; a call reads copy fd_flip and writes the other
     int16_t *d_fd_carry = nullptr;               // [2][nstreams][TL_FD_CARRY * 2], likewise
     TlDecStream *d_fd_state = nullptr;           // [nstreams] length and status of the last wanted slot of the call before
     uint8_t *d_fd_prev = nullptr;                // [nstreams][TL_FD_PREV_STRIDE] its bytes
     int16_t *d_fd_taps = nullptr;                // the decimator's three tables, a copy of the down feeds' own
     int16_t *d_fd_plane = nullptr;               // [nstreams][fd_plane_frames * TL_FD_PLANE] grow-only launch scratch with an owner of its own
-    tlb_frame_report *d_fd_rep = nullptr;        // reports of a call that asked for none, likewise
     TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -156,13 +216,6 @@ static inline hipError_t stage_reserve(tlb_batch *b, TlbStage k, size_t bytes)
     if (e == hipSuccess) b->stage_cap[k] = bytes;
     return e;
 }
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-    fprintf(stderr, "libtoolame-dab-hip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-    return TLB_ERR_HIP; } } while (0)
-
-// after a run of requests to a TlbMem (csrc/tlb_mem.h, which has printed the failing call): the one check
-#define MEMCHK(m) do { if ((m).failed()) return TLB_ERR_HIP; } while (0)
 
 // tlb_batch.cpp: one launch of the encode path on `st` (every entry point ends here)
 int tlb_launch(tlb_batch *b, const int16_t *d_pcm, int nframes, const uint8_t *d_xpad, const int32_t *d_xpad_len,
@@ -184,6 +237,7 @@ int feed_after_reconfigure(tlb_batch *b, int stream);
 int feed_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
 int feed_fits_adapted(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);      // ... for tlb_feed_set_adapted: a legal rate pair, any channel counts
 int feed_slot_bytes(const tlb_feed_config *cfg);
+int feed_build(TlConfig *c, const tlb_feed_config *cfg);           // the kernel-side record of a feed configuration, or why it is not legal
 int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
 // tlb_compare.cpp: the history as the first compare call makes it; the launch itself with a report that may be NULL (every slot skipped:
 // a tick that has no frames yet still advances the history)
@@ -201,14 +255,22 @@ int decimate_prepare(tlb_batch *b);
 int decimate_clear_streams(tlb_batch *b, int s0, int n);
 bool decimate_rate_fits(const tlb_batch *b, int stream, long encoder_rate);
 int16_t *decimate_taps_upload(TlbMem &m);        // the three tables in one buffer of m: [80][64], [3][64], [1][64] (the decimator's copy, and the down feeds')
-// tlb_feed_down.cpp: has the stream a down feed (a stream has ONE source: the other families ask before they set theirs); the position,
-// queue and history of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); after a reconfiguration, the stream's
-// down feed removed when its rate no longer pairs with the stream's
-bool feed_down_on(const tlb_batch *b, int stream);
+// tlb_feed_down.cpp: the position, queue and history of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); after
+// a reconfiguration, the stream's down feed removed when its rate no longer pairs with the stream's
 int feed_down_clear_streams(tlb_batch *b, int s0, int n);
 int feed_down_after_reconfigure(tlb_batch *b, int stream);
 // ... what the tick plane needs of it: is cfg legal and does it pair with streams [s0, s1) (nothing changes); tlb_feed_down_device with
 // slots of `stride` bytes, at least tlb_feed_down_stride(b)
 int feed_down_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
-int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int16_t *d_interleaved, tlb_frame_report *d_report, int nframes, void *hip_stream, int stride);
+int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
+
+// the encoder's rate of stream s
+static inline long batch_enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
+// the input families stream s has (csrc/tlb_inputs.h): what a batch-level setter asks tlb_input_may_set about
+static inline unsigned batch_inputs(const tlb_batch *b, int s)
+{
+    return (tlb_resample_source(b, s) ? TLB_IN_BIT(TLB_IN_UP_SOURCE) : 0u) | (tlb_decimate_source(b, s) ? TLB_IN_BIT(TLB_IN_DOWN_SOURCE) : 0u) |
+           (tlb_feed_get(b, s, nullptr) > 0 ? TLB_IN_BIT(TLB_IN_FEED) : 0u) | (b->fd.on(s) ? TLB_IN_BIT(TLB_IN_DOWN_FEED) : 0u);
+}
+static inline bool batch_may_set(const tlb_batch *b, int s, TlbInput f) { return tlb_input_may_set(TLB_INPUTS_STREAM, f, batch_inputs(b, s)); }
 int pft_shape(int max_af_len, int fec, int chunk_len, int transport, int *max_frags, int *frag_stride);

@@ -26,6 +26,7 @@
 #include "mp2_host.h"
 #include "mp2_resample.h"
 #include "tlb_blocks.h"
+#include "tlb_inputs.h"
 #include "tlb_mailbox.h"
 #include "tlb_plan.h"
 #ifdef TLB_FAULT_INJECT
@@ -161,15 +162,21 @@ struct tlb_node {
     int monitor = 0;                             // tlb_node_enable_monitor(): TLB_MONITOR_* of every shard's tick object (a restarted shard's too)
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
-    std::vector<long> source;                    // tlb_node_set_source(): the source rate of every stream (0: off), set again on a restarted shard; empty: never set
-    std::vector<long> down;                      // tlb_node_set_down_source(): the down source rate of every stream (0: off), set again on a restarted shard; empty: never set
-    bool any_down() const { for (long r : down) if (r) return true; return false; }
-    struct Feed : tlb_feed_config { int adapted; };      // adapted: set through tlb_node_set_feed_adapted, and set again that way
-    std::vector<Feed> feed;           // tlb_node_set_feed(): the feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
-    bool any_feed() const { for (const Feed &f : feed) if (f.bitrate) return true; return false; }
-    std::vector<Feed> dfeed;          // tlb_node_set_down_feed(): the down feed of every stream (bitrate 0: none), set again on a restarted shard; empty: never set
-    bool any_dfeed() const { for (const Feed &f : dfeed) if (f.bitrate) return true; return false; }
+    // The per-stream input families (csrc/tlb_inputs.h; node_families below): what tlb_node_set_source, _set_down_source, _set_feed and
+    // _set_down_feed gave every stream, set again on a restarted shard.  A source is its rate alone; samplerate 0: the stream has none;
+    // adapted: set through tlb_node_set_feed_adapted, and set again that way.  A family's vector is empty until it is first turned on.
+    struct Input : tlb_feed_config { int adapted; };
+    std::vector<Input> kept[TLB_IN_SHORT_READS];
+    // The families that are on, for tlb_input_may_set at OBJECT level.  That is the TICK plane's rule: every shard there is one tick object.
+    // On the BATCH plane the node holds nothing back and the mask is empty: the shards' batches answer stream by stream (batch_inputs).
+    unsigned inputs() const
+    {
+        unsigned m = short_reads ? TLB_IN_BIT(TLB_IN_SHORT_READS) : 0u;
+        for (int f = 0; f < TLB_IN_SHORT_READS && plane == TLB_NODE_TICK; f++)
+            for (const Input &v : kept[f]) if (v.samplerate) { m |= TLB_IN_BIT(f); break; }
+        return m;
+    }
 
     // Run fn(shard) on the thread of every LIVE shard at once.  A shard whose fn returns non-zero is marked broken there and then (on
     // its own thread, with HIP's last error of that thread) and is skipped from now on; the others are not disturbed.  Returns the
@@ -316,6 +323,37 @@ struct tlb_node {
 
 namespace {
 
+// How a remembered value of each per-stream family reaches a shard's object, tick or batch (k = -1: the whole block; a value that is off
+// clears); in the order a restarted shard gets them back
+using NodeInput = tlb_node::Input;
+int (*const node_families[TLB_IN_SHORT_READS])(Shard &sh, int k, const NodeInput &v) = {
+    /* up source   */ [](Shard &sh, int k, const NodeInput &v) { return sh.tick ? tlb_tick_set_source(sh.tick, k, v.samplerate) : tlb_resample_set_source(sh.batch, k, v.samplerate); },
+    /* down source */ [](Shard &sh, int k, const NodeInput &v) { return sh.tick ? tlb_tick_set_down_source(sh.tick, k, v.samplerate) : tlb_decimate_set_source(sh.batch, k, v.samplerate); },
+    /* feed        */ [](Shard &sh, int k, const NodeInput &v) {
+        const tlb_feed_config *c = v.bitrate ? &v : nullptr;        // (bitrate 0 is "none": tlb_feed_check_config lets no caller's cfg through with it)
+        if (v.adapted) return sh.tick ? tlb_tick_set_feed_adapted(sh.tick, k, c) : tlb_feed_set_adapted(sh.batch, k, c);
+        return sh.tick ? tlb_tick_set_feed(sh.tick, k, c) : tlb_feed_set(sh.batch, k, c);
+    },
+    /* down feed   */ [](Shard &sh, int k, const NodeInput &v) {
+        const tlb_feed_config *c = v.bitrate ? &v : nullptr;
+        return sh.tick ? tlb_tick_set_down_feed(sh.tick, k, c) : tlb_feed_down_set(sh.batch, k, c);
+    },
+};
+// The one path of the four setters, after their own checks of the value: the exclusion rule, then tlb_node::set_remembered.  `on`: the call
+// turns the family on for some stream; keep(i): what stream i is remembered with when the call goes through.
+template <class Keep> int node_set_input(tlb_node *nd, TlbInput f, int stream, bool on, const NodeInput &v, Keep keep)
+{
+    if (on && !tlb_input_may_set(TLB_INPUTS_OBJECT, f, nd->inputs())) return TLB_ERR_ARG;
+    return nd->set_remembered(stream, nd->kept[f], on, v, node_families[f], keep);
+}
+NodeInput node_rate(long rate) { NodeInput v = {}; v.samplerate = rate; return v; }
+NodeInput node_feed(const tlb_feed_config *cfg, bool adapted)
+{
+    NodeInput v = {};
+    if (cfg) { v.samplerate = cfg->samplerate; v.bitrate = cfg->bitrate; v.channels = cfg->channels; v.adapted = adapted; }
+    return v;
+}
+
 // the objects of one shard, made on the shard's own thread (creation and restart)
 int shard_make(tlb_node *nd, Shard &s, long long now_s)
 {
@@ -337,26 +375,11 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (!s.batch) return e ? e : TLB_ERR_HIP;
         if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) return TLB_ERR_HIP;
     }
-    for (int k = 0; k < s.n && !nd->source.empty(); k++) {           // the caller's sources, with fresh state
-        const long r = nd->source[(size_t)(s.first + k)];
-        if (r == 0) continue;
-        if (int rc = s.tick ? tlb_tick_set_source(s.tick, k, r) : tlb_resample_set_source(s.batch, k, r)) return rc;
-    }
-    for (int k = 0; k < s.n && !nd->down.empty(); k++) {             // the caller's down sources, with fresh state
-        const long r = nd->down[(size_t)(s.first + k)];
-        if (r == 0) continue;
-        if (int rc = s.tick ? tlb_tick_set_down_source(s.tick, k, r) : tlb_decimate_set_source(s.batch, k, r)) return rc;
-    }
-    for (int k = 0; k < s.n && !nd->feed.empty(); k++) {             // the caller's feeds, with fresh history
-        const tlb_node::Feed &f = nd->feed[(size_t)(s.first + k)];
-        if (!f.bitrate) continue;
-        if (int rc = s.tick ? (f.adapted ? tlb_tick_set_feed_adapted : tlb_tick_set_feed)(s.tick, k, &f) : (f.adapted ? tlb_feed_set_adapted : tlb_feed_set)(s.batch, k, &f)) return rc;
-    }
-    for (int k = 0; k < s.n && !nd->dfeed.empty(); k++) {            // the caller's down feeds, at tick 0
-        const tlb_node::Feed &f = nd->dfeed[(size_t)(s.first + k)];
-        if (!f.bitrate) continue;
-        if (int rc = s.tick ? tlb_tick_set_down_feed(s.tick, k, &f) : tlb_feed_down_set(s.batch, k, &f)) return rc;
-    }
+    for (int f = 0; f < TLB_IN_SHORT_READS; f++)                      // the caller's sources and feeds, with fresh state
+        for (int k = 0; k < s.n && !nd->kept[f].empty(); k++) {
+            const NodeInput &v = nd->kept[f][(size_t)(s.first + k)];
+            if (v.samplerate) if (int rc = node_families[f](s, k, v)) return rc;
+        }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
         if (g == 0.0) continue;
@@ -603,8 +626,7 @@ int32_t *tlb_node_xpad_len(tlb_node *nd, int stream) { return slot<INPUT, tlb_ti
 int tlb_node_enable_short_reads(tlb_node *nd)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
-    for (long r : nd->source) if (r) return TLB_ERR_ARG;             // a source and short reads exclude each other (include/toolame_batch.h)
-    if (nd->any_feed() || nd->any_down() || nd->any_dfeed()) return TLB_ERR_ARG;      // ... and so do a feed, a down source or a down feed and short reads
+    if (!tlb_input_may_set(TLB_INPUTS_OBJECT, TLB_IN_SHORT_READS, nd->inputs())) return TLB_ERR_ARG;
     if (nd->short_reads) return TLB_OK;
     const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
     if (!rc) nd->short_reads = true;
@@ -657,33 +679,19 @@ const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream)
     }
     return nullptr;
 }
-// A source rate for one stream or all: to the owning shards' objects, on their threads, between steps (tlb_node::set_remembered).
-int tlb_node_set_source(tlb_node *nd, int stream, long source_rate)
+// A source rate or a down source rate for one stream or all: to the owning shards' objects (tlb_tick_set_source / tlb_resample_set_source,
+// tlb_tick_set_down_source / tlb_decimate_set_source), on their threads, between steps (tlb_node::set_remembered).
+static int node_set_rate(tlb_node *nd, TlbInput f, int stream, long source_rate)
 {
     if (!nd || stream < -1 || stream >= nd->nstreams || source_rate < 0 || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     bool any = false;
-    if (int rc = tlb_source_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
-    if (any && (nd->short_reads || (nd->plane == TLB_NODE_TICK && (nd->any_feed() || nd->any_down() || nd->any_dfeed())))) return TLB_ERR_ARG;
-    return nd->set_remembered(stream, nd->source, any, source_rate,
-        [](Shard &sh, int k, long r) { return sh.tick ? tlb_tick_set_source(sh.tick, k, r) : tlb_resample_set_source(sh.batch, k, r); },
-        [&](int i) { return source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate; });      // (the encoder's own rate is no source)
+    if (int rc = tlb_rate_range(s0, s1, source_rate, f == TLB_IN_UP_SOURCE ? tlb_up_pair : tlb_down_pair, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
+    return node_set_input(nd, f, stream, any, node_rate(source_rate),
+        [&](int i) { return node_rate(source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate); });      // (the encoder's own rate is no source)
 }
-// A down source for one stream or all, the same way (tlb_tick_set_down_source / tlb_decimate_set_source of the owning shards' objects).
-int tlb_node_set_down_source(tlb_node *nd, int stream, long source_rate)
-{
-    if (!nd || stream < -1 || stream >= nd->nstreams || source_rate < 0 || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
-    bool any = false;
-    if (int rc = tlb_down_range(s0, s1, source_rate, [nd](int k) { return (long)nd->cfgs[(size_t)k].samplerate; }, &any)) return rc;
-    if (any && nd->plane == TLB_NODE_TICK) {                         // down sources exclude short reads, sources and feeds on one object (include/toolame_batch.h)
-        if (nd->short_reads || nd->any_feed() || nd->any_dfeed()) return TLB_ERR_ARG;
-        for (long r : nd->source) if (r) return TLB_ERR_ARG;
-    }
-    return nd->set_remembered(stream, nd->down, any, source_rate,
-        [](Shard &sh, int k, long r) { return sh.tick ? tlb_tick_set_down_source(sh.tick, k, r) : tlb_decimate_set_source(sh.batch, k, r); },
-        [&](int i) { return source_rate == nd->cfgs[(size_t)i].samplerate ? 0 : source_rate; });      // (the encoder's own rate is no source)
-}
+int tlb_node_set_source(tlb_node *nd, int stream, long source_rate) { return node_set_rate(nd, TLB_IN_UP_SOURCE, stream, source_rate); }
+int tlb_node_set_down_source(tlb_node *nd, int stream, long source_rate) { return node_set_rate(nd, TLB_IN_DOWN_SOURCE, stream, source_rate); }
 // the stream's wide slot in its shard's current input set: NULL for a broken or a late shard, while two ticks are in flight and while no
 // stream of the shard has a down source
 int16_t *tlb_node_down(tlb_node *nd, int stream) { return ask<INPUT>(nd, stream, (int16_t *)nullptr, [](tlb_tick *t, int k) { return tlb_tick_down(t, k); }); }
@@ -696,7 +704,7 @@ int tlb_node_down_need(const tlb_node *nd, int stream)
 }
 // A Layer II feed for one stream or all (cfg = NULL: removed; remembered as bitrate 0), the same way.  Every named stream is checked
 // before a shard is asked.
-static bool node_rates_adapt(long feed, long enc) { return feed == enc || tl_rs_ratio_of(feed, enc) != TL_RS_OFF; }
+static bool node_rates_adapt(long feed, long enc) { return feed == enc || tlb_up_pair(feed, enc); }
 static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, bool adapt)
 {
     if (!nd || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
@@ -708,21 +716,9 @@ static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, b
             if (cfg->samplerate != nd->cfgs[(size_t)i].samplerate) return TLB_ERR_SAMPLERATE;
             if (cfg->channels != (nd->cfgs[(size_t)i].mode == 'm' ? 1 : 2)) return TLB_ERR_MODE;
         }
-        if (nd->plane == TLB_NODE_TICK) {                            // feeds exclude short reads and sources on one object (include/toolame_batch.h)
-            if (nd->short_reads) return TLB_ERR_ARG;
-            for (long r : nd->source) if (r) return TLB_ERR_ARG;
-            if (nd->any_down() || nd->any_dfeed()) return TLB_ERR_ARG;
-        }
     }
-    tlb_node::Feed v = {};
-    if (cfg) { v.samplerate = cfg->samplerate; v.bitrate = cfg->bitrate; v.channels = cfg->channels; v.adapted = adapt; }
-    return nd->set_remembered(stream, nd->feed, cfg != nullptr, v,
-        [](Shard &sh, int k, const tlb_node::Feed &f) {
-            const tlb_feed_config *c = f.bitrate ? &f : nullptr;      // (bitrate 0 is "none": tlb_feed_check_config above lets no caller's cfg through with it)
-            if (f.adapted) return sh.tick ? tlb_tick_set_feed_adapted(sh.tick, k, c) : tlb_feed_set_adapted(sh.batch, k, c);
-            return sh.tick ? tlb_tick_set_feed(sh.tick, k, c) : tlb_feed_set(sh.batch, k, c);
-        },
-        [&](int) { return v; });
+    const NodeInput v = node_feed(cfg, adapt);
+    return node_set_input(nd, TLB_IN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
 }
 int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg) { return node_set_feed(nd, stream, cfg, false); }
 int tlb_node_set_feed_adapted(tlb_node *nd, int stream, const tlb_feed_config *cfg) { return node_set_feed(nd, stream, cfg, true); }
@@ -754,20 +750,10 @@ int tlb_node_set_down_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
     if (cfg) {
         if (int rc = tlb_feed_check_config(cfg)) return rc;
-        for (int i = s0; i < s1; i++) if (tl_dc_ratio_of(cfg->samplerate, nd->cfgs[(size_t)i].samplerate) == TL_DC_OFF) return TLB_ERR_SAMPLERATE;
-        if (nd->plane == TLB_NODE_TICK) {                            // (the legal pairs are the decimator's three) down feeds exclude short reads, sources, down sources and feeds on one object (include/toolame_batch.h)
-            if (nd->short_reads || nd->any_feed() || nd->any_down()) return TLB_ERR_ARG;
-            for (long r : nd->source) if (r) return TLB_ERR_ARG;
-        }
+        for (int i = s0; i < s1; i++) if (!tlb_down_pair(cfg->samplerate, nd->cfgs[(size_t)i].samplerate)) return TLB_ERR_SAMPLERATE;      // (the legal pairs are the decimator's three)
     }
-    tlb_node::Feed v = {};
-    if (cfg) { v.samplerate = cfg->samplerate; v.bitrate = cfg->bitrate; v.channels = cfg->channels; }
-    return nd->set_remembered(stream, nd->dfeed, cfg != nullptr, v,
-        [](Shard &sh, int k, const tlb_node::Feed &f) {
-            const tlb_feed_config *c = f.bitrate ? &f : nullptr;
-            return sh.tick ? tlb_tick_set_down_feed(sh.tick, k, c) : tlb_feed_down_set(sh.batch, k, c);
-        },
-        [&](int) { return v; });
+    const NodeInput v = node_feed(cfg, false);
+    return node_set_input(nd, TLB_IN_DOWN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
 }
 // the feed frames wanted in the stream's two slots of its shard's current input set (TICK plane; broken and late shards answer as tlb_node_need does)
 int tlb_node_down_feed_want(const tlb_node *nd, int stream)
@@ -911,13 +897,16 @@ int tlb_node_stream_reconfigure(tlb_node *nd, int stream, const tlb_stream_confi
     if (int rc = nd->gate(stream, &s, &k)) return rc;
     const int rc = nd->one(s->index, [&](Shard &sh) { return sh.tick ? tlb_tick_stream_reconfigure(sh.tick, k, cfg) : tlb_stream_reconfigure(sh.batch, k, cfg); });
     if (!rc) nd->cfgs[(size_t)stream] = *cfg;                        // a restart of the shard re-creates the stream as it is NOW
-    if (!rc && !nd->down.empty() && tl_dc_ratio_of(nd->down[(size_t)stream], cfg->samplerate) == TL_DC_OFF) nd->down[(size_t)stream] = 0;      // (a down source that no longer pairs is forgotten)
-    if (!rc && !nd->feed.empty()) {                                  // a feed the new rate or channel count no longer fits has been removed
-        tlb_node::Feed &f = nd->feed[(size_t)stream];
-        const bool fits = f.adapted ? node_rates_adapt(f.samplerate, cfg->samplerate) : f.samplerate == cfg->samplerate && f.channels == (cfg->mode == 'm' ? 1 : 2);
-        if (f.bitrate && !fits) f = tlb_node::Feed{};
+    if (rc) return rc;
+    // what the stream's new rate or channel count no longer fits has been removed by its object, and is forgotten here (an up source stays)
+    for (int f = TLB_IN_DOWN_SOURCE; f < TLB_IN_SHORT_READS; f++) {
+        if (nd->kept[f].empty()) continue;
+        NodeInput &v = nd->kept[f][(size_t)stream];
+        const bool fits = f != TLB_IN_FEED ? tlb_down_pair(v.samplerate, cfg->samplerate)
+                        : v.adapted    ? node_rates_adapt(v.samplerate, cfg->samplerate)
+                                       : v.samplerate == cfg->samplerate && v.channels == (cfg->mode == 'm' ? 1 : 2);
+        if (v.samplerate && !fits) v = NodeInput{};
     }
-    if (!rc && !nd->dfeed.empty() && tl_dc_ratio_of(nd->dfeed[(size_t)stream].samplerate, cfg->samplerate) == TL_DC_OFF) nd->dfeed[(size_t)stream] = tlb_node::Feed{};      // (a down feed that no longer pairs has been removed)
     return rc;
 }
 

@@ -61,26 +61,18 @@ static inline int tlb_plan_pairs(const std::vector<TlConfig> &configs, const std
 static inline int tlb_model_list(int psy) { return psy == 4 ? 2 : psy; }
 
 // ---- the opt-in rules the batch, the tick plane and the node level share ----
-// A source rate for the streams [s0, s1): every stream is checked before one is changed.  enc_rate(s) is the encoder rate of stream s.
-// A rate of 0 (off) or the encoder's own is no source.  Returns TLB_ERR_SAMPLERATE when some stream's (source, encoder) pair is no ratio the
-// resampler has, else 0; *any becomes true when some stream gets a real source (it is never cleared: ranges can be checked one after another).
-template <class EncRate> static inline int tlb_source_range(int s0, int s1, long source_rate, EncRate enc_rate, bool *any)
+// A source rate for the streams [s0, s1): every stream is checked before one is changed.  pairs(source, encoder) says whether the family
+// has that ratio (tlb_up_pair: the resampler; tlb_down_pair: the decimator, csrc/mp2_decimate.h); enc_rate(s) is the encoder rate of
+// stream s.  A rate of 0 (off) or the encoder's own is no source.  Returns TLB_ERR_SAMPLERATE when some stream's pair is none, else 0;
+// *any becomes true when some stream gets a real source (it is never cleared: ranges can be checked one after another).
+static inline bool tlb_up_pair(long source_rate, long enc) { return tl_rs_ratio_of(source_rate, enc) != TL_RS_OFF; }
+static inline bool tlb_down_pair(long source_rate, long enc) { return tl_dc_ratio_of(source_rate, enc) != TL_DC_OFF; }
+template <class Pairs, class EncRate> static inline int tlb_rate_range(int s0, int s1, long source_rate, Pairs pairs, EncRate enc_rate, bool *any)
 {
     for (int s = s0; s < s1; s++) {
         const long enc = enc_rate(s);
         if (source_rate == 0 || source_rate == enc) continue;
-        if (tl_rs_ratio_of(source_rate, enc) == TL_RS_OFF) return TLB_ERR_SAMPLERATE;
-        *any = true;
-    }
-    return 0;
-}
-// The same for a DOWN source (the decimator, csrc/mp2_decimate.h).
-template <class EncRate> static inline int tlb_down_range(int s0, int s1, long source_rate, EncRate enc_rate, bool *any)
-{
-    for (int s = s0; s < s1; s++) {
-        const long enc = enc_rate(s);
-        if (source_rate == 0 || source_rate == enc) continue;
-        if (tl_dc_ratio_of(source_rate, enc) == TL_DC_OFF) return TLB_ERR_SAMPLERATE;
+        if (!pairs(source_rate, enc)) return TLB_ERR_SAMPLERATE;
         *any = true;
     }
     return 0;

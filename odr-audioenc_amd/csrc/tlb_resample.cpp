@@ -18,7 +18,6 @@ static int need_of(int ratio, long frame)
     const long long hi = (1152 * (f + 1) - 1) * M / L + 1, lo = f > 0 ? (1152 * f - 1) * M / L + 1 : 0;
     return (int)(hi - lo);
 }
-static long encoder_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }
 
 bool resample_rate_fits(const tlb_batch *b, int stream, long rate)
 {
@@ -85,16 +84,15 @@ int tlb_resample_set_source(tlb_batch *b, int stream, long source_rate)
     if (!b || stream < -1 || stream >= b->nstreams || source_rate < 0) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? b->nstreams : stream + 1;
     bool any = false;
-    if (int rc = tlb_source_range(s0, s1, source_rate, [b](int s) { return encoder_rate(b, s); }, &any)) return rc;
-    // a stream has one source: not beside a down feed (tlb_feed_down_set)
-    for (int s = s0; any && s < s1; s++)
-        if (tl_rs_ratio_of(source_rate, encoder_rate(b, s)) != TL_RS_OFF && feed_down_on(b, s)) return TLB_ERR_ARG;
+    if (int rc = tlb_rate_range(s0, s1, source_rate, tlb_up_pair, [b](int s) { return batch_enc_rate(b, s); }, &any)) return rc;
+    for (int s = s0; any && s < s1; s++)                             // a stream has one source (csrc/tlb_inputs.h)
+        if (tlb_up_pair(source_rate, batch_enc_rate(b, s)) && !batch_may_set(b, s, TLB_IN_UP_SOURCE)) return TLB_ERR_ARG;
     if (!any && !b->d_rs_state) return TLB_OK;                       // off, and never on: nothing to allocate or to clear
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = resample_prepare(b)) return rc;
     std::vector<int32_t> ratio((size_t)(s1 - s0));
-    for (int s = s0; s < s1; s++) ratio[(size_t)(s - s0)] = tl_rs_ratio_of(source_rate, encoder_rate(b, s));
+    for (int s = s0; s < s1; s++) ratio[(size_t)(s - s0)] = tl_rs_ratio_of(source_rate, batch_enc_rate(b, s));
     HIPCHK(hipMemcpy(b->d_rs_ratio + s0, ratio.data(), sizeof(int32_t) * ratio.size(), hipMemcpyHostToDevice));
     for (int s = s0; s < s1; s++) {
         b->rs_ratio[(size_t)s] = ratio[(size_t)(s - s0)];

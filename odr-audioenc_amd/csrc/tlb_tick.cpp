@@ -14,6 +14,44 @@
 // The streams are split into groups (contiguous ranges, a private tlb_batch each): while group g's kernels run, group g+1's
 // PCM comes in and group g-1's packets go out, on three HIP streams (the link is full duplex).
 // ------------------------------------------------------------------------------------------
+// A FEED LANE: where a feed family (tlb_feed_*, tlb_feed_down_*) meets the tick plane.  The family names its batch-level calls and its slots per
+// stream; a tick object has one TickLane per family and every group one TickLaneGroup.  The frames and their lengths travel with the input
+// sets, the reports with the output sets.  `stride` is ONE slot width for every group (the widest feed the lane has had: it only grows); the
+// frame buffers are replaced when it grows and have an owner of their own (the old owner goes when the new one is complete), the rest
+// belongs to the object's `mem`.
+struct FeedFamily {
+    TlbInput input;
+    int slots;                                   // per stream and tick
+    int (*fits)(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg, bool adapt);
+    int (*set)(tlb_batch *b, int stream, const tlb_feed_config *cfg, bool adapt);
+    int (*get)(const tlb_batch *b, int stream, tlb_feed_config *cfg, bool *was_adapted);
+    int (*want)(const tlb_batch *b, int stream, int ahead);
+    int (*launch)(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
+};
+static const FeedFamily tick_families[2] = {
+    {TLB_IN_FEED, 1,                             // adapt: through tlb_feed_set_adapted (a legal rate pair and any channel counts instead of the stream's own)
+     [](const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg, bool adapt) { return (adapt ? feed_fits_adapted : feed_fits)(b, s0, s1, cfg); },
+     [](tlb_batch *b, int stream, const tlb_feed_config *cfg, bool adapt) { return (adapt ? tlb_feed_set_adapted : tlb_feed_set)(b, stream, cfg); },
+     [](const tlb_batch *b, int stream, tlb_feed_config *cfg, bool *was_adapted) { *was_adapted = tlb_feed_adapted(b, stream) > 0; return tlb_feed_get(b, stream, cfg); },
+     tlb_feed_want, feed_launch},
+    {TLB_IN_DOWN_FEED, 2,
+     [](const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg, bool) { return feed_down_fits(b, s0, s1, cfg); },
+     [](tlb_batch *b, int stream, const tlb_feed_config *cfg, bool) { return tlb_feed_down_set(b, stream, cfg); },
+     [](const tlb_batch *b, int stream, tlb_feed_config *cfg, bool *was_adapted) { *was_adapted = false; return tlb_feed_down_get(b, stream, cfg); },
+     tlb_feed_down_want, feed_down_launch},
+};
+enum { LANE_FEED, LANE_DOWN_FEED, LANES };       // submit order: feed before down feed, both ahead of the resampler and the decimator
+struct TickLaneGroup {
+    uint8_t *d_frames = nullptr; int32_t *d_len = nullptr; tlb_frame_report *d_report = nullptr;      // the group's slice of the tick's frames and lengths, the launch's reports
+    bool any = false, all = false;               // some / every stream of the group has a feed of the family (all: the group's PCM is not copied in)
+};
+struct TickLane {
+    bool on = false;                             // at least one stream has a feed of the family
+    int stride = 0;
+    uint8_t *h_frames[2] = {}; int32_t *h_len[2] = {}; tlb_frame_report *h_report[3] = {};
+    std::unique_ptr<TlbMem> mem;                 // owns h_frames[] and the groups' d_frames
+};
+
 struct TickGroup {
     tlb_batch *b = nullptr;
     int first = 0, n = 0, out_stride = 0, max_upf = 1, af_stride = 0, max_frags = 0, frag_stride = 0;
@@ -36,12 +74,7 @@ struct TickGroup {
     // confidence monitor (tlb_tick_enable_monitor): the decode call's reports (and PCM under AUDIO) of this tick's frames, the folded records
     tlb_frame_report *d_report = nullptr; int16_t *d_mpcm = nullptr; tlb_monitor_record *d_record = nullptr;
     tlb_compare_record *d_crecord = nullptr;                    // compare monitor (tlb_tick_enable_compare): the group's records
-    // Layer II feeds (tlb_tick_set_feed): the group's slice of the tick's feed frames and lengths, the feed call's reports
-    uint8_t *d_feed = nullptr; int32_t *d_feed_len = nullptr; tlb_frame_report *d_feed_report = nullptr;
-    bool any_fed = false, all_fed = false;                      // some / every stream of the group has a feed (all: the group's PCM is not copied in)
-    // down feeds (tlb_tick_set_down_feed): the same three with TWO slots per stream
-    uint8_t *d_dfeed = nullptr; int32_t *d_dfeed_len = nullptr; tlb_frame_report *d_dfeed_report = nullptr;
-    bool any_dfed = false, all_dfed = false;                    // some / every stream of the group has a down feed (all: the group's PCM is not copied in)
+    TickLaneGroup lane[LANES];                                  // Layer II feeds and down feeds (tlb_tick_set_feed, tlb_tick_set_down_feed)
     // down sources (tlb_tick_set_down_source): the group's slice of the tick's wide slots; the decimator writes the streams' slots of d_inter
     int16_t *d_wide = nullptr;
     bool any_down = false, all_down = false;                    // some / every stream of the group has a down source (all: the group's PCM is not copied in)
@@ -75,20 +108,7 @@ struct tlb_tick {
     // down sources, off until the first real tlb_tick_set_down_source: the wide slots [nstreams][TLB_DECIMATE_SLOT] travel with the input sets
     bool down = false;                           // at least one stream has a down source
     int16_t *h_wide[2] = {};
-    // Layer II feeds, off until the first tlb_tick_set_feed: the frames and their lengths travel with the input sets, the reports with the
-    // output sets.  feed_stride is ONE slot width for every group (the widest feed the object has had: it only grows); the frame buffers
-    // are replaced when it grows and have an owner of their own (feed_mem: the old owner goes when the new one is complete), the rest
-    // belongs to `mem`.
-    bool feed = false;                           // at least one stream has a feed
-    int feed_stride = 0;
-    uint8_t *h_feed[2] = {}; int32_t *h_feed_len[2] = {}; tlb_frame_report *h_feed_report[3] = {};
-    std::unique_ptr<TlbMem> feed_mem;            // owns h_feed[] and the groups' d_feed
-    // down feeds, off until the first tlb_tick_set_down_feed: as the feeds' buffers, with two slots per stream ([nstreams][2][dfeed_stride],
-    // lengths and reports [nstreams][2]) and owners of their own
-    bool dfeed = false;                          // at least one stream has a down feed
-    int dfeed_stride = 0;
-    uint8_t *h_dfeed[2] = {}; int32_t *h_dfeed_len[2] = {}; tlb_frame_report *h_dfeed_report[3] = {};
-    std::unique_ptr<TlbMem> dfeed_mem;           // owns h_dfeed[] and the groups' d_dfeed
+    TickLane lane[LANES];                        // Layer II feeds and down feeds, each off until its first set
     // compare monitor, off until tlb_tick_enable_compare(): needs the AUDIO monitor's decoded PCM; its records travel with the output sets too
     bool compare = false;
     tlb_compare_params cparams = {};
@@ -109,6 +129,13 @@ struct tlb_tick {
 };
 // a failing submit / wait / finish: drain what was queued, mark the object, hand the code on
 static int tick_fail(tlb_tick *t, int rc);
+// the input families that are on (csrc/tlb_inputs.h): what every opt-in and setter of the object asks tlb_input_may_set about
+static unsigned tick_inputs(const tlb_tick *t)
+{
+    return (t->resample ? TLB_IN_BIT(TLB_IN_UP_SOURCE) : 0u) | (t->down ? TLB_IN_BIT(TLB_IN_DOWN_SOURCE) : 0u) | (t->lane[LANE_FEED].on ? TLB_IN_BIT(TLB_IN_FEED) : 0u) |
+           (t->lane[LANE_DOWN_FEED].on ? TLB_IN_BIT(TLB_IN_DOWN_FEED) : 0u) | (t->short_reads ? TLB_IN_BIT(TLB_IN_SHORT_READS) : 0u);
+}
+static bool tick_may_set(const tlb_tick *t, TlbInput f) { return tlb_input_may_set(TLB_INPUTS_OBJECT, f, tick_inputs(t)); }
 #ifdef TLB_FAULT_INJECT
 static int tick_cross(tlb_tick *t, TickGroup &G);
 #endif
@@ -257,7 +284,7 @@ const uint32_t *tlb_tick_underruns(const tlb_tick *t) { return t && t->short_rea
 // call makes the device calls it always made.
 int tlb_tick_enable_short_reads(tlb_tick *t)
 {
-    if (!t || t->finished || t->ticks > 0 || t->resample || t->feed || t->down || t->dfeed) return TLB_ERR_ARG;      // (a source, a down source, a feed or a down feed and short reads exclude each other: include/toolame_batch.h)
+    if (!t || t->finished || t->ticks > 0 || !tick_may_set(t, TLB_IN_SHORT_READS)) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
@@ -344,84 +371,58 @@ const int16_t *tlb_tick_monitor_pcm(const tlb_tick *t, int *stream)
     if (stream) *stream = s;
     return s >= 0 ? t->h_listen[t->out_set] : nullptr;
 }
-// A source rate for one stream or all (tlb_resample_set_source of the group's batch), while no tick is in flight.  The first real source
-// gives every group its second device input buffer; from then on every submit runs the resampler.  An object that never sets one makes
-// the device calls it always made.
-int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate)
+// A source rate (tlb_resample_set_source of the group's batch) or a DOWN source (tlb_decimate_set_source) for one stream or all, while no tick is
+// in flight.  The first real source gives every group its second device input buffer (d_rs), and from then on every submit runs the resampler;
+// the first real down source gives the object its pinned wide buffers and every group its device one, and from then on, while some stream has
+// a down source, every submit copies the wide slices of the groups that have one and runs the decimator ahead of their ingest.  An object that
+// never sets one makes the device calls it always made.
+static int tick_set_rate(tlb_tick *t, int stream, long source_rate, bool down)
 {
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || source_rate < 0 || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
+    const auto pairs = down ? tlb_down_pair : tlb_up_pair;
+    const auto prepare = down ? decimate_prepare : resample_prepare;
+    const auto set = down ? tlb_decimate_set_source : tlb_resample_set_source;
+    const auto get = down ? tlb_decimate_source : tlb_resample_source;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
     bool any = false;
     std::vector<char> real(t->groups.size(), 0);                     // per group: the call gives some stream of it a real source
     if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) {     // every stream is checked before one is changed
-            const TickGroup &G = t->groups[(size_t)g];
+            const tlb_batch *b = t->groups[(size_t)g].b;
             bool r = false;
-            const int e = tlb_source_range(l0, l1, source_rate, [&G](int k) { return (long)G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate; }, &r);
+            const int e = tlb_rate_range(l0, l1, source_rate, pairs, [b](int k) { return batch_enc_rate(b, k); }, &r);
             real[(size_t)g] = r; any |= r;
             return e;
         })) return rc;
-    if (!any && !t->groups[0].d_rs) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
-    if (any && (t->short_reads || t->feed || t->down || t->dfeed)) return TLB_ERR_ARG;
+    const bool made = down ? t->h_wide[0] != nullptr : t->groups[0].d_rs != nullptr;
+    if (!any && !made) return TLB_OK;                                // off, and never on: nothing to allocate or to clear
+    if (any && !tick_may_set(t, down ? TLB_IN_DOWN_SOURCE : TLB_IN_UP_SOURCE)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
-    if (!t->groups[0].d_rs) {                                        // first real source: every group's buffer, and the resampler of the batches that get
-        TlbMem m;                                                    // a source, before anything is committed or a stream is changed
-        std::vector<TickGroup> gs = t->groups;
-        for (auto &G : gs) G.d_rs = m.dev<int16_t>((size_t)G.n * 2304);
-        for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = resample_prepare(gs[g].b)) return rc;
-        if (!m.settle()) return TLB_ERR_HIP;
-        m.commit(t->mem);
-        t->groups.swap(gs);
-    }
-    const int rc = t->blocks.visit(stream, [&](int g, int k) { return tlb_resample_set_source(t->groups[(size_t)g].b, k, source_rate); });
-    t->resample = false;                                             // "at least one source set", as the streams stand now
-    for (auto &G : t->groups)
-        for (int k = 0; k < G.n; k++) if (tlb_resample_source(G.b, k)) t->resample = true;
-    return rc;
-}
-// A down source for one stream or all (tlb_decimate_set_source of the group's batch), while no tick is in flight.  The first real one gives
-// the object its pinned wide buffers and every group its device one; from then on, while some stream has a down source, every submit copies
-// the wide slices of the groups that have one and runs the decimator ahead of their ingest.  An object that never sets one makes the device
-// calls it always made.
-int tlb_tick_set_down_source(tlb_tick *t, int stream, long source_rate)
-{
-    if (!t || t->finished || stream < -1 || stream >= t->nstreams || source_rate < 0 || t->ticks != t->waited) return TLB_ERR_ARG;
-    if (t->broken) return TLB_ERR_HIP;
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
-    bool any = false;
-    std::vector<char> real(t->groups.size(), 0);                     // per group: the call gives some stream of it a real down source
-    if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) {     // every stream is checked before one is changed
-            const TickGroup &G = t->groups[(size_t)g];
-            bool r = false;
-            const int e = tlb_down_range(l0, l1, source_rate, [&G](int k) { return (long)G.b->h_uniq[(size_t)G.b->h_stream_cfg[(size_t)k]].samplerate; }, &r);
-            real[(size_t)g] = r; any |= r;
-            return e;
-        })) return rc;
-    if (!any && !t->h_wide[0]) return TLB_OK;                        // off, and never on: nothing to allocate or to clear
-    if (any && (t->short_reads || t->feed || t->resample || t->dfeed)) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(t->device));
-    if (!t->h_wide[0]) {                                             // first real down source: the wide buffers, and the decimator of the batches that get
+    if (!made) {                                                     // first real source: the buffers, and the resampler or decimator of the batches that get
         TlbMem m;                                                    // one, before anything is committed or a stream is changed
         std::vector<TickGroup> gs = t->groups;
-        int16_t *h[2];
-        for (int k = 0; k < 2; k++) h[k] = m.pinned<int16_t>((size_t)t->nstreams * TLB_DECIMATE_SLOT);
-        for (auto &G : gs) G.d_wide = m.dev<int16_t>((size_t)G.n * TLB_DECIMATE_SLOT);
-        for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = decimate_prepare(gs[g].b)) return rc;
+        int16_t *h[2] = {};
+        for (int k = 0; k < 2 && down; k++) h[k] = m.pinned<int16_t>((size_t)t->nstreams * TLB_DECIMATE_SLOT);
+        for (auto &G : gs) (down ? G.d_wide : G.d_rs) = m.dev<int16_t>((size_t)G.n * (down ? TLB_DECIMATE_SLOT : 2304));
+        for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = prepare(gs[g].b)) return rc;
         if (!m.settle()) return TLB_ERR_HIP;
         m.commit(t->mem);
         t->groups.swap(gs);
-        memcpy(t->h_wide, h, sizeof h);
+        if (down) memcpy(t->h_wide, h, sizeof h);
     }
-    const int rc = t->blocks.visit(stream, [&](int g, int k) { return tlb_decimate_set_source(t->groups[(size_t)g].b, k, source_rate); });
-    t->down = false;                                                 // "at least one down source set", as the streams stand now
+    const int rc = t->blocks.visit(stream, [&](int g, int k) { return set(t->groups[(size_t)g].b, k, source_rate); });
+    bool on = false;                                                 // "at least one source set", as the streams stand now
     for (auto &G : t->groups) {
         int n = 0;
-        for (int k = 0; k < G.n; k++) n += tlb_decimate_source(G.b, k) != 0;
-        G.any_down = n > 0; G.all_down = n == G.n;
-        t->down |= G.any_down;
+        for (int k = 0; k < G.n; k++) n += get(G.b, k) != 0;
+        if (down) { G.any_down = n > 0; G.all_down = n == G.n; }
+        on |= n > 0;
     }
+    (down ? t->down : t->resample) = on;
     return rc;
 }
+int tlb_tick_set_source(tlb_tick *t, int stream, long source_rate) { return tick_set_rate(t, stream, source_rate, false); }
+int tlb_tick_set_down_source(tlb_tick *t, int stream, long source_rate) { return tick_set_rate(t, stream, source_rate, true); }
 int16_t *tlb_tick_down(tlb_tick *t, int stream)
 {
     if (!tick_input_free(t) || !t->down || stream < 0 || stream >= t->nstreams) return nullptr;
@@ -432,180 +433,115 @@ int tlb_tick_down_need(const tlb_tick *t, int stream)
     int k; const TickGroup *G = tick_group_of(t, stream, &k);
     return G ? tlb_decimate_need(G->b, k, 0) : -TLB_ERR_ARG;
 }
-// A Layer II feed for one stream or all (tlb_feed_set of the group's batch), while no tick is in flight.  The first feed gives the object
-// its pinned feed buffers and every group its device ones; a wider feed than any before replaces the frame buffers (RE-FETCH).  An object
-// that never sets one makes the device calls it always made.
-static void tick_feed_refresh(tlb_tick *t)
+// A feed of the lane's family for one stream or all (the family's set of the group's batch), while no tick is in flight.  The lane's first feed
+// gives the object its pinned buffers and every group its device ones; a wider feed than any before replaces the frame buffers (RE-FETCH).  An
+// object that never sets one makes the device calls it always made.
+static void tick_lane_refresh(tlb_tick *t, int lane)
 {
-    t->feed = false;
+    TickLane &L = t->lane[lane];
+    const FeedFamily &F = tick_families[lane];
+    L.on = false;
     for (auto &G : t->groups) {
+        TickLaneGroup &LG = G.lane[lane];
         int fed = 0;
-        for (int k = 0; k < G.n; k++) fed += tlb_feed_get(G.b, k, nullptr) > 0;
-        G.any_fed = fed > 0; G.all_fed = fed == G.n;
-        t->feed |= G.any_fed;
-        // a group without a fed stream runs no feed kernel: its streams read EMPTY (no tick is in flight, or the device has been waited for)
-        if (!G.any_fed && t->h_feed_report[0])
-            for (int k = 0; k < 3; k++) for (int i = 0; i < G.n; i++) { tlb_frame_report r = {}; r.status = TLB_DEC_EMPTY; t->h_feed_report[k][G.first + i] = r; }
+        bool adapted;
+        for (int k = 0; k < G.n; k++) fed += F.get(G.b, k, nullptr, &adapted) > 0;
+        LG.any = fed > 0; LG.all = fed == G.n;
+        L.on |= LG.any;
+        // a group without a fed stream runs no kernel of the family: its slots read EMPTY (no tick is in flight, or the device has been waited for)
+        if (!LG.any && L.h_report[0])
+            for (int k = 0; k < 3; k++) for (int i = 0; i < F.slots * G.n; i++) { tlb_frame_report r = {}; r.status = TLB_DEC_EMPTY; L.h_report[k][F.slots * G.first + i] = r; }
     }
 }
-// adapt: through tlb_feed_set_adapted (a legal rate pair and any channel counts instead of the stream's own)
-static int tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg, bool adapt)
+static int tick_lane_set(tlb_tick *t, int lane, int stream, const tlb_feed_config *cfg, bool adapt)
 {
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
-    if (!cfg && !t->h_feed_len[0]) return TLB_OK;                    // off, and never on: nothing to allocate or to clear
+    TickLane &L = t->lane[lane];
+    const FeedFamily &F = tick_families[lane];
+    if (!cfg && !L.h_len[0]) return TLB_OK;                          // off, and never on: nothing to allocate or to clear
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
     if (cfg) {
-        if (t->short_reads || t->resample || t->down || t->dfeed) return TLB_ERR_ARG;       // (include/toolame_batch.h: feeds exclude short reads, sources, down sources and down feeds)
+        if (!tick_may_set(t, F.input)) return TLB_ERR_ARG;
         // every stream is checked before one is changed
-        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return (adapt ? feed_fits_adapted : feed_fits)(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
+        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return F.fits(t->groups[(size_t)g].b, l0, l1, cfg, adapt); })) return rc;
     }
     HIPCHK(hipSetDevice(t->device));
-    const size_t ns = (size_t)t->nstreams;
-    if (!t->h_feed_len[0]) {                                         // the first feed: lengths and reports, made once
+    const size_t ns = (size_t)t->nstreams, per = (size_t)F.slots;
+    if (!L.h_len[0]) {                                               // the lane's first feed: lengths and reports, made once
         TlbMem m;
         std::vector<TickGroup> gs = t->groups;
         int32_t *h_len[2]; tlb_frame_report *h_rep[3];
-        for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(ns);
-        for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(ns);
-        for (auto &G : gs) { G.d_feed_len = m.dev<int32_t>((size_t)G.n); G.d_feed_report = m.dev<tlb_frame_report>((size_t)G.n); }
+        for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(per * ns);
+        for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(per * ns);
+        for (auto &G : gs) { G.lane[lane].d_len = m.dev<int32_t>(per * (size_t)G.n); G.lane[lane].d_report = m.dev<tlb_frame_report>(per * (size_t)G.n); }
         if (!m.settle()) return TLB_ERR_HIP;
         m.commit(t->mem);
         t->groups.swap(gs);
-        memcpy(t->h_feed_len, h_len, sizeof h_len); memcpy(t->h_feed_report, h_rep, sizeof h_rep);
+        memcpy(L.h_len, h_len, sizeof h_len); memcpy(L.h_report, h_rep, sizeof h_rep);
     }
     const int want = cfg ? feed_slot_bytes(cfg) : 0;
-    if (want > t->feed_stride) {                                     // wider slots: new frame buffers, all of them before any is let go (no tick is in flight)
+    if (want > L.stride) {                                           // wider slots: new frame buffers, all of them before any is let go (no tick is in flight)
         std::unique_ptr<TlbMem> m(new TlbMem);                       // stage, settle, then the owners change places: the narrower buffers go with the old one
         uint8_t *h[2];
         std::vector<uint8_t *> d(t->groups.size(), nullptr);
-        for (int k = 0; k < 2; k++) h[k] = m->pinned<uint8_t>(ns * (size_t)want);
-        for (size_t g = 0; g < d.size(); g++) d[g] = m->scratch<uint8_t>((size_t)t->groups[g].n * (size_t)want);
+        for (int k = 0; k < 2; k++) h[k] = m->pinned<uint8_t>(per * ns * (size_t)want);
+        for (size_t g = 0; g < d.size(); g++) d[g] = m->scratch<uint8_t>(per * (size_t)t->groups[g].n * (size_t)want);
         if (!m->settle()) return TLB_ERR_HIP;
-        t->feed_mem.swap(m);
-        for (int k = 0; k < 2; k++) t->h_feed[k] = h[k];
-        for (size_t g = 0; g < d.size(); g++) t->groups[g].d_feed = d[g];
-        t->feed_stride = want;
+        L.mem.swap(m);
+        for (int k = 0; k < 2; k++) L.h_frames[k] = h[k];
+        for (size_t g = 0; g < d.size(); g++) t->groups[g].lane[lane].d_frames = d[g];
+        L.stride = want;
     }
     // what the named streams have now: after a device failure half way the groups already changed get it back (fresh history), so that
     // "all or nothing" holds for the feeds themselves; the wider buffers stay
     std::vector<tlb_feed_config> before(ns, tlb_feed_config{0, 0, 0});
     std::vector<char> before_adapted(ns, 0);
     for (auto &G : t->groups) for (int k = 0; k < G.n; k++) {
-        (void)tlb_feed_get(G.b, k, &before[(size_t)(G.first + k)]);
-        before_adapted[(size_t)(G.first + k)] = tlb_feed_adapted(G.b, k) > 0;
+        bool a = false;
+        (void)F.get(G.b, k, &before[(size_t)(G.first + k)], &a);
+        before_adapted[(size_t)(G.first + k)] = a;
     }
     const int rc = t->blocks.visit(stream, [&](int g, int k) {
-        const int e = (adapt ? tlb_feed_set_adapted : tlb_feed_set)(t->groups[(size_t)g].b, k, cfg);
+        const int e = F.set(t->groups[(size_t)g].b, k, cfg, adapt);
         if (e) t->blocks.visit_range(s0, s1, [&](int u, int l0, int l1) {      // the named streams of the groups up to and including this one
             const TickGroup &U = t->groups[(size_t)u];
             for (int i = l0; i < l1 && u <= g; i++) {
                 const tlb_feed_config &f = before[(size_t)(U.first + i)];
-                (void)(before_adapted[(size_t)(U.first + i)] ? tlb_feed_set_adapted : tlb_feed_set)(U.b, i, f.bitrate ? &f : nullptr);
+                (void)F.set(U.b, i, f.bitrate ? &f : nullptr, before_adapted[(size_t)(U.first + i)] != 0);
             }
             return 0;
         });
         return e;
     });
-    tick_feed_refresh(t);
-    for (int k = 0; k < 2; k++) memset(t->h_feed_len[k], 0, ns * sizeof(int32_t));
+    tick_lane_refresh(t, lane);
+    for (int k = 0; k < 2; k++) memset(L.h_len[k], 0, per * ns * sizeof(int32_t));
     return rc;
 }
-int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_set_feed(t, stream, cfg, false); }
-int tlb_tick_set_feed_adapted(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_set_feed(t, stream, cfg, true); }
-// is a feed frame wanted in the stream's slot of the input set to fill next (the group's batch advances its position with every submit)
-int tlb_tick_feed_want(const tlb_tick *t, int stream)
+// the lane's accessors: the feed frames wanted in the stream's slots of the input set to fill next (the group's batch advances its position with
+// every submit); the input set's frames and lengths, the slot width, the reports of the tick waited for last
+static int tick_lane_want(const tlb_tick *t, int lane, int stream)
 {
     int k; const TickGroup *G = tick_group_of(t, stream, &k);
-    return G ? tlb_feed_want(G->b, k, 0) : -TLB_ERR_ARG;
+    return G ? tick_families[lane].want(G->b, k, 0) : -TLB_ERR_ARG;
 }
-uint8_t *tlb_tick_feed(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed[t->in_set] : nullptr; }
-int32_t *tlb_tick_feed_len(tlb_tick *t) { return tick_input_free(t) && t->feed ? t->h_feed_len[t->in_set] : nullptr; }
-int tlb_tick_feed_stride(const tlb_tick *t) { return t && t->feed ? t->feed_stride : 0; }
-const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t) { return t && t->feed ? t->h_feed_report[t->out_set] : nullptr; }
-// A down feed for one stream or all (tlb_feed_down_set of the group's batch), while no tick is in flight: tick_set_feed with two slots per
-// stream.  An object that never sets one makes the device calls it always made.
-static void tick_dfeed_refresh(tlb_tick *t)
-{
-    t->dfeed = false;
-    for (auto &G : t->groups) {
-        int fed = 0;
-        for (int k = 0; k < G.n; k++) fed += tlb_feed_down_get(G.b, k, nullptr) > 0;
-        G.any_dfed = fed > 0; G.all_dfed = fed == G.n;
-        t->dfeed |= G.any_dfed;
-        // a group without a fed stream runs no down-feed kernel: its slots read EMPTY (no tick is in flight, or the device has been waited for)
-        if (!G.any_dfed && t->h_dfeed_report[0])
-            for (int k = 0; k < 3; k++) for (int i = 0; i < 2 * G.n; i++) { tlb_frame_report r = {}; r.status = TLB_DEC_EMPTY; t->h_dfeed_report[k][2 * G.first + i] = r; }
-    }
-}
-int tlb_tick_set_down_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg)
-{
-    if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
-    if (t->broken) return TLB_ERR_HIP;
-    if (!cfg && !t->h_dfeed_len[0]) return TLB_OK;                   // off, and never on: nothing to allocate or to clear
-    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
-    if (cfg) {
-        if (t->short_reads || t->resample || t->down || t->feed) return TLB_ERR_ARG;       // (include/toolame_batch.h: down feeds exclude short reads, sources, down sources and feeds)
-        // every stream is checked before one is changed
-        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) { return feed_down_fits(t->groups[(size_t)g].b, l0, l1, cfg); })) return rc;
-    }
-    HIPCHK(hipSetDevice(t->device));
-    const size_t ns = (size_t)t->nstreams;
-    if (!t->h_dfeed_len[0]) {                                        // the first down feed: lengths and reports, made once
-        TlbMem m;
-        std::vector<TickGroup> gs = t->groups;
-        int32_t *h_len[2]; tlb_frame_report *h_rep[3];
-        for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(2 * ns);
-        for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(2 * ns);
-        for (auto &G : gs) { G.d_dfeed_len = m.dev<int32_t>(2 * (size_t)G.n); G.d_dfeed_report = m.dev<tlb_frame_report>(2 * (size_t)G.n); }
-        if (!m.settle()) return TLB_ERR_HIP;
-        m.commit(t->mem);
-        t->groups.swap(gs);
-        memcpy(t->h_dfeed_len, h_len, sizeof h_len); memcpy(t->h_dfeed_report, h_rep, sizeof h_rep);
-    }
-    const int want = cfg ? feed_slot_bytes(cfg) : 0;
-    if (want > t->dfeed_stride) {                                    // wider slots: new frame buffers, all of them before any is let go (no tick is in flight)
-        std::unique_ptr<TlbMem> m(new TlbMem);                       // stage, settle, then the owners change places: the narrower buffers go with the old one
-        uint8_t *h[2];
-        std::vector<uint8_t *> d(t->groups.size(), nullptr);
-        for (int k = 0; k < 2; k++) h[k] = m->pinned<uint8_t>(2 * ns * (size_t)want);
-        for (size_t g = 0; g < d.size(); g++) d[g] = m->scratch<uint8_t>(2 * (size_t)t->groups[g].n * (size_t)want);
-        if (!m->settle()) return TLB_ERR_HIP;
-        t->dfeed_mem.swap(m);
-        for (int k = 0; k < 2; k++) t->h_dfeed[k] = h[k];
-        for (size_t g = 0; g < d.size(); g++) t->groups[g].d_dfeed = d[g];
-        t->dfeed_stride = want;
-    }
-    // what the named streams have now: after a device failure half way the groups already changed get it back (fresh state), so that
-    // "all or nothing" holds for the down feeds themselves; the wider buffers stay
-    std::vector<tlb_feed_config> before(ns, tlb_feed_config{0, 0, 0});
-    for (auto &G : t->groups) for (int k = 0; k < G.n; k++) (void)tlb_feed_down_get(G.b, k, &before[(size_t)(G.first + k)]);
-    const int rc = t->blocks.visit(stream, [&](int g, int k) {
-        const int e = tlb_feed_down_set(t->groups[(size_t)g].b, k, cfg);
-        if (e) t->blocks.visit_range(s0, s1, [&](int u, int l0, int l1) {      // the named streams of the groups up to and including this one
-            const TickGroup &U = t->groups[(size_t)u];
-            for (int i = l0; i < l1 && u <= g; i++) {
-                const tlb_feed_config &f = before[(size_t)(U.first + i)];
-                (void)tlb_feed_down_set(U.b, i, f.bitrate ? &f : nullptr);
-            }
-            return 0;
-        });
-        return e;
-    });
-    tick_dfeed_refresh(t);
-    for (int k = 0; k < 2; k++) memset(t->h_dfeed_len[k], 0, 2 * ns * sizeof(int32_t));
-    return rc;
-}
-// the feed frames wanted in the stream's slots of the input set to fill next (the group's batch advances its position with every submit)
-int tlb_tick_down_feed_want(const tlb_tick *t, int stream)
-{
-    int k; const TickGroup *G = tick_group_of(t, stream, &k);
-    return G ? tlb_feed_down_want(G->b, k, 0) : -TLB_ERR_ARG;
-}
-uint8_t *tlb_tick_down_feed(tlb_tick *t) { return tick_input_free(t) && t->dfeed ? t->h_dfeed[t->in_set] : nullptr; }
-int32_t *tlb_tick_down_feed_len(tlb_tick *t) { return tick_input_free(t) && t->dfeed ? t->h_dfeed_len[t->in_set] : nullptr; }
-int tlb_tick_down_feed_stride(const tlb_tick *t) { return t && t->dfeed ? t->dfeed_stride : 0; }
-const tlb_frame_report *tlb_tick_down_feed_report(const tlb_tick *t) { return t && t->dfeed ? t->h_dfeed_report[t->out_set] : nullptr; }
+static uint8_t *tick_lane_frames(tlb_tick *t, int lane) { return tick_input_free(t) && t->lane[lane].on ? t->lane[lane].h_frames[t->in_set] : nullptr; }
+static int32_t *tick_lane_len(tlb_tick *t, int lane) { return tick_input_free(t) && t->lane[lane].on ? t->lane[lane].h_len[t->in_set] : nullptr; }
+static int tick_lane_stride(const tlb_tick *t, int lane) { return t && t->lane[lane].on ? t->lane[lane].stride : 0; }
+static const tlb_frame_report *tick_lane_report(const tlb_tick *t, int lane) { return t && t->lane[lane].on ? t->lane[lane].h_report[t->out_set] : nullptr; }
+int tlb_tick_set_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_lane_set(t, LANE_FEED, stream, cfg, false); }
+int tlb_tick_set_feed_adapted(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_lane_set(t, LANE_FEED, stream, cfg, true); }
+int tlb_tick_feed_want(const tlb_tick *t, int stream) { return tick_lane_want(t, LANE_FEED, stream); }
+uint8_t *tlb_tick_feed(tlb_tick *t) { return tick_lane_frames(t, LANE_FEED); }
+int32_t *tlb_tick_feed_len(tlb_tick *t) { return tick_lane_len(t, LANE_FEED); }
+int tlb_tick_feed_stride(const tlb_tick *t) { return tick_lane_stride(t, LANE_FEED); }
+const tlb_frame_report *tlb_tick_feed_report(const tlb_tick *t) { return tick_lane_report(t, LANE_FEED); }
+int tlb_tick_set_down_feed(tlb_tick *t, int stream, const tlb_feed_config *cfg) { return tick_lane_set(t, LANE_DOWN_FEED, stream, cfg, false); }
+int tlb_tick_down_feed_want(const tlb_tick *t, int stream) { return tick_lane_want(t, LANE_DOWN_FEED, stream); }
+uint8_t *tlb_tick_down_feed(tlb_tick *t) { return tick_lane_frames(t, LANE_DOWN_FEED); }
+int32_t *tlb_tick_down_feed_len(tlb_tick *t) { return tick_lane_len(t, LANE_DOWN_FEED); }
+int tlb_tick_down_feed_stride(const tlb_tick *t) { return tick_lane_stride(t, LANE_DOWN_FEED); }
+const tlb_frame_report *tlb_tick_down_feed_report(const tlb_tick *t) { return tick_lane_report(t, LANE_DOWN_FEED); }
 int tlb_tick_need(const tlb_tick *t, int stream)
 {
     int k; const TickGroup *G = tick_group_of(t, stream, &k);
@@ -642,8 +578,7 @@ int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config
     if (!G || t->finished) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     const int rc = tlb_stream_reconfigure(G->b, k, cfg);
-    if (t->feed) tick_feed_refresh(t);                               // (a feed the stream's new rate or channel count no longer fits has been removed)
-    if (t->dfeed) tick_dfeed_refresh(t);                             // (... and so has a down feed whose rate no longer pairs with the stream's)
+    for (int lane = 0; lane < LANES; lane++) if (t->lane[lane].on) tick_lane_refresh(t, lane);      // (a feed the stream's new rate or channel count no longer fits has been removed)
     return rc;
 }
 
@@ -678,8 +613,10 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
     // (tlb_tick_finish runs no feed kernel: its set shows the last tick's reports once more)
-    if (G.any_fed) HIPCHK(hipMemcpyAsync(t->h_feed_report[set] + G.first, G.d_feed_report, n * sizeof(tlb_frame_report), hipMemcpyDeviceToHost, t->s_out));
-    if (G.any_dfed) HIPCHK(hipMemcpyAsync(t->h_dfeed_report[set] + 2 * (size_t)G.first, G.d_dfeed_report, 2 * n * sizeof(tlb_frame_report), hipMemcpyDeviceToHost, t->s_out));
+    for (int lane = 0; lane < LANES; lane++) {
+        const size_t per = (size_t)tick_families[lane].slots;
+        if (G.lane[lane].any) HIPCHK(hipMemcpyAsync(t->lane[lane].h_report[set] + per * (size_t)G.first, G.lane[lane].d_report, per * n * sizeof(tlb_frame_report), hipMemcpyDeviceToHost, t->s_out));
+    }
     if (t->short_reads) {
         HIPCHK(hipMemcpyAsync(t->h_underrun_ms[set] + G.first, G.d_underrun_ms, n * 4, hipMemcpyDeviceToHost, t->s_out));
         HIPCHK(hipMemcpyAsync(t->h_underruns[set] + G.first, G.d_underruns, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -798,14 +735,16 @@ int tlb_tick_submit(tlb_tick *t)
         int rc = TLB_OK;
         hipError_t e = hipSuccess;
         if (t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_ingested, 0);
-        // a group all of whose streams have feeds takes no PCM over the link: the feed kernel writes every slot the ingest reads
+        // a group all of whose streams have feeds of one family takes no PCM over the link: the family's kernels write every slot the ingest reads
         // ... nor does a group all of whose streams have down sources: its wide slice comes in instead and the decimator writes every slot
-        // ... nor a group all of whose streams have down feeds
-        if (e == hipSuccess && !G.all_fed && !G.all_down && !G.all_dfed) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
-        if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed, t->h_feed[set] + (size_t)G.first * (size_t)t->feed_stride, n * (size_t)t->feed_stride, hipMemcpyHostToDevice, t->s_in);
-        if (e == hipSuccess && G.any_fed) e = hipMemcpyAsync(G.d_feed_len, t->h_feed_len[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
-        if (e == hipSuccess && G.any_dfed) e = hipMemcpyAsync(G.d_dfeed, t->h_dfeed[set] + 2 * (size_t)G.first * (size_t)t->dfeed_stride, 2 * n * (size_t)t->dfeed_stride, hipMemcpyHostToDevice, t->s_in);
-        if (e == hipSuccess && G.any_dfed) e = hipMemcpyAsync(G.d_dfeed_len, t->h_dfeed_len[set] + 2 * (size_t)G.first, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
+        if (e == hipSuccess && !G.lane[LANE_FEED].all && !G.all_down && !G.lane[LANE_DOWN_FEED].all) e = hipMemcpyAsync(G.d_inter, t->h_inter[set] + (size_t)G.first * 2304, n * 2304 * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
+        for (int lane = 0; lane < LANES; lane++) {
+            const TickLane &L = t->lane[lane];
+            const TickLaneGroup &LG = G.lane[lane];
+            const size_t per = (size_t)tick_families[lane].slots;
+            if (e == hipSuccess && LG.any) e = hipMemcpyAsync(LG.d_frames, L.h_frames[set] + per * (size_t)G.first * (size_t)L.stride, per * n * (size_t)L.stride, hipMemcpyHostToDevice, t->s_in);
+            if (e == hipSuccess && LG.any) e = hipMemcpyAsync(LG.d_len, L.h_len[set] + per * (size_t)G.first, per * n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
+        }
         if (e == hipSuccess && G.any_down) e = hipMemcpyAsync(G.d_wide, t->h_wide[set] + (size_t)G.first * TLB_DECIMATE_SLOT, n * TLB_DECIMATE_SLOT * sizeof(int16_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->short_reads) e = hipMemcpyAsync(G.d_valid, t->h_valid[set] + G.first, n * sizeof(int32_t), hipMemcpyHostToDevice, t->s_in);
         if (e == hipSuccess && t->with_xpad && t->ticks > 0) e = hipStreamWaitEvent(t->s_in, G.ev_encoded, 0);
@@ -815,8 +754,8 @@ int tlb_tick_submit(tlb_tick *t)
         if (e == hipSuccess) e = hipStreamWaitEvent(t->s_run, G.ev_in, 0);
         if (e == hipSuccess && t->ticks > 0) e = hipStreamWaitEvent(t->s_run, G.ev_out, 0);
         if (e != hipSuccess) rc = TLB_ERR_HIP;
-        if (!rc && G.any_fed) rc = feed_launch(G.b, G.d_feed, G.d_feed_len, 1, G.d_inter, G.d_feed_report, t->s_run, t->feed_stride);      // behind the copy-in, ahead of the ingest: a mixed group's fed slots are overwritten
-        if (!rc && G.any_dfed) rc = feed_down_launch(G.b, G.d_dfeed, G.d_dfeed_len, G.d_inter, G.d_dfeed_report, 1, t->s_run, t->dfeed_stride);      // likewise: decode, decimate, carry
+        for (int lane = 0; lane < LANES; lane++)                     // behind the copy-in, ahead of the ingest: a mixed group's fed slots are overwritten
+            if (!rc && G.lane[lane].any) rc = tick_families[lane].launch(G.b, G.lane[lane].d_frames, G.lane[lane].d_len, 1, G.d_inter, G.lane[lane].d_report, t->s_run, t->lane[lane].stride);
         if (!rc && t->resample) rc = tlb_resample_device(G.b, G.d_inter, 1, G.d_rs, t->s_run);
         if (!rc && G.any_down) rc = tlb_decimate_device(G.b, G.d_wide, 1, G.d_inter, t->s_run);      // behind the copy-in, ahead of the ingest: a mixed group's decimated slots are overwritten
         if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, t->resample ? G.d_rs : G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);
@@ -850,8 +789,8 @@ int tlb_tick_wait(tlb_tick *t)
     t->out_set = set;
     // the retired tick's input set goes back to the caller (now, or after the next submit): untouched streams are full reads
     if (t->short_reads) { int32_t *v = t->h_valid[t->waited & 1]; for (int i = 0; i < t->nstreams; i++) v[i] = TLB_SAMPLES_PER_FRAME; }
-    if (t->h_feed_len[0]) memset(t->h_feed_len[t->waited & 1], 0, (size_t)t->nstreams * sizeof(int32_t));      // ... and feed slots are empty
-    if (t->h_dfeed_len[0]) memset(t->h_dfeed_len[t->waited & 1], 0, 2 * (size_t)t->nstreams * sizeof(int32_t));
+    for (int lane = 0; lane < LANES; lane++)                         // ... and feed slots are empty
+        if (t->lane[lane].h_len[0]) memset(t->lane[lane].h_len[t->waited & 1], 0, (size_t)tick_families[lane].slots * (size_t)t->nstreams * sizeof(int32_t));
     t->waited++;
     return TLB_OK;
 }

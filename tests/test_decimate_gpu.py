@@ -86,6 +86,15 @@ def test_life_cycle(M, noise):
     b.close()
 
 
+def test_up_source_on_a_stream_with_a_down_source_is_refused(M):
+    """the other direction of test_life_cycle's last refusal, setters only: a stream has one source whichever family comes first"""
+    b = M.Batch(D.stream_configs(S))
+    b.set_down_source(48000, 0)                                      # stream 0 runs at 24 kHz: 16 kHz would be a legal up source of it
+    assert b.L.tlb_resample_set_source(b.h, 0, 16000) == 18
+    assert b.source(0) == 0 and b.down_source(0) == 48000
+    b.close()
+
+
 def test_overlapping_and_misaligned_buffers_are_refused(M):
     """host arrays standing in for device pointers: refused before any launch"""
     b = _down(M.Batch(D.stream_configs(S)))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a down feed costs and saves per tick (tlb_tick_set_down_feed), and what this commit costs an object that sets none, on the GPU.
 
-    python tools/tick_feed_down_cost.py [--streams 16384] [--ticks 100] [--rounds 5] [--psy 3] [--parent-lib PATH] [--out profiles/tick_feed_down.txt]
+    python tools/tick_feed_down_cost.py [--streams 16384] [--ticks 100] [--rounds 5] [--psy 3] [--parent-lib PATH] [--parent-legs] [--out profiles/tick_feed_down.txt]
 
 Tick objects of 24 kHz stereo 64 kbps, egress EDI AF, in one process on one box, the legs interleaved round by round:
   parent   the library of the parent commit (--parent-lib: a libtoolame_dab_hip.so built from it), 24 kHz PCM in       } (a): `plain` against
@@ -12,7 +12,10 @@ Tick objects of 24 kHz stereo 64 kbps, egress EDI AF, in one process on one box,
 Every round runs `ticks` ticks per leg with two ticks in flight (submit, submit, wait, ...) and keeps the median finished-tick interval
 (host clock, wait to wait) and the median of tlb_tick_last_ms (device clock: first copy-in queued -> last copy-out done).  The file gets
 the medians, minima and maxima over the rounds; the spread of the parent leg over its own rounds is the yardstick for (a).  A leg that
-cannot be run is written as NOT MEASURED with the reason."""
+cannot be run is written as NOT MEASURED with the reason.
+--parent-legs (a parent commit that has both families): the `fed` and `down` legs run on the parent's library too (`p-fed`, `p-down`), and
+every leg of this library is set against the same leg of the parent's, (c): the difference of the medians next to the spread (max - min over
+the rounds) the parent's leg shows in the same run, on both clocks."""
 import argparse
 import ctypes as C
 import sys
@@ -24,7 +27,8 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
-LEGS = ("parent", "plain", "fed", "down")
+LEGS = ("parent", "plain", "fed", "down", "p-fed", "p-down")
+PARENT_OF = {"plain": "parent", "fed": "p-fed", "down": "p-down"}
 
 
 def fmt(v):
@@ -39,6 +43,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--psy", type=int, default=3)
     ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--parent-legs", action="store_true", help="run the fed and down legs on --parent-lib too and compare leg by leg")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "tick_feed_down.txt"))
     args = ap.parse_args()
     import torch
@@ -62,10 +67,12 @@ def main():
     lines, objs, why = [], {}, {}
     libs = {"plain": None, "fed": None, "down": None}
     if args.parent_lib and Path(args.parent_lib).exists():
-        libs = {"parent": TL._bind(C.CDLL(str(Path(args.parent_lib).resolve()))), **libs}
+        parent = TL._bind(C.CDLL(str(Path(args.parent_lib).resolve())))
+        libs = {"parent": parent, **libs, **({"p-fed": parent, "p-down": parent} if args.parent_legs else {})}
     else:
         why["parent"] = "no library of the parent commit was given (--parent-lib)"
-    for name, lib in libs.items():
+    for leg, lib in libs.items():
+        name = leg[2:] if leg.startswith("p-") else leg               # what the leg does, whichever library does it
         t = M.Tick(cfg, egress="af", version=b"odr-audioenc_amd bench", lib=lib)
         if name == "down":
             t.set_down_source(48000)
@@ -96,7 +103,7 @@ def main():
             submit(); t.wait()
         if name == "fed":
             assert not t.down_feed_report["status"].any()
-        objs[name] = (t, submit)
+        objs[leg] = (t, submit)
     out = {k: {"interval_ms": [], "last_ms": []} for k in objs}
     for _ in range(args.rounds):
         for name, (t, submit) in objs.items():
@@ -119,7 +126,8 @@ def main():
     lines.append("A 24 kHz frame lasts 48 ms.  Over the link per stream and tick: fed 1160 bytes (two 576-byte slots, two lengths), down 9216, plain 4608.")
     for name in LEGS:
         if name not in out:
-            lines.append("%-7s NOT MEASURED: %s" % (name, why[name]))
+            if name in why:
+                lines.append("%-7s NOT MEASURED: %s" % (name, why[name]))
             continue
         lines.append("%-7s finished-tick interval ms: %s" % (name, fmt(out[name]["interval_ms"])))
         lines.append("%-7s tlb_tick_last_ms         : %s" % (name, fmt(out[name]["last_ms"])))
@@ -133,6 +141,11 @@ def main():
     lines.append("(b) fed - down    : interval %+.4f ms, last_ms %+.4f ms; fed - plain: interval %+.4f ms, last_ms %+.4f ms" % (
         med("fed", "interval_ms") - med("down", "interval_ms"), med("fed", "last_ms") - med("down", "last_ms"),
         med("fed", "interval_ms") - med("plain", "interval_ms"), med("fed", "last_ms") - med("plain", "last_ms")))
+    for name, p in PARENT_OF.items():
+        if args.parent_legs and p in out:
+            lines.append("(c) %-5s - %-6s: interval %+.4f ms (the parent leg's spread %.4f ms), last_ms %+.4f ms (spread %.4f ms)" % (
+                name, p, med(name, "interval_ms") - med(p, "interval_ms"), max(out[p]["interval_ms"]) - min(out[p]["interval_ms"]),
+                med(name, "last_ms") - med(p, "last_ms"), max(out[p]["last_ms"]) - min(out[p]["last_ms"])))
     text = "\n".join(lines) + "\n"
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(text)
