@@ -7,7 +7,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
 //   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
 //   header's padding bit, service s takes frame (tick + s) of it (wrapping round), one tick per frame of the file.  No PCM crosses the
@@ -29,6 +29,9 @@
 //   --compare: the compare monitor on top of it (tlb_tick_enable_compare with the header's default params; implies --monitor audio): every
 //   frame that leaves is decoded and set against the audio that went in.  A stream whose mismatch_run reaches 3 is printed when it does;
 //   one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any stream got there.
+//   --loudness: the loudness meter (tlb_tick_enable_loudness): the PCM the encoder is given (after -g) is measured on the device after
+//   ITU-R BS.1770-4 / EBU R 128.  One line per stream at the end: momentary (400 ms), short-term (3 s) and integrated loudness in LUFS
+//   (-inf where there is none yet), as "%.2f".
 // out.af: for every packet a little-endian uint32 length, then the packet.
 #include <chrono>
 #include <cstdint>
@@ -49,12 +52,12 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0;
     char mode = 0;
     double gain_db = 0.0;
     const char *feed_path = nullptr;
@@ -62,7 +65,8 @@ int main(int argc, char **argv)
     long feed_rate = 0;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
+        if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
+        if (k == "--loudness") { loudness = 1; i--; continue; }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") rate = std::atol(v);
@@ -131,6 +135,7 @@ int main(int argc, char **argv)
     if (gain_db != 0.0 && tlb_tick_set_gain_db(t, -1, gain_db)) die("gain", 0);
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
+    if (loudness) if (int rc = tlb_tick_enable_loudness(t)) die("tlb_tick_enable_loudness", rc);                 // likewise
     const bool down = source_rate > rate;                    // a source above the encoder's rate goes through the decimator and its wide slots
     if (source_rate && !down) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
     if (down) if (int rc = tlb_tick_set_down_source(t, -1, source_rate)) die("tlb_tick_set_down_source", rc);             // likewise
@@ -239,6 +244,14 @@ int main(int argc, char **argv)
         unsigned long compared = 0, judged = 0, mismatched = 0;
         for (int s = 0; s < nstreams; s++) { compared += c[s].frames_compared; judged += c[s].frames_judged; mismatched += c[s].mismatch_frames; }
         std::fprintf(stderr, "editick: compare: %lu frames compared, %lu judged, %lu mismatched, %d alarm(s)\n", compared, judged, mismatched, alarms);
+    }
+    if (loudness && frames > 0) {                                // the records of the last tick (the finish adds nothing); the gated value on request
+        const tlb_loudness_record *r = tlb_tick_loudness(t);
+        std::vector<tlb_loudness_programme_record> prog((size_t)nstreams);
+        if (int rc = tlb_tick_loudness_programme(t, prog.data())) die("tlb_tick_loudness_programme", rc);
+        for (int s = 0; s < nstreams; s++)
+            std::fprintf(stderr, "editick: loudness: stream %d: momentary %.2f LUFS, short-term %.2f LUFS, integrated %.2f LUFS (%u of %u blocks)\n", s,
+                         tlb_loudness_lufs(r[s].momentary), tlb_loudness_lufs(r[s].short_term), tlb_loudness_lufs(prog[(size_t)s].integrated), prog[(size_t)s].gated, r[s].blocks);
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",

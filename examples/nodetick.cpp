@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R]
+//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R]
 //   in.s16le: interleaved stereo at the services' rate (-r: 48000, the default, or 24000); stream s starts reading at frame s (so the
 //   services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
@@ -34,6 +34,8 @@
 //   reading at source frame 1152 s and takes tlb_node_need() consecutive frames every tick, wrapping around.  Not together with --short-every.
 //   With -r 24000, R = 48000, 44100 or 32000 is a DOWN source (tlb_node_set_down_source): the tlb_node_down_need() frames of a tick go into
 //   the service's wide slot (tlb_node_down) and are filtered and decimated on the GPUs.
+//   --loudness: the loudness meter (tlb_node_enable_loudness): the PCM every encoder is given is measured on its GPU after ITU-R BS.1770-4 /
+//   EBU R 128.  One line per service at the end: momentary, short-term and integrated loudness in LUFS (-inf where there is none yet).
 //   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
 //   frame that leaves is decoded on its GPU and set against the audio that went in.  A service whose mismatch_run reaches 3 is printed when
 //   it does; one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any service got there.
@@ -148,10 +150,10 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0;
     long rate = 48000;
     double deadline_ms = 0;
     long source_rate = 0;
@@ -160,7 +162,8 @@ int main(int argc, char **argv)
     std::string devs, outpath, feed_path;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compare") { compare = 1; i--; continue; }    // the one option without a value
+        if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
+        if (k == "--loudness") { loudness = 1; i--; continue; }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-n") nstreams = std::atoi(v);
@@ -254,6 +257,8 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_set_deadline_ms(nd, deadline_ms)) die("tlb_node_set_deadline_ms", rc);
     if (short_every)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
+    if (loudness)
+        if (int rc = tlb_node_enable_loudness(nd)) die("tlb_node_enable_loudness", rc);                 // likewise; a restarted shard measures again from zero
     if (monitor)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
     const bool down = source_rate > rate;
@@ -382,6 +387,14 @@ int main(int argc, char **argv)
         for (int s = 0; s < nstreams; s++)
             if (const tlb_compare_record *c = tlb_node_compare(nd, s)) { compared += c->frames_compared; judged += c->frames_judged; mismatched += c->mismatch_frames; }
         std::fprintf(stderr, "nodetick: compare: %lu frames compared, %lu judged, %lu mismatched, %d alarm(s)\n", compared, judged, mismatched, alarms);
+    }
+    if (loudness) {                                                       // the records of the last step; the gated value on request, between steps
+        std::vector<tlb_loudness_programme_record> prog((size_t)nstreams);
+        if (int rc = tlb_node_loudness_programme(nd, prog.data())) std::fprintf(stderr, "nodetick: tlb_node_loudness_programme (code %d)\n", rc);
+        for (int s = 0; s < nstreams; s++)
+            if (const tlb_loudness_record *r = tlb_node_loudness(nd, s))  // (NULL: its shard is down or late)
+                std::fprintf(stderr, "nodetick: loudness: service %d: momentary %.2f LUFS, short-term %.2f LUFS, integrated %.2f LUFS (%u of %u blocks)\n", s,
+                             tlb_loudness_lufs(r->momentary), tlb_loudness_lufs(r->short_term), tlb_loudness_lufs(prog[(size_t)s].integrated), prog[(size_t)s].gated, r->blocks);
     }
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",

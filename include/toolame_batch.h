@@ -1139,6 +1139,86 @@ int32_t *tlb_node_down_feed_len(tlb_node *nd, int stream);
 int tlb_node_down_feed_want(const tlb_node *nd, int stream);
 const tlb_frame_report *tlb_node_down_feed_report(const tlb_node *nd, int stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Programme loudness: momentary, short-term and gated programme ("integrated") loudness after ITU-R BS.1770-4 / EBU Tech 3341 of the PCM
+ * the encoder is given -- the ingest's planar output, therefore AFTER the stream's gain (tlb_set_gain_db is the actuator, this the
+ * measurement).  Opt-in; the meter lives on the device and reports ENERGIES as doubles: LUFS = -0.691 + 10 log10(E), tlb_loudness_lufs.
+ * THE ARITHMETIC.  The reference has no loudness meter, so this is the definition (tests/loudnesslib.py restates it in numpy, every
+ * comparison against it is bit for bit).  Every product and sum is its own rounded fp64 operation in the order written.
+ *   sample      x = (double)s * (1.0 / 32768.0)
+ *   K-weighting two biquads per channel in direct form I, t = ((b0*x) + (b1*x1)) + (b2*x2), y = (t - (a2*y2)) - (a1*y1); the second takes
+ *               the first's y as its x; state x1 x2 y1 y2 per stage and channel, zero at start, carried from frame to frame.  One
+ *               coefficient row per encoder rate (48, 44.1, 32, 24, 22.05, 16 kHz), committed as csrc/tl_loudness_tables.inc: the committed
+ *               table is the definition, tools/gen_loudness_tables.py the record of how it was made (the bilinear forms of BS.1770-4's
+ *               shelf and high-pass; at 48 kHz they are the coefficients the recommendation prints, to 1e-15)
+ *   bins        acc_c = acc_c + (y*y) sample by sample; a bin is 100 ms = rate / 10 samples (a frame closes at most one); on close
+ *               ms_c = acc_c / (double)binlen, z = ms_0 for a one-channel stream, ms_0 + ms_1 for a two-channel one (dual channel counts as
+ *               two channels; channel weights 1), acc = 0, z into a ring of 30
+ *   momentary   once 4 bins exist: m = (((z[-3] + z[-2]) + z[-1]) + z[0]) * 0.25        (400 ms)
+ *   short-term  once 30 bins exist: the ring summed oldest to newest, / 30.0             (3 s)
+ *               both are 0.0 before their bins exist; the maxima are plain > updates
+ *   gating      every m is one gating block.  E(L) = 10^((L + 0.691) / 10); edges e_0 = E(-70.0), e_j = E(-70.05 + 0.1 j), centres
+ *               c_j = E(-70.0 + 0.1 j), j up to 750, both in the committed table.  A block counts iff m > e_0, in the bin
+ *               #{k in 1..750: m >= e_k}; per stream 751 uint32 counts
+ *   programme   N = sum n_j, S = sum (double)n_j * c_j in ascending j; gate = 0.1 * (S / N); integrated = the same count-weighted mean over
+ *               the bins with c_j >= gate; both 0.0 when N == 0.  The 0.1 LU quantisation is part of the definition (its error of at
+ *               most 0.05 LU lies inside EBU Tech 3341's +-0.1 LU)
+ * RECORDS.  tlb_loudness_record: frames = PCM frames measured, bins = closed bins, blocks = gating blocks formed, gated = blocks above
+ * -70 LUFS (the histogram's total), then the four energies.  tlb_loudness_programme_record: gated = blocks at or above the relative gate.
+ * STATE.  About 3.4 KB of device memory per stream (filter state, ring, record, 3008 bytes of histogram: about 450 MB at 131 072
+ * streams), allocated by tlb_loudness_enable ALONE: a batch that never enables loudness allocates and queues nothing new, and the other
+ * calls answer TLB_ERR_ARG on it.
+ *   tlb_loudness_enable(b)            allocates the state (waits for the device once); a second call answers 0
+ *   tlb_loudness_device(b, d_pcm_planar, nframes, d_records, stream)
+ *                                     measures nframes of every stream, int16 [nframes][nstreams][2][1152] as tlb_ingest_device writes it
+ *                                     (16-byte aligned; the second row of a one-channel stream is not looked at), and writes
+ *                                     tlb_loudness_record [nstreams] (may be NULL) on hip_stream
+ *   tlb_loudness_host                 the same with host buffers
+ *   tlb_loudness_programme_device / _host     tlb_loudness_programme_record [nstreams] from the counts so far
+ *   tlb_loudness_reset(b, stream)     -1: every stream.  Waits for the queued work, then zeroes filter state, bins, ring, maxima, counters
+ *                                     and histogram: EBU mode's "reset"
+ *   tlb_loudness_taps(rate, out[10])  b0 b1 b2 a1 a2 of the shelf, then of the high-pass; no GPU.  TLB_ERR_SAMPLERATE for any other rate
+ *   tlb_loudness_scale(edges[751], centres[751])    the gating scale (each may be NULL); no GPU
+ *   tlb_loudness_lufs(energy)         -0.691 + 10 log10(energy); -inf for 0
+ * tlb_stream_reset and tlb_stream_reconfigure clear the stream's loudness state (the rate, and with it the coefficients and the bin length,
+ * may have changed); tlb_stream_finish leaves it.
+ * TICK PLANE.  tlb_tick_enable_loudness(t) before the first submit (TLB_ERR_ARG after it; a second call answers 0) enables the meter of
+ * every group's batch.  Every submit then queues the meter on the tick's planar PCM on the run stream, behind the ingest and behind the
+ * tick's encode and egress kernels; the 48-byte records travel with the three output sets behind the packets, on an event of their own: the
+ * packets' copy-out does not wait for them.  tlb_tick_loudness(t) is tlb_loudness_record [nstreams] of the tick waited for last (pinned,
+ * valid until the next wait); NULL when loudness is off.  The records count the PCM that went IN: after T waited ticks frames == T, and
+ * tlb_tick_finish adds nothing (its set shows the last tick's records).  tlb_tick_loudness_programme(t, out [nstreams]) and
+ * tlb_tick_loudness_reset(t, stream) (-1: all) are legal with no tick in flight (TLB_ERR_ARG otherwise, and when loudness is off).  An object
+ * that never enables loudness allocates and queues nothing new.
+ * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_loudness goes to every shard before the first submit, and a
+ * shard made by tlb_node_shard_restart is enabled again -- its records start from zero.  tlb_node_loudness(nd, stream) points at the STREAM's
+ * record and answers NULL for a broken, late or stale shard; tlb_node_loudness_programme(nd, out [nstreams]) fills the blocks of the live
+ * shards between steps (all zero for the others); tlb_node_loudness_reset routes like the stream life-cycle calls (TLB_ERR_HIP for a stream
+ * of a broken shard, TLB_ERR_LATE for one of a late shard), -1 goes to every live shard.
+ * NOT BUILT: true peak (oversampled), loudness range (LRA), acting on the gain, loudness of the decoded output (the monitors own that side).
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_LOUDNESS_BINS 751
+typedef struct { uint32_t frames, bins, blocks, gated;
+                 double momentary, short_term, momentary_max, short_term_max; } tlb_loudness_record;      /* 48 bytes */
+typedef struct { double integrated, gate; uint32_t gated, reserved; } tlb_loudness_programme_record;     /* 24 bytes */
+int tlb_loudness_enable(tlb_batch *b);
+int tlb_loudness_device(tlb_batch *b, const int16_t *d_pcm_planar, int nframes, tlb_loudness_record *d_records, void *hip_stream);
+int tlb_loudness_host(tlb_batch *b, const int16_t *pcm_planar, int nframes, tlb_loudness_record *records);
+int tlb_loudness_programme_device(tlb_batch *b, tlb_loudness_programme_record *d_out, void *hip_stream);
+int tlb_loudness_programme_host(tlb_batch *b, tlb_loudness_programme_record *out);
+int tlb_loudness_reset(tlb_batch *b, int stream);
+int tlb_loudness_taps(long samplerate, double out[10]);
+int tlb_loudness_scale(double edges[751], double centres[751]);
+double tlb_loudness_lufs(double energy);
+int tlb_tick_enable_loudness(tlb_tick *t);
+const tlb_loudness_record *tlb_tick_loudness(const tlb_tick *t);
+int tlb_tick_loudness_programme(tlb_tick *t, tlb_loudness_programme_record *out);
+int tlb_tick_loudness_reset(tlb_tick *t, int stream);
+int tlb_node_enable_loudness(tlb_node *nd);
+const tlb_loudness_record *tlb_node_loudness(const tlb_node *nd, int stream);
+int tlb_node_loudness_programme(tlb_node *nd, tlb_loudness_programme_record *out);
+int tlb_node_loudness_reset(tlb_node *nd, int stream);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

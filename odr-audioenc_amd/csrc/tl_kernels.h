@@ -14,6 +14,7 @@
 #include "mp2_decimate.h"
 #include "mp2_feed_adapt.h"
 #include "mp2_feed_down.h"
+#include "mp2_loudness.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -67,4 +68,8 @@ hipError_t tlk_resample(unsigned blocks, hipStream_t st, const int16_t *source, 
 // uint32 [2][nstreams][64], ratio int32 [nstreams] (TL_DC_*; the slots of a TL_DC_OFF stream are left alone)
 hipError_t tlk_decimate(unsigned blocks, hipStream_t st, const int16_t *wide, int16_t *out, uint32_t *state, const int32_t *ratio, const int16_t *taps,
                         const TlConfig *configs, const int32_t *stream_cfg, int nstreams, int nframes, int flip);
+// toolame_loudness.hip: tl_loudness_kernel, one wave per 32 consecutive streams over the call's frames in order (csrc/mp2_loudness.h);
+// tl_loudness_programme_kernel, one lane per stream (tables: the whole table, the kernel takes its centres)
+hipError_t tlk_loudness(hipStream_t st, const TlLoudnessArgs &A);
+hipError_t tlk_loudness_programme(hipStream_t st, const uint32_t *hist, const double *tables, TlLoudnessProgramme *out, int nstreams);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

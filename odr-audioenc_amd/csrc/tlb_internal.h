@@ -203,6 +203,12 @@ struct tlb_batch {
     uint8_t *d_fd_prev = nullptr;                // [nstreams][TL_FD_PREV_STRIDE] its bytes
     int16_t *d_fd_taps = nullptr;                // the decimator's three tables, a copy of the down feeds' own
     int16_t *d_fd_plane = nullptr;               // [nstreams][fd_plane_frames * TL_FD_PLANE] grow-only launch scratch with an owner of its own
+    // loudness meter (tlb_loudness.cpp; csrc/mp2_loudness.h), allocated by tlb_loudness_enable alone: a batch that never enables it has none of it
+    double *d_ld_lane = nullptr, *d_ld_ring = nullptr;       // [TL_LD_LANE_WORDS][2 nstreams] filter state, acc and bin position per (stream, channel); [TL_LD_RING][nstreams]
+    TlLoudnessRecord *d_ld_rec = nullptr;        // [nstreams] the record as it is reported
+    uint32_t *d_ld_hist = nullptr;               // [TL_LD_HIST_ROWS][nstreams] gating blocks per 0.1 LU
+    TlLoudnessProgramme *d_ld_prog = nullptr;    // [nstreams] scratch of tlb_loudness_programme_host
+    double *d_ld_tables = nullptr;               // the committed table: taps [6][10], edges [751], centres [751]
     TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -263,6 +269,9 @@ int feed_down_after_reconfigure(tlb_batch *b, int stream);
 // slots of `stride` bytes, at least tlb_feed_down_stride(b)
 int feed_down_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
 int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
+
+// tlb_loudness.cpp: the loudness state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); nothing when loudness was never enabled
+int loudness_clear_streams(tlb_batch *b, int s0, int n);
 
 // the encoder's rate of stream s
 static inline long batch_enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }

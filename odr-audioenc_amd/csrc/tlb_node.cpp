@@ -162,6 +162,7 @@ struct tlb_node {
     int monitor = 0;                             // tlb_node_enable_monitor(): TLB_MONITOR_* of every shard's tick object (a restarted shard's too)
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
+    bool loudness = false;                       // tlb_node_enable_loudness(): every shard's tick object measures loudness (a restarted shard's too, from zero)
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
     // The per-stream input families (csrc/tlb_inputs.h; node_families below): what tlb_node_set_source, _set_down_source, _set_feed and
     // _set_down_feed gave every stream, set again on a restarted shard.  A source is its rate alone; samplerate 0: the stream has none;
@@ -368,6 +369,7 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (nd->short_reads) if (int rc = tlb_tick_enable_short_reads(s.tick)) return rc;
         if (nd->monitor) if (int rc = tlb_tick_enable_monitor(s.tick, nd->monitor)) return rc;
         if (nd->compare) if (int rc = tlb_tick_enable_compare(s.tick, &nd->cparams)) return rc;
+        if (nd->loudness) if (int rc = tlb_tick_enable_loudness(s.tick)) return rc;
         int k;
         if (nd->monitor && nd->of(nd->listen, &k) == &s) if (int rc = tlb_tick_monitor_listen(s.tick, k)) return rc;
     } else {
@@ -654,6 +656,33 @@ int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params)
     return rc;
 }
 const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_compare>(nd, stream); }
+// The loudness meter (tlb_tick_enable_loudness of every shard, on the shards' threads): before the first submit, TICK plane only.
+int tlb_node_enable_loudness(tlb_node *nd)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
+    if (nd->loudness) return TLB_OK;
+    const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_loudness(s.tick) : (int)TLB_ERR_HIP; });
+    if (!rc) nd->loudness = true;
+    return rc;
+}
+const tlb_loudness_record *tlb_node_loudness(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_loudness>(nd, stream); }
+// Programme loudness of every stream, out [nstreams], between steps: each live shard fills its block on its own thread; the records of a
+// broken or late shard's streams are all zero.
+int tlb_node_loudness_programme(tlb_node *nd, tlb_loudness_programme_record *out)
+{
+    if (!nd || !out || !nd->loudness || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    memset(out, 0, sizeof(tlb_loudness_programme_record) * (size_t)nd->nstreams);
+    return nd->live("loudness_programme", [out](Shard &s) { return tlb_tick_loudness_programme(s.tick, out + s.first); });
+}
+// EBU mode's reset of one stream (to its shard, through the gate of the life-cycle calls) or of all (-1: every live shard), between steps.
+int tlb_node_loudness_reset(tlb_node *nd, int stream)
+{
+    if (!nd || !nd->loudness || stream < -1 || stream >= nd->nstreams || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    if (stream < 0) return nd->live("loudness_reset", [](Shard &s) { return tlb_tick_loudness_reset(s.tick, -1); });
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return rc;
+    return nd->one(s->index, [&](Shard &sh) { return tlb_tick_loudness_reset(sh.tick, k); });
+}
 // One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'
 // tick objects that their next submit reads; no shard but a late one runs a job between the node's calls, and a late one is left alone
 // (it cannot be the stream's shard: TLB_ERR_LATE).

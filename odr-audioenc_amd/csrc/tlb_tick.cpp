@@ -78,6 +78,8 @@ struct TickGroup {
     // down sources (tlb_tick_set_down_source): the group's slice of the tick's wide slots; the decimator writes the streams' slots of d_inter
     int16_t *d_wide = nullptr;
     bool any_down = false, all_down = false;                    // some / every stream of the group has a down source (all: the group's PCM is not copied in)
+    tlb_loudness_record *d_loud = nullptr;                      // loudness meter (tlb_tick_enable_loudness): the group's records of this tick
+    hipEvent_t ev_loud = nullptr;                               // ... written: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_mon = nullptr;                                // decode + fold (+ compare) done: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
@@ -113,6 +115,9 @@ struct tlb_tick {
     bool compare = false;
     tlb_compare_params cparams = {};
     tlb_compare_record *h_crecord[3] = {};
+    // loudness meter, off until tlb_tick_enable_loudness(): the records travel with the output sets
+    bool loudness = false;
+    tlb_loudness_record *h_loud[3] = {};
 #ifdef TLB_FAULT_INJECT
     int damage_nth = 0, damage_stream = 0, damage_byte = 0; uint8_t damage_xor = 0, damage_val = 0;      // tlb_debug_tick_damage_next
     int cross_nth = 0, cross_a = -1, cross_b = -1; bool cross_on = false; uint8_t *d_cross_tmp = nullptr;   // tlb_debug_tick_cross_from
@@ -155,6 +160,7 @@ void tlb_tick_destroy(tlb_tick *t)
         if (g.ev_encoded) (void)hipEventDestroy(g.ev_encoded);
         if (g.ev_out) (void)hipEventDestroy(g.ev_out);
         if (g.ev_mon) (void)hipEventDestroy(g.ev_mon);
+        if (g.ev_loud) (void)hipEventDestroy(g.ev_loud);
     }
     if (t->s_in) (void)hipStreamDestroy(t->s_in);
     if (t->s_run) (void)hipStreamDestroy(t->s_run);
@@ -359,6 +365,48 @@ int tlb_tick_enable_compare(tlb_tick *t, const tlb_compare_params *params)
     return TLB_OK;
 }
 const tlb_compare_record *tlb_tick_compare(const tlb_tick *t) { return t && t->compare ? t->h_crecord[t->out_set] : nullptr; }
+// The loudness meter (tlb_loudness_*) is opted into the same way: the state of every group's batch is made here, and every submit then queues
+// the meter on the tick's planar PCM (d_pcm, what the encoder is given) behind the egress kernels.  An object that never makes the call
+// allocates and queues nothing new.
+int tlb_tick_enable_loudness(tlb_tick *t)
+{
+    if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (t->loudness) return TLB_OK;
+    HIPCHK(hipSetDevice(t->device));
+    for (auto &G : t->groups) if (!G.ev_loud) HIPCHK(hipEventCreateWithFlags(&G.ev_loud, hipEventDisableTiming));  // (a refused attempt keeps them for the next)
+    TlbMem m;
+    std::vector<TickGroup> gs = t->groups;
+    tlb_loudness_record *h_loud[3];
+    for (int k = 0; k < 3; k++) h_loud[k] = m.pinned<tlb_loudness_record>((size_t)t->nstreams);
+    for (auto &G : gs) {
+        if (int rc = tlb_loudness_enable(G.b)) return rc;
+        G.d_loud = m.dev<tlb_loudness_record>((size_t)G.n);
+    }
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(t->mem);
+    t->groups.swap(gs);
+    memcpy(t->h_loud, h_loud, sizeof h_loud);
+    t->loudness = true;
+    return TLB_OK;
+}
+const tlb_loudness_record *tlb_tick_loudness(const tlb_tick *t) { return t && t->loudness ? t->h_loud[t->out_set] : nullptr; }
+// Programme loudness of every stream from the counts so far, and EBU mode's reset (stream -1: all): legal with no tick in flight.
+int tlb_tick_loudness_programme(tlb_tick *t, tlb_loudness_programme_record *out)
+{
+    if (!t || !out || !t->loudness || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    for (auto &G : t->groups) if (int rc = tlb_loudness_programme_host(G.b, out + G.first)) return rc;
+    return TLB_OK;
+}
+int tlb_tick_loudness_reset(tlb_tick *t, int stream)
+{
+    if (!t || !t->loudness || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (stream >= 0) { int k; const TickGroup *G = tick_group_of(t, stream, &k); return tlb_loudness_reset(G->b, k); }
+    for (auto &G : t->groups) if (int rc = tlb_loudness_reset(G.b, -1)) return rc;
+    return TLB_OK;
+}
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)
 {
     if (!t || t->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
@@ -609,6 +657,10 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
         if (int rc = compare_launch(G.b, new_input ? G.d_pcm : nullptr, G.d_mpcm, have_frames ? G.d_report : nullptr, 1, &t->cparams, G.d_crecord, t->s_run)) return rc;
         HIPCHK(hipEventRecord(G.ev_mon, t->s_run));
     }
+    if (t->loudness && new_input) {                                  // the PCM that went IN this tick (the flush has none: its set shows the same records)
+        if (int rc = tlb_loudness_device(G.b, G.d_pcm, 1, G.d_loud, t->s_run)) return rc;
+        HIPCHK(hipEventRecord(G.ev_loud, t->s_run));
+    }
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -643,6 +695,10 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
         const int k = t->listen_of[set] - G.first;
         if (G.d_mpcm && k >= 0 && k < G.n)
             HIPCHK(hipMemcpyAsync(t->h_listen[set], G.d_mpcm + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME, 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost, t->s_out));
+    }
+    if (t->loudness) {                                               // ... and the loudness records, on an event of their own
+        if (new_input) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_loud, 0));
+        HIPCHK(hipMemcpyAsync(t->h_loud[set] + G.first, G.d_loud, n * sizeof(tlb_loudness_record), hipMemcpyDeviceToHost, t->s_out));
     }
     HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed (the monitor's reads of d_frames included)
     return TLB_OK;

@@ -284,6 +284,27 @@ def _bind(L):
         L.tlb_tick_need.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_node_need.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_loudness_device"):         # loudness meter
+        L.tlb_loudness_enable.argtypes = [C.c_void_p]
+        L.tlb_loudness_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_loudness_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_loudness_programme_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_loudness_programme_host.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_loudness_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_loudness_taps.argtypes = [C.c_long, C.c_void_p]
+        L.tlb_loudness_scale.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_loudness_lufs.restype = C.c_double
+        L.tlb_loudness_lufs.argtypes = [C.c_double]
+        L.tlb_tick_enable_loudness.argtypes = [C.c_void_p]
+        L.tlb_tick_loudness.restype = C.c_void_p
+        L.tlb_tick_loudness.argtypes = [C.c_void_p]
+        L.tlb_tick_loudness_programme.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_tick_loudness_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_enable_loudness.argtypes = [C.c_void_p]
+        L.tlb_node_loudness.restype = C.c_void_p
+        L.tlb_node_loudness.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_loudness_programme.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_node_loudness_reset.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "tlb_decimate_device"):         # device decimator (down sources)
         L.tlb_decimate_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_decimate_source.restype = C.c_long
@@ -402,6 +423,36 @@ def decimate_taps(source_rate, encoder_rate):
     if not p:
         return None
     return np.ctypeslib.as_array((C.c_int16 * (l.value * tt.value)).from_address(p)).reshape(l.value, tt.value).copy(), l.value, m.value
+
+
+# tlb_loudness_record / tlb_loudness_programme_record: energies, LUFS = loudness_lufs(E)
+LOUDNESS_DTYPE = np.dtype([("frames", np.uint32), ("bins", np.uint32), ("blocks", np.uint32), ("gated", np.uint32),
+                           ("momentary", np.float64), ("short_term", np.float64), ("momentary_max", np.float64), ("short_term_max", np.float64)])
+LOUDNESS_PROGRAMME_DTYPE = np.dtype([("integrated", np.float64), ("gate", np.float64), ("gated", np.uint32), ("reserved", np.uint32)])
+LOUDNESS_BINS = 751
+
+
+def loudness_lufs(energy):
+    """-0.691 + 10 log10(energy); -inf for 0 (tlb_loudness_lufs)"""
+    return float(load_library().tlb_loudness_lufs(float(energy)))
+
+
+def loudness_taps(samplerate):
+    """the committed K-weighting row of an encoder rate -> float64 [10]: b0 b1 b2 a1 a2 of the shelf, then of the high-pass; no GPU"""
+    out = np.zeros(10, dtype=np.float64)
+    rc = load_library().tlb_loudness_taps(int(samplerate), out.ctypes.data)
+    if rc:
+        raise ToolameError(rc, "tlb_loudness_taps")
+    return out
+
+
+def loudness_scale():
+    """the committed gating scale -> (edges float64 [751], centres float64 [751]); no GPU"""
+    edges, centres = np.zeros(LOUDNESS_BINS, dtype=np.float64), np.zeros(LOUDNESS_BINS, dtype=np.float64)
+    rc = load_library().tlb_loudness_scale(edges.ctypes.data, centres.ctypes.data)
+    if rc:
+        raise ToolameError(rc, "tlb_loudness_scale")
+    return edges, centres
 
 
 def feed_check_config(cfg):
@@ -711,6 +762,33 @@ class Tick:
         if not p:
             return None
         return np.frombuffer((C.c_uint8 * (self.nstreams * MONITOR_DTYPE.itemsize)).from_address(p), dtype=MONITOR_DTYPE)
+
+    # -- loudness meter (tlb_loudness_device on the tick's planar PCM): before the first submit --
+    def enable_loudness(self):
+        rc = self.L.tlb_tick_enable_loudness(self.h)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_loudness")
+
+    @property
+    def loudness(self):
+        """LOUDNESS_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when not enabled"""
+        p = self.L.tlb_tick_loudness(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * LOUDNESS_DTYPE.itemsize)).from_address(p), dtype=LOUDNESS_DTYPE)
+
+    def loudness_programme(self):
+        """LOUDNESS_PROGRAMME_DTYPE [nstreams] from the counts so far; with no tick in flight"""
+        out = np.zeros(self.nstreams, dtype=LOUDNESS_PROGRAMME_DTYPE)
+        rc = self.L.tlb_tick_loudness_programme(self.h, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_loudness_programme")
+        return out
+
+    def loudness_reset(self, s=-1):
+        rc = self.L.tlb_tick_loudness_reset(self.h, int(s))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_loudness_reset")
 
     # -- compare monitor (tlb_compare_device behind the decode): after enable_monitor("audio"), before the first submit --
     def enable_compare(self, params=None):
@@ -1253,6 +1331,39 @@ class Batch:
             raise ToolameError(rc, "tlb_decimate_host")
         return out
 
+    # -- loudness meter (tlb_loudness_*): momentary, short-term and gated programme loudness of the PCM the encoder is given --
+    def enable_loudness(self):
+        """allocates the meter's state on the device (about 3.4 KB per stream); a second call does nothing"""
+        rc = self.L.tlb_loudness_enable(self.h)
+        if rc:
+            raise ToolameError(rc, "tlb_loudness_enable")
+
+    def loudness(self, pcm_planar):
+        """int16 [nframes, nstreams, 2, 1152] planar PCM as ingest() returns it -> LOUDNESS_DTYPE [nstreams] after these frames"""
+        a = np.ascontiguousarray(pcm_planar, dtype=np.int16)
+        nf = a.shape[0]
+        if a.shape != (nf, self.nstreams, 2, SAMPLES):
+            raise ToolameError(18, f"pcm shape {a.shape}")
+        out = np.zeros(self.nstreams, dtype=LOUDNESS_DTYPE)
+        rc = self.L.tlb_loudness_host(self.h, a.ctypes.data, nf, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_loudness_host")
+        return out
+
+    def loudness_programme(self):
+        """LOUDNESS_PROGRAMME_DTYPE [nstreams]: gated programme loudness of everything measured since the streams' resets"""
+        out = np.zeros(self.nstreams, dtype=LOUDNESS_PROGRAMME_DTYPE)
+        rc = self.L.tlb_loudness_programme_host(self.h, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_loudness_programme_host")
+        return out
+
+    def loudness_reset(self, s=-1):
+        """EBU mode's reset of one stream, or of every stream (-1)"""
+        rc = self.L.tlb_loudness_reset(self.h, s)
+        if rc:
+            raise ToolameError(rc, "tlb_loudness_reset")
+
     def ingest(self, interleaved, valid=None):
         """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2]).
         valid: int32 [nframes, nstreams] sample frames each slot delivers -- a short read is stretched over the frame as the reference
@@ -1695,6 +1806,26 @@ class Node:
         if not p:
             return None
         return np.frombuffer((C.c_uint8 * MONITOR_DTYPE.itemsize).from_address(p), dtype=MONITOR_DTYPE)[0].copy()
+
+    # loudness meter (Tick.enable_loudness, per stream with node-wide indices)
+    def enable_loudness(self):
+        self._rc(self.L.tlb_node_enable_loudness(self.h), "tlb_node_enable_loudness")
+
+    def loudness(self, s):
+        """the stream's record (a LOUDNESS_DTYPE scalar, copied) of the step waited for last; None when not enabled and for a broken, late or stale shard"""
+        p = self.L.tlb_node_loudness(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * LOUDNESS_DTYPE.itemsize).from_address(p), dtype=LOUDNESS_DTYPE)[0].copy()
+
+    def loudness_programme(self):
+        """LOUDNESS_PROGRAMME_DTYPE [nstreams], between steps; all zero for the streams of a broken or late shard"""
+        out = np.zeros(self.nstreams, dtype=LOUDNESS_PROGRAMME_DTYPE)
+        self._rc(self.L.tlb_node_loudness_programme(self.h, out.ctypes.data), "tlb_node_loudness_programme")
+        return out
+
+    def loudness_reset(self, s=-1):
+        self._rc(self.L.tlb_node_loudness_reset(self.h, int(s)), "tlb_node_loudness_reset")
 
     # compare monitor (Tick.enable_compare, per stream with node-wide indices)
     def enable_compare(self, params=None):
