@@ -13,7 +13,8 @@
 //     per-lane "registers" are [64] arrays, so the CPU test-suite executes exactly the device
 //     algorithm (same arithmetic, same order) and compares it with the oracle.
 // The block below is where the two part: whatever has a device form and an emulation form (a cross-lane exchange, a builtin, an asm
-// idiom) is a named primitive with both halves HERE, and the stage headers use it without asking which build they are in.  Loop pragmas
+// idiom) is a named primitive with both halves HERE, and the stage headers use it without asking which build they are in.  Each primitive's
+// two halves are run side by side, and against an oracle written from its comment, by the probe (csrc/mp2_probe.h, tests/test_probe_*.py).  Loop pragmas
 // (#pragma unroll / nounroll) are written bare: emulation builds pass -Wno-unknown-pragmas and g++ ignores them.
 //
 // Exactness rules: fp64 everywhere, no FMA contraction (-ffp-contract=off),
@@ -51,8 +52,10 @@ TL_FN int tlh_argmin_u64(const uint64_t (&v)[64])
     for (int i = 1; i < 64; i += 2) if (v[i] == m) return i;
     return -1;
 }
+// (no NaN among the values: no caller makes one.  Of tied maxima the LAST is kept, as the device's ladder keeps it -- the lane's own value over
+// the one shifted in: a row of -0.0 then +0.0 gives +0.0 in both halves, tests/test_probe_emu.py / test_probe_gpu.py)
 TL_FN void tlh_row16_max_f64(double (&d)[64], const double (&v)[64])
-{ for (int r = 0; r < 4; r++) { double m = v[16 * r]; for (int i = 1; i < 16; i++) if (m < v[16 * r + i]) m = v[16 * r + i]; for (int i = 0; i < 16; i++) d[16 * r + i] = m; } }
+{ for (int r = 0; r < 4; r++) { double m = v[16 * r]; for (int i = 1; i < 16; i++) if (!(v[16 * r + i] < m)) m = v[16 * r + i]; for (int i = 0; i < 16; i++) d[16 * r + i] = m; } }
 #define TL_ROW16_MAX_F64(dst, src) tlh_row16_max_f64(dst, src)      /* valid in lane 15 of each row of 16 (all lanes here) */
 TL_FN void tlh_incl_xscan_u32(uint32_t (&d)[64], const uint32_t (&v)[64]) { uint32_t x = 0; for (int i = 0; i < 64; i++) { x ^= v[i]; d[i] = x; } }
 #define TL_WAVE_INCL_XSCAN_U32(dst, src) tlh_incl_xscan_u32(dst, src)

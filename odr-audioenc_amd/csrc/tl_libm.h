@@ -23,7 +23,10 @@
 // them out of the same libm.so.6, bit patterns, nothing retyped).
 //
 // Proof: tools/libm_agree.c runs every function here against the host's libm on >= 1e8 arguments each
-// (profiles/libm_agree_r03.txt: 0 differing results), tests/test_libm_agree.py on a smaller sample in the CPU suite.
+// (profiles/libm_agree_r03.txt: 0 differing results), tests/test_libm_agree.py on a smaller sample in the CPU suite.  That is the HOST half of
+// this header; the branches under __HIP_DEVICE_COMPILE__ (hardware seeds, inline v_fma_f64 / v_min_f64 / v_max_f64, __device__ tables) run in
+// the probe (csrc/mp2_probe.h): every device-path form on a gfx950, 2^20 arguments each, bit-equal to the host half and to the host's libm
+// (tests/test_probe_gpu.py; the seeds' measured error: profiles/probe_seeds.txt).
 // Domain notes are at each function; outside them the functions still return what glibc returns unless stated.
 #pragma once
 #include <stdint.h>
@@ -91,7 +94,9 @@ __device__ inline __attribute__((always_inline)) double tlm_fma_k_(double a, dou
 #else
 #define TLM_FMA_K(a, b, bits) TLM_FMA((a), (b), TLM_D(bits))
 #endif
-// TLM_MIN_NN(a, b): the smaller of two numbers, NEITHER a NaN (the caller's precondition): `b < a ? b : a` in one v_min_f64.  Through
+// TLM_MIN_NN(a, b): the smaller of two numbers, NEITHER a NaN and not zeros of OPPOSITE sign (the caller's precondition; the instruction orders
+// -0.0 below +0.0, the host expression keeps its first operand -- both pinned by tests/test_probe_emu.py / test_probe_gpu.py; the callers pass
+// magnitudes and an energy against 0.0005): `b < a ? b : a` in one v_min_f64.  Through
 // fmin() the compiler first canonicalises every operand that comes from memory (a v_max_f64 x, x each: the instruction quiets signalling
 // NaNs and the language's fmin must not) -- twice the instructions for a case that cannot occur here.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -588,9 +593,15 @@ TLM_HD double tlm_atan2(double y, double x) { return tlm_atan2_t(y, x, tlm_atan_
 // operands -- for every operand the scaled forms would leave unscaled they execute the same arithmetic, hence return the same bits,
 // i.e. the correctly rounded result (the final fused step sees the exact residual) -- and a reciprocal refined once serves every
 // quotient by the same divisor (e_atan2.c divides twice by max(|x|, |y|)).
-// Domain: divisor and square-root argument normal and in [2^-500, 2^500], dividend zero or in [2^-900, 2^500]; sqrt(+0) = +0 is a select.
+// Domain: divisor and square-root argument normal and in [2^-500, 2^500], dividend +0 or of magnitude in [2^-900, 2^500] (either sign: the second
+// quotient's dividend is a residual; a dividend of -0.0 would come out as +0 -- the residual of a zero quotient is n + 0 -- and no caller has one);
+// sqrt(+-0) = +-0 is a select.
 // The seed is v_rcp_f64 / v_rsq_f64 on the device; on the host (emulation, tools) the exact 1/d, 1/sqrt(x) rounded -- the refinement
 // converges to the same result from any seed good to ~2^-20 (tools/libm_agree.cpp perturbs the seed to show it, 1e8 operands each).
+// Measured on a gfx950 (profiles/probe_seeds.txt, tests/test_probe_gpu.py asserts it): v_rcp_f64 is good to 2^-24.4, v_rsq_f64 to 2^-24.2, the
+// reciprocal refined from the seed to 2^-53.  The quotient's final fused correction squares whatever error the reciprocal still has, so n / d
+// comes out correctly rounded from a reciprocal of ONE Newton step too (2^-48.7) on every operand tried: the second step is margin down to the
+// stated 2^-20, and only the check on the refined reciprocal itself (2^-52) sees it go missing.
 TLM_HD double tlm_rcp_seed(double d)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -27,6 +27,14 @@ int tlb_debug_node_stall_next(tlb_node *nd, int shard, int nth, int ms, int rc);
  * to the runtime (1 = the next; 0 disarms): the creation, first-use and opt-in paths then fail as they would when memory runs out.  The
  * counter is atomic (node shards allocate on their own threads).  Nothing is launched and the device is not touched. */
 int tlb_debug_alloc_fail_next(int nth);
+/* The probe (csrc/mp2_probe.h, csrc/toolame_probe.hip): ONE form of csrc/tl_libm.h's device half (form: TLP_LOG_PN ...; table: 0 = the global
+ * table, 1 = its LDS copy, log family only) over n arguments a[i] (and b[i] where the form takes two; else b may be NULL), results to r0[i] (and
+ * r1[i] where it returns two; else r1 may be NULL) -- resp. ONE cross-lane primitive of csrc/mp2_wave.h (prim: TLP_WAVE_MIN_U64 ...) over nwaves
+ * cases of 64 64-bit words (layout at the enum).  HOST pointers: device buffers through the library's memory owner, one launch on the current
+ * device, waited for, copied out.  TLB_ERR_ARG for an unknown form / primitive, n <= 0, a missing pointer and for ANY argument outside the
+ * form's stated domain (tlp_in_domain): checked on the host before anything is queued, so nothing out of domain reaches the device. */
+int tlb_debug_probe_libm(int form, int table, long n, const double *a, const double *b, double *r0, double *r1);
+int tlb_debug_probe_wave(int prim, int nwaves, const void *in, const void *in2, void *out);
 #ifdef __cplusplus
 }
 #endif
