@@ -7,7 +7,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
 //   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
 //   header's padding bit, service s takes frame (tick + s) of it (wrapping round), one tick per frame of the file.  No PCM crosses the
@@ -32,8 +32,12 @@
 //   --loudness: the loudness meter (tlb_tick_enable_loudness): the PCM the encoder is given (after -g) is measured on the device after
 //   ITU-R BS.1770-4 / EBU R 128.  One line per stream at the end: momentary (400 ms), short-term (3 s) and integrated loudness in LUFS
 //   (-inf where there is none yet), as "%.2f".
+//   --truepeak [DBTP]: the true-peak meter (tlb_tick_enable_truepeak): the same PCM oversampled four times on the device after ITU-R
+//   BS.1770-4 Annex 2, against a ceiling of DBTP (default -1, EBU R 128's).  One line per stream at the end: the maximum true peak in
+//   dBTP, the largest sample in dBFS and the number of frames over the ceiling.
 // out.af: for every packet a little-endian uint32 length, then the packet.
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -52,12 +56,13 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0;
+    double ceiling_db = -1.0;
     char mode = 0;
     double gain_db = 0.0;
     const char *feed_path = nullptr;
@@ -67,6 +72,13 @@ int main(int argc, char **argv)
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
         if (k == "--loudness") { loudness = 1; i--; continue; }
+        if (k == "--truepeak") {                                 // its value is optional: taken when the next argument is a number
+            truepeak = 1;
+            char *end = nullptr;
+            const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) ceiling_db = v; else i--;
+            continue;
+        }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") rate = std::atol(v);
@@ -136,6 +148,8 @@ int main(int argc, char **argv)
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
     if (loudness) if (int rc = tlb_tick_enable_loudness(t)) die("tlb_tick_enable_loudness", rc);                 // likewise
+    const uint32_t ceiling = (uint32_t)std::llround(1073741824.0 * std::pow(10.0, ceiling_db / 20.0));             // in units of 2^-30 of full scale
+    if (truepeak) if (int rc = tlb_tick_enable_truepeak(t, ceiling)) die("tlb_tick_enable_truepeak", rc);        // likewise
     const bool down = source_rate > rate;                    // a source above the encoder's rate goes through the decimator and its wide slots
     if (source_rate && !down) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
     if (down) if (int rc = tlb_tick_set_down_source(t, -1, source_rate)) die("tlb_tick_set_down_source", rc);             // likewise
@@ -252,6 +266,15 @@ int main(int argc, char **argv)
         for (int s = 0; s < nstreams; s++)
             std::fprintf(stderr, "editick: loudness: stream %d: momentary %.2f LUFS, short-term %.2f LUFS, integrated %.2f LUFS (%u of %u blocks)\n", s,
                          tlb_loudness_lufs(r[s].momentary), tlb_loudness_lufs(r[s].short_term), tlb_loudness_lufs(prog[(size_t)s].integrated), prog[(size_t)s].gated, r[s].blocks);
+    }
+    if (truepeak && frames > 0) {                                // the records of the last tick (the finish adds nothing)
+        const tlb_truepeak_record *r = tlb_tick_truepeak(t);
+        for (int s = 0; s < nstreams; s++) {
+            const uint32_t pk = r[s].peak_max[0] > r[s].peak_max[1] ? r[s].peak_max[0] : r[s].peak_max[1];
+            const uint32_t sm = r[s].sample_max[0] > r[s].sample_max[1] ? r[s].sample_max[0] : r[s].sample_max[1];
+            std::fprintf(stderr, "editick: truepeak: stream %d: max %.2f dBTP, samples %.2f dBFS, %u of %u frames over %.2f dBTP\n", s,
+                         tlb_truepeak_dbtp(pk), tlb_truepeak_dbtp(sm << 15), r[s].overs, r[s].frames, tlb_truepeak_dbtp(ceiling));
+        }
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",

@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R]
+//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R]
 //   in.s16le: interleaved stereo at the services' rate (-r: 48000, the default, or 24000); stream s starts reading at frame s (so the
 //   services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
@@ -36,10 +36,14 @@
 //   the service's wide slot (tlb_node_down) and are filtered and decimated on the GPUs.
 //   --loudness: the loudness meter (tlb_node_enable_loudness): the PCM every encoder is given is measured on its GPU after ITU-R BS.1770-4 /
 //   EBU R 128.  One line per service at the end: momentary, short-term and integrated loudness in LUFS (-inf where there is none yet).
+//   --truepeak [DBTP]: the true-peak meter (tlb_node_enable_truepeak): the same PCM oversampled four times on its GPU after ITU-R BS.1770-4
+//   Annex 2, against a ceiling of DBTP (default -1, EBU R 128's).  One line per service at the end: the maximum true peak in dBTP, the
+//   largest sample in dBFS and the number of frames over the ceiling.
 //   --compare: the compare monitor on top of it (tlb_node_enable_compare with the header's default params; implies --monitor audio): every
 //   frame that leaves is decoded on its GPU and set against the audio that went in.  A service whose mismatch_run reaches 3 is printed when
 //   it does; one summary line at the end -- frames compared, judged, mismatched -- and exit status 4 when any service got there.
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -150,10 +154,11 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0;
+    double ceiling_db = -1.0;
     long rate = 48000;
     double deadline_ms = 0;
     long source_rate = 0;
@@ -164,6 +169,13 @@ int main(int argc, char **argv)
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
         if (k == "--loudness") { loudness = 1; i--; continue; }
+        if (k == "--truepeak") {                                 // its value is optional: taken when the next argument is a number
+            truepeak = 1;
+            char *end = nullptr;
+            const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) ceiling_db = v; else i--;
+            continue;
+        }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-n") nstreams = std::atoi(v);
@@ -259,6 +271,9 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
     if (loudness)
         if (int rc = tlb_node_enable_loudness(nd)) die("tlb_node_enable_loudness", rc);                 // likewise; a restarted shard measures again from zero
+    const uint32_t ceiling = (uint32_t)std::llround(1073741824.0 * std::pow(10.0, ceiling_db / 20.0));    // in units of 2^-30 of full scale
+    if (truepeak)
+        if (int rc = tlb_node_enable_truepeak(nd, ceiling)) die("tlb_node_enable_truepeak", rc);        // likewise, with the same ceiling
     if (monitor)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
     const bool down = source_rate > rate;
@@ -396,6 +411,14 @@ int main(int argc, char **argv)
                 std::fprintf(stderr, "nodetick: loudness: service %d: momentary %.2f LUFS, short-term %.2f LUFS, integrated %.2f LUFS (%u of %u blocks)\n", s,
                              tlb_loudness_lufs(r->momentary), tlb_loudness_lufs(r->short_term), tlb_loudness_lufs(prog[(size_t)s].integrated), prog[(size_t)s].gated, r->blocks);
     }
+    if (truepeak)                                                         // the records of the last step
+        for (int s = 0; s < nstreams; s++)
+            if (const tlb_truepeak_record *r = tlb_node_truepeak(nd, s)) {    // (NULL: its shard is down or late)
+                const uint32_t pk = r->peak_max[0] > r->peak_max[1] ? r->peak_max[0] : r->peak_max[1];
+                const uint32_t sm = r->sample_max[0] > r->sample_max[1] ? r->sample_max[0] : r->sample_max[1];
+                std::fprintf(stderr, "nodetick: truepeak: service %d: max %.2f dBTP, samples %.2f dBFS, %u of %u frames over %.2f dBTP\n", s,
+                             tlb_truepeak_dbtp(pk), tlb_truepeak_dbtp(sm << 15), r->overs, r->frames, tlb_truepeak_dbtp(ceiling));
+            }
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",
                 nstreams, G, ticks, tot.frames, npk, nby, sec, sec > 0 ? tot.frames / sec : 0.0, sec > 0 ? ticks * 0.024 / sec : 0.0);

@@ -1195,7 +1195,7 @@ const tlb_frame_report *tlb_node_down_feed_report(const tlb_node *nd, int stream
  * record and answers NULL for a broken, late or stale shard; tlb_node_loudness_programme(nd, out [nstreams]) fills the blocks of the live
  * shards between steps (all zero for the others); tlb_node_loudness_reset routes like the stream life-cycle calls (TLB_ERR_HIP for a stream
  * of a broken shard, TLB_ERR_LATE for one of a late shard), -1 goes to every live shard.
- * NOT BUILT: true peak (oversampled), loudness range (LRA), acting on the gain, loudness of the decoded output (the monitors own that side).
+ * NOT BUILT: loudness range (LRA), acting on the gain, loudness of the decoded output (the monitors own that side).
  * ------------------------------------------------------------------------------------------ */
 #define TLB_LOUDNESS_BINS 751
 typedef struct { uint32_t frames, bins, blocks, gated;
@@ -1218,6 +1218,73 @@ int tlb_node_enable_loudness(tlb_node *nd);
 const tlb_loudness_record *tlb_node_loudness(const tlb_node *nd, int stream);
 int tlb_node_loudness_programme(tlb_node *nd, tlb_loudness_programme_record *out);
 int tlb_node_loudness_reset(tlb_node *nd, int stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Maximum true peak: the largest value the signal reaches BETWEEN its samples, after ITU-R BS.1770-4 Annex 2, of the PCM the encoder is
+ * given -- the ingest's planar output, AFTER the stream's gain, what the loudness meter reads too.  EBU R 128 holds a head-end to a maximum
+ * true peak of -1 dBTP beside its -23 LUFS; the sample peaks of the ingest under-read it by up to 3 dB (a sine at fs / 4 sampled 45 degrees
+ * off its crests shows -3 dBFS at 0 dBTP), and a Layer II decoder at the listener's end reconstructs exactly those peaks.  Opt-in; the
+ * meter lives on the device.
+ * THE ARITHMETIC.  The reference has no true-peak meter, so this is the definition, in integers (tests/truepeaklib.py restates it in numpy
+ * int64, every comparison against it is byte for byte on the records).  4x oversampling by a polyphase FIR, then the absolute maximum; 4x at
+ * every encoder rate, since an n-times meter's under-read depends on the signal's frequency relative to the sample rate and not on the rate.
+ *   table       int16 H[3][TLB_TRUEPEAK_TAPS], committed as csrc/tl_truepeak_taps.inc: the phases 1/4, 2/4, 3/4 between two samples of a
+ *               fourth-band prototype (a Kaiser-windowed sinc, beta = 8, 12 taps per phase as BS.1770-4's own filter has; the committed
+ *               table is the definition, tools/gen_truepeak_taps.py the record of how it was made).  Every row sums to exactly 32768, row 3
+ *               is row 1 reversed, row 2 is symmetric.  Phase 0 of such a prototype is the sample itself and is not stored:
+ *               v_0(n) = 32768 x[n], so true peak >= sample peak by construction and no tap of 32768 has to fit an int16
+ *   per channel x[n] are the stream's planar samples since its last reset, zeros before it.  For p = 1, 2, 3
+ *               v_p(n) = sum_{t = 0 .. 11} H[p][t] x[n - t], the exact integer sum: max_p sum_t |H[p][t]| = 57 760 and 57 760 * 32768 <
+ *               2^31, so a WHOLE ROW is summed in 32 bits, in any order, and no half sums in 64 bits are needed
+ *   frame       peak = max over the frame's 1152 n of max(32768 |x[n]|, |v_1(n)|, |v_2(n)|, |v_3(n)|): an unsigned 32-bit number in units
+ *               of 2^-30 of full scale.  An interpolated value belongs to the frame in which its NEWEST sample x[n] arrives (the point it
+ *               stands for lies between x[n - 6] and x[n - 5]); the last 11 samples of a channel are carried from frame to frame and
+ *               from call to call
+ *   dBTP        tlb_truepeak_dbtp(v) = 20 log10(v / 2^30), -inf for 0
+ * RECORD.  tlb_truepeak_record, 32 bytes: frames = PCM frames measured; overs = frames in which either channel's peak is STRICTLY above the
+ * ceiling; peak[2] = the last measured frame's peak per channel; peak_max[2] = the maximum since the reset; sample_max[2] = the largest
+ * |x| since the reset, 0 .. 32768.  A one-channel stream leaves index 1 zero, and its second PCM row is not looked at; dual channel counts
+ * as two channels.
+ * CEILING.  Given at enable time in the same 2^-30 units; 0 selects TLB_TRUEPEAK_CEILING_DEFAULT = llround(2^30 * 10^(-1/20)), -1 dBTP.
+ * STATE.  80 bytes of device memory per stream (the record and 2 x 12 carried samples, of which the oldest is never used), allocated by
+ * tlb_truepeak_enable ALONE: a batch that never enables it allocates and queues nothing new, and the other calls answer TLB_ERR_ARG on it.
+ *   tlb_truepeak_enable(b, ceiling)   allocates the state (waits for the device once); a second call answers 0 and leaves the ceiling
+ *   tlb_truepeak_device(b, d_pcm_planar, nframes, d_records, stream)
+ *                                     measures nframes of every stream, int16 [nframes][nstreams][2][1152] as tlb_ingest_device writes it
+ *                                     (16-byte aligned), and writes tlb_truepeak_record [nstreams] (may be NULL) on hip_stream
+ *   tlb_truepeak_host                 the same with host buffers
+ *   tlb_truepeak_reset(b, stream)     -1: every stream.  Waits for the queued work, then zeroes the record and the carried samples
+ *   tlb_truepeak_taps(out[3][12])     the committed table; no GPU
+ *   tlb_truepeak_dbtp(v)              no GPU
+ * tlb_stream_reset, tlb_stream_reconfigure and tlb_reset clear the stream's true-peak state; tlb_stream_finish leaves it.
+ * TICK PLANE.  tlb_tick_enable_truepeak(t, ceiling) before the first submit (TLB_ERR_ARG after it; a second call answers 0) enables the
+ * meter of every group's batch.  Every submit with new input then queues the meter on the tick's planar PCM on the run stream, behind the
+ * tick's encode and egress kernels and behind the loudness meter when both are on; the 32-byte records travel with the three output sets
+ * behind the packets, on an event of their own: the packets' copy-out does not wait for them.  tlb_tick_truepeak(t) is tlb_truepeak_record
+ * [nstreams] of the tick waited for last (pinned, valid until the next wait); NULL when the meter is off.  After T waited ticks
+ * frames == T, and tlb_tick_finish adds nothing.  tlb_tick_truepeak_reset(t, stream) (-1: all) is legal with no tick in flight (TLB_ERR_ARG
+ * otherwise, and when the meter is off).
+ * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_truepeak goes to every shard before the first submit, and a
+ * shard made by tlb_node_shard_restart is enabled again with the same ceiling -- its records start from zero.  tlb_node_truepeak(nd, stream)
+ * points at the STREAM's record and answers NULL for a broken, late or stale shard; tlb_node_truepeak_reset routes like
+ * tlb_node_loudness_reset.
+ * NOT BUILT: loudness range (LRA), acting on the gain (a limiter), true peak of the decoded output.
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_TRUEPEAK_TAPS 12
+#define TLB_TRUEPEAK_CEILING_DEFAULT 956973408u
+typedef struct { uint32_t frames, overs, peak[2], peak_max[2], sample_max[2]; } tlb_truepeak_record;      /* 32 bytes */
+int tlb_truepeak_enable(tlb_batch *b, uint32_t ceiling);
+int tlb_truepeak_device(tlb_batch *b, const int16_t *d_pcm_planar, int nframes, tlb_truepeak_record *d_records, void *hip_stream);
+int tlb_truepeak_host(tlb_batch *b, const int16_t *pcm_planar, int nframes, tlb_truepeak_record *records);
+int tlb_truepeak_reset(tlb_batch *b, int stream);
+int tlb_truepeak_taps(int16_t out[3][TLB_TRUEPEAK_TAPS]);
+double tlb_truepeak_dbtp(uint32_t v);
+int tlb_tick_enable_truepeak(tlb_tick *t, uint32_t ceiling);
+const tlb_truepeak_record *tlb_tick_truepeak(const tlb_tick *t);
+int tlb_tick_truepeak_reset(tlb_tick *t, int stream);
+int tlb_node_enable_truepeak(tlb_node *nd, uint32_t ceiling);
+const tlb_truepeak_record *tlb_node_truepeak(const tlb_node *nd, int stream);
+int tlb_node_truepeak_reset(tlb_node *nd, int stream);
 
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);

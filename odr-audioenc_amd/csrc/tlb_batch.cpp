@@ -198,6 +198,7 @@ int tlb_reset(tlb_batch *b)
     if (int rc = batch_build_lists(b)) return rc;
     if (int rc = batch_clear_streams(b, 0, b->nstreams)) return rc;
     if (int rc = loudness_clear_streams(b, 0, b->nstreams)) return rc;
+    if (int rc = truepeak_clear_streams(b, 0, b->nstreams)) return rc;
     b->frames = 0; b->psy2_flip = 0; b->work_clean = false; b->broken = false;
     return TLB_OK;
 }
@@ -212,6 +213,7 @@ int tlb_stream_reset(tlb_batch *b, int stream)
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = loudness_clear_streams(b, stream, 1)) return rc;    // (tlb_stream_finish leaves the loudness state: the programme goes on)
+    if (int rc = truepeak_clear_streams(b, stream, 1)) return rc;    // (likewise: the maximum goes on)
     return batch_clear_streams(b, stream, 1);
 }
 
@@ -286,6 +288,7 @@ int tlb_stream_reconfigure(tlb_batch *b, int stream, const tlb_stream_config *cf
     if (int rc = feed_after_reconfigure(b, stream)) return rc;       // a feed at another rate or channel count than the stream's new ones is removed
     if (int rc = feed_down_after_reconfigure(b, stream)) return rc;  // ... and a down feed whose rate no longer pairs with the stream's new one
     if (int rc = loudness_clear_streams(b, stream, 1)) return rc;    // ... and the loudness meter starts over: coefficients and bin length follow the rate
+    if (int rc = truepeak_clear_streams(b, stream, 1)) return rc;    // ... and the true-peak meter: the channel count may have changed
     return batch_clear_streams(b, stream, 1);
 }
 

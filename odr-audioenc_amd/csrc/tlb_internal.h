@@ -209,6 +209,11 @@ struct tlb_batch {
     uint32_t *d_ld_hist = nullptr;               // [TL_LD_HIST_ROWS][nstreams] gating blocks per 0.1 LU
     TlLoudnessProgramme *d_ld_prog = nullptr;    // [nstreams] scratch of tlb_loudness_programme_host
     double *d_ld_tables = nullptr;               // the committed table: taps [6][10], edges [751], centres [751]
+    // true-peak meter (tlb_truepeak.cpp; csrc/mp2_truepeak.h), allocated by tlb_truepeak_enable alone: a batch that never enables it has none of it
+    TlTruePeakRecord *d_tp_rec = nullptr;        // [nstreams] the record as it is reported
+    uint32_t *d_tp_hist = nullptr;               // [nstreams][2][TL_TP_CARRY / 2] the carried samples of either channel
+    int16_t *d_tp_taps = nullptr;                // the committed table [3][TL_TP_TAPS]
+    uint32_t tp_ceiling = 0;                     // in units of 2^-30 of full scale
     TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -272,6 +277,8 @@ int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len
 
 // tlb_loudness.cpp: the loudness state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); nothing when loudness was never enabled
 int loudness_clear_streams(tlb_batch *b, int s0, int n);
+// tlb_truepeak.cpp: likewise for the true-peak meter
+int truepeak_clear_streams(tlb_batch *b, int s0, int n);
 
 // the encoder's rate of stream s
 static inline long batch_enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }

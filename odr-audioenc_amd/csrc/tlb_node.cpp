@@ -163,6 +163,8 @@ struct tlb_node {
     bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
     tlb_compare_params cparams = {};
     bool loudness = false;                       // tlb_node_enable_loudness(): every shard's tick object measures loudness (a restarted shard's too, from zero)
+    bool truepeak = false;                       // tlb_node_enable_truepeak(): every shard's tick object measures true peak against tp_ceiling (a restarted shard's too, from zero)
+    uint32_t tp_ceiling = 0;
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
     // The per-stream input families (csrc/tlb_inputs.h; node_families below): what tlb_node_set_source, _set_down_source, _set_feed and
     // _set_down_feed gave every stream, set again on a restarted shard.  A source is its rate alone; samplerate 0: the stream has none;
@@ -370,6 +372,7 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (nd->monitor) if (int rc = tlb_tick_enable_monitor(s.tick, nd->monitor)) return rc;
         if (nd->compare) if (int rc = tlb_tick_enable_compare(s.tick, &nd->cparams)) return rc;
         if (nd->loudness) if (int rc = tlb_tick_enable_loudness(s.tick)) return rc;
+        if (nd->truepeak) if (int rc = tlb_tick_enable_truepeak(s.tick, nd->tp_ceiling)) return rc;
         int k;
         if (nd->monitor && nd->of(nd->listen, &k) == &s) if (int rc = tlb_tick_monitor_listen(s.tick, k)) return rc;
     } else {
@@ -682,6 +685,25 @@ int tlb_node_loudness_reset(tlb_node *nd, int stream)
     int k; Shard *s;
     if (int rc = nd->gate(stream, &s, &k)) return rc;
     return nd->one(s->index, [&](Shard &sh) { return tlb_tick_loudness_reset(sh.tick, k); });
+}
+// The true-peak meter (tlb_tick_enable_truepeak of every shard, on the shards' threads): before the first submit, TICK plane only.
+int tlb_node_enable_truepeak(tlb_node *nd, uint32_t ceiling)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
+    if (nd->truepeak) return TLB_OK;
+    const int rc = nd->all([ceiling](Shard &s) { return s.tick ? tlb_tick_enable_truepeak(s.tick, ceiling) : (int)TLB_ERR_HIP; });
+    if (!rc) { nd->truepeak = true; nd->tp_ceiling = ceiling; }
+    return rc;
+}
+const tlb_truepeak_record *tlb_node_truepeak(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_truepeak>(nd, stream); }
+// The reset of one stream (to its shard, through the gate of the life-cycle calls) or of all (-1: every live shard), between steps.
+int tlb_node_truepeak_reset(tlb_node *nd, int stream)
+{
+    if (!nd || !nd->truepeak || stream < -1 || stream >= nd->nstreams || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    if (stream < 0) return nd->live("truepeak_reset", [](Shard &s) { return tlb_tick_truepeak_reset(s.tick, -1); });
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return rc;
+    return nd->one(s->index, [&](Shard &sh) { return tlb_tick_truepeak_reset(sh.tick, k); });
 }
 // One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'
 // tick objects that their next submit reads; no shard but a late one runs a job between the node's calls, and a late one is left alone

@@ -80,6 +80,8 @@ struct TickGroup {
     bool any_down = false, all_down = false;                    // some / every stream of the group has a down source (all: the group's PCM is not copied in)
     tlb_loudness_record *d_loud = nullptr;                      // loudness meter (tlb_tick_enable_loudness): the group's records of this tick
     hipEvent_t ev_loud = nullptr;                               // ... written: the records' copy-out waits for it, the packets' does not
+    tlb_truepeak_record *d_tpeak = nullptr;                     // true-peak meter (tlb_tick_enable_truepeak): the group's records of this tick
+    hipEvent_t ev_tpeak = nullptr;                              // ... written: likewise
     hipEvent_t ev_mon = nullptr;                                // decode + fold (+ compare) done: the records' copy-out waits for it, the packets' does not
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
@@ -118,6 +120,9 @@ struct tlb_tick {
     // loudness meter, off until tlb_tick_enable_loudness(): the records travel with the output sets
     bool loudness = false;
     tlb_loudness_record *h_loud[3] = {};
+    // true-peak meter, off until tlb_tick_enable_truepeak(): likewise
+    bool truepeak = false;
+    tlb_truepeak_record *h_tpeak[3] = {};
 #ifdef TLB_FAULT_INJECT
     int damage_nth = 0, damage_stream = 0, damage_byte = 0; uint8_t damage_xor = 0, damage_val = 0;      // tlb_debug_tick_damage_next
     int cross_nth = 0, cross_a = -1, cross_b = -1; bool cross_on = false; uint8_t *d_cross_tmp = nullptr;   // tlb_debug_tick_cross_from
@@ -161,6 +166,7 @@ void tlb_tick_destroy(tlb_tick *t)
         if (g.ev_out) (void)hipEventDestroy(g.ev_out);
         if (g.ev_mon) (void)hipEventDestroy(g.ev_mon);
         if (g.ev_loud) (void)hipEventDestroy(g.ev_loud);
+        if (g.ev_tpeak) (void)hipEventDestroy(g.ev_tpeak);
     }
     if (t->s_in) (void)hipStreamDestroy(t->s_in);
     if (t->s_run) (void)hipStreamDestroy(t->s_run);
@@ -405,6 +411,39 @@ int tlb_tick_loudness_reset(tlb_tick *t, int stream)
     if (t->broken) return TLB_ERR_HIP;
     if (stream >= 0) { int k; const TickGroup *G = tick_group_of(t, stream, &k); return tlb_loudness_reset(G->b, k); }
     for (auto &G : t->groups) if (int rc = tlb_loudness_reset(G.b, -1)) return rc;
+    return TLB_OK;
+}
+// The true-peak meter (tlb_truepeak_*) likewise: the state of every group's batch is made here with the one ceiling, and every submit with
+// new input then queues the meter on d_pcm behind the egress kernels -- and behind the loudness meter when both are on.
+int tlb_tick_enable_truepeak(tlb_tick *t, uint32_t ceiling)
+{
+    if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (t->truepeak) return TLB_OK;
+    HIPCHK(hipSetDevice(t->device));
+    for (auto &G : t->groups) if (!G.ev_tpeak) HIPCHK(hipEventCreateWithFlags(&G.ev_tpeak, hipEventDisableTiming));  // (a refused attempt keeps them for the next)
+    TlbMem m;
+    std::vector<TickGroup> gs = t->groups;
+    tlb_truepeak_record *h_tpeak[3];
+    for (int k = 0; k < 3; k++) h_tpeak[k] = m.pinned<tlb_truepeak_record>((size_t)t->nstreams);
+    for (auto &G : gs) {
+        if (int rc = tlb_truepeak_enable(G.b, ceiling)) return rc;
+        G.d_tpeak = m.dev<tlb_truepeak_record>((size_t)G.n);
+    }
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(t->mem);
+    t->groups.swap(gs);
+    memcpy(t->h_tpeak, h_tpeak, sizeof h_tpeak);
+    t->truepeak = true;
+    return TLB_OK;
+}
+const tlb_truepeak_record *tlb_tick_truepeak(const tlb_tick *t) { return t && t->truepeak ? t->h_tpeak[t->out_set] : nullptr; }
+int tlb_tick_truepeak_reset(tlb_tick *t, int stream)
+{
+    if (!t || !t->truepeak || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (stream >= 0) { int k; const TickGroup *G = tick_group_of(t, stream, &k); return tlb_truepeak_reset(G->b, k); }
+    for (auto &G : t->groups) if (int rc = tlb_truepeak_reset(G.b, -1)) return rc;
     return TLB_OK;
 }
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)
@@ -661,6 +700,10 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
         if (int rc = tlb_loudness_device(G.b, G.d_pcm, 1, G.d_loud, t->s_run)) return rc;
         HIPCHK(hipEventRecord(G.ev_loud, t->s_run));
     }
+    if (t->truepeak && new_input) {                                  // likewise, behind the loudness meter on the same PCM
+        if (int rc = tlb_truepeak_device(G.b, G.d_pcm, 1, G.d_tpeak, t->s_run)) return rc;
+        HIPCHK(hipEventRecord(G.ev_tpeak, t->s_run));
+    }
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
     HIPCHK(hipMemcpyAsync(t->h_silence[set] + G.first, G.d_silence, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -699,6 +742,10 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
     if (t->loudness) {                                               // ... and the loudness records, on an event of their own
         if (new_input) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_loud, 0));
         HIPCHK(hipMemcpyAsync(t->h_loud[set] + G.first, G.d_loud, n * sizeof(tlb_loudness_record), hipMemcpyDeviceToHost, t->s_out));
+    }
+    if (t->truepeak) {                                               // ... and the true-peak records, on theirs
+        if (new_input) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_tpeak, 0));
+        HIPCHK(hipMemcpyAsync(t->h_tpeak[set] + G.first, G.d_tpeak, n * sizeof(tlb_truepeak_record), hipMemcpyDeviceToHost, t->s_out));
     }
     HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed (the monitor's reads of d_frames included)
     return TLB_OK;

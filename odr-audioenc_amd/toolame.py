@@ -305,6 +305,22 @@ def _bind(L):
         L.tlb_node_loudness.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_loudness_programme.argtypes = [C.c_void_p, C.c_void_p]
         L.tlb_node_loudness_reset.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_truepeak_device"):         # true-peak meter
+        L.tlb_truepeak_enable.argtypes = [C.c_void_p, C.c_uint32]
+        L.tlb_truepeak_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_truepeak_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_truepeak_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_truepeak_taps.argtypes = [C.c_void_p]
+        L.tlb_truepeak_dbtp.restype = C.c_double
+        L.tlb_truepeak_dbtp.argtypes = [C.c_uint32]
+        L.tlb_tick_enable_truepeak.argtypes = [C.c_void_p, C.c_uint32]
+        L.tlb_tick_truepeak.restype = C.c_void_p
+        L.tlb_tick_truepeak.argtypes = [C.c_void_p]
+        L.tlb_tick_truepeak_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_enable_truepeak.argtypes = [C.c_void_p, C.c_uint32]
+        L.tlb_node_truepeak.restype = C.c_void_p
+        L.tlb_node_truepeak.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_truepeak_reset.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "tlb_decimate_device"):         # device decimator (down sources)
         L.tlb_decimate_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_decimate_source.restype = C.c_long
@@ -453,6 +469,26 @@ def loudness_scale():
     if rc:
         raise ToolameError(rc, "tlb_loudness_scale")
     return edges, centres
+
+
+# tlb_truepeak_record: peaks in units of 2^-30 of full scale, dBTP = truepeak_dbtp(v); sample_max 0 .. 32768
+TRUEPEAK_DTYPE = np.dtype([("frames", np.uint32), ("overs", np.uint32), ("peak", np.uint32, (2,)), ("peak_max", np.uint32, (2,)), ("sample_max", np.uint32, (2,))])
+TRUEPEAK_TAPS = 12
+TRUEPEAK_CEILING_DEFAULT = 956973408                                 # -1 dBTP: llround(2^30 * 10^(-1/20)), TLB_TRUEPEAK_CEILING_DEFAULT
+
+
+def truepeak_dbtp(v):
+    """20 log10(v / 2^30); -inf for 0 (tlb_truepeak_dbtp)"""
+    return float(load_library().tlb_truepeak_dbtp(int(v)))
+
+
+def truepeak_taps():
+    """the committed interpolation table -> int16 [3][12]: the phases 1/4, 2/4, 3/4; no GPU"""
+    out = np.zeros((3, TRUEPEAK_TAPS), dtype=np.int16)
+    rc = load_library().tlb_truepeak_taps(out.ctypes.data)
+    if rc:
+        raise ToolameError(rc, "tlb_truepeak_taps")
+    return out
 
 
 def feed_check_config(cfg):
@@ -789,6 +825,26 @@ class Tick:
         rc = self.L.tlb_tick_loudness_reset(self.h, int(s))
         if rc:
             raise ToolameError(rc, "tlb_tick_loudness_reset")
+
+    # -- true-peak meter (tlb_truepeak_device on the tick's planar PCM): before the first submit --
+    def enable_truepeak(self, ceiling=0):
+        """ceiling in units of 2^-30 of full scale; 0: TRUEPEAK_CEILING_DEFAULT (-1 dBTP)"""
+        rc = self.L.tlb_tick_enable_truepeak(self.h, int(ceiling))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_truepeak")
+
+    @property
+    def truepeak(self):
+        """TRUEPEAK_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when not enabled"""
+        p = self.L.tlb_tick_truepeak(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * TRUEPEAK_DTYPE.itemsize)).from_address(p), dtype=TRUEPEAK_DTYPE)
+
+    def truepeak_reset(self, s=-1):
+        rc = self.L.tlb_tick_truepeak_reset(self.h, int(s))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_truepeak_reset")
 
     # -- compare monitor (tlb_compare_device behind the decode): after enable_monitor("audio"), before the first submit --
     def enable_compare(self, params=None):
@@ -1364,6 +1420,32 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_loudness_reset")
 
+    # -- true-peak meter (tlb_truepeak_*): the 4x oversampled maximum of the PCM the encoder is given --
+    def enable_truepeak(self, ceiling=0):
+        """allocates the meter's state on the device (80 bytes per stream); ceiling in units of 2^-30 of full scale, 0: -1 dBTP; a second
+        call does nothing and leaves the ceiling"""
+        rc = self.L.tlb_truepeak_enable(self.h, int(ceiling))
+        if rc:
+            raise ToolameError(rc, "tlb_truepeak_enable")
+
+    def truepeak(self, pcm_planar):
+        """int16 [nframes, nstreams, 2, 1152] planar PCM as ingest() returns it -> TRUEPEAK_DTYPE [nstreams] after these frames"""
+        a = np.ascontiguousarray(pcm_planar, dtype=np.int16)
+        nf = a.shape[0]
+        if a.shape != (nf, self.nstreams, 2, SAMPLES):
+            raise ToolameError(18, f"pcm shape {a.shape}")
+        out = np.zeros(self.nstreams, dtype=TRUEPEAK_DTYPE)
+        rc = self.L.tlb_truepeak_host(self.h, a.ctypes.data, nf, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_truepeak_host")
+        return out
+
+    def truepeak_reset(self, s=-1):
+        """one stream's record and carried samples back to zero, or every stream's (-1)"""
+        rc = self.L.tlb_truepeak_reset(self.h, s)
+        if rc:
+            raise ToolameError(rc, "tlb_truepeak_reset")
+
     def ingest(self, interleaved, valid=None):
         """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2]).
         valid: int32 [nframes, nstreams] sample frames each slot delivers -- a short read is stretched over the frame as the reference
@@ -1826,6 +1908,20 @@ class Node:
 
     def loudness_reset(self, s=-1):
         self._rc(self.L.tlb_node_loudness_reset(self.h, int(s)), "tlb_node_loudness_reset")
+
+    # true-peak meter (Tick.enable_truepeak, per stream with node-wide indices)
+    def enable_truepeak(self, ceiling=0):
+        self._rc(self.L.tlb_node_enable_truepeak(self.h, int(ceiling)), "tlb_node_enable_truepeak")
+
+    def truepeak(self, s):
+        """the stream's record (a TRUEPEAK_DTYPE scalar, copied) of the step waited for last; None when not enabled and for a broken, late or stale shard"""
+        p = self.L.tlb_node_truepeak(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * TRUEPEAK_DTYPE.itemsize).from_address(p), dtype=TRUEPEAK_DTYPE)[0].copy()
+
+    def truepeak_reset(self, s=-1):
+        self._rc(self.L.tlb_node_truepeak_reset(self.h, int(s)), "tlb_node_truepeak_reset")
 
     # compare monitor (Tick.enable_compare, per stream with node-wide indices)
     def enable_compare(self, params=None):

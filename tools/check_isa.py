@@ -55,6 +55,8 @@ LIMITS = [
     # loudness meter (csrc/toolame_loudness.hip): a lane per (stream, channel) with the filter state and a chunk of PCM ahead in registers; 64 rows of 144 bytes in LDS
     (re.compile(r"tl_loudness_kernel"), dict(vgpr=168, lds=9216, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     (re.compile(r"tl_loudness_programme_kernel"), dict(vgpr=168, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # true-peak meter (csrc/toolame_truepeak.hip): a wave per stream, a window of 15 + 14 dwords and three pieces ahead in registers; two rows of 2336 bytes in LDS
+    (re.compile(r"tl_truepeak_kernel"), dict(vgpr=128, lds=4672, vgpr_spill=0, sgpr_spill=0, scratch=0)),
 ]
 
 
