@@ -184,6 +184,15 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
     return decimate_clear_streams(b, s0, n);                         // ... and so does the decimator
 }
 
+// ... and the PCM meters' state of them, where a meter is enabled.  It is apart from batch_clear_streams: tlb_stream_finish leaves it, so
+// that a programme's loudness and its maximum true peak go on.  A reset starts both over; so does a reconfiguration, after which the
+// loudness meter's coefficients and bin length follow the new rate and the true-peak meter's carried samples the new channel count.
+static int meters_clear_streams(tlb_batch *b, int s0, int n)
+{
+    if (int rc = loudness_clear_streams(b, s0, n)) return rc;
+    return truepeak_clear_streams(b, s0, n);
+}
+
 int tlb_reset(tlb_batch *b)
 {
     if (!b) return TLB_ERR_ARG;
@@ -197,8 +206,7 @@ int tlb_reset(tlb_batch *b)
     HIPCHK(hipMemcpy(b->d_stream_cfg, b->h_stream_cfg.data(), sizeof(int32_t) * (size_t)b->nstreams, hipMemcpyHostToDevice));
     if (int rc = batch_build_lists(b)) return rc;
     if (int rc = batch_clear_streams(b, 0, b->nstreams)) return rc;
-    if (int rc = loudness_clear_streams(b, 0, b->nstreams)) return rc;
-    if (int rc = truepeak_clear_streams(b, 0, b->nstreams)) return rc;
+    if (int rc = meters_clear_streams(b, 0, b->nstreams)) return rc;
     b->frames = 0; b->psy2_flip = 0; b->work_clean = false; b->broken = false;
     return TLB_OK;
 }
@@ -212,8 +220,7 @@ int tlb_stream_reset(tlb_batch *b, int stream)
     if (!b || stream < 0 || stream >= b->nstreams) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
-    if (int rc = loudness_clear_streams(b, stream, 1)) return rc;    // (tlb_stream_finish leaves the loudness state: the programme goes on)
-    if (int rc = truepeak_clear_streams(b, stream, 1)) return rc;    // (likewise: the maximum goes on)
+    if (int rc = meters_clear_streams(b, stream, 1)) return rc;      // (tlb_stream_finish leaves the meters: the programme and the maximum go on)
     return batch_clear_streams(b, stream, 1);
 }
 
@@ -287,8 +294,7 @@ int tlb_stream_reconfigure(tlb_batch *b, int stream, const tlb_stream_config *cf
     }
     if (int rc = feed_after_reconfigure(b, stream)) return rc;       // a feed at another rate or channel count than the stream's new ones is removed
     if (int rc = feed_down_after_reconfigure(b, stream)) return rc;  // ... and a down feed whose rate no longer pairs with the stream's new one
-    if (int rc = loudness_clear_streams(b, stream, 1)) return rc;    // ... and the loudness meter starts over: coefficients and bin length follow the rate
-    if (int rc = truepeak_clear_streams(b, stream, 1)) return rc;    // ... and the true-peak meter: the channel count may have changed
+    if (int rc = meters_clear_streams(b, stream, 1)) return rc;      // ... and the meters start over (the rate and the channel count may have changed)
     return batch_clear_streams(b, stream, 1);
 }
 

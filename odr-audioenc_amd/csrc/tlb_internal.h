@@ -275,10 +275,36 @@ int feed_down_after_reconfigure(tlb_batch *b, int stream);
 int feed_down_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
 int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
 
-// tlb_loudness.cpp: the loudness state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle); nothing when loudness was never enabled
+// The PCM meters (tlb_loudness.cpp, tlb_truepeak.cpp).  A meter's state of streams [s0, s0 + n) back to zero (the device is idle); nothing
+// when the meter was never enabled
 int loudness_clear_streams(tlb_batch *b, int s0, int n);
-// tlb_truepeak.cpp: likewise for the true-peak meter
 int truepeak_clear_streams(tlb_batch *b, int s0, int n);
+// ... the one body of tlb_*_host: `state`, what the meter's enable made (NULL: never enabled); scratch PCM and records, one launch of the
+// meter's *_device, the records back
+template <class Rec> int meter_host(tlb_batch *b, const void *state, const int16_t *pcm_planar, int nframes, Rec *records,
+                                    int (*device)(tlb_batch *, const int16_t *, int, Rec *, void *))
+{
+    if (!b || !pcm_planar || !records || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30) || !state) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t vals = (size_t)nframes * (size_t)b->nstreams * 2 * TLB_SAMPLES_PER_FRAME;
+    TlbMem m;
+    int16_t *d_pcm = m.scratch<int16_t>(vals);
+    Rec *d_rec = m.scratch<Rec>((size_t)b->nstreams);
+    MEMCHK(m);
+    HIPCHK(hipMemcpy(d_pcm, pcm_planar, vals * sizeof(int16_t), hipMemcpyHostToDevice));
+    if (int rc = device(b, d_pcm, nframes, d_rec, nullptr)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(records, d_rec, (size_t)b->nstreams * sizeof(Rec), hipMemcpyDeviceToHost));
+    return TLB_OK;
+}
+// ... and of tlb_*_reset: one stream's state, or every stream's (-1), through the meter's clear
+static inline int meter_reset(tlb_batch *b, const void *state, int stream, int (*clear)(tlb_batch *, int, int))
+{
+    if (!b || stream < -1 || stream >= b->nstreams || !state) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());
+    return stream < 0 ? clear(b, 0, b->nstreams) : clear(b, stream, 1);
+}
 
 // the encoder's rate of stream s
 static inline long batch_enc_rate(const tlb_batch *b, int s) { return b->h_uniq[(size_t)b->h_stream_cfg[(size_t)s]].samplerate; }

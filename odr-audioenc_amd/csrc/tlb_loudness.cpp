@@ -83,18 +83,7 @@ int tlb_loudness_device(tlb_batch *b, const int16_t *d_pcm_planar, int nframes, 
 
 int tlb_loudness_host(tlb_batch *b, const int16_t *pcm_planar, int nframes, tlb_loudness_record *records)
 {
-    if (!b || !pcm_planar || !records || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30) || !b->d_ld_lane) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t vals = (size_t)nframes * (size_t)b->nstreams * 2 * TLB_SAMPLES_PER_FRAME;
-    TlbMem m;
-    int16_t *d_pcm = m.scratch<int16_t>(vals);
-    tlb_loudness_record *d_rec = m.scratch<tlb_loudness_record>((size_t)b->nstreams);
-    MEMCHK(m);
-    HIPCHK(hipMemcpy(d_pcm, pcm_planar, vals * sizeof(int16_t), hipMemcpyHostToDevice));
-    if (int rc = tlb_loudness_device(b, d_pcm, nframes, d_rec, nullptr)) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(records, d_rec, (size_t)b->nstreams * sizeof(tlb_loudness_record), hipMemcpyDeviceToHost));
-    return TLB_OK;
+    return meter_host(b, b ? b->d_ld_lane : nullptr, pcm_planar, nframes, records, tlb_loudness_device);
 }
 
 int tlb_loudness_programme_device(tlb_batch *b, tlb_loudness_programme_record *d_out, void *hip_stream)
@@ -116,12 +105,6 @@ int tlb_loudness_programme_host(tlb_batch *b, tlb_loudness_programme_record *out
     return TLB_OK;
 }
 
-int tlb_loudness_reset(tlb_batch *b, int stream)
-{
-    if (!b || stream < -1 || stream >= b->nstreams || !b->d_ld_lane) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipDeviceSynchronize());
-    return stream < 0 ? loudness_clear_streams(b, 0, b->nstreams) : loudness_clear_streams(b, stream, 1);
-}
+int tlb_loudness_reset(tlb_batch *b, int stream) { return meter_reset(b, b ? b->d_ld_lane : nullptr, stream, loudness_clear_streams); }
 
 }  // extern "C"

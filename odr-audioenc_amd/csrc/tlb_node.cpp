@@ -144,6 +144,8 @@ int tick_wait_job(Shard &s)
 
 }  // namespace
 
+enum { OPT_SHORT_READS, OPT_MONITOR, OPT_COMPARE, OPT_LOUDNESS, OPT_TRUEPEAK, OPTS };     // in the order a restarted shard gets them back
+
 struct tlb_node {
     int plane = TLB_NODE_TICK, nstreams = 0;
     tlb_node_config cfg;                         // as given at creation (the version string copied into `version`)
@@ -158,13 +160,11 @@ struct tlb_node {
     double wall_ns = 0;
     long submitted = 0, waited = 0;              // node steps: submits / waits so far (a step's index is its submit's)
     double deadline_ms = 0;                      // TICK DEADLINE; 0 = none
-    bool short_reads = false;                    // tlb_node_enable_short_reads(): every shard's tick object carries `valid` and the underrun counters (a restarted shard's too)
-    int monitor = 0;                             // tlb_node_enable_monitor(): TLB_MONITOR_* of every shard's tick object (a restarted shard's too)
-    bool compare = false;                        // tlb_node_enable_compare(): every shard's tick object compares with cparams (a restarted shard's too)
-    tlb_compare_params cparams = {};
-    bool loudness = false;                       // tlb_node_enable_loudness(): every shard's tick object measures loudness (a restarted shard's too, from zero)
-    bool truepeak = false;                       // tlb_node_enable_truepeak(): every shard's tick object measures true peak against tp_ceiling (a restarted shard's too, from zero)
-    uint32_t tp_ceiling = 0;
+    // The options of the shards' tick objects (node_options below): on, and what its enable call was given -- each option reads its own
+    // member.  A restarted shard's object gets them again (the meters start from zero there).
+    struct Option { bool on = false; int what = 0; tlb_compare_params cparams = {}; uint32_t ceiling = 0; };
+    Option opt[OPTS];
+    int monitor() const { return opt[OPT_MONITOR].what; }            // TLB_MONITOR_* of every shard's tick object; 0: off
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
     // The per-stream input families (csrc/tlb_inputs.h; node_families below): what tlb_node_set_source, _set_down_source, _set_feed and
     // _set_down_feed gave every stream, set again on a restarted shard.  A source is its rate alone; samplerate 0: the stream has none;
@@ -175,7 +175,7 @@ struct tlb_node {
     // On the BATCH plane the node holds nothing back and the mask is empty: the shards' batches answer stream by stream (batch_inputs).
     unsigned inputs() const
     {
-        unsigned m = short_reads ? TLB_IN_BIT(TLB_IN_SHORT_READS) : 0u;
+        unsigned m = opt[OPT_SHORT_READS].on ? TLB_IN_BIT(TLB_IN_SHORT_READS) : 0u;
         for (int f = 0; f < TLB_IN_SHORT_READS && plane == TLB_NODE_TICK; f++)
             for (const Input &v : kept[f]) if (v.samplerate) { m |= TLB_IN_BIT(f); break; }
         return m;
@@ -357,6 +357,40 @@ NodeInput node_feed(const tlb_feed_config *cfg, bool adapted)
     return v;
 }
 
+// The options of a shard's tick object, beside the families: how a remembered one reaches the object (the node's enable calls, and
+// shard_make for a restarted shard, in this order), and for a PCM meter its reset
+using NodeOption = tlb_node::Option;
+const struct { int (*enable)(tlb_tick *t, const NodeOption &v); int (*reset)(tlb_tick *t, int stream); const char *reset_name; } node_options[OPTS] = {
+    /* short reads */ {[](tlb_tick *t, const NodeOption &) { return tlb_tick_enable_short_reads(t); }, nullptr, nullptr},
+    /* monitor     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_monitor(t, v.what); }, nullptr, nullptr},
+    /* compare     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_compare(t, &v.cparams); }, nullptr, nullptr},
+    /* loudness    */ {[](tlb_tick *t, const NodeOption &) { return tlb_tick_enable_loudness(t); }, tlb_tick_loudness_reset, "loudness_reset"},
+    /* true peak   */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_truepeak(t, v.ceiling); }, tlb_tick_truepeak_reset, "truepeak_reset"},
+};
+// The one body of tlb_node_enable_*: TICK plane only, before the first submit, and `ok`, the option's own precondition.  An option that is
+// on answers TLB_OK to a call that is the `same` as the one that turned it on, TLB_ERR_ARG to another.  Else every shard's tick object is
+// given v, on the shards' threads, and the node remembers v.
+const auto always = [](const auto &) { return true; };
+template <class Ok, class Same> int node_enable(tlb_node *nd, int o, NodeOption v, Ok ok, Same same)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0 || !ok(*nd)) return TLB_ERR_ARG;
+    if (nd->opt[o].on) return same(nd->opt[o]) ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    const int rc = nd->all([&](Shard &s) { return s.tick ? node_options[o].enable(s.tick, v) : (int)TLB_ERR_HIP; });
+    v.on = true;
+    if (!rc) nd->opt[o] = v;
+    return rc;
+}
+// ... and of a meter's reset of one stream (to its shard, through the gate of the life-cycle calls) or of all (-1: every live shard), between steps
+int node_meter_reset(tlb_node *nd, int o, int stream)
+{
+    if (!nd || !nd->opt[o].on || stream < -1 || stream >= nd->nstreams || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    const auto reset = node_options[o].reset;
+    if (stream < 0) return nd->live(node_options[o].reset_name, [reset](Shard &s) { return reset(s.tick, -1); });
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return rc;
+    return nd->one(s->index, [&](Shard &sh) { return reset(sh.tick, k); });
+}
+
 // the objects of one shard, made on the shard's own thread (creation and restart)
 int shard_make(tlb_node *nd, Shard &s, long long now_s)
 {
@@ -368,13 +402,9 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         if (now_s >= 0) tc.now_s = now_s;
         s.tick = tlb_tick_create(s.device, s.n, nd->cfgs.data() + s.first, &tc, &e);
         if (!s.tick) return e ? e : TLB_ERR_HIP;
-        if (nd->short_reads) if (int rc = tlb_tick_enable_short_reads(s.tick)) return rc;
-        if (nd->monitor) if (int rc = tlb_tick_enable_monitor(s.tick, nd->monitor)) return rc;
-        if (nd->compare) if (int rc = tlb_tick_enable_compare(s.tick, &nd->cparams)) return rc;
-        if (nd->loudness) if (int rc = tlb_tick_enable_loudness(s.tick)) return rc;
-        if (nd->truepeak) if (int rc = tlb_tick_enable_truepeak(s.tick, nd->tp_ceiling)) return rc;
+        for (int o = 0; o < OPTS; o++) if (nd->opt[o].on) if (int rc = node_options[o].enable(s.tick, nd->opt[o])) return rc;
         int k;
-        if (nd->monitor && nd->of(nd->listen, &k) == &s) if (int rc = tlb_tick_monitor_listen(s.tick, k)) return rc;
+        if (nd->monitor() && nd->of(nd->listen, &k) == &s) if (int rc = tlb_tick_monitor_listen(s.tick, k)) return rc;
     } else {
         s.batch = tlb_create(s.device, s.n, nd->cfgs.data() + s.first, &e);
         if (!s.batch) return e ? e : TLB_ERR_HIP;
@@ -627,90 +657,51 @@ int tlb_node_shard_deadline_status(const tlb_node *nd, int shard, tlb_node_shard
 int16_t *tlb_node_pcm(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_pcm>(nd, stream, 2 * TLB_SAMPLES_PER_FRAME); }
 uint8_t *tlb_node_xpad(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_xpad>(nd, stream, TLB_MAX_XPAD); }
 int32_t *tlb_node_xpad_len(tlb_node *nd, int stream) { return slot<INPUT, tlb_tick_xpad_len>(nd, stream); }
-// Short reads (tlb_tick_enable_short_reads of every shard, on the shards' threads): before the first submit, TICK plane only.
+// The options (node_enable: tlb_tick_enable_* of every shard, on the shards' threads, before the first submit, TICK plane only).  Short
+// reads are an input family too (csrc/tlb_inputs.h).
 int tlb_node_enable_short_reads(tlb_node *nd)
 {
-    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
-    if (!tlb_input_may_set(TLB_INPUTS_OBJECT, TLB_IN_SHORT_READS, nd->inputs())) return TLB_ERR_ARG;
-    if (nd->short_reads) return TLB_OK;
-    const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_short_reads(s.tick) : (int)TLB_ERR_HIP; });
-    if (!rc) nd->short_reads = true;
-    return rc;
+    return node_enable(nd, OPT_SHORT_READS, NodeOption{}, [](const tlb_node &n) { return tlb_input_may_set(TLB_INPUTS_OBJECT, TLB_IN_SHORT_READS, n.inputs()); }, always);
 }
-// The confidence monitor (tlb_tick_enable_monitor of every shard, on the shards' threads): before the first submit, TICK plane only.
 int tlb_node_enable_monitor(tlb_node *nd, int what)
 {
-    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0 || (what != TLB_MONITOR_CHECK && what != TLB_MONITOR_AUDIO)) return TLB_ERR_ARG;
-    if (nd->monitor) return nd->monitor == what ? (int)TLB_OK : (int)TLB_ERR_ARG;
-    const int rc = nd->all([what](Shard &s) { return s.tick ? tlb_tick_enable_monitor(s.tick, what) : (int)TLB_ERR_HIP; });
-    if (!rc) nd->monitor = what;
-    return rc;
+    NodeOption v; v.what = what;
+    return node_enable(nd, OPT_MONITOR, v, [what](const tlb_node &) { return what == TLB_MONITOR_CHECK || what == TLB_MONITOR_AUDIO; },
+                       [what](const NodeOption &was) { return was.what == what; });
 }
 const tlb_monitor_record *tlb_node_monitor(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_monitor>(nd, stream); }
-// The compare monitor (tlb_tick_enable_compare of every shard): after tlb_node_enable_monitor(TLB_MONITOR_AUDIO), before the first submit.
+// The compare monitor: after tlb_node_enable_monitor(TLB_MONITOR_AUDIO).
 int tlb_node_enable_compare(tlb_node *nd, const tlb_compare_params *params)
 {
-    if (!nd || !params || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0 || nd->monitor != TLB_MONITOR_AUDIO) return TLB_ERR_ARG;
-    if (!tlb_compare_params_legal(params)) return TLB_ERR_ARG;
-    if (nd->compare) return tlb_compare_params_same(*params, nd->cparams) ? (int)TLB_OK : (int)TLB_ERR_ARG;
-    const tlb_compare_params P = *params;
-    const int rc = nd->all([P](Shard &s) { return s.tick ? tlb_tick_enable_compare(s.tick, &P) : (int)TLB_ERR_HIP; });
-    if (!rc) { nd->cparams = P; nd->compare = true; }
-    return rc;
+    NodeOption v; if (params) v.cparams = *params;
+    return node_enable(nd, OPT_COMPARE, v, [params](const tlb_node &n) { return params && n.monitor() == TLB_MONITOR_AUDIO && tlb_compare_params_legal(params); },
+                       [params](const NodeOption &was) { return tlb_compare_params_same(*params, was.cparams); });
 }
 const tlb_compare_record *tlb_node_compare(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_compare>(nd, stream); }
-// The loudness meter (tlb_tick_enable_loudness of every shard, on the shards' threads): before the first submit, TICK plane only.
-int tlb_node_enable_loudness(tlb_node *nd)
-{
-    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
-    if (nd->loudness) return TLB_OK;
-    const int rc = nd->all([](Shard &s) { return s.tick ? tlb_tick_enable_loudness(s.tick) : (int)TLB_ERR_HIP; });
-    if (!rc) nd->loudness = true;
-    return rc;
-}
+int tlb_node_enable_loudness(tlb_node *nd) { return node_enable(nd, OPT_LOUDNESS, NodeOption{}, always, always); }
 const tlb_loudness_record *tlb_node_loudness(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_loudness>(nd, stream); }
+int tlb_node_loudness_reset(tlb_node *nd, int stream) { return node_meter_reset(nd, OPT_LOUDNESS, stream); }     // (EBU mode's reset)
 // Programme loudness of every stream, out [nstreams], between steps: each live shard fills its block on its own thread; the records of a
 // broken or late shard's streams are all zero.
 int tlb_node_loudness_programme(tlb_node *nd, tlb_loudness_programme_record *out)
 {
-    if (!nd || !out || !nd->loudness || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    if (!nd || !out || !nd->opt[OPT_LOUDNESS].on || !nd->t_submit.empty()) return TLB_ERR_ARG;
     memset(out, 0, sizeof(tlb_loudness_programme_record) * (size_t)nd->nstreams);
     return nd->live("loudness_programme", [out](Shard &s) { return tlb_tick_loudness_programme(s.tick, out + s.first); });
 }
-// EBU mode's reset of one stream (to its shard, through the gate of the life-cycle calls) or of all (-1: every live shard), between steps.
-int tlb_node_loudness_reset(tlb_node *nd, int stream)
-{
-    if (!nd || !nd->loudness || stream < -1 || stream >= nd->nstreams || !nd->t_submit.empty()) return TLB_ERR_ARG;
-    if (stream < 0) return nd->live("loudness_reset", [](Shard &s) { return tlb_tick_loudness_reset(s.tick, -1); });
-    int k; Shard *s;
-    if (int rc = nd->gate(stream, &s, &k)) return rc;
-    return nd->one(s->index, [&](Shard &sh) { return tlb_tick_loudness_reset(sh.tick, k); });
-}
-// The true-peak meter (tlb_tick_enable_truepeak of every shard, on the shards' threads): before the first submit, TICK plane only.
 int tlb_node_enable_truepeak(tlb_node *nd, uint32_t ceiling)
 {
-    if (!nd || nd->plane != TLB_NODE_TICK || nd->finished || nd->submitted > 0) return TLB_ERR_ARG;
-    if (nd->truepeak) return TLB_OK;
-    const int rc = nd->all([ceiling](Shard &s) { return s.tick ? tlb_tick_enable_truepeak(s.tick, ceiling) : (int)TLB_ERR_HIP; });
-    if (!rc) { nd->truepeak = true; nd->tp_ceiling = ceiling; }
-    return rc;
+    NodeOption v; v.ceiling = ceiling;
+    return node_enable(nd, OPT_TRUEPEAK, v, always, always);         // (a second call's ceiling is not looked at: the first one stays)
 }
 const tlb_truepeak_record *tlb_node_truepeak(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_truepeak>(nd, stream); }
-// The reset of one stream (to its shard, through the gate of the life-cycle calls) or of all (-1: every live shard), between steps.
-int tlb_node_truepeak_reset(tlb_node *nd, int stream)
-{
-    if (!nd || !nd->truepeak || stream < -1 || stream >= nd->nstreams || !nd->t_submit.empty()) return TLB_ERR_ARG;
-    if (stream < 0) return nd->live("truepeak_reset", [](Shard &s) { return tlb_tick_truepeak_reset(s.tick, -1); });
-    int k; Shard *s;
-    if (int rc = nd->gate(stream, &s, &k)) return rc;
-    return nd->one(s->index, [&](Shard &sh) { return tlb_tick_truepeak_reset(sh.tick, k); });
-}
+int tlb_node_truepeak_reset(tlb_node *nd, int stream) { return node_meter_reset(nd, OPT_TRUEPEAK, stream); }
 // One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'
 // tick objects that their next submit reads; no shard but a late one runs a job between the node's calls, and a late one is left alone
 // (it cannot be the stream's shard: TLB_ERR_LATE).
 int tlb_node_monitor_listen(tlb_node *nd, int stream)
 {
-    if (!nd || nd->plane != TLB_NODE_TICK || nd->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= nd->nstreams) return TLB_ERR_ARG;
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->monitor() != TLB_MONITOR_AUDIO || stream < -1 || stream >= nd->nstreams) return TLB_ERR_ARG;
     int k = 0; Shard *own = stream >= 0 ? nd->of(stream, &k) : nullptr;
     if (own) if (int rc = nd->usable(*own)) return rc;
     for (Shard *s : nd->shards)
@@ -721,7 +712,7 @@ int tlb_node_monitor_listen(tlb_node *nd, int stream)
 const int16_t *tlb_node_monitor_pcm(const tlb_node *nd, int *stream)
 {
     if (stream) *stream = -1;
-    if (!nd || nd->monitor != TLB_MONITOR_AUDIO) return nullptr;
+    if (!nd || nd->monitor() != TLB_MONITOR_AUDIO) return nullptr;
     for (const Shard *s : nd->shards) {
         if (!s->on() || s->stale || !s->tick) continue;
         int k = -1;

@@ -52,6 +52,39 @@ struct TickLane {
     std::unique_ptr<TlbMem> mem;                 // owns h_frames[] and the groups' d_frames
 };
 
+// A RECORD OPTION: an opt-in whose product is one fixed-size record per stream and tick that travels with the output sets.  What one has is
+// stated here once: the record's size and the option whose event its copy-out runs behind (its own, but the compare monitor's records are
+// written ahead of the monitor's event); per object its on flag and three pinned sets (TickRecords), per group the device array d_rec[] and
+// the event ev_rec[].  tick_record_enable stages the buffers and makes the events, tick_record_out is the copy-out, tick_record the accessor,
+// tlb_tick_destroy frees the events.  A PCM METER is a record option that also names its batch-level calls: enabled per batch with the
+// object's ceiling (the true-peak meter's; the others ignore it), run on the tick's planar PCM whenever there is new input, reset for one
+// stream or all between ticks.  tick_egress queues the meters in table order; the monitor's and the compare monitor's launches are its own.
+enum { REC_MONITOR, REC_COMPARE, REC_LOUDNESS, REC_TRUEPEAK, RECS };
+struct RecordOption {
+    size_t size;                                 // of one record
+    int ev;                                      // the option behind whose event (ev_rec[ev]) the copy-out runs
+    // a PCM meter's batch-level calls; NULL for the monitor and the compare monitor
+    int (*enable)(tlb_batch *b, uint32_t ceiling);
+    int (*launch)(tlb_batch *b, const int16_t *d_pcm_planar, int nframes, void *d_records, void *hip_stream);
+    int (*reset)(tlb_batch *b, int stream);
+};
+static const RecordOption tick_records[RECS] = {
+    {sizeof(tlb_monitor_record), REC_MONITOR, nullptr, nullptr, nullptr},
+    {sizeof(tlb_compare_record), REC_MONITOR, nullptr, nullptr, nullptr},
+    {sizeof(tlb_loudness_record), REC_LOUDNESS,
+     [](tlb_batch *b, uint32_t) { return tlb_loudness_enable(b); },
+     [](tlb_batch *b, const int16_t *d_pcm, int nframes, void *d_records, void *hip_stream) { return tlb_loudness_device(b, d_pcm, nframes, (tlb_loudness_record *)d_records, hip_stream); },
+     tlb_loudness_reset},
+    {sizeof(tlb_truepeak_record), REC_TRUEPEAK,
+     tlb_truepeak_enable,
+     [](tlb_batch *b, const int16_t *d_pcm, int nframes, void *d_records, void *hip_stream) { return tlb_truepeak_device(b, d_pcm, nframes, (tlb_truepeak_record *)d_records, hip_stream); },
+     tlb_truepeak_reset},
+};
+struct TickRecords {
+    bool on = false;
+    void *h[3] = {};
+};
+
 struct TickGroup {
     tlb_batch *b = nullptr;
     int first = 0, n = 0, out_stride = 0, max_upf = 1, af_stride = 0, max_frags = 0, frag_stride = 0;
@@ -71,18 +104,14 @@ struct TickGroup {
     uint8_t *h_frames[3] = {}; int32_t *h_flen[3] = {}; uint8_t *h_pkts[3] = {}; int32_t *h_plen[3] = {};
     uint8_t *h_frags[3] = {}; int32_t *h_fraglen[3] = {}, *h_nfrag[3] = {};
     uint8_t *h_msgs[3] = {};
-    // confidence monitor (tlb_tick_enable_monitor): the decode call's reports (and PCM under AUDIO) of this tick's frames, the folded records
-    tlb_frame_report *d_report = nullptr; int16_t *d_mpcm = nullptr; tlb_monitor_record *d_record = nullptr;
-    tlb_compare_record *d_crecord = nullptr;                    // compare monitor (tlb_tick_enable_compare): the group's records
+    // confidence monitor (tlb_tick_enable_monitor): the decode call's reports (and PCM under AUDIO) of this tick's frames
+    tlb_frame_report *d_report = nullptr; int16_t *d_mpcm = nullptr;
     TickLaneGroup lane[LANES];                                  // Layer II feeds and down feeds (tlb_tick_set_feed, tlb_tick_set_down_feed)
     // down sources (tlb_tick_set_down_source): the group's slice of the tick's wide slots; the decimator writes the streams' slots of d_inter
     int16_t *d_wide = nullptr;
     bool any_down = false, all_down = false;                    // some / every stream of the group has a down source (all: the group's PCM is not copied in)
-    tlb_loudness_record *d_loud = nullptr;                      // loudness meter (tlb_tick_enable_loudness): the group's records of this tick
-    hipEvent_t ev_loud = nullptr;                               // ... written: the records' copy-out waits for it, the packets' does not
-    tlb_truepeak_record *d_tpeak = nullptr;                     // true-peak meter (tlb_tick_enable_truepeak): the group's records of this tick
-    hipEvent_t ev_tpeak = nullptr;                              // ... written: likewise
-    hipEvent_t ev_mon = nullptr;                                // decode + fold (+ compare) done: the records' copy-out waits for it, the packets' does not
+    void *d_rec[RECS] = {};                                     // record options: the group's records of this tick
+    hipEvent_t ev_rec[RECS] = {};                               // ... written: the records' copy-out waits for it, the packets' does not (REC_MONITOR's: decode + fold (+ compare) done)
     hipEvent_t ev_in = nullptr, ev_run = nullptr;
     hipEvent_t ev_ingested = nullptr, ev_encoded = nullptr, ev_out = nullptr;   // the group's device buffers are single: the next tick's copy-in waits for this tick's
                                                                                 // ingest (d_inter) / encode (X-PAD), its kernels for this tick's copy-out
@@ -102,9 +131,10 @@ struct tlb_tick {
     // the two underrun counters with the output sets.  A set of h_valid is all 1152 whenever the caller can see it untouched.
     bool short_reads = false;
     int32_t *h_valid[2] = {}; uint32_t *h_underrun_ms[3] = {}, *h_underruns[3] = {};
-    // confidence monitor, off (0) until tlb_tick_enable_monitor(): the records and the listened stream's PCM travel with the output sets
+    TickRecords rec[RECS];                       // record options, each off until its enable
+    // confidence monitor, off (0) until tlb_tick_enable_monitor(): the listened stream's PCM travels with the output sets as the records do
     int monitor = 0;                             // TLB_MONITOR_CHECK / TLB_MONITOR_AUDIO
-    tlb_monitor_record *h_record[3] = {}; int16_t *h_listen[3] = {};
+    int16_t *h_listen[3] = {};
     int listen = -1;                             // the stream the NEXT submit carries (tlb_tick_monitor_listen); -1: none
     int listen_of[3] = {-1, -1, -1};             // ... the tick of each output set carried
     bool resample = false;                       // at least one stream has a source: every submit queues the resampler between copy-in and ingest
@@ -113,16 +143,7 @@ struct tlb_tick {
     bool down = false;                           // at least one stream has a down source
     int16_t *h_wide[2] = {};
     TickLane lane[LANES];                        // Layer II feeds and down feeds, each off until its first set
-    // compare monitor, off until tlb_tick_enable_compare(): needs the AUDIO monitor's decoded PCM; its records travel with the output sets too
-    bool compare = false;
-    tlb_compare_params cparams = {};
-    tlb_compare_record *h_crecord[3] = {};
-    // loudness meter, off until tlb_tick_enable_loudness(): the records travel with the output sets
-    bool loudness = false;
-    tlb_loudness_record *h_loud[3] = {};
-    // true-peak meter, off until tlb_tick_enable_truepeak(): likewise
-    bool truepeak = false;
-    tlb_truepeak_record *h_tpeak[3] = {};
+    tlb_compare_params cparams = {};             // compare monitor (tlb_tick_enable_compare): needs the AUDIO monitor's decoded PCM
 #ifdef TLB_FAULT_INJECT
     int damage_nth = 0, damage_stream = 0, damage_byte = 0; uint8_t damage_xor = 0, damage_val = 0;      // tlb_debug_tick_damage_next
     int cross_nth = 0, cross_a = -1, cross_b = -1; bool cross_on = false; uint8_t *d_cross_tmp = nullptr;   // tlb_debug_tick_cross_from
@@ -146,6 +167,43 @@ static unsigned tick_inputs(const tlb_tick *t)
            (t->lane[LANE_DOWN_FEED].on ? TLB_IN_BIT(TLB_IN_DOWN_FEED) : 0u) | (t->short_reads ? TLB_IN_BIT(TLB_IN_SHORT_READS) : 0u);
 }
 static bool tick_may_set(const tlb_tick *t, TlbInput f) { return tlb_input_may_set(TLB_INPUTS_OBJECT, f, tick_inputs(t)); }
+// THE STAGED OPT-IN, all or nothing: `stage` puts every buffer into a local owner and the groups' fields into a copy of the
+// groups, runs the batches' *_prepare, and may fail with a code; then settle, commit -- and only after that do the caller's own fields and the
+// option's flag change.  A refused attempt leaves the object as it was (what a batch made for itself stays: it is used by nothing yet).
+template <class Stage> static int tick_opt_in(tlb_tick *t, Stage stage)
+{
+    TlbMem m;
+    std::vector<TickGroup> gs = t->groups;
+    if (int rc = stage(m, gs)) return rc;
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(t->mem);
+    t->groups.swap(gs);
+    return TLB_OK;
+}
+// A record option is opted into the same way (after the caller's own argument checks): the events of its groups, then in one staged opt-in its
+// pinned sets and, group by group, what `stage` makes for the group (its batch's *_prepare or enable first) and the group's device array;
+// then the option is on.  `also`: three more pinned sets of `also_bytes` each that travel with the records (the monitor's listened PCM).
+// What else the caller sets stays with it.
+template <class Stage> static int tick_record_enable(tlb_tick *t, int r, Stage stage, size_t also_bytes = 0, void **also = nullptr)
+{
+    const RecordOption &R = tick_records[r];
+    HIPCHK(hipSetDevice(t->device));
+    for (auto &G : t->groups) if (!G.ev_rec[R.ev]) HIPCHK(hipEventCreateWithFlags(&G.ev_rec[R.ev], hipEventDisableTiming));   // (a refused attempt keeps them for the next)
+    void *h[3];
+    if (int rc = tick_opt_in(t, [&](TlbMem &m, std::vector<TickGroup> &gs) {
+            for (int k = 0; k < 3; k++) { h[k] = m.pinned<uint8_t>((size_t)t->nstreams * R.size); if (also) also[k] = m.pinned<uint8_t>(also_bytes); }
+            for (auto &G : gs) {
+                if (int rc = stage(m, G)) return rc;
+                G.d_rec[r] = m.dev<uint8_t>((size_t)G.n * R.size);
+            }
+            return 0;
+        })) return rc;
+    memcpy(t->rec[r].h, h, sizeof h);
+    t->rec[r].on = true;
+    return TLB_OK;
+}
+// ... and read the same way: the records of the tick waited for last, NULL while the option is off
+static const void *tick_record(const tlb_tick *t, int r) { return t && t->rec[r].on ? t->rec[r].h[t->out_set] : nullptr; }
 #ifdef TLB_FAULT_INJECT
 static int tick_cross(tlb_tick *t, TickGroup &G);
 #endif
@@ -164,9 +222,7 @@ void tlb_tick_destroy(tlb_tick *t)
         if (g.ev_ingested) (void)hipEventDestroy(g.ev_ingested);
         if (g.ev_encoded) (void)hipEventDestroy(g.ev_encoded);
         if (g.ev_out) (void)hipEventDestroy(g.ev_out);
-        if (g.ev_mon) (void)hipEventDestroy(g.ev_mon);
-        if (g.ev_loud) (void)hipEventDestroy(g.ev_loud);
-        if (g.ev_tpeak) (void)hipEventDestroy(g.ev_tpeak);
+        for (hipEvent_t e : g.ev_rec) if (e) (void)hipEventDestroy(e);
     }
     if (t->s_in) (void)hipStreamDestroy(t->s_in);
     if (t->s_run) (void)hipStreamDestroy(t->s_run);
@@ -301,50 +357,39 @@ int tlb_tick_enable_short_reads(tlb_tick *t)
     if (t->short_reads) return TLB_OK;
     HIPCHK(hipSetDevice(t->device));
     const size_t ns = (size_t)t->nstreams;
-    // The opt-in pattern, all or nothing: stage every buffer in a local owner and the groups' fields in a copy of the groups, run
-    // the batches' *_prepare, settle, commit -- and only then do the object's fields and the option's flag change.
-    TlbMem m;
-    std::vector<TickGroup> gs = t->groups;
     int32_t *h_valid[2]; uint32_t *h_ms[3], *h_n[3];
-    for (int k = 0; k < 2; k++) h_valid[k] = m.pinned<int32_t>(ns);
-    for (int k = 0; k < 3; k++) { h_ms[k] = m.pinned<uint32_t>(ns); h_n[k] = m.pinned<uint32_t>(ns); }
-    for (auto &G : gs) { G.d_valid = m.dev<int32_t>((size_t)G.n); G.d_underrun_ms = m.dev<uint32_t>((size_t)G.n); G.d_underruns = m.dev<uint32_t>((size_t)G.n); }
-    if (!m.settle()) return TLB_ERR_HIP;
-    m.commit(t->mem);
-    t->groups.swap(gs);
+    if (int rc = tick_opt_in(t, [&](TlbMem &m, std::vector<TickGroup> &gs) {
+            for (int k = 0; k < 2; k++) h_valid[k] = m.pinned<int32_t>(ns);
+            for (int k = 0; k < 3; k++) { h_ms[k] = m.pinned<uint32_t>(ns); h_n[k] = m.pinned<uint32_t>(ns); }
+            for (auto &G : gs) { G.d_valid = m.dev<int32_t>((size_t)G.n); G.d_underrun_ms = m.dev<uint32_t>((size_t)G.n); G.d_underruns = m.dev<uint32_t>((size_t)G.n); }
+            return 0;
+        })) return rc;
     for (int k = 0; k < 2; k++) for (size_t i = 0; i < ns; i++) h_valid[k][i] = TLB_SAMPLES_PER_FRAME;
     memcpy(t->h_valid, h_valid, sizeof h_valid); memcpy(t->h_underrun_ms, h_ms, sizeof h_ms); memcpy(t->h_underruns, h_n, sizeof h_n);
     t->short_reads = true;
     return TLB_OK;
 }
-// The confidence monitor is opted into the same way: the object then queues tlb_decode_device and the fold (tlb_monitor_device) behind
-// every tick's egress kernels.  The decoder's tables and state are made here, not by the first tick (the first decode call of a batch
-// waits for the device once).  An object that never makes the call makes the device calls it always made.
+// The confidence monitor, a record option (tick_record_enable): the object then queues tlb_decode_device and the fold (tlb_monitor_device) behind every tick's egress kernels.  The
+// decoder's tables and state are made here, not by the first tick (the first decode call of a batch waits for the device once).  An object
+// that never makes the call makes the device calls it always made.
 int tlb_tick_enable_monitor(tlb_tick *t, int what)
 {
     if (!t || t->finished || t->ticks > 0 || (what != TLB_MONITOR_CHECK && what != TLB_MONITOR_AUDIO)) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     if (t->monitor) return t->monitor == what ? (int)TLB_OK : (int)TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(t->device));
-    const size_t ns = (size_t)t->nstreams, pcm = 2 * TLB_SAMPLES_PER_FRAME;
-    for (auto &G : t->groups) if (!G.ev_mon) HIPCHK(hipEventCreateWithFlags(&G.ev_mon, hipEventDisableTiming));   // (a refused attempt keeps them for the next)
-    TlbMem m;
-    std::vector<TickGroup> gs = t->groups;
-    tlb_monitor_record *h_record[3]; int16_t *h_listen[3];
-    for (int k = 0; k < 3; k++) { h_record[k] = m.pinned<tlb_monitor_record>(ns); h_listen[k] = m.pinned<int16_t>(pcm); }
-    for (auto &G : gs) {
-        if (int rc = decode_prepare(G.b)) return rc;
-        G.d_report = m.dev<tlb_frame_report>((size_t)G.n); G.d_record = m.dev<tlb_monitor_record>((size_t)G.n);
-        if (what == TLB_MONITOR_AUDIO) G.d_mpcm = m.dev<int16_t>((size_t)G.n * pcm);
-    }
-    if (!m.settle()) return TLB_ERR_HIP;
-    m.commit(t->mem);
-    t->groups.swap(gs);
-    memcpy(t->h_record, h_record, sizeof h_record); memcpy(t->h_listen, h_listen, sizeof h_listen);
+    const size_t pcm = 2 * TLB_SAMPLES_PER_FRAME;
+    void *h_listen[3];
+    if (int rc = tick_record_enable(t, REC_MONITOR, [&](TlbMem &m, TickGroup &G) {
+            if (int rc = decode_prepare(G.b)) return rc;
+            G.d_report = m.dev<tlb_frame_report>((size_t)G.n);
+            if (what == TLB_MONITOR_AUDIO) G.d_mpcm = m.dev<int16_t>((size_t)G.n * pcm);
+            return 0;
+        }, pcm * sizeof(int16_t), h_listen)) return rc;
+    memcpy(t->h_listen, h_listen, sizeof h_listen);
     t->monitor = what;
     return TLB_OK;
 }
-const tlb_monitor_record *tlb_tick_monitor(const tlb_tick *t) { return t && t->monitor ? t->h_record[t->out_set] : nullptr; }
+const tlb_monitor_record *tlb_tick_monitor(const tlb_tick *t) { return (const tlb_monitor_record *)tick_record(t, REC_MONITOR); }
 // The compare monitor on top of it: the tick's planar PCM (d_pcm, what the encoder is given) against the decoded PCM of the frame that
 // leaves in the same tick (d_mpcm), through the history of the group's batch -- made here, not by the first tick.  Opt-in like the rest.
 int tlb_tick_enable_compare(tlb_tick *t, const tlb_compare_params *params)
@@ -352,100 +397,43 @@ int tlb_tick_enable_compare(tlb_tick *t, const tlb_compare_params *params)
     if (!t || !params || t->finished || t->ticks > 0 || t->monitor != TLB_MONITOR_AUDIO) return TLB_ERR_ARG;
     if (!tlb_compare_params_legal(params)) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
-    if (t->compare) return tlb_compare_params_same(*params, t->cparams) ? (int)TLB_OK : (int)TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(t->device));
-    TlbMem m;
-    std::vector<TickGroup> gs = t->groups;
-    tlb_compare_record *h_crecord[3];
-    for (int k = 0; k < 3; k++) h_crecord[k] = m.pinned<tlb_compare_record>((size_t)t->nstreams);
-    for (auto &G : gs) {
-        if (int rc = compare_prepare(G.b)) return rc;
-        G.d_crecord = m.dev<tlb_compare_record>((size_t)G.n);
-    }
-    if (!m.settle()) return TLB_ERR_HIP;
-    m.commit(t->mem);
-    t->groups.swap(gs);
-    memcpy(t->h_crecord, h_crecord, sizeof h_crecord);
+    if (t->rec[REC_COMPARE].on) return tlb_compare_params_same(*params, t->cparams) ? (int)TLB_OK : (int)TLB_ERR_ARG;
+    if (int rc = tick_record_enable(t, REC_COMPARE, [](TlbMem &, TickGroup &G) { return compare_prepare(G.b); })) return rc;
     t->cparams = *params;
-    t->compare = true;
     return TLB_OK;
 }
-const tlb_compare_record *tlb_tick_compare(const tlb_tick *t) { return t && t->compare ? t->h_crecord[t->out_set] : nullptr; }
-// The loudness meter (tlb_loudness_*) is opted into the same way: the state of every group's batch is made here, and every submit then queues
-// the meter on the tick's planar PCM (d_pcm, what the encoder is given) behind the egress kernels.  An object that never makes the call
-// allocates and queues nothing new.
-int tlb_tick_enable_loudness(tlb_tick *t)
+const tlb_compare_record *tlb_tick_compare(const tlb_tick *t) { return (const tlb_compare_record *)tick_record(t, REC_COMPARE); }
+// The PCM meters (tlb_loudness_*, tlb_truepeak_*): the state of every group's batch is made here (the true-peak meter's with the one ceiling),
+// and every submit with new input then queues the meter on the tick's planar PCM (d_pcm, what the encoder is given) behind the egress
+// kernels, in table order.  An object that never makes the call allocates and queues nothing new.
+static int tick_meter_enable(tlb_tick *t, int r, uint32_t ceiling)
 {
     if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
-    if (t->loudness) return TLB_OK;
-    HIPCHK(hipSetDevice(t->device));
-    for (auto &G : t->groups) if (!G.ev_loud) HIPCHK(hipEventCreateWithFlags(&G.ev_loud, hipEventDisableTiming));  // (a refused attempt keeps them for the next)
-    TlbMem m;
-    std::vector<TickGroup> gs = t->groups;
-    tlb_loudness_record *h_loud[3];
-    for (int k = 0; k < 3; k++) h_loud[k] = m.pinned<tlb_loudness_record>((size_t)t->nstreams);
-    for (auto &G : gs) {
-        if (int rc = tlb_loudness_enable(G.b)) return rc;
-        G.d_loud = m.dev<tlb_loudness_record>((size_t)G.n);
-    }
-    if (!m.settle()) return TLB_ERR_HIP;
-    m.commit(t->mem);
-    t->groups.swap(gs);
-    memcpy(t->h_loud, h_loud, sizeof h_loud);
-    t->loudness = true;
-    return TLB_OK;
+    if (t->rec[r].on) return TLB_OK;
+    return tick_record_enable(t, r, [&](TlbMem &, TickGroup &G) { return tick_records[r].enable(G.b, ceiling); });
 }
-const tlb_loudness_record *tlb_tick_loudness(const tlb_tick *t) { return t && t->loudness ? t->h_loud[t->out_set] : nullptr; }
-// Programme loudness of every stream from the counts so far, and EBU mode's reset (stream -1: all): legal with no tick in flight.
+// ... a meter's reset of one stream or of all (-1): legal with no tick in flight
+static int tick_meter_reset(tlb_tick *t, int r, int stream)
+{
+    if (!t || !t->rec[r].on || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    return t->blocks.visit(stream, [&](int g, int k) { return tick_records[r].reset(t->groups[(size_t)g].b, k); });
+}
+int tlb_tick_enable_loudness(tlb_tick *t) { return tick_meter_enable(t, REC_LOUDNESS, 0); }
+const tlb_loudness_record *tlb_tick_loudness(const tlb_tick *t) { return (const tlb_loudness_record *)tick_record(t, REC_LOUDNESS); }
+int tlb_tick_loudness_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_LOUDNESS, stream); }
+// Programme loudness of every stream from the counts so far: legal with no tick in flight.
 int tlb_tick_loudness_programme(tlb_tick *t, tlb_loudness_programme_record *out)
 {
-    if (!t || !out || !t->loudness || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (!t || !out || !t->rec[REC_LOUDNESS].on || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     for (auto &G : t->groups) if (int rc = tlb_loudness_programme_host(G.b, out + G.first)) return rc;
     return TLB_OK;
 }
-int tlb_tick_loudness_reset(tlb_tick *t, int stream)
-{
-    if (!t || !t->loudness || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
-    if (t->broken) return TLB_ERR_HIP;
-    if (stream >= 0) { int k; const TickGroup *G = tick_group_of(t, stream, &k); return tlb_loudness_reset(G->b, k); }
-    for (auto &G : t->groups) if (int rc = tlb_loudness_reset(G.b, -1)) return rc;
-    return TLB_OK;
-}
-// The true-peak meter (tlb_truepeak_*) likewise: the state of every group's batch is made here with the one ceiling, and every submit with
-// new input then queues the meter on d_pcm behind the egress kernels -- and behind the loudness meter when both are on.
-int tlb_tick_enable_truepeak(tlb_tick *t, uint32_t ceiling)
-{
-    if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
-    if (t->broken) return TLB_ERR_HIP;
-    if (t->truepeak) return TLB_OK;
-    HIPCHK(hipSetDevice(t->device));
-    for (auto &G : t->groups) if (!G.ev_tpeak) HIPCHK(hipEventCreateWithFlags(&G.ev_tpeak, hipEventDisableTiming));  // (a refused attempt keeps them for the next)
-    TlbMem m;
-    std::vector<TickGroup> gs = t->groups;
-    tlb_truepeak_record *h_tpeak[3];
-    for (int k = 0; k < 3; k++) h_tpeak[k] = m.pinned<tlb_truepeak_record>((size_t)t->nstreams);
-    for (auto &G : gs) {
-        if (int rc = tlb_truepeak_enable(G.b, ceiling)) return rc;
-        G.d_tpeak = m.dev<tlb_truepeak_record>((size_t)G.n);
-    }
-    if (!m.settle()) return TLB_ERR_HIP;
-    m.commit(t->mem);
-    t->groups.swap(gs);
-    memcpy(t->h_tpeak, h_tpeak, sizeof h_tpeak);
-    t->truepeak = true;
-    return TLB_OK;
-}
-const tlb_truepeak_record *tlb_tick_truepeak(const tlb_tick *t) { return t && t->truepeak ? t->h_tpeak[t->out_set] : nullptr; }
-int tlb_tick_truepeak_reset(tlb_tick *t, int stream)
-{
-    if (!t || !t->truepeak || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
-    if (t->broken) return TLB_ERR_HIP;
-    if (stream >= 0) { int k; const TickGroup *G = tick_group_of(t, stream, &k); return tlb_truepeak_reset(G->b, k); }
-    for (auto &G : t->groups) if (int rc = tlb_truepeak_reset(G.b, -1)) return rc;
-    return TLB_OK;
-}
+int tlb_tick_enable_truepeak(tlb_tick *t, uint32_t ceiling) { return tick_meter_enable(t, REC_TRUEPEAK, ceiling); }
+const tlb_truepeak_record *tlb_tick_truepeak(const tlb_tick *t) { return (const tlb_truepeak_record *)tick_record(t, REC_TRUEPEAK); }
+int tlb_tick_truepeak_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_TRUEPEAK, stream); }
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)
 {
     if (!t || t->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
@@ -486,15 +474,13 @@ static int tick_set_rate(tlb_tick *t, int stream, long source_rate, bool down)
     if (any && !tick_may_set(t, down ? TLB_IN_DOWN_SOURCE : TLB_IN_UP_SOURCE)) return TLB_ERR_ARG;
     HIPCHK(hipSetDevice(t->device));
     if (!made) {                                                     // first real source: the buffers, and the resampler or decimator of the batches that get
-        TlbMem m;                                                    // one, before anything is committed or a stream is changed
-        std::vector<TickGroup> gs = t->groups;
-        int16_t *h[2] = {};
-        for (int k = 0; k < 2 && down; k++) h[k] = m.pinned<int16_t>((size_t)t->nstreams * TLB_DECIMATE_SLOT);
-        for (auto &G : gs) (down ? G.d_wide : G.d_rs) = m.dev<int16_t>((size_t)G.n * (down ? TLB_DECIMATE_SLOT : 2304));
-        for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = prepare(gs[g].b)) return rc;
-        if (!m.settle()) return TLB_ERR_HIP;
-        m.commit(t->mem);
-        t->groups.swap(gs);
+        int16_t *h[2] = {};                                          // one, before anything is committed or a stream is changed
+        if (int rc = tick_opt_in(t, [&](TlbMem &m, std::vector<TickGroup> &gs) {
+                for (int k = 0; k < 2 && down; k++) h[k] = m.pinned<int16_t>((size_t)t->nstreams * TLB_DECIMATE_SLOT);
+                for (auto &G : gs) (down ? G.d_wide : G.d_rs) = m.dev<int16_t>((size_t)G.n * (down ? TLB_DECIMATE_SLOT : 2304));
+                for (size_t g = 0; g < gs.size(); g++) if (real[g]) if (int rc = prepare(gs[g].b)) return rc;
+                return 0;
+            })) return rc;
         if (down) memcpy(t->h_wide, h, sizeof h);
     }
     const int rc = t->blocks.visit(stream, [&](int g, int k) { return set(t->groups[(size_t)g].b, k, source_rate); });
@@ -556,15 +542,13 @@ static int tick_lane_set(tlb_tick *t, int lane, int stream, const tlb_feed_confi
     HIPCHK(hipSetDevice(t->device));
     const size_t ns = (size_t)t->nstreams, per = (size_t)F.slots;
     if (!L.h_len[0]) {                                               // the lane's first feed: lengths and reports, made once
-        TlbMem m;
-        std::vector<TickGroup> gs = t->groups;
         int32_t *h_len[2]; tlb_frame_report *h_rep[3];
-        for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(per * ns);
-        for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(per * ns);
-        for (auto &G : gs) { G.lane[lane].d_len = m.dev<int32_t>(per * (size_t)G.n); G.lane[lane].d_report = m.dev<tlb_frame_report>(per * (size_t)G.n); }
-        if (!m.settle()) return TLB_ERR_HIP;
-        m.commit(t->mem);
-        t->groups.swap(gs);
+        if (int rc = tick_opt_in(t, [&](TlbMem &m, std::vector<TickGroup> &gs) {
+                for (int k = 0; k < 2; k++) h_len[k] = m.pinned<int32_t>(per * ns);
+                for (int k = 0; k < 3; k++) h_rep[k] = m.pinned<tlb_frame_report>(per * ns);
+                for (auto &G : gs) { G.lane[lane].d_len = m.dev<int32_t>(per * (size_t)G.n); G.lane[lane].d_report = m.dev<tlb_frame_report>(per * (size_t)G.n); }
+                return 0;
+            })) return rc;
         memcpy(L.h_len, h_len, sizeof h_len); memcpy(L.h_report, h_rep, sizeof h_rep);
     }
     const int want = cfg ? feed_slot_bytes(cfg) : 0;
@@ -669,6 +653,14 @@ int tlb_tick_stream_reconfigure(tlb_tick *t, int stream, const tlb_stream_config
     return rc;
 }
 
+// the copy-out of a record option's records of this tick, queued on s_out; `wait`: behind the option's event (something wrote them this tick)
+static int tick_record_out(tlb_tick *t, TickGroup &G, int r, int set, bool wait)
+{
+    const RecordOption &R = tick_records[r];
+    if (wait) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_rec[R.ev], 0));
+    HIPCHK(hipMemcpyAsync((uint8_t *)t->rec[r].h[set] + (size_t)G.first * R.size, G.d_rec[r], (size_t)G.n * R.size, hipMemcpyDeviceToHost, t->s_out));
+    return TLB_OK;
+}
 // egress of the frames sitting in G.d_frames + copy-out, queued on s_run / s_out
 static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, bool new_input = true)
 {
@@ -686,23 +678,21 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
                                             G.d_frags, G.d_fraglen, G.d_nfrag, G.max_frags, G.frag_stride, t->s_run)) return rc;
     }
     HIPCHK(hipEventRecord(G.ev_run, t->s_run));
+    const bool compare = t->rec[REC_COMPARE].on;
     if (t->monitor && have_frames) {                                 // behind the egress kernels: the packets' copy-out waits for ev_run only
         if (int rc = tlb_decode_device(G.b, G.d_frames, G.d_flen, 1, G.d_report, nullptr, G.d_mpcm, t->s_run)) return rc;
-        if (int rc = tlb_monitor_device(G.b, G.d_report, G.d_mpcm, 1, G.d_record, t->s_run)) return rc;
-        if (!t->compare) HIPCHK(hipEventRecord(G.ev_mon, t->s_run));
+        if (int rc = tlb_monitor_device(G.b, G.d_report, G.d_mpcm, 1, (tlb_monitor_record *)G.d_rec[REC_MONITOR], t->s_run)) return rc;
+        if (!compare) HIPCHK(hipEventRecord(G.ev_rec[REC_MONITOR], t->s_run));
     }
-    if (t->compare) {                                                // behind the decode: this tick's input against the frame that leaves with it.  The first
+    if (compare) {                                                   // behind the decode: this tick's input against the frame that leaves with it.  The first
         // tick has no frame yet (no report: the slot counts as skipped) and only advances the history; the flush has no input and does not advance it
-        if (int rc = compare_launch(G.b, new_input ? G.d_pcm : nullptr, G.d_mpcm, have_frames ? G.d_report : nullptr, 1, &t->cparams, G.d_crecord, t->s_run)) return rc;
-        HIPCHK(hipEventRecord(G.ev_mon, t->s_run));
+        if (int rc = compare_launch(G.b, new_input ? G.d_pcm : nullptr, G.d_mpcm, have_frames ? G.d_report : nullptr, 1, &t->cparams, (tlb_compare_record *)G.d_rec[REC_COMPARE], t->s_run)) return rc;
+        HIPCHK(hipEventRecord(G.ev_rec[REC_MONITOR], t->s_run));
     }
-    if (t->loudness && new_input) {                                  // the PCM that went IN this tick (the flush has none: its set shows the same records)
-        if (int rc = tlb_loudness_device(G.b, G.d_pcm, 1, G.d_loud, t->s_run)) return rc;
-        HIPCHK(hipEventRecord(G.ev_loud, t->s_run));
-    }
-    if (t->truepeak && new_input) {                                  // likewise, behind the loudness meter on the same PCM
-        if (int rc = tlb_truepeak_device(G.b, G.d_pcm, 1, G.d_tpeak, t->s_run)) return rc;
-        HIPCHK(hipEventRecord(G.ev_tpeak, t->s_run));
+    for (int r = 0; r < RECS && new_input; r++) {                    // the meters that are on, one behind the other, on the PCM that went IN this tick
+        if (!t->rec[r].on || !tick_records[r].launch) continue;      // (the flush has none: its set shows the same records)
+        if (int rc = tick_records[r].launch(G.b, G.d_pcm, 1, G.d_rec[r], t->s_run)) return rc;
+        HIPCHK(hipEventRecord(G.ev_rec[r], t->s_run));
     }
     HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_run, 0));
     HIPCHK(hipMemcpyAsync(t->h_peaks[set] + (size_t)G.first * 2, G.d_peaks, n * 4, hipMemcpyDeviceToHost, t->s_out));
@@ -732,21 +722,14 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
         }
     }
     if (t->monitor) {                                                // the records (and the listened stream's frame) behind the packets
-        if (have_frames || t->compare) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_mon, 0));
-        HIPCHK(hipMemcpyAsync(t->h_record[set] + G.first, G.d_record, n * sizeof(tlb_monitor_record), hipMemcpyDeviceToHost, t->s_out));
-        if (t->compare) HIPCHK(hipMemcpyAsync(t->h_crecord[set] + G.first, G.d_crecord, n * sizeof(tlb_compare_record), hipMemcpyDeviceToHost, t->s_out));
+        if (int rc = tick_record_out(t, G, REC_MONITOR, set, have_frames || compare)) return rc;
+        if (compare) if (int rc = tick_record_out(t, G, REC_COMPARE, set, false)) return rc;     // (the monitor's event is theirs too)
         const int k = t->listen_of[set] - G.first;
         if (G.d_mpcm && k >= 0 && k < G.n)
             HIPCHK(hipMemcpyAsync(t->h_listen[set], G.d_mpcm + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME, 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost, t->s_out));
     }
-    if (t->loudness) {                                               // ... and the loudness records, on an event of their own
-        if (new_input) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_loud, 0));
-        HIPCHK(hipMemcpyAsync(t->h_loud[set] + G.first, G.d_loud, n * sizeof(tlb_loudness_record), hipMemcpyDeviceToHost, t->s_out));
-    }
-    if (t->truepeak) {                                               // ... and the true-peak records, on theirs
-        if (new_input) HIPCHK(hipStreamWaitEvent(t->s_out, G.ev_tpeak, 0));
-        HIPCHK(hipMemcpyAsync(t->h_tpeak[set] + G.first, G.d_tpeak, n * sizeof(tlb_truepeak_record), hipMemcpyDeviceToHost, t->s_out));
-    }
+    for (int r = 0; r < RECS; r++)                                   // ... and the meters' records, each on an event of its own
+        if (t->rec[r].on && tick_records[r].launch) if (int rc = tick_record_out(t, G, r, set, new_input)) return rc;
     HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed (the monitor's reads of d_frames included)
     return TLB_OK;
 }

@@ -66,26 +66,9 @@ int tlb_truepeak_device(tlb_batch *b, const int16_t *d_pcm_planar, int nframes, 
 
 int tlb_truepeak_host(tlb_batch *b, const int16_t *pcm_planar, int nframes, tlb_truepeak_record *records)
 {
-    if (!b || !pcm_planar || !records || nframes <= 0 || (long long)nframes * b->nstreams > (1ll << 30) || !b->d_tp_rec) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    const size_t vals = (size_t)nframes * (size_t)b->nstreams * 2 * TLB_SAMPLES_PER_FRAME;
-    TlbMem m;
-    int16_t *d_pcm = m.scratch<int16_t>(vals);
-    tlb_truepeak_record *d_rec = m.scratch<tlb_truepeak_record>((size_t)b->nstreams);
-    MEMCHK(m);
-    HIPCHK(hipMemcpy(d_pcm, pcm_planar, vals * sizeof(int16_t), hipMemcpyHostToDevice));
-    if (int rc = tlb_truepeak_device(b, d_pcm, nframes, d_rec, nullptr)) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(records, d_rec, (size_t)b->nstreams * sizeof(tlb_truepeak_record), hipMemcpyDeviceToHost));
-    return TLB_OK;
+    return meter_host(b, b ? b->d_tp_rec : nullptr, pcm_planar, nframes, records, tlb_truepeak_device);
 }
 
-int tlb_truepeak_reset(tlb_batch *b, int stream)
-{
-    if (!b || stream < -1 || stream >= b->nstreams || !b->d_tp_rec) return TLB_ERR_ARG;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipDeviceSynchronize());
-    return stream < 0 ? truepeak_clear_streams(b, 0, b->nstreams) : truepeak_clear_streams(b, stream, 1);
-}
+int tlb_truepeak_reset(tlb_batch *b, int stream) { return meter_reset(b, b ? b->d_tp_rec : nullptr, stream, truepeak_clear_streams); }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 """Every opt-in of a tick object is all or nothing (csrc/tlb_mem.h: stage, settle, commit, flag).  The fault-injection build refuses the nth
 allocation of the library's memory owner (tlb_debug_alloc_fail_next, csrc/tlb_debug.h): an allocation returns an error code, nothing is
-launched.  For enable_short_reads, enable_monitor(AUDIO), enable_compare after it and set_source(stream 0, 44100) the call is made with
-nth = 1, 2, ... armed until it is accepted: every refused attempt answers TLB_ERR_HIP, leaves the option off and the object healthy, and
+launched.  For enable_short_reads, enable_monitor(AUDIO), enable_compare after it, set_source(stream 0, 44100), enable_loudness and
+enable_truepeak the call is made with nth = 1, 2, ... armed until it is accepted: every refused attempt answers TLB_ERR_HIP, leaves the option off and the object healthy, and
 the object then produces, tick by tick and at the finish, the bytes of a twin that opted in with nothing armed.  That some attempt was
 refused after the first group's buffers had been staged is shown by counting: the same streams as ONE group are refused fewer times.
 (A tick object has no tlb_resample_source of its own: "no source" is tlb_tick_need == 1152 here, and 0 from the group's batch is what
@@ -93,6 +93,11 @@ OPTINS = {
                     off=lambda t: t.compare is None, touch=lambda t, f: None, records=lambda t: t.monitor.tobytes() + t.compare.tobytes()),
     "set_source": dict(before=[], call=lambda t: t.L.tlb_tick_set_source(t.h, 0, 44100), off=lambda t: t.need(0) == SAMPLES,
                        touch=lambda t, f: None, records=lambda t: bytes([t.need(0) & 255, t.need(0) >> 8])),
+    # (a batch's meter state that an earlier attempt made stays with the batch; the object's option is off until the whole call goes through)
+    "loudness": dict(before=[], call=lambda t: t.L.tlb_tick_enable_loudness(t.h), off=lambda t: t.loudness is None,
+                     touch=lambda t, f: None, records=lambda t: t.loudness.tobytes()),
+    "truepeak": dict(before=[], call=lambda t: t.L.tlb_tick_enable_truepeak(t.h, 0), off=lambda t: t.truepeak is None,
+                     touch=lambda t, f: None, records=lambda t: t.truepeak.tobytes()),
 }
 
 
