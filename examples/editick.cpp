@@ -7,7 +7,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
 //   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
 //   header's padding bit, service s takes frame (tick + s) of it (wrapping round), one tick per frame of the file.  No PCM crosses the
@@ -35,6 +35,10 @@
 //   --truepeak [DBTP]: the true-peak meter (tlb_tick_enable_truepeak): the same PCM oversampled four times on the device after ITU-R
 //   BS.1770-4 Annex 2, against a ceiling of DBTP (default -1, EBU R 128's).  One line per stream at the end: the maximum true peak in
 //   dBTP, the largest sample in dBFS and the number of frames over the ceiling.
+//   --limit [DBTP] --limit-release MS: the true-peak limiter (tlb_tick_enable_limiter) between the ingest and the encoder, with a ceiling of
+//   DBTP (default -1) and a release of MS milliseconds (default 100): what is encoded, and what the meters above read, is the limited PCM,
+//   63 samples late.  One line per stream at the end: the frames limited, the largest reduction (65536 - G, and in dB) and the input's
+//   maximum true peak.
 // out.af: for every packet a little-endian uint32 length, then the packet.
 #include <chrono>
 #include <cmath>
@@ -56,13 +60,13 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0;
-    double ceiling_db = -1.0;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0, limit = 0, limit_release = 0;
+    double ceiling_db = -1.0, limit_db = -1.0;
     char mode = 0;
     double gain_db = 0.0;
     const char *feed_path = nullptr;
@@ -79,6 +83,13 @@ int main(int argc, char **argv)
             if (i + 1 < argc && end != argv[i + 1] && !*end) ceiling_db = v; else i--;
             continue;
         }
+        if (k == "--limit") {                                    // likewise
+            limit = 1;
+            char *end = nullptr;
+            const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) limit_db = v; else i--;
+            continue;
+        }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") rate = std::atol(v);
@@ -91,6 +102,7 @@ int main(int argc, char **argv)
         else if (k == "-t") now_s = std::atoll(v);
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
+        else if (k == "--limit-release") limit_release = std::atoi(v);
         else if (k == "--source-rate") source_rate = std::atol(v);
         else if (k == "--feed") feed_path = v;
         else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
@@ -150,6 +162,8 @@ int main(int argc, char **argv)
     if (loudness) if (int rc = tlb_tick_enable_loudness(t)) die("tlb_tick_enable_loudness", rc);                 // likewise
     const uint32_t ceiling = (uint32_t)std::llround(1073741824.0 * std::pow(10.0, ceiling_db / 20.0));             // in units of 2^-30 of full scale
     if (truepeak) if (int rc = tlb_tick_enable_truepeak(t, ceiling)) die("tlb_tick_enable_truepeak", rc);        // likewise
+    const tlb_limiter_params lparams = {(uint32_t)std::llround(1073741824.0 * std::pow(10.0, limit_db / 20.0)), (uint32_t)limit_release};      // release 0: the default
+    if (limit) if (int rc = tlb_tick_enable_limiter(t, &lparams)) die("tlb_tick_enable_limiter", rc);             // likewise
     const bool down = source_rate > rate;                    // a source above the encoder's rate goes through the decimator and its wide slots
     if (source_rate && !down) if (int rc = tlb_tick_set_source(t, -1, source_rate)) die("tlb_tick_set_source", rc);       // while no tick is in flight
     if (down) if (int rc = tlb_tick_set_down_source(t, -1, source_rate)) die("tlb_tick_set_down_source", rc);             // likewise
@@ -275,6 +289,13 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "editick: truepeak: stream %d: max %.2f dBTP, samples %.2f dBFS, %u of %u frames over %.2f dBTP\n", s,
                          tlb_truepeak_dbtp(pk), tlb_truepeak_dbtp(sm << 15), r[s].overs, r[s].frames, tlb_truepeak_dbtp(ceiling));
         }
+    }
+    if (limit && frames > 0) {                                   // the records of the last tick (the finish adds nothing)
+        const tlb_limiter_record *r = tlb_tick_limiter(t);
+        for (int s = 0; s < nstreams; s++)
+            std::fprintf(stderr, "editick: limiter: stream %d: limited %u of %u frames, red_max %u (%.2f dB), input max %.2f dBTP, ceiling %.2f dBTP\n", s,
+                         r[s].limited, r[s].frames, r[s].red_max, r[s].red_max < 65536u ? 20.0 * std::log10((65536.0 - r[s].red_max) / 65536.0) : -INFINITY,
+                         tlb_truepeak_dbtp(r[s].peak_in_max), tlb_truepeak_dbtp(lparams.ceiling));
     }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     std::fprintf(stderr, "editick: %ld ticks of %d stream(s), %ld AF packets of stream 0, %.3f s (%.0f frames/s, PCIe and EDI included)\n",

@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R]
+//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R]
 //   in.s16le: interleaved stereo at the services' rate (-r: 48000, the default, or 24000); stream s starts reading at frame s (so the
 //   services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
@@ -154,11 +154,11 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0;
-    double ceiling_db = -1.0;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0, limit = 0, limit_release = 0;
+    double ceiling_db = -1.0, limit_db = -1.0;
     long rate = 48000;
     double deadline_ms = 0;
     long source_rate = 0;
@@ -176,6 +176,13 @@ int main(int argc, char **argv)
             if (i + 1 < argc && end != argv[i + 1] && !*end) ceiling_db = v; else i--;
             continue;
         }
+        if (k == "--limit") {                                    // likewise
+            limit = 1;
+            char *end = nullptr;
+            const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) limit_db = v; else i--;
+            continue;
+        }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-n") nstreams = std::atoi(v);
@@ -189,6 +196,7 @@ int main(int argc, char **argv)
         else if (k == "--deadline-ms") { deadline_ms = std::atof(v); if (!(deadline_ms > 0)) die("--deadline-ms wants a positive number", 0); }
         else if (k == "--short-every") short_every = std::atoi(v);
         else if (k == "--short-by") short_by = std::atoi(v);
+        else if (k == "--limit-release") limit_release = std::atoi(v);
         else if (k == "--source-rate") source_rate = std::atol(v);
         else if (k == "--feed") feed_path = v;
         else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
@@ -274,6 +282,9 @@ int main(int argc, char **argv)
     const uint32_t ceiling = (uint32_t)std::llround(1073741824.0 * std::pow(10.0, ceiling_db / 20.0));    // in units of 2^-30 of full scale
     if (truepeak)
         if (int rc = tlb_node_enable_truepeak(nd, ceiling)) die("tlb_node_enable_truepeak", rc);        // likewise, with the same ceiling
+    const tlb_limiter_params lparams = {(uint32_t)std::llround(1073741824.0 * std::pow(10.0, limit_db / 20.0)), (uint32_t)limit_release};      // release 0: the default
+    if (limit)
+        if (int rc = tlb_node_enable_limiter(nd, &lparams)) die("tlb_node_enable_limiter", rc);         // likewise, with the same parameters, from zero
     if (monitor)
         if (int rc = tlb_node_enable_monitor(nd, monitor)) die("tlb_node_enable_monitor", rc);          // likewise; a restarted shard is enabled again
     const bool down = source_rate > rate;
@@ -419,6 +430,12 @@ int main(int argc, char **argv)
                 std::fprintf(stderr, "nodetick: truepeak: service %d: max %.2f dBTP, samples %.2f dBFS, %u of %u frames over %.2f dBTP\n", s,
                              tlb_truepeak_dbtp(pk), tlb_truepeak_dbtp(sm << 15), r->overs, r->frames, tlb_truepeak_dbtp(ceiling));
             }
+    if (limit)                                                            // the records of the last step
+        for (int s = 0; s < nstreams; s++)
+            if (const tlb_limiter_record *r = tlb_node_limiter(nd, s))        // (NULL: its shard is down or late)
+                std::fprintf(stderr, "nodetick: limiter: service %d: limited %u of %u frames, red_max %u (%.2f dB), input max %.2f dBTP, ceiling %.2f dBTP\n", s,
+                             r->limited, r->frames, r->red_max, r->red_max < 65536u ? 20.0 * std::log10((65536.0 - r->red_max) / 65536.0) : -INFINITY,
+                             tlb_truepeak_dbtp(r->peak_in_max), tlb_truepeak_dbtp(lparams.ceiling));
     // one line for scripts: frames, packets, bytes, a hash of everything shipped (independent of G only per shard -- so print per-stream-order-free totals)
     std::printf("{\"streams\": %d, \"shards\": %d, \"ticks\": %d, \"frames\": %ld, \"packets\": %ld, \"bytes\": %ld, \"seconds\": %.4f, \"frames_per_s\": %.1f, \"realtime_x\": %.2f}\n",
                 nstreams, G, ticks, tot.frames, npk, nby, sec, sec > 0 ? tot.frames / sec : 0.0, sec > 0 ? ticks * 0.024 / sec : 0.0);

@@ -1195,7 +1195,8 @@ const tlb_frame_report *tlb_node_down_feed_report(const tlb_node *nd, int stream
  * record and answers NULL for a broken, late or stale shard; tlb_node_loudness_programme(nd, out [nstreams]) fills the blocks of the live
  * shards between steps (all zero for the others); tlb_node_loudness_reset routes like the stream life-cycle calls (TLB_ERR_HIP for a stream
  * of a broken shard, TLB_ERR_LATE for one of a late shard), -1 goes to every live shard.
- * NOT BUILT: loudness range (LRA), acting on the gain, loudness of the decoded output (the monitors own that side).
+ * NOT BUILT: loudness range (LRA), loudness of the decoded output (the monitors own that side).  Acting on the gain: the caller's loop with
+ * tlb_set_gain_db, and the true-peak limiter below (tlb_limiter_*) as the net under it.
  * ------------------------------------------------------------------------------------------ */
 #define TLB_LOUDNESS_BINS 751
 typedef struct { uint32_t frames, bins, blocks, gated;
@@ -1268,7 +1269,7 @@ int tlb_node_loudness_reset(tlb_node *nd, int stream);
  * shard made by tlb_node_shard_restart is enabled again with the same ceiling -- its records start from zero.  tlb_node_truepeak(nd, stream)
  * points at the STREAM's record and answers NULL for a broken, late or stale shard; tlb_node_truepeak_reset routes like
  * tlb_node_loudness_reset.
- * NOT BUILT: loudness range (LRA), acting on the gain (a limiter), true peak of the decoded output.
+ * NOT BUILT: loudness range (LRA), true peak of the decoded output.  Acting on the gain: the true-peak limiter below (tlb_limiter_*).
  * ------------------------------------------------------------------------------------------ */
 #define TLB_TRUEPEAK_TAPS 12
 #define TLB_TRUEPEAK_CEILING_DEFAULT 956973408u
@@ -1285,6 +1286,83 @@ int tlb_tick_truepeak_reset(tlb_tick *t, int stream);
 int tlb_node_enable_truepeak(tlb_node *nd, uint32_t ceiling);
 const tlb_truepeak_record *tlb_node_truepeak(const tlb_node *nd, int stream);
 int tlb_node_truepeak_reset(tlb_node *nd, int stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * True-peak limiter: a look-ahead limiter on the planar PCM between the ingest and the encoder, so that a caller who raises a quiet service
+ * towards -23 LUFS with tlb_set_gain_db need not lower the whole programme for the frames the true-peak meter then counts in `overs`.
+ * Opt-in, per stream, in place, on the device.
+ * THE ARITHMETIC.  The reference has no limiter, so this is the definition, in integers (tests/limiterlib.py restates it in numpy int64,
+ * every comparison against it is byte for byte, on the PCM and on the records).  U = 2^30 is unity gain; TLB_LIMITER_WMIN = 64,
+ * TLB_LIMITER_WBOX = 32, TLB_LIMITER_DELAY = 63.  Per stream, x_c[n] are the planar samples the ingest wrote since the stream's last
+ * reset, zeros before it (the true-peak meter's convention), H the committed table csrc/tl_truepeak_taps.inc, unchanged:
+ *   1 detector  P[n] = max over the stream's channels c of max(32768 |x_c[n]|, |v_1|, |v_2|, |v_3|), v_p = sum_{t < 12} H[p][t] x_c[n - t]:
+ *               the meter's per-sample quantity, in units of 2^-30 of full scale, a row in 32 bits by the table's bound.  The channels are
+ *               LINKED; dual channel counts as two channels; a one-channel stream's second row is neither read nor written
+ *   2 required  r[n] = U if P[n] <= ceiling, else floor(ceiling 2^30 / P[n]) (a 64-bit product; the result is below U)
+ *   3 hold      m[n] = min(r[n - 63 .. n]); r = U before the reset
+ *   4 release   e[n] = min(m[n], min(U, e[n - 1] + S)), e[-1] = U: the gain recovers linearly, S per sample.  A (min, +) recurrence, so
+ *               e[n] = min(U, min_{k <= n}(m[k] + (n - k) S), e[-1] + (n + 1) S): a prefix minimum, not a serial chain
+ *   5 smooth    G[n] = (sum_{i < 32} e[n - i]) >> 19 (the sum is at most 2^35: 64 bits); e = U before the reset; 0 <= G <= 65536
+ *   6 apply     y_c[n] = sgn(x_c[n - 63]) ((|x_c[n - 63]| G[n]) >> 16): the product is at most 2^31 and fits unsigned 32 bits;
+ *               G = 65536 returns the sample itself, -32768 included
+ * The output is the input 63 samples late (1.3 ms at 48 kHz); nothing anywhere compensates that delay.
+ * WHY THESE WINDOWS.  Every e[n - i], i < 32, is <= r[k] for all k in [n - 63, n - 31], so the gain on x[j], which leaves at n = j + 63, is
+ * <= r[k] for every k in [j, j + 32]: every detector position k in [j, j + 11] that x[j] is a tap of.  Where r[k0] is a local minimum, G is
+ * flat at r[k0] over the 33 outputs around it: all 12 samples of the offending interpolation get the same gain.
+ *   THEOREM.      32768 |y_c[n]| <= ceiling for every sample, for any input.
+ *   NOT A THEOREM. The output's TRUE peak can pass the ceiling: the gain varies across an interpolation's taps when overs follow each other
+ *                 within a release of a few samples.  A numpy statement of this definition showed it on adversarial full-scale random
+ *                 input (tests/test_limiter_emu.py measures it; DESIGN 7m has the figure); on structured signals -- sines, bursts,
+ *                 squares, sweeps, gated tones -- the output's true peak stayed at or below the ceiling.
+ * PARAMETERS.  tlb_limiter_params { ceiling, release_ms }: ceiling in 2^-30 units, 0 selects TLB_TRUEPEAK_CEILING_DEFAULT, any other value
+ * must lie in [2^20, 2^30]; release_ms 0 selects TLB_LIMITER_RELEASE_DEFAULT_MS = 100, any other value must lie in [1, 10000].  A NULL
+ * pointer is both defaults.  Per stream S = tlb_limiter_step(release_ms, samplerate) = max(1, (2^30 * 1000) / (release_ms * samplerate)),
+ * computed in 64 bits on the host from the stream's ENCODER rate (no GPU; 0 for an illegal argument) and again on tlb_stream_reconfigure.
+ * RECORD.  tlb_limiter_record, 32 bytes, zero after a reset: frames; limited = frames with any G < 65536; samples = outputs with
+ * G < 65536, saturating; red_last = 65536 - min G of the last frame; red_max = the largest red_last since the reset; peak_in = max P of
+ * the last frame; peak_in_max; reserved = 0.  An output belongs to the frame whose index n it has.
+ * STATE.  720 bytes of device memory per stream (the record, 64 samples of delay line per channel, the carried r as four lanes' suffix
+ * minima, the carried e of two lanes; csrc/mp2_limiter.h), allocated by tlb_limiter_enable ALONE: a batch that never enables it allocates
+ * and queues nothing new, and the other calls answer TLB_ERR_ARG on it.
+ *   tlb_limiter_enable(b, params)     allocates the state (waits for the device once); a second call with equal parameters answers 0, with
+ *                                     different ones TLB_ERR_ARG
+ *   tlb_limiter_device(b, d_pcm_planar, nframes, d_records, stream)
+ *                                     limits nframes of every stream IN PLACE, int16 [nframes][nstreams][2][1152] as tlb_ingest_device
+ *                                     writes it (16-byte aligned), and writes tlb_limiter_record [nstreams] (may be NULL) on hip_stream
+ *   tlb_limiter_host                  the same with host buffers (records may be NULL)
+ *   tlb_limiter_reset(b, stream)      -1: every stream.  Waits for the queued work, then zeroes the record, the delay line and the gains
+ *   tlb_limiter_step(release_ms, samplerate)    no GPU
+ * tlb_stream_reset, tlb_stream_reconfigure and tlb_reset clear the stream's limiter state; tlb_stream_finish leaves it, and the 63 samples
+ * still in the delay line are NOT flushed: they leave with the stream's next frames, or never.
+ * TICK PLANE.  tlb_tick_enable_limiter(t, params) before the first submit (TLB_ERR_ARG after it; a second call as above) enables the limiter
+ * of every group's batch.  Every submit then queues it on the tick's planar PCM on the run stream, behind the ingest and AHEAD of the
+ * encoder: the encoder, the compare monitor and both meters see the limited PCM.  The ingest's peaks and the silence counter remain those
+ * of the INPUT.  The 32-byte records travel with the three output sets behind the packets, on an event of their own.  tlb_tick_limiter(t) is
+ * tlb_limiter_record [nstreams] of the tick waited for last (pinned, valid until the next wait); NULL when the limiter is off.  After T
+ * waited ticks frames == T, and tlb_tick_finish adds nothing.  tlb_tick_limiter_reset(t, stream) (-1: all) is legal with no tick in flight.
+ * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_limiter goes to every shard before the first submit, and a shard
+ * made by tlb_node_shard_restart is enabled again with the same parameters, from zero.  tlb_node_limiter(nd, stream) points at the STREAM's
+ * record and answers NULL for a broken, late or stale shard; tlb_node_limiter_reset routes like tlb_node_loudness_reset.
+ * NOT BUILT: a loudness-driven automatic gain (the caller's loop stays the policy), multiband or soft-knee dynamics, unlinked channels,
+ * compensating the delay, limiting the decoded output.
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_LIMITER_WMIN 64
+#define TLB_LIMITER_WBOX 32
+#define TLB_LIMITER_DELAY 63
+#define TLB_LIMITER_RELEASE_DEFAULT_MS 100u
+typedef struct { uint32_t ceiling; uint32_t release_ms; } tlb_limiter_params;
+typedef struct { uint32_t frames, limited, samples, red_last, red_max, peak_in, peak_in_max, reserved; } tlb_limiter_record;      /* 32 bytes */
+int tlb_limiter_enable(tlb_batch *b, const tlb_limiter_params *params);
+int tlb_limiter_device(tlb_batch *b, int16_t *d_pcm_planar, int nframes, tlb_limiter_record *d_records, void *hip_stream);
+int tlb_limiter_host(tlb_batch *b, int16_t *pcm_planar, int nframes, tlb_limiter_record *records);
+int tlb_limiter_reset(tlb_batch *b, int stream);
+uint32_t tlb_limiter_step(uint32_t release_ms, long samplerate);
+int tlb_tick_enable_limiter(tlb_tick *t, const tlb_limiter_params *params);
+const tlb_limiter_record *tlb_tick_limiter(const tlb_tick *t);
+int tlb_tick_limiter_reset(tlb_tick *t, int stream);
+int tlb_node_enable_limiter(tlb_node *nd, const tlb_limiter_params *params);
+const tlb_limiter_record *tlb_node_limiter(const tlb_node *nd, int stream);
+int tlb_node_limiter_reset(tlb_node *nd, int stream);
 
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);

@@ -16,6 +16,7 @@
 #include "mp2_feed_down.h"
 #include "mp2_loudness.h"
 #include "mp2_truepeak.h"
+#include "mp2_limiter.h"
 
 #define TL_HEAD_STRIDE 32             // int32 per list head of the persistent kernels' work lists: one 128-byte line each (9 heads)
 #ifndef TL_MAIN_WPE
@@ -75,4 +76,6 @@ hipError_t tlk_loudness(hipStream_t st, const TlLoudnessArgs &A);
 hipError_t tlk_loudness_programme(hipStream_t st, const uint32_t *hist, const double *tables, TlLoudnessProgramme *out, int nstreams);
 // toolame_truepeak.hip: tl_truepeak_kernel, one wave per stream over the call's frames in order (csrc/mp2_truepeak.h)
 hipError_t tlk_truepeak(hipStream_t st, const TlTruePeakArgs &A);
+// toolame_limiter.hip: tl_limiter_kernel, one wave per stream over the call's frames in order, in place (csrc/mp2_limiter.h)
+hipError_t tlk_limiter(hipStream_t st, const TlLimiterArgs &A);
 size_t tlk_lds_bytes_per_wave(void);          // the largest per-wave LDS block among the kernels

@@ -190,6 +190,7 @@ static int batch_clear_streams(tlb_batch *b, int s0, int n)
 static int meters_clear_streams(tlb_batch *b, int s0, int n)
 {
     if (int rc = loudness_clear_streams(b, s0, n)) return rc;
+    if (int rc = limiter_clear_streams(b, s0, n)) return rc;         // (the limiter's delay line and gains too: its step follows the new rate)
     return truepeak_clear_streams(b, s0, n);
 }
 

@@ -214,6 +214,12 @@ struct tlb_batch {
     uint32_t *d_tp_hist = nullptr;               // [nstreams][2][TL_TP_CARRY / 2] the carried samples of either channel
     int16_t *d_tp_taps = nullptr;                // the committed table [3][TL_TP_TAPS]
     uint32_t tp_ceiling = 0;                     // in units of 2^-30 of full scale
+    // true-peak limiter (tlb_limiter.cpp; csrc/mp2_limiter.h), allocated by tlb_limiter_enable alone: a batch that never enables it has none of it
+    TlLimiterRecord *d_lm_rec = nullptr;         // [nstreams] the record as it is reported
+    uint32_t *d_lm_state = nullptr;              // [nstreams][TL_LM_STATE] the delay line and the carried r and e
+    uint32_t *d_lm_step = nullptr;               // [nstreams] S from the stream's encoder rate
+    int16_t *d_lm_taps = nullptr;                // the true-peak meter's committed table, a copy of the limiter's own
+    tlb_limiter_params lm_params = {0, 0};       // as enabled, the defaults filled in
     TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -279,6 +285,7 @@ int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len
 // when the meter was never enabled
 int loudness_clear_streams(tlb_batch *b, int s0, int n);
 int truepeak_clear_streams(tlb_batch *b, int s0, int n);
+int limiter_clear_streams(tlb_batch *b, int s0, int n);             // (tlb_limiter.cpp: the limiter's, and its steps from the streams' rates as they are now)
 // ... the one body of tlb_*_host: `state`, what the meter's enable made (NULL: never enabled); scratch PCM and records, one launch of the
 // meter's *_device, the records back
 template <class Rec> int meter_host(tlb_batch *b, const void *state, const int16_t *pcm_planar, int nframes, Rec *records,

@@ -144,7 +144,7 @@ int tick_wait_job(Shard &s)
 
 }  // namespace
 
-enum { OPT_SHORT_READS, OPT_MONITOR, OPT_COMPARE, OPT_LOUDNESS, OPT_TRUEPEAK, OPTS };     // in the order a restarted shard gets them back
+enum { OPT_SHORT_READS, OPT_MONITOR, OPT_COMPARE, OPT_LOUDNESS, OPT_TRUEPEAK, OPT_LIMITER, OPTS };     // in the order a restarted shard gets them back
 
 struct tlb_node {
     int plane = TLB_NODE_TICK, nstreams = 0;
@@ -162,7 +162,7 @@ struct tlb_node {
     double deadline_ms = 0;                      // TICK DEADLINE; 0 = none
     // The options of the shards' tick objects (node_options below): on, and what its enable call was given -- each option reads its own
     // member.  A restarted shard's object gets them again (the meters start from zero there).
-    struct Option { bool on = false; int what = 0; tlb_compare_params cparams = {}; uint32_t ceiling = 0; };
+    struct Option { bool on = false; int what = 0; tlb_compare_params cparams = {}; uint32_t ceiling = 0; tlb_limiter_params lparams = {0, 0}; };
     Option opt[OPTS];
     int monitor() const { return opt[OPT_MONITOR].what; }            // TLB_MONITOR_* of every shard's tick object; 0: off
     int listen = -1;                             // tlb_node_monitor_listen(): the node-wide stream listened to; -1: none
@@ -366,6 +366,7 @@ const struct { int (*enable)(tlb_tick *t, const NodeOption &v); int (*reset)(tlb
     /* compare     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_compare(t, &v.cparams); }, nullptr, nullptr},
     /* loudness    */ {[](tlb_tick *t, const NodeOption &) { return tlb_tick_enable_loudness(t); }, tlb_tick_loudness_reset, "loudness_reset"},
     /* true peak   */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_truepeak(t, v.ceiling); }, tlb_tick_truepeak_reset, "truepeak_reset"},
+    /* limiter     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_limiter(t, &v.lparams); }, tlb_tick_limiter_reset, "limiter_reset"},
 };
 // The one body of tlb_node_enable_*: TICK plane only, before the first submit, and `ok`, the option's own precondition.  An option that is
 // on answers TLB_OK to a call that is the `same` as the one that turned it on, TLB_ERR_ARG to another.  Else every shard's tick object is
@@ -696,6 +697,21 @@ int tlb_node_enable_truepeak(tlb_node *nd, uint32_t ceiling)
 }
 const tlb_truepeak_record *tlb_node_truepeak(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_truepeak>(nd, stream); }
 int tlb_node_truepeak_reset(tlb_node *nd, int stream) { return node_meter_reset(nd, OPT_TRUEPEAK, stream); }
+// The true-peak limiter: a second call must name the parameters of the first (0 and the default it selects are the same parameter).
+static tlb_limiter_params limiter_params_of(const tlb_limiter_params *p)
+{
+    tlb_limiter_params v = {p && p->ceiling ? p->ceiling : TLB_TRUEPEAK_CEILING_DEFAULT, p && p->release_ms ? p->release_ms : TLB_LIMITER_RELEASE_DEFAULT_MS};
+    return v;
+}
+int tlb_node_enable_limiter(tlb_node *nd, const tlb_limiter_params *params)
+{
+    NodeOption v; v.lparams = limiter_params_of(params);
+    const tlb_limiter_params p = v.lparams;
+    return node_enable(nd, OPT_LIMITER, v, [p](const tlb_node &) { return p.ceiling >= (1u << 20) && p.ceiling <= (1u << 30) && p.release_ms >= 1u && p.release_ms <= 10000u; },
+                       [p](const NodeOption &was) { return was.lparams.ceiling == p.ceiling && was.lparams.release_ms == p.release_ms; });
+}
+const tlb_limiter_record *tlb_node_limiter(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_limiter>(nd, stream); }
+int tlb_node_limiter_reset(tlb_node *nd, int stream) { return node_meter_reset(nd, OPT_LIMITER, stream); }
 // One stream of the node, or none: the selection goes to the stream's shard and is cleared on the others.  It is a field of the shards'
 // tick objects that their next submit reads; no shard but a late one runs a job between the node's calls, and a late one is left alone
 // (it cannot be the stream's shard: TLB_ERR_LATE).

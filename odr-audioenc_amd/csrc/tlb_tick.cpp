@@ -59,7 +59,7 @@ struct TickLane {
 // tlb_tick_destroy frees the events.  A PCM METER is a record option that also names its batch-level calls: enabled per batch with the
 // object's ceiling (the true-peak meter's; the others ignore it), run on the tick's planar PCM whenever there is new input, reset for one
 // stream or all between ticks.  tick_egress queues the meters in table order; the monitor's and the compare monitor's launches are its own.
-enum { REC_MONITOR, REC_COMPARE, REC_LOUDNESS, REC_TRUEPEAK, RECS };
+enum { REC_MONITOR, REC_COMPARE, REC_LOUDNESS, REC_TRUEPEAK, REC_LIMITER, RECS };
 struct RecordOption {
     size_t size;                                 // of one record
     int ev;                                      // the option behind whose event (ev_rec[ev]) the copy-out runs
@@ -79,6 +79,8 @@ static const RecordOption tick_records[RECS] = {
      tlb_truepeak_enable,
      [](tlb_batch *b, const int16_t *d_pcm, int nframes, void *d_records, void *hip_stream) { return tlb_truepeak_device(b, d_pcm, nframes, (tlb_truepeak_record *)d_records, hip_stream); },
      tlb_truepeak_reset},
+    // the limiter is no meter: tlb_tick_submit queues it AHEAD of the encoder, with its own parameters (tlb_tick_enable_limiter); its reset is a meter's
+    {sizeof(tlb_limiter_record), REC_LIMITER, nullptr, nullptr, tlb_limiter_reset},
 };
 struct TickRecords {
     bool on = false;
@@ -434,6 +436,18 @@ int tlb_tick_loudness_programme(tlb_tick *t, tlb_loudness_programme_record *out)
 int tlb_tick_enable_truepeak(tlb_tick *t, uint32_t ceiling) { return tick_meter_enable(t, REC_TRUEPEAK, ceiling); }
 const tlb_truepeak_record *tlb_tick_truepeak(const tlb_tick *t) { return (const tlb_truepeak_record *)tick_record(t, REC_TRUEPEAK); }
 int tlb_tick_truepeak_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_TRUEPEAK, stream); }
+// The true-peak limiter (tlb_limiter_*): the state of every group's batch is made here, and every submit then queues the limiter on the
+// tick's planar PCM behind the ingest and ahead of the encoder (tlb_tick_submit).  An object that never makes the call allocates and queues
+// nothing new.
+int tlb_tick_enable_limiter(tlb_tick *t, const tlb_limiter_params *params)
+{
+    if (!t || t->finished || t->ticks > 0) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (t->rec[REC_LIMITER].on) return tlb_limiter_enable(t->groups[0].b, params);      // (equal parameters: 0, others: TLB_ERR_ARG)
+    return tick_record_enable(t, REC_LIMITER, [&](TlbMem &, TickGroup &G) { return tlb_limiter_enable(G.b, params); });
+}
+const tlb_limiter_record *tlb_tick_limiter(const tlb_tick *t) { return (const tlb_limiter_record *)tick_record(t, REC_LIMITER); }
+int tlb_tick_limiter_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_LIMITER, stream); }
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)
 {
     if (!t || t->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
@@ -729,7 +743,7 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
             HIPCHK(hipMemcpyAsync(t->h_listen[set], G.d_mpcm + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME, 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost, t->s_out));
     }
     for (int r = 0; r < RECS; r++)                                   // ... and the meters' records, each on an event of its own
-        if (t->rec[r].on && tick_records[r].launch) if (int rc = tick_record_out(t, G, r, set, new_input)) return rc;
+        if (t->rec[r].on && (tick_records[r].launch || r == REC_LIMITER)) if (int rc = tick_record_out(t, G, r, set, new_input)) return rc;
     HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed (the monitor's reads of d_frames included)
     return TLB_OK;
 }
@@ -848,6 +862,9 @@ int tlb_tick_submit(tlb_tick *t)
         if (!rc && t->short_reads) rc = tlb_ingest_device_valid(G.b, G.d_inter, G.d_valid, 1, G.d_pcm, G.d_peaks, t->s_run);
         // (the counters here and not with the silence counter: the next tick's copy-in may overwrite d_valid once ev_ingested has passed)
         if (!rc && t->short_reads) rc = tlb_underrun_device(G.b, G.d_valid, 1, G.d_underrun_ms, G.d_underruns, t->s_run);
+        // the limiter, in place, between the ingest and the encoder: what follows sees the limited PCM; d_peaks stay the input's
+        if (!rc && t->rec[REC_LIMITER].on) rc = tlb_limiter_device(G.b, G.d_pcm, 1, (tlb_limiter_record *)G.d_rec[REC_LIMITER], t->s_run);
+        if (!rc && t->rec[REC_LIMITER].on && hipEventRecord(G.ev_rec[REC_LIMITER], t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc && hipEventRecord(G.ev_ingested, t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc) rc = tlb_launch(G.b, G.d_pcm, 1, t->with_xpad ? G.d_xpad : nullptr, t->with_xpad ? G.d_xl : nullptr, G.d_frames, nullptr, t->s_run, nullptr, G.d_flen);
         if (!rc && hipEventRecord(G.ev_encoded, t->s_run) != hipSuccess) rc = TLB_ERR_HIP;

@@ -321,6 +321,21 @@ def _bind(L):
         L.tlb_node_truepeak.restype = C.c_void_p
         L.tlb_node_truepeak.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_truepeak_reset.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_limiter_device"):          # true-peak limiter
+        L.tlb_limiter_enable.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_limiter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.tlb_limiter_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.tlb_limiter_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_limiter_step.restype = C.c_uint32
+        L.tlb_limiter_step.argtypes = [C.c_uint32, C.c_long]
+        L.tlb_tick_enable_limiter.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_tick_limiter.restype = C.c_void_p
+        L.tlb_tick_limiter.argtypes = [C.c_void_p]
+        L.tlb_tick_limiter_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_enable_limiter.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_node_limiter.restype = C.c_void_p
+        L.tlb_node_limiter.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_limiter_reset.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "tlb_decimate_device"):         # device decimator (down sources)
         L.tlb_decimate_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_decimate_source.restype = C.c_long
@@ -475,6 +490,21 @@ def loudness_scale():
 TRUEPEAK_DTYPE = np.dtype([("frames", np.uint32), ("overs", np.uint32), ("peak", np.uint32, (2,)), ("peak_max", np.uint32, (2,)), ("sample_max", np.uint32, (2,))])
 TRUEPEAK_TAPS = 12
 TRUEPEAK_CEILING_DEFAULT = 956973408                                 # -1 dBTP: llround(2^30 * 10^(-1/20)), TLB_TRUEPEAK_CEILING_DEFAULT
+
+
+# tlb_limiter_record: reductions as 65536 - G (0: unity), peaks in units of 2^-30 of full scale
+LIMITER_DTYPE = np.dtype([("frames", np.uint32), ("limited", np.uint32), ("samples", np.uint32), ("red_last", np.uint32), ("red_max", np.uint32),
+                          ("peak_in", np.uint32), ("peak_in_max", np.uint32), ("reserved", np.uint32)])
+LIMITER_DELAY = 63                                                   # samples the limited PCM is late, TLB_LIMITER_DELAY
+
+
+def limiter_step(release_ms, samplerate):
+    """the gain's recovery per sample in units of 2^-30, max(1, 2^30 * 1000 / (release_ms * samplerate)); 0 ms: the default 100 (tlb_limiter_step; no GPU)"""
+    return int(load_library().tlb_limiter_step(int(release_ms), int(samplerate)))
+
+
+def _limiter_params(ceiling, release_ms):
+    return (C.c_uint32 * 2)(int(ceiling), int(release_ms))
 
 
 def truepeak_dbtp(v):
@@ -845,6 +875,26 @@ class Tick:
         rc = self.L.tlb_tick_truepeak_reset(self.h, int(s))
         if rc:
             raise ToolameError(rc, "tlb_tick_truepeak_reset")
+
+    # -- true-peak limiter (tlb_limiter_device on the tick's planar PCM, between the ingest and the encoder): before the first submit --
+    def enable_limiter(self, ceiling=0, release_ms=0):
+        """ceiling in units of 2^-30 of full scale, 0: TRUEPEAK_CEILING_DEFAULT (-1 dBTP); release_ms 0: 100"""
+        rc = self.L.tlb_tick_enable_limiter(self.h, _limiter_params(ceiling, release_ms))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_limiter")
+
+    @property
+    def limiter(self):
+        """LIMITER_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when not enabled"""
+        p = self.L.tlb_tick_limiter(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * LIMITER_DTYPE.itemsize)).from_address(p), dtype=LIMITER_DTYPE)
+
+    def limiter_reset(self, s=-1):
+        rc = self.L.tlb_tick_limiter_reset(self.h, int(s))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_limiter_reset")
 
     # -- compare monitor (tlb_compare_device behind the decode): after enable_monitor("audio"), before the first submit --
     def enable_compare(self, params=None):
@@ -1446,6 +1496,32 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_truepeak_reset")
 
+    # -- true-peak limiter (tlb_limiter_*): a look-ahead limiter on the PCM the encoder is given, 63 samples late --
+    def enable_limiter(self, ceiling=0, release_ms=0):
+        """allocates the limiter's state on the device (720 bytes per stream); ceiling in units of 2^-30 of full scale, 0: -1 dBTP;
+        release_ms 0: 100; a second call must name the same parameters"""
+        rc = self.L.tlb_limiter_enable(self.h, _limiter_params(ceiling, release_ms))
+        if rc:
+            raise ToolameError(rc, "tlb_limiter_enable")
+
+    def limit(self, pcm_planar):
+        """int16 [nframes, nstreams, 2, 1152] planar PCM as ingest() returns it -> (the limited PCM, LIMITER_DTYPE [nstreams] after these frames)"""
+        a = np.array(pcm_planar, dtype=np.int16, order="C")           # a copy: the call works in place
+        nf = a.shape[0]
+        if a.shape != (nf, self.nstreams, 2, SAMPLES):
+            raise ToolameError(18, f"pcm shape {a.shape}")
+        out = np.zeros(self.nstreams, dtype=LIMITER_DTYPE)
+        rc = self.L.tlb_limiter_host(self.h, a.ctypes.data, nf, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_limiter_host")
+        return a, out
+
+    def limiter_reset(self, s=-1):
+        """one stream's record, delay line and gains back to zero, or every stream's (-1)"""
+        rc = self.L.tlb_limiter_reset(self.h, s)
+        if rc:
+            raise ToolameError(rc, "tlb_limiter_reset")
+
     def ingest(self, interleaved, valid=None):
         """int16 [nframes, nstreams, 2304] interleaved s16le -> (planar [nframes, nstreams, 2, 1152], peaks [.., 2]).
         valid: int32 [nframes, nstreams] sample frames each slot delivers -- a short read is stretched over the frame as the reference
@@ -1922,6 +1998,20 @@ class Node:
 
     def truepeak_reset(self, s=-1):
         self._rc(self.L.tlb_node_truepeak_reset(self.h, int(s)), "tlb_node_truepeak_reset")
+
+    # true-peak limiter (Tick.enable_limiter, per stream with node-wide indices)
+    def enable_limiter(self, ceiling=0, release_ms=0):
+        self._rc(self.L.tlb_node_enable_limiter(self.h, _limiter_params(ceiling, release_ms)), "tlb_node_enable_limiter")
+
+    def limiter(self, s):
+        """the stream's record (a LIMITER_DTYPE scalar, copied) of the step waited for last; None when not enabled and for a broken, late or stale shard"""
+        p = self.L.tlb_node_limiter(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * LIMITER_DTYPE.itemsize).from_address(p), dtype=LIMITER_DTYPE)[0].copy()
+
+    def limiter_reset(self, s=-1):
+        self._rc(self.L.tlb_node_limiter_reset(self.h, int(s)), "tlb_node_limiter_reset")
 
     # compare monitor (Tick.enable_compare, per stream with node-wide indices)
     def enable_compare(self, params=None):

@@ -57,6 +57,9 @@ LIMITS = [
     (re.compile(r"tl_loudness_programme_kernel"), dict(vgpr=168, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # true-peak meter (csrc/toolame_truepeak.hip): a wave per stream, a window of 15 + 14 dwords and three pieces ahead in registers; two rows of 2336 bytes in LDS
     (re.compile(r"tl_truepeak_kernel"), dict(vgpr=128, lds=4672, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # true-peak limiter (csrc/toolame_limiter.hip): the meter's window for the detector, six pieces ahead, 18 gains and 20 delayed dwords in registers (three waves a SIMD);
+    # LDS: two rows of 2432 bytes, the lanes' 19 words, the carried lanes twice, the hand-on values
+    (re.compile(r"tl_limiter_kernel"), dict(vgpr=168, lds=11152, vgpr_spill=0, sgpr_spill=0, scratch=0)),
 ]
 
 

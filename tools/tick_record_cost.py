@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """What a record option adds to a tick, and what this commit costs an object with and without it, on the GPU.
 
-    python tools/tick_record_cost.py --option monitor|compare|loudness|truepeak|all [--streams 16384] [--psy 3] [--ticks 200] [--rounds 5]
-                                     [--parent-lib PATH] [--out profiles/tick_records.txt]
+    python tools/tick_record_cost.py --option monitor|compare|loudness|truepeak|limiter|all [--streams 16384] [--psy 3] [--ticks 200] [--rounds 5]
+                                     [--hot] [--parent-lib PATH] [--out profiles/tick_records.txt]
 
 The record options of a tick object (csrc/tlb_tick.cpp, tick_records): `monitor` (tlb_tick_enable_monitor, TLB_MONITOR_AUDIO), `compare`
-(tlb_tick_enable_compare with the default params; its `off` legs have the AUDIO monitor it needs), `loudness`, `truepeak`, and `all` four.
+(tlb_tick_enable_compare with the default params; its `off` legs have the AUDIO monitor it needs), `loudness`, `truepeak`, and `all` four; and `limiter`
+(tlb_tick_enable_limiter, the defaults: it runs AHEAD of the encoder; --hot clips the input 30 dB up, so that its active path runs on every frame -- the encoder then
+encodes another signal in every leg, so hot legs compare with hot legs only).
 One tick object per leg -- `parent` and `parent-on` (--parent-lib: a libtoolame_dab_hip.so built from the parent commit, loaded beside this
 one; `parent-on` only when that library has the option's entry points), `off` (this library, the option never enabled) and `on` -- all
 48 kHz stereo 128 kbps, egress EDI AF, the legs interleaved round by round in one process on one box.  Every round runs `ticks` ticks of
@@ -25,13 +27,13 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 # option -> (what its `off` legs enable, what its `on` legs enable on top), by the names below
-OPTIONS = {"monitor": ((), ("monitor",)), "compare": (("monitor",), ("compare",)), "loudness": ((), ("loudness",)), "truepeak": ((), ("truepeak",)),
+OPTIONS = {"monitor": ((), ("monitor",)), "compare": (("monitor",), ("compare",)), "loudness": ((), ("loudness",)), "truepeak": ((), ("truepeak",)), "limiter": ((), ("limiter",)),
            "all": ((), ("monitor", "compare", "loudness", "truepeak"))}
 ENABLE = {"monitor": lambda t: t.enable_monitor("audio"), "compare": lambda t: t.enable_compare(), "loudness": lambda t: t.enable_loudness(),
-          "truepeak": lambda t: t.enable_truepeak()}
+          "truepeak": lambda t: t.enable_truepeak(), "limiter": lambda t: t.enable_limiter()}
 # ... and a count from the option's records, to show that it ran
 MEASURED = {"monitor": lambda t: t.monitor["frames"], "compare": lambda t: t.compare["frames_compared"], "loudness": lambda t: t.loudness["frames"],
-            "truepeak": lambda t: t.truepeak["frames"]}
+            "truepeak": lambda t: t.truepeak["frames"], "limiter": lambda t: t.limiter["frames"]}
 
 
 def fmt(v):
@@ -46,6 +48,7 @@ def main():
     ap.add_argument("--psy", type=int, default=3)
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--hot", action="store_true")
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "tick_records.txt"))
     args = ap.parse_args()
@@ -60,6 +63,8 @@ def main():
     cfg = [M.StreamConfig(samplerate=48000, mode="s", bitrate=128, psy_model=args.psy)] * ns
     nd = min(ns, 1024)
     pcm0 = np.stack([gen_pcm(s, 0, 0, 1)[0].T.reshape(-1) for s in range(nd)])
+    if args.hot:
+        pcm0 = np.clip(pcm0.astype(np.int64) * 32, -32768, 32767).astype(np.int16)
     legs, why = {}, {}                                               # leg -> (library, what it enables)
     if args.parent_lib and Path(args.parent_lib).exists():
         parent = TL._bind(C.CDLL(str(Path(args.parent_lib).resolve())))
@@ -96,10 +101,12 @@ def main():
             out[name]["median_ms"].append(float(np.median(dev)))
             out[name]["max_ms"].append(float(dev.max()))
     measured = {o: int(MEASURED[o](objs["on"]).sum()) for o in extra}
+    if "limiter" in extra:
+        measured["limiter: limited"] = int(objs["on"].limiter["limited"].sum())
     for t in objs.values():
         t.close()
     lines = ["tools/tick_record_cost.py --option %s on %s: %d streams of 48 kHz stereo 128 kbps psy %d, EDI AF, %d ticks of tlb_tick_run per round" %
-             (args.option, torch.cuda.get_device_name(0), ns, args.psy, args.ticks),
+             (args.option + (" --hot" if args.hot else ""), torch.cuda.get_device_name(0), ns, args.psy, args.ticks),
              "and leg, %d rounds interleaved in one process.  Per leg: the rounds' medians and maxima of tlb_tick_last_ms (device clock).  A 48 kHz frame" % args.rounds,
              "lasts 24 ms.  The `off` legs enable: %s; the `on` legs on top of it: %s." % (", ".join(base) or "nothing", ", ".join(extra))]
     for name in ("parent", "parent-on", "off", "on"):
