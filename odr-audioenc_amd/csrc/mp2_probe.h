@@ -6,6 +6,7 @@
 // so the one text runs on the device (csrc/toolame_probe.hip, linked into the fault-injection TEST library alone) and with -DTL_EMULATE on
 // the host (tests/emu/mp2_probe_emu.cpp).  tests/probelib.py holds the argument sets and the oracles, tests/test_probe_emu.py compares the
 // emulation with glibc and with the oracles, tests/test_probe_gpu.py the device with the emulation.  The product library has none of this.
+// The third family -- the shared stage helpers of mp2_dbsum.h, one by one -- has a header of its own, mp2_probe_stage.h, included at the end.
 #pragma once
 #include "mp2_wave.h"
 
@@ -245,3 +246,6 @@ TL_FN void tl_probe_wave_unit(int prim, const uint64_t *in, const uint64_t *in2,
     }
     TL_LANES_BEGIN out[lane] = L(o); TL_LANES_END
 }
+
+// ---- (c) the stage helpers of mp2_dbsum.h: mp2_probe_stage.h
+#include "mp2_probe_stage.h"

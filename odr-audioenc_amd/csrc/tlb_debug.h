@@ -35,6 +35,11 @@ int tlb_debug_alloc_fail_next(int nth);
  * form's stated domain (tlp_in_domain): checked on the host before anything is queued, so nothing out of domain reaches the device. */
 int tlb_debug_probe_libm(int form, int table, long n, const double *a, const double *b, double *r0, double *r1);
 int tlb_debug_probe_wave(int prim, int nwaves, const void *in, const void *in2, void *out);
+/* The third family (csrc/mp2_probe_stage.h): ONE group of the stage helpers of csrc/mp2_dbsum.h (form: TLS_ADD_DB ...) over n lane-arguments or n cases of a
+ * wave; the arrays and their layouts are stated at the enum, an array a form does not have may be NULL.  HOST pointers, the library's memory owner, one
+ * launch, waited for, copied out, like the two above.  TLB_ERR_ARG for an unknown form, n <= 0, a missing pointer and for ANY argument or case outside
+ * the form's stated domain (tls_in_domain) -- checked on the host before anything is queued: the helpers make LDS indexes from counts, rows and lengths. */
+int tlb_debug_probe_stage(int form, long n, const void *in0, const void *in1, const void *in2, void *out0, void *out1);
 #ifdef __cplusplus
 }
 #endif

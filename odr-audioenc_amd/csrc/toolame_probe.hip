@@ -1,9 +1,11 @@
 // toolame_probe.hip -- TEST BUILDS ONLY: the probe kernels over the bodies of mp2_probe.h and their C entry points (csrc/tlb_debug.h).
 // A unit of the fault-injection TEST library alone (csrc/Makefile: PROBE_UNITS, the kernels' own flags -- they are what is under test);
 // the product library links none of it.  Nothing here provokes anything: every argument is checked against its form's stated domain on
-// the host before a byte is copied, and a case of the wave probe against what its primitive requires of a lane number.
+// the host before a byte is copied, a case of the wave probe against what its primitive requires of a lane number, and every argument
+// and case of the stage probe against the domain mp2_probe_stage.h states (counts, row ranges, field lengths: all that becomes an LDS index).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <vector>
 #include "mp2_host.h"
 #include "mp2_probe.h"
 #include "tlb_debug.h"
@@ -28,6 +30,29 @@ __global__ void __launch_bounds__(256) tl_probe_wave_kernel(int prim, int nwaves
     const int wave = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * 4 + wave;
     if (w >= nwaves) return;                                              // (wave-uniform; no workgroup barrier below)
     tl_probe_wave_unit(prim, in + (size_t)w * 64 * tlp_in_words(prim), in2 + (size_t)w * 64, out + (size_t)w * 64 * tlp_out_words(prim), pair[wave]);
+}
+
+// the stage helpers (mp2_probe_stage.h): 256 threads = four waves, each with its own TlStageLds; the dB-sum table and the scalefactor table are copied
+// into the workgroup's LDS as the model phase and the encode prologue keep them.  Lane forms: 64 consecutive arguments a wave; case forms: one case a wave.
+__global__ void __launch_bounds__(256) tl_probe_stage_kernel(int form, long n, const double *dblog, const double *sftab, const void *in0, const void *in1,
+                                                             const void *in2, void *out0, void *out1)
+{
+    __shared__ __attribute__((aligned(16))) double dbt[1002];
+    __shared__ __attribute__((aligned(16))) double sfl[64];
+    __shared__ TlStageLds lds[4];
+    for (int i = (int)threadIdx.x; i < 1002; i += 256) dbt[i] = dblog[i];
+    if (threadIdx.x < 64) sfl[threadIdx.x] = sftab[threadIdx.x];
+    __syncthreads();
+    const int wave = (int)(threadIdx.x >> 6);
+    if (form < TLS_LANE_FORMS) {
+        const long i0 = (long)blockIdx.x * 256 + 64 * wave;
+        if (i0 >= n) return;                                              // (wave-uniform; no workgroup barrier below)
+        tl_probe_stage_lanes(form, lds[wave], dbt, sfl, i0, n, in0, in1, in2, out0, out1);
+    } else {
+        const long k = (long)blockIdx.x * 4 + wave;
+        if (k >= n) return;
+        tl_probe_stage_case(form, lds[wave], k, in0, in1, in2, out0, out1);
+    }
 }
 
 #ifdef TLB_FAULT_INJECT
@@ -72,6 +97,41 @@ extern "C" int tlb_debug_probe_wave(int prim, int nwaves, const void *in, const 
     TLP_HIP(hipGetLastError());
     TLP_HIP(hipDeviceSynchronize());
     TLP_HIP(hipMemcpy(out, dout, nw * ow * 8, hipMemcpyDeviceToHost));
+    return TLB_OK;
+}
+
+extern "C" int tlb_debug_probe_stage(int form, long n, const void *in0, const void *in1, const void *in2, void *out0, void *out1)
+{
+    if (form < 0 || form >= TLS_NFORMS || n <= 0 || n > tls_max_n(form)) return TLB_ERR_ARG;
+    size_t by[5];
+    tls_bytes(form, n, by);
+    const void *hin[3] = {in0, in1, in2};
+    void *hout[2] = {out0, out1};
+    for (int k = 0; k < 3; k++) if (by[k] && !hin[k]) return TLB_ERR_ARG;
+    for (int k = 0; k < 2; k++) if (by[3 + k] && !hout[k]) return TLB_ERR_ARG;
+    if (!tls_in_domain(form, n, in0, in1, in2)) return TLB_ERR_ARG;
+    static TlTables T;                                                    // the kernels' own tables (mp2_host.cpp), built once
+    static bool built = false;
+    if (!built) { tl_build_tables(&T); built = true; }
+    std::vector<double> recip;
+    if (form == TLS_DIV_BY) {                                             // the reciprocal the way the host makes TlConfig::p1_linerw
+        recip.resize((size_t)n);
+        for (long i = 0; i < n; i++) recip[(size_t)i] = 1.0 / ((const double *)in1)[i];
+        hin[2] = recip.data(); by[2] = 8 * (size_t)n;
+    }
+    TlbMem m;
+    double *ddb = m.scratch<double>(1002), *dsf = m.scratch<double>(64);
+    m.upload(ddb, T.dblog, 1002 * sizeof(double));
+    m.upload(dsf, T.shared.scalefactor, 64 * sizeof(double));
+    char *din[3], *dout[2];
+    for (int k = 0; k < 3; k++) { din[k] = m.dev<char>(by[k]); if (by[k]) m.upload(din[k], hin[k], by[k]); }
+    for (int k = 0; k < 2; k++) dout[k] = m.dev<char>(by[3 + k]);
+    if (!m.settle()) return TLB_ERR_HIP;
+    const long per = form < TLS_LANE_FORMS ? 256 : 4;
+    tl_probe_stage_kernel<<<dim3((unsigned)((n + per - 1) / per)), dim3(256), 0, 0>>>(form, n, ddb, dsf, din[0], din[1], din[2], dout[0], dout[1]);
+    TLP_HIP(hipGetLastError());
+    TLP_HIP(hipDeviceSynchronize());
+    for (int k = 0; k < 2; k++) if (by[3 + k]) TLP_HIP(hipMemcpy(hout[k], dout[k], by[3 + k], hipMemcpyDeviceToHost));
     return TLB_OK;
 }
 #endif

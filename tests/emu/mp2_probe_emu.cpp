@@ -1,5 +1,6 @@
-// TEST-ONLY: csrc/mp2_probe.h as a lane loop on the host (-DTL_EMULATE): the host halves of tl_libm.h and of mp2_wave.h's primitives, called
-// one by one through the same text the probe kernels run (csrc/toolame_probe.hip).  Built at first use by tests/probelib.py.
+// TEST-ONLY: csrc/mp2_probe.h as a lane loop on the host (-DTL_EMULATE): the host halves of tl_libm.h and of mp2_wave.h's primitives, and the stage
+// helpers of mp2_dbsum.h (csrc/mp2_probe_stage.h), called one by one through the same text the probe kernels run (csrc/toolame_probe.hip).
+// Built at first use by tests/probelib.py, together with csrc/mp2_host.cpp (the kernels' own tables).
 #define TL_EMULATE 1
 #include <math.h>
 #include <stdlib.h>
@@ -40,5 +41,46 @@ __attribute__((visibility("default"))) int probe_wave(int prim, int nwaves, cons
     for (int w = 0; w < nwaves; w++) tl_probe_wave_unit(prim, hin + w * iw, two ? hin2 + (size_t)w * 64 : zero, (uint64_t *)out + w * ow, pair);
     return 0;
 }
+
+// as tlb_debug_probe_stage (csrc/tlb_debug.h): 0, or 18 (TLB_ERR_ARG) for what that call refuses
+__attribute__((visibility("default"))) int probe_stage(int form, long n, const void *in0, const void *in1, const void *in2, void *out0, void *out1)
+{
+    if (form < 0 || form >= TLS_NFORMS || n <= 0 || n > tls_max_n(form)) return 18;
+    size_t by[5];
+    tls_bytes(form, n, by);
+    const void *hin[3] = {in0, in1, in2};
+    void *hout[2] = {out0, out1};
+    for (int k = 0; k < 3; k++) if (by[k] && !hin[k]) return 18;
+    for (int k = 0; k < 2; k++) if (by[3 + k] && !hout[k]) return 18;
+    if (!tls_in_domain(form, n, in0, in1, in2)) return 18;
+    static TlTables T;
+    static bool built = false;
+    if (!built) { tl_build_tables(&T); built = true; }
+    std::vector<double> recip;
+    if (form == TLS_DIV_BY) {
+        recip.resize((size_t)n);
+        for (long i = 0; i < n; i++) recip[(size_t)i] = 1.0 / ((const double *)in1)[i];
+        in2 = recip.data();
+    }
+    static TlStageLds w;
+    if (form < TLS_LANE_FORMS) for (long i0 = 0; i0 < n; i0 += 64) tl_probe_stage_lanes(form, w, T.dblog, T.shared.scalefactor, i0, n, in0, in1, in2, out0, out1);
+    else for (long k = 0; k < n; k++) tl_probe_stage_case(form, w, k, in0, in1, in2, out0, out1);
+    return 0;
+}
+
+// The bark values of the library's own threshold tables (csrc/mp2_host.cpp tl_build_config): psy 1 the rows of TlConfig::p1_bark, psy 3 the rows
+// TlConfig::p3_subset picks of p3_bark.  out[136]; returns the number of rows, or -1 for a rate or model the library refuses.
+__attribute__((visibility("default"))) int probe_bark_table(int psy, long samplerate, double *out)
+{
+    static TlConfig C;
+    if ((psy != 1 && psy != 3) || tl_build_config(&C, samplerate, 'm', samplerate < 32000 ? 32 : 64, psy, 0) != TL_OK) return -1;
+    if (psy == 1) { for (int i = 0; i < C.p1_sub; i++) out[i] = C.p1_bark[i]; return C.p1_sub; }
+    for (int i = 0; i < 136; i++) out[i] = C.p3_bark[C.p3_subset[i]];
+    return 136;
+}
+// the dB-sum table the probe's kernels read (TlTables::dblog[0..1001]: psycho_1.c:170-178 and its two closing entries) -- data for the oracles
+__attribute__((visibility("default"))) void probe_dbtable(double *out) { static TlTables T; tl_build_tables(&T); for (int i = 0; i < 1002; i++) out[i] = T.dblog[i]; }
+// the scalefactor table the probe's kernels read (TlTables::shared)
+__attribute__((visibility("default"))) void probe_scalefactors(double *out) { static TlTables T; tl_build_tables(&T); for (int i = 0; i < 64; i++) out[i] = T.shared.scalefactor[i]; }
 
 }

@@ -1,5 +1,6 @@
 """Support for tests/test_probe_emu.py and tests/test_probe_gpu.py: the argument sets, the references and the bindings of the probe
-(csrc/mp2_probe.h: every device-path form of csrc/tl_libm.h and every cross-lane primitive of csrc/mp2_wave.h, one by one).
+(csrc/mp2_probe.h: every device-path form of csrc/tl_libm.h and every cross-lane primitive of csrc/mp2_wave.h, one by one; csrc/mp2_probe_stage.h:
+every shared stage helper of csrc/mp2_dbsum.h -- its sets and oracles are the last part of this file).
 
 * libm forms: 2^20 arguments per form from numpy.random.default_rng, the distributions of tools/libm_agree.cpp worker() restated inside
   each form's stated domain (the encoder's ranges, every binade of the domain, the neighbourhoods of the routines' branch points), plus
@@ -65,9 +66,10 @@ def _build(name, args):
 
 
 def emu():
-    """tests/emu/mp2_probe_emu.cpp, the flags of the other emulations (tests/loudnesslib.py GXX)"""
-    L = _build("libmp2probeemu.so", GXX + ["-shared", str(ROOT / "tests" / "emu" / "mp2_probe_emu.cpp"), "-lm"])
+    """tests/emu/mp2_probe_emu.cpp with the library's table builder (csrc/mp2_host.cpp), the flags of the other emulations (tests/loudnesslib.py GXX)"""
+    L = _build("libmp2probeemu.so", GXX + ["-shared", str(ROOT / "tests" / "emu" / "mp2_probe_emu.cpp"), str(ROOT / "odr-audioenc_amd" / "csrc" / "mp2_host.cpp"), "-lm"])
     bind_probe(L.probe_libm, L.probe_wave)
+    bind_stage(L.probe_stage)
     return L
 
 
@@ -700,9 +702,10 @@ OUTSIDE2 = {
 }
 
 
-def check_argument_checks(libm_fn, wave_fn):
+def check_argument_checks(libm_fn, wave_fn, stage_fn):
     """what the probe refuses with TLB_ERR_ARG, the same for the emulation's entry and the device's (both test files call this):
     an argument outside the form's domain -- alone, or last among good ones --, an unknown form, n = 0, a missing pointer"""
+    check_stage_argument_checks(stage_fn)
     good = np.array([1.5, 2.5, 3.5])
     for form, xs in OUTSIDE.items():
         for x in xs:
@@ -735,3 +738,828 @@ def check_argument_checks(libm_fn, wave_fn):
     assert rc == 0 and r0.tolist() == [2.0, 1.5, 1e5]
     rc, out = run_wave(wave_fn, "wave_min_u64", np.arange(128, dtype=np.uint64).reshape(2, 64) + np.uint64(5))
     assert rc == 0 and (out[0] == 5).all() and (out[1] == 69).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The third family: the stage helpers of csrc/mp2_dbsum.h (csrc/mp2_probe_stage.h).  Argument sets (fixed seeds) and oracles.  The oracles are
+# written from what the comments of mp2_dbsum.h state, in the branchy shape of the model's description; the assertions are on raw bits and
+# integers, nothing has a tolerance.  Tables (the dB-sum table, the scalefactors, the bark rows) are data read through the emulation library.
+STAGE = {"add_db": 0, "mask": 1, "mnr_key": 2, "sf_index": 3, "div_by": 4, "spans": 5, "min_rows": 6, "bits": 7}
+STAGE_NFORMS = 8
+STAGE_TESTS = ("add_db", "mask", "spans", "min_rows", "mnr_key", "sf_index", "div_by", "put_bits", "put_bits48")
+NSTAGE_RANDOM = 1 << 18
+TL_DBMIN = -200.0
+FAR_HI = 0xC0F00000
+MASKER_MAX, LIST, ROWS, FIELDS, FRAME_WORDS, FRAME_BITS = 128, 192, 136, 6, 434, 1728 * 8
+RATES6 = (48000, 44100, 32000, 24000, 22050, 16000)
+I32 = np.int32
+
+
+def bind_stage(fn):
+    fn.argtypes = [C.c_int, C.c_long] + [C.c_void_p] * 5
+
+
+def _emu_tables():
+    """the library's own tables through the emulation: dblog[0..1001], the scalefactors, the bark rows of psy 1 and psy 3 at the six rates"""
+    if "tables" not in _built:
+        L = emu()
+        db, sf = np.empty(1002), np.empty(64)
+        L.probe_dbtable(_ptr(db))
+        L.probe_scalefactors(_ptr(sf))
+        barks = {}
+        for psy in (1, 3):
+            for fs in RATES6:
+                buf = np.empty(136)
+                L.probe_bark_table.argtypes = [C.c_int, C.c_long, C.c_void_p]
+                n = L.probe_bark_table(psy, fs, _ptr(buf))
+                assert n > 100, (psy, fs, n)
+                barks[(psy, fs)] = buf[:n].copy()
+        _built["tables"] = (db, sf, barks)
+    return _built["tables"]
+
+
+def _near(x, k):
+    """x and its k neighbours on either side"""
+    out = [np.asarray(x, dtype=np.float64)]
+    lo = hi = out[0]
+    for _ in range(k):
+        lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+        out += [lo, hi]
+    return np.concatenate([np.ravel(v) for v in out])
+
+
+def _bits_report(name, what, i, args, got, want):
+    h = lambda v: hex(int(np.asarray(v).view(U64 if np.asarray(v).dtype.itemsize == 8 else np.uint32))) if np.asarray(v).dtype.kind == "f" else hex(int(v))
+    return "%s, %s: argument %d = %s -> %s, want %s" % (name, what, i, ", ".join("%s=%s" % (k, (float(v).hex() if isinstance(v, float) else v)) for k, v in args.items()), h(got), h(want))
+
+
+# ---- 1. dB sums
+def add_db_oracle(a, b, tab):
+    """psycho_1.c:180-205 as the comment of tl_add_db states it: the larger operand beyond +-990, else the operand chosen by the sign of the
+    truncated index plus the table entry"""
+    f = 10.0 * (a - b)
+    i = np.trunc(np.clip(f, -991.0, 991.0)).astype(np.int64)
+    mid = np.where(i >= 0, a + tab[np.clip(i, 0, 990)], b + tab[np.clip(-i, 0, 990)])
+    return np.where(f > 990.0, a, np.where(f < -990.0, b, mid))
+
+
+def far_levels(n, seed=5):
+    """levels whose high word is 0xC0F00000: what a masking term out of reach becomes"""
+    r = np.random.default_rng(seed)
+    lo = np.concatenate([[0, 1, 0xffffffff, 0x80000000], r.integers(0, 1 << 32, n - 4, dtype=U64)]).astype(U64)
+    return _u2d((U64(FAR_HI) << U64(32)) | lo)
+
+
+def add_db_set():
+    """-> dict(a, b, named: {name: slice}, far: indices where one operand is the far level (the sum must be the other operand's bits))"""
+    if "add_db" in _args:
+        return _args["add_db"]
+    A, B, named = [], [], {}
+
+    def add(name, a, b):
+        a, b = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64))
+        s = sum(len(x) for x in A)
+        A.append(np.ravel(a).copy()); B.append(np.ravel(b).copy())
+        named[name] = slice(s, s + a.size)
+
+    lev = np.arange(-2000, 1201) / 10.0                                    # -200 .. 120
+    add("equal operands", lev, lev)
+    add("b = TL_DBMIN", lev, TL_DBMIN)
+    add("a = TL_DBMIN", TL_DBMIN, lev)
+    d = np.concatenate([_near(k / 10.0, 4) for k in range(-991, 992)])     # 10 (a - b): every integer in [-991, 991] and the doubles on both sides of it
+    add("10 (a - b) at every integer, a - 0", d, 0.0)
+    add("10 (a - b) at every integer, 0 - b", 0.0, -d)
+    f = 10.0 * d
+    ks = np.arange(-991, 992)
+    assert np.isin(ks[np.abs(ks) % 2 == 0], f).mean() > 0.9 and all(np.isin([-991.0, -990.0, -1.0, 0.0, 1.0, 990.0, 991.0], f))
+    for k in (-990, -1, 1, 990):                                           # ... each cut has arguments strictly on both sides
+        assert (f[(f > k - 1e-9) & (f < k)].size and f[(f > k) & (f < k + 1e-9)].size)
+    g = np.random.default_rng(41)
+    i, j = g.integers(-2000, 1201, 20000), g.integers(-1000, 1001, 20000)
+    add("0.1 dB grid", i * 0.1, np.clip(i - j, -2000, 1200) * 0.1)
+    far = far_levels(512)
+    other = np.resize(np.concatenate([[TL_DBMIN, -100.0, -0.0625, 0.0, -0.0, 15.0, 40.0, 96.3, 110.0], lev[::97]]), 512)
+    add("far level as b", other, far)
+    add("far level as a", far, other)
+    z = np.array([0.0, -0.0, 0.0, -0.0, 0.0, -0.0, 0.05, 0.05, -0.05, -0.05, 0.0, -0.0, 0.0, -0.0])
+    zb = np.array([0.0, -0.0, -0.0, 0.0, 0.05, 0.05, 0.0, -0.0, 0.0, -0.0, -0.05, -0.05, 99.5, -99.5])
+    add("signed zeros", z, zb)
+    d99 = np.concatenate([_near(99.0, 4), _near(-99.0, 4)])
+    for x in (-120.5, -50.25, 0.0, 60.125):
+        add("differences around 99 dB at %g" % x, x, x - d99)
+        add("differences around 99 dB below %g" % x, x - d99, x)
+    nmade = sum(len(x) for x in A)
+    add("random", g.uniform(-200.0, 120.0, NSTAGE_RANDOM), g.uniform(-200.0, 120.0, NSTAGE_RANDOM))
+    S = dict(a=np.concatenate(A), b=np.concatenate(B), named=named, constructed=nmade, random=NSTAGE_RANDOM)
+    S["far"] = (named["far level as b"], named["far level as a"])
+    _args["add_db"] = S
+    return S
+
+
+def add_db_check(S, out0, out1, tab=None, ref=None):
+    """out0 / out1 of a run against the oracle (tab) or another run's outputs (ref) -> None or the first difference; the three forms agree"""
+    a, b = S["a"], S["b"]
+    n = a.size
+    j = np.arange(n) ^ 1
+    j = np.where(j < n, j, np.arange(n))
+    if ref is not None:
+        w0, w1 = ref
+    else:
+        w = add_db_oracle(a, b, tab)
+        w0, w1 = w, np.stack([w, w[j], w, w[j]], axis=1).ravel()
+    bad = same_bits(out0, w0)
+    if bad.size:
+        return _bits_report("tl_add_db", _name_of(S, bad[0]), bad[0], dict(a=float(a[bad[0]]), b=float(b[bad[0]])), out0[bad[0]], w0[bad[0]]) + " (%d differ)" % bad.size
+    bad = same_bits(out1, w1)
+    if bad.size:
+        i, k = divmod(int(bad[0]), 4)
+        p = int(j[i]) if k & 1 else i
+        return _bits_report(("tl_add_db2", "tl_add_db2_k")[k >> 1], _name_of(S, p) + (" (second pair)" if k & 1 else ""), p, dict(a=float(a[p]), b=float(b[p])), out1[bad[0]], w1[bad[0]]) + " (%d differ)" % bad.size
+    o = out1.reshape(n, 4)
+    if same_bits(o[:, 0], out0).size or same_bits(o[:, 2], out0).size:
+        return "the three dB-sum forms disagree with one another"
+    return None
+
+
+def _name_of(S, i):
+    for k, s in S["named"].items():
+        if s.start <= i < s.stop:
+            return "'%s'" % k
+    return "?"
+
+
+# ---- 2. masking terms
+MASK_LEVELS = (TL_DBMIN, -100.0, -0.0625, 0.0, 15.0, 40.0, 96.3, 110.0)
+MASK_X0 = (TL_DBMIN, -60.3, 0.0, 35.7, 96.3)
+
+
+def mask_set():
+    """-> dict(x, mb, aux [n, 4] = (line bark, x0, tonal, live), named)"""
+    if "mask" in _args:
+        return _args["mask"]
+    _, _, barks = _emu_tables()
+    pairs = []
+    for key, t in barks.items():                                           # EVERY ordered pair (masker bark, line bark) of every table
+        m, l = np.meshgrid(t, t, indexing="ij")
+        pairs.append(np.stack([m.ravel(), l.ravel()], axis=1))
+    pairs = np.unique(np.concatenate(pairs).view(U64), axis=0).view(np.float64)       # (tables share rows: each distinct pair once)
+    npairs = pairs.shape[0]
+    assert npairs > 100000
+    X, MB, AUX, named = [], [], [], {}
+
+    def add(name, x, mb, lb, x0, tonal, live):
+        x, mb, lb, x0, tonal, live = (np.ravel(v).astype(np.float64) for v in np.broadcast_arrays(x, mb, lb, x0, tonal, live))
+        s = sum(len(v) for v in X)
+        X.append(x); MB.append(mb); AUX.append(np.stack([lb, x0, tonal, live], axis=1))
+        named[name] = slice(s, s + x.size)
+
+    lv = np.array(MASK_LEVELS)
+    pi, li = np.meshgrid(np.arange(npairs), np.arange(8), indexing="ij")
+    pi, li = pi.ravel(), li.ravel()
+    add("every bark pair of the threshold tables x 8 levels", lv[li], pairs[pi, 0], pairs[pi, 1], np.array(MASK_X0)[(pi + li) % 5], (pi + li) & 1, ((pi >> 1) + li) & 1 ^ 1)
+    # distances of exactly 0, +-1, -3, 8 and the doubles beside them: dz = line - masker, exact with one of the two at 0; and around 12 bark
+    mbs, lbs = [], []
+    for dz in (0.0, 1.0, -1.0, -3.0, 8.0):
+        v = _near(abs(dz), 3)
+        v = v[v >= 0]
+        if dz >= 0:
+            mbs.append(np.zeros(v.size)); lbs.append(v)
+        if dz <= 0:
+            mbs.append(v); lbs.append(np.zeros(v.size))
+        w = _near(12.0 + dz, 3)
+        mbs.append(np.full(w.size, 12.0)); lbs.append(w)
+        mbs.append(w); lbs.append(np.full(w.size, 12.0 + 2 * dz) if 0 <= 12.0 + 2 * dz <= 32 else np.full(w.size, 12.0))
+    mbs, lbs = np.concatenate(mbs), np.concatenate(lbs)
+    g4 = np.array(np.meshgrid(np.arange(mbs.size), np.arange(8), [0, 1], [0, 1], indexing="ij")).reshape(4, -1)
+    add("distances of exactly 0, +-1, -3, 8 and the doubles beside them", lv[g4[1]], mbs[g4[0]], lbs[g4[0]], np.array(MASK_X0)[(g4[0] + g4[1]) % 5], g4[2], g4[3])
+    nmade = sum(len(v) for v in X)
+    g = np.random.default_rng(42)
+    n = NSTAGE_RANDOM
+    add("random", g.uniform(-200.0, 120.0, n), g.uniform(0.0, 25.5, n), g.uniform(0.0, 25.5, n), g.uniform(-200.0, 120.0, n), g.integers(0, 2, n), g.integers(0, 2, n))
+    S = dict(x=np.concatenate(X), mb=np.concatenate(MB), aux=np.ascontiguousarray(np.concatenate(AUX)), named=named, constructed=nmade, random=n)
+    _args["mask"] = S
+    return S
+
+
+def mask_oracle(S, tab):
+    """-> (record [n, 5], term [n], in reach [n], step [n]): av as written, the four-piece masking function, the reach test -3 <= dz < 8"""
+    x, mb = S["x"], S["mb"]
+    lb, x0, tonal = S["aux"][:, 0], S["aux"][:, 1], S["aux"][:, 2] != 0
+    av = np.where(tonal, -1.525 - 0.275 * mb - 4.5 + x, -1.525 - 0.175 * mb - 0.5 + x)
+    g, nn = 0.4 * x + 6, 17 - 0.15 * x
+    dz = lb - mb
+    vf = np.where(dz < -1, 17 * (dz + 1) - g, np.where(dz < 0, g * dz, np.where(dz < 1, -17 * dz, -(dz - 1) * nn - 17)))
+    term = av + vf
+    reach = (dz >= -3) & (dz < 8)
+    step = np.where(reach, add_db_oracle(x0, term, tab), x0)
+    return np.stack([mb, av, g, np.full(x.size, 17.0), nn], axis=1), term, reach, step
+
+
+def mask_check(S, out0, out1, tab):
+    rec, term, reach, step = mask_oracle(S, tab)
+    arg = lambda i: dict(x=float(S["x"][i]), masker_bark=float(S["mb"][i]), line_bark=float(S["aux"][i, 0]), x0=float(S["aux"][i, 1]), tonal=int(S["aux"][i, 2]), live=int(S["aux"][i, 3]))
+    o0, o1 = out0.reshape(-1, 8), out1.reshape(-1, 5)
+    for k, name in enumerate(("bark", "av", "g", "c17", "n")):
+        bad = same_bits(o1[:, k], rec[:, k])
+        if bad.size:
+            return _bits_report("tl_masker_consts." + name, _name_of(S, bad[0]), bad[0], arg(bad[0]), o1[bad[0], k], rec[bad[0], k]) + " (%d differ)" % bad.size
+    live = S["aux"][:, 3] != 0
+    for k, name in enumerate(("tl_mask_term", "tl_mask_term (other live)", "tl_mask_term_k", "tl_mask_term_k (other live)", "tl_mask_term_w", "tl_mask_term_w (other live)")):
+        on = reach & (live if k % 2 == 0 else ~live)
+        got = o0[:, k].view(U64)
+        bad = np.flatnonzero(np.where(on, got != term.view(U64), (got >> U64(32)) != U64(FAR_HI)))
+        if bad.size:
+            i = bad[0]
+            return _bits_report(name, _name_of(S, i) + (" in reach" if on[i] else " out of reach or not live: high word 0xC0F00000"), i, arg(i), o0[i, k], term[i]) + " (%d differ)" % bad.size
+    bad = same_bits(o0[:, 6], step)
+    if bad.size:
+        return _bits_report("tl_mask_step", _name_of(S, bad[0]), bad[0], arg(bad[0]), o0[bad[0], 6], step[bad[0]]) + " (%d differ)" % bad.size
+    return None
+
+
+# ---- 3. masker spans
+SPAN_NTONE = (0, 1, 2, 31, 32, 33, 63, 64, 65, 127)
+SPAN_NNOISE = (0, 1, 31, 32, 33, 63)
+
+
+def _span_case(g, nt, nn, kind, slack, inv=None):
+    """one case: the list (tones ascending, noise ascending; runs of equal barks for kind 'runs'), the slack behind it, 64 (blo, bhi)"""
+    nm = nt + nn
+    step = 0.25 if kind == "runs" else 0.001
+    mk = lambda n: np.sort(np.round(g.uniform(0.0, 25.0, n) / step) * step)
+    lst = np.concatenate([mk(nt), mk(nn)])
+    if inv == "seam" and nt and nn:                                        # the seam alone: the first noise bark below the last tone's
+        lst[:nt] = np.maximum(lst[:nt], 1.0)
+        lst[nt] = 0.5 * lst[nt - 1]
+        lst[nt:] = np.sort(lst[nt:])
+    elif inv is not None:                                                  # an inversion at q: list[q] < list[q - 1]
+        q = inv
+        lst[q - 1], lst[q] = max(lst[q - 1], lst[q]) + 0.5, min(lst[q - 1], lst[q])
+    full = np.empty(LIST)
+    full[:nm] = lst
+    lo, hi = (lst.min(), lst.max()) if nm else (5.0, 6.0)
+    full[nm:] = -1e300 if slack == 0 else g.uniform(lo, hi, LIST - nm) if slack == 1 else np.round(g.uniform(lo, hi, LIST - nm) / 0.25) * 0.25
+    b = np.empty((64, 2))
+    c = g.uniform(0.0, 25.0, 64)
+    b[:, 0], b[:, 1] = c - 8.0, c + 3.0                                    # the callers' spans
+    pick = lambda n: lst[g.integers(0, nm, n)] if nm else g.uniform(0.0, 25.0, n)
+    b[0:8, 0] = pick(8)                                                    # a bound equal to a list value
+    b[8:16, 1] = pick(8)
+    b[16:20, 0], b[16:20, 1] = pick(4), pick(4)                            # both (half of them empty: bhi <= blo)
+    v = pick(4)
+    b[20:24, 0] = b[20:24, 1] = v                                          # blo = bhi
+    b[24] = (lo, hi); b[25] = (np.nextafter(lo, -1), hi); b[26] = (lo, np.nextafter(hi, -1)); b[27] = (hi, hi + 1)      # the first, the last
+    b[28] = (-5.0, lo - 1e-9 if lo > 0 else -1.0); b[29] = (hi, 40.0); b[30] = (-10.0, 40.0); b[31] = (20.0, 3.0)       # below all, above all, everything, empty
+    if nt:
+        b[32] = (lst[nt - 1], 40.0); b[33] = (-1.0, lst[0]); b[34] = (np.nextafter(lst[nt - 1], -1), lst[nt - 1])
+    if nn:
+        b[35] = (lst[nm - 1], 40.0); b[36] = (-1.0, lst[nt]); b[37] = (np.nextafter(lst[nm - 1], -1), lst[nm - 1])
+    return full, b
+
+
+def spans_set():
+    """-> dict(list [n, 192], bounds [n, 64, 2], counts [n, 2], named)"""
+    if "spans" in _args:
+        return _args["spans"]
+    g = np.random.default_rng(43)
+    Ls, Bs, Cs, names = [], [], [], []
+
+    def add(name, nt, nn, *a, **k):
+        full, b = _span_case(g, nt, nn, *a, **k)
+        Ls.append(full); Bs.append(b); Cs.append((nt, nn)); names.append(name)
+
+    for nt in SPAN_NTONE:
+        for nn in SPAN_NNOISE:
+            if nt + nn > MASKER_MAX:
+                continue
+            for kind in ("plain", "runs"):
+                for slack in (0, 1, 2):
+                    add("sorted %s, slack %d" % (kind, slack), nt, nn, kind, slack)
+            nm = nt + nn
+            for q in sorted({1, nm - 1, 64, 65} - {nt}):                   # unsorted: at q = 1, the last element, the lane wrap -- never AT the seam here
+                if 1 <= q < nm:
+                    add("inversion at q = %d" % q, nt, nn, "plain", q & 1, inv=q)
+            if nt and nn:
+                add("inversion at the seam alone", nt, nn, "plain", 0, inv="seam")
+                add("inversion at the seam alone", nt, nn, "runs", 1, inv="seam")
+    add("gate: 128 tones", 128, 0, "plain", 0)
+    add("gate: 64 noise components", 64, 64, "plain", 1)
+    add("gate: 64 noise components", 0, 64, "runs", 0)
+    nmade = len(Ls)
+    for _ in range(2048):
+        nt = int(g.integers(0, 128))
+        nn = int(g.integers(0, min(63, MASKER_MAX - nt) + 1))
+        nm = nt + nn
+        inv = int(g.integers(1, nm)) if nm > 1 and g.integers(0, 5) == 0 else None
+        add("random", nt, nn, ("plain", "runs")[int(g.integers(0, 2))], int(g.integers(0, 3)), inv=inv)
+    S = dict(list=np.array(Ls), bounds=np.array(Bs), counts=np.array(Cs, dtype=I32), names=names, constructed=nmade, random=2048)
+    _args["spans"] = S
+    return S
+
+
+def spans_oracle(S):
+    """a plain look at every masker: the first and last index with blo < bark <= bhi among the tones and among the noise components
+    (empty: nm, -1); sorted: all(mb[q] >= mb[q - 1] for q != ntone)"""
+    lst, b, cnt = S["list"][:, :MASKER_MAX], S["bounds"], S["counts"].astype(np.int64)
+    n = lst.shape[0]
+    q = np.arange(MASKER_MAX)[None, None, :]
+    nt, nm = cnt[:, 0][:, None, None], cnt.sum(axis=1)[:, None, None]
+    hit = (lst[:, None, :] > b[:, :, 0:1]) & (lst[:, None, :] <= b[:, :, 1:2]) & (q < nm)
+    out = np.empty((n, 64, 4), dtype=np.int64)
+    for k, part in enumerate((hit & (q < nt), hit & (q >= nt))):
+        some = part.any(axis=2)
+        out[:, :, 2 * k] = np.where(some, part.argmax(axis=2), nm[:, :, 0])
+        out[:, :, 2 * k + 1] = np.where(some, MASKER_MAX - 1 - part[:, :, ::-1].argmax(axis=2), -1)
+    qq = np.arange(1, MASKER_MAX)[None, :]
+    down = (lst[:, 1:] < lst[:, :-1]) & (qq < nm[:, :, 0]) & (qq != nt[:, :, 0])
+    srt = ~down.any(axis=1)
+    return out, srt
+
+
+def spans_check(S, out0, out1):
+    want, srt = spans_oracle(S)
+    o = out0.reshape(-1, 64, 8).astype(np.int64)
+    flags = out1.reshape(-1, 2)
+    cnt = S["counts"]
+    bad = np.flatnonzero(flags[:, 0] != srt)
+    if bad.size:
+        return "tl_maskers_sorted, case %d (%s, ntone %d, nnoise %d): %d, want %d (%d differ)" % (bad[0], S["names"][bad[0]], cnt[bad[0], 0], cnt[bad[0], 1], flags[bad[0], 0], srt[bad[0]], bad.size)
+    gate = srt & (cnt[:, 0] < 128) & (cnt[:, 1] < 64)
+    bad = np.flatnonzero(flags[:, 1] != gate)
+    if bad.size:
+        return "the callers' gate, case %d (%s): %d, want %d" % (bad[0], S["names"][bad[0]], flags[bad[0], 1], gate[bad[0]])
+    for name, got, ref in (("tl_mask_spans", o[:, :, :4], want), ("tl_mask_spans_sorted", o[:, :, 4:], np.where(gate[:, None, None], want, -2))):
+        bad = np.argwhere((got != ref).any(axis=2))
+        if bad.size:
+            c, l = bad[0]
+            return "%s, case %d (%s, ntone %d, nnoise %d), lane %d, blo=%s bhi=%s: %s, want %s (%d lanes differ)" % (
+                name, c, S["names"][c], cnt[c, 0], cnt[c, 1], l, float(S["bounds"][c, l, 0]).hex(), float(S["bounds"][c, l, 1]).hex(), got[c, l].tolist(), ref[c, l].tolist(), bad.shape[0])
+    return None
+
+
+# ---- 4. tl_min_rows
+MIN_ROWS_N = (1, 2, 3, 4, 5, 6, 7, 8, 9, 27)
+
+
+def min_rows_set():
+    """-> dict(col [n, 136], m [n, 64], rows [n, 64, 3] = (j0, n, take_first)): per case one column and 64 lanes over (n, take_first, m below /
+    among / above the rows)"""
+    if "min_rows" in _args:
+        return _args["min_rows"]
+    g = np.random.default_rng(44)
+    cols = []
+    pz, nz = 0.0, -0.0
+    for rep in range(6):
+        base = g.normal(20.0, 30.0, ROWS)
+        cols += [base, np.round(base / 20.0) * 20.0,                                        # few distinct values: duplicates
+                 np.tile([pz, nz], ROWS // 2), np.tile([nz, pz], ROWS // 2),                # +0.0 / -0.0 neighbours, both orders
+                 np.where(g.integers(0, 3, ROWS) == 0, np.tile([pz, nz], ROWS // 2), np.abs(base) + 1.0),      # zeros are the minima, among positive rows
+                 np.where(g.integers(0, 3, ROWS) == 0, np.tile([nz, pz], ROWS // 2), np.abs(base) + 1.0),
+                 np.where(g.integers(0, 2, ROWS) == 0, np.tile([nz, nz, pz, pz], ROWS // 4), np.tile([pz, nz], ROWS // 2)),
+                 np.sort(base), np.sort(base)[::-1], np.full(ROWS, 7.5)]
+    nmade = len(cols)
+    cols += [g.normal(20.0, 30.0, ROWS) for _ in range(192)] + [np.round(g.normal(0.0, 1.0, ROWS)) * g.choice([0.0, -0.0, 1.0], ROWS) for _ in range(64)]
+    col = np.array(cols)
+    n = col.shape[0]
+    rows = np.empty((n, 64, 3), dtype=I32)
+    m = np.empty((n, 64))
+    for c in range(n):
+        for l in range(64):
+            cnt = MIN_ROWS_N[l % 10] if l < 60 else (27, 9, 4, 1)[l - 60]
+            tf = (l // 10) & 1
+            j0 = (0, ROWS - cnt)[l & 1] if (c % 3 == 0 and l < 60) else int(g.integers(0, ROWS - cnt + 1))
+            seg = col[c, j0:j0 + cnt]
+            kind = (l // 20) % 3 if l < 60 else l - 60
+            m[c, l] = (seg.min() - 10.0, seg[int(g.integers(0, cnt))], 999999.9, 0.0)[kind]
+            rows[c, l] = (j0, cnt, tf)
+    S = dict(col=col, m=m, rows=rows, constructed=nmade * 64, random=(n - nmade) * 64)
+    _args["min_rows"] = S
+    return S
+
+
+def min_rows_oracle(S):
+    """the reference's running minimum: m = row j0 first (take_first) or the given m, then `if m > v: m = v` row by row -- the first zero met stays"""
+    col, rows = S["col"], S["rows"].astype(np.int64)
+    m = S["m"].copy()
+    c = np.arange(col.shape[0])[:, None]
+    for r in range(27):
+        on = r < rows[:, :, 1]
+        v = col[c, np.minimum(rows[:, :, 0] + r, ROWS - 1)]
+        take = on & ((m > v) | ((r == 0) & (rows[:, :, 2] != 0)))
+        m = np.where(take, v, m)
+    return m
+
+
+def min_rows_check(S, out0):
+    want = min_rows_oracle(S)
+    bad = np.argwhere(out0.reshape(want.shape).view(U64) != want.view(U64))
+    if bad.size:
+        c, l = bad[0]
+        j0, cnt, tf = S["rows"][c, l]
+        return "tl_min_rows, case %d lane %d: rows [%d, %d) = %s, m = %s, take_first = %d -> %s, want %s (%d differ)" % (
+            c, l, j0, j0 + cnt, [float(v).hex() for v in S["col"][c, j0:j0 + cnt]], float(S["m"][c, l]).hex(), tf, float(out0.reshape(want.shape)[c, l]).hex(), float(want[c, l]).hex(), bad.shape[0])
+    return None
+
+
+# ---- 5. tl_mnr_key
+def mnr_key_set():
+    if "mnr_key" in _args:
+        return _args["mnr_key"]
+    g = np.random.default_rng(45)
+    lim = 999999.0
+    made = np.concatenate([_pm(np.concatenate([[0.0, MINSUB, MINN, 1e-300, 1e-20, 0.1, 1.0, 96.3, 999998.0, 1e6, 1e7, 1e300, MAXN], ONES, POW2_ALL[::16]])),
+                           _near(lim, 8), _near(-lim, 2), np.arange(-120, 121) * 0.5, _near(999999.9, 1)])
+    rnd = np.concatenate([g.normal(0.0, 40.0, NSTAGE_RANDOM // 2), g.choice([-1.0, 1.0], NSTAGE_RANDOM // 2) * np.ldexp(g.uniform(1.0, 2.0, NSTAGE_RANDOM // 2), g.integers(-1074, 1024, NSTAGE_RANDOM // 2).astype(np.int32))])
+    S = dict(x=np.concatenate([made, rnd]), constructed=made.size, random=rnd.size)
+    _args["mnr_key"] = S
+    return S
+
+
+def mnr_key_oracle(x):
+    """Python integers on the bits: below 999999.0 the bits of x (a zero of either sign as +0) with the sign bit set for x >= 0, inverted for x < 0; else ~0"""
+    out = []
+    for u, v in zip(_d2u(x).tolist(), x.tolist()):
+        if not (999999.0 > v):
+            out.append((1 << 64) - 1)
+            continue
+        if v == 0.0:
+            u = 0
+        out.append(((1 << 64) - 1 - u) if u >> 63 else (u | (1 << 63)))
+    return out
+
+
+def mnr_key_check(S, out0):
+    x = S["x"]
+    want = mnr_key_oracle(x)
+    got = out0.tolist()
+    for i, (a, b) in enumerate(zip(got, want)):
+        if a != b:
+            return "tl_mnr_key: argument %d = %s -> %#x, want %#x" % (i, float(x[i]).hex(), a, b)
+    # what the allocation relies on: ascending doubles give strictly ascending keys; +-0.0 one key; from 999999.0 on exactly ~0
+    xs = np.unique(x[x < 999999.0])                                        # (sorted; -0.0 and 0.0 are one value here)
+    ks = np.array([got[i] for i in np.unique(x, return_index=True)[1]], dtype=U64)[:xs.size]
+    if not (ks[1:] > ks[:-1]).all():
+        i = int(np.flatnonzero(~(ks[1:] > ks[:-1]))[0])
+        return "tl_mnr_key: keys of %s and %s do not ascend" % (float(xs[i]).hex(), float(xs[i + 1]).hex())
+    k0 = {got[i] for i in np.flatnonzero(x == 0.0)}
+    if len(k0) != 1:
+        return "tl_mnr_key: +0.0 and -0.0 have different keys"
+    if not all(got[i] == (1 << 64) - 1 for i in np.flatnonzero(x >= 999999.0)) or any(got[i] == (1 << 64) - 1 for i in np.flatnonzero(x < 999999.0)):
+        return "tl_mnr_key: ~0 is not exactly the keys from 999999.0 on"
+    return None
+
+
+# ---- 6. scalefactor index and count
+def scalefactors():
+    return _emu_tables()[1]
+
+
+def sf_index_set(sf):
+    """the set of tests/test_emu_parity.py test_scalefactor_index: every table entry and its neighbours, powers of two and their neighbours, random
+    magnitudes over the whole range, zero and denormals -- below 2.0"""
+    rng = np.random.default_rng(11)
+    p2 = 2.0 ** np.arange(-80, 1)
+    vals = np.concatenate([sf, np.nextafter(sf, 0), np.nextafter(sf, 4), p2, np.nextafter(p2, 0), np.nextafter(p2, 4),
+                           10.0 ** rng.uniform(-25, 0.3, 400000), rng.uniform(0, 2, 400000), [0.0, 5e-324, 1e-310, 1e-300, 1.999999]])
+    return np.ascontiguousarray(vals[vals < 2.0])
+
+
+def sf_index_check(vals, sf, out0, out1):
+    """both searches == (number of table entries >= the argument) - 1, 0 when there is none; tl_sfs_count(i) = 3, 2, 1, 2 for scfsi i & 3"""
+    asc = sf[::-1]
+    assert (np.diff(asc) > 0).all()
+    cnt = 64 - np.searchsorted(asc, vals, side="left")
+    want = np.maximum(cnt - 1, 0)
+    o = out0.reshape(-1, 2)
+    for k, name in enumerate(("tl_sf_index", "tl_sf_index_ref")):
+        bad = np.flatnonzero(o[:, k] != want)
+        if bad.size:
+            return "%s: argument %d = %s -> %d, want %d (%d differ)" % (name, bad[0], float(vals[bad[0]]).hex(), o[bad[0], k], want[bad[0]], bad.size)
+    bad = np.flatnonzero(out1 != np.array([3, 2, 1, 2])[np.arange(vals.size) & 3])
+    if bad.size:
+        return "tl_sfs_count(%d) = %d" % (bad[0], out1[bad[0]])
+    return None
+
+
+# ---- 7. tl_div_by
+def hardest(d):
+    """Dividends whose quotient by d lies within ~2^-106 (relative) of a rounding midpoint: S * 2^53 = (2M+1) * D + t
+    for small t, solved for the odd 2M+1 modulo a power of two (D = integer significand of d)."""
+    import math
+    m, e = math.frexp(d)
+    D = int(m * (1 << 53))
+    z = (D & -D).bit_length() - 1
+    Dp, mod = D >> z, 1 << (53 - z)
+    inv = pow(Dp, -1, mod)
+    out = []
+    for tp in range(-15, 16, 2):
+        r = (-tp * inv) % mod
+        for k in range(0, 1 << z if z < 6 else 64):
+            o = r + k * mod
+            if not (o & 1):
+                continue
+            o |= 1 << 53                                        # 2M+1 in [2^53, 2^54)
+            num = o * D + (tp << z)
+            if num % (1 << 53):
+                continue
+            S = num >> 53
+            while S >= (1 << 53) and not (S & 1):
+                S >>= 1
+            if (1 << 52) <= S < (1 << 53):
+                out.append(math.ldexp(float(S), -52))
+    return out
+
+
+def div_by_sets(sf, n):
+    """the sets of tests/test_emu_parity.py test_quantiser_division, divisor by divisor -> (d, dividends, number of hardest() dividends): n random
+    dividends over the subband-sample range, n exact multiples, n next to a representable quotient, 3 n next to a rounding midpoint, and
+    every hardest() dividend of both signs.  Divisors: the scalefactors; the critical-band widths 1..200 (psy 1 noise weights)."""
+    rng = np.random.default_rng(7)
+    for d in np.concatenate([sf, np.arange(1.0, 201.0)]):
+        s_rand = rng.uniform(-2.5, 2.5, n) * 10.0 ** rng.uniform(-12, 0, n)
+        q = rng.uniform(0.5, 4.0, n) * rng.choice([-1.0, 1.0], n)
+        near_rep = np.nextafter(q * d, rng.choice([-np.inf, np.inf], n))      # quotient within an ulp of q
+        half = (np.nextafter(np.abs(q), np.inf) - np.abs(q)) / 2
+        mid = (np.abs(q).astype(np.longdouble) + half.astype(np.longdouble)) * np.sign(q).astype(np.longdouble)
+        near_mid = (mid * np.longdouble(d)).astype(np.float64)              # quotient within an ulp-fraction of a midpoint
+        hard = np.array(hardest(float(d)), dtype=np.float64)
+        s_all = np.ascontiguousarray(np.concatenate([s_rand, q * d, near_rep, near_mid, np.nextafter(near_mid, np.inf),
+                                                     np.nextafter(near_mid, -np.inf), hard, -hard]))
+        yield float(d), s_all, len(hard)
+
+
+def div_by_set():
+    """the probe's set: each randomly drawn class (uniform, exact multiple, next to a representable quotient, next to a midpoint and its two
+    neighbours) thinned to 2^14 draws per divisor, every hardest() dividend of both signs kept, and a zero dividend of either sign per divisor"""
+    if "div_by" in _args:
+        return _args["div_by"]
+    Ss, Ds, Cl, nhard, n = [], [], [], 0, 1 << 14
+    for d, s, nh in div_by_sets(scalefactors(), n):
+        Ss.append(s); Ds.append(np.full(s.size, d)); nhard += 2 * nh
+        Cl.append(np.concatenate([np.repeat(np.arange(6, dtype=np.int8), n), np.full(2 * nh, 6, dtype=np.int8)]))
+        Ss.append(np.array([0.0, -0.0])); Ds.append(np.full(2, d)); Cl.append(np.full(2, 7, dtype=np.int8))
+    s, d = np.concatenate(Ss), np.concatenate(Ds)
+    S = dict(cls=np.concatenate(Cl), s=s, d=d, constructed=s.size - 6 * 264 * (1 << 14), random=6 * 264 * (1 << 14), hardest=nhard)
+    _args["div_by"] = S
+    return S
+
+
+def div_by_check(S, out0, out1):
+    """numpy's s / d; where the dividend is a zero, compared after + 0.0 (the header documents the sign)"""
+    s, d = S["s"], S["d"]
+    want = s / d
+    z = s == 0.0
+    for name, got in (("tl_div_by (reciprocal made in the kernel)", out0), ("tl_div_by (reciprocal made on the host)", out1)):
+        bad = same_bits(np.where(z, got + 0.0, got), np.where(z, want + 0.0, want))
+        if bad.size:
+            what = ("'random'", "'exact multiple'", "'next to a representable quotient'", "'next to a midpoint'", "'above one next to a midpoint'", "'below one next to a midpoint'", "'hardest()'", "'zero dividend'")
+            cl = np.bincount(S["cls"][bad], minlength=8)
+            if cl[6]:                                                      # a constructed dividend first
+                bad = bad[S["cls"][bad] == 6]
+            return _bits_report(name, what[S["cls"][bad[0]]] + " " + str(cl.tolist()), bad[0], dict(s=float(s[bad[0]]), d=float(d[bad[0]])), got[bad[0]], want[bad[0]]) + " (%d differ)" % bad.size
+    return None
+
+
+# ---- 8. bit writer and CRC
+def bits_set(wide):
+    """-> dict(val [n, 64, 6] u64, len [n, 64, 6] i32, par [n, 2] = (start, wide)).  tl_put_bits: lengths 0..32, zeros included; tl_put_bits48: 1..48
+    (0 = no field: its callers skip one)"""
+    key = "bits%d" % wide
+    if key in _args:
+        return _args[key]
+    g = np.random.default_rng(46 + wide)
+    top = 48 if wide else 32
+    lens, vals, starts, names = [], [], [], []
+
+    def add(name, start, ln, ones=False):
+        ln = np.asarray(ln, dtype=np.int64).reshape(64, FIELDS)
+        assert start + ln.sum() <= FRAME_BITS and ln.min() >= 0 and ln.max() <= top
+        full = (np.ones((64, FIELDS), dtype=U64) << ln.astype(U64)) - U64(1)
+        v = full if ones else g.integers(0, 1 << 63, (64, FIELDS), dtype=U64) & full
+        lens.append(ln.astype(I32)); vals.append(v); starts.append(start); names.append(name)
+
+    for start in range(64):                                                # every start offset
+        add("start offset, random lengths", start, g.integers(0 if not wide else 1, top + 1, (64, FIELDS)))
+        add("start offset, all-ones values", start, g.integers(1, top + 1, (64, FIELDS)), ones=True)
+    for start in (0, 1, 31, 32, 33, 63):
+        ln = g.integers(1, top + 1, (64, FIELDS))
+        pos = start
+        for l in range(64):                                                # every lane's third and last field end exactly on a word boundary
+            for f in range(FIELDS):
+                if f in (2, 5):
+                    r = (-pos) % 32
+                    ln[l, f] = r if r else 32
+                pos += ln[l, f]
+        add("fields ending on a word boundary", start, ln, ones=start & 1)
+        add("short fields: neighbouring lanes share a word", start, g.integers(0 if not wide else 1, 6, (64, FIELDS)), ones=start == 63)
+        add("one-bit fields", start, np.ones((64, FIELDS)), ones=True)
+        if wide:
+            ln = np.zeros((64, FIELDS), dtype=np.int64)
+            ln[:, :4] = 48                                                 # a 48-bit field at offset o > 16 spans three words: every offset occurs (48 l + start mod 32)
+            add("48-bit fields spanning three words", start, ln, ones=True)
+            ln = g.integers(33, 49, (64, FIELDS))
+            ln[:, 4:] = 0
+            add("fields of 33..48 bits", start, ln)
+        else:
+            add("32-bit fields", start, np.full((64, FIELDS), 32), ones=True)
+            ln = g.integers(0, 33, (64, FIELDS))
+            ln[g.integers(0, 2, (64, FIELDS)) == 0] = 0
+            add("many empty fields", start, ln)
+    nmade = len(lens)
+    for _ in range(256):
+        add("random", int(g.integers(0, 64)), g.integers(0 if not wide else 1, top + 1, (64, FIELDS)), ones=bool(g.integers(0, 4) == 0))
+    S = dict(val=np.array(vals), len=np.array(lens), par=np.array([(s, wide) for s in starts], dtype=I32), names=names, constructed=nmade, random=256)
+    _args[key] = S
+    return S
+
+
+def _crc_lanes(val, ln, poly, top, init):
+    """a bitwise CRC (crc.c:43-56 / :99-113) of each lane's fields, MSB first, all lanes side by side"""
+    crc = np.full(val.shape[:2], init, dtype=np.int64)
+    mask = 2 * top - 1
+    for f in range(FIELDS):
+        v, nb = val[:, :, f], ln[:, :, f].astype(np.int64)
+        for k in range(int(nb.max())):
+            on = k < nb
+            bit = ((v >> np.maximum(nb - 1 - k, 0).astype(U64)) & U64(1)).astype(np.int64)
+            carry = (crc & top) != 0
+            new = ((crc << 1) & mask) ^ np.where(carry != (bit != 0), poly, 0)
+            crc = np.where(on, new, crc)
+    return crc
+
+
+def bits_oracle(S):
+    """the frame as one Python integer: the fields MSB first at running offsets from `start`; its words, their byte swaps; the CRCs"""
+    val, ln = S["val"], S["len"]
+    n = val.shape[0]
+    words = np.empty((n, FRAME_WORDS), dtype=np.uint32)
+    nbits = 32 * FRAME_WORDS
+    for c in range(n):
+        big, pos = 0, int(S["par"][c, 0])
+        for v, nb in zip(val[c].ravel().tolist(), ln[c].ravel().tolist()):
+            big |= v << (nbits - pos - nb)
+            pos += nb
+        words[c] = np.frombuffer(big.to_bytes(4 * FRAME_WORDS, "big"), dtype=">u4")
+    swapped = words.byteswap()
+    crc = np.stack([_crc_lanes(val, ln, 0x8005, 0x8000, 0xffff), _crc_lanes(val, ln, 0x1d, 0x80, 0)], axis=2)
+    return words, swapped, crc
+
+
+def bits_check(S, out0, out1):
+    words, swapped, crc = bits_oracle(S)
+    o = out0.reshape(-1, 3, FRAME_WORDS)
+    name = "tl_put_bits48" if S["par"][0, 1] else "tl_put_bits"
+    for k, (what, ref) in enumerate(((name + ": frame word", words), ("tl_get_bit: frame word read bit by bit", words), ("tl_bswap of frame word", swapped))):
+        bad = np.argwhere(o[:, k] != ref)
+        if bad.size:
+            c, w = bad[0]
+            return "%s %d of case %d (%s, start %d): %#010x, want %#010x (%d words differ)" % (what, w, c, S["names"][c], S["par"][c, 0], o[c, k, w], ref[c, w], bad.shape[0])
+    bad = np.argwhere(out1.reshape(-1, 64, 2).astype(np.int64) != crc)
+    if bad.size:
+        c, l, k = bad[0]
+        return "tl_crc_upd (%s) of case %d lane %d: fields %s lengths %s -> %#x, want %#x" % (("CRC-16", "ScF-CRC")[k], c, l, [hex(int(v)) for v in S["val"][c, l]], S["len"][c, l].tolist(),
+                                                                                             out1.reshape(-1, 64, 2)[c, l, k], crc[c, l, k])
+    return None
+
+
+# ---- running a form
+def run_stage(fn, test):
+    """fn = probe_stage of the emulation or tlb_debug_probe_stage of the TEST library -> (rc, S, out0, out1)"""
+    f64 = lambda shape: np.full(shape, np.nan)
+    if test == "add_db":
+        S = add_db_set()
+        n, ins, outs = S["a"].size, (S["a"], S["b"], None), (f64(S["a"].size), f64(4 * S["a"].size))
+    elif test == "mask":
+        S = mask_set()
+        n, ins, outs = S["x"].size, (S["x"], S["mb"], S["aux"]), (f64(8 * S["x"].size), f64(5 * S["x"].size))
+    elif test == "mnr_key":
+        S = mnr_key_set()
+        n, ins, outs = S["x"].size, (S["x"], None, None), (np.zeros(S["x"].size, dtype=U64), None)
+    elif test == "sf_index":
+        v = sf_index_set(scalefactors())
+        S = dict(x=v, constructed=v.size - 800000, random=800000)
+        n, ins, outs = v.size, (v, None, None), (np.full(2 * v.size, -1, dtype=I32), np.full(v.size, -1, dtype=I32))
+    elif test == "div_by":
+        S = div_by_set()
+        n, ins, outs = S["s"].size, (S["s"], S["d"], None), (f64(S["s"].size), f64(S["s"].size))
+    elif test == "spans":
+        S = spans_set()
+        n = S["list"].shape[0]
+        ins, outs = (S["list"], S["bounds"], S["counts"]), (np.full(512 * n, -9, dtype=I32), np.full(2 * n, -9, dtype=I32))
+    elif test == "min_rows":
+        S = min_rows_set()
+        n = S["col"].shape[0]
+        ins, outs = (S["col"], S["m"], S["rows"]), (f64(64 * n), None)
+    else:
+        S = bits_set(1 if test == "put_bits48" else 0)
+        n = S["val"].shape[0]
+        ins, outs = (S["val"], S["len"], S["par"]), (np.full(3 * FRAME_WORDS * n, 0xdeadbeef, dtype=np.uint32), np.full(128 * n, 0xdeadbeef, dtype=np.uint32))
+    form = STAGE["bits" if test.startswith("put_bits") else test]
+    ins = [None if x is None else np.ascontiguousarray(x) for x in ins]
+    rc = fn(form, n, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(outs[0]), _ptr(outs[1]))
+    return rc, S, outs[0], outs[1]
+
+
+def stage_check(test, S, out0, out1):
+    """a run's outputs against the form's oracle -> None, or a message naming form, argument and both results"""
+    tab = _emu_tables()[0]
+    if test == "add_db":
+        msg = add_db_check(S, out0, out1, tab=tab)
+        if msg is None:                                                    # the far level leaves the other operand's bits
+            sb, sa = S["far"]
+            if same_bits(out0[sb], S["a"][sb]).size or same_bits(out0[sa], S["b"][sa]).size:
+                msg = "tl_add_db: a sum with the far level is not the other operand"
+        return msg
+    if test == "mask":
+        return mask_check(S, out0, out1, tab)
+    if test == "spans":
+        return spans_check(S, out0, out1)
+    if test == "min_rows":
+        return min_rows_check(S, out0)
+    if test == "mnr_key":
+        return mnr_key_check(S, out0)
+    if test == "sf_index":
+        return sf_index_check(S["x"], scalefactors(), out0, out1)
+    if test == "div_by":
+        return div_by_check(S, out0, out1)
+    return bits_check(S, out0, out1)
+
+
+def stage_same(test, S, dev, emu_out):
+    """device == emulation, every word of both outputs -> None or a message naming the first argument / case that differs and both results"""
+    per = {"add_db": (1, 4), "mask": (8, 5), "mnr_key": (1, 0), "sf_index": (2, 1), "div_by": (1, 1), "spans": (512, 2), "min_rows": (64, 0),
+           "put_bits": (3 * FRAME_WORDS, 128), "put_bits48": (3 * FRAME_WORDS, 128)}[test]
+    raw = lambda x: x.view(U64) if x.dtype == np.float64 else x
+    for k in range(2):
+        if dev[k] is None:
+            continue
+        bad = np.flatnonzero(raw(dev[k]) != raw(emu_out[k]))
+        if bad.size:
+            i, j = divmod(int(bad[0]), per[k])
+            return "%s, device / emulation: output %d, %s %d, word %d: device %#x, emulation %#x (%d words differ)" % (
+                test, k, "argument" if STAGE["bits" if test.startswith("put_bits") else test] < 5 else "case", i, j, int(raw(dev[k])[bad[0]]), int(raw(emu_out[k])[bad[0]]), bad.size)
+    return None
+
+
+def _stage_call(fn, form, n, *arrs):
+    arrs = [None if x is None else np.ascontiguousarray(x) for x in arrs]
+    return fn(form, n, *[_ptr(x) for x in arrs])
+
+
+def check_stage_argument_checks(fn):
+    """what the stage probe refuses with TLB_ERR_ARG before anything is queued: one argument outside each form's domain, an unknown form, n = 0, a
+    missing pointer -- and a good call afterwards returns the right values"""
+    d = lambda *v: np.array(v, dtype=np.float64)
+    o = lambda k: np.zeros(k)
+    good_a, good_b = d(1.0, 2.0, 3.0), d(0.0, -5.0, 2.5)
+    call = lambda form, n, *a: _stage_call(fn, STAGE[form], n, *a)
+    assert call("add_db", 3, d(1.0, np.nan, 3.0), good_b, None, o(3), o(12)) == ERR_ARG                         # a NaN operand
+    assert call("add_db", 3, good_a, d(0.0, 2.0 ** 19, 1.0), None, o(3), o(12)) == ERR_ARG                      # a dB operand of 2^19
+    assert call("add_db", 3, good_a, d(0.0, -np.inf, 1.0), None, o(3), o(12)) == ERR_ARG
+    aux = np.array([[10.0, 0.0, 1.0, 1.0]] * 3)
+    assert call("mask", 3, good_a, d(1.0, 32.5, 3.0), aux, o(24), o(15)) == ERR_ARG                             # a bark above 32
+    assert call("mask", 3, good_a, d(1.0, -0.5, 3.0), aux, o(24), o(15)) == ERR_ARG
+    bad_aux = aux.copy(); bad_aux[2, 2] = 0.5
+    assert call("mask", 3, good_a, good_a, bad_aux, o(24), o(15)) == ERR_ARG                                    # tonal is 0 or 1
+    bad_aux = aux.copy(); bad_aux[1, 0] = np.nan
+    assert call("mask", 3, good_a, good_a, bad_aux, o(24), o(15)) == ERR_ARG
+    assert call("mnr_key", 3, d(1.0, np.nan, 2.0), None, None, np.zeros(3, dtype=U64), None) == ERR_ARG
+    assert call("sf_index", 3, d(1.0, 2.0, 0.5), None, None, np.zeros(6, dtype=I32), np.zeros(3, dtype=I32)) == ERR_ARG        # cur_max < 2
+    assert call("sf_index", 3, d(1.0, -1e-9, 0.5), None, None, np.zeros(6, dtype=I32), np.zeros(3, dtype=I32)) == ERR_ARG
+    assert call("div_by", 3, good_a, d(1.0, 0.0, 3.0), None, o(3), o(3)) == ERR_ARG                             # no divisor of the encoder
+    assert call("div_by", 3, good_a, d(1.0, float(np.nextafter(2.0, 0.0)), 3.0), None, o(3), o(3)) == ERR_ARG   # a significand of all ones: Markstein's exception
+    assert call("div_by", 3, d(1.0, 1e300, 3.0), good_a, None, o(3), o(3)) == ERR_ARG
+    lst, bnd = np.tile(np.linspace(0.0, 24.0, LIST), (2, 1)), np.tile(d(2.0, 13.0), (2, 64, 1))
+    so, sf_ = np.zeros(1024, dtype=I32), np.zeros(4, dtype=I32)
+    assert call("spans", 2, lst, bnd, np.array([[3, 4], [65, 64]], dtype=I32), so, sf_) == ERR_ARG               # ntone + nnoise = 129
+    assert call("spans", 2, lst, bnd, np.array([[3, 4], [-1, 4]], dtype=I32), so, sf_) == ERR_ARG
+    bad_lst = lst.copy(); bad_lst[1, 5] = np.nan
+    assert call("spans", 2, bad_lst, bnd, np.array([[3, 4], [10, 4]], dtype=I32), so, sf_) == ERR_ARG
+    col, m = np.zeros((2, ROWS)), np.zeros((2, 64))
+    rows = np.tile(np.array([0, 4, 1], dtype=I32), (2, 64, 1))
+    bad_rows = rows.copy(); bad_rows[1, 63] = (130, 7, 0)                                                       # rows [130, 137): past the column
+    assert call("min_rows", 2, col, m, bad_rows, o(128), None) == ERR_ARG
+    bad_rows = rows.copy(); bad_rows[0, 1] = (3, 0, 0)
+    assert call("min_rows", 2, col, m, bad_rows, o(128), None) == ERR_ARG
+    val, ln = np.zeros((2, 64, FIELDS), dtype=U64), np.full((2, 64, FIELDS), 30, dtype=I32)
+    bo, bc = np.zeros(2 * 3 * FRAME_WORDS, dtype=np.uint32), np.zeros(256, dtype=np.uint32)
+    par = np.array([[0, 0], [0, 0]], dtype=I32)
+    assert call("bits", 2, val, np.full((2, 64, FIELDS), 48, dtype=I32), np.array([[0, 1], [0, 1]], dtype=I32), bo, bc) == ERR_ARG      # 18432 bits: a field runs past the frame
+    bad_ln = ln.copy(); bad_ln[1, 7, 2] = 33
+    assert call("bits", 2, val, bad_ln, par, bo, bc) == ERR_ARG                                                 # tl_put_bits takes 0..32
+    bad_val = val.copy(); bad_val[0, 0, 0] = U64(1) << U64(30)
+    assert call("bits", 2, bad_val, ln, par, bo, bc) == ERR_ARG                                                 # a value wider than its field
+    assert call("bits", 2, val, ln, np.array([[0, 0], [64, 0]], dtype=I32), bo, bc) == ERR_ARG
+    p = o(16)
+    q = _ptr(p)
+    assert fn(-1, 2, q, q, q, q, q) == ERR_ARG and fn(STAGE_NFORMS, 2, q, q, q, q, q) == ERR_ARG                # an unknown form
+    assert fn(0, 0, q, q, q, q, q) == ERR_ARG and fn(0, -3, q, q, q, q, q) == ERR_ARG                           # n = 0
+    assert fn(0, 2, None, q, q, q, q) == ERR_ARG and fn(0, 2, q, None, q, q, q) == ERR_ARG and fn(0, 2, q, q, q, None, q) == ERR_ARG and fn(0, 2, q, q, q, q, None) == ERR_ARG
+    assert fn(STAGE["mask"], 2, q, q, None, q, q) == ERR_ARG and fn(STAGE["spans"], 1, q, q, None, q, q) == ERR_ARG
+    # ... and a good call after all that returns the right values
+    o0, o1 = o(3), o(12)
+    assert call("add_db", 3, d(10.0, 0.0, -300.0), d(10.0, 150.0, 5.0), None, o0, o1) == 0
+    tab = _emu_tables()[0]
+    assert o0.tolist() == [10.0 + tab[0], 150.0, 5.0] and o1.reshape(3, 4)[:, 0].tolist() == o0.tolist()
+    k = np.zeros(2, dtype=U64)
+    assert call("mnr_key", 2, d(0.0, 1e6), None, None, k, None) == 0 and k.tolist() == [1 << 63, (1 << 64) - 1]

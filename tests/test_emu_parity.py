@@ -10,6 +10,7 @@ import emulib as E
 import oraclelib as O
 from conftest import golden_cases
 from pcmgen import gen_pcm
+from probelib import div_by_sets, sf_index_set
 
 
 def _emu_stream(pcm, xpad=None, xpad_len=None, chunks=(None,), **cfg):
@@ -145,11 +146,7 @@ def test_scalefactor_index():
     tab = (C.c_double * 64)()
     L.emu_scalefactors(tab)
     sf = np.array(tab)
-    rng = np.random.default_rng(11)
-    p2 = 2.0 ** np.arange(-80, 1)
-    vals = np.concatenate([sf, np.nextafter(sf, 0), np.nextafter(sf, 4), p2, np.nextafter(p2, 0), np.nextafter(p2, 4),
-                           10.0 ** rng.uniform(-25, 0.3, 400000), rng.uniform(0, 2, 400000), [0.0, 5e-324, 1e-310, 1e-300, 1.999999]])
-    vals = np.ascontiguousarray(vals[vals < 2.0])
+    vals = sf_index_set(sf)                                         # (tests/probelib.py: the device probe runs the same set)
     assert L.emu_sf_index_check(vals.ctypes.data, len(vals)) == 0
 
 
@@ -172,47 +169,9 @@ def test_quantiser_division():
     assert sf[0] == 2.0 and sf[63] == 1e-20
     # Markstein's exception: no divisor has an all-ones significand
     assert not np.any((sf.view(np.uint64) & np.uint64((1 << 52) - 1)) == np.uint64((1 << 52) - 1))
-    rng = np.random.default_rng(7)
-    n = 100000
-
-    def hardest(d):
-        """Dividends whose quotient by d lies within ~2^-106 (relative) of a rounding midpoint: S * 2^53 = (2M+1) * D + t
-        for small t, solved for the odd 2M+1 modulo a power of two (D = integer significand of d)."""
-        m, e = math.frexp(d)
-        D = int(m * (1 << 53))
-        z = (D & -D).bit_length() - 1
-        Dp, mod = D >> z, 1 << (53 - z)
-        inv = pow(Dp, -1, mod)
-        out = []
-        for tp in range(-15, 16, 2):
-            r = (-tp * inv) % mod
-            for k in range(0, 1 << z if z < 6 else 64):
-                o = r + k * mod
-                if not (o & 1):
-                    continue
-                o |= 1 << 53                                        # 2M+1 in [2^53, 2^54)
-                num = o * D + (tp << z)
-                if num % (1 << 53):
-                    continue
-                S = num >> 53
-                while S >= (1 << 53) and not (S & 1):
-                    S >>= 1
-                if (1 << 52) <= S < (1 << 53):
-                    out.append(math.ldexp(float(S), -52))
-        return out
-
     nhard = 0
-    for d in np.concatenate([sf, np.arange(1.0, 201.0)]):           # scalefactors; critical-band widths (psy 1 noise weights)
-        s_rand = rng.uniform(-2.5, 2.5, n) * 10.0 ** rng.uniform(-12, 0, n)
-        q = rng.uniform(0.5, 4.0, n) * rng.choice([-1.0, 1.0], n)
-        near_rep = np.nextafter(q * d, rng.choice([-np.inf, np.inf], n))      # quotient within an ulp of q
-        half = (np.nextafter(np.abs(q), np.inf) - np.abs(q)) / 2
-        mid = (np.abs(q).astype(np.longdouble) + half.astype(np.longdouble)) * np.sign(q).astype(np.longdouble)
-        near_mid = (mid * np.longdouble(d)).astype(np.float64)              # quotient within an ulp-fraction of a midpoint
-        hard = np.array(hardest(float(d)), dtype=np.float64)
-        nhard += len(hard)
-        s_all = np.ascontiguousarray(np.concatenate([s_rand, q * d, near_rep, near_mid, np.nextafter(near_mid, np.inf),
-                                                     np.nextafter(near_mid, -np.inf), hard, -hard]))
+    for d, s_all, nh in div_by_sets(sf, 100000):                    # (tests/probelib.py: scalefactors, then the critical-band widths 1..200; the device probe runs a thinned set)
+        nhard += nh
         d_all = np.full(s_all.shape, d)
         assert L.emu_div_by_check(s_all.ctypes.data, d_all.ctypes.data, len(s_all)) == 0
     assert nhard > 1000

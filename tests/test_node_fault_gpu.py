@@ -51,7 +51,7 @@ def _planar(inter_s, c):
 def test_product_library_has_no_fault_hooks(M):
     """the hooks exist in the TEST build only"""
     L = M.load_library()
-    for name in ("tlb_debug_fail_next", "tlb_debug_tick_fail_next", "tlb_debug_node_fail_next", "tlb_debug_probe_libm", "tlb_debug_probe_wave"):
+    for name in ("tlb_debug_fail_next", "tlb_debug_tick_fail_next", "tlb_debug_node_fail_next", "tlb_debug_probe_libm", "tlb_debug_probe_wave", "tlb_debug_probe_stage"):
         assert not hasattr(L, name), name
 
 

@@ -1,6 +1,7 @@
 """The probe on the host (csrc/mp2_probe.h with -DTL_EMULATE, tests/emu/mp2_probe_emu.cpp): every device-path form of csrc/tl_libm.h against
 this machine's libm, bit for bit, on the full argument sets of tests/probelib.py, and every cross-lane primitive of csrc/mp2_wave.h against
-a numpy oracle written from the primitive's comment on the full case sets.
+a numpy oracle written from the primitive's comment on the full case sets, and every shared stage helper of csrc/mp2_dbsum.h
+(csrc/mp2_probe_stage.h) against an oracle written from the definition its comment states, on raw bits and integers.
 
 That is what the GPU file (tests/test_probe_gpu.py) rests on: the argument sets lie inside the forms' stated domains (the probe refuses
 anything else), and references, generators and oracles are right before a GPU is involved."""
@@ -52,7 +53,7 @@ def test_seeds_of_the_host_half_meet_the_refinements_precondition(E):
 
 
 def test_argument_checks(E):
-    P.check_argument_checks(E.probe_libm, E.probe_wave)
+    P.check_argument_checks(E.probe_libm, E.probe_wave, E.probe_stage)
 
 
 @pytest.mark.parametrize("prim", list(P.PRIMS))
@@ -67,3 +68,13 @@ def test_wave_primitive_is_what_its_comment_says(E, prim):
     assert not bad.size, "%s: %d words differ; first: case %d, row %s -> %s, want %s" % (
         prim, bad.shape[0], bad[0][0], [hex(int(x)) for x in np.ravel(w[bad[0][0]])], [hex(int(x)) for x in np.ravel(out[bad[0][0]])],
         [hex(int(x)) for x in np.ravel(want[bad[0][0]])])
+
+
+@pytest.mark.parametrize("test", P.STAGE_TESTS)
+def test_stage_helper_is_what_its_definition_says(E, test):
+    """the stage helpers of csrc/mp2_dbsum.h through the emulation == the oracle on the full set, and the whole set inside the form's domain (rc 0)"""
+    rc, S, out0, out1 = P.run_stage(E.probe_stage, test)
+    assert rc == 0, "an argument of the set lies outside the form's stated domain"
+    assert S["constructed"] > 0 and S["random"] >= 256
+    msg = P.stage_check(test, S, out0, out1)
+    assert msg is None, msg

@@ -1,7 +1,9 @@
 """The probe on the GPU (csrc/toolame_probe.hip in the fault-injection TEST library, csrc/tlb_debug.h: tlb_debug_probe_libm / _wave): the
 DEVICE halves of csrc/tl_libm.h and of csrc/mp2_wave.h's cross-lane primitives, one by one, on the argument and case sets of
 tests/probelib.py -- hardware reciprocal / reciprocal-square-root seeds, inline v_fma_f64 / v_min_f64 / v_max_f64, tables as device globals,
-as LDS copies and rearranged (TL_SCT), DPP ladders, permlane swaps, ballots.
+as LDS copies and rearranged (TL_SCT), DPP ladders, permlane swaps, ballots -- and (tlb_debug_probe_stage, csrc/mp2_probe_stage.h) the shared stage helpers
+of csrc/mp2_dbsum.h as the device build compiles them: dB sums, masking terms, masker spans, row minimum, allocation key, scalefactor index, exact
+division, the bit writer (64 lanes' atomicOr into one LDS frame) and the CRC step.
 
 The hard assertion is device == emulation (tests/emu/mp2_probe_emu.cpp, the host halves through the same text), bit for bit: it does not
 depend on this machine's libm.  tests/test_probe_emu.py has shown the emulation equal to glibc and to the oracles on the same sets, and the
@@ -31,6 +33,7 @@ def FI(M):
         M.build()
     L = M.load_fault_library()
     P.bind_probe(L.tlb_debug_probe_libm, L.tlb_debug_probe_wave)
+    P.bind_stage(L.tlb_debug_probe_stage)
     return L
 
 
@@ -94,7 +97,7 @@ def test_hardware_seeds_meet_the_refinements_precondition(FI):
 
 def test_argument_checks(FI):
     """outside a form's domain, unknown form, n = 0, a missing pointer: 18 each, before anything is queued; then a good call with the right bits"""
-    P.check_argument_checks(FI.tlb_debug_probe_libm, FI.tlb_debug_probe_wave)
+    P.check_argument_checks(FI.tlb_debug_probe_libm, FI.tlb_debug_probe_wave, FI.tlb_debug_probe_stage)
 
 
 @pytest.mark.parametrize("prim", list(P.PRIMS))
@@ -110,3 +113,16 @@ def test_wave_primitive_device_is_emulation_is_oracle(FI, E, prim):
         assert not bad.size, "%s, device / %s: %d words differ; first: case %d, row %s -> %s, want %s" % (
             prim, name, bad.shape[0], bad[0][0], [hex(int(x)) for x in np.ravel(w[bad[0][0]])], [hex(int(x)) for x in np.ravel(dev[bad[0][0]])],
             [hex(int(x)) for x in np.ravel(ref[bad[0][0]])])
+
+
+@pytest.mark.parametrize("test", P.STAGE_TESTS)
+def test_stage_helper_device_is_emulation_is_oracle(FI, E, test):
+    """one launch per form: every output word of the device == the emulation's (the hard assertion), and == the oracle written from the definition"""
+    rc, S, d0, d1 = P.run_stage(FI.tlb_debug_probe_stage, test)
+    assert rc == 0
+    rc, _, e0, e1 = P.run_stage(E.probe_stage, test)
+    assert rc == 0
+    msg = P.stage_same(test, S, (d0, d1), (e0, e1))
+    assert msg is None, msg
+    msg = P.stage_check(test, S, d0, d1)
+    assert msg is None, "device / oracle: " + msg
