@@ -204,6 +204,9 @@ TL_FN double tl_min_rows(const double *ltg, int j0, int n, double m, bool take_f
     const int last = j0 + n - 1;
     for (int j = j0; j <= last; j += 4) {
         const double a = ltg[j], b = ltg[j + 1 <= last ? j + 1 : last], c = ltg[j + 2 <= last ? j + 2 : last], d = ltg[j + 3 <= last ? j + 3 : last];
+        // (Not tlm_min_lt / one v_min_f64, although no row of a real frame is a -0.0: this helper's contract, pinned on the device by the
+        // min_rows family of the stage probe, is the comparison's result on rows of +0.0 and -0.0 too -- the first zero met stays -- and the
+        // instruction orders the zeros.)
         if (take_first && j == j0) m = a; else if (m > a) m = a;
         if (m > b) m = b;
         if (m > c) m = c;

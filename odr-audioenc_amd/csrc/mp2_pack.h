@@ -49,8 +49,10 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
     else if (c < nch && sb < sblimit) {
         unsigned lo = 63;
         for (int gr = 0; gr < 3; gr++) {
-            double m = fabs(L(smp)[gr * 12 + 11]);
-            for (int j = 10; j >= 0; j--) { double t = fabs(L(smp)[gr * 12 + j]); if (t > m) m = t; }
+            // m = fabs(s[11]); if (fabs(s[j]) > m) m = fabs(s[j]) -- one v_max_f64 m, |s[j]|, m per sample (tl_libm.h): magnitudes of subband
+            // samples, which are finite sums of products of 16-bit PCM and window / matrix constants: no NaN, and fabs() leaves no -0.0
+            double m = tlm_maxabs2_gt(L(smp)[gr * 12 + 10], L(smp)[gr * 12 + 11], TLM_MM_SCF);
+            for (int j = 9; j >= 0; j--) m = tlm_maxabs_gt(L(smp)[gr * 12 + j], m, TLM_MM_SCF);
             unsigned idx = tl_sf_index(B->scalefactor, m);
             L(scf)[gr] = (int)idx;
             w.scf[c][gr][sb] = (uint8_t)idx;
@@ -73,8 +75,9 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
                 PV(double, other);
                 TL_SWAP1_F64(other, , smp, [gr * 12 + j]);
                 TL_LANES_BEGIN
-                double t = fabs(.5 * (L(smp)[gr * 12 + j] + L(other)));     // ch0 lane: .5*(L+R)
-                if (j == 11 || t > L(jm)) L(jm) = t;
+                const double h = .5 * (L(smp)[gr * 12 + j] + L(other));     // ch0 lane: .5*(L+R)
+                // t = fabs(h); if (j == 11 || t > jm) jm = t -- a magnitude against a magnitude, both finite (see K2): one v_max_f64 jm, |h|, jm
+                if (j == 11) L(jm) = fabs(h); else L(jm) = tlm_maxabs_gt(h, L(jm), TLM_MM_JSCF);
                 TL_LANES_END
             }
             TL_LANES_BEGIN
@@ -121,7 +124,10 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
         if (c < nch) {
             const double a = w.smr[c][sb], m = w.psy_m[c][sb];
             const double val = B->scale_db[w.minidx[c][sb]];
-            const double top = a > val ? a : val;
+            // a > val ? a : val in one v_max_f64: a is the model's level (ten times a logarithm of a positive normal number, a line's level in
+            // dB, or the 0.0 left for a subband the model does not look at) and val a table entry 20 log10(32768 sf) - 10 -- both finite,
+            // and no entry of the table is a zero, so the pair is never two zeros
+            const double top = tlm_max_gt(a, val, TLM_MM_SMR);
             w.smr[c][sb] = top - m;
         }
         TL_LANES_END
@@ -587,8 +593,8 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
     if (sb < sblimit) {
         unsigned lo = 63;
         for (int gr = 0; gr < 3; gr++) {
-            double m = fabs(L(smp)[gr * 12 + 11]);
-            for (int j = 10; j >= 0; j--) { double t = fabs(L(smp)[gr * 12 + j]); if (t > m) m = t; }
+            double m = tlm_maxabs2_gt(L(smp)[gr * 12 + 10], L(smp)[gr * 12 + 11], TLM_MM_SCF);        // as in tl_encode_frame: finite magnitudes
+            for (int j = 9; j >= 0; j--) m = tlm_maxabs_gt(L(smp)[gr * 12 + j], m, TLM_MM_SCF);
             unsigned idx = tl_sf_index(B->scalefactor, m);
             L(scf)[gr] = (int)idx;
             if (idx < lo) lo = idx;
@@ -610,7 +616,7 @@ TL_FN void tl_encode_pair(TlMainLds &w, const TlBlockShared *TL_RESTRICT B, cons
     } else {
         const double a = w.smr[c][sb], m = w.psy_m[c][sb];
         const double val = B->scale_db[w.minidx[c][sb]];
-        const double top = a > val ? a : val;
+        const double top = tlm_max_gt(a, val, TLM_MM_SMR);               // as in tl_encode_frame: finite, val never a zero
         w.smr[c][sb] = top - m;
     }
     TL_LANES_END

@@ -19,9 +19,11 @@
 // The floor (`energy < 1E-20 ? -200 + POWERNORM : ...`, psycho_1.c:243-246) is one maximum: log10 of the double 1E-20 is exactly -20.0
 // in glibc and in its restatement here (tests/test_libm_agree.py pins it), so 10 * log10(max(e, 1E-20)) + POWERNORM is the reference's
 // value on either side of the test -- (-200.0 + POWERNORM) is the same sum -- and the argument of the logarithm is always normal.
+// tlm_fmax_k (tl_libm.h) is fmax() as the one v_max_f64 e, e, 1E-20: the energy is a sum of squares of finite transform outputs, read from
+// LDS -- never a NaN, so there is nothing for a v_max_f64 e, e, e to quiet first -- and 1E-20 is no zero.
 TL_FN double tl_power_db(double e, const uint64_t *lt)
 {
-    return 10 * tlm_log10_pn(__builtin_fmax(e, 1E-20), lt) + TL_POWERNORM;
+    return 10 * tlm_log10_pn(tlm_fmax_k(e, 1E-20, TLM_MM_POWER), lt) + TL_POWERNORM;
 }
 // The 512 logarithms of a channel in two halves (tl_libm.h: tlm_log10_main_pn / tlm_log10_near1_pn).  About one argument in eleven takes
 // e_log.c's "close to 1.0" branch (26 operations the other ten have no use for -- and every wave of 64 has some): tl_power_db_main runs
@@ -30,7 +32,7 @@ TL_FN double tl_power_db(double e, const uint64_t *lt)
 // level overwritten.  One or two such passes per channel instead of eight.
 TL_FN double tl_power_db_main(double e, const uint64_t *lt, bool *near1)
 {
-    return 10 * tlm_log10_main_pn(__builtin_fmax(e, 1E-20), lt, near1) + TL_POWERNORM;
+    return 10 * tlm_log10_main_pn(tlm_fmax_k(e, 1E-20, TLM_MM_POWER), lt, near1) + TL_POWERNORM;
 }
 #define TL_DEFER(w) ((uint16_t *)(w).cinfo)
 TL_FN void tl_power_near1(TlPsyLds &w, int pos0, int cnt)
@@ -39,7 +41,7 @@ TL_FN void tl_power_near1(TlPsyLds &w, int pos0, int cnt)
     if (lane < cnt) {
         const int i = TL_DEFER(w)[pos0 + lane];
         const double e = w.u.fft[TL_EX(i)];
-        TL_PX(w)[i] = 10 * tlm_log10_near1_pn(__builtin_fmax(e, 1E-20)) + TL_POWERNORM;
+        TL_PX(w)[i] = 10 * tlm_log10_near1_pn(tlm_fmax_k(e, 1E-20, TLM_MM_POWER)) + TL_POWERNORM;
     }
     TL_LANES_END
 }
@@ -79,8 +81,19 @@ TL_FN void tl_cand_chunk(TlPsyLds &w, int c8, int &ncand)
     const bool has = run != 0;
     const double max = pk - 7;
     bool fail = false;
+    if constexpr (PSY3) {
 #pragma unroll
-    for (int j = 2; j <= RMAX; j++) fail = fail || (PSY3 ? (pk - a[j]) < 7.0 : max < a[j]);
+        for (int j = 2; j <= RMAX; j++) fail = fail || (pk - a[j]) < 7.0;
+    } else if constexpr (RMAX >= 2) {
+        // `fail = fail || max < a[j]` over the neighbours: max is below one of them if and only if it is below the largest.  The compiler
+        // finds that form by itself, but must first quiet every level it loaded (a v_max_f64 a, a, a each, one per neighbour): the levels
+        // are 10 log10 of a normal number + TL_POWERNORM, finite and never a -0.0 (and `<` does not tell the zeros apart), so the running
+        // maximum is one v_max_f64 per neighbour
+        double top = a[2];
+#pragma unroll
+        for (int j = 3; j <= RMAX; j++) top = tlm_max_gt(a[j], top, TLM_MM_CAND);
+        fail = max < top;
+    }
     cnd = cnd && !(has && fail);
     // The LEFT-hand neighbours are not looked at here: what they decide depends on the walk, and the walk looks at them for the
     // candidates alone (tl_cand_left) -- a few dozen lines instead of five hundred.
@@ -576,7 +589,9 @@ TL_FN void tl_psy1_thresholds(TlPsyLds &w, const double *TL_RESTRICT db, const T
             if (base != 1) {                                         // (a second pass is a 4-line tail at most; the branch is wave-uniform)
                 bk0 = C->p1_bark[k0]; bk1 = C->p1_bark[h1 ? k1 : k0]; hr0 = C->p1_hear[k0]; hr1 = C->p1_hear[h1 ? k1 : k0];
             }
-            const double blo = (bk0 < bk1 ? bk0 : bk1) - 8.0, bhi = (bk0 < bk1 ? bk1 : bk0) + 3.0;
+            // (bk0 < bk1 ? bk0 : bk1) and (bk0 < bk1 ? bk1 : bk0), which is bk1 > bk0 ? bk1 : bk0, in one v_min_f64 / v_max_f64 each: bark values of
+            // table lines 1 and up are positive and finite
+            const double blo = tlm_min_lt(bk0, bk1, TLM_MM_BARK) - 8.0, bhi = tlm_max_gt(bk1, bk0, TLM_MM_BARK) + 3.0;
             const TlMasker *mk = TL_MK4(w);
             const int nm = ntone + nnoise;
             int a0, a1, b0, b1;                                     // spans inside the tone part and inside the noise part
@@ -1166,7 +1181,8 @@ TL_FN int tl_psy3_front(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double
         // subband 4 it + r: the maximum sits in lane 16 r + 15; the record keeps it in lane 4 it + r (the encoder takes the
         // maximum with the scalefactor level, psycho_3.c:180-182)
         PV(double, xm);
-        TL_LANES_BEGIN L(xm) = TL_DBMIN < L(pxm) ? L(pxm) : TL_DBMIN; TL_LANES_END
+        // TL_DBMIN < pxm ? pxm : TL_DBMIN is pxm > TL_DBMIN ? pxm : TL_DBMIN, one v_max_f64: a row's maximum of finite levels against -200.0
+        TL_LANES_BEGIN L(xm) = tlm_max_gt_k(L(pxm), TL_DBMIN, TLM_MM_XMAX); TL_LANES_END
         TL_LANES_BEGIN
         {
             const double v = TL_OTHER(xm, , 16 * (lane & 3) + 15);
@@ -1469,8 +1485,10 @@ TL_FN void tl_psy3_back(TlPsyLds &w, const double *TL_RESTRICT db, const TlConfi
         const double b0 = L(sb0), b1 = L(sb1);
         const TlMasker *mk = TL_MK4(w);
         int ta0, ta1, tb0, tb1;
-        if (srt) tl_mask_spans_sorted<64, 32>(TL_MK_BARK(w), ntone, nnoise, (b0 < b1 ? b0 : b1) - 8.0, (b0 < b1 ? b1 : b0) + 3.0, ta0, ta1, tb0, tb1);
-        else tl_mask_spans(mk, ntone + nnoise, ntone, (b0 < b1 ? b0 : b1) - 8.0, (b0 < b1 ? b1 : b0) + 3.0, ta0, ta1, tb0, tb1);
+        // (b0 < b1 ? b0 : b1) and (b0 < b1 ? b1 : b0) as in tl_psy1_thresholds: bark values are finite and none is negative, -0.0 included
+        const double blo = tlm_min_lt(b0, b1, TLM_MM_BARK) - 8.0, bhi = tlm_max_gt(b1, b0, TLM_MM_BARK) + 3.0;
+        if (srt) tl_mask_spans_sorted<64, 32>(TL_MK_BARK(w), ntone, nnoise, blo, bhi, ta0, ta1, tb0, tb1);
+        else tl_mask_spans(mk, ntone + nnoise, ntone, blo, bhi, ta0, ta1, tb0, tb1);
         double lt0 = TL_DBMIN, ln0 = TL_DBMIN, lt1 = TL_DBMIN, ln1 = TL_DBMIN;
         uint32_t far_hi = 0xC0F00000u;
         TL_PIN(far_hi);

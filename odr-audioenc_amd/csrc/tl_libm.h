@@ -118,6 +118,73 @@ __device__ inline __attribute__((always_inline)) double tlm_max_nn_(double a, do
 #define TLM_MIN_NN(a, b) ((b) < (a) ? (b) : (a))
 #define TLM_MAX_NN(a, b) ((a) < (b) ? (b) : (a))
 #endif
+// The frame kernels' forms of the same two instructions (models 0, 1 and 3: mp2_pack.h, mp2_psy13.h), each NAMED AFTER THE STATEMENT
+// IT REPLACES and, on the host and in the emulation, that very statement -- so the lane loops and the oracle compute what they always did:
+//   tlm_max_gt(t, m)       t > m ? t : m                              (`if (t > m) m = t`, `a > val ? a : val`, `b0 < b1 ? b1 : b0`)
+//   tlm_min_lt(t, m)       t < m ? t : m                              (`b0 < b1 ? b0 : b1`)
+//   tlm_maxabs_gt(x, m)    fabs(x) > m ? fabs(x) : m                  (the |x| source modifier: no v_and_b32 makes the magnitude first)
+//   tlm_maxabs2_gt(x, y)   fabs(x) > fabs(y) ? fabs(x) : fabs(y)      (the first step of a running maximum of magnitudes)
+//   tlm_max_gt_k(t, k)     t > k ? t : k, k a constant (a scalar pair instead of two v_mov_b32)
+//   tlm_fmax_k(e, k)       fmax(e, k), k a constant                   (no v_max_f64 e, e, e to quiet an operand that came from memory)
+// Without a fast-math flag the compiler must keep compare + two v_cndmask_b32 for the comparisons (and a v_and_b32 for a magnitude): the statement and the
+// instruction differ when an operand is a NaN or the operands are zeros of opposite sign.  The precondition of every caller is that neither
+// occurs; each site says why, and reports its operand pair to TL_DBG_MINMAX, which counts in the emulation the pairs that break it
+// (emu_minmax_stats; tests/test_minmax_forms_emu.py wants zero).  The hook is an empty macro everywhere else.
+enum { TLM_MM_SCF, TLM_MM_JSCF, TLM_MM_SMR, TLM_MM_POWER, TLM_MM_BARK, TLM_MM_CAND, TLM_MM_XMAX, TLM_MM_SITES };
+#if defined(TL_EMULATE)
+static long tlm_mm_pairs[TLM_MM_SITES], tlm_mm_unsafe[TLM_MM_SITES];
+static inline void tlm_mm_report(int site, double a, double b)
+{
+    const uint64_t ua = tlm_d2u(a), ub = tlm_d2u(b);
+    const bool nan = a != a || b != b, zeros = ((ua | ub) << 1) == 0 && ((ua ^ ub) >> 63) != 0;
+    tlm_mm_pairs[site]++;
+    if (nan || zeros) tlm_mm_unsafe[site]++;
+}
+#define TL_DBG_MINMAX(site, a, b) tlm_mm_report((site), (a), (b))
+// out[0]: unsafe pairs of all sites, out[1]: pairs of all sites, out[2 + 2 s] / out[3 + 2 s]: pairs / unsafe pairs of site s
+extern "C" __attribute__((weak, visibility("default"))) void emu_minmax_stats(long *out)
+{
+    out[0] = out[1] = 0;
+    for (int s = 0; s < TLM_MM_SITES; s++) { out[2 + 2 * s] = tlm_mm_pairs[s]; out[3 + 2 * s] = tlm_mm_unsafe[s]; out[1] += tlm_mm_pairs[s]; out[0] += tlm_mm_unsafe[s]; }
+}
+#else
+#define TL_DBG_MINMAX(site, a, b) ((void)0)
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ inline __attribute__((always_inline)) double tlm_max_gt(double t, double m, int site) { return tlm_max_nn_(t, m); }
+__device__ inline __attribute__((always_inline)) double tlm_min_lt(double t, double m, int site) { return tlm_min_nn_(t, m); }
+__device__ inline __attribute__((always_inline)) double tlm_maxabs_gt(double x, double m, int site)
+{
+    double r;
+    asm("v_max_f64 %0, |%1|, %2" : "=v"(r) : "v"(x), "v"(m));
+    return r;
+}
+__device__ inline __attribute__((always_inline)) double tlm_maxabs2_gt(double x, double y, int site)
+{
+    double r;
+    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(x), "v"(y));
+    return r;
+}
+__device__ inline __attribute__((always_inline)) double tlm_max_gt_k(double t, double k, int site)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(t), "s"(k));
+    return r;
+}
+__device__ inline __attribute__((always_inline)) double tlm_fmax_k(double e, double k, int site)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(e), "s"(k));
+    return r;
+}
+#else
+TLM_HD double tlm_max_gt(double t, double m, int site) { TL_DBG_MINMAX(site, t, m); return t > m ? t : m; }
+TLM_HD double tlm_min_lt(double t, double m, int site) { TL_DBG_MINMAX(site, t, m); return t < m ? t : m; }
+TLM_HD double tlm_maxabs_gt(double x, double m, int site) { const double t = __builtin_fabs(x); TL_DBG_MINMAX(site, t, m); return t > m ? t : m; }
+TLM_HD double tlm_maxabs2_gt(double x, double y, int site) { const double t = __builtin_fabs(x), m = __builtin_fabs(y); TL_DBG_MINMAX(site, t, m); return t > m ? t : m; }
+TLM_HD double tlm_max_gt_k(double t, double k, int site) { TL_DBG_MINMAX(site, t, k); return t > k ? t : k; }
+TLM_HD double tlm_fmax_k(double e, double k, int site) { TL_DBG_MINMAX(site, e, k); return __builtin_fmax(e, k); }
+#endif
 
 // ------------------------------------------------------------------------------------------------------------
 // log (e_log.c).  TAB = {invc, logc}[128] as bit patterns (global table or an LDS copy of it).
