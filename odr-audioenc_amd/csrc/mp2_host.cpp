@@ -56,7 +56,13 @@ void tl_build_synth_tables(TlSynthTables *Y)
 void tl_build_tables(TlTables *T)
 {
     memset(T, 0, sizeof *T);
-    for (int i = 0; i < 512; i++) { T->enwindow[i] = (double)TL_ENWINDOW_E9[i] / 1e9; T->enwindow_s[i] = T->enwindow[i] / 32768; }
+    for (int i = 0; i < 512; i++) {
+        T->enwindow[i] = (double)TL_ENWINDOW_E9[i] / 1e9;
+        // the filterbank's operand table (mp2_fb.h): rows (i mod 64) 49..63 are only ever subtracted, so they carry the minus; row 48 is
+        // used by no yprime and is the +0.0 row of the lanes that own yprime[0]
+        const int r = i & 63;
+        T->enwindow_s[i] = r == 48 ? 0.0 : (r > 48 ? -(T->enwindow[i] / 32768) : T->enwindow[i] / 32768);
+    }
     for (int i = 0; i < 63; i++) T->scalefactor[i] = (double)TL_SCALEFACTOR_E14[i] / 1e14;
     T->scalefactor[63] = 1e-20;
     for (int q = 0; q < 18; q++) {

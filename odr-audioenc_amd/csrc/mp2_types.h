@@ -42,7 +42,8 @@ struct TlPackTables {
 // fft.c:38-73,1139-1149, encode_new.c:16-100,448-462)
 struct TlTables {
     double enwindow[512];
-    double enwindow_s[512];      // enwindow / 32768: the filterbank scales the coefficient instead of the sample (exact, see mp2_wave.h K1)
+    double enwindow_s[512];      // NOT the window: tl_filterbank's private operand table (mp2_fb.h).  enwindow / 32768 (the filterbank scales the coefficient
+                                 // instead of the sample, exact) with rows (index mod 64) 49..63 negated and row 48 = +0.0, so that yprime is one sum in every lane
     double dct[16][32];
     double hann[1024];
     double hann_s[1024];          // hann[i] / 32768 (exact): the model's window with the sample scaling folded in (tl_psy_spectrum)
