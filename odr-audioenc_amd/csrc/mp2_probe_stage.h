@@ -6,9 +6,13 @@
 // below call each helper alone, the way the stage headers do: the dB-sum table is the kernels' own dblog[0..1001] in LDS, the scalefactor
 // table the block's LDS copy, masker records are TlMasker made by tl_masker_consts where TL_MK4 lies, the bark list lies where TL_MK_BARK
 // lies (with TL_LTG behind it: the readable slack tl_mask_spans_sorted relies on), the frame is a zeroed LDS frame written by all lanes.
+// One layer up, the last form calls the bit allocation alone (mp2_alloc.h: tl_allocate, tl_allocate_pair), one wave per case, with the per-lane
+// constants made as tl_encode_frame / tl_encode_pair make them (mp2_pack.h) and B the workgroup's LDS copy of TlBlockShared: whole frames seldom
+// bring exact ties between cells, a budget that ends on a round's sum, or a refusal followed by a cheaper admission.
 // Lane-SPMD text: it runs on the device (csrc/toolame_probe.hip) and, with -DTL_EMULATE, on the host (tests/emu/mp2_probe_emu.cpp).
 // tests/probelib.py holds the argument sets and the oracles.
 #pragma once
+#include "mp2_host.h"
 #include "mp2_wave.h"
 
 // n = lane-arguments (one lane each) for the first group, cases (one wave each) for the second.  d = double, i = int32, u = uint32, U = uint64.
@@ -30,6 +34,10 @@ enum {
     TLS_BITS,           // in0 U[384 n] six field values per lane, in1 i[384 n] their lengths (0: no field), in2 i[2 n] start offset 0..63, wide (0: tl_put_bits,
                         // 1: tl_put_bits48) -> out0 u[3 F n]: the frame's F words, the same read through tl_get_bit, tl_bswap of each;
                         // out1 u[128 n] per lane tl_crc_upd over its own fields: CRC-16, ScF-CRC
+    TLS_ALLOC,          // in0 d[64 n] the SMR of every lane, in1 i[64 n] its scfsi 0..3 (lane = 2 sb + ch; pair call: lane = 2 sb + unit), in2 i[8 n]:
+                        // allocation table 0..4, nch, jsbound, call (0: tl_allocate, 1: tl_allocate_pair -- two mono streams), adb, adb of unit 1
+                        // (pair call), 0, 0 -- adb as tl_encode_frame passes it: the frame's bits before bbal + 16 + 32 is taken off
+                        // -> out0 i[64 n] ba of every lane (0 in a dead one); out1 i[n] the bits left that tl_allocate returns (0 for the pair call)
     TLS_NFORMS
 };
 #define TLS_LIST 192                                  /* TL_MASKER_MAX barks + 64 of slack: tl_mask_spans_sorted<64, 32> reads up to [ntone + 62] <= [189] */
@@ -49,6 +57,26 @@ struct alignas(16) TlStageLds {
     uint32_t frame[TLS_FRAME_WORDS];
 };
 
+// line, nbal and sblimit of the five allocation tables, as tl_build_config leaves them in TlConfig (mp2_host.cpp): read from a configuration
+// that selects each table.  Global memory on the device, as the configuration record is.
+struct TlsAllocTab { int32_t sblimit[5]; uint8_t line[5][32], nbal[5][32]; };
+static inline const TlsAllocTab *tls_alloc_tab()
+{
+    static TlsAllocTab A;
+    static TlConfig C;
+    static bool built = false;
+    if (!built) {
+        static const struct { long fs; char mode; int kbps; } pick[5] = {{48000, 's', 192}, {32000, 's', 192}, {48000, 'm', 48}, {32000, 'm', 48}, {24000, 's', 64}};
+        for (int t = 0; t < 5; t++) {
+            if (tl_build_config(&C, pick[t].fs, pick[t].mode, pick[t].kbps, 1, 0) != TL_OK || C.tab != t) return nullptr;
+            A.sblimit[t] = C.sblimit;
+            for (int sb = 0; sb < 32; sb++) { A.line[t][sb] = C.line[sb]; A.nbal[t][sb] = C.nbal[sb]; }
+        }
+        built = true;
+    }
+    return &A;
+}
+
 // element counts (in bytes) of the five arrays of a call; 0: the form has no such array
 static inline void tls_bytes(int form, long n, size_t by[5])
 {
@@ -63,6 +91,7 @@ static inline void tls_bytes(int form, long n, size_t by[5])
     case TLS_SPANS: by[0] = 8 * TLS_LIST * N; by[1] = 8 * 128 * N; by[2] = 8 * N; by[3] = 4 * 512 * N; by[4] = 8 * N; break;
     case TLS_MIN_ROWS: by[0] = 8 * TLS_ROWS * N; by[1] = 8 * 64 * N; by[2] = 4 * 192 * N; by[3] = 8 * 64 * N; break;
     case TLS_BITS: by[0] = 8 * 64 * TLS_FIELDS * N; by[1] = 4 * 64 * TLS_FIELDS * N; by[2] = 8 * N; by[3] = 4 * 3 * TLS_FRAME_WORDS * N; by[4] = 4 * 128 * N; break;
+    case TLS_ALLOC: by[0] = 8 * 64 * N; by[1] = 4 * 64 * N; by[2] = 4 * 8 * N; by[3] = 4 * 64 * N; by[4] = 4 * N; break;
     }
 }
 static inline long tls_max_n(int form) { return form < TLS_LANE_FORMS ? (1l << 26) : (1l << 16); }
@@ -133,6 +162,25 @@ static inline bool tls_in_domain(int form, long n, const void *in0, const void *
             if (end > TL_MAX_FRAME_BYTES * 8) return false;                                                                  // every field ends inside the frame
         }
         return true;
+    case TLS_ALLOC: {
+        const TlsAllocTab *A = tls_alloc_tab();
+        if (!A) return false;
+        for (long k = 0; k < n; k++) {
+            const int32_t *p = ic + 8 * k;
+            const int tab = p[0], nch = p[1], jsb = p[2], call = p[3];
+            if (tab < 0 || tab > 4 || (nch != 1 && nch != 2) || (call != 0 && call != 1) || (call == 1 && nch != 1)) return false;
+            const int sbl = A->sblimit[tab];
+            if (jsb != 4 && jsb != 8 && jsb != 12 && jsb != 16 && jsb != sbl) return false;                                   // (above sblimit: joint stereo with tables 2 and 3)
+            int bbal = 0;
+            for (int sb = 0; sb < sbl; sb++) bbal += A->nbal[tab][sb] * (sb < jsb ? nch : 1);
+            for (int u = 0; u <= call; u++) if (p[4 + u] < bbal + 48 || p[4 + u] > 8 * TL_MAX_FRAME_BYTES) return false;    // the budget tl_build_config lets through
+            for (int l = 0; l < 64; l++) {
+                if (ib[64 * k + l] < 0 || ib[64 * k + l] > 3) return false;
+                if (!tls_mag_le(a[64 * k + l], 1000.0)) return false;                                                        // every MNR far from the reference's 999999.0
+            }
+        }
+        return true;
+    }
     }
     return false;
 }
@@ -214,7 +262,7 @@ TL_FN void tl_probe_stage_lanes(int form, TlStageLds &w, const double *db, const
     }
 }
 
-// one case, one wave
+// one case, one wave (the helper forms; the allocation form has a body of its own below: it takes the tables the helpers do not)
 TL_FN void tl_probe_stage_case(int form, TlStageLds &w, long k, const void *in0, const void *in1, const void *in2, void *out0, void *out1)
 {
     const int32_t *ic = (const int32_t *)in2;
@@ -296,4 +344,44 @@ TL_FN void tl_probe_stage_case(int form, TlStageLds &w, long k, const void *in0,
     } break;
     default: break;
     }
+}
+
+// one case of TLS_ALLOC, one wave.  B: the workgroup's LDS copy of TlBlockShared on the device, A: the allocation tables
+TL_FN void tl_probe_alloc_case(const TlBlockShared *TL_RESTRICT B, const TlsAllocTab *TL_RESTRICT A, long k, const void *in0, const void *in1, const void *in2, void *out0, void *out1)
+{
+    const int32_t *ic = (const int32_t *)in2;
+    const double *smr = (const double *)in0 + 64 * k;
+    const int32_t *sel = (const int32_t *)in1 + 64 * k, *p = ic + 8 * k;
+    const int tab = TL_UNI_I(p[0]), nch = TL_UNI_I(p[1]), jsbound = TL_UNI_I(p[2]), call = TL_UNI_I(p[3]), adb0 = TL_UNI_I(p[4]), adb1 = TL_UNI_I(p[5]);
+    const int sblimit = TL_UNI_I(A->sblimit[tab]);
+    // the per-lane constants as the encoder makes them (mp2_pack.h: a_ln / a_nbal from the configuration's line and nbal, a_sfs / a_sfs_o from
+    // the cell's and the partner channel's scfsi)
+    PV(int, a_ln); PV(int, a_nbal); PV(int, a_sfs); PV(int, a_sfs_o); PV(double, a_smr); PV(int, ba);
+    int left = 0;
+    if (call == 0) {
+        TL_LANES_BEGIN
+        const int c = lane & 1, sb = lane >> 1;
+        const bool live = c < nch && sb < sblimit;
+        L(a_ln) = live ? A->line[tab][sb] : 0;
+        L(a_nbal) = live ? A->nbal[tab][sb] : 0;
+        L(a_sfs) = live ? 6 * tl_sfs_count((unsigned)sel[lane]) : 0;
+        L(a_sfs_o) = (live && nch == 2) ? 6 * tl_sfs_count((unsigned)sel[lane ^ 1]) : 0;
+        L(a_smr) = live ? smr[lane] : 0.0;
+        TL_LANES_END
+        left = tl_allocate(B, adb0, nch, sblimit, jsbound, a_ln, a_nbal, a_sfs, a_sfs_o, a_smr, ba);
+    } else {
+        TL_LANES_BEGIN
+        const int sb = lane >> 1;
+        const bool live = sb < sblimit;
+        L(a_ln) = live ? A->line[tab][sb] : 0;
+        L(a_nbal) = live ? A->nbal[tab][sb] : 0;
+        L(a_sfs) = live ? 6 * tl_sfs_count((unsigned)sel[lane]) : 0;
+        L(a_smr) = live ? smr[lane] : 0.0;
+        TL_LANES_END
+        tl_allocate_pair(B, adb0, adb1, sblimit, a_ln, a_nbal, a_sfs, a_smr, ba);
+    }
+    TL_LANES_BEGIN
+    ((int32_t *)out0)[64 * k + lane] = L(ba);
+    if (lane == 0) ((int32_t *)out1)[k] = left;
+    TL_LANES_END
 }

@@ -38,7 +38,9 @@ int tlb_debug_probe_wave(int prim, int nwaves, const void *in, const void *in2, 
 /* The third family (csrc/mp2_probe_stage.h): ONE group of the stage helpers of csrc/mp2_dbsum.h (form: TLS_ADD_DB ...) over n lane-arguments or n cases of a
  * wave; the arrays and their layouts are stated at the enum, an array a form does not have may be NULL.  HOST pointers, the library's memory owner, one
  * launch, waited for, copied out, like the two above.  TLB_ERR_ARG for an unknown form, n <= 0, a missing pointer and for ANY argument or case outside
- * the form's stated domain (tls_in_domain) -- checked on the host before anything is queued: the helpers make LDS indexes from counts, rows and lengths. */
+ * the form's stated domain (tls_in_domain) -- checked on the host before anything is queued: the helpers make LDS indexes from counts, rows and lengths.
+ * The last form, TLS_ALLOC, is one layer up: the bit allocation of csrc/mp2_alloc.h alone (tl_allocate, or tl_allocate_pair for two mono streams), one
+ * wave per case, from an allocation table, nch, jsbound, the frame's bits and per lane an SMR and a scfsi; it returns ba of all 64 lanes and the bits left. */
 int tlb_debug_probe_stage(int form, long n, const void *in0, const void *in1, const void *in2, void *out0, void *out1);
 #ifdef __cplusplus
 }

@@ -33,15 +33,19 @@ __global__ void __launch_bounds__(256) tl_probe_wave_kernel(int prim, int nwaves
 }
 
 // the stage helpers (mp2_probe_stage.h): 256 threads = four waves, each with its own TlStageLds; the dB-sum table and the scalefactor table are copied
-// into the workgroup's LDS as the model phase and the encode prologue keep them.  Lane forms: 64 consecutive arguments a wave; case forms: one case a wave.
-__global__ void __launch_bounds__(256) tl_probe_stage_kernel(int form, long n, const double *dblog, const double *sftab, const void *in0, const void *in1,
-                                                             const void *in2, void *out0, void *out1)
+// into the workgroup's LDS as the model phase and the encode prologue keep them, and for the allocation form TlBlockShared, where the frame kernel keeps it.
+// Lane forms: 64 consecutive arguments a wave; case forms: one case a wave.
+__global__ void __launch_bounds__(256) tl_probe_stage_kernel(int form, long n, const double *dblog, const double *sftab, const TlBlockShared *shared,
+                                                             const TlsAllocTab *atab, const void *in0, const void *in1, const void *in2, void *out0, void *out1)
 {
+    static_assert(sizeof(TlBlockShared) % 8 == 0, "copied as doubles");
+    __shared__ TlBlockShared blk;
     __shared__ __attribute__((aligned(16))) double dbt[1002];
     __shared__ __attribute__((aligned(16))) double sfl[64];
     __shared__ TlStageLds lds[4];
     for (int i = (int)threadIdx.x; i < 1002; i += 256) dbt[i] = dblog[i];
     if (threadIdx.x < 64) sfl[threadIdx.x] = sftab[threadIdx.x];
+    if (form == TLS_ALLOC) for (int i = (int)threadIdx.x; i < (int)(sizeof(TlBlockShared) / 8); i += 256) ((double *)&blk)[i] = ((const double *)shared)[i];
     __syncthreads();
     const int wave = (int)(threadIdx.x >> 6);
     if (form < TLS_LANE_FORMS) {
@@ -51,7 +55,8 @@ __global__ void __launch_bounds__(256) tl_probe_stage_kernel(int form, long n, c
     } else {
         const long k = (long)blockIdx.x * 4 + wave;
         if (k >= n) return;
-        tl_probe_stage_case(form, lds[wave], k, in0, in1, in2, out0, out1);
+        if (form == TLS_ALLOC) tl_probe_alloc_case(&blk, atab, k, in0, in1, in2, out0, out1);
+        else tl_probe_stage_case(form, lds[wave], k, in0, in1, in2, out0, out1);
     }
 }
 
@@ -123,12 +128,16 @@ extern "C" int tlb_debug_probe_stage(int form, long n, const void *in0, const vo
     double *ddb = m.scratch<double>(1002), *dsf = m.scratch<double>(64);
     m.upload(ddb, T.dblog, 1002 * sizeof(double));
     m.upload(dsf, T.shared.scalefactor, 64 * sizeof(double));
+    TlBlockShared *dsh = m.scratch<TlBlockShared>(1);
+    TlsAllocTab *dat = m.scratch<TlsAllocTab>(1);
+    m.upload(dsh, &T.shared, sizeof(TlBlockShared));
+    if (form == TLS_ALLOC) m.upload(dat, tls_alloc_tab(), sizeof(TlsAllocTab));      // (not NULL: tls_in_domain has passed)
     char *din[3], *dout[2];
     for (int k = 0; k < 3; k++) { din[k] = m.dev<char>(by[k]); if (by[k]) m.upload(din[k], hin[k], by[k]); }
     for (int k = 0; k < 2; k++) dout[k] = m.dev<char>(by[3 + k]);
     if (!m.settle()) return TLB_ERR_HIP;
     const long per = form < TLS_LANE_FORMS ? 256 : 4;
-    tl_probe_stage_kernel<<<dim3((unsigned)((n + per - 1) / per)), dim3(256), 0, 0>>>(form, n, ddb, dsf, din[0], din[1], din[2], dout[0], dout[1]);
+    tl_probe_stage_kernel<<<dim3((unsigned)((n + per - 1) / per)), dim3(256), 0, 0>>>(form, n, ddb, dsf, dsh, dat, din[0], din[1], din[2], dout[0], dout[1]);
     TLP_HIP(hipGetLastError());
     TLP_HIP(hipDeviceSynchronize());
     for (int k = 0; k < 2; k++) if (by[3 + k]) TLP_HIP(hipMemcpy(hout[k], dout[k], by[3 + k], hipMemcpyDeviceToHost));

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../odr-audioenc_amd/csrc/mp2_host.h"
 #include "../../odr-audioenc_amd/csrc/mp2_probe.h"
+#include "../../odr-audioenc_amd/csrc/mp2_tables.inc"
 
 extern "C" {
 
@@ -64,6 +65,7 @@ __attribute__((visibility("default"))) int probe_stage(int form, long n, const v
     }
     static TlStageLds w;
     if (form < TLS_LANE_FORMS) for (long i0 = 0; i0 < n; i0 += 64) tl_probe_stage_lanes(form, w, T.dblog, T.shared.scalefactor, i0, n, in0, in1, in2, out0, out1);
+    else if (form == TLS_ALLOC) for (long k = 0; k < n; k++) tl_probe_alloc_case(&T.shared, tls_alloc_tab(), k, in0, in1, in2, out0, out1);
     else for (long k = 0; k < n; k++) tl_probe_stage_case(form, w, k, in0, in1, in2, out0, out1);
     return 0;
 }
@@ -80,6 +82,19 @@ __attribute__((visibility("default"))) int probe_bark_table(int psy, long sample
 }
 // the dB-sum table the probe's kernels read (TlTables::dblog[0..1001]: psycho_1.c:170-178 and its two closing entries) -- data for the oracles
 __attribute__((visibility("default"))) void probe_dbtable(double *out) { static TlTables T; tl_build_tables(&T); for (int i = 0; i < 1002; i++) out[i] = T.dblog[i]; }
+// the Layer II allocation tables of csrc/mp2_tables.inc as they stand there, none of what the kernels derive from them -- data for the oracle of the
+// allocation form: TL_SNR_E2[18], TL_BITS[18], TL_GROUP[18], TL_NBAL[9], TL_STEP_INDEX[144], TL_LINE[160] (255 above sblimit), TL_TABLE_SBLIMIT[5]
+__attribute__((visibility("default"))) void probe_alloc_tables(int32_t *out)
+{
+    int o = 0;
+    for (int i = 0; i < 18; i++) out[o++] = TL_SNR_E2[i];
+    for (int i = 0; i < 18; i++) out[o++] = TL_BITS[i];
+    for (int i = 0; i < 18; i++) out[o++] = TL_GROUP[i];
+    for (int i = 0; i < 9; i++) out[o++] = TL_NBAL[i];
+    for (int i = 0; i < 144; i++) out[o++] = TL_STEP_INDEX[i];
+    for (int i = 0; i < 160; i++) out[o++] = TL_LINE[i];
+    for (int i = 0; i < 5; i++) out[o++] = TL_TABLE_SBLIMIT[i];
+}
 // the scalefactor table the probe's kernels read (TlTables::shared)
 __attribute__((visibility("default"))) void probe_scalefactors(double *out) { static TlTables T; tl_build_tables(&T); for (int i = 0; i < 64; i++) out[i] = T.shared.scalefactor[i]; }
 

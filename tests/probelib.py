@@ -1,6 +1,7 @@
 """Support for tests/test_probe_emu.py and tests/test_probe_gpu.py: the argument sets, the references and the bindings of the probe
 (csrc/mp2_probe.h: every device-path form of csrc/tl_libm.h and every cross-lane primitive of csrc/mp2_wave.h, one by one; csrc/mp2_probe_stage.h:
-every shared stage helper of csrc/mp2_dbsum.h -- its sets and oracles are the last part of this file).
+every shared stage helper of csrc/mp2_dbsum.h and, one layer up, the bit allocation of csrc/mp2_alloc.h alone -- its sets and oracles are the last
+part of this file).
 
 * libm forms: 2^20 arguments per form from numpy.random.default_rng, the distributions of tools/libm_agree.cpp worker() restated inside
   each form's stated domain (the encoder's ranges, every binade of the domain, the neighbourhoods of the routines' branch points), plus
@@ -744,9 +745,9 @@ def check_argument_checks(libm_fn, wave_fn, stage_fn):
 # The third family: the stage helpers of csrc/mp2_dbsum.h (csrc/mp2_probe_stage.h).  Argument sets (fixed seeds) and oracles.  The oracles are
 # written from what the comments of mp2_dbsum.h state, in the branchy shape of the model's description; the assertions are on raw bits and
 # integers, nothing has a tolerance.  Tables (the dB-sum table, the scalefactors, the bark rows) are data read through the emulation library.
-STAGE = {"add_db": 0, "mask": 1, "mnr_key": 2, "sf_index": 3, "div_by": 4, "spans": 5, "min_rows": 6, "bits": 7}
-STAGE_NFORMS = 8
-STAGE_TESTS = ("add_db", "mask", "spans", "min_rows", "mnr_key", "sf_index", "div_by", "put_bits", "put_bits48")
+STAGE = {"add_db": 0, "mask": 1, "mnr_key": 2, "sf_index": 3, "div_by": 4, "spans": 5, "min_rows": 6, "bits": 7, "alloc": 8}
+STAGE_NFORMS = 9
+STAGE_TESTS = ("add_db", "mask", "spans", "min_rows", "mnr_key", "sf_index", "div_by", "put_bits", "put_bits48", "alloc", "alloc_pair")
 NSTAGE_RANDOM = 1 << 18
 TL_DBMIN = -200.0
 FAR_HI = 0xC0F00000
@@ -1422,7 +1423,299 @@ def bits_check(S, out0, out1):
     return None
 
 
+# ---- 9. the bit allocation (csrc/mp2_alloc.h: tl_allocate, tl_allocate_pair), one layer above the helpers
+# The oracle is the reference's own loop (a_bit_allocation_new with maxmnr_new, encode_new.c:1061-1187) restated from its definition, one
+# event at a time: the smallest MNR = SNR - SMR in double, first in (channel, subband) order by the scan's strict `>` against the 999999.0
+# sentinel; the step's price (samples; at a cell's first step the scfsi code and the scalefactors, of both channels above jsbound); a step
+# that does not fit closes its cell for good (used = 2), so does the line's last allocation; above jsbound the partner channel copies the
+# winner's allocation and state.  No key, no round, nothing of csrc/ but the Layer II tables of mp2_tables.inc as they stand there.  All
+# cases advance in lockstep (one event of every unfinished case per pass) -- numpy over the cases, not over the algorithm.  tests/
+# test_alloc_oracle_golden.py pins it to the reference's bit_alloc taps.
+ALLOC_MAX_ADB = 8 * 1728                                                   # 8 * TL_MAX_FRAME_BYTES
+ALLOC_SMALL = 999999.0
+SFS_PER_SCFSI = np.array([3, 2, 1, 2])
+ALLOC_COVER = 32                                                           # cases of each form of call that must meet each coverage condition
+
+
+def _alloc_tables():
+    if "alloc_tables" not in _built:
+        L = emu()
+        buf = np.zeros(18 * 3 + 9 + 144 + 160 + 5, dtype=I32)
+        L.probe_alloc_tables.argtypes, L.probe_alloc_tables.restype = [C.c_void_p], None
+        L.probe_alloc_tables(_ptr(buf))
+        o = np.cumsum([0, 18, 18, 18, 9, 144, 160, 5])
+        snr_e2, bits, group, nbal, step, line, sbl = (buf[o[i]:o[i + 1]].astype(np.int64) for i in range(7))
+        _built["alloc_tables"] = dict(snr=snr_e2 / 100.0, bits12=12 * group * bits, nbal=nbal, step=step.reshape(9, 16), line=line.reshape(5, 32), sblimit=sbl)
+    return _built["alloc_tables"]
+
+
+def _alloc_geometry(tab, nch, jsb):
+    """per case: line and nbal per subband (0 above sblimit), the last allocation of each line, live cells [n, 2, 32], joint subbands, bbal"""
+    T = _alloc_tables()
+    sb = np.arange(32)
+    sbl = T["sblimit"][tab]
+    insb = sb[None, :] < sbl[:, None]
+    line = np.where(insb, T["line"][tab], 0)
+    nbal = np.where(insb, T["nbal"][line], 0)
+    live = insb[:, None, :] & (np.arange(2)[None, :, None] < nch[:, None, None])
+    joint = insb & (nch[:, None] == 2) & (sb[None, :] >= jsb[:, None])
+    bbal = (nbal * np.where(sb[None, :] < jsb[:, None], nch[:, None], 1)).sum(axis=1)
+    return line, (1 << nbal) - 1, live, joint, bbal
+
+
+def alloc_greedy(tab, nch, jsb, adb, smr, scfsi):
+    """n cases.  tab, nch, jsb, adb: int [n]; smr double [n, 2, 32], scfsi [n, 2, 32] (cells that are not live are not looked at)
+    -> dict(ba [n, 2, 32], left [n], ad [n], and the trace: per event e of case i  cell [n, E] (32 ch + sb; -1 behind the case's last event),
+    price [n, E], ok [n, E] (admitted / refused), tied [n, E] (another cell, not the joint partner, had the same MNR), xlevel [n, E] (... at
+    another allocation level), ch1 [n, E] (a joint pair's event won by channel 1))"""
+    T = _alloc_tables()
+    tab, nch, jsb, adb = (np.asarray(v, dtype=np.int64) for v in (tab, nch, jsb, adb))
+    smr = np.asarray(smr, dtype=np.float64)
+    n = tab.size
+    rows = np.arange(n)
+    line, maxa, live, joint, bbal = _alloc_geometry(tab, nch, jsb)
+    ad = adb - (bbal + 16 + 32)
+    snr_of = lambda ln, b: T["snr"][T["step"][ln, b]]
+    b12_of = lambda ln, b: T["bits12"][T["step"][ln, b]]
+    mnr = T["snr"][0] - smr
+    used = np.where(live, 0, 2)
+    ba = np.zeros((n, 2, 32), dtype=np.int64)
+    spent = np.zeros(n, dtype=np.int64)                                    # bspl + bscf + bsel
+    sfs = 6 * SFS_PER_SCFSI[np.asarray(scfsi, dtype=np.int64)]
+    cand = np.where(used != 2, mnr, np.inf)                                # what maxmnr_new may still pick
+    steps = []
+    while True:
+        flat = cand.reshape(n, 64)
+        idx = flat.argmin(axis=1)                                          # the first of equal minima in (ch, sb) order: the scan's strict `>`
+        val = flat[rows, idx]
+        r = np.flatnonzero(val < ALLOC_SMALL)
+        if not r.size:
+            break
+        ch, s = idx[r] // 32, idx[r] % 32
+        oth = 1 - ch
+        ln, cur = line[r, s], ba[r, ch, s]
+        first = used[r, ch, s] == 0
+        jn = joint[r, s]
+        inc = b12_of(ln, cur + 1) - np.where(first, 0, b12_of(ln, cur))
+        seli = np.where(first, 2 + 2 * jn, 0)
+        scale = np.where(first, sfs[r, ch, s] + np.where(jn, sfs[r, oth, s], 0), 0)
+        price = inc + seli + scale
+        ok = ad[r] >= spent[r] + price
+        eq = cand[r] == val[r][:, None, None]
+        ncell = np.where(joint[r], eq[:, 0] | eq[:, 1], eq[:, 0].astype(np.int64) + eq[:, 1]).sum(axis=1)
+        lv_hi, lv_lo = np.where(eq, ba[r], -1).max(axis=(1, 2)), np.where(eq, ba[r], 99).min(axis=(1, 2))
+        steps.append((r, idx[r], price, ok, ncell > 1, (ncell > 1) & (lv_hi != lv_lo), jn & (ch == 1)))
+        nb = cur + ok
+        ba[r, ch, s] = nb
+        spent[r] += np.where(ok, price, 0)
+        u = np.where(ok & (nb < maxa[r, s]), 1, 2)
+        used[r, ch, s] = u
+        mnr[r, ch, s] = np.where(ok, snr_of(ln, nb) - smr[r, ch, s], mnr[r, ch, s])
+        cand[r, ch, s] = np.where(u != 2, mnr[r, ch, s], np.inf)
+        j = np.flatnonzero(jn)                                             # above jsbound the allocation applies to both channels
+        rj, sj, oj = r[j], s[j], oth[j]
+        ba[rj, oj, sj] = nb[j]
+        used[rj, oj, sj] = u[j]
+        mnr[rj, oj, sj] = snr_of(ln[j], nb[j]) - smr[rj, oj, sj]
+        cand[rj, oj, sj] = np.where(u[j] != 2, mnr[rj, oj, sj], np.inf)
+    E = len(steps)
+    out = dict(ba=np.where(live, ba, 0), left=ad - spent, ad=ad, cell=np.full((n, E), -1, dtype=np.int16), price=np.zeros((n, E), dtype=I32),
+               ok=np.zeros((n, E), dtype=bool), tied=np.zeros((n, E), dtype=bool), xlevel=np.zeros((n, E), dtype=bool), ch1=np.zeros((n, E), dtype=bool),
+               saturated=(np.where(live, ba, maxa[:, None, :]) == maxa[:, None, :]).all(axis=(1, 2)))
+    for e, (r, cell, price, ok, tied, xl, c1) in enumerate(steps):
+        out["cell"][r, e], out["price"][r, e], out["ok"][r, e], out["tied"][r, e], out["xlevel"][r, e], out["ch1"][r, e] = cell, price, ok, tied, xl, c1
+    return out
+
+
+def alloc_facts(R):
+    """what the coverage conditions ask of a trace, per case"""
+    ok, there = R["ok"], R["cell"] >= 0
+    E = ok.shape[1]
+    pos = np.arange(E)[None, :]
+    first_no = np.where(there & ~ok, pos, E).min(axis=1) if E else np.zeros(ok.shape[0], dtype=np.int64)
+    last_ok = np.where(ok, pos, -1).max(axis=1) if E else np.full(ok.shape[0], -1)
+    return dict(tied=R["tied"].any(axis=1), xlevel=R["xlevel"].any(axis=1), refused_then_admitted=first_no < last_ok, left_zero=R["left"] == 0,
+                nothing=~ok.any(axis=1), saturated=R["saturated"], ch1=(R["ch1"] & ok).any(axis=1), events=there.sum(axis=1), free=first_no)
+
+
+ALLOC_SMR_KINDS = ("random", "all cells equal", "channels identical", "a short list of integers", "cells at different levels tie", "extremes -200 / 0 / 96",
+                   "upper channel first")
+
+
+def _alloc_smr(g, kind, tab, T):
+    """-> smr [2, 32], scfsi [2, 32]: every cell filled, live or not (what is not live must not matter)"""
+    smr = g.uniform(-30.0, 60.0, (2, 32))
+    sel = g.integers(0, 4, (2, 32))
+    if kind == "all cells equal":
+        smr[:] = g.choice([-7.0, 0.0, 3.5, 20.0, 41.0])
+        if g.integers(0, 2):
+            sel[:] = g.integers(0, 4)
+    elif kind == "channels identical":
+        smr[1] = smr[0]
+        if g.integers(0, 2):
+            sel[1] = sel[0]
+    elif kind == "a short list of integers":
+        smr = g.choice([-3.0, 0.0, 2.0, 5.0, 9.0, 12.0, 20.0], (2, 32))
+    elif kind == "cells at different levels tie":
+        # SMRs that put cells at DIFFERENT allocation levels on the same MNR m: smr = snr(line, level) - m, kept only where snr - smr gives m
+        # back on the bits (m a multiple of 1/64: the difference is then usually exact); two values of m per case
+        line = np.where(T["line"][tab] == 255, 0, T["line"][tab])
+        top = (1 << T["nbal"][line]) - 1
+        for m in g.integers(-20 * 64, 30 * 64, 2) / 64.0:
+            lvl = g.integers(0, np.broadcast_to(top, (2, 32)))
+            snr = T["snr"][T["step"][np.broadcast_to(line, (2, 32)), lvl]]
+            v = snr - m
+            take = (snr - v == m) & (g.random((2, 32)) < 0.45)
+            smr = np.where(take, v, smr)
+    elif kind == "extremes -200 / 0 / 96":
+        smr = g.choice([-200.0, 0.0, 96.0], (2, 32))
+    elif kind == "upper channel first":                                   # channel 1 has the larger SMR, so the smaller MNR: a joint pair acts on the partner's key
+        smr[1] = smr[0] + g.uniform(0.5, 25.0, 32)
+    return smr, sel
+
+
+ALLOC_BUDGETS = ("bbal + 48: nothing fits", "a few bits: nothing fits", "exactly the first event", "exactly the events up to k", "one bit short of the events up to k",
+                 "exactly the events up to k'", "one bit short of the events up to k'", "the largest frame", "random")
+
+
+def _alloc_budget(g, kind, bbal, cum, ncell):
+    """cum: cumulative prices of the case's events at the largest budget, up to its first refusal (the greedy order of every smaller budget starts alike)"""
+    base = int(bbal) + 48
+    if kind == "bbal + 48: nothing fits" or not cum.size:
+        return base
+    if kind == "a few bits: nothing fits":
+        return base + int(g.integers(1, 60))                               # the cheapest first step is 60 + 2 + 6 bits
+    if kind == "exactly the first event":
+        return base + int(cum[0])
+    if kind == "the largest frame":
+        return ALLOC_MAX_ADB
+    if kind == "random":
+        return int(g.integers(base, ALLOC_MAX_ADB + 1)) if g.integers(0, 2) else int(g.integers(base, min(base + 3000, ALLOC_MAX_ADB) + 1))
+    if kind.endswith("k'"):                                                # every cell has stepped the same number of times: the end of a round where all tie
+        k = min(int(ncell) * int(g.integers(1, 4)), cum.size)
+    else:
+        k = int(g.integers(2, cum.size + 1)) if cum.size > 2 else cum.size
+    return min(base + int(cum[k - 1]) - (1 if kind.startswith("one bit short") else 0), ALLOC_MAX_ADB)
+
+
+# the pair call: budgets of unit 0 and unit 1
+ALLOC_PAIR_BUDGETS = (("one bit short of the events up to k", "the largest frame"), ("the largest frame", "one bit short of the events up to k"),
+                      ("one bit short of the events up to k", "one bit short of the events up to k'"), ("one bit short of the events up to k'", "one bit short of the events up to k"),
+                      ("bbal + 48: nothing fits", "the largest frame"), ("the largest frame", "bbal + 48: nothing fits"), ("bbal + 48: nothing fits", "a few bits: nothing fits"),
+                      ("exactly the events up to k", "one bit short of the events up to k"), ("exactly the first event", "random"), ("random", "exactly the first event"),
+                      ("a few bits: nothing fits", "exactly the events up to k'"), ("the largest frame", "the largest frame"), ("exactly the events up to k", "exactly the events up to k'"),
+                      ("random", "one bit short of the events up to k"))
+
+
+def alloc_set(pair):
+    """-> dict(tab, nch, jsb, call [n], adb [n, 2], smr [n, 2, 32], scfsi [n, 2, 32] ([case][ch or unit][sb]), names).  Every table, both nch, every legal
+    jsbound; the SMR kinds of ALLOC_SMR_KINDS; budgets placed on the oracle's trace of the same case at the largest budget"""
+    key = "alloc%d" % pair
+    if key in _args:
+        return _args[key]
+    T = _alloc_tables()
+    g = np.random.default_rng(48 + pair)
+    if pair:
+        cfgs = [(t, 1, int(T["sblimit"][t])) for t in range(5)] * 3
+    else:
+        cfgs = [(t, 1, int(T["sblimit"][t])) for t in range(5)] + [(t, 2, j) for t in range(5) for j in sorted({4, 8, 12, 16, int(T["sblimit"][t])})]
+    base = []                                                              # (tab, nch, jsb, kind, smr, scfsi)
+    for t, nch, jsb in cfgs:
+        for kind in ALLOC_SMR_KINDS:
+            if kind == "upper channel first" and not (nch == 2 and jsb < T["sblimit"][t]) and not pair:
+                kind = "cells at different levels tie"
+            base.append((t, nch, jsb, kind) + _alloc_smr(g, kind, t, T))
+    arr = lambda i: np.array([b[i] for b in base])
+    if pair:                                                               # each unit a mono allocation of its own
+        full = [alloc_greedy(arr(0), arr(1), arr(2), np.full(len(base), ALLOC_MAX_ADB), np.stack([arr(4)[:, u], arr(4)[:, u]], axis=1), np.stack([arr(5)[:, u], arr(5)[:, u]], axis=1)) for u in range(2)]
+    else:
+        full = [alloc_greedy(arr(0), arr(1), arr(2), np.full(len(base), ALLOC_MAX_ADB), arr(4), arr(5))]
+    facts = [alloc_facts(R) for R in full]
+    _, _, live, joint, bbal = _alloc_geometry(arr(0), arr(1), arr(2))
+    ncell = live.sum(axis=(1, 2)) - joint.sum(axis=1)
+    cases = []                                                             # (tab, nch, jsb, adb0, adb1, smr, scfsi, name)
+    for i, (t, nch, jsb, kind, smr, sel) in enumerate(base):
+        cum = [np.cumsum(R["price"][i, :F["free"][i]]) for R, F in zip(full, facts)]
+        if pair:
+            for k0, k1 in ALLOC_PAIR_BUDGETS:
+                cases.append((t, nch, jsb, _alloc_budget(g, k0, bbal[i], cum[0], ncell[i]), _alloc_budget(g, k1, bbal[i], cum[1], ncell[i]), smr, sel, "%s; unit 0: %s, unit 1: %s" % (kind, k0, k1)))
+        else:
+            for k0 in ALLOC_BUDGETS:
+                cases.append((t, nch, jsb, _alloc_budget(g, k0, bbal[i], cum[0], ncell[i]), 0, smr, sel, "%s; %s" % (kind, k0)))
+    nmade = len(cases)
+    nrandom = 1024
+    for _ in range(nrandom):
+        t = int(g.integers(0, 5))
+        nch = 1 if pair else int(g.integers(1, 3))
+        jsb = int(g.choice(sorted({4, 8, 12, 16, int(T["sblimit"][t])}))) if not pair else int(T["sblimit"][t])
+        smr, sel = _alloc_smr(g, "random", t, T)
+        bb = int(_alloc_geometry(np.array([t]), np.array([nch]), np.array([jsb]))[4][0])
+        cases.append((t, nch, jsb, _alloc_budget(g, "random", bb, np.ones(1), 0), _alloc_budget(g, "random", bb, np.ones(1), 0) if pair else 0, smr, sel, "random"))
+    col = lambda i, dt: np.array([c[i] for c in cases], dtype=dt)
+    S = dict(tab=col(0, I32), nch=col(1, I32), jsb=col(2, I32), call=np.full(len(cases), pair, dtype=I32), adb=np.stack([col(3, I32), col(4, I32)], axis=1),
+             smr=col(5, np.float64), scfsi=col(6, I32), names=[c[7] for c in cases], constructed=nmade, random=nrandom)
+    assert len(cases) <= 8192
+    _args[key] = S
+    return S
+
+
+def alloc_oracle(S):
+    """-> (ba per lane [n, 64], bits left [n] (0 for the pair call), the traces: one for tl_allocate, one per unit for tl_allocate_pair).  Made once per set"""
+    if "oracle" not in S:
+        if S["call"][0]:
+            two = lambda x, u: np.stack([x[:, u], x[:, u]], axis=1)
+            R = [alloc_greedy(S["tab"], S["nch"], S["jsb"], S["adb"][:, u], two(S["smr"], u), two(S["scfsi"], u)) for u in range(2)]
+            ba = np.stack([R[0]["ba"][:, 0], R[1]["ba"][:, 0]], axis=2)   # lane 2 sb + u
+            left = np.zeros(S["tab"].size, dtype=np.int64)
+        else:
+            R = [alloc_greedy(S["tab"], S["nch"], S["jsb"], S["adb"][:, 0], S["smr"], S["scfsi"])]
+            ba, left = R[0]["ba"].transpose(0, 2, 1), R[0]["left"]
+        S["oracle"] = (ba.reshape(-1, 64), left, R)
+    return S["oracle"]
+
+
+def _alloc_report(S, who, other, c, got_ba, want_ba, got_left, want_left):
+    """the case, its table / nch / jsbound / budget, the first differing (channel, subband) with both values"""
+    pair = int(S["call"][c])
+    head = "%s, %s / %s: case %d (%s): table %d, nch %d, jsbound %d, adb %s" % (
+        "tl_allocate_pair" if pair else "tl_allocate", who, other, c, S["names"][c], S["tab"][c], S["nch"][c], S["jsb"][c], S["adb"][c].tolist() if pair else int(S["adb"][c, 0]))
+    d = np.flatnonzero(got_ba != want_ba)
+    if d.size:
+        return "%s: %s %d subband %d: ba %d, want %d (%d cells differ)" % (head, "unit" if pair else "channel", d[0] & 1, d[0] >> 1, got_ba[d[0]], want_ba[d[0]], d.size)
+    return "%s: bits left %d, want %d" % (head, got_left, want_left)
+
+
+def alloc_check(S, out0, out1):
+    ba, left, _ = alloc_oracle(S)
+    got = out0.reshape(-1, 64)
+    bad = np.flatnonzero((got != ba).any(axis=1) | (out1 != left))
+    if bad.size:
+        c = int(bad[0])
+        return _alloc_report(S, "result", "oracle", c, got[c], ba[c], out1[c], left[c]) + " (%d cases differ)" % bad.size
+    return None
+
+
+def alloc_coverage(S):
+    """the coverage conditions of the set, from the oracle's traces -> {condition: number of cases}; for the pair call a condition counts where a unit meets it"""
+    _, _, R = alloc_oracle(S)
+    F = [alloc_facts(r) for r in R]
+    names = ["tied", "xlevel", "refused_then_admitted", "left_zero", "nothing", "saturated"] + ([] if S["call"][0] else ["ch1"])
+    cover = {k: int(np.any([f[k] for f in F], axis=0).sum()) for k in names}
+    if S["call"][0]:
+        cover["units_differ"] = int((F[0]["events"] != F[1]["events"]).sum())
+        # what the pair call is about: one unit's events stop short while the other's go on / both stop short / one has nothing from the start
+        short = [f["refused_then_admitted"] | (~f["saturated"] & ~f["nothing"]) for f in F]
+        cover["one_unit_short"] = int((short[0] & F[1]["saturated"] | short[1] & F[0]["saturated"]).sum())
+        cover["both_units_short"] = int((short[0] & short[1]).sum())
+        cover["one_unit_nothing"] = int((F[0]["nothing"] != F[1]["nothing"]).sum())
+    return cover
+
+
 # ---- running a form
+def _form_of(test):
+    return STAGE["bits" if test.startswith("put_bits") else "alloc" if test.startswith("alloc") else test]
+
+
 def run_stage(fn, test):
     """fn = probe_stage of the emulation or tlb_debug_probe_stage of the TEST library -> (rc, S, out0, out1)"""
     f64 = lambda shape: np.full(shape, np.nan)
@@ -1450,11 +1743,18 @@ def run_stage(fn, test):
         S = min_rows_set()
         n = S["col"].shape[0]
         ins, outs = (S["col"], S["m"], S["rows"]), (f64(64 * n), None)
+    elif test.startswith("alloc"):
+        S = alloc_set(1 if test == "alloc_pair" else 0)
+        n = S["tab"].size
+        par = np.zeros((n, 8), dtype=I32)
+        par[:, 0], par[:, 1], par[:, 2], par[:, 3], par[:, 4:6] = S["tab"], S["nch"], S["jsb"], S["call"], S["adb"]
+        ins = (S["smr"].transpose(0, 2, 1), S["scfsi"].transpose(0, 2, 1), par)             # lane = 2 sb + ch (or unit)
+        outs = (np.full(64 * n, -9, dtype=I32), np.full(n, -9, dtype=I32))
     else:
         S = bits_set(1 if test == "put_bits48" else 0)
         n = S["val"].shape[0]
         ins, outs = (S["val"], S["len"], S["par"]), (np.full(3 * FRAME_WORDS * n, 0xdeadbeef, dtype=np.uint32), np.full(128 * n, 0xdeadbeef, dtype=np.uint32))
-    form = STAGE["bits" if test.startswith("put_bits") else test]
+    form = _form_of(test)
     ins = [None if x is None else np.ascontiguousarray(x) for x in ins]
     rc = fn(form, n, _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(outs[0]), _ptr(outs[1]))
     return rc, S, outs[0], outs[1]
@@ -1482,14 +1782,23 @@ def stage_check(test, S, out0, out1):
         return sf_index_check(S["x"], scalefactors(), out0, out1)
     if test == "div_by":
         return div_by_check(S, out0, out1)
+    if test.startswith("alloc"):
+        return alloc_check(S, out0, out1)
     return bits_check(S, out0, out1)
 
 
 def stage_same(test, S, dev, emu_out):
     """device == emulation, every word of both outputs -> None or a message naming the first argument / case that differs and both results"""
     per = {"add_db": (1, 4), "mask": (8, 5), "mnr_key": (1, 0), "sf_index": (2, 1), "div_by": (1, 1), "spans": (512, 2), "min_rows": (64, 0),
-           "put_bits": (3 * FRAME_WORDS, 128), "put_bits48": (3 * FRAME_WORDS, 128)}[test]
+           "put_bits": (3 * FRAME_WORDS, 128), "put_bits48": (3 * FRAME_WORDS, 128), "alloc": (64, 1), "alloc_pair": (64, 1)}[test]
     raw = lambda x: x.view(U64) if x.dtype == np.float64 else x
+    if test.startswith("alloc"):                                          # the case, its parameters and the first differing cell
+        d, e = dev[0].reshape(-1, 64), emu_out[0].reshape(-1, 64)
+        bad = np.flatnonzero((d != e).any(axis=1) | (dev[1] != emu_out[1]))
+        if bad.size:
+            c = int(bad[0])
+            return _alloc_report(S, "device", "emulation", c, d[c], e[c], dev[1][c], emu_out[1][c]) + " (%d cases differ)" % bad.size
+        return None
     for k in range(2):
         if dev[k] is None:
             continue
@@ -1497,7 +1806,7 @@ def stage_same(test, S, dev, emu_out):
         if bad.size:
             i, j = divmod(int(bad[0]), per[k])
             return "%s, device / emulation: output %d, %s %d, word %d: device %#x, emulation %#x (%d words differ)" % (
-                test, k, "argument" if STAGE["bits" if test.startswith("put_bits") else test] < 5 else "case", i, j, int(raw(dev[k])[bad[0]]), int(raw(emu_out[k])[bad[0]]), bad.size)
+                test, k, "argument" if _form_of(test) < 5 else "case", i, j, int(raw(dev[k])[bad[0]]), int(raw(emu_out[k])[bad[0]]), bad.size)
     return None
 
 
@@ -1550,6 +1859,33 @@ def check_stage_argument_checks(fn):
     bad_val = val.copy(); bad_val[0, 0, 0] = U64(1) << U64(30)
     assert call("bits", 2, bad_val, ln, par, bo, bc) == ERR_ARG                                                 # a value wider than its field
     assert call("bits", 2, val, ln, np.array([[0, 0], [64, 0]], dtype=I32), bo, bc) == ERR_ARG
+    # the allocation: one case outside each rule of its domain beside a good one
+    asmr, asel = np.zeros((2, 64)), np.zeros((2, 64), dtype=I32)
+    apar = np.array([[0, 2, 27, 0, 3000, 0, 0, 0], [4, 1, 30, 1, 2000, 1500, 0, 0]], dtype=I32)
+    ao, al = np.zeros(128, dtype=I32), np.zeros(2, dtype=I32)
+
+    def alloc_with(case, **kw):
+        par, smr, sel = apar.copy(), asmr.copy(), asel.copy()
+        for k, v in kw.items():
+            if k == "smr":
+                smr[case, 17] = v
+            elif k == "scfsi":
+                sel[case, 40] = v
+            else:
+                par[case, {"tab": 0, "nch": 1, "jsb": 2, "call": 3, "adb": 4, "adb1": 5}[k]] = v
+        return call("alloc", 2, smr, sel, par, ao, al)
+    assert alloc_with(0) == 0
+    assert alloc_with(0, tab=5) == ERR_ARG and alloc_with(1, tab=-1) == ERR_ARG                                 # tables 0..4
+    assert alloc_with(0, nch=3) == ERR_ARG and alloc_with(0, nch=0) == ERR_ARG
+    assert alloc_with(1, nch=2) == ERR_ARG                                                                      # the pair call is two MONO streams
+    assert alloc_with(0, call=2) == ERR_ARG
+    assert alloc_with(0, jsb=5) == ERR_ARG and alloc_with(0, jsb=30) == ERR_ARG                                 # 4, 8, 12, 16 or the table's sblimit (27)
+    assert alloc_with(0, jsb=16) == 0
+    assert alloc_with(1, scfsi=4) == ERR_ARG and alloc_with(0, scfsi=-1) == ERR_ARG
+    assert alloc_with(0, smr=np.nan) == ERR_ARG and alloc_with(1, smr=1000.5) == ERR_ARG and alloc_with(0, smr=-np.inf) == ERR_ARG
+    assert alloc_with(0, adb=100) == ERR_ARG                                                                    # below bbal + 48: a negative budget
+    assert alloc_with(0, adb=ALLOC_MAX_ADB + 1) == ERR_ARG
+    assert alloc_with(1, adb1=75 + 47) == ERR_ARG and alloc_with(1, adb1=75 + 48) == 0                          # unit 1's budget too (table 4 mono: bbal = 75)
     p = o(16)
     q = _ptr(p)
     assert fn(-1, 2, q, q, q, q, q) == ERR_ARG and fn(STAGE_NFORMS, 2, q, q, q, q, q) == ERR_ARG                # an unknown form

@@ -1,7 +1,12 @@
 """The probe on the host (csrc/mp2_probe.h with -DTL_EMULATE, tests/emu/mp2_probe_emu.cpp): every device-path form of csrc/tl_libm.h against
 this machine's libm, bit for bit, on the full argument sets of tests/probelib.py, and every cross-lane primitive of csrc/mp2_wave.h against
 a numpy oracle written from the primitive's comment on the full case sets, and every shared stage helper of csrc/mp2_dbsum.h
-(csrc/mp2_probe_stage.h) against an oracle written from the definition its comment states, on raw bits and integers.
+(csrc/mp2_probe_stage.h) against an oracle written from the definition its comment states, on raw bits and integers -- and, one layer up, the
+bit allocation alone (csrc/mp2_alloc.h: tl_allocate and tl_allocate_pair, the parameters `alloc` and `alloc_pair`) against the reference's
+greedy loop restated event by event (tests/test_alloc_oracle_golden.py pins that restatement to the reference's taps), on sets built for
+what whole frames seldom bring: exact ties, also between cells at different allocation levels, budgets that end on an event's cumulative
+price or one bit short of it, refusals followed by cheaper admissions, units of a mono pair that stop at different times.  The set's coverage
+conditions are checked from the oracle's trace.
 
 That is what the GPU file (tests/test_probe_gpu.py) rests on: the argument sets lie inside the forms' stated domains (the probe refuses
 anything else), and references, generators and oracles are right before a GPU is involved."""
@@ -78,3 +83,22 @@ def test_stage_helper_is_what_its_definition_says(E, test):
     assert S["constructed"] > 0 and S["random"] >= 256
     msg = P.stage_check(test, S, out0, out1)
     assert msg is None, msg
+
+
+@pytest.mark.parametrize("test", ("alloc", "alloc_pair"))
+def test_allocation_sets_reach_the_hard_cases(E, test):
+    """conditions on the SET, from the oracle's trace (tests/probelib.py alloc_coverage), none of them a measurement: each holds for at least
+    ALLOC_COVER cases of the form of call -- an event with a tied minimum between different cells, one between cells at different allocation
+    levels, a refusal followed by a later admission, bits left exactly 0, nothing admitted, every cell saturated, a joint pair's event won by
+    channel 1 (tl_allocate), and for tl_allocate_pair: the units finish after different numbers of events, one unit stops short while the other
+    runs to the end, both stop short, one unit has nothing while the other goes on.  Every table, both nch, every legal jsbound occur."""
+    S = P.alloc_set(1 if test == "alloc_pair" else 0)
+    cover = P.alloc_coverage(S)
+    short = {k: v for k, v in cover.items() if v < P.ALLOC_COVER}
+    assert not short, "%s: too few cases for %s (all: %s)" % (test, short, cover)
+    T = P._alloc_tables()
+    seen = set(zip(S["tab"].tolist(), S["nch"].tolist(), S["jsb"].tolist()))
+    for t in range(5):
+        want = {(t, 1, int(T["sblimit"][t]))} | (set() if test == "alloc_pair" else {(t, 2, j) for j in (4, 8, 12, 16, int(T["sblimit"][t]))})
+        assert want <= seen, (t, sorted(want - seen))
+    assert S["tab"].size <= 8192

@@ -3,7 +3,9 @@ DEVICE halves of csrc/tl_libm.h and of csrc/mp2_wave.h's cross-lane primitives, 
 tests/probelib.py -- hardware reciprocal / reciprocal-square-root seeds, inline v_fma_f64 / v_min_f64 / v_max_f64, tables as device globals,
 as LDS copies and rearranged (TL_SCT), DPP ladders, permlane swaps, ballots -- and (tlb_debug_probe_stage, csrc/mp2_probe_stage.h) the shared stage helpers
 of csrc/mp2_dbsum.h as the device build compiles them: dB sums, masking terms, masker spans, row minimum, allocation key, scalefactor index, exact
-division, the bit writer (64 lanes' atomicOr into one LDS frame) and the CRC step.
+division, the bit writer (64 lanes' atomicOr into one LDS frame) and the CRC step -- and, one layer up, the bit allocation alone (csrc/mp2_alloc.h:
+tl_allocate and tl_allocate_pair, one wave per case, TlBlockShared in the workgroup's LDS as the frame kernel keeps it) against the reference's greedy
+loop restated event by event, on sets of ties, budget edges and refusals that whole frames seldom bring (the parameters `alloc` and `alloc_pair`).
 
 The hard assertion is device == emulation (tests/emu/mp2_probe_emu.cpp, the host halves through the same text), bit for bit: it does not
 depend on this machine's libm.  tests/test_probe_emu.py has shown the emulation equal to glibc and to the oracles on the same sets, and the
