@@ -8,6 +8,7 @@
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
 //                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
+//                [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
 //   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
 //   header's padding bit, service s takes frame (tick + s) of it (wrapping round), one tick per frame of the file.  No PCM crosses the
@@ -16,6 +17,11 @@
 //   (tlb_tick_set_feed_adapted): on the ticks tlb_tick_feed_want says want no frame the slot stays empty and the file does not advance.
 //   R above the rate of a 24000 Hz encoder (48000, 44100, 32000) is a DOWN FEED (tlb_tick_set_down_feed): every tick takes the one or two
 //   frames tlb_tick_down_feed_want asks for into the stream's two slots, and the device decodes, filters and decimates them.
+//   --feed-drop-every N --feed-drop-run M: lost packets on a strict feed: the last M ticks of every N leave every stream's feed slot empty
+//   (the frames they would have carried are gone: the file advances).  Without --conceal each is 24 ms of silence, cut in hard.
+//   --conceal [HOLD] --conceal-step N: feed concealment (tlb_tick_enable_conceal) on a strict feed: a lost frame is the last good one once
+//   more, N scalefactor-index units (default 3: 6 dB) quieter per lost frame, for HOLD frames (default 4), then the filterbank rings out.
+//   One line at the end: the records summed over the streams -- slots, passed, concealed, muted, loss runs, the longest run.
 //   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
 //   encoder's rate on the device (tlb_tick_set_source): each tick reads tlb_tick_need() source frames per stream, not 1152.  Not together
 //   with --short-every.  R above the rate of a 24000 Hz encoder (48000, 44100, 32000) is a DOWN source (tlb_tick_set_down_source): each tick
@@ -60,7 +66,7 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]] [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
@@ -72,6 +78,7 @@ int main(int argc, char **argv)
     const char *feed_path = nullptr;
     int feed_kbps = 0, feed_channels = 0;
     long feed_rate = 0;
+    int conceal = 0, conceal_step = 3, drop_every = 0, drop_run = 0;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
@@ -88,6 +95,14 @@ int main(int argc, char **argv)
             char *end = nullptr;
             const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
             if (i + 1 < argc && end != argv[i + 1] && !*end) limit_db = v; else i--;
+            continue;
+        }
+        if (k == "--conceal") {                                  // likewise: HOLD is taken when the next argument is a number
+            conceal = 4;
+            char *end = nullptr;
+            const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) conceal = (int)v; else i--;
+            if (conceal < 1 || conceal > TLB_CONCEAL_MAX_HOLD) die("--conceal HOLD: 1..16", conceal);
             continue;
         }
         if (i + 1 >= argc) die("option without a value", 0);
@@ -108,6 +123,9 @@ int main(int argc, char **argv)
         else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
         else if (k == "--feed-rate") feed_rate = std::atol(v);
         else if (k == "--feed-channels") feed_channels = std::atoi(v);
+        else if (k == "--conceal-step") conceal_step = std::atoi(v);
+        else if (k == "--feed-drop-every") drop_every = std::atoi(v);
+        else if (k == "--feed-drop-run") drop_run = std::atoi(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -123,6 +141,8 @@ int main(int argc, char **argv)
     tlb_feed_config feed = {feed_rate ? feed_rate : rate, feed_kbps, feed_channels ? feed_channels : channels};      // the encoder's unless told otherwise
     const bool down_feed = feed_path && feed.samplerate > rate;  // a feed above the encoder's rate: two slots per tick, decoded and decimated
     const bool adapt = !down_feed && (feed.samplerate != rate || feed.channels != channels);
+    if (drop_every < 0 || drop_run < 0 || drop_run > drop_every || (drop_every > 0) != (drop_run > 0)) die("--feed-drop-every N --feed-drop-run M: 1 <= M <= N, both or neither", 0);
+    if ((conceal || drop_every) && (!feed_path || down_feed || adapt)) die("--conceal and --feed-drop-every need a strict --feed (the encoder's rate and channel count)", 0);
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;                              // --feed: where each frame lies in the file
     if (feed_path) {
@@ -170,6 +190,7 @@ int main(int argc, char **argv)
     if (down_feed) { if (int rc = tlb_tick_set_down_feed(t, -1, &feed)) die("tlb_tick_set_down_feed", rc); }      // likewise
     else if (feed_path && !adapt) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);
     if (feed_path && adapt) if (int rc = tlb_tick_set_feed_adapted(t, -1, &feed)) die("tlb_tick_set_feed_adapted", rc);
+    if (conceal) if (int rc = tlb_tick_enable_conceal(t, -1, conceal, conceal_step)) die("tlb_tick_enable_conceal", rc);       // behind the feed, while no tick is in flight
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
@@ -225,7 +246,8 @@ int main(int argc, char **argv)
         uint8_t *fr = tlb_tick_feed(t);                          // pinned [nstreams][tlb_tick_feed_stride()], re-fetched every tick like the PCM
         int32_t *ln = tlb_tick_feed_len(t);                      // pinned [nstreams]: every set comes back all 0
         const size_t stride = (size_t)tlb_tick_feed_stride(t);
-        for (int s = 0; s < nstreams && want; s++) {
+        const bool dropped = drop_every && frames % drop_every >= drop_every - drop_run;      // the packets of this tick are lost: the slots stay empty
+        for (int s = 0; s < nstreams && want && !dropped; s++) {
             const size_t k = (used + (size_t)s) % fpos.size();
             std::memcpy(fr + stride * (size_t)s, &mp2[fpos[k]], flen[k]);
             ln[s] = (int32_t)flen[k];
@@ -260,6 +282,16 @@ int main(int argc, char **argv)
         std::fprintf(stderr, "editick: stream 0: %u short reads, %u ms since its last full read\n", n[0], ms[0]);
     }
     if (feed_path) std::fprintf(stderr, "editick: feed: %zu frames of %d kbps in the file, %ld feed frames did not pass\n", fpos.size(), feed_kbps, bad_feed);
+    if (conceal && frames > 0) {                                 // the records of the last tick (the finish adds nothing), summed over the streams
+        const tlb_conceal_record *r = tlb_tick_conceal(t);
+        unsigned long c[5] = {0, 0, 0, 0, 0};
+        uint32_t longest = 0;
+        for (int s = 0; s < nstreams; s++) {
+            c[0] += r[s].frames; c[1] += r[s].passed; c[2] += r[s].concealed; c[3] += r[s].muted; c[4] += r[s].runs;
+            if (r[s].longest > longest) longest = r[s].longest;
+        }
+        std::fprintf(stderr, "editick: conceal: %lu slots, %lu passed, %lu concealed, %lu muted, %lu runs, longest %u\n", c[0], c[1], c[2], c[3], c[4], longest);
+    }
     unsigned long checked = 0, bad = 0;
     if (monitor) {
         const tlb_monitor_record *r = tlb_tick_monitor(t);

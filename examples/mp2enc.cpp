@@ -7,7 +7,7 @@
 //        -> whole frames -> file                          (what src/odr-audioenc.cpp:1208-1225 re-frames out of the bursts)
 //
 // build: g++ -O2 -std=c++17 examples/mp2enc.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o mp2enc
-// usage: mp2enc in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [--verify]
+// usage: mp2enc in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [--verify] [--from-mp2 [--conceal [HOLD]]]
 // --verify: every frame is read back on the device right after it was encoded (tlb_decode_host: header, CRC-16, ScF-CRC, bit budget);
 // any TLB_DEC_BAD_MASK flag ends the run with exit status 3.
 // --from-mp2: the input is an MPEG Layer II file, a transcode: its first header gives the feed's rate, bitrate and channel count (which are
@@ -17,6 +17,9 @@
 // 48 kHz encoder, stereo for mono, ...; a slot of the call then holds a frame only on the ticks tlb_feed_want_at says want one.
 // A 48, 44.1 or 32 kHz file with -r 24000 is a DOWN FEED (tlb_feed_down_set): a tick has two slots and takes the one or two frames
 // tlb_feed_down_want_at asks for; the device decodes, filters and decimates them (tlb_feed_down_host).
+// --conceal [HOLD] (with --from-mp2, the file's own rate and channel count): feed concealment (tlb_conceal_enable, step 3): a frame of the
+// file that does not pass goes in as the last good frame once more, 6 dB quieter per lost frame, for HOLD frames (default 4), then the
+// filterbank rings out -- not as silence.  One more line at the end: stream 0's record.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -36,7 +39,7 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [--verify] [--from-mp2]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.mp2 [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [--verify] [--from-mp2 [--conceal [HOLD]]]\n", argv[0]);
         return 2;
     }
     long rate = 48000;
@@ -44,10 +47,19 @@ int main(int argc, char **argv)
     char mode = 0;
     double gain_db = 0.0;
     bool verify = false, from_mp2 = false, rate_given = false, channels_given = false;
+    int conceal = 0;
     for (int i = 3; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--verify") { verify = true; i -= 1; continue; }
         if (k == "--from-mp2") { from_mp2 = true; i -= 1; continue; }
+        if (k == "--conceal") {                              // HOLD is taken when the next argument is a number
+            conceal = 4;
+            char *end = nullptr;
+            const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) conceal = (int)v; else i -= 1;
+            if (conceal < 1 || conceal > TLB_CONCEAL_MAX_HOLD) die("--conceal HOLD: 1..16", conceal);
+            continue;
+        }
         if (i + 1 >= argc) die("option without a value", 0);
         const char *v = argv[i + 1];
         if (k == "-r") { rate = std::atol(v); rate_given = true; }
@@ -129,6 +141,8 @@ int main(int argc, char **argv)
     if (down && (err = tlb_feed_down_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_down_set", err);
     if (from_mp2 && !adapt && !down && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
     if (adapt && (err = tlb_feed_set_adapted(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set_adapted", err);
+    if (conceal && (!from_mp2 || adapt || down)) die("--conceal needs --from-mp2 at the file's own rate and channel count (a strict feed)", 0);
+    if (conceal && (err = tlb_conceal_enable(enc, -1, conceal, 3)) != TLB_OK) die("tlb_conceal_enable", err);
     const int fstride = down ? tlb_feed_down_stride(enc) : tlb_feed_stride(enc);
     const size_t per_tick = down ? 2 : 1;                     // feed slots per stream and tick
 
@@ -210,6 +224,12 @@ int main(int argc, char **argv)
                  nframes, nstreams, dt, (double)nframes * nstreams / dt, (double)nframes * 1152.0 / (double)rate / dt, written, tlb_version());
     if (from_mp2) std::fprintf(stderr, "mp2enc: transcoded from %ld Hz, %d kbps, %d channel(s): %zu frames, %ld did not pass and went in as silence\n",
                                feed.samplerate, feed.bitrate, feed.channels, fpos.size(), bad_feed);
+    if (conceal) {
+        std::vector<tlb_conceal_record> rec((size_t)nstreams);
+        if ((err = tlb_conceal_records_host(enc, rec.data())) != TLB_OK) die("tlb_conceal_records_host", err);
+        std::fprintf(stderr, "mp2enc: conceal: %u slots, %u passed, %u concealed, %u muted, %u runs, longest %u\n", rec[0].frames, rec[0].passed, rec[0].concealed,
+                     rec[0].muted, rec[0].runs, rec[0].longest);
+    }
     if (verify) std::fprintf(stderr, "mp2enc: verify ok: %ld frames read back on the device, %ld bad\n", checked, tlb_decode_bad_frames(enc));
     tlb_destroy(enc);
     return 0;

@@ -23,6 +23,10 @@
 //   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
 //   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
+//   --feed-drop-every N --feed-drop-run M (a strict --feed): the last M ticks of every N leave every service's feed slot empty -- lost packets.
+//   --conceal [HOLD] --conceal-step N (a strict --feed): feed concealment (tlb_node_enable_conceal): a lost frame is the last good one once more,
+//   N scalefactor-index units (default 3: 6 dB) quieter per lost frame, for HOLD frames (default 4), then the filterbank rings out.  One line
+//   at the end: the services' records summed -- slots, passed, concealed, muted, loss runs, the longest run.
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file (the services' rate, two channels, K kbps) decoded on the GPUs ahead
 //   of the ingest (tlb_node_set_feed): the file is cut into frames by the arithmetic length and each header's padding bit, service s takes
 //   frame (tick + s) of it, wrapping round; no PCM crosses the link and in.s16le is not opened (give "-").  Not together with --short-every
@@ -74,6 +78,7 @@ struct Ctx {
     const std::vector<size_t> *fpos, *flen;
     std::vector<size_t> *fcur;                               // --feed-rate / --feed-channels (an adapted feed): the next frame of every service; NULL: a strict feed
     bool down_feed;                                          // --feed-rate above the services' rate: two slots per tick, one or two frames as the schedule says
+    int drop_every, drop_run;                                // --feed-drop-every / --feed-drop-run; 0: no tick's packets are lost
 };
 
 // step 1 on shard `g`'s thread: the block's services copy their frame of this tick into the pinned input set
@@ -103,6 +108,7 @@ static void fill(void *vctx, int g, int first, int n)
             die("no feed set free", s);
         }
         size_t f = ((size_t)s + (size_t)c.tick) % c.fpos->size();
+        if (c.drop_every && c.tick % c.drop_every >= c.drop_every - c.drop_run) continue;      // this tick's packets are lost: the slot stays empty
         if (c.fcur) {                                            // an adapted feed: a frame only where this tick wants one, and the file advances only then
             if (tlb_node_feed_want(c.nd, s) <= 0) continue;
             f = (*c.fcur)[(size_t)s]++ % c.fpos->size();
@@ -154,7 +160,7 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]] [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]\n", argv[0]);
         return 2;
     }
     int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0, limit = 0, limit_release = 0;
@@ -165,6 +171,7 @@ int main(int argc, char **argv)
     int feed_kbps = 0, feed_channels = 2;
     long feed_rate = 0;                                      // 0: the services' own
     std::string devs, outpath, feed_path;
+    int conceal = 0, conceal_step = 3, drop_every = 0, drop_run = 0;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
@@ -181,6 +188,14 @@ int main(int argc, char **argv)
             char *end = nullptr;
             const double v = i + 1 < argc ? std::strtod(argv[i + 1], &end) : 0.0;
             if (i + 1 < argc && end != argv[i + 1] && !*end) limit_db = v; else i--;
+            continue;
+        }
+        if (k == "--conceal") {                                  // likewise: HOLD is taken when the next argument is a number
+            conceal = 4;
+            char *end = nullptr;
+            const long v = i + 1 < argc ? std::strtol(argv[i + 1], &end, 10) : 0;
+            if (i + 1 < argc && end != argv[i + 1] && !*end) conceal = (int)v; else i--;
+            if (conceal < 1 || conceal > TLB_CONCEAL_MAX_HOLD) die("--conceal HOLD: 1..16", conceal);
             continue;
         }
         if (i + 1 >= argc) die("option without a value", 0);
@@ -202,6 +217,9 @@ int main(int argc, char **argv)
         else if (k == "--feed-bitrate") feed_kbps = std::atoi(v);
         else if (k == "--feed-rate") feed_rate = std::atol(v);
         else if (k == "--feed-channels") feed_channels = std::atoi(v);
+        else if (k == "--conceal-step") conceal_step = std::atoi(v);
+        else if (k == "--feed-drop-every") drop_every = std::atoi(v);
+        else if (k == "--feed-drop-run") drop_run = std::atoi(v);
         else if (k == "--monitor") { monitor = !std::strcmp(v, "check") ? TLB_MONITOR_CHECK : !std::strcmp(v, "audio") ? TLB_MONITOR_AUDIO : 0; if (!monitor) die("--monitor check|audio", 0); }
         else die("unknown option", 0);
     }
@@ -224,6 +242,8 @@ int main(int argc, char **argv)
     tlb_feed_config feed = {feed_rate, feed_kbps, feed_channels};   // the services' own rate and channel count unless told otherwise
     const bool down_feed = !feed_path.empty() && feed_rate > rate;   // a feed above the services' rate (tlb_node_set_down_feed)
     const bool adapt = !down_feed && (feed_rate != rate || feed_channels != 2);
+    if (drop_every < 0 || drop_run < 0 || drop_run > drop_every || (drop_every > 0) != (drop_run > 0)) die("--feed-drop-every N --feed-drop-run M: 1 <= M <= N, both or neither", 0);
+    if ((conceal || drop_every) && (feed_path.empty() || down_feed || adapt)) die("--conceal and --feed-drop-every need a strict --feed (the services' rate, two channels)", 0);
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;
     if (!feed_path.empty()) {
@@ -295,6 +315,8 @@ int main(int argc, char **argv)
     if (down_feed) { if (int rc = tlb_node_set_down_feed(nd, -1, &feed)) die("tlb_node_set_down_feed", rc); }       // between steps; a restarted shard's down feeds are set again at tick 0
     else if (!feed_path.empty())
         if (int rc = adapt ? tlb_node_set_feed_adapted(nd, -1, &feed) : tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
+    if (conceal)
+        if (int rc = tlb_node_enable_conceal(nd, -1, conceal, conceal_step)) die("tlb_node_enable_conceal", rc);      // behind the feeds, between steps; a restarted shard's is set again
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare)
         if (int rc = tlb_node_enable_compare(nd, &cparams)) die("tlb_node_enable_compare", rc);         // after the audio monitor, before the first submit
@@ -304,7 +326,7 @@ int main(int argc, char **argv)
     std::vector<size_t> spos((size_t)nstreams), fcur((size_t)nstreams);
     for (int s = 0; s < nstreams; s++) fcur[(size_t)s] = (size_t)s;     // an adapted feed: service s starts s frames into the file
     for (int s = 0; s < nstreams && !pcm.empty(); s++) spos[(size_t)s] = ((size_t)s * 1152) % (pcm.size() / 2);
-    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, down, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt || down_feed ? &fcur : nullptr, down_feed};
+    Ctx ctx{nd, &pcm, nframes_in, 0, &hash, &packets, &bytes, short_every, short_by, source_rate, down, &spos, feed_path.empty() ? nullptr : &mp2, &fpos, &flen, adapt || down_feed ? &fcur : nullptr, down_feed, drop_every, drop_run};
     std::FILE *fo = outpath.empty() ? nullptr : std::fopen(outpath.c_str(), "wb");
     int alarms = 0; long taps = 0;                               // compare monitor: times a service's mismatch_run reached 3
     uint32_t longest_run = 0;                                    // confidence monitor: the longest bad run any service has shown after a tick
@@ -400,6 +422,16 @@ int main(int argc, char **argv)
         unsigned long total = 0; uint32_t worst = 0;
         for (int s = 0; s < nstreams; s++) { total += tlb_node_underruns(nd, s); const uint32_t ms = tlb_node_underrun_ms(nd, s); if (ms > worst) worst = ms; }
         std::fprintf(stderr, "nodetick: %lu short reads in all, longest time without a full read %u ms\n", total, worst);
+    }
+    if (conceal) {                                                        // the records of the last step, summed (NULL: the service's shard is down or late)
+        unsigned long c[5] = {0, 0, 0, 0, 0};
+        uint32_t longest = 0;
+        for (int s = 0; s < nstreams; s++)
+            if (const tlb_conceal_record *r = tlb_node_conceal(nd, s)) {
+                c[0] += r->frames; c[1] += r->passed; c[2] += r->concealed; c[3] += r->muted; c[4] += r->runs;
+                if (r->longest > longest) longest = r->longest;
+            }
+        std::fprintf(stderr, "nodetick: conceal: %lu slots, %lu passed, %lu concealed, %lu muted, %lu runs, longest %u\n", c[0], c[1], c[2], c[3], c[4], longest);
     }
     unsigned long checked = 0, bad = 0;
     if (monitor) {                                                        // (a restarted shard's records count from its restart)

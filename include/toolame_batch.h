@@ -1364,6 +1364,76 @@ int tlb_node_enable_limiter(tlb_node *nd, const tlb_limiter_params *params);
 const tlb_limiter_record *tlb_node_limiter(const tlb_node *nd, int stream);
 int tlb_node_limiter_reset(tlb_node *nd, int stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CONCEALMENT of lost frames on a strict Layer II feed (tlb_conceal_*; csrc/mp2_conceal.h, csrc/toolame_conceal.hip).  Without it "an empty
+ * slot or a frame that does not pass is silence" (tlb_feed_*): 24 ms of digital zero cut in hard, and the good frame behind it synthesised
+ * over a silent filter history -- two discontinuities per lost packet, which the encoder then broadcasts.  With it a lost frame is the last
+ * good frame once more, quieter with every repeat, and the good frame behind a loss continues from that repeat.
+ * THE RULE.  The reference has no concealment (its inputs leave it to their decoders), so this is the definition (tests/conceallib.py
+ * restates it).  Per stream two parameters: hold, 1..TLB_CONCEAL_MAX_HOLD frames, and step, 1..TLB_CONCEAL_MAX_STEP scalefactor-index units
+ * per lost frame (scalefactor[i] = 2^(1 - i/3): 3 is 6.02 dB; index 63 is 1e-20).
+ *   A slot PASSES when its feed report has none of TLB_DEC_BAD_MASK | TLB_DEC_EMPTY, else it is LOST.
+ *   G     the bytes of the last slot that passed; none before the first passing slot and after a reset
+ *   k     consecutive lost slots ending at this one, 0 for a passing slot; it carries across calls
+ *   o(k)  o(0) = 0; o(k) = step * k for 1 <= k <= hold; o(k) = MUTE for k > hold
+ *   "G at offset o" is G parsed as a feed frame, every cell's three scalefactor indices replaced by min(index + o, 63); at MUTE all are 63
+ *   a lost slot with run k:      no G, or o(k - 1) = MUTE: zeros, as without concealment.  Otherwise the synthesis of G at o(k) over the
+ *                                history G at o(k - 1): frame hold + 1 is the all-63 frame over the last audible repeat -- the filterbank's
+ *                                tail rings out and is not cut
+ *   a passing slot behind a loss of run k': G (the one from before this slot) exists and o(k') != MUTE: its own bytes over the history G at
+ *                                o(k').  Otherwise silent history, as without concealment
+ *   a passing slot behind a passing slot: untouched
+ * The result depends on the sequence of slots only, never on how it is cut into calls or ticks.  The feed's own tlb_frame_report is
+ * unchanged: a concealed slot still reports why it was lost.
+ * RECORD.  tlb_conceal_record, 32 bytes: frames = slots seen; passed; concealed = lost slots synthesised from G (the ring-out frame
+ * included); muted = lost slots left as zeros; runs = loss runs begun; longest = the longest loss run; run = k now; offset = o(k) of the last
+ * slot, 0 for a passing one, TLB_CONCEAL_MUTE for MUTE.  A stream without concealment has an all-zero record.
+ * CALLS.  Opt-in per stream; a batch that never enables it allocates nothing and makes the device calls it made before.
+ *   tlb_conceal_enable(b, stream, hold, step)  stream -1: every stream; every named stream is checked before anything changes.  hold 0
+ *                                     switches concealment off (step is then not read).  TLB_ERR_ARG for a stream without a strict feed
+ *                                     (none, an adapted one, a down feed), hold > 16, step outside 1..21.  Waits for the queued work;
+ *                                     the named streams' G, run and record start again
+ *   tlb_conceal_get(b, stream, &hold, &step)  1: on, 0: off (both 0), negative: -TLB_ERR_ARG.  Either pointer may be NULL
+ *   tlb_conceal_reset(b, stream)      -1: every stream.  Waits for the queued work, then forgets G, run and the record; the parameters stay
+ *   tlb_conceal_records_device(b, d_records, hip_stream)  queues a copy of tlb_conceal_record [nstreams] into device memory on hip_stream
+ *                                     (the stream the feed calls are queued on): the records as of the last feed call queued there
+ *   tlb_conceal_records_host(b, records)  waits for the device, then the same into host memory
+ * tlb_feed_device and tlb_feed_host queue the two concealment kernels themselves, behind the feed's own two (which run exactly as before),
+ * whenever some stream of the batch has concealment on.  tlb_feed_set on a stream (removal included) switches its concealment OFF -- G would
+ * be a frame of another format --, and tlb_feed_reset and every call that implies it (tlb_reset, tlb_stream_reset, tlb_stream_reconfigure)
+ * forget the stream's G, run and record like tlb_conceal_reset.
+ * Device memory per stream of a batch that has concealment on: the feed history's slot width (tlb_feed_stride at the time; at most 1728
+ * bytes, 576 for 192 kbps at 48 kHz) for G, plus 48 (the record and the parameters with G's length).
+ * TICK PLANE.  tlb_tick_enable_conceal(t, stream, hold, step) is tlb_conceal_enable routed to the stream's group (-1: all, checked first),
+ * legal while no tick is in flight (TLB_ERR_ARG otherwise); the first call that switches concealment on makes the records' pinned sets.
+ * The records travel with the three output sets behind the packets, on an event of their own.  tlb_tick_conceal(t) is tlb_conceal_record
+ * [nstreams] of the tick waited for last (pinned, valid until the next wait); NULL until concealment has been enabled.  tlb_tick_finish
+ * adds nothing.  tlb_tick_conceal_reset(t, stream) (-1: all) is legal with no tick in flight.  tlb_tick_set_feed on a stream switches its
+ * concealment off as tlb_feed_set does.
+ * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_conceal routes to the stream's shard (-1: every shard) between
+ * steps; every named stream needs a strict feed set through tlb_node_set_feed, and tlb_node_set_feed on a stream switches its concealment
+ * off.  A shard made by tlb_node_shard_restart gets its streams' concealment again behind their feeds, from zero.  tlb_node_conceal(nd,
+ * stream) points at the STREAM's record and answers NULL for a broken, late or stale shard and for a shard none of whose streams ever
+ * enabled it; tlb_node_conceal_reset routes like tlb_node_loudness_reset.
+ * NOT BUILT: concealment for adapted and down feeds (their queues hold decoded samples; the same rule applies to the frame ahead of the
+ * queue), interpolation between the frames either side of a loss, any change to the feed report.
+ * ------------------------------------------------------------------------------------------ */
+#define TLB_CONCEAL_MAX_HOLD 16
+#define TLB_CONCEAL_MAX_STEP 21
+#define TLB_CONCEAL_MUTE 0xFFFFFFFFu
+typedef struct { uint32_t frames, passed, concealed, muted, runs, longest, run, offset; } tlb_conceal_record;      /* 32 bytes */
+int tlb_conceal_enable(tlb_batch *b, int stream, int hold, int step);
+int tlb_conceal_get(const tlb_batch *b, int stream, int *hold, int *step);
+int tlb_conceal_reset(tlb_batch *b, int stream);
+int tlb_conceal_records_device(tlb_batch *b, tlb_conceal_record *d_records, void *hip_stream);
+int tlb_conceal_records_host(tlb_batch *b, tlb_conceal_record *records);
+int tlb_tick_enable_conceal(tlb_tick *t, int stream, int hold, int step);
+const tlb_conceal_record *tlb_tick_conceal(const tlb_tick *t);
+int tlb_tick_conceal_reset(tlb_tick *t, int stream);
+int tlb_node_enable_conceal(tlb_node *nd, int stream, int hold, int step);
+const tlb_conceal_record *tlb_node_conceal(const tlb_node *nd, int stream);
+int tlb_node_conceal_reset(tlb_node *nd, int stream);
+
 /* Diagnostic only: per-stage cycle stamps [nframes][nstreams][32] (csrc/mp2_wave.h TL_STAMP), host buffers. */
 int tlb_encode_host_stamps(tlb_batch *b, const int16_t *pcm, int nframes, long long *stamps);
 

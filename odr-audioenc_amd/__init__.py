@@ -19,4 +19,5 @@ from .toolame import (  # noqa: F401
     LOUDNESS_DTYPE, LOUDNESS_PROGRAMME_DTYPE, LOUDNESS_BINS, loudness_lufs, loudness_taps, loudness_scale,
     TRUEPEAK_DTYPE, TRUEPEAK_TAPS, TRUEPEAK_CEILING_DEFAULT, truepeak_dbtp, truepeak_taps,
     LIMITER_DTYPE, LIMITER_DELAY, limiter_step,
+    CONCEAL_DTYPE, CONCEAL_MUTE,
 )

@@ -14,6 +14,7 @@
 #include "mp2_decimate.h"
 #include "mp2_feed_adapt.h"
 #include "mp2_feed_down.h"
+#include "mp2_conceal.h"
 #include "mp2_loudness.h"
 #include "mp2_truepeak.h"
 #include "mp2_limiter.h"
@@ -44,6 +45,9 @@ hipError_t tlk_edi_pft(unsigned bx, unsigned by, hipStream_t st, const TlPftArgs
 hipError_t tlk_decode(hipStream_t st, const TlDecLaunch &A);
 // toolame_feed.hip: tl_feed_kernel over every (stream, slot) of the launch, then tl_feed_carry_kernel per stream
 hipError_t tlk_feed(hipStream_t st, const TlFeedLaunch &A);
+// toolame_conceal.hip: behind tlk_feed on the same stream when some stream has concealment on: tl_conceal_kernel over every (stream, slot)
+// of the launch, then tl_conceal_carry_kernel per stream (csrc/mp2_conceal.h)
+hipError_t tlk_conceal(hipStream_t st, const TlConcealLaunch &A);
 // toolame_feed_adapt.hip: the decode kernel over every (stream, slot) of the call, the resample kernel (one workgroup per slot), then the carry kernel per stream
 hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A);
 // toolame_feed_down.hip: the decode kernel over every (stream, slot) of the call with two slots per tick, the decimate kernel (one workgroup per tick and stream), then the carry kernel per stream

@@ -49,6 +49,7 @@ int feed_clear_streams(tlb_batch *b, int s0, int n)
 {
     if (!b->d_feed_state) return TLB_OK;
     HIPCHK(hipMemset(b->d_feed_state + s0, 0, sizeof(TlDecStream) * (size_t)n));
+    if (int rc = conceal_clear_streams(b, s0, n)) return rc;         // a stream's concealment starts again with its history (G, run, record)
     if (!b->d_fa_carry) return TLB_OK;
     for (int k = 0; k < 2; k++) {                                    // an adapted stream's next tick is tick 0 and its queue is empty
         HIPCHK(hipMemset(b->d_fa_carry + ((size_t)k * (size_t)b->nstreams + (size_t)s0) * (TL_FA_CARRY * 2), 0, sizeof(int16_t) * TL_FA_CARRY * 2 * (size_t)n));
@@ -139,6 +140,7 @@ static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_con
         for (int32_t x : b->fa_ratio) b->n_adapted += x >= 0;
     }
     for (int s = s0; s < s1; s++) { b->feed.idx[(size_t)s] = idx; b->feed.cfg[(size_t)s] = cfg; }
+    if (int rc = conceal_clear_streams(b, s0, s1 - s0, true)) return rc;      // another feed, or none: concealment off (G would be a frame of another format)
     return feed_clear_streams(b, s0, s1 - s0);
 }
 
@@ -178,6 +180,7 @@ int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int
     A.state = b->d_feed_state; A.prev = b->d_feed_prev; A.prev_stride = b->feed_prev_stride;
     A.nstreams = b->nstreams; A.nframes = nframes; A.stride = stride;
     if (n_strict || !b->n_adapted) HIPCHK(tlk_feed((hipStream_t)hip_stream, A));
+    if (int rc = conceal_launch(b, A, hip_stream)) return rc;        // (nothing unless some stream has concealment on: behind the strict launch, ahead of the adapted streams')
     if (!b->n_adapted) return TLB_OK;
     // the adapted streams, behind the strict launch (to which they are streams without a feed): decode, resample, carry
     TlFeedAdaptLaunch D;
@@ -235,6 +238,7 @@ static int feed_set(tlb_batch *b, int stream, const tlb_feed_config *cfg, bool a
     if (adapt) if (int rc = adapt_prepare(b)) return rc;
     if (int rc = b->feed.reserve(b->feed.h_configs.size() + (idx < 0 ? 1 : 0))) return rc;
     if (int rc = feed_prev_reserve(b, tl_feed_slot_bytes(*c))) return rc;
+    if (int rc = conceal_g_reserve(b, b->feed_prev_stride)) return rc;
     if (int rc = b->feed.add(*cfg, *c, &idx)) return rc;
     return feed_assign(b, s0, s1, idx, *cfg, adapt);
 }

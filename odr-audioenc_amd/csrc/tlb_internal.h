@@ -220,6 +220,15 @@ struct tlb_batch {
     uint32_t *d_lm_step = nullptr;               // [nstreams] S from the stream's encoder rate
     int16_t *d_lm_taps = nullptr;                // the true-peak meter's committed table, a copy of the limiter's own
     tlb_limiter_params lm_params = {0, 0};       // as enabled, the defaults filled in
+    // feed concealment (tlb_conceal.cpp; csrc/mp2_conceal.h), allocated by the first tlb_conceal_enable that switches it on: a batch that
+    // never enables it has none of it
+    std::vector<TlConcealStream> cc_host;        // [nstreams] the parameters as set (g_len is not kept here); empty until allocated
+    int n_conceal = 0;                           // streams with hold > 0: the feed launch queues the two kernels while this is not 0
+    TlConcealStream *d_cc_state = nullptr;       // [nstreams]
+    TlConcealRecord *d_cc_rec = nullptr;         // [nstreams] the record as it is reported
+    uint8_t *d_cc_g = nullptr;                   // [nstreams][cc_g_stride] the last passing slot; replaced when a longer feed frame arrives
+    int cc_g_stride = 0;
+    std::unique_ptr<TlbMem> cc_g_mem;            // ... hence an owner of its own
     TlbMem mem;                                 // owns every device buffer above that is made once and kept until tlb_destroy (csrc/tlb_mem.h); d_configs and
                                                  // stage[] are replaced during the object's life and are freed one by one
     int fail_in = 0;                             // test builds only (-DTLB_FAULT_INJECT, csrc/tlb_debug.h): the fail_in-th launch from now fails
@@ -280,6 +289,12 @@ int feed_down_after_reconfigure(tlb_batch *b, int stream);
 // slots of `stride` bytes, at least tlb_feed_down_stride(b)
 int feed_down_fits(const tlb_batch *b, int s0, int s1, const tlb_feed_config *cfg);
 int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int nframes, int16_t *d_interleaved, tlb_frame_report *d_report, void *hip_stream, int stride);
+// tlb_conceal.cpp: nothing when concealment was never enabled.  G, run and record of streams [s0, s0 + n) forgotten (off: and their
+// concealment switched off; the life-cycle calls, the device is idle); room for slots of `stride` bytes in the G buffer, what it holds
+// kept; the two kernels behind the feed launch A on `hip_stream`
+int conceal_clear_streams(tlb_batch *b, int s0, int n, bool off = false);
+int conceal_g_reserve(tlb_batch *b, int stride);
+int conceal_launch(tlb_batch *b, const TlFeedLaunch &A, void *hip_stream);
 
 // The PCM meters (tlb_loudness.cpp, tlb_truepeak.cpp).  A meter's state of streams [s0, s0 + n) back to zero (the device is idle); nothing
 // when the meter was never enabled

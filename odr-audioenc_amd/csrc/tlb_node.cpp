@@ -171,6 +171,9 @@ struct tlb_node {
     // adapted: set through tlb_node_set_feed_adapted, and set again that way.  A family's vector is empty until it is first turned on.
     struct Input : tlb_feed_config { int adapted; };
     std::vector<Input> kept[TLB_IN_SHORT_READS];
+    // the feed concealment of every stream (tlb_node_enable_conceal), set again on a restarted shard behind its feeds; empty until first switched on
+    struct Conceal { int hold = 0, step = 0; };
+    std::vector<Conceal> kept_conceal;
     // The families that are on, for tlb_input_may_set at OBJECT level.  That is the TICK plane's rule: every shard there is one tick object.
     // On the BATCH plane the node holds nothing back and the mask is empty: the shards' batches answer stream by stream (batch_inputs).
     unsigned inputs() const
@@ -416,6 +419,10 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
             const NodeInput &v = nd->kept[f][(size_t)(s.first + k)];
             if (v.samplerate) if (int rc = node_families[f](s, k, v)) return rc;
         }
+    for (int k = 0; k < s.n && s.tick && !nd->kept_conceal.empty(); k++) {      // the feeds' concealment, from zero
+        const tlb_node::Conceal &c = nd->kept_conceal[(size_t)(s.first + k)];
+        if (c.hold) if (int rc = tlb_tick_enable_conceal(s.tick, k, c.hold, c.step)) return rc;
+    }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
         if (g == 0.0) continue;
@@ -776,7 +783,32 @@ static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, b
         }
     }
     const NodeInput v = node_feed(cfg, adapt);
-    return node_set_input(nd, TLB_IN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
+    const int rc = node_set_input(nd, TLB_IN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
+    for (int i = s0; i < s1 && !rc && !nd->kept_conceal.empty(); i++) nd->kept_conceal[(size_t)i] = tlb_node::Conceal{};      // (a stream's new feed, or none, starts without concealment)
+    return rc;
+}
+// The feed concealment, per stream (TICK plane): tlb_tick_enable_conceal of the owning shards' objects between steps, remembered for restarts.
+// Every named stream needs a strict feed the node remembers; the rest is tlb_node::set_remembered's
+int tlb_node_enable_conceal(tlb_node *nd, int stream, int hold, int step)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    if (hold < 0 || hold > TLB_CONCEAL_MAX_HOLD || (hold > 0 && (step < 1 || step > TLB_CONCEAL_MAX_STEP))) return TLB_ERR_ARG;
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
+    const std::vector<NodeInput> &feeds = nd->kept[TLB_IN_FEED];
+    for (int i = s0; i < s1 && hold > 0; i++) if (feeds.empty() || !feeds[(size_t)i].samplerate || feeds[(size_t)i].adapted) return TLB_ERR_ARG;
+    tlb_node::Conceal v; v.hold = hold; v.step = hold ? step : 0;
+    return nd->set_remembered(stream, nd->kept_conceal, hold > 0, v,
+                              [](Shard &sh, int k, const tlb_node::Conceal &c) { return sh.tick ? tlb_tick_enable_conceal(sh.tick, k, c.hold, c.step) : (int)TLB_ERR_HIP; },
+                              [&](int) { return v; });
+}
+const tlb_conceal_record *tlb_node_conceal(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_conceal>(nd, stream); }
+int tlb_node_conceal_reset(tlb_node *nd, int stream)
+{
+    if (!nd || nd->plane != TLB_NODE_TICK || nd->kept_conceal.empty() || stream < -1 || stream >= nd->nstreams || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    if (stream < 0) return nd->live("conceal_reset", [](Shard &s) { return tlb_tick_conceal_reset(s.tick, -1); });
+    int k; Shard *s;
+    if (int rc = nd->gate(stream, &s, &k)) return rc;
+    return nd->one(s->index, [&](Shard &sh) { return tlb_tick_conceal_reset(sh.tick, k); });
 }
 int tlb_node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg) { return node_set_feed(nd, stream, cfg, false); }
 int tlb_node_set_feed_adapted(tlb_node *nd, int stream, const tlb_feed_config *cfg) { return node_set_feed(nd, stream, cfg, true); }

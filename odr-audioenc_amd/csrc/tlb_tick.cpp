@@ -59,7 +59,7 @@ struct TickLane {
 // tlb_tick_destroy frees the events.  A PCM METER is a record option that also names its batch-level calls: enabled per batch with the
 // object's ceiling (the true-peak meter's; the others ignore it), run on the tick's planar PCM whenever there is new input, reset for one
 // stream or all between ticks.  tick_egress queues the meters in table order; the monitor's and the compare monitor's launches are its own.
-enum { REC_MONITOR, REC_COMPARE, REC_LOUDNESS, REC_TRUEPEAK, REC_LIMITER, RECS };
+enum { REC_MONITOR, REC_COMPARE, REC_LOUDNESS, REC_TRUEPEAK, REC_LIMITER, REC_CONCEAL, RECS };
 struct RecordOption {
     size_t size;                                 // of one record
     int ev;                                      // the option behind whose event (ev_rec[ev]) the copy-out runs
@@ -81,6 +81,9 @@ static const RecordOption tick_records[RECS] = {
      tlb_truepeak_reset},
     // the limiter is no meter: tlb_tick_submit queues it AHEAD of the encoder, with its own parameters (tlb_tick_enable_limiter); its reset is a meter's
     {sizeof(tlb_limiter_record), REC_LIMITER, nullptr, nullptr, tlb_limiter_reset},
+    // the feed concealment is no meter either: the feed launch of tlb_tick_submit queues its kernels, and the batches' records are copied into
+    // the groups' behind it (tlb_tick_enable_conceal: per stream, between ticks); its reset is a meter's
+    {sizeof(tlb_conceal_record), REC_CONCEAL, nullptr, nullptr, tlb_conceal_reset},
 };
 struct TickRecords {
     bool on = false;
@@ -448,6 +451,27 @@ int tlb_tick_enable_limiter(tlb_tick *t, const tlb_limiter_params *params)
 }
 const tlb_limiter_record *tlb_tick_limiter(const tlb_tick *t) { return (const tlb_limiter_record *)tick_record(t, REC_LIMITER); }
 int tlb_tick_limiter_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_LIMITER, stream); }
+// The feed concealment (tlb_conceal_*): per stream, while no tick is in flight.  Every named stream is checked before one is changed; the first
+// call that switches concealment on makes the record option's buffers.  The kernels are the feed launch's own business (feed_launch); every
+// submit then copies the batches' records into the groups' behind it.  An object that never makes the call allocates and queues nothing new.
+int tlb_tick_enable_conceal(tlb_tick *t, int stream, int hold, int step)
+{
+    if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (hold < 0 || hold > TLB_CONCEAL_MAX_HOLD || (hold > 0 && (step < 1 || step > TLB_CONCEAL_MAX_STEP))) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    if (hold == 0 && !t->rec[REC_CONCEAL].on) return TLB_OK;         // off, and never on
+    const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? t->nstreams : stream + 1;
+    if (hold > 0)
+        if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) {
+                const tlb_batch *b = t->groups[(size_t)g].b;
+                for (int k = l0; k < l1; k++) if (tlb_feed_get(b, k, nullptr) <= 0 || tlb_feed_adapted(b, k) != 0) return (int)TLB_ERR_ARG;
+                return (int)TLB_OK;
+            })) return rc;
+    if (!t->rec[REC_CONCEAL].on) if (int rc = tick_record_enable(t, REC_CONCEAL, [](TlbMem &, TickGroup &) { return 0; })) return rc;
+    return t->blocks.visit(stream, [&](int g, int k) { return tlb_conceal_enable(t->groups[(size_t)g].b, k, hold, step); });
+}
+const tlb_conceal_record *tlb_tick_conceal(const tlb_tick *t) { return (const tlb_conceal_record *)tick_record(t, REC_CONCEAL); }
+int tlb_tick_conceal_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_CONCEAL, stream); }
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)
 {
     if (!t || t->monitor != TLB_MONITOR_AUDIO || stream < -1 || stream >= t->nstreams) return TLB_ERR_ARG;
@@ -743,7 +767,7 @@ static int tick_egress(tlb_tick *t, TickGroup &G, bool have_frames, int set, boo
             HIPCHK(hipMemcpyAsync(t->h_listen[set], G.d_mpcm + (size_t)k * 2 * TLB_SAMPLES_PER_FRAME, 2 * TLB_SAMPLES_PER_FRAME * sizeof(int16_t), hipMemcpyDeviceToHost, t->s_out));
     }
     for (int r = 0; r < RECS; r++)                                   // ... and the meters' records, each on an event of its own
-        if (t->rec[r].on && (tick_records[r].launch || r == REC_LIMITER)) if (int rc = tick_record_out(t, G, r, set, new_input)) return rc;
+        if (t->rec[r].on && (tick_records[r].launch || r == REC_LIMITER || r == REC_CONCEAL)) if (int rc = tick_record_out(t, G, r, set, new_input)) return rc;
     HIPCHK(hipEventRecord(G.ev_out, t->s_out));                      // the group's device output buffers are free again once this has passed (the monitor's reads of d_frames included)
     return TLB_OK;
 }
@@ -856,6 +880,9 @@ int tlb_tick_submit(tlb_tick *t)
         if (e != hipSuccess) rc = TLB_ERR_HIP;
         for (int lane = 0; lane < LANES; lane++)                     // behind the copy-in, ahead of the ingest: a mixed group's fed slots are overwritten
             if (!rc && G.lane[lane].any) rc = tick_families[lane].launch(G.b, G.lane[lane].d_frames, G.lane[lane].d_len, 1, G.d_inter, G.lane[lane].d_report, t->s_run, t->lane[lane].stride);
+        // the concealment's records as the feed launch has just left them (a group whose batch never enabled it shows zeros), on an event of their own
+        if (!rc && t->rec[REC_CONCEAL].on && G.b->d_cc_rec) rc = tlb_conceal_records_device(G.b, (tlb_conceal_record *)G.d_rec[REC_CONCEAL], t->s_run);
+        if (!rc && t->rec[REC_CONCEAL].on && hipEventRecord(G.ev_rec[REC_CONCEAL], t->s_run) != hipSuccess) rc = TLB_ERR_HIP;
         if (!rc && t->resample) rc = tlb_resample_device(G.b, G.d_inter, 1, G.d_rs, t->s_run);
         if (!rc && G.any_down) rc = tlb_decimate_device(G.b, G.d_wide, 1, G.d_inter, t->s_run);      // behind the copy-in, ahead of the ingest: a mixed group's decimated slots are overwritten
         if (!rc && !t->short_reads) rc = tlb_ingest_device(G.b, t->resample ? G.d_rs : G.d_inter, 1, G.d_pcm, G.d_peaks, t->s_run);

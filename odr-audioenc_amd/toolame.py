@@ -336,6 +336,20 @@ def _bind(L):
         L.tlb_node_limiter.restype = C.c_void_p
         L.tlb_node_limiter.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_limiter_reset.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_conceal_enable"):          # feed concealment
+        L.tlb_conceal_enable.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.tlb_conceal_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.tlb_conceal_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_conceal_records_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_conceal_records_host.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_tick_enable_conceal.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.tlb_tick_conceal.restype = C.c_void_p
+        L.tlb_tick_conceal.argtypes = [C.c_void_p]
+        L.tlb_tick_conceal_reset.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_enable_conceal.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.tlb_node_conceal.restype = C.c_void_p
+        L.tlb_node_conceal.argtypes = [C.c_void_p, C.c_int]
+        L.tlb_node_conceal_reset.argtypes = [C.c_void_p, C.c_int]
     if hasattr(L, "tlb_decimate_device"):         # device decimator (down sources)
         L.tlb_decimate_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_decimate_source.restype = C.c_long
@@ -493,6 +507,10 @@ TRUEPEAK_CEILING_DEFAULT = 956973408                                 # -1 dBTP: 
 
 
 # tlb_limiter_record: reductions as 65536 - G (0: unity), peaks in units of 2^-30 of full scale
+# tlb_conceal_record: slots seen / passed / lost and synthesised from the last good frame / lost and left as zeros, loss runs begun, the longest
+# one, the run now and the scalefactor-index offset of the last slot (CONCEAL_MUTE: beyond hold)
+CONCEAL_DTYPE = np.dtype([(n, np.uint32) for n in ("frames", "passed", "concealed", "muted", "runs", "longest", "run", "offset")])
+CONCEAL_MUTE = 0xFFFFFFFF
 LIMITER_DTYPE = np.dtype([("frames", np.uint32), ("limited", np.uint32), ("samples", np.uint32), ("red_last", np.uint32), ("red_max", np.uint32),
                           ("peak_in", np.uint32), ("peak_in_max", np.uint32), ("reserved", np.uint32)])
 LIMITER_DELAY = 63                                                   # samples the limited PCM is late, TLB_LIMITER_DELAY
@@ -876,6 +894,26 @@ class Tick:
         if rc:
             raise ToolameError(rc, "tlb_tick_truepeak_reset")
 
+    # -- feed concealment (tlb_conceal_* of the groups' batches): per stream, while no tick is in flight --
+    def enable_conceal(self, hold=4, step=3, stream=-1):
+        """a lost feed frame repeats the last good one, `step` scalefactor-index units (3: 6 dB) quieter per lost frame, for `hold` frames,
+        then rings out; hold 0 switches it off.  stream -1: every stream (each needs a strict feed)"""
+        rc = self.L.tlb_tick_enable_conceal(self.h, int(stream), int(hold), int(step))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_conceal")
+
+    def conceal(self):
+        """CONCEAL_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when never enabled"""
+        p = self.L.tlb_tick_conceal(self.h)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * (self.nstreams * CONCEAL_DTYPE.itemsize)).from_address(p), dtype=CONCEAL_DTYPE)
+
+    def conceal_reset(self, s=-1):
+        rc = self.L.tlb_tick_conceal_reset(self.h, int(s))
+        if rc:
+            raise ToolameError(rc, "tlb_tick_conceal_reset")
+
     # -- true-peak limiter (tlb_limiter_device on the tick's planar PCM, between the ingest and the encoder): before the first submit --
     def enable_limiter(self, ceiling=0, release_ms=0):
         """ceiling in units of 2^-30 of full scale, 0: TRUEPEAK_CEILING_DEFAULT (-1 dBTP); release_ms 0: 100"""
@@ -1227,6 +1265,36 @@ class Batch:
         rc = self.L.tlb_feed_device(self.h, d_frames_ptr, d_len_ptr, nframes, d_interleaved_ptr, d_report_ptr, stream)
         if rc:
             raise ToolameError(rc, "tlb_feed_device")
+
+    # -- feed concealment (tlb_conceal_*): a lost frame of a strict feed is the last good one once more, quieter, and not silence --
+    def enable_conceal(self, hold=4, step=3, stream=-1):
+        """hold 1..16 frames, step 1..21 scalefactor-index units per lost frame (3: 6 dB); hold 0 switches it off.  stream -1: every stream,
+        each of which needs a strict feed (checked before anything changes).  feed() then conceals by itself."""
+        rc = self.L.tlb_conceal_enable(self.h, int(stream), int(hold), int(step))
+        if rc:
+            raise ToolameError(rc, "tlb_conceal_enable")
+
+    def conceal_cfg(self, s):
+        """(hold, step) of stream s, None when its concealment is off"""
+        hold, step = C.c_int(0), C.c_int(0)
+        n = self.L.tlb_conceal_get(self.h, int(s), C.byref(hold), C.byref(step))
+        if n < 0:
+            raise ToolameError(-n, "tlb_conceal_get")
+        return (hold.value, step.value) if n else None
+
+    def conceal_records(self):
+        """CONCEAL_DTYPE [nstreams] after the feed calls so far (waits for the device)"""
+        out = np.zeros(self.nstreams, dtype=CONCEAL_DTYPE)
+        rc = self.L.tlb_conceal_records_host(self.h, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_conceal_records_host")
+        return out
+
+    def conceal_reset(self, s=-1):
+        """forget the last good frame, the run and the record of stream s (-1: all); the parameters stay"""
+        rc = self.L.tlb_conceal_reset(self.h, int(s))
+        if rc:
+            raise ToolameError(rc, "tlb_conceal_reset")
 
     # -- down feeds: a 48, 44.1 or 32 kHz Layer II feed for a 24 kHz stream, decoded and decimated into the ingest's input (tlb_feed_down_*) --
     def set_down_feed(self, stream, cfg):
@@ -1998,6 +2066,20 @@ class Node:
 
     def truepeak_reset(self, s=-1):
         self._rc(self.L.tlb_node_truepeak_reset(self.h, int(s)), "tlb_node_truepeak_reset")
+
+    # feed concealment (Tick.enable_conceal, per stream with node-wide indices; between steps)
+    def enable_conceal(self, hold=4, step=3, stream=-1):
+        self._rc(self.L.tlb_node_enable_conceal(self.h, int(stream), int(hold), int(step)), "tlb_node_enable_conceal")
+
+    def conceal(self, s):
+        """the stream's record (a CONCEAL_DTYPE scalar, copied) of the step waited for last; None when never enabled and for a broken, late or stale shard"""
+        p = self.L.tlb_node_conceal(self.h, s)
+        if not p:
+            return None
+        return np.frombuffer((C.c_uint8 * CONCEAL_DTYPE.itemsize).from_address(p), dtype=CONCEAL_DTYPE)[0].copy()
+
+    def conceal_reset(self, s=-1):
+        self._rc(self.L.tlb_node_conceal_reset(self.h, int(s)), "tlb_node_conceal_reset")
 
     # true-peak limiter (Tick.enable_limiter, per stream with node-wide indices)
     def enable_limiter(self, ceiling=0, release_ms=0):

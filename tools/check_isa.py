@@ -52,6 +52,9 @@ LIMITS = [
     # down feeds (csrc/toolame_feed_down.hip): the feed kernel's body and occupancy; the decimate kernel's LDS plus 1152 int16 of outputs
     (re.compile(r"tl_feed_down_decode_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
     (re.compile(r"tl_feed_down_decimate_kernel"), dict(vgpr=128, lds=20992 + 2304, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # feed concealment (csrc/toolame_conceal.hip): the feed kernel's two parses and its synthesis behind one ballot over the reports; same occupancy
+    (re.compile(r"tl_conceal_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
+    (re.compile(r"tl_conceal_carry_kernel"), dict(vgpr=128, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # loudness meter (csrc/toolame_loudness.hip): a lane per (stream, channel) with the filter state and a chunk of PCM ahead in registers; 64 rows of 144 bytes in LDS
     (re.compile(r"tl_loudness_kernel"), dict(vgpr=168, lds=9216, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     (re.compile(r"tl_loudness_programme_kernel"), dict(vgpr=168, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),

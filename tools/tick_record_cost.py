@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a record option adds to a tick, and what this commit costs an object with and without it, on the GPU.
 
-    python tools/tick_record_cost.py --option monitor|compare|loudness|truepeak|limiter|all [--streams 16384] [--psy 3] [--ticks 200] [--rounds 5]
+    python tools/tick_record_cost.py --option monitor|compare|loudness|truepeak|limiter|all|conceal [--streams 16384] [--psy 3] [--ticks 200] [--rounds 5]
                                      [--hot] [--parent-lib PATH] [--out profiles/tick_records.txt]
 
 The record options of a tick object (csrc/tlb_tick.cpp, tick_records): `monitor` (tlb_tick_enable_monitor, TLB_MONITOR_AUDIO), `compare`
@@ -14,7 +14,13 @@ one; `parent-on` only when that library has the option's entry points), `off` (t
 tlb_tick_run per leg and keeps the median and the maximum of tlb_tick_last_ms (device clock: first copy-in queued -> last copy-out done,
 the records' copy-out included).  The file gets the medians, minima and maxima over the rounds.  The condition: `off` makes the device
 calls `parent` makes and `on` those `parent-on` makes, so each median belongs inside its parent leg's own run-to-run spread.  A leg that
-cannot be run is written as NOT MEASURED with the reason."""
+cannot be run is written as NOT MEASURED with the reason.
+`conceal` (tlb_tick_enable_conceal, hold 4, step 3) is measured on another workload, since it lives on the feed path: every stream on a strict 192 kbps
+Layer II feed (no PCM crosses the link).  Legs: `parent` (--parent-lib), `off` (this library, never enabled), and three with concealment on:
+`on-0` no slot lost, `on-10` every tenth slot of every stream lost (staggered over the streams), `on-all` every slot lost (every unit
+synthesises as long as hold lasts, so the leg's ticks are cut into runs of hold + 1 lost slots and one good one -- but the feed kernel then
+decodes next to nothing), and `on-alt` every other slot lost, staggered: every unit of the concealment kernel synthesises (a lost slot, or the
+good slot behind one) while the feed kernel still decodes half the slots -- the most work the option can ADD to a tick."""
 import argparse
 import ctypes as C
 import sys
@@ -41,9 +47,88 @@ def fmt(v):
     return "median %.4f  min %.4f  max %.4f  (rounds: %s)" % (np.median(v), v.min(), v.max(), " ".join("%.4f" % x for x in v))
 
 
+def main_conceal(args):
+    import torch
+    import odr_audioenc_amd as M
+    from odr_audioenc_amd import toolame as TL
+    from pcmgen import gen_pcm
+    import declib as D
+    ns, hold, step = args.streams, 4, 3
+    cfg = [M.StreamConfig(samplerate=48000, mode="s", bitrate=128, psy_model=args.psy)] * ns
+    src = M.Batch([M.StreamConfig(samplerate=48000, mode="s", bitrate=192, psy_model=1)])      # eight source frames; stream s is fed frame s % 8 every tick
+    data, _ = src.encode(gen_pcm(7, 0, 0, 8)[:, None])
+    frames = D.cut_frames(data[0] + src.flush()[0], dict(samplerate=48000, kbps=192))
+    src.close()
+    assert len(frames) == 8 and all(len(f) == 576 for f in frames)
+    rows = np.stack([np.frombuffer(frames[s % 8], dtype=np.uint8) for s in range(ns)])
+    legs, why = {}, {}                                               # leg -> (library, concealment on, which (tick, stream) slots are lost)
+    if args.parent_lib and Path(args.parent_lib).exists():
+        legs["parent"] = (TL._bind(C.CDLL(str(Path(args.parent_lib).resolve()))), False, None)
+    else:
+        why["parent"] = "no library of the parent commit was given (--parent-lib)"
+    sidx = np.arange(ns)
+    legs["off"] = (None, False, None)
+    legs["on-0"] = (None, True, None)
+    legs["on-10"] = (None, True, lambda i: (i + sidx) % 10 == 0)
+    legs["on-all"] = (None, True, lambda i: np.full(ns, i % (hold + 2) != 0))      # one good slot, then hold + 1 lost ones that all synthesise
+    legs["on-alt"] = (None, True, lambda i: (i + sidx) % 2 == 0)
+    objs, count = {}, {}
+    for name, (lib, on, lost) in legs.items():
+        t = M.Tick(cfg, egress="af", version=b"odr-audioenc_amd bench", lib=lib)
+        t.set_feed(-1, M.FeedConfig(48000, 192, 2))
+        if on:
+            t.enable_conceal(hold, step)
+        for _ in range(6):                                            # both input sets' frames, and the warm-up: code objects loaded, every buffer touched
+            t.feed[:, :576] = rows
+            t.feed_len[:] = 576
+            t.run()
+        objs[name], count[name] = t, 0
+    out = {k: {"median_ms": [], "max_ms": []} for k in objs}
+    for _ in range(args.rounds):
+        for name, t in objs.items():
+            lost = legs[name][2]
+            dev = np.empty(args.ticks)
+            for i in range(args.ticks):
+                t.feed_len[:] = 576 if lost is None else np.where(lost(count[name]), 0, 576)
+                count[name] += 1
+                t.run()
+                dev[i] = t.last_ms()
+            out[name]["median_ms"].append(float(np.median(dev)))
+            out[name]["max_ms"].append(float(dev.max()))
+    recs = {n: {f: int(objs[n].conceal()[f].sum()) for f in ("frames", "passed", "concealed", "muted")} for n in objs if legs[n][1]}
+    for t in objs.values():
+        t.close()
+    lines = ["tools/tick_record_cost.py --option conceal on %s: %d streams of 48 kHz stereo 128 kbps psy %d, every stream on a strict 192 kbps feed," %
+             (torch.cuda.get_device_name(0), ns, args.psy),
+             "EDI AF, %d ticks of tlb_tick_run per round and leg, %d rounds interleaved in one process.  Per leg: the rounds' medians and maxima of" % (args.ticks, args.rounds),
+             "tlb_tick_last_ms (device clock).  A 48 kHz frame lasts 24 ms.  Concealment: hold %d, step %d." % (hold, step)]
+    for name in ("parent", "off", "on-0", "on-10", "on-all", "on-alt"):
+        if name not in out:
+            lines.append("%-9s NOT MEASURED: %s" % (name, why[name]))
+            continue
+        lines.append("%-9s median of a round ms : %s" % (name, fmt(out[name]["median_ms"])))
+        lines.append("%-9s maximum of a round ms: %s" % (name, fmt(out[name]["max_ms"])))
+    med = lambda n: float(np.median(out[n]["median_ms"]))
+    sp = lambda n: max(out[n]["median_ms"]) - min(out[n]["median_ms"])
+    if "parent" in out:
+        d = med("off") - med("parent")
+        lines.append("(a) off - parent: %+.4f ms; the parent leg's own spread over its rounds: %.4f ms -> %s" % (d, sp("parent"), "inside it" if abs(d) <= sp("parent") else "OUTSIDE it"))
+    else:
+        lines.append("(a) off - parent: NOT MEASURED")
+    for tag, leg, what in (("(b)", "on-0", "enabled, no loss: the units that leave early"), ("(c)", "on-10", "every tenth slot lost"), ("(d)", "on-all", "every slot lost but one in %d" % (hold + 2)),
+                           ("(e)", "on-alt", "every other slot lost, staggered: every concealment unit synthesises")):
+        lines.append("%s %s - off: %+.4f ms per tick for %d streams (%s; spread of the leg %.4f ms, of off %.4f ms; records: %s)" %
+                     (tag, leg, med(leg) - med("off"), ns, what, sp(leg), sp("off"), ", ".join("%s %d" % kv for kv in recs[leg].items())))
+    lines.append("131 072 streams: NOT MEASURED.")
+    text = "\n".join(lines) + "\n"
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(text)
+    print(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", choices=list(OPTIONS), required=True)
+    ap.add_argument("--option", choices=list(OPTIONS) + ["conceal"], required=True)
     ap.add_argument("--streams", type=int, default=16384)
     ap.add_argument("--psy", type=int, default=3)
     ap.add_argument("--ticks", type=int, default=200)
@@ -55,6 +140,8 @@ def main():
     import torch
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures, it does not estimate")
+    if args.option == "conceal":
+        return main_conceal(args)
     import odr_audioenc_amd as M
     from odr_audioenc_amd import toolame as TL
     from pcmgen import gen_pcm
