@@ -231,7 +231,8 @@ TL_FN void tl_encode_frame(TlMainLds &w, const TlTables *TL_RESTRICT T, const Tl
         // them).  If together they still fit, they are all taken in one round; the one-at-a-time loop takes over
         // when a round no longer fits (or is empty), so the refusal rule above is applied event by event.
         PV(int, ba);
-        adb_left = tl_allocate(B, adb, nch, sblimit, jsbound, a_ln, a_nbal, a_sfs, a_sfs_o, a_smr, ba);
+        // (the closing round's histogram: 64 words of the staging union -- the PCM is dead since the filterbank, the frame is zeroed below)
+        adb_left = tl_allocate(B, adb, nch, sblimit, jsbound, a_ln, a_nbal, a_sfs, a_sfs_o, a_smr, ba, w.u.frame[0]);
         TL_LANES_BEGIN
         const int c = lane & 1, sb = lane >> 1;
         w.balloc[c][sb] = (uint8_t)((c < nch && sb < sblimit) ? L(ba) : 0);

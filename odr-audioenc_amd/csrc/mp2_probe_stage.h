@@ -347,8 +347,14 @@ TL_FN void tl_probe_stage_case(int form, TlStageLds &w, long k, const void *in0,
 }
 
 // one case of TLS_ALLOC, one wave.  B: the workgroup's LDS copy of TlBlockShared on the device, A: the allocation tables
-TL_FN void tl_probe_alloc_case(const TlBlockShared *TL_RESTRICT B, const TlsAllocTab *TL_RESTRICT A, long k, const void *in0, const void *in1, const void *in2, void *out0, void *out1)
+// hist: tl_allocate's 64 scratch words -- TlStageLds::frame on the device; the emulation's entry point passes none and gets a local array
+TL_FN void tl_probe_alloc_case(const TlBlockShared *TL_RESTRICT B, const TlsAllocTab *TL_RESTRICT A, long k, const void *in0, const void *in1, const void *in2, void *out0, void *out1,
+                               uint32_t *hist = nullptr)
 {
+#ifdef TL_EMULATE
+    uint32_t hist_own[64];
+    if (!hist) hist = hist_own;
+#endif
     const int32_t *ic = (const int32_t *)in2;
     const double *smr = (const double *)in0 + 64 * k;
     const int32_t *sel = (const int32_t *)in1 + 64 * k, *p = ic + 8 * k;
@@ -368,7 +374,7 @@ TL_FN void tl_probe_alloc_case(const TlBlockShared *TL_RESTRICT B, const TlsAllo
         L(a_sfs_o) = (live && nch == 2) ? 6 * tl_sfs_count((unsigned)sel[lane ^ 1]) : 0;
         L(a_smr) = live ? smr[lane] : 0.0;
         TL_LANES_END
-        left = tl_allocate(B, adb0, nch, sblimit, jsbound, a_ln, a_nbal, a_sfs, a_sfs_o, a_smr, ba);
+        left = tl_allocate(B, adb0, nch, sblimit, jsbound, a_ln, a_nbal, a_sfs, a_sfs_o, a_smr, ba, hist);
     } else {
         TL_LANES_BEGIN
         const int sb = lane >> 1;

@@ -39,6 +39,7 @@
 #define PARGA(T, name, n) T (&name)[64][n]
 #define TL_OTHER(name, idx, src) name[src] idx          /* value of another lane's register */
 #define TL_ATOMIC_OR(p, v) (*(p) |= (v))
+#define TL_ATOMIC_ADD(p, v) (*(p) += (v))
 TL_FN uint64_t tlh_ballot(const bool (&p)[64]) { uint64_t m = 0; for (int i = 0; i < 64; i++) if (p[i]) m |= 1ull << i; return m; }
 TL_FN uint64_t tlh_min_u64(const uint64_t (&v)[64]) { uint64_t m = v[0]; for (int i = 1; i < 64; i++) if (v[i] < m) m = v[i]; return m; }
 TL_FN int tlh_sum_i32(const int (&v)[64]) { int s = 0; for (int i = 0; i < 64; i++) s += v[i]; return s; }
@@ -106,6 +107,7 @@ TL_FN int tl_sign_bit(double x) { return (int)(tl_d2u(x) >> 63); }              
 #define PARGA(T, name, n) T (&name)[n]
 #define TL_OTHER(name, idx, src) tld_shfl_f64(name idx, src)
 #define TL_ATOMIC_OR(p, v) atomicOr((p), (v))
+#define TL_ATOMIC_ADD(p, v) atomicAdd((p), (v))                 /* LDS, result unused: one ds_add_u32 */
 TL_FN double tld_shfl_f64(double v, int src) { return __shfl(v, src, 64); }
 TL_FN double tld_swap1_f64(double v) {
     // value of lane^1 (the other channel of the same subband): DPP quad_perm [1,0,3,2], no LDS crossbar

@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(256) tl_probe_stage_kernel(int form, long n, c
     } else {
         const long k = (long)blockIdx.x * 4 + wave;
         if (k >= n) return;
-        if (form == TLS_ALLOC) tl_probe_alloc_case(&blk, atab, k, in0, in1, in2, out0, out1);
+        if (form == TLS_ALLOC) tl_probe_alloc_case(&blk, atab, k, in0, in1, in2, out0, out1, lds[wave].frame);
         else tl_probe_stage_case(form, lds[wave], k, in0, in1, in2, out0, out1);
     }
 }
