@@ -17,9 +17,10 @@
 //   (tlb_tick_set_feed_adapted): on the ticks tlb_tick_feed_want says want no frame the slot stays empty and the file does not advance.
 //   R above the rate of a 24000 Hz encoder (48000, 44100, 32000) is a DOWN FEED (tlb_tick_set_down_feed): every tick takes the one or two
 //   frames tlb_tick_down_feed_want asks for into the stream's two slots, and the device decodes, filters and decimates them.
-//   --feed-drop-every N --feed-drop-run M: lost packets on a strict feed: the last M ticks of every N leave every stream's feed slot empty
+//   --feed-drop-every N --feed-drop-run M: lost packets: the last M of every N WANTED slots (on a strict feed: ticks) stay empty in every stream
 //   (the frames they would have carried are gone: the file advances).  Without --conceal each is 24 ms of silence, cut in hard.
-//   --conceal [HOLD] --conceal-step N: feed concealment (tlb_tick_enable_conceal) on a strict feed: a lost frame is the last good one once
+//   --conceal [HOLD] --conceal-step N: feed concealment (tlb_tick_enable_conceal; tlb_tick_enable_feed_loss with --feed-rate / --feed-channels and
+//   for a down feed, where the lost WANTED slots are concealed ahead of the resampler or decimator): a lost frame is the last good one once
 //   more, N scalefactor-index units (default 3: 6 dB) quieter per lost frame, for HOLD frames (default 4), then the filterbank rings out.
 //   One line at the end: the records summed over the streams -- slots, passed, concealed, muted, loss runs, the longest run.
 //   --source-rate R: the input file is at R Hz (44100 for a 48000 Hz encoder, 32000; 22050 or 16000 for 24000 Hz) and is resampled to the
@@ -142,7 +143,7 @@ int main(int argc, char **argv)
     const bool down_feed = feed_path && feed.samplerate > rate;  // a feed above the encoder's rate: two slots per tick, decoded and decimated
     const bool adapt = !down_feed && (feed.samplerate != rate || feed.channels != channels);
     if (drop_every < 0 || drop_run < 0 || drop_run > drop_every || (drop_every > 0) != (drop_run > 0)) die("--feed-drop-every N --feed-drop-run M: 1 <= M <= N, both or neither", 0);
-    if ((conceal || drop_every) && (!feed_path || down_feed || adapt)) die("--conceal and --feed-drop-every need a strict --feed (the encoder's rate and channel count)", 0);
+    if ((conceal || drop_every) && !feed_path) die("--conceal and --feed-drop-every need a strict --feed (the encoder's rate and channel count)", 0);
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;                              // --feed: where each frame lies in the file
     if (feed_path) {
@@ -190,7 +191,8 @@ int main(int argc, char **argv)
     if (down_feed) { if (int rc = tlb_tick_set_down_feed(t, -1, &feed)) die("tlb_tick_set_down_feed", rc); }      // likewise
     else if (feed_path && !adapt) if (int rc = tlb_tick_set_feed(t, -1, &feed)) die("tlb_tick_set_feed", rc);
     if (feed_path && adapt) if (int rc = tlb_tick_set_feed_adapted(t, -1, &feed)) die("tlb_tick_set_feed_adapted", rc);
-    if (conceal) if (int rc = tlb_tick_enable_conceal(t, -1, conceal, conceal_step)) die("tlb_tick_enable_conceal", rc);       // behind the feed, while no tick is in flight
+    if (conceal && !(adapt || down_feed)) if (int rc = tlb_tick_enable_conceal(t, -1, conceal, conceal_step)) die("tlb_tick_enable_conceal", rc);       // behind the feed, while no tick is in flight
+    if (conceal && (adapt || down_feed)) if (int rc = tlb_tick_enable_feed_loss(t, -1, conceal, conceal_step)) die("tlb_tick_enable_feed_loss", rc);     // an adapted or a down feed: its WANTED slots
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare) if (int rc = tlb_tick_enable_compare(t, &cparams)) die("tlb_tick_enable_compare", rc);          // after the audio monitor, before the first submit
 
@@ -221,6 +223,8 @@ int main(int argc, char **argv)
                 }
     };
     size_t used = 0;                                             // feed frames stream 0 has been given; stream s is s frames ahead in the file
+    // the packets of wanted slot k (counted from 0) are lost: the slot stays empty, and the file advances
+    auto dropped = [&](size_t k) { return drop_every && k % (size_t)drop_every >= (size_t)(drop_every - drop_run); };
     for (; down_feed;) {                                         // a down feed: one or two frames of the file per tick, as the schedule says
         const size_t want = (size_t)tlb_tick_down_feed_want(t, 0);   // (every stream has the one configuration: all want the same)
         if (used + want > fpos.size()) break;
@@ -229,6 +233,7 @@ int main(int argc, char **argv)
         const size_t stride = (size_t)tlb_tick_down_feed_stride(t);
         for (int s = 0; s < nstreams; s++)
             for (size_t j = 0; j < want; j++) {
+                if (dropped(used + j)) continue;
                 const size_t k = (used + j + (size_t)s) % fpos.size();
                 std::memcpy(fr + stride * (2 * (size_t)s + j), &mp2[fpos[k]], flen[k]);
                 ln[2 * s + (int)j] = (int32_t)flen[k];
@@ -246,8 +251,7 @@ int main(int argc, char **argv)
         uint8_t *fr = tlb_tick_feed(t);                          // pinned [nstreams][tlb_tick_feed_stride()], re-fetched every tick like the PCM
         int32_t *ln = tlb_tick_feed_len(t);                      // pinned [nstreams]: every set comes back all 0
         const size_t stride = (size_t)tlb_tick_feed_stride(t);
-        const bool dropped = drop_every && frames % drop_every >= drop_every - drop_run;      // the packets of this tick are lost: the slots stay empty
-        for (int s = 0; s < nstreams && want && !dropped; s++) {
+        for (int s = 0; s < nstreams && want && !dropped(used); s++) {
             const size_t k = (used + (size_t)s) % fpos.size();
             std::memcpy(fr + stride * (size_t)s, &mp2[fpos[k]], flen[k]);
             ln[s] = (int32_t)flen[k];

@@ -17,9 +17,10 @@
 // 48 kHz encoder, stereo for mono, ...; a slot of the call then holds a frame only on the ticks tlb_feed_want_at says want one.
 // A 48, 44.1 or 32 kHz file with -r 24000 is a DOWN FEED (tlb_feed_down_set): a tick has two slots and takes the one or two frames
 // tlb_feed_down_want_at asks for; the device decodes, filters and decimates them (tlb_feed_down_host).
-// --conceal [HOLD] (with --from-mp2, the file's own rate and channel count): feed concealment (tlb_conceal_enable, step 3): a frame of the
-// file that does not pass goes in as the last good frame once more, 6 dB quieter per lost frame, for HOLD frames (default 4), then the
-// filterbank rings out -- not as silence.  One more line at the end: stream 0's record.
+// --conceal [HOLD] (with --from-mp2): feed concealment, step 3: a frame of the file that does not pass goes in as the last good frame
+// once more, 6 dB quieter per lost frame, for HOLD frames (default 4), then the filterbank rings out -- not as silence.  At the file's own
+// rate and channel count that is tlb_conceal_enable; with -r or -c (an adapted or a down feed) it is tlb_feed_loss_enable, which conceals
+// the feed's WANTED slots ahead of the resampler or decimator.  One more line at the end: stream 0's record.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -141,8 +142,9 @@ int main(int argc, char **argv)
     if (down && (err = tlb_feed_down_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_down_set", err);
     if (from_mp2 && !adapt && !down && (err = tlb_feed_set(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set", err);
     if (adapt && (err = tlb_feed_set_adapted(enc, -1, &feed)) != TLB_OK) die("tlb_feed_set_adapted", err);
-    if (conceal && (!from_mp2 || adapt || down)) die("--conceal needs --from-mp2 at the file's own rate and channel count (a strict feed)", 0);
-    if (conceal && (err = tlb_conceal_enable(enc, -1, conceal, 3)) != TLB_OK) die("tlb_conceal_enable", err);
+    if (conceal && !from_mp2) die("--conceal needs --from-mp2 (a Layer II feed to conceal)", 0);
+    if (conceal && !(adapt || down) && (err = tlb_conceal_enable(enc, -1, conceal, 3)) != TLB_OK) die("tlb_conceal_enable", err);
+    if (conceal && (adapt || down) && (err = tlb_feed_loss_enable(enc, -1, conceal, 3)) != TLB_OK) die("tlb_feed_loss_enable", err);     // -r / -c: the feed's WANTED slots
     const int fstride = down ? tlb_feed_down_stride(enc) : tlb_feed_stride(enc);
     const size_t per_tick = down ? 2 : 1;                     // feed slots per stream and tick
 

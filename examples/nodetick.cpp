@@ -23,8 +23,9 @@
 //   --monitor check|audio: the confidence monitor (tlb_node_enable_monitor): every frame that leaves is checked on its GPU (audio: also
 //   decoded); one summary line at the end -- frames checked, bad frames, longest bad run over all services, services whose decoded output
 //   is silent -- and a non-zero exit status when any frame was bad.
-//   --feed-drop-every N --feed-drop-run M (a strict --feed): the last M ticks of every N leave every service's feed slot empty -- lost packets.
-//   --conceal [HOLD] --conceal-step N (a strict --feed): feed concealment (tlb_node_enable_conceal): a lost frame is the last good one once more,
+//   --feed-drop-every N --feed-drop-run M (with --feed): the last M of every N WANTED slots of every service (on a strict feed: ticks) stay empty -- lost packets.
+//   --conceal [HOLD] --conceal-step N (with --feed; tlb_node_enable_feed_loss with --feed-rate / --feed-channels and for a down feed, where a
+//   dropped frame is a WANTED slot left empty): feed concealment (tlb_node_enable_conceal): a lost frame is the last good one once more,
 //   N scalefactor-index units (default 3: 6 dB) quieter per lost frame, for HOLD frames (default 4), then the filterbank rings out.  One line
 //   at the end: the services' records summed -- slots, passed, concealed, muted, loss runs, the longest run.
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file (the services' rate, two channels, K kbps) decoded on the GPUs ahead
@@ -94,7 +95,8 @@ static void fill(void *vctx, int g, int first, int n)
         }
         const size_t stride = (size_t)tlb_node_down_feed_stride(c.nd, s);
         for (int j = 0; j < tlb_node_down_feed_want(c.nd, s); j++) {
-            const size_t f = (*c.fcur)[(size_t)s]++ % c.fpos->size();
+            const size_t k = (*c.fcur)[(size_t)s]++, f = k % c.fpos->size();      // the service's wanted slot k - s
+            if (c.drop_every && (k - (size_t)s) % (size_t)c.drop_every >= (size_t)(c.drop_every - c.drop_run)) continue;       // its packets are lost: the slot stays empty, the file advances
             std::memcpy(slot + stride * (size_t)j, c.mp2->data() + (*c.fpos)[f], (*c.flen)[f]);
             len[j] = (int32_t)(*c.flen)[f];                          // untouched, it reads 0: an empty slot
         }
@@ -107,12 +109,13 @@ static void fill(void *vctx, int g, int first, int n)
             if (tlb_node_shard_status(c.nd, g, nullptr) != TLB_SHARD_OK) return;
             die("no feed set free", s);
         }
-        size_t f = ((size_t)s + (size_t)c.tick) % c.fpos->size();
-        if (c.drop_every && c.tick % c.drop_every >= c.drop_every - c.drop_run) continue;      // this tick's packets are lost: the slot stays empty
+        size_t f = ((size_t)s + (size_t)c.tick) % c.fpos->size(), k = (size_t)c.tick;      // k: the service's wanted slot, on a strict feed the tick
         if (c.fcur) {                                            // an adapted feed: a frame only where this tick wants one, and the file advances only then
             if (tlb_node_feed_want(c.nd, s) <= 0) continue;
-            f = (*c.fcur)[(size_t)s]++ % c.fpos->size();
+            k = (*c.fcur)[(size_t)s]++ - (size_t)s;
+            f = (k + (size_t)s) % c.fpos->size();
         }
+        if (c.drop_every && k % (size_t)c.drop_every >= (size_t)(c.drop_every - c.drop_run)) continue;       // this slot's packets are lost: it stays empty
         std::memcpy(slot, c.mp2->data() + (*c.fpos)[f], (*c.flen)[f]);
         *len = (int32_t)(*c.flen)[f];                            // untouched, it reads 0: an empty slot
     }
@@ -243,7 +246,7 @@ int main(int argc, char **argv)
     const bool down_feed = !feed_path.empty() && feed_rate > rate;   // a feed above the services' rate (tlb_node_set_down_feed)
     const bool adapt = !down_feed && (feed_rate != rate || feed_channels != 2);
     if (drop_every < 0 || drop_run < 0 || drop_run > drop_every || (drop_every > 0) != (drop_run > 0)) die("--feed-drop-every N --feed-drop-run M: 1 <= M <= N, both or neither", 0);
-    if ((conceal || drop_every) && (feed_path.empty() || down_feed || adapt)) die("--conceal and --feed-drop-every need a strict --feed (the services' rate, two channels)", 0);
+    if ((conceal || drop_every) && feed_path.empty()) die("--conceal and --feed-drop-every need a strict --feed (the services' rate, two channels)", 0);
     std::vector<uint8_t> mp2;
     std::vector<size_t> fpos, flen;
     if (!feed_path.empty()) {
@@ -315,8 +318,10 @@ int main(int argc, char **argv)
     if (down_feed) { if (int rc = tlb_node_set_down_feed(nd, -1, &feed)) die("tlb_node_set_down_feed", rc); }       // between steps; a restarted shard's down feeds are set again at tick 0
     else if (!feed_path.empty())
         if (int rc = adapt ? tlb_node_set_feed_adapted(nd, -1, &feed) : tlb_node_set_feed(nd, -1, &feed)) die("tlb_node_set_feed", rc);                    // between steps; a restarted shard's feeds are set again
-    if (conceal)
+    if (conceal && !(adapt || down_feed))
         if (int rc = tlb_node_enable_conceal(nd, -1, conceal, conceal_step)) die("tlb_node_enable_conceal", rc);      // behind the feeds, between steps; a restarted shard's is set again
+    if (conceal && (adapt || down_feed))                                 // an adapted or a down feed: its WANTED slots, ahead of the resampler or decimator
+        if (int rc = tlb_node_enable_feed_loss(nd, -1, conceal, conceal_step)) die("tlb_node_enable_feed_loss", rc);
     const tlb_compare_params cparams = {TLB_COMPARE_DEFAULT_MIN_ENERGY, TLB_COMPARE_DEFAULT_CORR_NUM, TLB_COMPARE_DEFAULT_CORR_DEN};
     if (compare)
         if (int rc = tlb_node_enable_compare(nd, &cparams)) die("tlb_node_enable_compare", rc);         // after the audio monitor, before the first submit

@@ -1365,7 +1365,9 @@ const tlb_limiter_record *tlb_node_limiter(const tlb_node *nd, int stream);
 int tlb_node_limiter_reset(tlb_node *nd, int stream);
 
 /* ------------------------------------------------------------------------------------------
- * CONCEALMENT of lost frames on a strict Layer II feed (tlb_conceal_*; csrc/mp2_conceal.h, csrc/toolame_conceal.hip).  Without it "an empty
+ * CONCEALMENT of lost frames on a Layer II feed -- strict, adapted or down (tlb_conceal_*; csrc/mp2_conceal.h, csrc/toolame_conceal.hip and,
+ * for adapted and down feeds, tlb_feed_loss_enable / tlb_*_enable_feed_loss -- the tlb_conceal_* names are the strict-feed family as it was
+ * first shipped, and its set is closed --; csrc/mp2_conceal_conv.h, csrc/toolame_conceal_conv.hip).  Without it "an empty
  * slot or a frame that does not pass is silence" (tlb_feed_*): 24 ms of digital zero cut in hard, and the good frame behind it synthesised
  * over a silent filter history -- two discontinuities per lost packet, which the encoder then broadcasts.  With it a lost frame is the last
  * good frame once more, quieter with every repeat, and the good frame behind a loss continues from that repeat.
@@ -1385,7 +1387,15 @@ int tlb_node_limiter_reset(tlb_node *nd, int stream);
  *   a passing slot behind a passing slot: untouched
  * The result depends on the sequence of slots only, never on how it is cut into calls or ticks.  The feed's own tlb_frame_report is
  * unchanged: a concealed slot still reports why it was lost.
- * RECORD.  tlb_conceal_record, 32 bytes: frames = slots seen; passed; concealed = lost slots synthesised from G (the ring-out frame
+ * THE SEQUENCE.  A strict feed wants a frame every tick: every slot is a slot of the sequence, and an empty one is a lost packet.  The
+ * sequence of a stream with an ADAPTED or a DOWN feed is its WANTED slots only, in order: the ticks with tlb_feed_want_at == 1, or slots
+ * j < tlb_feed_down_want_at of every tick, slot 0 before slot 1.  An unwanted slot, empty or TLB_DEC_UNWANTED, is no slot of the sequence:
+ * it neither passes nor is lost, and touches neither k nor G nor the record.  What the rule makes of a wanted slot replaces its 1152 decoded
+ * source frames, in the feed's channel layout, BEFORE the channel map and the resampler or decimator read them and before the queue keeps
+ * them.  So the PCM the ingest receives is, bit for bit, that of the chain "strict feed with tlb_conceal_enable at the feed's own rate and
+ * channel count over the wanted slots, the channel map, tlb_resample_* or tlb_decimate_*" -- both discontinuities are gone before the filter
+ * could smear them.
+ * RECORD.  tlb_conceal_record, 32 bytes: frames = slots of the sequence seen (wanted slots); passed; concealed = lost slots synthesised from G (the ring-out frame
  * included); muted = lost slots left as zeros; runs = loss runs begun; longest = the longest loss run; run = k now; offset = o(k) of the last
  * slot, 0 for a passing one, TLB_CONCEAL_MUTE for MUTE.  A stream without concealment has an all-zero record.
  * CALLS.  Opt-in per stream; a batch that never enables it allocates nothing and makes the device calls it made before.
@@ -1393,44 +1403,58 @@ int tlb_node_limiter_reset(tlb_node *nd, int stream);
  *                                     switches concealment off (step is then not read).  TLB_ERR_ARG for a stream without a strict feed
  *                                     (none, an adapted one, a down feed), hold > 16, step outside 1..21.  Waits for the queued work;
  *                                     the named streams' G, run and record start again
+ *   tlb_feed_loss_enable(b, stream, hold, step)  the same call for a stream with a Layer II feed of ANY kind: on a stream with a strict
+ *                                     feed it is tlb_conceal_enable; on one with an adapted or a down feed it switches the concealment
+ *                                     of THE SEQUENCE above on.  TLB_ERR_ARG for a stream with no feed at all, hold > 16, step outside
+ *                                     1..21; -1 and hold 0 as above.  The four calls below serve every kind of stream
  *   tlb_conceal_get(b, stream, &hold, &step)  1: on, 0: off (both 0), negative: -TLB_ERR_ARG.  Either pointer may be NULL
  *   tlb_conceal_reset(b, stream)      -1: every stream.  Waits for the queued work, then forgets G, run and the record; the parameters stay
  *   tlb_conceal_records_device(b, d_records, hip_stream)  queues a copy of tlb_conceal_record [nstreams] into device memory on hip_stream
  *                                     (the stream the feed calls are queued on): the records as of the last feed call queued there
  *   tlb_conceal_records_host(b, records)  waits for the device, then the same into host memory
  * tlb_feed_device and tlb_feed_host queue the two concealment kernels themselves, behind the feed's own two (which run exactly as before),
- * whenever some stream of the batch has concealment on.  tlb_feed_set on a stream (removal included) switches its concealment OFF -- G would
- * be a frame of another format --, and tlb_feed_reset and every call that implies it (tlb_reset, tlb_stream_reset, tlb_stream_reconfigure)
- * forget the stream's G, run and record like tlb_conceal_reset.
- * Device memory per stream of a batch that has concealment on: the feed history's slot width (tlb_feed_stride at the time; at most 1728
- * bytes, 576 for 192 kbps at 48 kHz) for G, plus 48 (the record and the parameters with G's length).
+ * whenever some stream with a strict feed has concealment on.  The adapted path then runs decode, conceal, resample, carry, conceal-carry and
+ * the down path (tlb_feed_down_device / _host) decode, conceal, decimate, carry, conceal-carry, the two new kernels only when some adapted
+ * (or down) stream of the batch has concealment on: a batch without one queues exactly the kernels it queued before.  tlb_feed_set,
+ * tlb_feed_set_adapted and tlb_feed_down_set on a stream (removal included) switch its concealment OFF -- G would be a frame of another
+ * format --, and tlb_feed_reset, tlb_feed_down_reset and every call that implies either (tlb_reset, tlb_stream_reset,
+ * tlb_stream_reconfigure) forget the stream's G, run and record like tlb_conceal_reset.  tlb_stream_reconfigure keeps hold and step of a
+ * stream of any kind whose feed stays legal with the new configuration; one that removes the feed takes the concealment with it.
+ * Device memory per stream of a batch that has concealment on: the widest feed history slot of any kind in the batch (tlb_feed_stride at
+ * the time, 576 bytes for 192 kbps at 48 kHz; 1728 once the batch has a down feed) for G, plus 48 (the record and the parameters with G's
+ * length).
  * TICK PLANE.  tlb_tick_enable_conceal(t, stream, hold, step) is tlb_conceal_enable routed to the stream's group (-1: all, checked first),
  * legal while no tick is in flight (TLB_ERR_ARG otherwise); the first call that switches concealment on makes the records' pinned sets.
  * The records travel with the three output sets behind the packets, on an event of their own.  tlb_tick_conceal(t) is tlb_conceal_record
  * [nstreams] of the tick waited for last (pinned, valid until the next wait); NULL until concealment has been enabled.  tlb_tick_finish
  * adds nothing.  tlb_tick_conceal_reset(t, stream) (-1: all) is legal with no tick in flight.  tlb_tick_set_feed on a stream switches its
- * concealment off as tlb_feed_set does.
+ * concealment off as tlb_feed_set does, and so do tlb_tick_set_feed_adapted and tlb_tick_set_down_feed.  tlb_tick_enable_feed_loss is
+ * tlb_feed_loss_enable routed the same way.
  * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_conceal routes to the stream's shard (-1: every shard) between
  * steps; every named stream needs a strict feed set through tlb_node_set_feed, and tlb_node_set_feed on a stream switches its concealment
  * off.  A shard made by tlb_node_shard_restart gets its streams' concealment again behind their feeds, from zero.  tlb_node_conceal(nd,
  * stream) points at the STREAM's record and answers NULL for a broken, late or stale shard and for a shard none of whose streams ever
- * enabled it; tlb_node_conceal_reset routes like tlb_node_loudness_reset.
- * NOT BUILT: concealment for adapted and down feeds (their queues hold decoded samples; the same rule applies to the frame ahead of the
- * queue), interpolation between the frames either side of a loss, any change to the feed report.
+ * enabled it; tlb_node_conceal_reset routes like tlb_node_loudness_reset.  tlb_node_enable_feed_loss (TICK plane only) accepts a feed of
+ * any kind the node remembers (tlb_node_set_feed, _set_feed_adapted, _set_down_feed; each of them switches the stream's concealment off) and
+ * is set again on a restarted shard the same way.
+ * NOT BUILT: interpolation between the frames either side of a loss, any change to the feed report.
  * ------------------------------------------------------------------------------------------ */
 #define TLB_CONCEAL_MAX_HOLD 16
 #define TLB_CONCEAL_MAX_STEP 21
 #define TLB_CONCEAL_MUTE 0xFFFFFFFFu
 typedef struct { uint32_t frames, passed, concealed, muted, runs, longest, run, offset; } tlb_conceal_record;      /* 32 bytes */
 int tlb_conceal_enable(tlb_batch *b, int stream, int hold, int step);
+int tlb_feed_loss_enable(tlb_batch *b, int stream, int hold, int step);
 int tlb_conceal_get(const tlb_batch *b, int stream, int *hold, int *step);
 int tlb_conceal_reset(tlb_batch *b, int stream);
 int tlb_conceal_records_device(tlb_batch *b, tlb_conceal_record *d_records, void *hip_stream);
 int tlb_conceal_records_host(tlb_batch *b, tlb_conceal_record *records);
 int tlb_tick_enable_conceal(tlb_tick *t, int stream, int hold, int step);
+int tlb_tick_enable_feed_loss(tlb_tick *t, int stream, int hold, int step);
 const tlb_conceal_record *tlb_tick_conceal(const tlb_tick *t);
 int tlb_tick_conceal_reset(tlb_tick *t, int stream);
 int tlb_node_enable_conceal(tlb_node *nd, int stream, int hold, int step);
+int tlb_node_enable_feed_loss(tlb_node *nd, int stream, int hold, int step);
 const tlb_conceal_record *tlb_node_conceal(const tlb_node *nd, int stream);
 int tlb_node_conceal_reset(tlb_node *nd, int stream);
 

@@ -15,6 +15,7 @@
 #include "mp2_feed_adapt.h"
 #include "mp2_feed_down.h"
 #include "mp2_conceal.h"
+#include "mp2_conceal_conv.h"
 #include "mp2_loudness.h"
 #include "mp2_truepeak.h"
 #include "mp2_limiter.h"
@@ -48,10 +49,18 @@ hipError_t tlk_feed(hipStream_t st, const TlFeedLaunch &A);
 // toolame_conceal.hip: behind tlk_feed on the same stream when some stream has concealment on: tl_conceal_kernel over every (stream, slot)
 // of the launch, then tl_conceal_carry_kernel per stream (csrc/mp2_conceal.h)
 hipError_t tlk_conceal(hipStream_t st, const TlConcealLaunch &A);
-// toolame_feed_adapt.hip: the decode kernel over every (stream, slot) of the call, the resample kernel (one workgroup per slot), then the carry kernel per stream
-hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A);
-// toolame_feed_down.hip: the decode kernel over every (stream, slot) of the call with two slots per tick, the decimate kernel (one workgroup per tick and stream), then the carry kernel per stream
-hipError_t tlk_feed_down(hipStream_t st, const TlFeedDownLaunch &A);
+// toolame_feed_adapt.hip: the decode kernel over every (stream, slot) of the call, the resample kernel (one workgroup per slot), then the carry kernel per stream.
+// cc (some adapted stream has concealment on): tlk_conceal_adapt behind the decode kernel and tlk_conceal_adapt_carry behind the carry kernel
+hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A, const TlConcealConv *cc = nullptr);
+// toolame_feed_down.hip: the decode kernel over every (stream, slot) of the call with two slots per tick, the decimate kernel (one workgroup per tick and stream), then the carry kernel per stream.
+// cc (some stream with a down feed has concealment on): tlk_conceal_down behind the decode kernel and tlk_conceal_down_carry behind the carry kernel
+hipError_t tlk_feed_down(hipStream_t st, const TlFeedDownLaunch &A, const TlConcealConv *cc = nullptr);
+// toolame_conceal_conv.hip (csrc/mp2_conceal_conv.h), one kernel each: tl_conceal_adapt_kernel over every (tick, stream), tl_conceal_down_kernel over every
+// (tick, stream, slot), and their carry kernels per stream
+hipError_t tlk_conceal_adapt(hipStream_t st, const TlConcealAdaptLaunch &A);
+hipError_t tlk_conceal_adapt_carry(hipStream_t st, const TlConcealAdaptLaunch &A);
+hipError_t tlk_conceal_down(hipStream_t st, const TlConcealDownLaunch &A);
+hipError_t tlk_conceal_down_carry(hipStream_t st, const TlConcealDownLaunch &A);
 // toolame_ingest.hip: tl_ingest_valid_kernel, or tl_ingest_kernel when valid (int32 [nframes][nstreams]) is NULL (one workgroup per slot);
 // tl_silence_kernel and tl_underrun_kernel (256 threads, one per stream)
 hipError_t tlk_ingest(unsigned blocks, hipStream_t st, const int16_t *in, const int32_t *valid /* may be NULL */, int16_t *out, int16_t *peaks, const double *gain,

@@ -1,6 +1,7 @@
 // tlb_conceal.cpp -- the batch-level entry points of the feed concealment (include/toolame_batch.h, tlb_conceal_*): the per-stream
-// parameters, record and G buffer (allocated by the first tlb_conceal_enable that switches concealment on) and the launch of the kernels of
-// toolame_conceal.hip behind the feed's own (tlb_feed.cpp: feed_launch) through tl_kernels.h.  Host C++.
+// parameters, record and G buffer (allocated by the first tlb_conceal_enable or tlb_feed_loss_enable that switches concealment on) and
+// the launch of the kernels of toolame_conceal.hip behind the feed's own (tlb_feed.cpp: feed_launch) through tl_kernels.h.  The adapted
+// and the down path queue the kernels of toolame_conceal_conv.hip themselves, with the arrays conceal_conv hands them.  Host C++.
 #include <stddef.h>
 #include "tlb_internal.h"
 
@@ -15,12 +16,34 @@ int conceal_clear_streams(tlb_batch *b, int s0, int n, bool off)
 {
     if (!b->d_cc_state) return TLB_OK;
     for (int s = s0; s < s0 + n && off; s++) b->cc_host[(size_t)s].hold = b->cc_host[(size_t)s].step = 0;
-    b->n_conceal = 0;
-    for (const TlConcealStream &c : b->cc_host) b->n_conceal += c.hold != 0;
+    b->n_conceal = b->n_conceal_adapt = b->n_conceal_down = 0;
+    for (int s = 0; s < b->nstreams; s++)
+        if (b->cc_host[(size_t)s].hold) ++*(b->fd.on(s) ? &b->n_conceal_down : tlb_feed_adapted(b, s) > 0 ? &b->n_conceal_adapt : &b->n_conceal);
     HIPCHK(hipMemcpy(b->d_cc_state + s0, b->cc_host.data() + s0, (size_t)n * sizeof(TlConcealStream), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(b->d_cc_rec + s0, 0, (size_t)n * sizeof(TlConcealRecord)));
     HIPCHK(hipDeviceSynchronize());              // the callers' streams do not wait for the null stream
     return TLB_OK;
+}
+
+int conceal_clear_family(tlb_batch *b, int s0, int n, bool down, bool off)
+{
+    if (!b->d_cc_state) return TLB_OK;
+    const auto other = [&](int s) { return down ? b->feed.on(s) : b->fd.on(s); };     // (a stream has one feed: csrc/tlb_inputs.h)
+    for (int s = s0; s < s0 + n;) {
+        if (other(s)) { s++; continue; }
+        int e = s;
+        while (e < s0 + n && !other(e)) e++;
+        if (int rc = conceal_clear_streams(b, s, e - s, off)) return rc;
+        s = e;
+    }
+    return TLB_OK;
+}
+
+const TlConcealConv *conceal_conv(const tlb_batch *b, bool down, TlConcealConv *x)
+{
+    if (!(down ? b->n_conceal_down : b->n_conceal_adapt)) return nullptr;
+    x->cs = b->d_cc_state; x->rec = b->d_cc_rec; x->g = b->d_cc_g; x->g_stride = b->cc_g_stride; x->pad_ = 0;
+    return x;
 }
 
 // room for slots of `stride` bytes in the G buffer; what it holds is kept (the device is idle).  An owner of its own, as d_feed_prev has
@@ -38,7 +61,7 @@ int conceal_g_reserve(tlb_batch *b, int stride)
     return TLB_OK;
 }
 
-// the first enable that switches concealment on: parameters (all off), records, and G as wide as the feed history's slots
+// the first enable that switches concealment on: parameters (all off), records, and G as wide as the widest feed history slot of any kind
 static int conceal_prepare(tlb_batch *b)
 {
     if (b->d_cc_state) return TLB_OK;
@@ -49,7 +72,8 @@ static int conceal_prepare(tlb_batch *b)
     if (!m.settle()) return TLB_ERR_HIP;
     b->cc_host.assign(n, TlConcealStream{0, 0, 0, 0});
     b->d_cc_state = st;
-    if (int rc = conceal_g_reserve(b, b->feed_prev_stride)) { b->d_cc_state = nullptr; b->cc_host.clear(); return rc; }
+    const int wide = b->d_fd_cfg && b->feed_prev_stride < TL_FD_PREV_STRIDE ? TL_FD_PREV_STRIDE : b->feed_prev_stride;
+    if (int rc = conceal_g_reserve(b, wide)) { b->d_cc_state = nullptr; b->cc_host.clear(); return rc; }
     m.commit(b->mem);
     b->d_cc_rec = rec;
     return TLB_OK;
@@ -65,9 +89,8 @@ int conceal_launch(tlb_batch *b, const TlFeedLaunch &A, void *hip_stream)
     return TLB_OK;
 }
 
-extern "C" {
-
-int tlb_conceal_enable(tlb_batch *b, int stream, int hold, int step)
+// any_feed: an adapted or a down feed will do (tlb_feed_loss_enable)
+static int conceal_enable(tlb_batch *b, int stream, int hold, int step, bool any_feed)
 {
     if (!b || stream < -1 || stream >= b->nstreams || hold < 0 || hold > TL_CC_MAX_HOLD) return TLB_ERR_ARG;
     if (hold > 0 && (step < 1 || step > TL_CC_MAX_STEP)) return TLB_ERR_ARG;
@@ -78,8 +101,11 @@ int tlb_conceal_enable(tlb_batch *b, int stream, int hold, int step)
         HIPCHK(hipDeviceSynchronize());
         return conceal_clear_streams(b, s0, s1 - s0, true);
     }
-    // every named stream is checked before anything changes: a strict feed (an adapted stream's queue, and a down feed's, hold decoded samples)
-    for (int s = s0; s < s1; s++) if (tlb_feed_get(b, s, nullptr) <= 0 || tlb_feed_adapted(b, s) != 0) return TLB_ERR_ARG;
+    // every named stream is checked before anything changes: a strict feed, or with any_feed a Layer II feed of any kind
+    for (int s = s0; s < s1; s++) {
+        const bool strict = tlb_feed_get(b, s, nullptr) > 0 && tlb_feed_adapted(b, s) == 0;
+        if (!strict && !(any_feed && (tlb_feed_get(b, s, nullptr) > 0 || tlb_feed_down_get(b, s, nullptr) > 0))) return TLB_ERR_ARG;
+    }
     if (b->broken) return TLB_ERR_HIP;
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
@@ -87,6 +113,11 @@ int tlb_conceal_enable(tlb_batch *b, int stream, int hold, int step)
     for (int s = s0; s < s1; s++) { b->cc_host[(size_t)s].hold = (uint32_t)hold; b->cc_host[(size_t)s].step = (uint32_t)step; }
     return conceal_clear_streams(b, s0, s1 - s0);
 }
+
+extern "C" {
+
+int tlb_conceal_enable(tlb_batch *b, int stream, int hold, int step) { return conceal_enable(b, stream, hold, step, false); }
+int tlb_feed_loss_enable(tlb_batch *b, int stream, int hold, int step) { return conceal_enable(b, stream, hold, step, true); }
 
 int tlb_conceal_get(const tlb_batch *b, int stream, int *hold, int *step)
 {

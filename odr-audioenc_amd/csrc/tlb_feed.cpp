@@ -49,7 +49,7 @@ int feed_clear_streams(tlb_batch *b, int s0, int n)
 {
     if (!b->d_feed_state) return TLB_OK;
     HIPCHK(hipMemset(b->d_feed_state + s0, 0, sizeof(TlDecStream) * (size_t)n));
-    if (int rc = conceal_clear_streams(b, s0, n)) return rc;         // a stream's concealment starts again with its history (G, run, record)
+    if (int rc = conceal_clear_family(b, s0, n, false)) return rc;   // a stream's concealment starts again with its history (G, run, record); a down feed's has its own
     if (!b->d_fa_carry) return TLB_OK;
     for (int k = 0; k < 2; k++) {                                    // an adapted stream's next tick is tick 0 and its queue is empty
         HIPCHK(hipMemset(b->d_fa_carry + ((size_t)k * (size_t)b->nstreams + (size_t)s0) * (TL_FA_CARRY * 2), 0, sizeof(int16_t) * TL_FA_CARRY * 2 * (size_t)n));
@@ -126,7 +126,9 @@ static int feed_prev_reserve(tlb_batch *b, int stride)
 
 // streams [s0, s1) get feed record `idx` (-1: none); their history starts again
 // adapt: the record goes into the adapted path's table and the strict kernel sees a stream without a feed
-static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_config &cfg, bool adapt = false)
+// same_feed: the streams keep the feed they have (a reconfiguration that leaves the pair legal): their concealment stays on, and
+// feed_clear_streams forgets its G, run and record with the history
+static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_config &cfg, bool adapt = false, bool same_feed = false)
 {
     std::vector<int32_t> v((size_t)(s1 - s0), adapt ? -1 : idx);
     HIPCHK(hipMemcpy(b->d_feed_cfg + s0, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice));
@@ -140,7 +142,7 @@ static int feed_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_con
         for (int32_t x : b->fa_ratio) b->n_adapted += x >= 0;
     }
     for (int s = s0; s < s1; s++) { b->feed.idx[(size_t)s] = idx; b->feed.cfg[(size_t)s] = cfg; }
-    if (int rc = conceal_clear_streams(b, s0, s1 - s0, true)) return rc;      // another feed, or none: concealment off (G would be a frame of another format)
+    if (!same_feed) if (int rc = conceal_clear_family(b, s0, s1 - s0, false, true)) return rc;       // another feed, or none: concealment off (G would be a frame of another format)
     return feed_clear_streams(b, s0, s1 - s0);
 }
 
@@ -150,7 +152,7 @@ int feed_after_reconfigure(tlb_batch *b, int stream)
     const tlb_stream_config &sc = b->h_uniq[(size_t)b->h_stream_cfg[(size_t)stream]];
     const tlb_feed_config fc = b->feed.cfg[(size_t)stream];
     if (adapted(b, stream)) {                                        // kept while the rates still form a legal pair, whatever the channel counts; the caller clears the state
-        if (tl_fa_ratio_of(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed.idx[(size_t)stream], fc, true);
+        if (tl_fa_ratio_of(fc.samplerate, sc.samplerate) >= 0) return feed_assign(b, stream, stream + 1, b->feed.idx[(size_t)stream], fc, true, true);      // (its concealment stays, as a strict and a down feed's do)
     } else if (fc.samplerate == sc.samplerate && fc.channels == (sc.mode == 'm' ? 1 : 2)) return TLB_OK;
     return feed_assign(b, stream, stream + 1, -1, tlb_feed_config{0, 0, 0});
 }
@@ -188,7 +190,8 @@ int feed_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len, int
     D.F = A; D.F.feed_cfg = b->d_fa_cfg;
     D.ratio = b->d_fa_ratio; D.sconfigs = b->d_configs; D.stream_cfg = b->d_stream_cfg; D.taps = b->d_fa_taps;
     D.plane = b->d_fa_plane; D.carry = b->d_fa_carry; D.pos = b->d_fa_pos; D.flip = b->fa_flip; D.strict_ran = n_strict > 0;
-    HIPCHK(tlk_feed_adapt((hipStream_t)hip_stream, D));
+    TlConcealConv X;                                                 // (NULL unless some adapted stream has concealment on: conceal behind decode, its carry behind carry)
+    HIPCHK(tlk_feed_adapt((hipStream_t)hip_stream, D, conceal_conv(b, false, &X)));
     b->fa_flip ^= 1;
     for (int s = 0; s < b->nstreams; s++)
         if (adapted(b, s)) b->fa_pos[(size_t)s] = (int32_t)(((long long)b->fa_pos[(size_t)s] + nframes) % tl_fa_cycle(b->fa_ratio[(size_t)s]));

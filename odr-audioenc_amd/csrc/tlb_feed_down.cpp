@@ -22,7 +22,7 @@ int feed_down_clear_streams(tlb_batch *b, int s0, int n)
         HIPCHK(hipMemset(b->d_fd_pos + (size_t)k * (size_t)b->nstreams + (size_t)s0, 0, sizeof(int32_t) * (size_t)n));
     }
     for (int s = s0; s < s0 + n; s++) b->fd_pos[(size_t)s] = 0;
-    return TLB_OK;
+    return conceal_clear_family(b, s0, n, true);                     // a stream's concealment starts again with its history (G, run, record)
 }
 
 // room for `frames` ticks per stream in the source plane: grow-only launch scratch with an owner of its own (the device is idle)
@@ -70,6 +70,7 @@ static int down_assign(tlb_batch *b, int s0, int s1, int idx, const tlb_feed_con
     for (int s = s0; s < s1; s++) { b->fd.idx[(size_t)s] = idx; b->fd.cfg[(size_t)s] = cfg; b->fd_ratio[(size_t)s] = r[(size_t)(s - s0)]; }
     b->n_down = 0;
     for (int32_t x : b->fd.idx) b->n_down += x >= 0;
+    if (int rc = conceal_clear_family(b, s0, s1 - s0, true, true)) return rc;        // another down feed, or none: concealment off, as tlb_feed_set does
     return feed_down_clear_streams(b, s0, s1 - s0);
 }
 
@@ -102,7 +103,8 @@ int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len
     D.F.nstreams = b->nstreams; D.F.nframes = nframes; D.F.stride = stride;
     D.ratio = b->d_fd_ratio; D.sconfigs = b->d_configs; D.stream_cfg = b->d_stream_cfg; D.taps = b->d_fd_taps;
     D.plane = b->d_fd_plane; D.carry = b->d_fd_carry; D.pos = b->d_fd_pos; D.flip = b->fd_flip;
-    HIPCHK(tlk_feed_down((hipStream_t)hip_stream, D));
+    TlConcealConv X;                                                 // (NULL unless some stream with a down feed has concealment on: conceal behind decode, its carry behind carry)
+    HIPCHK(tlk_feed_down((hipStream_t)hip_stream, D, conceal_conv(b, true, &X)));
     b->fd_flip ^= 1;
     for (int s = 0; s < b->nstreams; s++)
         if (b->fd.on(s)) b->fd_pos[(size_t)s] = (int32_t)(((long long)b->fd_pos[(size_t)s] + nframes) % tl_fd_cycle(b->fd_ratio[(size_t)s]));
@@ -132,6 +134,7 @@ int tlb_feed_down_set(tlb_batch *b, int stream, const tlb_feed_config *cfg)
     HIPCHK(hipSetDevice(b->device));
     HIPCHK(hipDeviceSynchronize());
     if (int rc = down_prepare(b)) return rc;
+    if (int rc = conceal_g_reserve(b, TL_FD_PREV_STRIDE)) return rc; // (nothing unless concealment was enabled: G is as wide as the widest history slot)
     if (int rc = b->fd.reserve(b->fd.h_configs.size() + (idx < 0 ? 1 : 0))) return rc;
     if (int rc = b->fd.add(*cfg, *c, &idx)) return rc;
     return down_assign(b, s0, s1, idx, *cfg);

@@ -220,10 +220,11 @@ struct tlb_batch {
     uint32_t *d_lm_step = nullptr;               // [nstreams] S from the stream's encoder rate
     int16_t *d_lm_taps = nullptr;                // the true-peak meter's committed table, a copy of the limiter's own
     tlb_limiter_params lm_params = {0, 0};       // as enabled, the defaults filled in
-    // feed concealment (tlb_conceal.cpp; csrc/mp2_conceal.h), allocated by the first tlb_conceal_enable that switches it on: a batch that
-    // never enables it has none of it
+    // feed concealment (tlb_conceal.cpp; csrc/mp2_conceal.h, csrc/mp2_conceal_conv.h), allocated by the first tlb_conceal_enable or
+    // tlb_feed_loss_enable that switches it on: a batch that never enables it has none of it
     std::vector<TlConcealStream> cc_host;        // [nstreams] the parameters as set (g_len is not kept here); empty until allocated
-    int n_conceal = 0;                           // streams with hold > 0: the feed launch queues the two kernels while this is not 0
+    int n_conceal = 0;                           // streams with a strict feed and hold > 0: the feed launch queues the two kernels while this is not 0
+    int n_conceal_adapt = 0, n_conceal_down = 0; // ... with an adapted / a down feed: that path's launch queues the two kernels of toolame_conceal_conv.hip
     TlConcealStream *d_cc_state = nullptr;       // [nstreams]
     TlConcealRecord *d_cc_rec = nullptr;         // [nstreams] the record as it is reported
     uint8_t *d_cc_g = nullptr;                   // [nstreams][cc_g_stride] the last passing slot; replaced when a longer feed frame arrives
@@ -295,6 +296,11 @@ int feed_down_launch(tlb_batch *b, const uint8_t *d_frames, const int32_t *d_len
 int conceal_clear_streams(tlb_batch *b, int s0, int n, bool off = false);
 int conceal_g_reserve(tlb_batch *b, int stride);
 int conceal_launch(tlb_batch *b, const TlFeedLaunch &A, void *hip_stream);
+// ... the same clearing for one feed family's life-cycle calls: down = false leaves the streams with a down feed alone (tlb_feed_*),
+// down = true those with a strict or an adapted feed (tlb_feed_down_*); the concealment's arrays for the adapted (down = false) or the
+// down path's launch into *x, NULL: no such stream has concealment on and the path queues what it always queued
+int conceal_clear_family(tlb_batch *b, int s0, int n, bool down, bool off = false);
+const TlConcealConv *conceal_conv(const tlb_batch *b, bool down, TlConcealConv *x);
 
 // The PCM meters (tlb_loudness.cpp, tlb_truepeak.cpp).  A meter's state of streams [s0, s0 + n) back to zero (the device is idle); nothing
 // when the meter was never enabled

@@ -171,8 +171,9 @@ struct tlb_node {
     // adapted: set through tlb_node_set_feed_adapted, and set again that way.  A family's vector is empty until it is first turned on.
     struct Input : tlb_feed_config { int adapted; };
     std::vector<Input> kept[TLB_IN_SHORT_READS];
-    // the feed concealment of every stream (tlb_node_enable_conceal), set again on a restarted shard behind its feeds; empty until first switched on
-    struct Conceal { int hold = 0, step = 0; };
+    // the feed concealment of every stream (tlb_node_enable_conceal, tlb_node_enable_feed_loss: any_feed, and set again that way), set again
+    // on a restarted shard behind its feeds; empty until first switched on
+    struct Conceal { int hold = 0, step = 0, any_feed = 0; };
     std::vector<Conceal> kept_conceal;
     // The families that are on, for tlb_input_may_set at OBJECT level.  That is the TICK plane's rule: every shard there is one tick object.
     // On the BATCH plane the node holds nothing back and the mask is empty: the shards' batches answer stream by stream (batch_inputs).
@@ -421,7 +422,7 @@ int shard_make(tlb_node *nd, Shard &s, long long now_s)
         }
     for (int k = 0; k < s.n && s.tick && !nd->kept_conceal.empty(); k++) {      // the feeds' concealment, from zero
         const tlb_node::Conceal &c = nd->kept_conceal[(size_t)(s.first + k)];
-        if (c.hold) if (int rc = tlb_tick_enable_conceal(s.tick, k, c.hold, c.step)) return rc;
+        if (c.hold) if (int rc = (c.any_feed ? tlb_tick_enable_feed_loss : tlb_tick_enable_conceal)(s.tick, k, c.hold, c.step)) return rc;
     }
     for (int k = 0; k < s.n; k++) {                                  // the caller's gains (0 dB needs no call)
         const double g = nd->gain_db[(size_t)(s.first + k)];
@@ -784,23 +785,32 @@ static int node_set_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg, b
     }
     const NodeInput v = node_feed(cfg, adapt);
     const int rc = node_set_input(nd, TLB_IN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
-    for (int i = s0; i < s1 && !rc && !nd->kept_conceal.empty(); i++) nd->kept_conceal[(size_t)i] = tlb_node::Conceal{};      // (a stream's new feed, or none, starts without concealment)
+    for (int i = s0; i < s1 && !rc && !nd->kept_conceal.empty(); i++)                // (a stream's new feed, or none, starts without concealment; a down feed's is its own family's)
+        if (nd->kept[TLB_IN_DOWN_FEED].empty() || !nd->kept[TLB_IN_DOWN_FEED][(size_t)i].samplerate) nd->kept_conceal[(size_t)i] = tlb_node::Conceal{};
     return rc;
 }
 // The feed concealment, per stream (TICK plane): tlb_tick_enable_conceal of the owning shards' objects between steps, remembered for restarts.
 // Every named stream needs a strict feed the node remembers; the rest is tlb_node::set_remembered's
-int tlb_node_enable_conceal(tlb_node *nd, int stream, int hold, int step)
+// any_feed (tlb_node_enable_feed_loss): a feed of any kind the node remembers, adapted and down feeds included
+static int node_enable_conceal(tlb_node *nd, int stream, int hold, int step, bool any_feed)
 {
     if (!nd || nd->plane != TLB_NODE_TICK || stream < -1 || stream >= nd->nstreams || nd->finished || !nd->t_submit.empty()) return TLB_ERR_ARG;
     if (hold < 0 || hold > TLB_CONCEAL_MAX_HOLD || (hold > 0 && (step < 1 || step > TLB_CONCEAL_MAX_STEP))) return TLB_ERR_ARG;
     const int s0 = stream < 0 ? 0 : stream, s1 = stream < 0 ? nd->nstreams : stream + 1;
-    const std::vector<NodeInput> &feeds = nd->kept[TLB_IN_FEED];
-    for (int i = s0; i < s1 && hold > 0; i++) if (feeds.empty() || !feeds[(size_t)i].samplerate || feeds[(size_t)i].adapted) return TLB_ERR_ARG;
-    tlb_node::Conceal v; v.hold = hold; v.step = hold ? step : 0;
+    const std::vector<NodeInput> &feeds = nd->kept[TLB_IN_FEED], &down = nd->kept[TLB_IN_DOWN_FEED];
+    for (int i = s0; i < s1 && hold > 0; i++) {
+        const bool fed = !feeds.empty() && feeds[(size_t)i].samplerate;
+        if (!(fed && !feeds[(size_t)i].adapted) && !(any_feed && (fed || (!down.empty() && down[(size_t)i].samplerate)))) return TLB_ERR_ARG;
+    }
+    tlb_node::Conceal v; v.hold = hold; v.step = hold ? step : 0; v.any_feed = hold && any_feed;
     return nd->set_remembered(stream, nd->kept_conceal, hold > 0, v,
-                              [](Shard &sh, int k, const tlb_node::Conceal &c) { return sh.tick ? tlb_tick_enable_conceal(sh.tick, k, c.hold, c.step) : (int)TLB_ERR_HIP; },
+                              [](Shard &sh, int k, const tlb_node::Conceal &c) {
+                                  return sh.tick ? (c.any_feed ? tlb_tick_enable_feed_loss : tlb_tick_enable_conceal)(sh.tick, k, c.hold, c.step) : (int)TLB_ERR_HIP;
+                              },
                               [&](int) { return v; });
 }
+int tlb_node_enable_conceal(tlb_node *nd, int stream, int hold, int step) { return node_enable_conceal(nd, stream, hold, step, false); }
+int tlb_node_enable_feed_loss(tlb_node *nd, int stream, int hold, int step) { return node_enable_conceal(nd, stream, hold, step, true); }
 const tlb_conceal_record *tlb_node_conceal(const tlb_node *nd, int stream) { return slot<READ, tlb_tick_conceal>(nd, stream); }
 int tlb_node_conceal_reset(tlb_node *nd, int stream)
 {
@@ -843,7 +853,10 @@ int tlb_node_set_down_feed(tlb_node *nd, int stream, const tlb_feed_config *cfg)
         for (int i = s0; i < s1; i++) if (!tlb_down_pair(cfg->samplerate, nd->cfgs[(size_t)i].samplerate)) return TLB_ERR_SAMPLERATE;      // (the legal pairs are the decimator's three)
     }
     const NodeInput v = node_feed(cfg, false);
-    return node_set_input(nd, TLB_IN_DOWN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
+    const int rc = node_set_input(nd, TLB_IN_DOWN_FEED, stream, cfg != nullptr, v, [&](int) { return v; });
+    for (int i = s0; i < s1 && !rc && !nd->kept_conceal.empty(); i++)                // (a stream's new down feed, or none, starts without concealment)
+        if (nd->kept[TLB_IN_FEED].empty() || !nd->kept[TLB_IN_FEED][(size_t)i].samplerate) nd->kept_conceal[(size_t)i] = tlb_node::Conceal{};
+    return rc;
 }
 // the feed frames wanted in the stream's two slots of its shard's current input set (TICK plane; broken and late shards answer as tlb_node_need does)
 int tlb_node_down_feed_want(const tlb_node *nd, int stream)

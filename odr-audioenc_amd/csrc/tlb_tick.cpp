@@ -454,7 +454,8 @@ int tlb_tick_limiter_reset(tlb_tick *t, int stream) { return tick_meter_reset(t,
 // The feed concealment (tlb_conceal_*): per stream, while no tick is in flight.  Every named stream is checked before one is changed; the first
 // call that switches concealment on makes the record option's buffers.  The kernels are the feed launch's own business (feed_launch); every
 // submit then copies the batches' records into the groups' behind it.  An object that never makes the call allocates and queues nothing new.
-int tlb_tick_enable_conceal(tlb_tick *t, int stream, int hold, int step)
+// any_feed (tlb_tick_enable_feed_loss): an adapted or a down feed will do, and the batches are asked through tlb_feed_loss_enable
+static int tick_enable_conceal(tlb_tick *t, int stream, int hold, int step, bool any_feed)
 {
     if (!t || t->finished || stream < -1 || stream >= t->nstreams || t->ticks != t->waited) return TLB_ERR_ARG;
     if (hold < 0 || hold > TLB_CONCEAL_MAX_HOLD || (hold > 0 && (step < 1 || step > TLB_CONCEAL_MAX_STEP))) return TLB_ERR_ARG;
@@ -464,12 +465,17 @@ int tlb_tick_enable_conceal(tlb_tick *t, int stream, int hold, int step)
     if (hold > 0)
         if (int rc = t->blocks.visit_range(s0, s1, [&](int g, int l0, int l1) {
                 const tlb_batch *b = t->groups[(size_t)g].b;
-                for (int k = l0; k < l1; k++) if (tlb_feed_get(b, k, nullptr) <= 0 || tlb_feed_adapted(b, k) != 0) return (int)TLB_ERR_ARG;
+                for (int k = l0; k < l1; k++) {
+                    const bool strict = tlb_feed_get(b, k, nullptr) > 0 && tlb_feed_adapted(b, k) == 0;
+                    if (!strict && !(any_feed && (tlb_feed_get(b, k, nullptr) > 0 || tlb_feed_down_get(b, k, nullptr) > 0))) return (int)TLB_ERR_ARG;
+                }
                 return (int)TLB_OK;
             })) return rc;
     if (!t->rec[REC_CONCEAL].on) if (int rc = tick_record_enable(t, REC_CONCEAL, [](TlbMem &, TickGroup &) { return 0; })) return rc;
-    return t->blocks.visit(stream, [&](int g, int k) { return tlb_conceal_enable(t->groups[(size_t)g].b, k, hold, step); });
+    return t->blocks.visit(stream, [&](int g, int k) { return (any_feed ? tlb_feed_loss_enable : tlb_conceal_enable)(t->groups[(size_t)g].b, k, hold, step); });
 }
+int tlb_tick_enable_conceal(tlb_tick *t, int stream, int hold, int step) { return tick_enable_conceal(t, stream, hold, step, false); }
+int tlb_tick_enable_feed_loss(tlb_tick *t, int stream, int hold, int step) { return tick_enable_conceal(t, stream, hold, step, true); }
 const tlb_conceal_record *tlb_tick_conceal(const tlb_tick *t) { return (const tlb_conceal_record *)tick_record(t, REC_CONCEAL); }
 int tlb_tick_conceal_reset(tlb_tick *t, int stream) { return tick_meter_reset(t, REC_CONCEAL, stream); }
 int tlb_tick_monitor_listen(tlb_tick *t, int stream)

@@ -56,15 +56,17 @@ __global__ void __launch_bounds__(64 * TL_FA_WAVES) tl_feed_adapt_carry_kernel(T
     if (s < A.F.nstreams) tl_fa_carry(A, s);
 }
 
-hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A)
+hipError_t tlk_feed_adapt(hipStream_t st, const TlFeedAdaptLaunch &A, const TlConcealConv *cc)
 {
     const long long units = (long long)A.F.nstreams * A.F.nframes;
     hipLaunchKernelGGL(tl_feed_adapt_decode_kernel, dim3((unsigned)((units + TL_FA_WAVES - 1) / TL_FA_WAVES)), dim3(64 * TL_FA_WAVES), 0, st, A);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (cc && (e = tlk_conceal_adapt(st, TlConcealAdaptLaunch{A, *cc})) != hipSuccess) return e;      // the lost slots' rows, before the resampler reads the plane
     hipLaunchKernelGGL(tl_feed_adapt_resample_kernel, dim3((unsigned)units), dim3(64 * TL_RS_WAVES), 0, st, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tl_feed_adapt_carry_kernel, dim3((unsigned)((A.F.nstreams + TL_FA_WAVES - 1) / TL_FA_WAVES)), dim3(64 * TL_FA_WAVES), 0, st, A);
-    return hipGetLastError();
+    e = hipGetLastError();
+    return cc && e == hipSuccess ? tlk_conceal_adapt_carry(st, TlConcealAdaptLaunch{A, *cc}) : e;
 }

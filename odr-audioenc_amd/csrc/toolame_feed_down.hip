@@ -56,15 +56,17 @@ __global__ void __launch_bounds__(64 * TL_FD_WAVES) tl_feed_down_carry_kernel(Tl
     if (s < A.F.nstreams) tl_fd_carry(A, s);
 }
 
-hipError_t tlk_feed_down(hipStream_t st, const TlFeedDownLaunch &A)
+hipError_t tlk_feed_down(hipStream_t st, const TlFeedDownLaunch &A, const TlConcealConv *cc)
 {
     const long long units = (long long)A.F.nstreams * A.F.nframes;
     hipLaunchKernelGGL(tl_feed_down_decode_kernel, dim3((unsigned)((2 * units + TL_FD_WAVES - 1) / TL_FD_WAVES)), dim3(64 * TL_FD_WAVES), 0, st, A);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (cc && (e = tlk_conceal_down(st, TlConcealDownLaunch{A, *cc})) != hipSuccess) return e;        // the lost slots' rows, before the decimator reads the plane
     hipLaunchKernelGGL(tl_feed_down_decimate_kernel, dim3((unsigned)units), dim3(64 * TL_DC_WAVES), 0, st, A);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tl_feed_down_carry_kernel, dim3((unsigned)((A.F.nstreams + TL_FD_WAVES - 1) / TL_FD_WAVES)), dim3(64 * TL_FD_WAVES), 0, st, A);
-    return hipGetLastError();
+    e = hipGetLastError();
+    return cc && e == hipSuccess ? tlk_conceal_down_carry(st, TlConcealDownLaunch{A, *cc}) : e;
 }

@@ -350,6 +350,9 @@ def _bind(L):
         L.tlb_node_conceal.restype = C.c_void_p
         L.tlb_node_conceal.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_conceal_reset.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_feed_loss_enable"):     # ... on adapted and down feeds
+        for name in ("tlb_feed_loss_enable", "tlb_tick_enable_feed_loss", "tlb_node_enable_feed_loss"):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "tlb_decimate_device"):         # device decimator (down sources)
         L.tlb_decimate_set_source.argtypes = [C.c_void_p, C.c_int, C.c_long]
         L.tlb_decimate_source.restype = C.c_long
@@ -895,12 +898,14 @@ class Tick:
             raise ToolameError(rc, "tlb_tick_truepeak_reset")
 
     # -- feed concealment (tlb_conceal_* of the groups' batches): per stream, while no tick is in flight --
-    def enable_conceal(self, hold=4, step=3, stream=-1):
+    def enable_conceal(self, hold=4, step=3, stream=-1, any_feed=False):
         """a lost feed frame repeats the last good one, `step` scalefactor-index units (3: 6 dB) quieter per lost frame, for `hold` frames,
-        then rings out; hold 0 switches it off.  stream -1: every stream (each needs a strict feed)"""
-        rc = self.L.tlb_tick_enable_conceal(self.h, int(stream), int(hold), int(step))
+        then rings out; hold 0 switches it off.  stream -1: every stream (each needs a strict feed; any_feed: a feed of any kind, adapted
+        and down feeds included: tlb_tick_enable_feed_loss)"""
+        name = "tlb_tick_enable_feed_loss" if any_feed else "tlb_tick_enable_conceal"
+        rc = getattr(self.L, name)(self.h, int(stream), int(hold), int(step))
         if rc:
-            raise ToolameError(rc, "tlb_tick_enable_conceal")
+            raise ToolameError(rc, name)
 
     def conceal(self):
         """CONCEAL_DTYPE [nstreams] of the tick waited for last (a view of the object's pinned memory); None when never enabled"""
@@ -1267,12 +1272,15 @@ class Batch:
             raise ToolameError(rc, "tlb_feed_device")
 
     # -- feed concealment (tlb_conceal_*): a lost frame of a strict feed is the last good one once more, quieter, and not silence --
-    def enable_conceal(self, hold=4, step=3, stream=-1):
+    def enable_conceal(self, hold=4, step=3, stream=-1, any_feed=False):
         """hold 1..16 frames, step 1..21 scalefactor-index units per lost frame (3: 6 dB); hold 0 switches it off.  stream -1: every stream,
-        each of which needs a strict feed (checked before anything changes).  feed() then conceals by itself."""
-        rc = self.L.tlb_conceal_enable(self.h, int(stream), int(hold), int(step))
+        each of which needs a strict feed (checked before anything changes).  feed() then conceals by itself.  any_feed: a feed of any
+        kind will do (tlb_feed_loss_enable): an adapted or a down feed's lost WANTED slots are concealed ahead of the resampler or
+        decimator, by feed() and down_feed() themselves."""
+        name = "tlb_feed_loss_enable" if any_feed else "tlb_conceal_enable"
+        rc = getattr(self.L, name)(self.h, int(stream), int(hold), int(step))
         if rc:
-            raise ToolameError(rc, "tlb_conceal_enable")
+            raise ToolameError(rc, name)
 
     def conceal_cfg(self, s):
         """(hold, step) of stream s, None when its concealment is off"""
@@ -2068,8 +2076,9 @@ class Node:
         self._rc(self.L.tlb_node_truepeak_reset(self.h, int(s)), "tlb_node_truepeak_reset")
 
     # feed concealment (Tick.enable_conceal, per stream with node-wide indices; between steps)
-    def enable_conceal(self, hold=4, step=3, stream=-1):
-        self._rc(self.L.tlb_node_enable_conceal(self.h, int(stream), int(hold), int(step)), "tlb_node_enable_conceal")
+    def enable_conceal(self, hold=4, step=3, stream=-1, any_feed=False):
+        name = "tlb_node_enable_feed_loss" if any_feed else "tlb_node_enable_conceal"
+        self._rc(getattr(self.L, name)(self.h, int(stream), int(hold), int(step)), name)
 
     def conceal(self, s):
         """the stream's record (a CONCEAL_DTYPE scalar, copied) of the step waited for last; None when never enabled and for a broken, late or stale shard"""

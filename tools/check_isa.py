@@ -55,6 +55,9 @@ LIMITS = [
     # feed concealment (csrc/toolame_conceal.hip): the feed kernel's two parses and its synthesis behind one ballot over the reports; same occupancy
     (re.compile(r"tl_conceal_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
     (re.compile(r"tl_conceal_carry_kernel"), dict(vgpr=128, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # ... on adapted and down feeds (csrc/toolame_conceal_conv.hip): the same unit behind two masks over the positions; same occupancy
+    (re.compile(r"tl_conceal_(adapt|down)_kernel"), dict(vgpr=168, lds=163840 // 3, vgpr_spill=0, scratch=0, pairs2_frac=0.0)),
+    (re.compile(r"tl_conceal_(adapt|down)_carry_kernel"), dict(vgpr=128, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # loudness meter (csrc/toolame_loudness.hip): a lane per (stream, channel) with the filter state and a chunk of PCM ahead in registers; 64 rows of 144 bytes in LDS
     (re.compile(r"tl_loudness_kernel"), dict(vgpr=168, lds=9216, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     (re.compile(r"tl_loudness_programme_kernel"), dict(vgpr=168, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
