@@ -7,7 +7,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/editick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o editick
 // usage: editick in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m s|j|d|m] [-p psy] [-g gain_dB] [-n streams] [-t now_s]
-//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
+//                [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--lra] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]]
 //                [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]
 //   --feed FILE.mp2 --feed-bitrate K: the services' source is an MPEG Layer II file at the encoder's rate (-r) and channel count (-c) and
 //   at K kbps, decoded on the device ahead of the ingest (tlb_tick_set_feed): the file is cut into frames by the arithmetic length and each
@@ -39,6 +39,8 @@
 //   --loudness: the loudness meter (tlb_tick_enable_loudness): the PCM the encoder is given (after -g) is measured on the device after
 //   ITU-R BS.1770-4 / EBU R 128.  One line per stream at the end: momentary (400 ms), short-term (3 s) and integrated loudness in LUFS
 //   (-inf where there is none yet), as "%.2f".
+//   --lra: the loudness range on top of it (tlb_tick_enable_lra; implies --loudness): EBU Tech 3342's LRA from the short-term values.  One
+//   more line per stream behind the loudness line: LRA in LU as "%.1f", the 10th and the 95th percentile in LUFS, gated of counted blocks.
 //   --truepeak [DBTP]: the true-peak meter (tlb_tick_enable_truepeak): the same PCM oversampled four times on the device after ITU-R
 //   BS.1770-4 Annex 2, against a ceiling of DBTP (default -1, EBU R 128's).  One line per stream at the end: the maximum true peak in
 //   dBTP, the largest sample in dBFS and the number of frames over the ceiling.
@@ -67,12 +69,12 @@ static void die(const char *what, int code)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]] [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le out.af [-r rate] [-c channels] [-b kbps] [-m mode] [-p psy] [-g gain_dB] [-n streams] [-t now_s] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--lra] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]] [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]\n", argv[0]);
         return 2;
     }
     long rate = 48000, source_rate = 0;
     long long now_s = 1700000000;
-    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0, limit = 0, limit_release = 0;
+    int channels = 2, kbps = 128, psy = 1, nstreams = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, lra = 0, truepeak = 0, limit = 0, limit_release = 0;
     double ceiling_db = -1.0, limit_db = -1.0;
     char mode = 0;
     double gain_db = 0.0;
@@ -84,6 +86,7 @@ int main(int argc, char **argv)
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
         if (k == "--loudness") { loudness = 1; i--; continue; }
+        if (k == "--lra") { loudness = lra = 1; i--; continue; }
         if (k == "--truepeak") {                                 // its value is optional: taken when the next argument is a number
             truepeak = 1;
             char *end = nullptr;
@@ -181,6 +184,7 @@ int main(int argc, char **argv)
     if (short_every) if (int rc = tlb_tick_enable_short_reads(t)) die("tlb_tick_enable_short_reads", rc);     // before the first submit
     if (monitor) if (int rc = tlb_tick_enable_monitor(t, monitor)) die("tlb_tick_enable_monitor", rc);           // likewise
     if (loudness) if (int rc = tlb_tick_enable_loudness(t)) die("tlb_tick_enable_loudness", rc);                 // likewise
+    if (lra) if (int rc = tlb_tick_enable_lra(t)) die("tlb_tick_enable_lra", rc);                                // ... behind loudness
     const uint32_t ceiling = (uint32_t)std::llround(1073741824.0 * std::pow(10.0, ceiling_db / 20.0));             // in units of 2^-30 of full scale
     if (truepeak) if (int rc = tlb_tick_enable_truepeak(t, ceiling)) die("tlb_tick_enable_truepeak", rc);        // likewise
     const tlb_limiter_params lparams = {(uint32_t)std::llround(1073741824.0 * std::pow(10.0, limit_db / 20.0)), (uint32_t)limit_release};      // release 0: the default
@@ -316,6 +320,13 @@ int main(int argc, char **argv)
         for (int s = 0; s < nstreams; s++)
             std::fprintf(stderr, "editick: loudness: stream %d: momentary %.2f LUFS, short-term %.2f LUFS, integrated %.2f LUFS (%u of %u blocks)\n", s,
                          tlb_loudness_lufs(r[s].momentary), tlb_loudness_lufs(r[s].short_term), tlb_loudness_lufs(prog[(size_t)s].integrated), prog[(size_t)s].gated, r[s].blocks);
+    }
+    if (lra && frames > 0) {                                     // the range of everything measured, on request like the gated value
+        std::vector<tlb_lra_record> range((size_t)nstreams);
+        if (int rc = tlb_tick_lra(t, range.data())) die("tlb_tick_lra", rc);
+        for (int s = 0; s < nstreams; s++)
+            std::fprintf(stderr, "editick: lra: stream %d: LRA %.1f LU, low %.2f LUFS, high %.2f LUFS (%u of %u blocks)\n", s, tlb_lra_lu(&range[(size_t)s]),
+                         tlb_loudness_lufs(range[(size_t)s].low), tlb_loudness_lufs(range[(size_t)s].high), range[(size_t)s].gated, range[(size_t)s].blocks);
     }
     if (truepeak && frames > 0) {                                // the records of the last tick (the finish adds nothing)
         const tlb_truepeak_record *r = tlb_tick_truepeak(t);

@@ -11,7 +11,7 @@
 //
 // build: g++ -O2 -std=c++17 examples/nodetick.cpp -Iinclude -Lodr-audioenc_amd -ltoolame_dab_hip -Wl,-rpath,$PWD/odr-audioenc_amd -o nodetick
 // usage: nodetick in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D]
-//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R]
+//                 [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--lra] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R]
 //   in.s16le: interleaved stereo at the services' rate (-r: 48000, the default, or 24000); stream s starts reading at frame s (so the
 //   services differ), wrapping around.
 //   -d: HIP device of each shard (default 0,1,...,G-1 modulo the device count; "0,0" = two shards on one GPU).
@@ -41,6 +41,8 @@
 //   the service's wide slot (tlb_node_down) and are filtered and decimated on the GPUs.
 //   --loudness: the loudness meter (tlb_node_enable_loudness): the PCM every encoder is given is measured on its GPU after ITU-R BS.1770-4 /
 //   EBU R 128.  One line per service at the end: momentary, short-term and integrated loudness in LUFS (-inf where there is none yet).
+//   --lra: the loudness range on top of it (tlb_node_enable_lra; implies --loudness): EBU Tech 3342's LRA from the short-term values.  One
+//   more line per service behind the loudness lines: LRA in LU, the 10th and the 95th percentile in LUFS, gated of counted blocks.
 //   --truepeak [DBTP]: the true-peak meter (tlb_node_enable_truepeak): the same PCM oversampled four times on its GPU after ITU-R BS.1770-4
 //   Annex 2, against a ceiling of DBTP (default -1, EBU R 128's).  One line per service at the end: the maximum true peak in dBTP, the
 //   largest sample in dBFS and the number of frames over the ceiling.
@@ -163,10 +165,10 @@ static void ship(void *vctx, int g, int first, int n)
 int main(int argc, char **argv)
 {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]] [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s in.s16le [-n streams] [-G shards] [-d dev,dev,...] [-k ticks] [-r rate] [-b kbps] [-p psy] [-o out.af] [--deadline-ms D] [--short-every N --short-by M] [--monitor check|audio] [--compare] [--loudness] [--lra] [--truepeak [DBTP]] [--limit [DBTP] --limit-release MS] [--source-rate R] [--feed FILE.mp2 --feed-bitrate K [--feed-rate R] [--feed-channels C]] [--conceal [HOLD] --conceal-step N] [--feed-drop-every N --feed-drop-run M]\n", argv[0]);
         return 2;
     }
-    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, truepeak = 0, limit = 0, limit_release = 0;
+    int nstreams = 64, G = 0, ticks = 50, kbps = 128, psy = 1, short_every = 0, short_by = 0, monitor = 0, compare = 0, loudness = 0, lra = 0, truepeak = 0, limit = 0, limit_release = 0;
     double ceiling_db = -1.0, limit_db = -1.0;
     long rate = 48000;
     double deadline_ms = 0;
@@ -179,6 +181,7 @@ int main(int argc, char **argv)
         const std::string k = argv[i];
         if (k == "--compare") { compare = 1; i--; continue; }    // the two options without a value
         if (k == "--loudness") { loudness = 1; i--; continue; }
+        if (k == "--lra") { loudness = lra = 1; i--; continue; }
         if (k == "--truepeak") {                                 // its value is optional: taken when the next argument is a number
             truepeak = 1;
             char *end = nullptr;
@@ -302,6 +305,8 @@ int main(int argc, char **argv)
         if (int rc = tlb_node_enable_short_reads(nd)) die("tlb_node_enable_short_reads", rc);      // before the first submit
     if (loudness)
         if (int rc = tlb_node_enable_loudness(nd)) die("tlb_node_enable_loudness", rc);                 // likewise; a restarted shard measures again from zero
+    if (lra)
+        if (int rc = tlb_node_enable_lra(nd)) die("tlb_node_enable_lra", rc);                           // ... behind loudness
     const uint32_t ceiling = (uint32_t)std::llround(1073741824.0 * std::pow(10.0, ceiling_db / 20.0));    // in units of 2^-30 of full scale
     if (truepeak)
         if (int rc = tlb_node_enable_truepeak(nd, ceiling)) die("tlb_node_enable_truepeak", rc);        // likewise, with the same ceiling
@@ -458,6 +463,13 @@ int main(int argc, char **argv)
             if (const tlb_loudness_record *r = tlb_node_loudness(nd, s))  // (NULL: its shard is down or late)
                 std::fprintf(stderr, "nodetick: loudness: service %d: momentary %.2f LUFS, short-term %.2f LUFS, integrated %.2f LUFS (%u of %u blocks)\n", s,
                              tlb_loudness_lufs(r->momentary), tlb_loudness_lufs(r->short_term), tlb_loudness_lufs(prog[(size_t)s].integrated), prog[(size_t)s].gated, r->blocks);
+    }
+    if (lra) {                                                            // the range of everything measured, between steps (all zero: its shard is down or late)
+        std::vector<tlb_lra_record> range((size_t)nstreams);
+        if (int rc = tlb_node_lra(nd, range.data())) std::fprintf(stderr, "nodetick: tlb_node_lra (code %d)\n", rc);
+        for (int s = 0; s < nstreams; s++)
+            std::fprintf(stderr, "nodetick: lra: service %d: LRA %.1f LU, low %.2f LUFS, high %.2f LUFS (%u of %u blocks)\n", s, tlb_lra_lu(&range[(size_t)s]),
+                         tlb_loudness_lufs(range[(size_t)s].low), tlb_loudness_lufs(range[(size_t)s].high), range[(size_t)s].gated, range[(size_t)s].blocks);
     }
     if (truepeak)                                                         // the records of the last step
         for (int s = 0; s < nstreams; s++)

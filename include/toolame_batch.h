@@ -1195,7 +1195,7 @@ const tlb_frame_report *tlb_node_down_feed_report(const tlb_node *nd, int stream
  * record and answers NULL for a broken, late or stale shard; tlb_node_loudness_programme(nd, out [nstreams]) fills the blocks of the live
  * shards between steps (all zero for the others); tlb_node_loudness_reset routes like the stream life-cycle calls (TLB_ERR_HIP for a stream
  * of a broken shard, TLB_ERR_LATE for one of a late shard), -1 goes to every live shard.
- * NOT BUILT: loudness range (LRA), loudness of the decoded output (the monitors own that side).  Acting on the gain: the caller's loop with
+ * NOT BUILT: loudness of the decoded output (the monitors own that side; loudness range is tlb_lra_* below).  Acting on the gain: the caller's loop with
  * tlb_set_gain_db, and the true-peak limiter below (tlb_limiter_*) as the net under it.
  * ------------------------------------------------------------------------------------------ */
 #define TLB_LOUDNESS_BINS 751
@@ -1219,6 +1219,54 @@ int tlb_node_enable_loudness(tlb_node *nd);
 const tlb_loudness_record *tlb_node_loudness(const tlb_node *nd, int stream);
 int tlb_node_loudness_programme(tlb_node *nd, tlb_loudness_programme_record *out);
 int tlb_node_loudness_reset(tlb_node *nd, int stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Loudness range (LRA) after EBU Tech 3342: how far apart the quiet and the loud passages of a programme lie, from the distribution of the
+ * SHORT-TERM values the loudness meter above forms.  With it the meter is an "EBU Mode" meter (EBU Tech 3341 section 2); it tells whether
+ * a programme can be brought to target by a static gain (tlb_set_gain_db) or needs dynamics first.  Opt-in ON TOP of tlb_loudness_enable.
+ * THE ARITHMETIC.  The reference has no such meter, so this is the definition (tests/lralib.py restates it in Python ints and numpy
+ * float64, every comparison against it is bit for bit).
+ *   range block every short-term value st the loudness meter forms is one range block: one per closed bin from bin 30 on, so 10 per
+ *               second with 2.9 s of overlap (Tech 3342 asks for at least 2 s).  A block counts iff st > e_0, in the bin
+ *               #{k in 1..750: st >= e_k} of a SECOND set of 751 uint32 counts per stream; edges e and centres c are the loudness
+ *               meter's (tlb_loudness_scale)
+ *   range       over the bins in ascending j: N = sum n_j, S = sum (double)n_j * c_j; gate = 0.01 * (S / N), one division and one
+ *               multiplication by the literal, each rounded: -20 LU relative to the absolute-gated mean.  The distribution is the bins
+ *               with c_j >= gate, N2 their total.  Nearest ranks in 64-bit integers: r_lo = (N2 + 4) / 10 and
+ *               r_hi = (19 (N2 - 1) + 10) / 20, which are floor((N2 - 1) * 0.10 + 0.5) and floor((N2 - 1) * 0.95 + 0.5).  low_bin is the
+ *               first gated bin whose cumulative count over the gated bins exceeds r_lo, high_bin likewise for r_hi; low = c[low_bin],
+ *               high = c[high_bin]; LRA = 0.1 * (high_bin - low_bin) LU, an integer number of tenths because the centres are 0.1 LU
+ *               apart.  Everything is 0 when N == 0.  The 0.1 LU quantisation is part of the definition: each percentile is at most
+ *               0.05 LU off, and Tech 3342's tolerance is +-1 LU
+ * RECORD.  tlb_lra_record, 40 bytes, little-endian, no padding: low, high, gate are energies (LUFS = tlb_loudness_lufs), blocks = N,
+ * gated = N2, then the two bins.  tlb_lra_lu(rec) = 0.1 * (high_bin - low_bin) on the host, 0 for NULL.
+ * STATE.  3008 bytes of device memory per stream (the second histogram) and the scratch of tlb_lra_host, allocated by tlb_lra_enable ALONE: a
+ * batch that never enables it allocates and queues nothing new, and runs the kernels it always ran.
+ *   tlb_lra_enable(b)                 after tlb_loudness_enable (TLB_ERR_ARG before it); allocates the counts (waits for the device
+ *                                     once); a second call answers 0.  From this call on tlb_loudness_device / _host of the batch launch
+ *                                     the counting twin of their kernel INSTEAD of it: their records and the programme histogram are bit for
+ *                                     bit what they are without the range
+ *   tlb_lra_device(b, d_out, stream)  tlb_lra_record [nstreams] from the counts so far, on hip_stream; d_out 8-byte aligned
+ *   tlb_lra_host(b, out)              the same with a host buffer
+ * There is no reset of its own: EBU Mode has one reset.  tlb_loudness_reset, tlb_stream_reset and tlb_stream_reconfigure zero the stream's
+ * range counts with the rest of its loudness state; tlb_stream_finish leaves them.
+ * TICK PLANE.  tlb_tick_enable_lra(t) after tlb_tick_enable_loudness and before the first submit (TLB_ERR_ARG otherwise; a second call
+ * answers 0).  The tick's per-submit queue is unchanged: the meter's one launch is the other kernel.  tlb_tick_lra(t, out [nstreams]) is
+ * legal with no tick in flight, like tlb_tick_loudness_programme.
+ * NODE LEVEL, TICK plane only (a BATCH node: TLB_ERR_ARG): tlb_node_enable_lra after tlb_node_enable_loudness goes to every shard before
+ * the first submit, and a shard made by tlb_node_shard_restart is enabled again -- its counts start from zero.  tlb_node_lra(nd, out
+ * [nstreams]) fills the blocks of the live shards between steps (all zero for the others).
+ * NOT BUILT: the range of the decoded output, a 1 Hz block rate.  Acting on the range stays the caller's policy.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { double low, high, gate; uint32_t blocks, gated; int32_t low_bin, high_bin; } tlb_lra_record;      /* 40 bytes */
+int tlb_lra_enable(tlb_batch *b);
+int tlb_lra_device(tlb_batch *b, tlb_lra_record *d_out, void *hip_stream);
+int tlb_lra_host(tlb_batch *b, tlb_lra_record *out);
+double tlb_lra_lu(const tlb_lra_record *rec);
+int tlb_tick_enable_lra(tlb_tick *t);
+int tlb_tick_lra(tlb_tick *t, tlb_lra_record *out);
+int tlb_node_enable_lra(tlb_node *nd);
+int tlb_node_lra(tlb_node *nd, tlb_lra_record *out);
 
 /* ---------------------------------------------------------------------------------------------
  * Maximum true peak: the largest value the signal reaches BETWEEN its samples, after ITU-R BS.1770-4 Annex 2, of the PCM the encoder is
@@ -1269,7 +1317,7 @@ int tlb_node_loudness_reset(tlb_node *nd, int stream);
  * shard made by tlb_node_shard_restart is enabled again with the same ceiling -- its records start from zero.  tlb_node_truepeak(nd, stream)
  * points at the STREAM's record and answers NULL for a broken, late or stale shard; tlb_node_truepeak_reset routes like
  * tlb_node_loudness_reset.
- * NOT BUILT: loudness range (LRA), true peak of the decoded output.  Acting on the gain: the true-peak limiter below (tlb_limiter_*).
+ * NOT BUILT: true peak of the decoded output.  Acting on the gain: the true-peak limiter below (tlb_limiter_*).
  * ------------------------------------------------------------------------------------------ */
 #define TLB_TRUEPEAK_TAPS 12
 #define TLB_TRUEPEAK_CEILING_DEFAULT 956973408u

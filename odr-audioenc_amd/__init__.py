@@ -17,6 +17,7 @@ from .toolame import (  # noqa: F401
     COMPARE_JUDGED0, COMPARE_JUDGED1, COMPARE_MISMATCH, COMPARE_SWAPPED, COMPARE_SKIPPED,
     resample_need_at, resample_taps, decimate_need_at, decimate_taps, DECIMATE_SLOT, FeedConfig, feed_check_config, feed_frame_bytes, feed_want_at, down_feed_want_at, DEC_UNWANTED,
     LOUDNESS_DTYPE, LOUDNESS_PROGRAMME_DTYPE, LOUDNESS_BINS, loudness_lufs, loudness_taps, loudness_scale,
+    LRA_DTYPE, lra_lu,
     TRUEPEAK_DTYPE, TRUEPEAK_TAPS, TRUEPEAK_CEILING_DEFAULT, truepeak_dbtp, truepeak_taps,
     LIMITER_DTYPE, LIMITER_DELAY, limiter_step,
     CONCEAL_DTYPE, CONCEAL_MUTE,

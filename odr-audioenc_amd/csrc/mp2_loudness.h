@@ -32,6 +32,11 @@
 //   rec    TlLoudnessRecord [nstreams]             the record as it is reported
 //   hist   uint32 [TL_LD_HIST_ROWS][nstreams]      751 counts and a row of padding: neighbouring streams' words lie together, here and in
 //                                                  tl_loudness_programme
+// Loudness range (tlb_lra_*).  Every short-term value st is also a RANGE BLOCK: counted iff st > e_0, in bin #{k in 1..750: st >= e_k} of a
+// second histogram, by the counting instantiation of the wave's body (tl_lra_wave; tl_loudness_wave is the other and the text it always
+// was).  tl_lra_range turns a stream's counts into its record: gate 0.01 * (S / N), nearest ranks over the gated bins.  Device memory,
+// allocated by tlb_lra_enable alone (3008 bytes per stream):
+//   hist_st uint32 [TL_LD_HIST_ROWS][nstreams]     laid out like hist; handed to the kernel beside TlLoudnessArgs (TlLraArgs), not inside it
 #pragma once
 #include <stdint.h>
 #include "mp2_types.h"
@@ -69,6 +74,14 @@ struct TlLoudnessArgs {
     int nstreams, nframes;
 };
 
+// Loudness range (tlb_lra_*): the meter's arguments as they are and the second histogram beside them, so that tl_loudness_kernel's
+// argument block does not change
+struct TlLraRecord { double low, high, gate; uint32_t blocks, gated; int32_t low_bin, high_bin; };                                  // tlb_lra_record
+struct TlLraArgs {
+    TlLoudnessArgs A;
+    uint32_t *hist_st;                // [TL_LD_HIST_ROWS][nstreams] range blocks per 0.1 LU, laid out like hist
+};
+
 #ifdef TL_FN                          // behind mp2_wave.h only: the host translation units take the constants and records above and nothing else
 struct alignas(16) TlLoudnessLds { int16_t x[64 * TL_LD_PITCH]; };   // 9216 bytes per wave
 
@@ -88,8 +101,9 @@ TL_FN int tl_ld_bin_of(const double *TL_RESTRICT edges, double m)
     return lo;
 }
 
-// The wave of streams [32 wv, 32 wv + 32) over the call's frames.
-TL_FN void tl_loudness_wave(const TlLoudnessArgs &A, TlLoudnessLds &w, int wv)
+// The wave of streams [32 wv, 32 wv + 32) over the call's frames.  RANGE: every short-term value is also a range block of the loudness
+// range (tlb_lra_*), counted in hist_st; without it hist_st is not looked at and the text is tl_loudness_wave's as it always was.
+template <bool RANGE> TL_FN void tl_loudness_wave_t(const TlLoudnessArgs &A, uint32_t *hist_st, TlLoudnessLds &w, int wv)
 {
     const int ns = A.nstreams, s0 = wv * TL_LD_STREAMS, total = A.nframes * TL_LD_CHUNKS;
     const size_t lanes = 2 * (size_t)ns;
@@ -197,6 +211,10 @@ TL_FN void tl_loudness_wave(const TlLoudnessArgs &A, TlLoudnessLds &w, int wv)
                     const double st = sum / 30.0;
                     R->short_term = st;
                     if (st > R->short_term_max) R->short_term_max = st;
+                    if (RANGE && st > edges[0]) {
+                        uint32_t *h = hist_st + (size_t)tl_ld_bin_of(edges, st) * (size_t)ns + (size_t)s;
+                        *h = *h + 1u;
+                    }
                 }
             }
             L(closed) = 0;
@@ -219,6 +237,8 @@ TL_FN void tl_loudness_wave(const TlLoudnessArgs &A, TlLoudnessLds &w, int wv)
         }
     TL_LANES_END
 }
+TL_FN void tl_loudness_wave(const TlLoudnessArgs &A, TlLoudnessLds &w, int wv) { tl_loudness_wave_t<false>(A, nullptr, w, wv); }
+TL_FN void tl_lra_wave(const TlLraArgs &X, TlLoudnessLds &w, int wv) { tl_loudness_wave_t<true>(X.A, X.hist_st, w, wv); }
 
 // Programme loudness of stream s from its counts: the two ascending passes.  centres: the table's third part.
 TL_FN void tl_loudness_programme(const uint32_t *TL_RESTRICT hist, const double *TL_RESTRICT centres, TlLoudnessProgramme *TL_RESTRICT out, int s, int nstreams)
@@ -243,6 +263,42 @@ TL_FN void tl_loudness_programme(const uint32_t *TL_RESTRICT hist, const double 
         }
         P.integrated = S2 / (double)N2;
         P.gated = N2;
+    }
+    out[s] = P;
+}
+
+// Loudness range of stream s from its range-block counts (include/toolame_batch.h, "Loudness range"): the gate 20 LU below the mean of
+// the counted blocks, then the nearest ranks of the 10th and the 95th percentile among the bins at or above it, in one ascending walk.
+TL_FN void tl_lra_range(const uint32_t *TL_RESTRICT hist, const double *TL_RESTRICT centres, TlLraRecord *TL_RESTRICT out, int s, int nstreams)
+{
+    uint32_t N = 0u;
+    double S = 0.0;
+#pragma nounroll
+    for (int j = 0; j < TL_LD_BINS; j++) {
+        const uint32_t n = hist[(size_t)j * (size_t)nstreams + (size_t)s];
+        N += n; S = S + ((double)n * centres[j]);
+    }
+    TlLraRecord P = {0.0, 0.0, 0.0, 0u, 0u, 0, 0};
+    if (N) {
+        P.gate = 0.01 * (S / (double)N);
+        P.blocks = N;
+        uint32_t N2 = 0u;
+#pragma nounroll
+        for (int j = 0; j < TL_LD_BINS; j++)
+            if (centres[j] >= P.gate) N2 += hist[(size_t)j * (size_t)nstreams + (size_t)s];
+        P.gated = N2;
+        const uint64_t r_lo = ((uint64_t)N2 + 4u) / 10u, r_hi = (19u * ((uint64_t)N2 - 1u) + 10u) / 20u;
+        uint64_t cum = 0u;
+        int lo = -1, hi = -1;
+#pragma nounroll
+        for (int j = 0; j < TL_LD_BINS && hi < 0; j++) {
+            if (!(centres[j] >= P.gate)) continue;
+            cum += hist[(size_t)j * (size_t)nstreams + (size_t)s];
+            if (lo < 0 && cum > r_lo) lo = j;
+            if (cum > r_hi) hi = j;
+        }
+        P.low_bin = lo; P.high_bin = hi;
+        P.low = centres[lo]; P.high = centres[hi];
     }
     out[s] = P;
 }

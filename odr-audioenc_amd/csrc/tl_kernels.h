@@ -87,6 +87,9 @@ hipError_t tlk_decimate(unsigned blocks, hipStream_t st, const int16_t *wide, in
 // tl_loudness_programme_kernel, one lane per stream (tables: the whole table, the kernel takes its centres)
 hipError_t tlk_loudness(hipStream_t st, const TlLoudnessArgs &A);
 hipError_t tlk_loudness_programme(hipStream_t st, const uint32_t *hist, const double *tables, TlLoudnessProgramme *out, int nstreams);
+// ... tl_lra_kernel, the same wave counting range blocks too, launched in tl_loudness_kernel's place; tl_lra_range_kernel, one lane per stream
+hipError_t tlk_lra(hipStream_t st, const TlLraArgs &X);
+hipError_t tlk_lra_range(hipStream_t st, const uint32_t *hist_st, const double *tables, TlLraRecord *out, int nstreams);
 // toolame_truepeak.hip: tl_truepeak_kernel, one wave per stream over the call's frames in order (csrc/mp2_truepeak.h)
 hipError_t tlk_truepeak(hipStream_t st, const TlTruePeakArgs &A);
 // toolame_limiter.hip: tl_limiter_kernel, one wave per stream over the call's frames in order, in place (csrc/mp2_limiter.h)

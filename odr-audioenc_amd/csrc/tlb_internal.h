@@ -209,6 +209,9 @@ struct tlb_batch {
     uint32_t *d_ld_hist = nullptr;               // [TL_LD_HIST_ROWS][nstreams] gating blocks per 0.1 LU
     TlLoudnessProgramme *d_ld_prog = nullptr;    // [nstreams] scratch of tlb_loudness_programme_host
     double *d_ld_tables = nullptr;               // the committed table: taps [6][10], edges [751], centres [751]
+    // ... its loudness range (tlb_lra_*), allocated by tlb_lra_enable alone: a batch that never enables it has none of it and launches tl_loudness_kernel
+    uint32_t *d_ld_hist_st = nullptr;            // [TL_LD_HIST_ROWS][nstreams] range blocks (short-term values) per 0.1 LU
+    TlLraRecord *d_ld_lra = nullptr;             // [nstreams] scratch of tlb_lra_host
     // true-peak meter (tlb_truepeak.cpp; csrc/mp2_truepeak.h), allocated by tlb_truepeak_enable alone: a batch that never enables it has none of it
     TlTruePeakRecord *d_tp_rec = nullptr;        // [nstreams] the record as it is reported
     uint32_t *d_tp_hist = nullptr;               // [nstreams][2][TL_TP_CARRY / 2] the carried samples of either channel

@@ -12,6 +12,9 @@ static_assert(sizeof(tlb_loudness_programme_record) == sizeof(TlLoudnessProgramm
               offsetof(tlb_loudness_programme_record, gated) == offsetof(TlLoudnessProgramme, gated), "C-ABI programme record");
 static_assert(sizeof tl_loudness_taps == TL_LD_RATES * 10 * sizeof(double) && sizeof tl_loudness_edges == TL_LD_BINS * sizeof(double) &&
               sizeof tl_loudness_centres == TL_LD_BINS * sizeof(double) && TLB_LOUDNESS_BINS == TL_LD_BINS, "table shapes");
+static_assert(sizeof(tlb_lra_record) == sizeof(TlLraRecord) && sizeof(tlb_lra_record) == 40 && offsetof(tlb_lra_record, gate) == offsetof(TlLraRecord, gate) &&
+              offsetof(tlb_lra_record, blocks) == offsetof(TlLraRecord, blocks) && offsetof(tlb_lra_record, high_bin) == offsetof(TlLraRecord, high_bin) &&
+              offsetof(tlb_lra_record, high_bin) == 36, "C-ABI range record");
 
 // the loudness state of streams [s0, s0 + n) back to zero (the life-cycle calls; the device is idle).  The arrays are laid out by row with
 // the streams side by side, so a range of streams is a column block of each
@@ -22,6 +25,7 @@ int loudness_clear_streams(tlb_batch *b, int s0, int n)
     HIPCHK(hipMemset2D(b->d_ld_lane + 2 * (size_t)s0, 2 * ns * sizeof(double), 0, 2 * (size_t)n * sizeof(double), TL_LD_LANE_WORDS));
     HIPCHK(hipMemset2D(b->d_ld_ring + s0, ns * sizeof(double), 0, (size_t)n * sizeof(double), TL_LD_RING));
     HIPCHK(hipMemset2D(b->d_ld_hist + s0, ns * sizeof(uint32_t), 0, (size_t)n * sizeof(uint32_t), TL_LD_HIST_ROWS));
+    if (b->d_ld_hist_st) HIPCHK(hipMemset2D(b->d_ld_hist_st + s0, ns * sizeof(uint32_t), 0, (size_t)n * sizeof(uint32_t), TL_LD_HIST_ROWS));      // (tlb_lra_*: EBU Mode has one reset)
     HIPCHK(hipMemset(b->d_ld_rec + s0, 0, (size_t)n * sizeof(TlLoudnessRecord)));
     HIPCHK(hipDeviceSynchronize());              // the callers' streams do not wait for the null stream
     return TLB_OK;
@@ -77,7 +81,9 @@ int tlb_loudness_device(tlb_batch *b, const int16_t *d_pcm_planar, int nframes, 
     HIPCHK(hipSetDevice(b->device));
     const TlLoudnessArgs A = {d_pcm_planar, b->d_ld_lane, b->d_ld_ring, b->d_ld_rec, (TlLoudnessRecord *)d_records, b->d_ld_hist, b->d_ld_tables,
                               b->d_configs, b->d_stream_cfg, b->nstreams, nframes};
-    HIPCHK(tlk_loudness((hipStream_t)hip_stream, A));
+    // a batch with the loudness range on runs the counting twin in the kernel's place: one launch either way
+    if (b->d_ld_hist_st) { const TlLraArgs X = {A, b->d_ld_hist_st}; HIPCHK(tlk_lra((hipStream_t)hip_stream, X)); }
+    else HIPCHK(tlk_loudness((hipStream_t)hip_stream, A));
     return TLB_OK;
 }
 
@@ -106,5 +112,42 @@ int tlb_loudness_programme_host(tlb_batch *b, tlb_loudness_programme_record *out
 }
 
 int tlb_loudness_reset(tlb_batch *b, int stream) { return meter_reset(b, b ? b->d_ld_lane : nullptr, stream, loudness_clear_streams); }
+
+// Loudness range (tlb_lra_*): the second histogram, made here alone; the counting is tlb_loudness_device's other kernel.
+int tlb_lra_enable(tlb_batch *b)
+{
+    if (!b || !b->d_ld_lane) return TLB_ERR_ARG;         // on top of the loudness meter only
+    if (b->d_ld_hist_st) return TLB_OK;
+    HIPCHK(hipSetDevice(b->device));
+    const size_t ns = (size_t)b->nstreams;
+    TlbMem m;
+    uint32_t *hist_st = m.dev<uint32_t>(TL_LD_HIST_ROWS * ns);
+    TlLraRecord *lra = m.scratch<TlLraRecord>(ns);
+    if (!m.settle()) return TLB_ERR_HIP;
+    m.commit(b->mem);
+    b->d_ld_hist_st = hist_st; b->d_ld_lra = lra;
+    return TLB_OK;
+}
+
+int tlb_lra_device(tlb_batch *b, tlb_lra_record *d_out, void *hip_stream)
+{
+    if (!b || !d_out || ((uintptr_t)d_out & 7u) || !b->d_ld_hist_st) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(tlk_lra_range((hipStream_t)hip_stream, b->d_ld_hist_st, b->d_ld_tables, (TlLraRecord *)d_out, b->nstreams));
+    return TLB_OK;
+}
+
+int tlb_lra_host(tlb_batch *b, tlb_lra_record *out)
+{
+    if (!b || !out || !b->d_ld_hist_st) return TLB_ERR_ARG;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());              // launches queued on the caller's streams have written their counts
+    if (int rc = tlb_lra_device(b, (tlb_lra_record *)b->d_ld_lra, nullptr)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, b->d_ld_lra, (size_t)b->nstreams * sizeof(tlb_lra_record), hipMemcpyDeviceToHost));
+    return TLB_OK;
+}
+
+double tlb_lra_lu(const tlb_lra_record *rec) { return rec ? 0.1 * (double)(rec->high_bin - rec->low_bin) : 0.0; }
 
 }  // extern "C"

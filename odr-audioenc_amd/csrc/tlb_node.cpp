@@ -144,7 +144,7 @@ int tick_wait_job(Shard &s)
 
 }  // namespace
 
-enum { OPT_SHORT_READS, OPT_MONITOR, OPT_COMPARE, OPT_LOUDNESS, OPT_TRUEPEAK, OPT_LIMITER, OPTS };     // in the order a restarted shard gets them back
+enum { OPT_SHORT_READS, OPT_MONITOR, OPT_COMPARE, OPT_LOUDNESS, OPT_LRA, OPT_TRUEPEAK, OPT_LIMITER, OPTS };     // in the order a restarted shard gets them back
 
 struct tlb_node {
     int plane = TLB_NODE_TICK, nstreams = 0;
@@ -369,6 +369,7 @@ const struct { int (*enable)(tlb_tick *t, const NodeOption &v); int (*reset)(tlb
     /* monitor     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_monitor(t, v.what); }, nullptr, nullptr},
     /* compare     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_compare(t, &v.cparams); }, nullptr, nullptr},
     /* loudness    */ {[](tlb_tick *t, const NodeOption &) { return tlb_tick_enable_loudness(t); }, tlb_tick_loudness_reset, "loudness_reset"},
+    /* range       */ {[](tlb_tick *t, const NodeOption &) { return tlb_tick_enable_lra(t); }, nullptr, nullptr},      // (behind loudness: its reset is the range's)
     /* true peak   */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_truepeak(t, v.ceiling); }, tlb_tick_truepeak_reset, "truepeak_reset"},
     /* limiter     */ {[](tlb_tick *t, const NodeOption &v) { return tlb_tick_enable_limiter(t, &v.lparams); }, tlb_tick_limiter_reset, "limiter_reset"},
 };
@@ -697,6 +698,14 @@ int tlb_node_loudness_programme(tlb_node *nd, tlb_loudness_programme_record *out
     if (!nd || !out || !nd->opt[OPT_LOUDNESS].on || !nd->t_submit.empty()) return TLB_ERR_ARG;
     memset(out, 0, sizeof(tlb_loudness_programme_record) * (size_t)nd->nstreams);
     return nd->live("loudness_programme", [out](Shard &s) { return tlb_tick_loudness_programme(s.tick, out + s.first); });
+}
+// The loudness range: after tlb_node_enable_loudness.  The range of every stream, out [nstreams], between steps, as the programme loudness.
+int tlb_node_enable_lra(tlb_node *nd) { return node_enable(nd, OPT_LRA, NodeOption{}, [](const tlb_node &n) { return n.opt[OPT_LOUDNESS].on; }, always); }
+int tlb_node_lra(tlb_node *nd, tlb_lra_record *out)
+{
+    if (!nd || !out || !nd->opt[OPT_LRA].on || !nd->t_submit.empty()) return TLB_ERR_ARG;
+    memset(out, 0, sizeof(tlb_lra_record) * (size_t)nd->nstreams);
+    return nd->live("lra", [out](Shard &s) { return tlb_tick_lra(s.tick, out + s.first); });
 }
 int tlb_node_enable_truepeak(tlb_node *nd, uint32_t ceiling)
 {

@@ -137,6 +137,7 @@ struct tlb_tick {
     bool short_reads = false;
     int32_t *h_valid[2] = {}; uint32_t *h_underrun_ms[3] = {}, *h_underruns[3] = {};
     TickRecords rec[RECS];                       // record options, each off until its enable
+    bool lra = false;                            // loudness range (tlb_tick_enable_lra): the groups' batches count range blocks in the loudness meter's launch
     // confidence monitor, off (0) until tlb_tick_enable_monitor(): the listened stream's PCM travels with the output sets as the records do
     int monitor = 0;                             // TLB_MONITOR_CHECK / TLB_MONITOR_AUDIO
     int16_t *h_listen[3] = {};
@@ -434,6 +435,24 @@ int tlb_tick_loudness_programme(tlb_tick *t, tlb_loudness_programme_record *out)
     if (!t || !out || !t->rec[REC_LOUDNESS].on || t->ticks != t->waited) return TLB_ERR_ARG;
     if (t->broken) return TLB_ERR_HIP;
     for (auto &G : t->groups) if (int rc = tlb_loudness_programme_host(G.b, out + G.first)) return rc;
+    return TLB_OK;
+}
+// The loudness range on top of the meter (tlb_lra_*): the second histogram of every group's batch is made here; the meter's one launch per
+// submit is then the counting kernel, and the tick's queue is what it was.
+int tlb_tick_enable_lra(tlb_tick *t)
+{
+    if (!t || t->finished || t->ticks > 0 || !t->rec[REC_LOUDNESS].on) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    for (auto &G : t->groups) if (int rc = tlb_lra_enable(G.b)) return rc;
+    t->lra = true;
+    return TLB_OK;
+}
+// ... the range of every stream from the counts so far: legal with no tick in flight.
+int tlb_tick_lra(tlb_tick *t, tlb_lra_record *out)
+{
+    if (!t || !out || !t->lra || t->ticks != t->waited) return TLB_ERR_ARG;
+    if (t->broken) return TLB_ERR_HIP;
+    for (auto &G : t->groups) if (int rc = tlb_lra_host(G.b, out + G.first)) return rc;
     return TLB_OK;
 }
 int tlb_tick_enable_truepeak(tlb_tick *t, uint32_t ceiling) { return tick_meter_enable(t, REC_TRUEPEAK, ceiling); }

@@ -305,6 +305,16 @@ def _bind(L):
         L.tlb_node_loudness.argtypes = [C.c_void_p, C.c_int]
         L.tlb_node_loudness_programme.argtypes = [C.c_void_p, C.c_void_p]
         L.tlb_node_loudness_reset.argtypes = [C.c_void_p, C.c_int]
+    if hasattr(L, "tlb_lra_device"):              # loudness range on top of the loudness meter
+        L.tlb_lra_enable.argtypes = [C.c_void_p]
+        L.tlb_lra_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.tlb_lra_host.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_lra_lu.restype = C.c_double
+        L.tlb_lra_lu.argtypes = [C.c_void_p]
+        L.tlb_tick_enable_lra.argtypes = [C.c_void_p]
+        L.tlb_tick_lra.argtypes = [C.c_void_p, C.c_void_p]
+        L.tlb_node_enable_lra.argtypes = [C.c_void_p]
+        L.tlb_node_lra.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "tlb_truepeak_device"):         # true-peak meter
         L.tlb_truepeak_enable.argtypes = [C.c_void_p, C.c_uint32]
         L.tlb_truepeak_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -501,6 +511,17 @@ def loudness_scale():
     if rc:
         raise ToolameError(rc, "tlb_loudness_scale")
     return edges, centres
+
+
+# tlb_lra_record: the 10th and the 95th percentile and the relative gate as energies, the counted and the gated range blocks, the two bins
+LRA_DTYPE = np.dtype([("low", np.float64), ("high", np.float64), ("gate", np.float64), ("blocks", np.uint32), ("gated", np.uint32),
+                      ("low_bin", np.int32), ("high_bin", np.int32)])
+
+
+def lra_lu(rec):
+    """loudness range of one LRA_DTYPE record in LU: 0.1 * (high_bin - low_bin) (tlb_lra_lu)"""
+    a = np.array(rec, dtype=LRA_DTYPE).reshape(1)
+    return float(load_library().tlb_lra_lu(a.ctypes.data))
 
 
 # tlb_truepeak_record: peaks in units of 2^-30 of full scale, dBTP = truepeak_dbtp(v); sample_max 0 .. 32768
@@ -870,6 +891,21 @@ class Tick:
         rc = self.L.tlb_tick_loudness_programme(self.h, out.ctypes.data)
         if rc:
             raise ToolameError(rc, "tlb_tick_loudness_programme")
+        return out
+
+    # -- loudness range (tlb_lra_*): after enable_loudness, before the first submit --
+    def enable_lra(self):
+        rc = self.L.tlb_tick_enable_lra(self.h)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_enable_lra")
+        return self
+
+    def lra(self):
+        """LRA_DTYPE [nstreams] from the range blocks so far; with no tick in flight"""
+        out = np.zeros(self.nstreams, dtype=LRA_DTYPE)
+        rc = self.L.tlb_tick_lra(self.h, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_tick_lra")
         return out
 
     def loudness_reset(self, s=-1):
@@ -1546,6 +1582,22 @@ class Batch:
         if rc:
             raise ToolameError(rc, "tlb_loudness_reset")
 
+    # -- loudness range (tlb_lra_*): EBU Tech 3342's LRA from the meter's short-term values --
+    def enable_lra(self):
+        """after enable_loudness: allocates the range-block counts on the device (3008 bytes per stream); from here on loudness() counts
+        range blocks too; a second call does nothing"""
+        rc = self.L.tlb_lra_enable(self.h)
+        if rc:
+            raise ToolameError(rc, "tlb_lra_enable")
+
+    def lra(self):
+        """LRA_DTYPE [nstreams]: loudness range of everything measured since the streams' resets (LU: lra_lu)"""
+        out = np.zeros(self.nstreams, dtype=LRA_DTYPE)
+        rc = self.L.tlb_lra_host(self.h, out.ctypes.data)
+        if rc:
+            raise ToolameError(rc, "tlb_lra_host")
+        return out
+
     # -- true-peak meter (tlb_truepeak_*): the 4x oversampled maximum of the PCM the encoder is given --
     def enable_truepeak(self, ceiling=0):
         """allocates the meter's state on the device (80 bytes per stream); ceiling in units of 2^-30 of full scale, 0: -1 dBTP; a second
@@ -2060,6 +2112,17 @@ class Node:
 
     def loudness_reset(self, s=-1):
         self._rc(self.L.tlb_node_loudness_reset(self.h, int(s)), "tlb_node_loudness_reset")
+
+    # loudness range (Tick.enable_lra): after enable_loudness
+    def enable_lra(self):
+        self._rc(self.L.tlb_node_enable_lra(self.h), "tlb_node_enable_lra")
+        return self
+
+    def lra(self):
+        """LRA_DTYPE [nstreams], between steps; all zero for the streams of a broken or late shard"""
+        out = np.zeros(self.nstreams, dtype=LRA_DTYPE)
+        self._rc(self.L.tlb_node_lra(self.h, out.ctypes.data), "tlb_node_lra")
+        return out
 
     # true-peak meter (Tick.enable_truepeak, per stream with node-wide indices)
     def enable_truepeak(self, ceiling=0):

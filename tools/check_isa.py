@@ -61,6 +61,9 @@ LIMITS = [
     # loudness meter (csrc/toolame_loudness.hip): a lane per (stream, channel) with the filter state and a chunk of PCM ahead in registers; 64 rows of 144 bytes in LDS
     (re.compile(r"tl_loudness_kernel"), dict(vgpr=168, lds=9216, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     (re.compile(r"tl_loudness_programme_kernel"), dict(vgpr=168, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    # ... its loudness range: the meter's kernel counting range blocks too, same geometry; one lane per stream over the 751 counts
+    (re.compile(r"tl_lra_kernel"), dict(vgpr=168, lds=9216, vgpr_spill=0, sgpr_spill=0, scratch=0)),
+    (re.compile(r"tl_lra_range_kernel"), dict(vgpr=168, lds=0, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # true-peak meter (csrc/toolame_truepeak.hip): a wave per stream, a window of 15 + 14 dwords and three pieces ahead in registers; two rows of 2336 bytes in LDS
     (re.compile(r"tl_truepeak_kernel"), dict(vgpr=128, lds=4672, vgpr_spill=0, sgpr_spill=0, scratch=0)),
     # true-peak limiter (csrc/toolame_limiter.hip): the meter's window for the detector, six pieces ahead, 18 gains and 20 delayed dwords in registers (three waves a SIMD);

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """What a record option adds to a tick, and what this commit costs an object with and without it, on the GPU.
 
-    python tools/tick_record_cost.py --option monitor|compare|loudness|truepeak|limiter|all|conceal [--streams 16384] [--psy 3] [--ticks 200] [--rounds 5]
+    python tools/tick_record_cost.py --option monitor|compare|loudness|lra|truepeak|limiter|all|conceal [--streams 16384] [--psy 3] [--ticks 200] [--rounds 5]
                                      [--hot] [--parent-lib PATH] [--out profiles/tick_records.txt]
 
 The record options of a tick object (csrc/tlb_tick.cpp, tick_records): `monitor` (tlb_tick_enable_monitor, TLB_MONITOR_AUDIO), `compare`
-(tlb_tick_enable_compare with the default params; its `off` legs have the AUDIO monitor it needs), `loudness`, `truepeak`, and `all` four; and `limiter`
+(tlb_tick_enable_compare with the default params; its `off` legs have the AUDIO monitor it needs), `loudness`, `truepeak`, and `all` four; `lra`
+(tlb_tick_enable_lra: its `off` legs have the loudness meter it counts in, so that `on - off` is the counting of range blocks alone); and `limiter`
 (tlb_tick_enable_limiter, the defaults: it runs AHEAD of the encoder; --hot clips the input 30 dB up, so that its active path runs on every frame -- the encoder then
 encodes another signal in every leg, so hot legs compare with hot legs only).
 One tick object per leg -- `parent` and `parent-on` (--parent-lib: a libtoolame_dab_hip.so built from the parent commit, loaded beside this
@@ -33,12 +34,12 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
 # option -> (what its `off` legs enable, what its `on` legs enable on top), by the names below
-OPTIONS = {"monitor": ((), ("monitor",)), "compare": (("monitor",), ("compare",)), "loudness": ((), ("loudness",)), "truepeak": ((), ("truepeak",)), "limiter": ((), ("limiter",)),
+OPTIONS = {"monitor": ((), ("monitor",)), "compare": (("monitor",), ("compare",)), "loudness": ((), ("loudness",)), "lra": (("loudness",), ("lra",)), "truepeak": ((), ("truepeak",)), "limiter": ((), ("limiter",)),
            "all": ((), ("monitor", "compare", "loudness", "truepeak"))}
-ENABLE = {"monitor": lambda t: t.enable_monitor("audio"), "compare": lambda t: t.enable_compare(), "loudness": lambda t: t.enable_loudness(),
+ENABLE = {"monitor": lambda t: t.enable_monitor("audio"), "compare": lambda t: t.enable_compare(), "loudness": lambda t: t.enable_loudness(), "lra": lambda t: t.enable_lra(),
           "truepeak": lambda t: t.enable_truepeak(), "limiter": lambda t: t.enable_limiter()}
 # ... and a count from the option's records, to show that it ran
-MEASURED = {"monitor": lambda t: t.monitor["frames"], "compare": lambda t: t.compare["frames_compared"], "loudness": lambda t: t.loudness["frames"],
+MEASURED = {"monitor": lambda t: t.monitor["frames"], "compare": lambda t: t.compare["frames_compared"], "loudness": lambda t: t.loudness["frames"], "lra": lambda t: t.lra()["blocks"],
             "truepeak": lambda t: t.truepeak["frames"], "limiter": lambda t: t.limiter["frames"]}
 
 
@@ -210,7 +211,7 @@ def main():
         spread = max(out[ref]["median_ms"]) - min(out[ref]["median_ms"])
         d = med(leg) - med(ref)
         lines.append("%s %s - %s: %+.4f ms; the %s leg's own spread over its rounds: %.4f ms -> %s" % (tag, leg, ref, d, ref, spread, "inside it" if abs(d) <= spread else "OUTSIDE it"))
-    lines.append("(c) on - off: %+.4f ms per tick for %d streams (in all: %s)" % (med("on") - med("off"), ns, ", ".join("%s %d frames" % kv for kv in measured.items())))
+    lines.append("(c) on - off: %+.4f ms per tick for %d streams (in all: %s)" % (med("on") - med("off"), ns, ", ".join("%s %d %s" % (k, v, "range blocks" if k == "lra" else "frames") for k, v in measured.items())))
     text = "\n".join(lines) + "\n"
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     Path(args.out).write_text(text)
