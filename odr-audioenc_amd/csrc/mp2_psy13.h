@@ -553,7 +553,10 @@ TL_FN void tl_psy1_centres2(TlPsyLds &w, int nbands, PARG(double, bsum), PARG(do
 }
 
 // individual + global masking thresholds, minimum per subband, SMR (psycho_1.c:480-581) from the masker lists
-TL_FN void tl_psy1_thresholds(TlPsyLds &w, const double *TL_RESTRICT db, const TlConfig *TL_RESTRICT C, int ch, int ntone, int nnoise, PARGA(double, rec, 4), long long *sp)
+// ordered: the caller states that both masker lists are ascending in bark and short enough for the bisected spans (ntone < 128, nnoise < 64),
+// so the order test is not run (the emulation runs it nevertheless and counts a contradiction: TL_DBG_ORDER)
+TL_FN void tl_psy1_thresholds(TlPsyLds &w, const double *TL_RESTRICT db, const TlConfig *TL_RESTRICT C, int ch, int ntone, int nnoise, PARGA(double, rec, 4), long long *sp,
+                              bool ordered = false)
 {
     TL_STAMP(sp, 5);
     TL_PRIO2(TL_PS_THR);
@@ -577,9 +580,14 @@ TL_FN void tl_psy1_thresholds(TlPsyLds &w, const double *TL_RESTRICT db, const T
     TL_LANES_END
     // Each lane folds the maskers into two ADJACENT table lines at once (two independent dB-sum chains).  A masker only
     // reaches lines with -3 <= dz < 8 bark, so a lane first finds the first and last masker (tones, then noise, in list
-    // order) that reaches either of its lines and walks only that span; the per-line range test stays in the walk, so
-    // nothing depends on the lists being sorted.
-    const bool srt = ntone < 128 && nnoise < 64 && tl_maskers_sorted(TL_MK_BARK(w), ntone, nnoise);
+    // order) that reaches either of its lines and walks only that span; the per-line range test stays in the walk.  The
+    // spans come from a look at every masker (any order) or, when both lists are ascending in bark, by bisection -- which
+    // DOES depend on the order: `srt` is the order test's answer, or the caller's word (`ordered`) in its place.
+#if defined(TL_EMULATE)
+    if (ordered) { TL_DBG_ORDER(0, 1); TL_DBG_ORDER(1, ntone < 128 && nnoise < 64 && tl_maskers_sorted(TL_MK_BARK(w), ntone, nnoise) ? 0 : 1); }
+    else TL_DBG_ORDER(2, 1);
+#endif
+    const bool srt = ordered || (ntone < 128 && nnoise < 64 && tl_maskers_sorted(TL_MK_BARK(w), ntone, nnoise));
     for (int base = 1; base < (TL_EXP_LEVEL >= 1 ? 0 : sub); base += 128) {       // 126..132 lines: one full pass + a 4-line tail at most
         TL_LANES_BEGIN
         const int k0 = base + 2 * lane, k1 = k0 + 1;
@@ -629,7 +637,12 @@ TL_FN void tl_psy1_thresholds(TlPsyLds &w, const double *TL_RESTRICT db, const T
         int n = L(mmn), j0 = L(mmj);
         if (n == 0) m = C->p1_hear[sub - 1];
         else {
-            m = tl_min_rows(TL_LTG(w), j0, n, 0.0, true);
+            // `min = LTg[j0]; if (min > LTg[j]) min = LTg[j]` in one v_min_f64 per row.  Precondition (TLM_MM_ROWS): every row written above is
+            // tl_add_db(hear, x): one of its finite operands plus a table entry that is positive or -0.0 -- never a NaN, and a -0.0 only if that
+            // operand was one (a sum that cancels rounds to +0.0).  That no operand is a -0.0 -- no threshold in quiet of the tables, no running
+            // sum, no masking term -- is NOT proved here: it rests on the emulation's count of unsafe pairs at this site, which
+            // tests/test_thr_min_emu.py wants at zero.  What a breach could change is the sign of a minimum that is a zero.
+            m = tlm_min_rows_lt(TL_LTG(w), j0, n, TLM_MM_ROWS);
         }
         L(rec)[2 + ch] = m;                                         // the encoder finishes the line (tl_encode_frame, TL_PSY_EXT): SMR = max(spike, scale level) - m, psycho_1.c:575-580
     } else if (lane < 32) L(rec)[2 + ch] = 0.0;                     // subbands the model leaves alone
@@ -765,7 +778,12 @@ TL_FN void tl_psy1_back(TlPsyLds &w, const double *TL_RESTRICT db, const TlConfi
 // offset per half.  Needs at most TL_P1B_LIST tones in either list.  Channel 0's tone records are read from the second set of arrays
 // (TL_P1B_*; its list entry from the parked register tl0), channel 1's from the wave's own.  Channel 1's masker list is written where
 // tl_psy1_thresholds reads it, channel 0's to TL_P1B_MKX / TL_P1B_MKBARK.
-struct TlPsy1Mk2 { int ntone0, nnoise0, ntone1, nnoise1; };
+// ordered: both lists of both channels are ascending in bark BY CONSTRUCTION, so that the thresholds need not test it -- the tones are kept in
+// chain order, which is the order of their lines; a merge of two close tones keeps one of the two in its place; the noise components are kept
+// in band order, their centres rising with the band; and a line's bark value (p1_lbark) does not fall as the line rises UP TO THE LAST LINE OF
+// THE THRESHOLD TABLE.  A line above it maps to table entry 0 (psycho_1.c's map[] is zero there), bark 0: a kept tone or noise centre up there
+// (rare: above 20 kHz at 48 kHz) ends its list out of order, and the pass reports the frame as not ordered.
+struct TlPsy1Mk2 { int ntone0, nnoise0, ntone1, nnoise1; bool ordered; };
 TL_FN TlPsy1Mk2 tl_psy1_decimate2(TlPsyLds &w, const TlConfig *TL_RESTRICT C, int nbands, int nl0, int nl1, PARG(int, tl0),
                                   PARG(double, bsum), PARG(int, ncen), PARG(bool, ontone))
 {
@@ -791,6 +809,7 @@ TL_FN TlPsy1Mk2 tl_psy1_decimate2(TlPsyLds &w, const TlConfig *TL_RESTRICT C, in
         }
     }
     TlPsy1Mk2 r;
+    const int lastline = C->p1_line[C->p1_sub - 1];
     // the noise components' table values are requested now and used after the tones (see tl_psy1_back)
     PV(double, nbk0); PV(double, nhear0);
     TL_LANES_BEGIN
@@ -799,7 +818,7 @@ TL_FN TlPsy1Mk2 tl_psy1_decimate2(TlPsyLds &w, const TlConfig *TL_RESTRICT C, in
     TL_LANES_END
     // tones: keep if not erased and not below the threshold in quiet (order preserved); one pass, a list per half
     {
-        PV(bool, keep); PV(double, kx); PV(double, kb); PV(int, tline); PV(int, tcc); PV(double, tbk); PV(double, thr); PV(bool, inl);
+        PV(bool, keep); PV(double, kx); PV(double, kb); PV(int, tline); PV(int, tcc); PV(double, tbk); PV(double, thr); PV(bool, inl); PV(bool, high);
         TL_LANES_BEGIN
         const bool second = lane >= 32;
         const int k = lane & 31;
@@ -827,9 +846,10 @@ TL_FN TlPsy1Mk2 tl_psy1_decimate2(TlPsyLds &w, const TlConfig *TL_RESTRICT C, in
             bk = L(tbk);
             kp = !((L(tcc) >> 13) & 1) && !(L(kx) < L(thr));
         }
-        L(keep) = kp; L(kb) = bk;
+        L(keep) = kp; L(kb) = bk; L(high) = kp && L(tline) > lastline;
         TL_LANES_END
         const uint64_t m = TL_BALLOT(keep);
+        r.ordered = TL_BALLOT(high) == 0ull;
         TL_LANES_BEGIN
         if ((m >> lane) & 1ull) {
             const bool second = lane >= 32;
@@ -877,11 +897,13 @@ TL_FN TlPsy1Mk2 tl_psy1_decimate2(TlPsyLds &w, const TlConfig *TL_RESTRICT C, in
     }
     // noise: band order, keep if not below the threshold in quiet (psycho_1.c:429-442)
     {
-        PV(bool, keepn);
+        PV(bool, keepn); PV(bool, highn);
         TL_LANES_BEGIN
         L(keepn) = (lane & 31) < nbands && !(L(nlev) < L(nhear0));
+        L(highn) = L(keepn) && L(ncen) > lastline;
         TL_LANES_END
         const uint64_t mn = TL_BALLOT(keepn);
+        r.ordered = r.ordered && TL_BALLOT(highn) == 0ull;
         TL_LANES_BEGIN
         if ((mn >> lane) & 1ull) {
             const bool second = lane >= 32;
@@ -988,7 +1010,7 @@ TL_FN void tl_psy1_finish(TlPsyLds &w, const double *TL_RESTRICT db, const TlCon
     tl_psy1_limits(C, nbands, blo, bhi);
     TL_PRIO(1); tl_psy1_chain(w, db, nbands, bsum, wt); TL_PRIO(0);
     tl_psy1_centres(w, nbands, bsum, wt, blo, bhi);
-    if (st.dead_head) tl_psy1_deadhead(w, db, C, ch, st, rec, sp); else tl_psy1_back(w, db, C, ch, st, rec, sp);
+    if (st.dead_head) { TL_DBG_ORDER(3, 1); tl_psy1_deadhead(w, db, C, ch, st, rec, sp); } else tl_psy1_back(w, db, C, ch, st, rec, sp);
 }
 TL_FN void tl_psy1(TlPsyLds &w, const TlTables *TL_RESTRICT T, const double *TL_RESTRICT db,
                    const TlConfig *TL_RESTRICT C, const TlPcmView &pv, int ch, PARGA(double, rec, 4), long long *sp)
@@ -1076,7 +1098,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
             //      line types rebuilt from conf_c, so that both channels' small records are resident at once ----
             TL_DBG_BACK(0);
             PV(int, ncen); PV(bool, ontone);
-            TlPsy1Mk2 mk = {0, 0, 0, 0};
+            TlPsy1Mk2 mk = {0, 0, 0, 0, false};
             if (TL_EXP_LEVEL < 3) {
                 TL_LANES_BEGIN
                 ((double *)TL_P1B_PTYPE(w))[lane] = 0.0;                // 520 bytes of zeros
@@ -1092,7 +1114,10 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
                 tl_psy1_centres2(w, nbands, bsum, wt, blo, bhi, ncen, ontone);
                 if (TL_EXP_LEVEL < 2) mk = tl_psy1_decimate2(w, C, nbands, s0.nlist, s1.nlist, ptl, bsum, ncen, ontone);
             }
-            tl_psy1_thresholds(w, db, C, 1, mk.ntone1, mk.nnoise1, rec, sp1);
+            // No dead head, so no replayed tones: the lists are ascending in bark by construction unless a masker lies above the threshold
+            // table's last line (mk.ordered, see TlPsy1Mk2), and with at most TL_P1B_LIST tones and 27 noise components they are within the
+            // bisected spans' limits.  The thresholds then do not test the order.
+            tl_psy1_thresholds(w, db, C, 1, mk.ntone1, mk.nnoise1, rec, sp1, mk.ordered);
             // channel 0's masker list moves to where the thresholds read it (at most TL_P1B_LIST + 27 <= 64 entries)
             TL_LANES_BEGIN
             if (lane < mk.ntone0 + mk.nnoise0) {
@@ -1100,7 +1125,7 @@ TL_FN void tl_psy1_stereo(TlPsyLds &w, const TlTables *TL_RESTRICT T, const doub
                 TL_MK_X(w)[lane] = x; TL_MK_BARK(w)[lane] = bk;
             }
             TL_LANES_END
-            tl_psy1_thresholds(w, db, C, 0, mk.ntone0, mk.nnoise0, rec, sp0);
+            tl_psy1_thresholds(w, db, C, 0, mk.ntone0, mk.nnoise0, rec, sp0, mk.ordered);
             return;
         }
         TL_DBG_BACK(1);

@@ -320,6 +320,17 @@ extern "C" __attribute__((weak, visibility("default"))) void emu_back_stats(long
 #define TL_DBG_TONES(n, dh) ((void)0)
 #define TL_DBG_CAND(n) ((void)0)
 #endif
+// Every emulation build: the threshold stage's order test (tl_psy1_thresholds).  A caller that states its masker lists ascending by
+// construction skips tl_maskers_sorted on the device; the emulation runs it all the same and counts -- 0: channels whose order was stated,
+// 1: of these, the ones the test contradicts (must stay 0), 2: channels that ran the test because nothing was stated, 3: dead-head channels
+// (tl_psy1_finish; they are among the ones of 2).
+#if defined(TL_EMULATE)
+static long tl_dbg_order[4] = {0, 0, 0, 0};
+#define TL_DBG_ORDER(k, n) (tl_dbg_order[k] += (n))
+extern "C" __attribute__((weak, visibility("default"))) void emu_order_stats(long *out) { for (int i = 0; i < 4; i++) out[i] = tl_dbg_order[i]; }
+#else
+#define TL_DBG_ORDER(k, n) ((void)0)
+#endif
 // Diagnostic builds only (tools/instr_budget.sh): TL_EXP_LEVEL = n removes the last n stages of psy model 1 (results are then
 // wrong on purpose); the VALU-instruction counters of successive levels attribute the instructions to the stages.
 #ifndef TL_EXP_LEVEL

@@ -130,9 +130,11 @@ __device__ inline __attribute__((always_inline)) double tlm_max_nn_(double a, do
 // instruction differ when an operand is a NaN or the operands are zeros of opposite sign.  The precondition of every caller is that neither
 // occurs; each site says why, and reports its operand pair to TL_DBG_MINMAX, which counts in the emulation the pairs that break it
 // (emu_minmax_stats; tests/test_minmax_forms_emu.py wants zero).  The hook is an empty macro everywhere else.
-enum { TLM_MM_SCF, TLM_MM_JSCF, TLM_MM_SMR, TLM_MM_POWER, TLM_MM_BARK, TLM_MM_CAND, TLM_MM_XMAX, TLM_MM_SITES };
+// (TLM_MM_ROWS, the subband minima of tlm_min_rows_lt, came later and is counted by the same hook but read through emu_minmax_rows_stats:
+// emu_minmax_stats keeps the seven sites and the totals its callers size their buffers for.)
+enum { TLM_MM_SCF, TLM_MM_JSCF, TLM_MM_SMR, TLM_MM_POWER, TLM_MM_BARK, TLM_MM_CAND, TLM_MM_XMAX, TLM_MM_SITES, TLM_MM_ROWS = TLM_MM_SITES, TLM_MM_ALL };
 #if defined(TL_EMULATE)
-static long tlm_mm_pairs[TLM_MM_SITES], tlm_mm_unsafe[TLM_MM_SITES];
+static long tlm_mm_pairs[TLM_MM_ALL], tlm_mm_unsafe[TLM_MM_ALL];
 static inline void tlm_mm_report(int site, double a, double b)
 {
     const uint64_t ua = tlm_d2u(a), ub = tlm_d2u(b);
@@ -147,6 +149,8 @@ extern "C" __attribute__((weak, visibility("default"))) void emu_minmax_stats(lo
     out[0] = out[1] = 0;
     for (int s = 0; s < TLM_MM_SITES; s++) { out[2 + 2 * s] = tlm_mm_pairs[s]; out[3 + 2 * s] = tlm_mm_unsafe[s]; out[1] += tlm_mm_pairs[s]; out[0] += tlm_mm_unsafe[s]; }
 }
+// out[0]: unsafe pairs of TLM_MM_ROWS, out[1]: its pairs
+extern "C" __attribute__((weak, visibility("default"))) void emu_minmax_rows_stats(long *out) { out[0] = tlm_mm_unsafe[TLM_MM_ROWS]; out[1] = tlm_mm_pairs[TLM_MM_ROWS]; }
 #else
 #define TL_DBG_MINMAX(site, a, b) ((void)0)
 #endif
@@ -185,6 +189,24 @@ TLM_HD double tlm_maxabs2_gt(double x, double y, int site) { const double t = __
 TLM_HD double tlm_max_gt_k(double t, double k, int site) { TL_DBG_MINMAX(site, t, k); return t > k ? t : k; }
 TLM_HD double tlm_fmax_k(double e, double k, int site) { TL_DBG_MINMAX(site, e, k); return __builtin_fmax(e, k); }
 #endif
+// tlm_min_rows_lt(rows, j0, n): `m = rows[j0]; for the rows after it: if (m > rows[j]) m = rows[j]` over the n >= 1 rows [j0, j0 + n), one
+// tlm_min_lt per row, four rows per trip.  The CALLER'S precondition is tlm_min_lt's for every pair of rows: no NaN, no zeros of opposite
+// sign.  Then the smallest row has one bit pattern whatever the order, so the four rows of a trip are paired first (two independent
+// instructions, then one) and the trip's minimum joins the running one.  A trip that would pass the last row is moved back to end on it --
+// ONE clamped offset per trip; it meets rows again that are already in the minimum -- and a run of fewer than four rows repeats its last
+// row through three offsets made once per call.  Nothing outside [j0, j0 + n) is read.
+TLM_HD double tlm_min_rows_lt(const double *rows, int j0, int n, int site)
+{
+    const int last = n - 1;
+    const int o1 = last < 1 ? last : 1, o2 = last < 2 ? last : 2, o3 = last < 3 ? last : 3;
+    const double *p = rows + j0;
+    double m = tlm_min_lt(tlm_min_lt(p[o1], p[0], site), tlm_min_lt(p[o3], p[o2], site), site);
+    for (int d = 4; d < n; d += 4) {                                  // (n > 4 in here)
+        const double *q = p + (d < n - 4 ? d : n - 4);
+        m = tlm_min_lt(tlm_min_lt(tlm_min_lt(q[1], q[0], site), tlm_min_lt(q[3], q[2], site), site), m, site);
+    }
+    return m;
+}
 
 // ------------------------------------------------------------------------------------------------------------
 // log (e_log.c).  TAB = {invc, logc}[128] as bit patterns (global table or an LDS copy of it).
